@@ -33,6 +33,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 PEAK_FP32_MFMA_TFLOPS = 157.3  # /opt/skills/guides/MI355X_MICROARCH.md "Peak FP32 (matrix)" (spec)
+DUMP_BUDGET_BYTES = 64 << 20   # --dump-outputs: all files together
+DUMP_SAMPLE_SEED = 1234        # --dump-outputs: positions kept when the outputs exceed the budget
 
 
 def parse():
@@ -77,7 +79,34 @@ def parse():
                          "in the deferred loops); 0 = off everywhere")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget-s", type=float, default=15.0)
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed loops, write what the last timed step returned as DIR/<name>.npy (float32; at most "
+                         f"{DUMP_BUDGET_BYTES >> 20} MB in all, a fixed seeded sample beyond that); N > 1: DIR/<name>.rank<r>.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def dump_outputs(outputs, out_dir, suffix=""):
+    """Write the arrays the timed path returned as out_dir/<name><suffix>.npy (float32).  When they hold more than
+    DUMP_BUDGET_BYTES in all, every array is cut to the same fraction of its elements: a flat sample at indices drawn from a
+    fixed seed (sorted), so the same arguments give the same positions on every run.  Returns {name: what was written}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in outputs.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    written = {}
+    for name, a in arrays.items():
+        if total > DUMP_BUDGET_BYTES:
+            keep = max(1, a.size * DUMP_BUDGET_BYTES // total)
+            idx = np.sort(np.random.Generator(np.random.PCG64(DUMP_SAMPLE_SEED)).choice(a.size, size=keep, replace=False))
+            np.save(os.path.join(out_dir, name + suffix + ".npy"), np.ascontiguousarray(a.reshape(-1)[idx]))
+            written[name] = {"shape": list(a.shape), "sampled_elements": int(keep), "sample_seed": DUMP_SAMPLE_SEED}
+        else:
+            np.save(os.path.join(out_dir, name + suffix + ".npy"), np.ascontiguousarray(a))
+            written[name] = {"shape": list(a.shape)}
+    return written
 
 
 def cpu_baseline(sd, inputs, budget_s, norm, fullsubnet=False):
@@ -503,6 +532,10 @@ def main():
             result["cirm_rel_err"] = max(e / m for e, m in errs.values())
             result["cirm_checked_utterances"] = sorted(errs)
             result["cirm_worst_utterance"] = max(errs, key=lambda i: errs[i][0] / errs[i][1])
+    if args.dump_outputs:
+        # the last timed step's return value (model.enhance_wave: the enhanced waveform; the forward: the cIRM mask)
+        result["dumped_outputs"] = dump_outputs({"enhanced_wave" if args.wave else "cirm_mask": out}, args.dump_outputs,
+                                                f".rank{rank}" if world > 1 else "")
     if rank == 0:
         from fullsubnet_plus_amd import box as box_mod2
         result["box"]["rocm_smi_after"] = box_mod2.smi_snapshot()

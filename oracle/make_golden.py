@@ -2,7 +2,8 @@
 
 Run in the build container (needs /root/reference):
 
-    python -m oracle.make_golden            # writes tests/golden/*.npz
+    python -m oracle.make_golden                   # writes tests/golden/*.npz
+    python -m oracle.make_golden reference_facts   # writes tests/golden/reference/ (main_reference_facts)
 
 Each fixture holds, for one (weights seed/profile, model args, input spec):
   out     - the reference's fp32 forward output (FullSubNet_Plus.forward,
@@ -290,8 +291,60 @@ def main_fsn(only):
               flush=True)
 
 
+FACTS_DIR = os.path.join(GOLDEN_DIR, "reference")        # a subdirectory: tests/_util.golden_names() lists the forward fixtures
+FACTS_PATH = os.path.join(FACTS_DIR, "facts.json")
+BASE_MODEL_PATH = os.path.join(FACTS_DIR, "base_model.npz")
+NORM_SHAPES = [(3, 1, 257, 20), (2, 3, 34, 61), (1, 2, 5, 300)]
+UNFOLD_CASES = [((2, 1, 257, 12), 15), ((2, 3, 40, 7), 1), ((1, 2, 9, 5), 0), ((2, 1, 33, 4), 8)]
+
+
+def config_digest(cfg):
+    """sha256 of a parsed TOML document (key order and formatting do not count)."""
+    import hashlib
+    return hashlib.sha256(json.dumps(cfg, sort_keys=True).encode()).hexdigest()
+
+
+def base_model_inputs():
+    """The inputs the BaseModel helper checks run on: [(shape, x)] for the norms, then [(nb, x)] for unfold (one seeded stream)."""
+    rng = np.random.Generator(np.random.PCG64(31))
+    norms = [(s, torch.from_numpy(np.abs(rng.standard_normal(s)).astype(np.float32) + 0.1)) for s in NORM_SHAPES]
+    unfolds = [(nb, torch.from_numpy(rng.standard_normal(s).astype(np.float32))) for s, nb in UNFOLD_CASES]
+    return norms, unfolds
+
+
+def main_reference_facts():
+    """tests/golden/reference/facts.json + base_model.npz: what the tests pin about the reference besides forward
+    outputs - the digest of its config/inference.toml and that file's [model].path, its [model.args], the parameter trees
+    (name, shape) of both model classes, and its BaseModel norm / unfold outputs on base_model_inputs()."""
+    import hashlib
+    import tomli
+    from . import fsnp_torch
+    FullSubNet_Plus = ref_loader.load_reference()
+    Model = ref_loader.load_reference_fullsubnet()
+    from audio_zen.model.base_model import BaseModel  # type: ignore
+    with open(os.path.join(ref_loader.REFERENCE_ROOT, "config", "inference.toml"), "rb") as f:
+        toml = tomli.load(f)
+    facts = {"inference_toml_digest": config_digest(toml), "inference_toml_model_path": toml["model"]["path"],
+             "model_args": ref_loader.reference_model_args(),
+             "state_dict_tree": [[k, list(v.shape)] for k, v in FullSubNet_Plus(**ref_loader.DEFAULT_MODEL_ARGS).state_dict().items()],
+             "fullsubnet_state_dict_tree": [[k, list(v.shape)] for k, v in
+                                            Model(**ref_loader.FULLSUBNET_MODEL_ARGS).state_dict().items()]}
+    norms, unfolds = base_model_inputs()
+    vectors = {f"{name}_{i}": getattr(BaseModel, name)(x).numpy() for i, (_, x) in enumerate(norms) for name in fsnp_torch.NORMS}
+    facts["unfold_sha256"] = [hashlib.sha256(BaseModel.unfold(x, nb).contiguous().numpy().tobytes()).hexdigest() for nb, x in unfolds]
+    os.makedirs(FACTS_DIR, exist_ok=True)
+    with open(FACTS_PATH, "w") as f:
+        json.dump(facts, f, indent=1)
+        f.write("\n")
+    np.savez_compressed(BASE_MODEL_PATH, **vectors)
+    print(f"{FACTS_PATH}, {BASE_MODEL_PATH} [{os.path.getsize(BASE_MODEL_PATH) / 1024:.0f} KB]")
+
+
 def main():
     only = set(sys.argv[1:])
+    if only == {"reference_facts"}:
+        main_reference_facts()
+        return
     if not only or any(n.startswith("fsn_") for n in only):
         main_fsn(only)
         if only and all(n.startswith("fsn_") for n in only):

@@ -77,6 +77,13 @@ class Golden:
                     output_size=a.get("output_size", 2))
 
 
+def reference_facts():
+    """tests/golden/reference/facts.json: what oracle/make_golden.py main_reference_facts recorded about the reference (its config
+    digest, [model.args], parameter trees and unfold digests), so the checks against it run where the reference is not mounted."""
+    with open(os.path.join(GOLDEN_DIR, "reference", "facts.json")) as f:
+        return json.load(f)
+
+
 def rel_err(a, b):
     a = np.asarray(a, dtype=np.float64)
     b = np.asarray(b, dtype=np.float64)

@@ -42,25 +42,31 @@ def test_bench_plain_gpus2_self_launches_two_ranks():
     assert r["gather_ms"] > 0
 
 
-def test_bench_eight_ranks_on_one_device():
-    """eight processes loading the library, creating handles, packing weights and running at once had never happened.
-    `bench.py --gpus 8 --same-device`: eight ranks share GPU 0 (gloo for the collectives: RCCL wants a GPU per rank; the exchange-free
-    kernel, because eight processes' co-resident launches could hold parts of one chip against each other) - what remains is exactly
-    the N = 8 plumbing: self-launch, rendezvous, per-rank inputs, barrier-bracketed timing, max over ranks, the mask gather, and the
-    roofline block of the slowest rank."""
-    res = _run([sys.executable, "bench.py", "--gpus", "8", "--same-device", "--dist-backend", "gloo", "--steps", "2",
+def test_bench_four_ranks_on_one_device():
+    """many processes loading the library, creating handles, packing weights and running at once had never happened.
+    `bench.py --gpus 4 --same-device` under torch.distributed.run: four ranks share GPU 0 (gloo for the collectives: RCCL wants a GPU
+    per rank; the exchange-free kernel, because more than two processes' co-resident launches could hold parts of one chip against
+    each other) - what remains is the N > 2 plumbing: rendezvous, per-rank inputs, barrier-bracketed timing, max over ranks, the mask
+    gather, and the roofline block of the slowest rank.  Four ranks, launched by torch.distributed.run (whose agent does not open the
+    GPU), keep this test and the pytest process that runs it within the limit of six processes on one GPU that a shared machine
+    allows; bench.py's own launcher is covered at N = 2 above."""
+    with socket.socket() as sk:
+        sk.bind(("127.0.0.1", 0))
+        port = sk.getsockname()[1]
+    res = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=4", "--master-addr", "127.0.0.1",
+                "--master-port", str(port), "bench.py", "--gpus", "4", "--same-device", "--dist-backend", "gloo", "--steps", "2",
                 "--warmup", "1", "--batch", "2", "--no-cpu-baseline", "--no-alt", "--strong", "--repeats", "1", "--probe-ms", "5"], timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     r = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
     # round 6: the same launch also times BASELINE.json configs[2] as worded - ONE global batch on rank 0, scatter + forward + gather - next
-    # to the weak-scaling headline, and every rank reports what its box held (here: eight probes of the one device)
+    # to the weak-scaling headline, and every rank reports what its box held (here: four probes of the one device)
     st = r["strong"]
-    assert st["global_batch"] == 16 and st["ms_per_step"] > 0 and st["value"] > 0 and st["via_host_memory"] is True
+    assert st["global_batch"] == 8 and st["ms_per_step"] > 0 and st["value"] > 0 and st["via_host_memory"] is True
     assert st["scatter_ms"] > 0 and st["gather_ms"] > 0 and st["forward_ms_slowest_rank"] > 0
-    assert st["bytes_scattered_per_step"] == 16 * r["config"]["frames_per_clip"] * 257 * 8
-    assert len(r["box"]["per_rank"]) == 8 and all(p["mfma_tflops_after"] > 0 for p in r["box"]["per_rank"])
-    assert r["n_gpus"] == 8 and r["dist"]["world_size_seen"] == 8 and r["config"]["global_batch"] == 16
-    assert r["dist"]["gathered_shape"][0] == 16 and 0 <= r["dist"]["roofline_of_rank"] < 8
+    assert st["bytes_scattered_per_step"] == 8 * r["config"]["frames_per_clip"] * 257 * 8
+    assert len(r["box"]["per_rank"]) == 4 and all(p["mfma_tflops_after"] > 0 for p in r["box"]["per_rank"])
+    assert r["n_gpus"] == 4 and r["dist"]["world_size_seen"] == 4 and r["config"]["global_batch"] == 8
+    assert r["dist"]["gathered_shape"][0] == 8 and 0 <= r["dist"]["roofline_of_rank"] < 4
     assert r["dist"]["per_rank_ms_per_step"]["max"] >= r["dist"]["per_rank_ms_per_step"]["min"] > 0
     assert r["roofline"]["avg_launch_ms"] > 0 and r["roofline"]["subband_plan"][0]["kernel"].startswith("lstm2_fc_kernel")
 

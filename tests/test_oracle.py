@@ -5,7 +5,7 @@ import pytest
 import torch
 
 from oracle import fsnp_numpy, fsnp_torch, ref_loader
-from tests._util import Golden, golden_names, rel_err
+from tests._util import Golden, golden_names, reference_facts, rel_err
 
 SMALL = [n for n in golden_names() if "2s" not in n and "10s" not in n and "_att_" not in n and "_eca_" not in n and "_cbam_" not in n and "gru" not in n and "tcn" not in n and "fbn" not in n]
 
@@ -59,23 +59,28 @@ def test_batch_two_raises_like_reference():
 
 
 def test_frozen_model_args_match_reference_toml():
-    if not ref_loader.reference_available():
-        pytest.skip("reference not present on this box")
-    assert ref_loader.reference_model_args() == ref_loader.DEFAULT_MODEL_ARGS
+    facts = reference_facts()
+    assert facts["model_args"] == ref_loader.DEFAULT_MODEL_ARGS
+    if ref_loader.reference_available():
+        assert ref_loader.reference_model_args() == facts["model_args"]
 
 
 def test_state_dict_matches_reference_parameter_tree():
+    from oracle.weights import make_state_dict
+    sd = make_state_dict(0)
+    tree = {k: tuple(shape) for k, shape in reference_facts()["state_dict_tree"]}
+    assert set(sd) == set(tree)
+    for k in sd:
+        assert tuple(sd[k].shape) == tree[k], k
+    assert sum(v.numel() for v in sd.values()) == 8_675_102
     if not ref_loader.reference_available():
-        pytest.skip("reference not present on this box")
+        return
     cls = ref_loader.load_reference()
     model = cls(**ref_loader.DEFAULT_MODEL_ARGS)
     ref_sd = model.state_dict()
-    from oracle.weights import make_state_dict
-    sd = make_state_dict(0)
     assert set(sd) == set(ref_sd)
     for k in sd:
         assert tuple(sd[k].shape) == tuple(ref_sd[k].shape), k
-    assert sum(v.numel() for v in sd.values()) == 8_675_102
 
 
 # ---------------------------------------------------------------- the original FullSubNet
@@ -95,11 +100,15 @@ def test_fullsubnet_torch_port_matches_reference(name):
 
 
 def test_fullsubnet_state_dict_matches_reference_parameter_tree():
-    if not ref_loader.reference_available():
-        pytest.skip("reference not mounted")
     from oracle.weights import make_state_dict_fullsubnet
-    ref = ref_loader.load_reference_fullsubnet()(**ref_loader.FULLSUBNET_MODEL_ARGS)
     sd = make_state_dict_fullsubnet(0)
+    tree = reference_facts()["fullsubnet_state_dict_tree"]
+    assert list(sd.keys()) == [k for k, _ in tree]
+    for k, shape in tree:
+        assert tuple(sd[k].shape) == tuple(shape), k
+    if not ref_loader.reference_available():
+        return
+    ref = ref_loader.load_reference_fullsubnet()(**ref_loader.FULLSUBNET_MODEL_ARGS)
     rsd = ref.state_dict()
     assert list(sd.keys()) == list(rsd.keys())
     for k in sd:
@@ -124,20 +133,29 @@ def test_committed_golden_is_what_the_generator_produces():
 
 def test_helper_restatements_match_the_reference_base_model():
     """oracle/fsnp_torch.py NORMS / unfold - the checkers of `model.norm` / `model.unfold` (fsnp_norm, fsnp_unfold) - against the reference's
-    own BaseModel static functions (audio_zen/model/base_model.py:15-47, 210-316), on the shapes the GPU test uses."""
+    own BaseModel static functions (audio_zen/model/base_model.py:15-47, 210-316), on the shapes the GPU test uses: their outputs as
+    stored in tests/golden/reference/ (oracle/make_golden.py main_reference_facts), and the functions themselves when the reference is
+    mounted."""
+    import hashlib
+    from oracle import make_golden
+    norms, unfolds = make_golden.base_model_inputs()
+    stored = np.load(make_golden.BASE_MODEL_PATH)
+    for i, (shape, x) in enumerate(norms):
+        for name, fn in fsnp_torch.NORMS.items():
+            want = torch.from_numpy(stored[f"{name}_{i}"])
+            got = fn(x)
+            assert got.shape == want.shape == shape, name
+            assert float((got - want).abs().max()) <= 2e-6 * float(want.abs().max()), name
+    for (nb, x), digest in zip(unfolds, reference_facts()["unfold_sha256"], strict=True):
+        assert hashlib.sha256(fsnp_torch.unfold(x, nb).contiguous().numpy().tobytes()).hexdigest() == digest, nb
     if not ref_loader.reference_available():
-        pytest.skip("reference not mounted")
-    import numpy as np
-    import torch
+        return
     ref_loader.load_reference()
     from audio_zen.model.base_model import BaseModel  # type: ignore
-    rng = np.random.Generator(np.random.PCG64(31))
-    for shape in [(3, 1, 257, 20), (2, 3, 34, 61), (1, 2, 5, 300)]:
-        x = torch.from_numpy(np.abs(rng.standard_normal(shape)).astype(np.float32) + 0.1)
+    for shape, x in norms:
         for name, fn in fsnp_torch.NORMS.items():
             want = getattr(BaseModel, name)(x)
             got = fn(x)
             assert float((got - want).abs().max()) <= 2e-6 * float(want.abs().max()), name
-    for shape, nb in [((2, 1, 257, 12), 15), ((2, 3, 40, 7), 1), ((1, 2, 9, 5), 0), ((2, 1, 33, 4), 8)]:
-        x = torch.from_numpy(rng.standard_normal(shape).astype(np.float32))
+    for nb, x in unfolds:
         assert torch.equal(fsnp_torch.unfold(x, nb), BaseModel.unfold(x, nb))
