@@ -63,6 +63,11 @@ SYMBOLS = {
     "fsnp_debug_set_costs": (c_i32, [c_vp, ctypes.POINTER(ctypes.c_double), c_i32]),
     "fsnp_debug_plan_rows2": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.c_double, c_i32, ctypes.POINTER(ctypes.c_double),
                               ctypes.POINTER(c_i32), c_i32]),
+    "fsnp_debug_coop_side_by_side": (c_i32, [ctypes.POINTER(c_i32 * 8), c_i32, c_i32, ctypes.POINTER(c_i32 * 8), c_i32, c_i32, c_i32]),
+    "fsnp_debug_fullsubnet_pairing": (c_i32, [c_i32, c_i32, c_i32, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_i32), c_i32]),
+    "fsnp_debug_pipeline_pairing": (c_i32, [c_vp, c_i32, ctypes.POINTER(c_i32), c_i32]),
+    "fsnp_debug_coop_chain_stats": (c_i32, [c_vp, ctypes.POINTER(c_i64 * 2), c_i32]),
+    "fsnp_debug_fullband_launch": (c_i32, [c_vp, c_i32, ctypes.POINTER(c_i32 * 4)]),
     "fsnp_forward_flops": (ctypes.c_double, [c_vp, c_i32, c_i32, c_i32]),
     "fsnp_lstm_flops": (ctypes.c_double, [c_vp, c_i64, c_i32]),
     "fsnp_debug_lstm_profile": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i64]),
@@ -97,7 +102,7 @@ SYMBOLS = {
     "fsnp_version": (ctypes.c_char_p, []),
 }
 
-ABI_VERSION = 10         # FSNP_ABI_VERSION of the include/fsnp.h these signatures were written against
+ABI_VERSION = 11         # FSNP_ABI_VERSION of the include/fsnp.h these signatures were written against
 
 _lib = None
 

@@ -209,36 +209,53 @@ __global__ __launch_bounds__(256) void prologue_kernel(PrologueArgs a) {
 // of one process) could each hold part of the chip and wait for peers that cannot be scheduled, so within a process
 // they are chained per device: each one waits for the previous one's completion event.  Other kernels always finish,
 // so they cannot close a cycle; a foreign PROCESS still can - that case ends in the kernels' wall-clock timeout.
-// Round 6: two such launches of ONE handle may run side by side when their workgroups - one per CU each - fit on the chip together
-// (`wgs` of both known, sum <= num_cus - 8): the pipelined loop's deferred remainder chunk of forward i (48 workgroups that own their CUs)
-// and the original FullSubNet's full-band LSTM of forward i + 1 (64 workgroups) used to wait for each other through this chain, which is
-// what kept FullSubNet at B = 32 above its 29 ms bar.  Both are resident at once whatever the dispatch order, so neither can wait for a CU
-// the other holds; everything else (other handles, unknown sizes, sums beyond the chip) is chained as before.
+// Two such launches of ONE handle on two streams may run side by side when one of them can always become fully resident whatever the other
+// holds, counted per XCD (planner.h coop_side_by_side): the pipelined loop's deferred remainder chunk of forward i (side stream, owns its
+// CUs) and the original FullSubNet's full-band LSTM of forward i + 1 (caller's stream) used to wait for each other through this chain,
+// which is what kept FullSubNet at B = 32 above its 29 ms bar (29.7 -> 28.5 ms).  Round 6 decided this on whole-chip totals (sum of
+// workgroups <= CUs - 8); the dispatcher deals workgroups to the XCDs by index, not by room, so a pair that fits the chip can still
+// overflow an XCD (a 2-tile half-tile ping-pong remainder - 24 owned CUs on each of two XCDs - beside a 2-tile full-band launch at one
+// workgroup per CU: 24 + 16 > 32).  Everything else (other handles, unknown sizes or occupancy) is chained as before; an earlier launch
+// on the same stream is behind this one anyway (waited for - a no-op in stream order - and not counted).
 static std::mutex g_coop_mu;
-struct CoopSlot { hipEvent_t ev = nullptr; bool used = false; const void* owner = nullptr; int wgs = 0; unsigned long long seq = 0; };
+struct CoopSlot {
+    hipEvent_t ev = nullptr; bool used = false; const void* owner = nullptr; hipStream_t stream = nullptr;
+    bool has_fp = false; CoopFootprint fp{}; unsigned long long seq = 0;
+};
 static CoopSlot g_coop[64][2];
 static unsigned long long g_coop_seq = 0;
+// fp = where the launch's workgroups go (nullptr: unknown - chained); counts the earlier launches of `owner` on other streams this one
+// runs beside / was chained behind into owner_stats (fsnp_debug_coop_chain_stats)
 template <typename F>
-static void launch_coop_chained(int dev, hipStream_t s, F launch, const void* owner = nullptr, int wgs = 0, int num_cus = 0) {
+static void launch_coop_chained(int dev, hipStream_t s, F launch, const void* owner = nullptr, const CoopFootprint* fp = nullptr,
+                                int cus_per_xcd = 0, int64_t* owner_stats = nullptr) {
     if (dev < 0 || dev >= 64) { launch(); return; }
     std::lock_guard<std::mutex> lk(g_coop_mu);
     CoopSlot* sl = g_coop[dev];
     const int order[2] = {sl[0].seq <= sl[1].seq ? 0 : 1, sl[0].seq <= sl[1].seq ? 1 : 0};      // older first
-    bool waited[2] = {false, false};
-    int beside = wgs;
+    bool behind[2] = {false, false};
+    int beside = -1;                    // a slot this launch runs beside
     for (int o = 0; o < 2; ++o) {
-        CoopSlot& c = sl[order[o]];
+        const int k = order[o];
+        CoopSlot& c = sl[k];
         if (!c.used) continue;
-        const bool fits = owner && c.owner == owner && wgs > 0 && c.wgs > 0 && num_cus > 0 && beside + c.wgs <= num_cus - 8;
-        if (fits) beside += c.wgs;
-        else { (void)hipStreamWaitEvent(s, c.ev, 0); waited[order[o]] = true; }
+        const bool other_stream = c.stream != s, mine = owner && c.owner == owner;
+        bool fits = other_stream && mine && fp && c.has_fp;
+        if (fits) {
+            // (a launch this one already runs beside, on a third stream, may be in flight together with c: both are blockers then)
+            const bool both = beside >= 0 && sl[beside].stream != c.stream;
+            fits = coop_side_by_side(both ? coop_footprint_sum(*fp, sl[beside].fp) : *fp, c.fp, cus_per_xcd);
+        }
+        if (fits) beside = k;
+        else { (void)hipStreamWaitEvent(s, c.ev, 0); behind[k] = true; }
+        if (other_stream && mine && owner_stats) ++owner_stats[fits ? 0 : 1];
     }
     launch();
     // the slot this launch takes: a free one, else one it waited for (that launch is behind it now), else one that has finished, else
     // the older one - after waiting for it
     int k = -1;
     for (int i = 0; i < 2 && k < 0; ++i) if (!sl[i].used) k = i;
-    for (int o = 0; o < 2 && k < 0; ++o) if (waited[order[o]]) k = order[o];
+    for (int o = 0; o < 2 && k < 0; ++o) if (behind[order[o]]) k = order[o];
     for (int o = 0; o < 2 && k < 0; ++o) {
         if (hipEventQuery(sl[order[o]].ev) == hipSuccess) k = order[o];
         else (void)hipGetLastError();
@@ -246,7 +263,9 @@ static void launch_coop_chained(int dev, hipStream_t s, F launch, const void* ow
     if (k < 0) { k = order[0]; (void)hipStreamWaitEvent(s, sl[k].ev, 0); }
     if (!sl[k].ev && hipEventCreateWithFlags(&sl[k].ev, hipEventDisableTiming) != hipSuccess) { sl[k].ev = nullptr; sl[k].used = false; return; }
     sl[k].used = hipEventRecord(sl[k].ev, s) == hipSuccess;
-    sl[k].owner = owner; sl[k].wgs = wgs; sl[k].seq = ++g_coop_seq;
+    sl[k].owner = owner; sl[k].stream = s; sl[k].seq = ++g_coop_seq;
+    sl[k].has_fp = fp != nullptr;
+    if (fp) sl[k].fp = *fp;
 }
 
 // The planner itself (cost table, launch shapes, shortest path over tile counts) is host-only code: planner.h / planner.cpp.
@@ -266,6 +285,8 @@ static double forward_gather_bytes(const fsnp_handle* h, int B, int T) {
     return 2.0 * ((double)align_up((size_t)(nbr * B * ((double)T + h->cfg.look_ahead) * h->FP * 4), 256));
 }
 static int chunk_workgroups(const fsnp_handle* h, const SbChunk& c) { return chunk_workgroups(pctx(h), c); }
+// where a sub-band chunk's workgroups go; one per CU (owned or not: the least a launch that does not own its CUs is sure to get)
+static CoopFootprint sb_chunk_footprint(const fsnp_handle* h, const SbChunk& c, bool own_cu) { return chunk_footprint(pctx(h), c, own_cu, 1); }
 // Launches chunks [first, last) of the plan on stream s.  `bar` = per-tile arrival counters followed (at bar +
 // plan.coop_tiles, 64-byte aligned by the caller) by the launch-abort word.
 static void launch_sb_lstm(const fsnp_handle* h, const SbPlan& plan, const LstmArgs& a, float* hx, unsigned* bar, unsigned* abort_word,
@@ -302,18 +323,14 @@ static void launch_sb_lstm(const fsnp_handle* h, const SbPlan& plan, const LstmA
         ca.coop_abort = abort_word;
         ca.coop_units = c.units; ca.coop_groups = c.groups; ca.coop_rows_per_group = c.rpg;
         // XCD-local workgroup placement (lstm_common.h), unless the launch was planned with two workgroups per CU
-        constexpr int xcd_local = 1;
-        {
-            const int S = c.kind == 8 ? h->H / 16 : (c.kind == 1 || c.kind == 9) ? h->H / c.units : h->H / 128;
-            const int T = c.kind == 2 ? c.groups : c.num_tiles, cpx = h->num_cus_real / 8;
-            ca.coop_xcd = xcd_local && h->num_cus_real % 8 == 0 && xcd_local_blocks_per_xcd(S, T, cpx) <= cpx ? cpx : 0;
-        }
+        ca.coop_xcd = chunk_coop_xcd(pctx(h), c);
+        const CoopFootprint fp = sb_chunk_footprint(h, c, ca.coop_own_cu > 0);
         launch_coop_chained(h->device, s, [&] {
             if (c.kind == 8) { if (h->lw.hp_wave && lstm_hpw_available(h->lw)) launch_lstm_hpw(h->lw, ca, s); else launch_lstm_hp(h->lw, ca, s); }
             else if (c.kind == 9) launch_lstm_coopw(h->lw, ca, s);
             else if (c.kind == 1) launch_lstm_coop(h->lw, ca, s);
             else launch_lstm_coopn(h->lw, ca, s);
-        }, h, chunk_workgroups(h, c), h->num_cus_real);
+        }, h, &fp, h->num_cus_real / kNumXcds, h->coop_chain_stats);
     }
     if (after_first && last_chunk == nchunks) (void)hipEventRecord(after_first, s);
 }
@@ -332,26 +349,48 @@ static int fb_coop_units(const fsnp_handle* h, int B) {
     return u > 32 ? 0 : u;
 }
 
-// Pipelined serving loop (fsnp_set_pipeline): which chunks of a plan go to the side stream, where they overlap the NEXT forward's
-// full-band stages.  Deferred column-split launches own their CUs (LstmArgs::coop_own_cu), so the overlapped stages run on what is
-// left: that pays while the deferred launches leave at least 32 CUs free (B = 32: 48 workgroups, 28.2 -> 27.5 ms; B = 1: 216, 1.97 ->
-// 1.77) and LOSES when they fill the chip (B = 40: a 66-tile remainder, 36.9 -> 37.5 ms; B = 21: the overlapped stage took 5.4 ms
-// instead of 0.66 - profiles/r04_bench_configs.md): the planner defers only in the first case.
+// Pipelined serving loop (fsnp_set_pipeline): which chunks of a plan go to the side stream (planner.cpp plan_first_deferred)
 //   returns: first deferred chunk (== chunks.size(): nothing is deferred; 0: the whole plan)
-static int plan_first_deferred(const fsnp_handle* h, const SbPlan& plan) {
-    const int n = (int)plan.chunks.size();
-    auto fills_chip = [](const SbChunk& c) { return c.kind == 0 || c.kind == 4; };       // one (half) tile per CU, no exchange
-    if (n == 0 || h->sb_tcn) return n;
-    int first = n;
-    if (n > 1 && fills_chip(plan.chunks[0])) {
-        first = 1;
-        while (first < n && fills_chip(plan.chunks[first])) ++first;
-    } else if (h->defer_small && !fills_chip(plan.chunks[0])) {
-        first = 0;
+static int plan_first_deferred(const fsnp_handle* h, const SbPlan& plan) { return plan_first_deferred(pctx(h), plan, h->defer_small != 0); }
+// which kernel runs the full-band LSTM of a `batch`-utterance FullSubNet forward, in what shape (fsnp_debug_fullband_launch)
+struct FbShape { int kernel, tiles, rows_per_tile, units; };      // kernel: 0 = lstm_coop_seq (K split), 1 = lstm_fbv (VALU), 2 = lstm_generic
+static FbShape fb_shape(const fsnp_handle* h, int batch) {
+    if (h->generic_fb) {               // (runtime-sized kernel for a full-band model no K-split instantiation exists for: workgroups of rg sequences)
+        const int rg = lstm_generic_rows_per_group(h->CH, h->F, batch, h->num_cus_real);
+        return {2, rg > 0 ? cdiv(batch, rg) : 0, rg, 0};
     }
-    int busiest = 0;
-    for (int i = first; i < n; ++i) busiest = std::max(busiest, chunk_workgroups(h, plan.chunks[i]));
-    return (first < n && busiest <= h->num_cus_real - 32) ? first : n;
+    if (h->fb_valu && lstm_fbv_available(h->fbw, batch, h->num_cus_real)) return {1, fb_row_tiles(batch), 32, 0};
+    return {0, fb_row_tiles(batch), 32, fb_coop_units(h, batch)};
+}
+// the full-band LSTM launch of the original FullSubNet (lstm_coop_seq, never owns its CUs): round robin, at the occupancy measured at commit
+static CoopFootprint fb_coop_footprint(const PlannerCtx& c, int CH, int batch, int fb_per_cu) {
+    const int tiles = fb_row_tiles(batch), u = lstm_coop_pick_units(CH, tiles, c.num_cus_real, 8);      // (fb_coop_units)
+    const bool ok = u > 0 && u <= 32;
+    return coop_footprint_round_robin(ok ? tiles * (CH / u) : 0, false, ok ? fb_per_cu : 0);
+}
+static int fb_units_index(int units) { return units == 8 ? 0 : units == 16 ? 1 : 2; }
+// The side-by-side decision of the pipelined FullSubNet loop at `batch` utterances (full mode): for every chunk of the plan that goes to
+// the side stream, may the next forward's full-band LSTM run beside it?  Records of 9 ints (fsnp_debug.h: fsnp_debug_pipeline_pairing).
+//   fb_per_cu: measured occupancy at 8 / 16 / 32 units per workgroup; fb_valu: the full-band LSTM runs on lstm_fbv instead (chained: B <= 4)
+static int pipeline_pairing(const PlannerCtx& c, bool defer_small, int F, int CH, int batch, const int fb_per_cu[3], bool fb_valu,
+                            int32_t* out, int max_records) {
+    const SbPlan plan = plan_sb(c, batch * F);
+    const int first = plan_first_deferred(c, plan, defer_small), cpx = c.num_cus_real % kNumXcds == 0 ? c.num_cus_real / kNumXcds : 0;
+    const int u = lstm_coop_pick_units(CH, fb_row_tiles(batch), c.num_cus_real, 8);
+    const CoopFootprint fb = fb_valu ? coop_footprint_round_robin(0, false, 0) : fb_coop_footprint(c, CH, batch, fb_per_cu[fb_units_index(u)]);
+    int fb_wgs = 0, fb_max = 0;
+    for (int x = 0; x < kNumXcds; ++x) { fb_wgs += fb.per_xcd[x]; fb_max = std::max(fb_max, fb.per_xcd[x]); }
+    int n = 0;
+    for (int i = first; i < (int)plan.chunks.size() && n < max_records; ++i, ++n) {
+        const SbChunk& k = plan.chunks[i];
+        const CoopFootprint f = chunk_footprint(c, k, chunk_workgroups(c, k) <= c.num_cus_real, 1);    // (launch_sb_lstm: coop_own_cu)
+        int f_max = 0;
+        for (int x = 0; x < kNumXcds; ++x) f_max = std::max(f_max, f.per_xcd[x]);
+        int32_t* o = out + 9 * n;
+        o[0] = i; o[1] = k.kind; o[2] = k.num_tiles; o[3] = chunk_workgroups(c, k); o[4] = f_max;
+        o[5] = fb_wgs; o[6] = fb_max; o[7] = fb.per_cu; o[8] = fb_wgs > 0 && coop_side_by_side(f, fb, cpx) ? 1 : 0;
+    }
+    return n;
 }
 
 static int rows_per_utt(const fsnp_handle* h, int mode) {
@@ -1152,9 +1191,8 @@ static int forward_impl(fsnp_handle* h, const float* mag, const float* real, con
         fbuf.raw = fptr(w.att); fbuf.frame = reinterpret_cast<double*>(base + w.frame);
         fbuf.md = reinterpret_cast<NormMD*>(base + w.md);
         launch_frontend_mag(d, h->cfg.norm_type, mag, strides[0], is_complex, fbuf, s);
-        // (runtime-sized kernel for a full-band model no K-split instantiation exists for: workgroups of fb_rg sequences)
-        const int fb_rg = h->generic_fb ? lstm_generic_rows_per_group(h->CH, h->F, batch, h->num_cus_real) : 32;
-        const int fb_tiles = h->generic_fb ? cdiv(batch, fb_rg) : fb_row_tiles(batch);
+        const FbShape fbs = fb_shape(h, batch);
+        const int fb_rg = fbs.rows_per_tile, fb_tiles = fbs.tiles;
         RowDesc* fb_rows = reinterpret_cast<RowDesc*>(base + w.fb_rows);
         hipLaunchKernelGGL(build_rows_kernel, dim3(cdiv(fb_tiles * fb_rg, 256)), dim3(256), 0, s, fb_rows, batch, fb_tiles, fb_rg,
                            1, frames, 0, 0, 1, 1, 0, 2, 2);
@@ -1167,9 +1205,12 @@ static int forward_impl(fsnp_handle* h, const float* mag, const float* real, con
         fa.coop_units = fb_units; fa.coop_chaos = h->coop_chaos;
         const int chp = (int)align_up(d.CH, 4);           // row stride of the h1 sequence (a float4 multiple; pad columns written as zeros)
         fa.seq_stride = chp;
-        if (h->generic_fb) { fa.coop_rows_per_group = fb_rg; launch_lstm_generic(h->fbw, fa, true, s); }
-        else if (h->fb_valu && lstm_fbv_available(h->fbw, batch, h->num_cus_real)) launch_coop_chained(h->device, s, [&] { launch_lstm_fbv(h->fbw, fa, s); });   // B <= 4: VALU
-        else launch_coop_chained(h->device, s, [&] { launch_lstm_coop_seq(h->fbw, fa, s); }, h, fa.coop_units > 0 ? fb_tiles * (h->CH / fa.coop_units) : 0, h->num_cus_real);
+        if (fbs.kernel == 2) { fa.coop_rows_per_group = fb_rg; launch_lstm_generic(h->fbw, fa, true, s); }
+        else if (fbs.kernel == 1) launch_coop_chained(h->device, s, [&] { launch_lstm_fbv(h->fbw, fa, s); });   // B <= 4: VALU
+        else {
+            const CoopFootprint fp = fb_coop_footprint(pctx(h), h->CH, batch, h->occ_fb[fb_units_index(fb_units)]);
+            launch_coop_chained(h->device, s, [&] { launch_lstm_coop_seq(h->fbw, fa, s); }, h, &fp, h->num_cus_real / kNumXcds, h->coop_chain_stats);
+        }
         launch_linear_act(fptr(w.y1), chp, h->fsn_wf, h->fsn_kp, h->fsn_bf, fptr(w.fb), d.FP, d.CH, d.F, d.B, d.Tp,
                           h->cfg.fb_act, h->num_cus, s);
         launch_subband_stats(d, h->cfg.norm_type, sbuf, rows, num_slots, s);
@@ -1465,10 +1506,10 @@ int fsnp_debug_plan_rows(int32_t num_rows, int32_t num_cus, int32_t hidden, int3
     return fsnp_debug_plan_rows2(num_rows, num_cus, hidden, gru, coop, composite_gain, 1, nullptr, out, max_chunks);
 }
 
-int fsnp_debug_plan_rows2(int32_t num_rows, int32_t num_cus, int32_t hidden, int32_t gru, int32_t coop, double composite_gain,
-                          int32_t workgroups_per_cu, const double* costs, int32_t* out, int32_t max_chunks) {
-    if (!out || num_rows <= 0 || num_cus <= 0 || hidden < 128 || hidden % 128 != 0 || max_chunks <= 0) { set_error("fsnp_debug_plan_rows: bad argument"); return -1; }
-    PlannerCtx h;                       // host-only: the planner never touches the device
+// the planner of a handle on a chip of num_cus CUs whose kernels are all available (host only: the planner never touches the device)
+static PlannerCtx host_ctx(int32_t num_cus, int32_t hidden, int32_t gru, int32_t coop, double composite_gain, int32_t workgroups_per_cu,
+                           const double* costs) {
+    PlannerCtx h;
     h.H = hidden; h.num_cus = num_cus; h.num_cus_real = num_cus; h.gru = gru; h.lstm_coop = coop; h.composite_gain = composite_gain;
     h.cost = default_costs(); h.coop_occ = workgroups_per_cu >= 2 ? 2 : 1;
     for (int i = 0; i < 4; ++i) h.occ_ksplit[i] = h.coop_occ;
@@ -1482,6 +1523,13 @@ int fsnp_debug_plan_rows2(int32_t num_rows, int32_t num_cus, int32_t hidden, int
     h.rowtile_ok = gru == 0 || gru == 2;      // gru = 1: plan as if there were no one-tile-per-CU GRU kernel (round-1 shape)
     h.gru = gru != 0;
     if (gru == 2) h.cost.rowtile *= 0.75;
+    return h;
+}
+
+int fsnp_debug_plan_rows2(int32_t num_rows, int32_t num_cus, int32_t hidden, int32_t gru, int32_t coop, double composite_gain,
+                          int32_t workgroups_per_cu, const double* costs, int32_t* out, int32_t max_chunks) {
+    if (!out || num_rows <= 0 || num_cus <= 0 || hidden < 128 || hidden % 128 != 0 || max_chunks <= 0) { set_error("fsnp_debug_plan_rows: bad argument"); return -1; }
+    const PlannerCtx h = host_ctx(num_cus, hidden, gru, coop, composite_gain, workgroups_per_cu, costs);
     const SbPlan plan = plan_sb(h, num_rows);
     int n = 0;
     for (const SbChunk& c : plan.chunks) {
@@ -1492,6 +1540,50 @@ int fsnp_debug_plan_rows2(int32_t num_rows, int32_t num_cus, int32_t hidden, int
         ++n;
     }
     return n;
+}
+
+int fsnp_debug_coop_side_by_side(const int32_t a_per_xcd[8], int32_t a_own_cu, int32_t a_per_cu, const int32_t b_per_xcd[8],
+                                 int32_t b_own_cu, int32_t b_per_cu, int32_t cus_per_xcd) {
+    if (!a_per_xcd || !b_per_xcd) { set_error("fsnp_debug_coop_side_by_side: null argument"); return -1; }
+    CoopFootprint a{}, b{};
+    for (int x = 0; x < kNumXcds; ++x) {
+        if (a_per_xcd[x] < 0 || b_per_xcd[x] < 0) { set_error("fsnp_debug_coop_side_by_side: negative workgroup count"); return -1; }
+        a.per_xcd[x] = a_per_xcd[x]; b.per_xcd[x] = b_per_xcd[x];
+    }
+    a.own_cu = a_own_cu != 0; a.per_cu = a_per_cu; b.own_cu = b_own_cu != 0; b.per_cu = b_per_cu;
+    return coop_side_by_side(a, b, cus_per_xcd) ? 1 : 0;
+}
+
+int fsnp_debug_fullsubnet_pairing(int32_t batch, int32_t num_cus, int32_t fb_workgroups_per_cu, const double* costs, int32_t* out,
+                                  int32_t max_records) {
+    if (!out || batch <= 0 || num_cus <= 0 || max_records <= 0) { set_error("fsnp_debug_fullsubnet_pairing: bad argument"); return -1; }
+    const PlannerCtx c = host_ctx(num_cus, 384, 0, 1, 0.97, 1, costs);       // FullSubNet's sub-band model: LSTM, hidden 384
+    const int per_cu[3] = {fb_workgroups_per_cu, fb_workgroups_per_cu, fb_workgroups_per_cu};
+    return pipeline_pairing(c, true, 257, 512, batch, per_cu, batch <= 4, out, max_records);
+}
+
+int fsnp_debug_pipeline_pairing(const fsnp_handle* h, int32_t batch, int32_t* out, int32_t max_records) {
+    if (!h || !out || batch <= 0 || max_records <= 0) { set_error("fsnp_debug_pipeline_pairing: bad argument"); return -1; }
+    if (!h->committed) { set_error("fsnp_debug_pipeline_pairing: weights not committed (the decision depends on the kernels' occupancy)"); return -1; }
+    if (h->model != FSNP_MODEL_FULLSUBNET || h->generic_fb || h->sb_tcn) return 0;      // no column-split launch on the caller's stream
+    const bool valu = h->fb_valu && lstm_fbv_available(h->fbw, batch, h->num_cus_real);
+    return pipeline_pairing(pctx(h), h->defer_small != 0, h->F, h->CH, batch, h->occ_fb, valu, out, max_records);
+}
+
+int fsnp_debug_fullband_launch(const fsnp_handle* h, int32_t batch, int32_t out[4]) {
+    if (!h || !out || batch <= 0) { set_error("fsnp_debug_fullband_launch: bad argument"); return 1; }
+    if (h->model != FSNP_MODEL_FULLSUBNET) { set_error("fsnp_debug_fullband_launch: FullSubNet+ has no full-band LSTM"); return 2; }
+    const FbShape f = fb_shape(h, batch);
+    out[0] = f.kernel; out[1] = f.tiles; out[2] = f.rows_per_tile; out[3] = f.units;
+    return 0;
+}
+
+int fsnp_debug_coop_chain_stats(fsnp_handle* h, int64_t out[2], int32_t reset) {
+    if (!h || !out) { set_error("fsnp_debug_coop_chain_stats: null argument"); return 1; }
+    std::lock_guard<std::mutex> lk(g_coop_mu);
+    out[0] = h->coop_chain_stats[0]; out[1] = h->coop_chain_stats[1];
+    if (reset) h->coop_chain_stats[0] = h->coop_chain_stats[1] = 0;
+    return 0;
 }
 
 int fsnp_get_costs(const fsnp_handle* h, double out[FSNP_NUM_COSTS], int32_t* calibrated, int32_t* occ) {

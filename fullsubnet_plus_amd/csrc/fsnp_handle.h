@@ -65,6 +65,7 @@ struct fsnp_handle {
     CostTable cost{};            // per-step costs the planner minimises (defaults, then measured on the device)
     int coop_occ = 1;            // workgroups per CU the column-split kernels may be planned with (FSNP_COOP_OCC; 1 or 2) ...
     int occ_ksplit[4] = {1, 1, 1, 1}, occ_coopn[2] = {1, 1};   // ... and what each instantiation really fits (measured at commit)
+    int occ_fb[3] = {0, 0, 0};   // FullSubNet: workgroups of the full-band lstm_coop_seq at 8 / 16 / 32 units one CU holds (measured at commit; 0 = unknown)
     int calibrate = 0;           // FSNP_CALIBRATE=1: replace the built-in table by one measured on this device at the first planning call
     int sb_tcn = 0;              // 1 = the sub-band model is a TCN stack (FullSubNet+ with sequence_model="TCN")
     TcnWeights sbt{};            //     its weights (one branch, NIN input channels)
@@ -150,6 +151,8 @@ struct fsnp_handle {
     hipStream_t side_stream = nullptr;
     hipEvent_t ev_main = nullptr, ev_side[2] = {nullptr, nullptr};
     bool side_used[2] = {false, false};
+    // this handle's column-split launches that ran beside [0] / were chained behind [1] one of its own on another stream (launch_coop_chained)
+    mutable int64_t coop_chain_stats[2] = {0, 0};
     unsigned char* last_base = nullptr;   // workspace half of the last forward (fsnp_read_stage)
     hipEvent_t ev_done = nullptr;         // end of the last forward on its stream: a forward on another stream waits for it
     hipStream_t done_stream = nullptr;

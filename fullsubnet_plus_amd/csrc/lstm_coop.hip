@@ -908,5 +908,14 @@ void launch_lstm_coop_seq(const LstmWeights& w, const LstmArgs& a, hipStream_t s
     if (w.gru) launch_coop_units<512, 264, true, true>(w, a, s);
     else launch_coop_units<512, 264, true, false>(w, a, s);
 }
+// workgroups of that kernel at `units` hidden units per workgroup that fit one CU at once (0 = unknown)
+int lstm_coop_seq_occupancy(const LstmWeights& w, int units) {
+    LstmArgs a{};
+    a.coop_units = units;
+    int occ = 0;
+    if (w.gru) launch_coop_units<512, 264, true, true>(w, a, nullptr, &occ);
+    else launch_coop_units<512, 264, true, false>(w, a, nullptr, &occ);
+    return occ;
+}
 
 }  // namespace fsnp

@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "fsnp_common.h"
+#include "lstm_common.h"
 #include "planner.h"
 
 namespace fsnp {
@@ -249,6 +250,71 @@ SbPlan plan_sb(const PlannerCtx& h, int num_rows) {
     }
     for (const SbChunk& c : best) push(c);                     // empty = "this device cannot run the model"
     return p;
+}
+
+// Pipelined serving loop (fsnp_set_pipeline): which chunks of a plan go to the side stream, where they overlap the NEXT forward's
+// full-band stages.  Deferred column-split launches own their CUs (LstmArgs::coop_own_cu), so the overlapped stages run on what is
+// left: that pays while the deferred launches leave at least 32 CUs free (B = 32: 48 workgroups, 28.2 -> 27.5 ms; B = 1: 216, 1.97 ->
+// 1.77) and LOSES when they fill the chip (B = 40: a 66-tile remainder, 36.9 -> 37.5 ms; B = 21: the overlapped stage took 5.4 ms
+// instead of 0.66 - profiles/r04_bench_configs.md): the planner defers only in the first case.
+int plan_first_deferred(const PlannerCtx& h, const SbPlan& plan, bool defer_small) {
+    const int n = (int)plan.chunks.size();
+    auto fills_chip = [](const SbChunk& c) { return c.kind == 0 || c.kind == 4; };       // one (half) tile per CU, no exchange
+    if (n == 0 || h.sb_tcn) return n;
+    int first = n;
+    if (n > 1 && fills_chip(plan.chunks[0])) {
+        first = 1;
+        while (first < n && fills_chip(plan.chunks[first])) ++first;
+    } else if (defer_small && !fills_chip(plan.chunks[0])) {
+        first = 0;
+    }
+    int busiest = 0;
+    for (int i = first; i < n; ++i) busiest = std::max(busiest, chunk_workgroups(h, plan.chunks[i]));
+    return (first < n && busiest <= h.num_cus_real - 32) ? first : n;
+}
+
+// ---- side-by-side decision of two column-split launches (launch_coop_chained, fsnp_abi.hip)
+CoopFootprint coop_footprint_round_robin(int wgs, bool own_cu, int per_cu) {
+    CoopFootprint f{};
+    for (int x = 0; x < kNumXcds; ++x) f.per_xcd[x] = wgs / kNumXcds + (x < wgs % kNumXcds ? 1 : 0);
+    f.own_cu = own_cu ? 1 : 0; f.per_cu = per_cu;
+    return f;
+}
+// S workgroups per row tile and T tiles (kind 2: groups) of a column-split chunk, as its kernel decodes them
+static void chunk_split(const PlannerCtx& h, const SbChunk& c, int& S, int& T) {
+    S = c.kind == 8 ? h.H / 16 : (c.kind == 1 || c.kind == 9) ? h.H / c.units : h.H / 128;
+    T = c.kind == 2 ? c.groups : c.num_tiles;
+}
+int chunk_coop_xcd(const PlannerCtx& h, const SbChunk& c) {
+    int S, T;
+    chunk_split(h, c, S, T);
+    const int cpx = h.num_cus_real / kNumXcds;
+    return h.num_cus_real % kNumXcds == 0 && xcd_local_blocks_per_xcd(S, T, cpx) <= cpx ? cpx : 0;
+}
+CoopFootprint chunk_footprint(const PlannerCtx& h, const SbChunk& c, bool own_cu, int per_cu) {
+    const int cpx = chunk_coop_xcd(h, c);
+    if (!cpx) return coop_footprint_round_robin(chunk_workgroups(h, c), own_cu, per_cu);
+    int S, T;
+    chunk_split(h, c, S, T);
+    return coop_footprint_round_robin(kNumXcds * xcd_local_blocks_per_xcd(S, T, cpx), own_cu, per_cu);     // (its grid: 8 x that)
+}
+// `l` can always become fully resident beside `blocker`, which holds at most one CU per workgroup it was dealt on each XCD
+static bool always_resident(const CoopFootprint& blocker, const CoopFootprint& l, int cus_per_xcd) {
+    const int per_cu = l.own_cu ? 1 : l.per_cu;
+    if (per_cu <= 0) return false;
+    for (int x = 0; x < kNumXcds; ++x)
+        if (blocker.per_xcd[x] + cdiv(l.per_xcd[x], per_cu) > cus_per_xcd) return false;
+    return true;
+}
+bool coop_side_by_side(const CoopFootprint& a, const CoopFootprint& b, int cus_per_xcd) {
+    if (cus_per_xcd <= 0 || a.per_cu <= 0 || b.per_cu <= 0) return false;
+    return always_resident(a, b, cus_per_xcd) || always_resident(b, a, cus_per_xcd);
+}
+CoopFootprint coop_footprint_sum(const CoopFootprint& a, const CoopFootprint& b) {
+    CoopFootprint f{};
+    for (int x = 0; x < kNumXcds; ++x) f.per_xcd[x] = a.per_xcd[x] + b.per_xcd[x];
+    f.own_cu = 1; f.per_cu = 1;
+    return f;
 }
 
 }  // namespace fsnp

@@ -62,5 +62,29 @@ CostTable initial_costs(int sb_hidden, bool gru, bool sb_tcn);
 int chunk_workgroups(const PlannerCtx& h, const SbChunk& c);
 double est_step_us(const PlannerCtx& h, const SbChunk& c);
 SbPlan plan_sb(const PlannerCtx& h, int num_rows);       // empty plan = "this device cannot run the model"
+// pipelined serving loop (fsnp_set_pipeline): the first chunk that goes to the side stream (== chunks.size(): none; 0: the whole plan)
+int plan_first_deferred(const PlannerCtx& h, const SbPlan& plan, bool defer_small);
+
+// ---- may two column-split launches of one handle run side by side?  All the workgroups of each must be co-resident, and the
+// dispatcher deals workgroup id i to XCD i % 8 whatever room that XCD has: what has to fit is counted per XCD, not per chip.
+constexpr int kNumXcds = 8;
+struct CoopFootprint {
+    int per_xcd[kNumXcds];     // workgroups dealt to each XCD (those of an XCD-local launch that find no row tile exit at once: counted too)
+    int own_cu;                // 1: each workgroup claims a whole CU (LstmArgs::coop_own_cu), nothing else runs beside it there
+    int per_cu;                // workgroups of this kernel one CU holds at once (hipOccupancyMaxActiveBlocksPerMultiprocessor); <= 0: unknown
+};
+// a launch of `wgs` workgroups dealt round robin (coop_xcd = 0)
+CoopFootprint coop_footprint_round_robin(int wgs, bool own_cu, int per_cu);
+// the CUs per XCD launch_sb_lstm passes as LstmArgs::coop_xcd for chunk c (XCD-local placement, lstm_common.h), 0 = round robin
+int chunk_coop_xcd(const PlannerCtx& h, const SbChunk& c);
+// where chunk c's workgroups go (the placement launch_sb_lstm uses)
+CoopFootprint chunk_footprint(const PlannerCtx& h, const SbChunk& c, bool own_cu, int per_cu);
+// Side by side only if one of the two can ALWAYS become fully resident, whatever the other holds: on every XCD the CUs the other may
+// occupy (at most one per workgroup dealt there) plus the CUs this one needs at its own occupancy (one per workgroup if it owns its
+// CUs, else cdiv(workgroups there, per_cu)) fit in the XCD.  That one then runs to its end and frees its CUs for the other.
+// Unknown occupancy or CU count: false (chain them).
+bool coop_side_by_side(const CoopFootprint& a, const CoopFootprint& b, int cus_per_xcd);
+// two launches that may be in flight together, as one blocker: one whole CU per workgroup (for a further side-by-side check)
+CoopFootprint coop_footprint_sum(const CoopFootprint& a, const CoopFootprint& b);
 
 }  // namespace fsnp

@@ -785,6 +785,31 @@ class _HipModel(nn.Module):
         return [{"kernel": names[buf[7 * i]], "sequences": buf[7 * i + 1], "tiles": buf[7 * i + 2], "valu_rows": buf[7 * i + 3],
                  "precision": prec[buf[7 * i + 4]], "workgroups": buf[7 * i + 5], "deferred_when_pipelined": bool(buf[7 * i + 6])} for i in range(n)]
 
+    def pipeline_pairing(self, batch):
+        """-> [{"chunk", "kind", "tiles", "workgroups", "max_per_xcd", "fb_workgroups", "fb_max_per_xcd", "fb_per_cu", "side_by_side"}, ...]:
+        for each sub-band launch the pipelined loop defers at `batch` utterances (full mode), whether the next forward's full-band LSTM
+        runs beside it or is chained behind it, as this handle decides it (fsnp_debug_pipeline_pairing; FullSubNet+: [])."""
+        buf = (ctypes.c_int32 * (9 * 16))()
+        n = _lib.load().fsnp_debug_pipeline_pairing(self._handle, int(batch), buf, 16)
+        if n < 0:
+            raise RuntimeError(_lib.last_error())
+        keys = ("chunk", "kind", "tiles", "workgroups", "max_per_xcd", "fb_workgroups", "fb_max_per_xcd", "fb_per_cu", "side_by_side")
+        return [dict(zip(keys, buf[9 * i:9 * i + 9])) for i in range(n)]
+
+    def fullband_launch(self, batch):
+        """-> {"kernel", "tiles", "rows_per_tile", "units"}: the full-band LSTM launch of a `batch`-utterance forward of the original
+        FullSubNet (fsnp_debug_fullband_launch; kernel: "coop_seq" / "fbv" / "generic")."""
+        out = (ctypes.c_int32 * 4)()
+        _lib.check(_lib.load().fsnp_debug_fullband_launch(self._handle, int(batch), ctypes.byref(out)), "fsnp_debug_fullband_launch")
+        return {"kernel": ("coop_seq", "fbv", "generic")[out[0]], "tiles": out[1], "rows_per_tile": out[2], "units": out[3]}
+
+    def coop_chain_stats(self, reset=False):
+        """-> (beside, chained): this handle's column-split launches that ran beside / were chained behind one of its own launches on
+        another stream since the last reset (fsnp_debug_coop_chain_stats)."""
+        out = (ctypes.c_int64 * 2)()
+        _lib.check(_lib.load().fsnp_debug_coop_chain_stats(self._handle, ctypes.byref(out), int(bool(reset))), "fsnp_debug_coop_chain_stats")
+        return int(out[0]), int(out[1])
+
     def debug_set_costs(self, costs=None, workgroups_per_cu=1, device="cuda"):
         """Test hook: pin the planner's cost table (_lib.NUM_COSTS values, fsnp_get_costs order; None = built-in) and whether it
         may put two column-split workgroups on a CU (fsnp_debug_set_costs).  A shorter table prices the launch shapes it does

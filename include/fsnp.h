@@ -299,7 +299,7 @@ const char* fsnp_last_error(void);
 const char* fsnp_version(void);
 /* Binding sanity: FSNP_ABI_VERSION of the header the library was built from and sizeof(fsnp_config) as it sees it; a
  * binding compares both with its own idea before the first real call (fullsubnet_plus_amd/_lib.py does). */
-#define FSNP_ABI_VERSION 10
+#define FSNP_ABI_VERSION 11
 int32_t fsnp_abi_version(void);
 int32_t fsnp_config_size(void);
 

@@ -73,6 +73,34 @@ int fsnp_measure_costs(fsnp_handle* h, double out[FSNP_NUM_COSTS]);
 int fsnp_debug_plan_rows(int32_t num_rows, int32_t num_cus, int32_t hidden, int32_t gru, int32_t coop, double composite_gain,
                          int32_t* out, int32_t max_chunks);
 
+/* Round 7 - may two column-split launches of one handle run side by side?  Each must have all its workgroups resident at once, and the
+ * dispatcher deals workgroup id i to XCD i % 8 whatever room that XCD has, so the decision is taken per XCD (csrc/planner.h
+ * coop_side_by_side): side by side only if one of the two can ALWAYS become fully resident whatever the other holds - on every XCD the
+ * workgroups dealt there to the other one (at most one CU each) plus the CUs this one needs (one per workgroup if it owns its CUs,
+ * LstmArgs::coop_own_cu, else cdiv(its workgroups there, per_cu)) are at most cus_per_xcd.  Unknown occupancy (per_cu <= 0) or CU count:
+ * 0.  Launches are described by the workgroups dealt to each of the 8 XCDs.  Host only; returns 1 / 0 (< 0 on a bad argument). */
+int fsnp_debug_coop_side_by_side(const int32_t a_per_xcd[8], int32_t a_own_cu, int32_t a_per_cu, const int32_t b_per_xcd[8],
+                                 int32_t b_own_cu, int32_t b_per_cu, int32_t cus_per_xcd);
+/* The decision that predicate takes in the pipelined loop (fsnp_set_pipeline) of the original FullSubNet: for each sub-band launch a
+ * `batch`-utterance forward (full mode) defers to the side stream, may the NEXT forward's full-band LSTM (lstm_coop_seq, dealt round
+ * robin, never owns its CUs) run beside it?  Records of 9 ints: {chunk index in the plan, planner kind (fsnp_debug_plan_rows), row tiles,
+ * workgroups, most workgroups dealt to one XCD (the chunk owns its CUs; XCD-local placement where it fits, lstm_common.h), full-band
+ * workgroups (0: the VALU kernel runs instead, B <= 4 - chained), most full-band workgroups on one XCD, full-band workgroups per CU,
+ * side by side (1) or chained (0)}.  Returns the number of records (0: nothing is deferred at this batch).
+ * fsnp_debug_fullsubnet_pairing: host only, the default FullSubNet configuration on a chip of num_cus CUs in 8 XCDs whose full-band
+ * kernel holds fb_workgroups_per_cu workgroups per CU at every split width, planned with the built-in cost table or `costs`
+ * (fsnp_debug_plan_rows2's layout, NULL = built-in).  fsnp_debug_pipeline_pairing: what handle h decides - its own plan, CU count and
+ * the full-band kernel's occupancy measured at fsnp_commit_weights (0 records for FullSubNet+ handles).  fsnp_debug_coop_chain_stats:
+ * out[0] / out[1] = launches of h that ran beside / were chained behind a launch of h on another stream since the last reset. */
+int fsnp_debug_fullsubnet_pairing(int32_t batch, int32_t num_cus, int32_t fb_workgroups_per_cu, const double* costs, int32_t* out,
+                                  int32_t max_records);
+int fsnp_debug_pipeline_pairing(const fsnp_handle* h, int32_t batch, int32_t* out, int32_t max_records);
+int fsnp_debug_coop_chain_stats(fsnp_handle* h, int64_t out[2], int32_t reset);
+/* The full-band LSTM of a `batch`-utterance forward of a FullSubNet handle: out = {kernel (0 = lstm_coop_seq, the K split; 1 = lstm_fbv, the
+ * VALU kernel of B <= 4; 2 = lstm_generic, the runtime-sized kernel of full-band hidden sizes other than 512), row tiles (kernel 2:
+ * workgroups), sequences per tile (kernel 2: rows per workgroup, which grows with the batch), hidden units per workgroup (kernel 0)}. */
+int fsnp_debug_fullband_launch(const fsnp_handle* h, int32_t batch, int32_t out[4]);
+
 /* Test hook: pin the handle's cost table (fsnp_get_costs' layout; NULL = the built-in round-1 table) and the number of
  * column-split workgroups the planner may put on a CU (2 only ever applies to the launch shapes whose kernel fits a CU
  * twice - registers, LDS - as measured with hipOccupancyMaxActiveBlocksPerMultiprocessor at commit time); the lazy

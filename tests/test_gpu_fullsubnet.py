@@ -162,6 +162,163 @@ def test_fullsubnet_pipelined_loop_is_bit_identical(batch):
     m.check_errors()
 
 
+FSN_KW = ("look_ahead", "sb_num_neighbors", "fb_num_neighbors", "norm_type", "num_groups_in_drop_band", "fb_output_activate_function",
+          "sb_output_activate_function")
+# 1 ... 16 full-band row tiles (8 / 16 / 32 units per workgroup), exactly full and one-row tiles, sub-band plans with 0 ... 16 full rounds
+RANGE_BATCHES = [5, 8, 17, 31, 33, 48, 63, 64, 65, 96, 97, 128, 160, 255, 256, 257, 320, 511, 512]
+
+
+def _picked_utterances(m, batch, limit=6):
+    """The first and the last utterance, those holding a sub-band chunk boundary (describe_plan: sequences // 257) and both sides of
+    32-row full-band tile boundaries (the last, then the first, then the middle one), at most `limit`."""
+    cand = [0, batch - 1]
+    row = 0
+    for c in m.describe_plan(batch)[:-1]:
+        row += c["sequences"]
+        cand += [(row - 1) // 257, row // 257]
+    bounds = list(range(32, batch, 32))
+    for b in (bounds[-1:] + bounds[:1] + bounds[len(bounds) // 2:len(bounds) // 2 + 1]) if bounds else []:
+        cand += [b - 1, b]
+    out = []
+    for u in cand:
+        if u not in out and len(out) < limit:
+            out.append(u)
+    return sorted(out)
+
+
+@pytest.mark.parametrize("batch", RANGE_BATCHES)
+def test_fullsubnet_batch_range_vs_oracle(batch):
+    """The full-band LSTM (257 -> 512 x 2) on lstm_coop_seq in 32-row tiles across the batch range the model accepts (B = 5 ... 512:
+    1 ... 16 tiles, 256 workgroups at the top) and the sub-band plans those batches get, on 0.3 s clips against the fp32 oracle: the
+    first / last utterance, both sides of full-band tile boundaries and the utterances holding the sub-band chunk boundaries; a second
+    call is bitwise equal; parity-mode rows are a sub-selection of the full rows."""
+    sd = make_state_dict_fullsubnet(11, "harsh")
+    mag = make_inputs(batch, 0.3, 400 + batch)[0]
+    m = _model(dict(FULLSUBNET_MODEL_ARGS), sd, "full")
+    x = _cuda(mag)
+    out = m(x)
+    out2 = m(x)
+    fb = m.fullband_launch(batch)
+    tiles = -(-batch // 32)
+    assert fb == {"kernel": "coop_seq", "tiles": tiles, "rows_per_tile": 32, "units": 8 if tiles <= 4 else 16 if tiles <= 8 else 32}, fb
+    m.check_errors()
+    assert torch.equal(out, out2)
+    pick = _picked_utterances(m, batch)
+    want = fsnp_torch.forward_fullsubnet_full(sd, mag[pick], **{k: FULLSUBNET_MODEL_ARGS[k] for k in FSN_KW}).numpy()
+    err = rel_err(out[pick].cpu().numpy(), want)
+    _record(f"fullsubnet_range_b{batch}_full_vs_oracle", rel=err, utterances=pick, fb_units=fb["units"],
+            plan=[(c["kernel"].split()[0], c["tiles"]) for c in m.describe_plan(batch)])
+    assert err < TOL, (err, pick)
+    m.batch_mode = "parity"
+    par = m(x).cpu().numpy()
+    m.check_errors()
+    full = out.cpu().numpy()
+    n0 = (batch + 1) // 2
+    for r in sorted({0, 1, n0 - 1, n0, batch - 1}):
+        s, p = (2 * r, 0) if r < n0 else (2 * (r - n0) + 1, 1)
+        assert np.abs(par[r] - full[s][:, p:256:2, :]).max() <= 1e-6 * np.abs(full).max(), r
+
+
+@pytest.mark.parametrize("batch,rows_per_group", [(3, 1), (31, 1), (32, 2), (127, 2), (128, 4), (200, 4)])
+def test_fullsubnet_runtime_sized_fullband_across_batches(batch, rows_per_group):
+    """fb_model_hidden_size = 300 (no K-split instantiation): the full-band LSTM runs on the runtime-sized kernel (lstm_generic.hip), whose
+    sequences per workgroup grow with the batch (lstm_generic_rows_per_group: 1 / 2 / 4 from 32 / 128 sequences) - both sides of each step,
+    against the oracle, with the rows per group the handle used read back."""
+    args = dict(FULLSUBNET_MODEL_ARGS, fb_model_hidden_size=300)
+    sd = make_state_dict_fullsubnet(15, "default", fb_hidden=300)
+    mag = make_inputs(batch, 0.3, 600 + batch)[0]
+    m = _model(args, sd, "full")
+    x = _cuda(mag)
+    out = m(x)
+    m.check_errors()
+    fb = m.fullband_launch(batch)
+    assert fb["kernel"] == "generic" and fb["rows_per_tile"] == rows_per_group and fb["tiles"] == -(-batch // rows_per_group), fb
+    assert torch.equal(m(x), out)
+    pick = sorted({0, batch // 2, batch - 1} | ({rows_per_group * (batch // rows_per_group) - 1} if batch >= rows_per_group else set()))
+    want = fsnp_torch.forward_fullsubnet_full(sd, mag[pick], **{k: args[k] for k in FSN_KW}).numpy()
+    err = rel_err(out[pick].cpu().numpy(), want)
+    _record(f"fullsubnet_generic_fb300_b{batch}_full_vs_oracle", rel=err, utterances=pick, rows_per_group=rows_per_group)
+    assert err < TOL, (err, pick)
+
+
+def _pipelined_loop_matches_plain(m, batch, seed):
+    """A back-to-back pipelined loop over three different inputs and a repeat (error_check="deferred") = the plain calls, bit for bit;
+    then one error_check="sync" call.  -> coop_chain_stats() of the pipelined calls (the plain calls leave only launches on the caller's
+    stream behind them)."""
+    m.error_check = "deferred"
+    xs = [_cuda(make_inputs(batch, 0.3, seed + i)[0]) for i in range(3)]
+    plain = [m(x).clone() for x in xs]
+    torch.cuda.synchronize()
+    m.coop_chain_stats(reset=True)
+    m.set_pipeline(True)
+    try:
+        seq = [0, 1, 2, 0]
+        piped = [m(xs[i]) for i in seq]
+        m.flush()
+        torch.cuda.synchronize()
+        m.poll_errors()
+        for k, (i, y) in enumerate(zip(seq, piped)):
+            assert torch.equal(y, plain[i]), (batch, k)
+        m.error_check = "sync"
+        assert torch.equal(m(xs[1]), plain[1]), batch
+        m.check_errors()
+        return m.coop_chain_stats()
+    finally:
+        m.set_pipeline(False)
+        m.error_check = "sync"
+
+
+def _pick_by_signature(batches, signature, limit=24):
+    groups = {}
+    for b in batches:
+        groups.setdefault(signature(b), []).append(b)
+    chosen = sorted(v[0] for v in groups.values())
+    if len(chosen) > limit:
+        chosen = [chosen[round(i * (len(chosen) - 1) / (limit - 1))] for i in range(limit)]
+    return chosen, len(groups)
+
+
+def test_fullsubnet_pipelined_loop_at_every_plan_shape():
+    """fsnp_set_pipeline on the original FullSubNet at one batch per plan signature of the range above (sub-band kernels and tiles, what is
+    deferred, the full-band launch, and whether that launch runs beside the deferred chunk - csrc/planner.h coop_side_by_side, per XCD):
+    the handle's decision equals the host predicate fed this device's CU count and the full-band kernel's measured occupancy
+    (fsnp_debug_fullsubnet_pairing), the launches really ran beside / were chained as decided, and every output is the plain call's."""
+    import ctypes
+    from fullsubnet_plus_amd import _lib
+    sd = make_state_dict_fullsubnet(0, "default")
+    m = _model(FULLSUBNET_MODEL_ARGS, sd, "full")
+    m(_cuda(make_inputs(1, 0.3, 799)[0]))                 # (the handle is made by the first forward)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    lib = _lib.load()
+
+    def signature(b):
+        fb = m.fullband_launch(b)
+        return (tuple((c["kernel"], c["tiles"], c["deferred_when_pipelined"]) for c in m.describe_plan(b)),
+                (fb["kernel"], fb["tiles"], fb["units"]), tuple(r["side_by_side"] for r in m.pipeline_pairing(b)))
+
+    batches = [1, 2, 4, 16, 32] + RANGE_BATCHES
+    for b in batches:                                  # the handle's decision = the host predicate's, for every batch of the range
+        dev = m.pipeline_pairing(b)
+        per_cu = {r["fb_per_cu"] for r in dev if r["fb_workgroups"]} or {1}
+        assert len(per_cu) == 1, dev
+        buf = (ctypes.c_int32 * (9 * 16))()
+        n = lib.fsnp_debug_fullsubnet_pairing(b, cus, per_cu.pop(), None, buf, 16)
+        assert n == len(dev) and [list(r.values()) for r in dev] == [list(buf[9 * i:9 * i + 9]) for i in range(n)], (b, dev)
+    chosen, nsig = _pick_by_signature(batches, signature)
+    _record("fullsubnet_pipelined_plan_shapes", batches=chosen, signatures=nsig,
+            pairing={b: m.pipeline_pairing(b) for b in chosen})
+    print("pipelined FullSubNet batches:", chosen)
+    for b in chosen:
+        beside, chained = _pipelined_loop_matches_plain(m, b, 800 + b)
+        pairs = [r for r in m.pipeline_pairing(b) if r["fb_workgroups"]]
+        if any(r["side_by_side"] for r in pairs):
+            assert beside > 0 and chained == 0, (b, beside, chained, pairs)
+        else:
+            assert beside == 0, (b, beside, chained, pairs)
+            if pairs:
+                assert chained > 0, (b, beside, chained, pairs)
+
+
 def test_fullsubnet_enhance_epilogue():
     sd = make_state_dict_fullsubnet(12, "default")
     mag, real, imag = make_inputs(2, 1.0, 32)

@@ -1508,6 +1508,44 @@ def test_pipelined_mode_is_bit_identical(batch):
     assert torch.equal(m(*batches[1]), plain[1])
 
 
+def test_pipelined_loop_at_every_plan_shape():
+    """fsnp_set_pipeline at one batch per plan signature of B = 1 ... 128 (sub-band kernels, their tile counts, which launches are deferred
+    to the side stream): a back-to-back loop over three different inputs and a repeat under error_check="deferred" is the plain call, bit
+    for bit, after flush / poll_errors, and so is a final error_check="sync" call."""
+    sd = make_state_dict(2, "default")
+    m = _model(DEFAULT_MODEL_ARGS, sd, "full")
+    m(*_cuda(make_inputs(1, 0.3, 1199)))                   # (the handle is made by the first forward)
+    sig = {}
+    for b in range(1, 129):
+        key = tuple((c["kernel"], c["tiles"], c["deferred_when_pipelined"]) for c in m.describe_plan(b))
+        sig.setdefault(key, []).append(b)
+    chosen = sorted(v[0] for v in sig.values())
+    if len(chosen) > 24:
+        chosen = [chosen[round(i * (len(chosen) - 1) / 23)] for i in range(24)]
+    _record("pipelined_plan_shapes", batches=chosen, signatures=len(sig))
+    print("pipelined FullSubNet+ batches:", chosen)
+    for b in chosen:
+        m.error_check = "deferred"
+        xs = [_cuda(make_inputs(b, 0.3, 1200 + 7 * b + i)) for i in range(3)]
+        plain = [m(*x).clone() for x in xs]
+        torch.cuda.synchronize()
+        m.set_pipeline(True)
+        try:
+            seq = [0, 1, 2, 0]
+            piped = [m(*xs[i]) for i in seq]
+            m.flush()
+            torch.cuda.synchronize()
+            m.poll_errors()
+            for k, (i, y) in enumerate(zip(seq, piped)):
+                assert torch.equal(y, plain[i]), (b, k)
+            m.error_check = "sync"
+            assert torch.equal(m(*xs[1]), plain[1]), b
+            m.check_errors()
+        finally:
+            m.set_pipeline(False)
+            m.error_check = "sync"
+
+
 @pytest.mark.parametrize("batch,mode,two_per_cu", [(1, "full", False), (3, "full", False), (8, "full", False), (16, "full", False),
                                                    (12, "parity", False), (40, "full", True), (5, "full", False)])
 def test_pipelined_small_batches_run_whole_on_the_side_stream(batch, mode, two_per_cu):

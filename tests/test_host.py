@@ -1184,6 +1184,86 @@ def test_planner_follows_the_cost_table_and_two_workgroups_per_cu():
     assert all(c["kind"] != 9 for rows in (514, 1285, 2056) for c in plan(rows, 1, cheap_w, gru=1))          # LSTM only
 
 
+def _pairing(batch, fb_per_cu, costs=None, cus=256):
+    import ctypes as ct
+    lib = _lib.load()
+    buf = (ct.c_int32 * (9 * 16))()
+    arr = (ct.c_double * _lib.NUM_COSTS)(*(list(costs) + [1e9] * (_lib.NUM_COSTS - len(costs)))) if costs else None
+    n = lib.fsnp_debug_fullsubnet_pairing(batch, cus, fb_per_cu, arr, buf, 16)
+    assert n >= 0, lib.fsnp_last_error()
+    keys = ("chunk", "kind", "tiles", "workgroups", "max_per_xcd", "fb_workgroups", "fb_max_per_xcd", "fb_per_cu", "side_by_side")
+    return [dict(zip(keys, buf[9 * i:9 * i + 9])) for i in range(n)]
+
+
+def _side_by_side(a, a_own, a_per_cu, b, b_own, b_per_cu, cpx=32):
+    import ctypes as ct
+    A, B = (ct.c_int32 * 8)(*a), (ct.c_int32 * 8)(*b)
+    r = _lib.load().fsnp_debug_coop_side_by_side(ct.byref(A), a_own, a_per_cu, ct.byref(B), b_own, b_per_cu, cpx)
+    assert r in (0, 1), _lib.last_error()
+    return bool(r)
+
+
+def test_side_by_side_rule_counts_per_xcd():
+    """csrc/planner.h coop_side_by_side: two column-split launches may run side by side only if one of them can always become fully
+    resident whatever the other holds, counted on every XCD (the dispatcher deals workgroup i to XCD i % 8, not to where there is room)."""
+    rr = lambda n: [n // 8 + (x < n % 8) for x in range(8)]                    # round robin
+    assert _side_by_side([24, 24] + [0] * 6, 1, 1, rr(64), 0, 1)               # 24 owned + 8 on XCD0 / XCD1: exactly full
+    assert not _side_by_side([24, 24] + [0] * 6, 1, 1, rr(72), 0, 1)           # one workgroup more on XCD0: 24 + 9 > 32
+    assert not _side_by_side([24, 24] + [0] * 6, 1, 1, rr(128), 0, 1)          # 24 + 16 > 32 ...
+    assert _side_by_side([24, 24] + [0] * 6, 1, 1, rr(128), 0, 2)              # ... unless two full-band workgroups share a CU: 24 + 8
+    assert not _side_by_side([24, 24] + [0] * 6, 1, 1, rr(136), 0, 2)          # 24 + cdiv(17, 2) > 32
+    assert not _side_by_side([24, 24] + [0] * 6, 1, 1, rr(128), 1, 2)          # a launch that owns its CUs takes one per workgroup
+    assert not _side_by_side([24, 24] + [0] * 6, 1, 1, rr(64), 0, 0)           # occupancy unknown: chained
+    assert not _side_by_side([0] * 8, 1, 1, rr(64), 0, 1, cpx=0)               # CU count unknown: chained
+    assert _side_by_side(rr(128), 0, 1, [24, 24] + [0] * 6, 1, 1) == _side_by_side([24, 24] + [0] * 6, 1, 1, rr(128), 0, 1)   # symmetric
+    # either launch may be the one sure to become resident, but the same one on every XCD (a launch runs only once ALL its workgroups are in)
+    assert _side_by_side([30, 8] + [0] * 6, 0, 2, [8, 8] + [0] * 6, 0, 2, cpx=24)             # the first one: 8 + 15 / 8 + 4
+    assert not _side_by_side([30, 8] + [0] * 6, 0, 2, [8, 30] + [0] * 6, 0, 2, cpx=24)        # the first on XCD0 only, the second on XCD1 only
+    assert _side_by_side([16] * 8, 1, 1, [16] * 8, 1, 1) and not _side_by_side([16] * 8, 1, 1, [17] + [16] * 7, 1, 1)
+
+
+def test_fullsubnet_pipelined_pairs_fit_every_xcd():
+    """The pipelined loop of the original FullSubNet (fsnp_set_pipeline) runs the deferred remainder chunk of forward i (side stream, owns
+    its CUs) and the full-band LSTM of forward i + 1 (lstm_coop_seq: cdiv(B, 32) row tiles x 64 / 32 / 16 workgroups at 8 / 16 / 32
+    units, dealt round robin) side by side only if they fit per XCD (256 CUs = 8 XCDs x 32).  With the built-in cost table:
+      B = 32: 1 K-split tile (48 workgroups, 6 per XCD) + 64 (8 per XCD)        -> 14 <= 32: side by side (the 28.5 ms serving loop)
+      B = 64: 2 tiles (96, 12 per XCD) + 128 (16 per XCD)                     -> 28 <= 32: side by side
+      B = 96: 3 tiles (144, 18 per XCD) + 192 (24 per XCD)                    -> 42 at one full-band workgroup per CU: chained; 30 at two:
+                                                                                 side by side (the whole-chip rule chained it: 336 > 248)
+      B = 128: 4 tiles (192, 24) + 256 (32)                                   -> chained
+      B = 256, 511: 8 half-tile ping-pong tiles (24 per XCD, XCD-local) + 256 -> chained;  B = 512: 16 wave-owned tiles (24 per XCD) + 256
+    The case the round-6 whole-chip rule (sum of workgroups <= 256 - 8) got wrong: a plan whose B = 64 remainder runs on the half-tile
+    ping-pong kernel (2 row tiles x 24 workgroups, one XCD-local tile on each of XCD0 / XCD1 - what a measured cost table in which that
+    kernel is cheap plans) beside the 2-tile full-band launch: 48 + 128 = 176 <= 248 was accepted, but XCD0 needs 24 owned CUs + 16 for
+    the full-band workgroups at one per CU = 40 > 32 CUs - both launches can be left partly resident, each spinning on workgroups the other
+    keeps out, until the bounded wait aborts the forward (code 5).  At B = 32 the same kernel's one tile (24) + 8 is exactly full: kept."""
+    old_rule = lambda r: r["workgroups"] + r["fb_workgroups"] <= 256 - 8
+    want = {32: (1, 1), 64: (1, 1), 96: (0, 1), 128: (0, 0), 256: (0, 0), 512: (0, 0)}
+    for batch, sides in want.items():
+        for fb_per_cu, side in zip((1, 2), sides):
+            recs = _pairing(batch, fb_per_cu)
+            assert len(recs) == 1, (batch, recs)                                  # one deferred remainder chunk
+            r = recs[0]
+            assert r["chunk"] == 1 and r["fb_per_cu"] == fb_per_cu and r["side_by_side"] == side, (batch, fb_per_cu, r)
+            assert r["fb_workgroups"] == min(batch // 32, 4) * 64 if batch <= 128 else r["fb_workgroups"] == 256
+            assert r["fb_max_per_xcd"] == -(-r["fb_workgroups"] // 8)
+            fits = r["max_per_xcd"] + -(-r["fb_max_per_xcd"] // fb_per_cu) <= 32
+            assert bool(side) == fits, (batch, r)
+            assert old_rule(r) or not side or (batch, fb_per_cu) == (96, 2), r   # (B = 96 at two per CU fits per XCD: 18 + 12)
+    assert [(r["kind"], r["tiles"], r["max_per_xcd"]) for r in (_pairing(b, 1)[0] for b in (32, 64, 96, 128, 256, 511, 512))] == \
+        [(1, 1, 6), (1, 2, 12), (1, 3, 18), (1, 4, 24), (8, 8, 24), (8, 8, 24), (9, 16, 24)]
+    assert _pairing(33, 1) == [] and _pairing(40, 1) == [] and _pairing(8, 1) == []   # remainders that fill the chip are not deferred
+    assert all(r["fb_workgroups"] == 0 and not r["side_by_side"] for b in (1, 2) for r in _pairing(b, 1))   # B <= 4: VALU kernel, chained
+    # the round-6 advice case: half-tile ping-pong remainders (a cost table in which that kernel is cheap)
+    cheap_hp = [100] * 8 + [760, 950, 1510, 1900, 208, 0.11, 100, 100, 100, 100, 1000, 9, 11]
+    r32, r64 = _pairing(32, 1, cheap_hp), _pairing(64, 1, cheap_hp)
+    assert [(r["kind"], r["tiles"], r["workgroups"], r["max_per_xcd"]) for r in r32 + r64] == [(8, 1, 24, 24), (8, 2, 48, 24)]
+    assert r32[0]["side_by_side"] == 1 and r32[0]["max_per_xcd"] + r32[0]["fb_max_per_xcd"] == 32          # exactly full
+    assert old_rule(r64[0]) and r64[0]["workgroups"] + r64[0]["fb_workgroups"] == 176                      # the old rule let it through,
+    assert r64[0]["max_per_xcd"] + r64[0]["fb_max_per_xcd"] == 40 and r64[0]["side_by_side"] == 0          # but XCD0 needs 40 of 32 CUs
+    assert _pairing(64, 2, cheap_hp)[0]["side_by_side"] == 1                                               # (24 + 8 at two per CU)
+
+
 def test_oracle_is_only_reachable_from_the_allowed_places():
     """The oracle is test infrastructure: the product package never imports it, bench.py only inside its cpu_baseline
     leg, __graft_entry__ only inside build() (import check of the checker) and smoke()."""
