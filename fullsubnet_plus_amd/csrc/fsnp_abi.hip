@@ -87,13 +87,9 @@ int take_device_errors(fsnp_handle* h, const char* where) {
 // what the planner needs to know of a handle
 static PlannerCtx pctx(const fsnp_handle* h) {
     PlannerCtx c;
+    static_cast<PlannerOptions&>(c) = h->planner;
     c.H = h->H; c.NIN = h->NIN; c.num_cus = h->num_cus; c.num_cus_real = h->num_cus_real;
-    c.gru = h->gru != 0; c.sb_tcn = h->sb_tcn != 0; c.generic_sb = h->generic_sb; c.rowtile_ok = h->rowtile_ok; c.lstm16_ok = h->lstm16_ok;
-    c.hp_ok = h->hp_ok; c.coop_hp = h->coop_hp; c.coopw_ok = h->coopw_ok; c.coop_w = h->coop_w; c.ih_bf16 = h->ih_bf16; c.lstm_coop = h->lstm_coop; c.coop_occ = h->coop_occ;
-    for (int i = 0; i < 4; ++i) c.occ_ksplit[i] = h->occ_ksplit[i];
-    for (int i = 0; i < 2; ++i) c.occ_coopn[i] = h->occ_coopn[i];
-    c.pipeline = h->pipeline; c.composite_gain = h->composite_gain;
-    c.cost = h->cost;
+    c.gru = h->gru != 0; c.sb_tcn = h->sb_tcn != 0; c.generic_sb = h->generic_sb; c.ih_bf16 = h->ih_bf16;
     return c;
 }
 
@@ -269,7 +265,6 @@ static void launch_coop_chained(int dev, hipStream_t s, F launch, const void* ow
 }
 
 // The planner itself (cost table, launch shapes, shortest path over tile counts) is host-only code: planner.h / planner.cpp.
-static PlannerCtx pctx(const fsnp_handle* h);
 // gather_bytes: the furthest byte a recurrent kernel's input gather reaches from its base pointer.  The half-tile ping-pong kernel
 // (lstm_hp.hip) addresses its input through ONE buffer descriptor with 32-bit BYTE offsets (2 GiB), the other kernels with 32-bit
 // FLOAT offsets from a 64-bit pointer (8 GiB): beyond 2 GiB the planner is told not to use it (its loads would
@@ -301,13 +296,12 @@ static void launch_sb_lstm(const fsnp_handle* h, const SbPlan& plan, const LstmA
         ca.rows = a.rows + c.slot0;
         ca.num_rows = c.nrows; ca.num_tiles = c.num_tiles; ca.ex = c.ex;
         if (a.md_row) ca.md_row = a.md_row + (size_t)c.slot0 * a.Tp;
-        if (c.kind == 0) {
-            if (h->gru) launch_gru(h->lw, ca, s);
-            else { ca.clk = h->d_clk; launch_lstm(h->lw, ca, s); }
-            continue;
+        switch (c.kind) {
+        case SbKind::RowTile: if (h->gru) launch_gru(h->lw, ca, s); else { ca.clk = h->d_clk; launch_lstm(h->lw, ca, s); } continue;
+        case SbKind::HalfTile: launch_lstm16(h->lw, ca, s); continue;
+        case SbKind::Generic: ca.coop_rows_per_group = c.rpg; launch_lstm_generic(h->lw, ca, false, s); continue;
+        default: break;           // column split: below
         }
-        if (c.kind == 4) { launch_lstm16(h->lw, ca, s); continue; }
-        if (c.kind == 7) { ca.coop_rows_per_group = c.rpg; launch_lstm_generic(h->lw, ca, false, s); continue; }
         ca.coop_hx = hx + (size_t)c.coop_tile0 * hx_floats_per_tile;
         ca.coop_bar = bar + (size_t)c.coop_tile0 * kCoopCounterStride;
         ca.coop_bar_stride = kCoopCounterStride;
@@ -326,10 +320,12 @@ static void launch_sb_lstm(const fsnp_handle* h, const SbPlan& plan, const LstmA
         ca.coop_xcd = chunk_coop_xcd(pctx(h), c);
         const CoopFootprint fp = sb_chunk_footprint(h, c, ca.coop_own_cu > 0);
         launch_coop_chained(h->device, s, [&] {
-            if (c.kind == 8) { if (h->lw.hp_wave && lstm_hpw_available(h->lw)) launch_lstm_hpw(h->lw, ca, s); else launch_lstm_hp(h->lw, ca, s); }
-            else if (c.kind == 9) launch_lstm_coopw(h->lw, ca, s);
-            else if (c.kind == 1) launch_lstm_coop(h->lw, ca, s);
-            else launch_lstm_coopn(h->lw, ca, s);
+            switch (c.kind) {
+            case SbKind::HalfTilePingPong: (h->lw.hp_wave && lstm_hpw_available(h->lw) ? launch_lstm_hpw : launch_lstm_hp)(h->lw, ca, s); break;
+            case SbKind::WaveOwned: launch_lstm_coopw(h->lw, ca, s); break;
+            case SbKind::KSplit: launch_lstm_coop(h->lw, ca, s); break;
+            default: launch_lstm_coopn(h->lw, ca, s); break;
+            }
         }, h, &fp, h->num_cus_real / kNumXcds, h->coop_chain_stats);
     }
     if (after_first && last_chunk == nchunks) (void)hipEventRecord(after_first, s);
@@ -384,10 +380,9 @@ static int pipeline_pairing(const PlannerCtx& c, bool defer_small, int F, int CH
     for (int i = first; i < (int)plan.chunks.size() && n < max_records; ++i, ++n) {
         const SbChunk& k = plan.chunks[i];
         const CoopFootprint f = chunk_footprint(c, k, chunk_workgroups(c, k) <= c.num_cus_real, 1);    // (launch_sb_lstm: coop_own_cu)
-        int f_max = 0;
-        for (int x = 0; x < kNumXcds; ++x) f_max = std::max(f_max, f.per_xcd[x]);
+        const int f_max = *std::max_element(f.per_xcd, f.per_xcd + kNumXcds);
         int32_t* o = out + 9 * n;
-        o[0] = i; o[1] = k.kind; o[2] = k.num_tiles; o[3] = chunk_workgroups(c, k); o[4] = f_max;
+        o[0] = i; o[1] = (int)k.kind; o[2] = k.num_tiles; o[3] = chunk_workgroups(c, k); o[4] = f_max;
         o[5] = fb_wgs; o[6] = fb_max; o[7] = fb.per_cu; o[8] = fb_wgs > 0 && coop_side_by_side(f, fb, cpx) ? 1 : 0;
     }
     return n;
@@ -563,11 +558,11 @@ static std::mutex g_cal_mu;
 static std::map<CalKey, CostTable> g_cal_cache;
 
 static int calibrate_costs(fsnp_handle* h, bool adopt = true, CostTable* measured = nullptr) {
-    if (adopt && (h->cost.calibrated || !h->calibrate)) return 0;
+    if (adopt && (h->planner.cost.calibrated || !h->calibrate)) return 0;
     if (h->sb_tcn || h->generic_sb || !h->committed) return 0;
-    int occ_sig = h->coop_occ;
-    for (int i = 0; i < 4; ++i) occ_sig = occ_sig * 4 + h->occ_ksplit[i];
-    for (int i = 0; i < 2; ++i) occ_sig = occ_sig * 4 + h->occ_coopn[i];
+    int occ_sig = h->planner.coop_occ;
+    for (int i = 0; i < 4; ++i) occ_sig = occ_sig * 4 + h->planner.occ_ksplit[i];
+    for (int i = 0; i < 2; ++i) occ_sig = occ_sig * 4 + h->planner.occ_coopn[i];
     occ_sig = occ_sig * 2 + h->coop_skew;
     const CalKey key{h->device, h->H, h->KX, h->gru, occ_sig, h->num_cus_real};
     {
@@ -575,14 +570,14 @@ static int calibrate_costs(fsnp_handle* h, bool adopt = true, CostTable* measure
         auto it = g_cal_cache.find(key);
         if (it != g_cal_cache.end()) {
             if (measured) *measured = it->second;
-            if (adopt) h->cost = it->second;
+            if (adopt) h->planner.cost = it->second;
             return 0;
         }
     }
     // the timing launches overwrite the handle's workspace from a private stream: nothing of an earlier forward may still be
     // in flight on the caller's streams (ensure_workspace only synchronises when it grows)
     FSNP_HIP_CHECK(hipDeviceSynchronize());
-    const int S3 = h->H / 128, occ = h->coop_occ >= 2 ? 2 : 1;
+    const int S3 = h->H / 128, occ = h->planner.coop_occ >= 2 ? 2 : 1;
     const int steps_a = 8, steps_b = 40;
     const int max_tiles = std::max(h->num_cus_real, (h->num_cus_real * occ / S3) * 2);
     const size_t x_floats = (size_t)max_tiles * 32 * steps_b * h->NIN, o_floats = (size_t)max_tiles * 32 * 2 * steps_b;
@@ -602,11 +597,10 @@ static int calibrate_costs(fsnp_handle* h, bool adopt = true, CostTable* measure
     FSNP_CAL_CHECK(hipEventCreate(&e0));
     FSNP_CAL_CHECK(hipEventCreate(&e1));
     FSNP_CAL_CHECK(hipMemsetAsync(scratch, 0, (x_floats + o_floats) * 4, cs));
-    const bool had_pipeline = h->pipeline != 0;
-    CostTable t = h->cost;
-    if (h->rowtile_ok) {            // ramp the clocks: short launches on an idle chip run at a lower power state than a forward does
+    CostTable t = h->planner.cost;
+    if (h->planner.rowtile_ok) {            // ramp the clocks: short launches on an idle chip run at a lower power state than a forward does
         SbPlan warm;
-        warm.chunks = {SbChunk{0, 0, h->num_cus_real * 32, h->num_cus_real, 0, 32, 0, 0, 0, 0, 0}};
+        warm.chunks = {row_tile_chunk(0, h->num_cus_real * 32, h->num_cus_real)};
         warm.total_slots = h->num_cus_real * 32;
         for (int k = 0; k < 2; ++k)         // (the scratch buffers hold steps_b steps of max_tiles tiles: stay inside them)
             (void)run_dense_plan(h, warm, scratch, scratch + x_floats, h->num_cus_real * 32, steps_b, cs);
@@ -615,7 +609,7 @@ static int calibrate_costs(fsnp_handle* h, bool adopt = true, CostTable* measure
     auto time_shape = [&](SbChunk c) -> double {
         c.row0 = 0; c.nrows = c.num_tiles * c.rps; c.slot0 = 0; c.coop_tile0 = 0;
         SbPlan plan;
-        plan.chunks = {c}; plan.total_slots = c.num_tiles * c.rps; plan.coop_tiles = (c.kind == 1 || c.kind == 2 || c.kind == 8 || c.kind == 9) ? c.num_tiles : 0;
+        plan.chunks = {c}; plan.total_slots = c.num_tiles * c.rps; plan.coop_tiles = is_column_split(c.kind) ? c.num_tiles : 0;
         double ms[2] = {0, 0};
         for (int k = 0; k < 2; ++k) {
             const int steps = k == 0 ? steps_a : steps_b;
@@ -632,46 +626,45 @@ static int calibrate_costs(fsnp_handle* h, bool adopt = true, CostTable* measure
         }
         return (ms[1] - ms[0]) * 1000.0 / (steps_b - steps_a);
     };
-    (void)had_pipeline;
     for (int o = 0; o < occ && rc == 0; ++o) {
         const int slots = h->num_cus_real * (o + 1);
         for (int ui = 0; ui < 4 && rc == 0; ++ui) {
             const int u = 8 << ui, S = h->H / u;
             int tiles = slots / S;
-            if (o == 1 && (tiles * S <= h->num_cus_real || h->occ_ksplit[ui] < 2)) continue;   // never planned two per CU
+            if (o == 1 && (tiles * S <= h->num_cus_real || h->planner.occ_ksplit[ui] < 2)) continue;   // never planned two per CU
             if (tiles <= 0) continue;
-            const double us = time_shape(SbChunk{1, 0, 0, tiles, 0, 32, u, 0, 0, 0, 0});
+            const double us = time_shape(column_chunk(SbKind::KSplit, 0, 0, tiles, u, 0));
             if (us < 0) rc = 4; else t.ksplit[ui][o] = us;
             if (o == 0 && rc == 0) {
-                const double u1 = tiles > 1 ? time_shape(SbChunk{1, 0, 0, 1, 0, 32, u, 0, 0, 0, 0}) : us;
+                const double u1 = tiles > 1 ? time_shape(column_chunk(SbKind::KSplit, 0, 0, 1, u, 0)) : us;
                 if (u1 < 0) rc = 4; else t.ksplit1[ui] = u1 < us ? u1 : us;
             }
         }
         for (int rpg = 1; rpg <= 2 && rc == 0; ++rpg) {
             const int groups = slots / S3;
-            if (groups <= 0 || (o == 1 && h->occ_coopn[rpg - 1] < 2)) continue;
-            const double us = time_shape(SbChunk{2, 0, 0, groups * rpg, 0, 32, 0, groups, rpg, 0, 0});
+            if (groups <= 0 || (o == 1 && h->planner.occ_coopn[rpg - 1] < 2)) continue;
+            const double us = time_shape(column_chunk(SbKind::ThreeWay, 0, 0, groups * rpg, 0, rpg));
             if (us < 0) rc = 4; else t.coopn[rpg - 1][o] = us;
         }
     }
-    if (rc == 0 && h->rowtile_ok) {
-        const double us0 = time_shape(SbChunk{0, 0, 0, h->num_cus_real, 0, 32, 0, 0, 0, 0, 0});
+    if (rc == 0 && h->planner.rowtile_ok) {
+        const double us0 = time_shape(row_tile_chunk(0, 0, h->num_cus_real));
         if (us0 < 0) rc = 4;
         else t.rowtile = us0;           // the VALU-row surcharge keeps its measured ratio (0.11 per row)
     }
-    if (rc == 0 && h->hp_ok && h->num_cus_real / (h->H / 16) > 0) {
+    if (rc == 0 && h->planner.hp_ok && h->num_cus_real / (h->H / 16) > 0) {
         const int cap = h->num_cus_real / (h->H / 16);
-        const double u1 = time_shape(SbChunk{8, 0, 0, 1, 0, 32, 16, 0, 0, 0, 0}), uf = time_shape(SbChunk{8, 0, 0, cap, 0, 32, 16, 0, 0, 0, 0});
+        const double u1 = time_shape(column_chunk(SbKind::HalfTilePingPong, 0, 0, 1, 16, 0)), uf = time_shape(column_chunk(SbKind::HalfTilePingPong, 0, 0, cap, 16, 0));
         if (u1 < 0 || uf < 0) rc = 4; else { t.hp[0] = u1; t.hp[1] = uf; }
     }
-    for (int nt = 1; nt <= 3 && rc == 0 && h->coopw_ok; ++nt) {
+    for (int nt = 1; nt <= 3 && rc == 0 && h->planner.coopw_ok; ++nt) {
         const int u = 32 * nt, cap = h->num_cus_real / (h->H / u);
         if (cap <= 0) continue;
-        const double u1 = time_shape(SbChunk{9, 0, 0, 1, 0, 32, u, 0, 0, 0, 0}), uf = cap > 1 ? time_shape(SbChunk{9, 0, 0, cap, 0, 32, u, 0, 0, 0, 0}) : u1;
+        const double u1 = time_shape(column_chunk(SbKind::WaveOwned, 0, 0, 1, u, 0)), uf = cap > 1 ? time_shape(column_chunk(SbKind::WaveOwned, 0, 0, cap, u, 0)) : u1;
         if (u1 < 0 || uf < 0) rc = 4; else { t.coopw[nt - 1][0] = u1; t.coopw[nt - 1][1] = uf; }
     }
-    if (rc == 0 && h->lstm16_ok) {
-        const double us16 = time_shape(SbChunk{4, 0, 0, h->num_cus_real, 0, 16, 0, 0, 0, 0, 0});
+    if (rc == 0 && h->planner.lstm16_ok) {
+        const double us16 = time_shape(half_tile_chunk(0, 0, h->num_cus_real));
         if (us16 < 0) rc = 4; else t.rowtile16 = us16;
     }
     cleanup();
@@ -681,11 +674,11 @@ static int calibrate_costs(fsnp_handle* h, bool adopt = true, CostTable* measure
         // a calibration launch gave up (its workgroups were not all resident): never plan two workgroups per CU
         *reinterpret_cast<volatile unsigned*>(h->d_err) &= ~kErrTimeout;
         t = default_costs();
-        h->coop_occ = 1;
+        h->planner.coop_occ = 1;
     }
     t.calibrated = 1;
     if (measured) *measured = t;
-    if (adopt) h->cost = t;
+    if (adopt) h->planner.cost = t;
     std::lock_guard<std::mutex> lk(g_cal_mu);
     g_cal_cache[key] = t;
     return 0;
@@ -713,7 +706,7 @@ __global__ __launch_bounds__(256) void verify_compare_kernel(const float* __rest
     }
 }
 static bool plan_has_exchange(const SbPlan& plan) {
-    for (const SbChunk& c : plan.chunks) if (c.kind == 1 || c.kind == 2 || c.kind == 8 || c.kind == 9) return true;
+    for (const SbChunk& c : plan.chunks) if (is_column_split(c.kind)) return true;
     return false;
 }
 // `a` = the arguments of the forward's own sub-band launches (its rows / md_row belong to `plan`); out_elems = floats of the mask tensor
@@ -733,7 +726,7 @@ static int verify_pass(fsnp_handle* h, const SbPlan& plan, const Dims& d, int mo
         if (run_n == 0) return;
         const SbPlan one = plan_sb(pc, run_n);
         for (SbChunk k : one.chunks) {
-            if (k.kind != 0 && k.kind != 4) { bad = true; return; }
+            if (k.kind != SbKind::RowTile && k.kind != SbKind::HalfTile) { bad = true; return; }
             k.row0 += run0; k.slot0 = vp.total_slots; k.coop_tile0 = 0;
             vp.total_slots += k.num_tiles * k.rps;
             vp.chunks.push_back(k);
@@ -741,7 +734,7 @@ static int verify_pass(fsnp_handle* h, const SbPlan& plan, const Dims& d, int mo
         run_n = 0;
     };
     for (const SbChunk& c : plan.chunks) {
-        const bool exch = c.kind == 1 || c.kind == 2 || c.kind == 8 || c.kind == 9;
+        const bool exch = is_column_split(c.kind);
         if (exch && run_n > 0 && c.row0 == run0 + run_n) { run_n += c.nrows; continue; }
         flush();
         if (exch) { run0 = c.row0; run_n = c.nrows; }
@@ -820,16 +813,13 @@ __global__ __launch_bounds__(256) void vs_compare_kernel(const float* __restrict
 // 252-workgroup launches put 32 on some XCDs - the 32nd waited for the sample to end and the launch (all of whose workgroups must be
 // resident) with it: +7.7 ms per sampled forward (profiles/r06_verify_sample.md).  Such plans (B = 3, B = 8) are not sampled.
 static bool plan_can_be_sampled(const fsnp_handle* h, const SbPlan& plan) {
-    if (plan.chunks.empty() || !h->lstm16_ok || h->num_cus_real % 8 != 0) return false;
+    if (plan.chunks.empty() || !h->planner.lstm16_ok || h->num_cus_real % 8 != 0) return false;
     const int cpx = h->num_cus_real / 8;
+    const PlannerCtx pc = pctx(h);
     for (const SbChunk& c : plan.chunks) {
-        const bool exch = c.kind == 1 || c.kind == 2 || c.kind == 8 || c.kind == 9;
-        if (!exch || c.rps != 32) return false;
-        const int S = c.kind == 8 ? h->H / 16 : (c.kind == 1 || c.kind == 9) ? h->H / c.units : h->H / 128;
-        const int T = c.kind == 2 ? c.groups : c.num_tiles;
-        const int local = xcd_local_blocks_per_xcd(S, T, cpx);
-        const int per_xcd = local <= cpx ? local : cdiv(T * S, 8);       // (launch_sb_lstm: XCD-local placement where it fits, else round robin)
-        if (per_xcd > cpx - 1) return false;
+        if (!is_column_split(c.kind) || c.rps != 32) return false;
+        const CoopFootprint f = chunk_footprint(pc, c, true, 1);         // (launch_sb_lstm: XCD-local placement where it fits, else round robin)
+        if (*std::max_element(f.per_xcd, f.per_xcd + kNumXcds) > cpx - 1) return false;
     }
     return true;
 }
@@ -978,18 +968,20 @@ int fsnp_create(const fsnp_config* cfg, fsnp_handle** out) {
     }
     h->model = cfg->model;
     h->gru = cfg->sequence_model == FSNP_SEQ_GRU;
-    // one-tile-per-CU kernels: LSTM lstm.hip (H = 384, and 256 without VALU rows), GRU lstm_gru.hip (384); other sizes run on
-    // the column-split kernels only
-    h->rowtile_ok = !generic_sb && (cfg->sb_hidden == 384 || (cfg->sb_hidden == 256 && !h->gru));
     {
-        const char* e16 = getenv("FSNP_LSTM16");           // 0 = never plan the half-tile kernel
-        h->lstm16_ok = !(e16 && e16[0] == '0') && !generic_sb && !h->gru && cfg->sequence_model == FSNP_SEQ_LSTM && cfg->sb_hidden == 384 && nin <= 40;
+        auto env_is = [](const char* e, char c) { return e && e[0] == c; };
+        PlannerSwitches sw;                                    // each: "=0" never plans that kernel; FSNP_COOP_OCC=1: one workgroup per CU
+        sw.lstm16 = !env_is(getenv("FSNP_LSTM16"), '0');       // half tiles (lstm16.hip)
+        sw.lstm_coop = env_is(getenv("FSNP_LSTM_COOP"), '0') ? 0 : 1;   // column split (where a row-tile kernel exists)
+        sw.coop_hp = env_is(getenv("FSNP_COOP_HP"), '0') ? 0 : 1;       // half-tile ping-pong (else: wherever the cost table says it pays)
+        sw.coop_w = env_is(getenv("FSNP_COOP_W"), '0') ? 0 : 1;         // wave-owned column split (lstm_coopw.hip)
+        sw.coop_occ = env_is(getenv("FSNP_COOP_OCC"), '1') ? 1 : 2;     // (2 is checked against the kernels' occupancy at commit time)
+        h->planner = planner_options(cfg->sequence_model, cfg->sb_hidden, nin, generic_sb, sw);
+        h->coop_hp_cfg = h->planner.coop_hp;
+        h->hp_wave = env_is(getenv("FSNP_HP_WAVE"), '0') ? 0 : 1;       // 0: HalfTilePingPong launches on lstm_hp.hip instead of lstm_hpw.hip
+        h->calibrate = env_is(getenv("FSNP_CALIBRATE"), '1') ? 1 : 0;
     }
-    h->cost = initial_costs(cfg->sb_hidden, h->gru, cfg->sequence_model == FSNP_SEQ_TCN);
-    const char* ce = getenv("FSNP_CALIBRATE");
-    if (ce && ce[0] == '1') h->calibrate = 1;
-    const char* oe = getenv("FSNP_COOP_OCC");          // 1 = never plan two column-split workgroups per CU
-    h->coop_occ = oe && oe[0] == '1' ? 1 : 2;          // (2 is confirmed against the kernels' occupancy at commit time)
+    h->planner.cost = initial_costs(cfg->sb_hidden, h->gru, cfg->sequence_model == FSNP_SEQ_TCN);
     h->sb_tcn = cfg->sequence_model == FSNP_SEQ_TCN;
     h->XS = (int)align_up(nin, 4);
     h->NG = h->gru ? 3 : 4;
@@ -1004,26 +996,9 @@ int fsnp_create(const fsnp_config* cfg, fsnp_handle** out) {
     h->NB = fsn ? 0 : cfg->num_tcn_blocks;
     h->Fr = cfg->num_freqs / 2;
     build_specs(h);
-    const char* cp = getenv("FSNP_LSTM_COOP");
-    if (cp && cp[0] == '0') h->lstm_coop = 0;
-    {
-        // (The round-3 ping-pong K-split kernel lstm_pp.hip - opt-in, ahead of the other kernels at exactly 10 row tiles - was removed in
-        // round 4; its measurements stay in profiles/r03_column_split.md and profiles/r03_pp_*.txt.)
-        // The half-tile ping-pong kernel (lstm_hp.hip) is planned wherever the cost table says it pays (6 ... 10 row tiles: B = 1);
-        // FSNP_COOP_HP=0: never
-        const char* he = getenv("FSNP_COOP_HP");
-        h->coop_hp = he && he[0] == '0' ? 0 : 1;
-        h->coop_hp_cfg = h->coop_hp;
-        const char* hw = getenv("FSNP_HP_WAVE");           // 0 = kind-8 launches on lstm_hp.hip (round 3) instead of lstm_hpw.hip (round 6)
-        h->hp_wave = hw && hw[0] == '0' ? 0 : 1;
-        h->hp_ok = !generic_sb && cfg->sequence_model == FSNP_SEQ_LSTM && (cfg->sb_hidden == 384 || cfg->sb_hidden == 256);
-    }
     {
         const char* ve = getenv("FSNP_VERIFY_EVERY");      // N > 0: fsnp_set_verify(h, N) from the start (models with an exchange-free kernel)
-        if (ve && atoi(ve) > 0 && h->rowtile_ok && !generic_sb && cfg->sequence_model != FSNP_SEQ_TCN) h->verify_every = atoi(ve);
-        const char* we = getenv("FSNP_COOP_W");           // 0 = never plan the wave-owned column split (lstm_coopw.hip)
-        h->coop_w = we && we[0] == '0' ? 0 : 1;
-        h->coopw_ok = !generic_sb && cfg->sequence_model == FSNP_SEQ_LSTM && cfg->sb_hidden == 384;
+        if (ve && atoi(ve) > 0 && h->planner.rowtile_ok && !generic_sb && cfg->sequence_model != FSNP_SEQ_TCN) h->verify_every = atoi(ve);
     }
     const char* sk = getenv("FSNP_COOP_SKEW");
     if (sk && sk[0] == '0') h->coop_skew = 0;
@@ -1506,22 +1481,20 @@ int fsnp_debug_plan_rows(int32_t num_rows, int32_t num_cus, int32_t hidden, int3
     return fsnp_debug_plan_rows2(num_rows, num_cus, hidden, gru, coop, composite_gain, 1, nullptr, out, max_chunks);
 }
 
-// the planner of a handle on a chip of num_cus CUs whose kernels are all available (host only: the planner never touches the device)
+// the planner of a handle on a chip of num_cus CUs (host only): fsnp_create's kernels for an LSTM / GRU of 34 sub-band inputs, no switch set;
+// test overrides: never the runtime-sized kernel, a one-tile-per-CU kernel at every size but gru = 1 (round-1 shape; gru = 2: the GRU with one)
 static PlannerCtx host_ctx(int32_t num_cus, int32_t hidden, int32_t gru, int32_t coop, double composite_gain, int32_t workgroups_per_cu,
                            const double* costs) {
+    PlannerSwitches sw;
+    sw.lstm_coop = coop; sw.coop_occ = workgroups_per_cu >= 2 ? 2 : 1;
     PlannerCtx h;
-    h.H = hidden; h.num_cus = num_cus; h.num_cus_real = num_cus; h.gru = gru; h.lstm_coop = coop; h.composite_gain = composite_gain;
-    h.cost = default_costs(); h.coop_occ = workgroups_per_cu >= 2 ? 2 : 1;
+    static_cast<PlannerOptions&>(h) = planner_options(gru ? FSNP_SEQ_GRU : FSNP_SEQ_LSTM, hidden, 34, false, sw);
+    h.rowtile_ok = gru != 1;
+    h.H = hidden; h.NIN = 34; h.num_cus = num_cus; h.num_cus_real = num_cus; h.gru = gru != 0; h.composite_gain = composite_gain;
     for (int i = 0; i < 4; ++i) h.occ_ksplit[i] = h.coop_occ;
     for (int i = 0; i < 2; ++i) h.occ_coopn[i] = h.coop_occ;
+    h.cost = default_costs();
     if (costs) costs_from_array(h.cost, costs);
-    h.hp_ok = gru == 0 && (hidden == 384 || hidden == 256);
-    h.coop_hp = 1;
-    h.coopw_ok = gru == 0 && hidden == 384;
-    h.coop_w = 1;
-    h.lstm16_ok = gru == 0 && hidden == 384;
-    h.rowtile_ok = gru == 0 || gru == 2;      // gru = 1: plan as if there were no one-tile-per-CU GRU kernel (round-1 shape)
-    h.gru = gru != 0;
     if (gru == 2) h.cost.rowtile *= 0.75;
     return h;
 }
@@ -1535,7 +1508,7 @@ int fsnp_debug_plan_rows2(int32_t num_rows, int32_t num_cus, int32_t hidden, int
     for (const SbChunk& c : plan.chunks) {
         if (n >= max_chunks) break;
         int32_t* o = out + 8 * n;
-        o[0] = c.kind; o[1] = c.row0; o[2] = c.nrows; o[3] = c.num_tiles; o[4] = c.ex; o[5] = (c.kind == 1 || c.kind == 9) ? c.units : c.groups;
+        o[0] = (int)c.kind; o[1] = c.row0; o[2] = c.nrows; o[3] = c.num_tiles; o[4] = c.ex; o[5] = c.kind == SbKind::KSplit || c.kind == SbKind::WaveOwned ? c.units : c.groups;
         o[6] = c.rpg; o[7] = c.slot0;
         ++n;
     }
@@ -1589,9 +1562,9 @@ int fsnp_debug_coop_chain_stats(fsnp_handle* h, int64_t out[2], int32_t reset) {
 int fsnp_get_costs(const fsnp_handle* h, double out[FSNP_NUM_COSTS], int32_t* calibrated, int32_t* occ) {
     if (!h || !out) { set_error("fsnp_get_costs: null argument"); return 1; }
     static_assert(kNumCosts == FSNP_NUM_COSTS, "planner.h and fsnp.h agree on the flat table");
-    costs_to_array(h->cost, out);
-    if (calibrated) *calibrated = h->cost.calibrated;
-    if (occ) *occ = h->coop_occ;
+    costs_to_array(h->planner.cost, out);
+    if (calibrated) *calibrated = h->planner.cost.calibrated;
+    if (occ) *occ = h->planner.coop_occ;
     return 0;
 }
 
@@ -1600,7 +1573,7 @@ int fsnp_measure_costs(fsnp_handle* h, double out[FSNP_NUM_COSTS]) {
     if (!h->committed) { set_error("fsnp_measure_costs: weights not committed"); return 2; }
     if (h->sb_tcn) { set_error("fsnp_measure_costs: the sub-band model of this handle is a TCN (no recurrent kernels)"); return 2; }
     FSNP_ON_DEVICE(h);
-    CostTable t = h->cost;
+    CostTable t = h->planner.cost;
     if (calibrate_costs(h, false, &t)) return 4;
     costs_to_array(t, out);
     return 0;
@@ -1609,10 +1582,10 @@ int fsnp_measure_costs(fsnp_handle* h, double out[FSNP_NUM_COSTS]) {
 int fsnp_debug_set_costs(fsnp_handle* h, const double* costs, int32_t workgroups_per_cu) {
     if (!h || (workgroups_per_cu != 1 && workgroups_per_cu != 2)) { set_error("fsnp_debug_set_costs: bad argument"); return 1; }
     if (!h->committed) { set_error("fsnp_debug_set_costs: commit the weights first (the kernels' occupancy is checked then)"); return 2; }
-    h->cost = initial_costs(h->H, h->gru != 0, h->sb_tcn != 0);
-    if (costs) costs_from_array(h->cost, costs);
-    h->cost.calibrated = 1;          // pinned: the lazy calibration will not replace it
-    h->coop_occ = workgroups_per_cu;
+    h->planner.cost = initial_costs(h->H, h->gru != 0, h->sb_tcn != 0);
+    if (costs) costs_from_array(h->planner.cost, costs);
+    h->planner.cost.calibrated = 1;          // pinned: the lazy calibration will not replace it
+    h->planner.coop_occ = workgroups_per_cu;
     return 0;
 }
 
@@ -1622,10 +1595,7 @@ int fsnp_describe_plan(const fsnp_handle* h, int32_t batch, int32_t mode, int32_
     int n = 0;
     for (const SbChunk& c : plan.chunks) {
         if (n >= max_chunks) break;
-        // kind 4 = half-tile kernel, 11 = runtime-sized kernel, 12 = half-tile ping-pong (lstm_hp.hip), 13 = wave-owned column split (lstm_coopw.hip),
-        // 14 = half-tile ping-pong on its wave-owned kernel (lstm_hpw.hip: where launch_sb_lstm runs planner kind 8 by default)
-        const bool hpw = h->lw.hp_wave && lstm_hpw_available(h->lw);
-        out[4 * n + 0] = h->sb_tcn ? 3 : (c.kind == 7 ? 11 : c.kind == 8 ? (hpw ? 14 : 12) : c.kind == 9 ? 13 : c.kind);
+        out[4 * n + 0] = describe_code(c.kind, h->sb_tcn != 0, h->lw.hp_wave && lstm_hpw_available(h->lw));
         out[4 * n + 1] = c.nrows; out[4 * n + 2] = c.num_tiles; out[4 * n + 3] = c.ex;
         ++n;
     }
@@ -1645,8 +1615,8 @@ int fsnp_describe_plan_ex(const fsnp_handle* h, int32_t batch, int32_t mode, int
         // arithmetic of THIS chunk: the bf16 variants exist for the one-tile-per-CU LSTM kernel only (lstm.hip) and the half-tile kernel (lstm16.hip);
         // sequences that the plan hands to any other kernel run in fp32 whatever fsnp_set_precision says
         int prec = 0;
-        if (!h->sb_tcn && !h->gru && c.kind == 0) prec = h->ih_bf16 == 1 ? 1 : 0;
-        if (!h->sb_tcn && !h->gru && c.kind == 4 && h->ih_bf16 == 1 && h->lw.wpack16_bf) prec = 1;       // half-tile kernel: bf16 ih-GEMM too (round 4)
+        if (!h->sb_tcn && !h->gru && c.kind == SbKind::RowTile) prec = h->ih_bf16 == 1 ? 1 : 0;
+        if (!h->sb_tcn && !h->gru && c.kind == SbKind::HalfTile && h->ih_bf16 == 1 && h->lw.wpack16_bf) prec = 1;       // half-tile kernel: bf16 ih-GEMM too (round 4)
         out[7 * i + 4] = prec;
         out[7 * i + 5] = h->sb_tcn ? 0 : chunk_workgroups(h, c);
         out[7 * i + 6] = i >= first_deferred ? 1 : 0;        // the pipelined loop runs this launch on the side stream
@@ -1684,17 +1654,17 @@ int fsnp_debug_lstm_profile(fsnp_handle* h, const float* x, float* out, int32_t 
 int fsnp_debug_pp_profile(fsnp_handle* h, const float* x, float* out, int32_t num_seq, int32_t steps, int32_t tiles_per_group,
                           uint64_t* host_stamps, int64_t num_stamps) {
     if (!h || !x || !out || !host_stamps) { set_error("fsnp_debug_pp_profile: null argument"); return 1; }
-    if (!h->committed || (!h->hp_ok && tiles_per_group == 0)) { set_error("fsnp_debug_pp_profile: no half-tile ping-pong kernel for this handle"); return 2; }
+    if (!h->committed || (!h->planner.hp_ok && tiles_per_group == 0)) { set_error("fsnp_debug_pp_profile: no half-tile ping-pong kernel for this handle"); return 2; }
     // tiles_per_group: 0 = the half-tile ping-pong kernel (lstm_hp.hip: 2 halves x 16 stamps per step); 32 / 64 = the wave-owned column
     // split (lstm_coopw.hip) at that many units per workgroup (16 stamps per step: 8 per layer phase)
     const bool hp = tiles_per_group == 0, cw = tiles_per_group == 32 || tiles_per_group == 64 || tiles_per_group == 96;
     if ((!hp && !cw) || num_stamps != (int64_t)steps * (hp ? 32 : 16)) { set_error("fsnp_debug_pp_profile: tiles_per_group must be 0 (half-tile ping-pong kernel, steps * 32 stamps) or 32 / 64 (wave-owned column split, steps * 16 stamps)"); return 2; }
-    if (cw && !h->coopw_ok) { set_error("fsnp_debug_pp_profile: no wave-owned column split for this handle"); return 2; }
+    if (cw && !h->planner.coopw_ok) { set_error("fsnp_debug_pp_profile: no wave-owned column split for this handle"); return 2; }
     const int tiles = cdiv(num_seq, 32), groups = tiles, S = hp ? h->H / 16 : h->H / tiles_per_group;
     if (num_seq <= 0 || groups * S > h->num_cus_real) { set_error("fsnp_debug_pp_profile: the launch must fit the chip"); return 2; }
     FSNP_ON_DEVICE(h);
     SbPlan plan;
-    plan.chunks = {hp ? SbChunk{8, 0, num_seq, tiles, 0, 32, 16, 0, 0, 0, 0} : SbChunk{9, 0, num_seq, tiles, 0, 32, tiles_per_group, 0, 0, 0, 0}};
+    plan.chunks = {hp ? column_chunk(SbKind::HalfTilePingPong, 0, num_seq, tiles, 16, 0) : column_chunk(SbKind::WaveOwned, 0, num_seq, tiles, tiles_per_group, 0)};
     plan.total_slots = tiles * 32; plan.coop_tiles = tiles;
     const size_t rows_b = align_up((size_t)plan.total_slots * sizeof(RowDesc), 256), hx_b = align_up(lstm_coop_exchange_bytes(h->H, tiles), 256);
     const size_t bar_b = align_up(coop_counter_bytes(tiles), 256), st_b = (size_t)num_stamps * 8;
@@ -1750,7 +1720,7 @@ int fsnp_poll_errors(fsnp_handle* h) {
 
 int fsnp_set_verify(fsnp_handle* h, int32_t every) {
     if (!h || every < 0) { set_error("fsnp_set_verify: every must be >= 0 (0 = off)"); return 1; }
-    if (every > 0 && (!h->rowtile_ok || h->sb_tcn || h->generic_sb)) {
+    if (every > 0 && (!h->planner.rowtile_ok || h->sb_tcn || h->generic_sb)) {
         set_error("fsnp_set_verify: this model has no exchange-free (one-tile-per-CU) kernel to verify against");
         return 2;
     }
@@ -1840,21 +1810,21 @@ int64_t fsnp_dump_config(const fsnp_handle* h, char* buf, int64_t cap) {
     add("weights committed=%d precision=%d (0 fp32, 1 bf16 ih-GEMM) pipeline=%d timing=%d workspace=%zu bytes x %d\n",
         (int)h->committed, h->ih_bf16, h->pipeline, (int)h->timing, h->ws_bytes, h->ws_slots);
     add("effective settings (environment variable as read at fsnp_create = value in force):\n");
-    add("  FSNP_LSTM_COOP=%s -> column-split kernels %s\n", env("FSNP_LSTM_COOP"), h->lstm_coop ? "planned (auto)" : "never");
-    add("  FSNP_COOP_HP=%s -> half-tile ping-pong kernel (lstm_hp.hip / lstm_hpw.hip) %s\n", env("FSNP_COOP_HP"), !h->hp_ok ? "not built for this model" : h->coop_hp ? "planned" : "never");
+    add("  FSNP_LSTM_COOP=%s -> column-split kernels %s\n", env("FSNP_LSTM_COOP"), h->planner.lstm_coop ? "planned (auto)" : "never");
+    add("  FSNP_COOP_HP=%s -> half-tile ping-pong kernel (lstm_hp.hip / lstm_hpw.hip) %s\n", env("FSNP_COOP_HP"), !h->planner.hp_ok ? "not built for this model" : h->planner.coop_hp ? "planned" : "never");
     add("  FSNP_HP_WAVE=%s -> its launches run on %s\n", env("FSNP_HP_WAVE"), h->hp_wave && lstm_hpw_available(h->lw) ? "lstm_hpw.hip (wave-owned units, round 6)" : "lstm_hp.hip (gate-split waves, round 3)");
-    add("  FSNP_COOP_W=%s -> wave-owned column split (lstm_coopw.hip) %s\n", env("FSNP_COOP_W"), !h->coopw_ok ? "not built for this model" : h->coop_w ? "planned" : "never");
+    add("  FSNP_COOP_W=%s -> wave-owned column split (lstm_coopw.hip) %s\n", env("FSNP_COOP_W"), !h->planner.coopw_ok ? "not built for this model" : h->planner.coop_w ? "planned" : "never");
     add("  FSNP_COOP_SKEW=%s -> K-split schedule %s\n", env("FSNP_COOP_SKEW"), h->coop_skew ? "layer-skewed" : "serial");
-    add("  FSNP_COOP_OCC=%s -> column-split workgroups per CU the planner may use: %d\n", env("FSNP_COOP_OCC"), h->coop_occ);
-    add("  FSNP_LSTM16=%s -> half-tile kernel %s\n", env("FSNP_LSTM16"), h->lstm16_ok ? "planned" : "not used");
-    add("  FSNP_CALIBRATE=%s -> cost table %s\n", env("FSNP_CALIBRATE"), h->cost.calibrated ? "measured / pinned" : h->calibrate ? "to be measured at the first plan" : "built-in");
+    add("  FSNP_COOP_OCC=%s -> column-split workgroups per CU the planner may use: %d\n", env("FSNP_COOP_OCC"), h->planner.coop_occ);
+    add("  FSNP_LSTM16=%s -> half-tile kernel %s\n", env("FSNP_LSTM16"), h->planner.lstm16_ok ? "planned" : "not used");
+    add("  FSNP_CALIBRATE=%s -> cost table %s\n", env("FSNP_CALIBRATE"), h->planner.cost.calibrated ? "measured / pinned" : h->calibrate ? "to be measured at the first plan" : "built-in");
     add("  FSNP_GEMM_DMA=%s -> %d (0 = the general GEMM kernel everywhere)\n", env("FSNP_GEMM_DMA"), h->tw.gemm_dma);
     add("  FSNP_VERIFY_EVERY=%s -> exchange verification every %d forwards (0 = off)\n", env("FSNP_VERIFY_EVERY"), h->verify_every);
     add("  FSNP_DEBUG_STAGES=%s -> %d\n", env("FSNP_DEBUG_STAGES"), (int)h->debug);
+    const CostTable& t = h->planner.cost;
     add("cost table (us per step): K split full %.1f / %.1f / %.1f / %.1f, one tile %.1f / %.1f / %.1f / %.1f, three-way %.1f / %.1f, one tile per CU %.1f (+%.2f per VALU row), half tile %.1f, half-tile ping-pong %.1f / %.1f, wave-owned split full %.1f / %.1f / %.1f, one tile %.1f / %.1f / %.1f\n",
-        h->cost.ksplit[0][0], h->cost.ksplit[1][0], h->cost.ksplit[2][0], h->cost.ksplit[3][0], h->cost.ksplit1[0], h->cost.ksplit1[1],
-        h->cost.ksplit1[2], h->cost.ksplit1[3], h->cost.coopn[0][0], h->cost.coopn[1][0], h->cost.rowtile, h->cost.rowtile_ex, h->cost.rowtile16,
-        h->cost.hp[0], h->cost.hp[1], h->cost.coopw[0][1], h->cost.coopw[1][1], h->cost.coopw[2][1], h->cost.coopw[0][0], h->cost.coopw[1][0], h->cost.coopw[2][0]);
+        t.ksplit[0][0], t.ksplit[1][0], t.ksplit[2][0], t.ksplit[3][0], t.ksplit1[0], t.ksplit1[1], t.ksplit1[2], t.ksplit1[3], t.coopn[0][0], t.coopn[1][0],
+        t.rowtile, t.rowtile_ex, t.rowtile16, t.hp[0], t.hp[1], t.coopw[0][1], t.coopw[1][1], t.coopw[2][1], t.coopw[0][0], t.coopw[1][0], t.coopw[2][0]);
     if (buf && cap > 0) {
         const size_t n = o.size() < (size_t)cap - 1 ? o.size() : (size_t)cap - 1;
         memcpy(buf, o.data(), n);
@@ -1883,13 +1853,13 @@ int fsnp_debug_set_gemm_dma(fsnp_handle* h, int32_t mode) {
 
 int fsnp_debug_set_lstm_coop(fsnp_handle* h, int32_t mode) {
     if (!h || mode < 0 || mode > 4 || mode == 3) { set_error("fsnp_debug_set_lstm_coop: mode must be 0 (off), 1 (auto), 2 (auto, serial K-split schedule, no half-tile ping-pong kernel) or 4 (auto + the half-tile ping-pong kernel even where FSNP_COOP_HP=0)"); return 1; }
-    h->lstm_coop = mode != 0;
+    h->planner.lstm_coop = mode != 0;
     h->coop_skew = mode != 2;
-    h->coop_hp = mode == 4 ? 1 : mode == 1 ? h->coop_hp_cfg : 0;
+    h->planner.coop_hp = mode == 4 ? 1 : mode == 1 ? h->coop_hp_cfg : 0;
     h->fb_valu = mode == 1 || mode == 4;   // (FullSubNet: modes 0 and 2 keep the full-band LSTM on the K-split kernel, whatever the batch - mode 0 is
                                            // what the sync error policy retries with after a time-out, so it must not come back to the same exchange)
-    h->cost.calibrated = h->calibrate ? 0 : h->cost.calibrated;    // the K-split costs depend on the schedule: measure again
-    if (!h->cost.calibrated) h->cost = initial_costs(h->H, h->gru != 0, h->sb_tcn != 0);
+    h->planner.cost.calibrated = h->calibrate ? 0 : h->planner.cost.calibrated;    // the K-split costs depend on the schedule: measure again
+    if (!h->planner.cost.calibrated) h->planner.cost = initial_costs(h->H, h->gru != 0, h->sb_tcn != 0);
     return 0;
 }
 

@@ -60,11 +60,7 @@ struct fsnp_handle {
     int model = FSNP_MODEL_FULLSUBNET_PLUS;
     int NFB = 3;                 // full-band features per sub-band frame: 3 (FullSubNet+) or 1 (FullSubNet)
     int gru = 0;                 // 1 = nn.GRU cells (sub-band model; FullSubNet: also the full-band model)
-    bool lstm16_ok = false;      // the half-tile kernel (lstm16.hip) exists for this handle (LSTM, H = 384, K = 40) and is enabled
-    bool rowtile_ok = true;      // a one-tile-per-CU kernel (lstm.hip / lstm_gru.hip) exists for this handle's sub-band model
-    CostTable cost{};            // per-step costs the planner minimises (defaults, then measured on the device)
-    int coop_occ = 1;            // workgroups per CU the column-split kernels may be planned with (FSNP_COOP_OCC; 1 or 2) ...
-    int occ_ksplit[4] = {1, 1, 1, 1}, occ_coopn[2] = {1, 1};   // ... and what each instantiation really fits (measured at commit)
+    PlannerOptions planner{};    // what the sub-band planner knows of the handle besides its sizes (planner.h; occupancies measured at commit)
     int occ_fb[3] = {0, 0, 0};   // FullSubNet: workgroups of the full-band lstm_coop_seq at 8 / 16 / 32 units one CU holds (measured at commit; 0 = unknown)
     int calibrate = 0;           // FSNP_CALIBRATE=1: replace the built-in table by one measured on this device at the first planning call
     int sb_tcn = 0;              // 1 = the sub-band model is a TCN stack (FullSubNet+ with sequence_model="TCN")
@@ -87,19 +83,15 @@ struct fsnp_handle {
     int num_cus = 256;
     int num_cus_real = 256;   // never overridden: residency of the cooperative kernel depends on the real chip
     int ih_bf16 = 0;             // 1 = BASELINE.json configs[4]: layer-1 ih-GEMM of the sub-band LSTM in bf16
-    int lstm_coop = 1;           // 0 = never, 1 = automatic (small batches)
     int coop_chaos = 0;          // fsnp_debug_set_chaos: drift injection seed for the column-split kernels (0 = off)
     int coop_skew = 1;           // K-split kernel: 1 = layer-skewed schedule (lstm2_coop_skew_kernel), 0 = the serial one (FSNP_COOP_SKEW=0)
     bool generic_sb = false;     // the sub-band recurrent model runs on the runtime-sized kernel (lstm_generic.hip): a hidden size or an
                                  // input width no tuned kernel is instantiated for
     bool generic_fb = false;     // FullSubNet: the same for the full-band recurrent model (fb_model_hidden_size != 512 or > 264 bins)
-    bool hp_ok = false;          // the half-tile ping-pong kernel (lstm_hp.hip) exists for this handle's sub-band model
-    int hp_wave = 1;             // kind-8 launches run on the wave-owned variant (lstm_hpw.hip); FSNP_HP_WAVE=0: lstm_hp.hip
-    int coop_hp = 0, coop_hp_cfg = 0;   // ... and the planner may use it (FSNP_COOP_HP=0: never; fsnp_debug_set_lstm_coop(h, 4): even then)
+    int hp_wave = 1;             // HalfTilePingPong launches run on the wave-owned variant (lstm_hpw.hip); FSNP_HP_WAVE=0: lstm_hp.hip
+    int coop_hp_cfg = 0;         // planner.coop_hp as FSNP_COOP_HP set it (fsnp_debug_set_lstm_coop(h, 1) restores it)
     int fb_valu = 1;             // FullSubNet: the full-band LSTM of <= 4 utterances runs on the VALU kernel (lstm_fbv.hip); fsnp_debug_set_gemm_dma-like
                                  // test switch: fsnp_debug_set_lstm_coop(h, 2) turns it off together with the other round-3+ schedules
-    bool coopw_ok = false;       // the wave-owned column split (lstm_coopw.hip) exists for this handle's sub-band model (LSTM, H = 384) ...
-    int coop_w = 1;              // ... and the planner may use it (FSNP_COOP_W=0: never)
     unsigned* d_err = nullptr;   // [0] = error bits of finished launches (kErr*): an inter-workgroup wait timed out in a column-split LSTM
                                  // kernel / the watched source tensors no longer match the packed weights / a verification pass
                                  // disagreed.  Host-mapped, so the NEXT call on
@@ -133,8 +125,6 @@ struct fsnp_handle {
     float* d_stft = nullptr;     // [fwd (2F pad 384) x n_fft][inv (n_fft pad 384) x (2F pad 16)][window n_fft][zero bias 768]
     unsigned char* io = nullptr;
     size_t io_bytes = 0;
-
-    double composite_gain = 0.97;   // a row-tile + remainder plan must be estimated this much cheaper to be chosen
 
     bool timing = false;
     std::vector<TimingRec> timing_recs;   // recorded, not yet read back (drained by fsnp_get_timing, or when 256 pile up)

@@ -372,7 +372,7 @@ int fsnp_commit_weights(fsnp_handle* h) {
     }
     size_t o_wpack16 = 0, o_wpack16_bf = 0;
     bool have16_bf = false;
-    if (h->lstm16_ok) {
+    if (h->planner.lstm16_ok) {
         o_wpack16 = alloc(lstm16_pack_floats(H, h->KX));
         lstm16_pack_weights(H, h->NIN, h->KX, sbw.wih0.data(), sbw.whh0.data(), sbw.wih1.data(), sbw.whh1.data(), blob.data() + o_wpack16);
         if (h->KX == 40 && H == 384) {                 // bf16-ih stream of the half-tile kernel (configs[4], round 4)
@@ -394,14 +394,14 @@ int fsnp_commit_weights(fsnp_handle* h) {
                                blob.data() + o_wpack_coop[ui]);
     }
     size_t o_wpack_hp = 0, o_wpack_hpw = 0;
-    if (h->hp_ok) {
+    if (h->planner.hp_ok) {
         o_wpack_hp = alloc(lstm_hp_pack_floats(H, h->KX));
         lstm_hp_pack_weights(H, h->NIN, h->KX, sbw.wih0.data(), sbw.whh0.data(), sbw.wih1.data(), sbw.whh1.data(), blob.data() + o_wpack_hp);
         o_wpack_hpw = alloc(lstm_hpw_pack_floats(H, h->KX));
         lstm_hpw_pack_weights(H, h->NIN, h->KX, sbw.wih0.data(), sbw.whh0.data(), sbw.wih1.data(), sbw.whh1.data(), blob.data() + o_wpack_hpw);
     }
     size_t o_wpack_coopw = 0;
-    if (h->coopw_ok) {
+    if (h->planner.coopw_ok) {
         o_wpack_coopw = alloc(lstm_coopw_pack_floats(H, h->KX));
         lstm_coopw_pack_weights(H, h->NIN, h->KX, sbw.wih0.data(), sbw.whh0.data(), sbw.wih1.data(), sbw.whh1.data(), blob.data() + o_wpack_coopw);
     }
@@ -470,9 +470,9 @@ int fsnp_commit_weights(fsnp_handle* h) {
     h->lw.wpack = d + o_wpack; h->lw.wpack12 = d + o_wpack12; for (int ui = 0; ui < 4; ++ui) h->lw.wpack_coop[ui] = d + o_wpack_coop[ui];
     h->lw.wpack_coopn = d + o_wpack_coopn;
     h->lw.wpack_hp = d + o_wpack_hp;
-    h->lw.wpack_hpw = h->hp_ok ? d + o_wpack_hpw : nullptr;
+    h->lw.wpack_hpw = h->planner.hp_ok ? d + o_wpack_hpw : nullptr;
     h->lw.hp_wave = h->hp_wave;
-    h->lw.wpack_coopw = h->coopw_ok ? d + o_wpack_coopw : nullptr;
+    h->lw.wpack_coopw = h->planner.coopw_ok ? d + o_wpack_coopw : nullptr;
     h->lw.wpack_gru = d + o_wpack_gru;
     h->lw.wpack16 = d + o_wpack16;
     h->lw.wpack16_bf = have16_bf ? d + o_wpack16_bf : nullptr;
@@ -492,8 +492,8 @@ int fsnp_commit_weights(fsnp_handle* h) {
     h->d_refl_w = d + o_refl;
     h->d_refl_wfb = d + o_reflfb;
     if (tuned) {                                // which column-split instantiations fit twice on a CU (registers, LDS)
-        for (int ui = 0; ui < 4; ++ui) h->occ_ksplit[ui] = std::max(1, lstm_coop_occupancy(h->lw, 8 << ui));
-        for (int rpg = 1; rpg <= 2; ++rpg) h->occ_coopn[rpg - 1] = std::max(1, lstm_coopn_occupancy(h->lw, rpg));
+        for (int ui = 0; ui < 4; ++ui) h->planner.occ_ksplit[ui] = std::max(1, lstm_coop_occupancy(h->lw, 8 << ui));
+        for (int rpg = 1; rpg <= 2; ++rpg) h->planner.occ_coopn[rpg - 1] = std::max(1, lstm_coopn_occupancy(h->lw, rpg));
     }
     for (int ui = 0; ui < 3 && fsn && !h->generic_fb; ++ui) h->occ_fb[ui] = lstm_coop_seq_occupancy(h->fbw, 8 << ui);   // (pipelined loop: launch_coop_chained)
     if (h->generic_sb && lstm_generic_check(h->H, h->NIN, false)) return 2;

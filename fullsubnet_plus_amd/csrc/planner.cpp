@@ -38,26 +38,30 @@ CostTable default_costs() {
     for (int i = 0; i < 3; ++i) { t.coopw[i][0] = cw1[i]; t.coopw[i][1] = cwf[i]; }
     return t;
 }
-// flat layout (include/fsnp.h, fsnp_get_costs): [0..7] K split full launch x {one, two per CU} at 8 / 16 / 32 / 64 units, [8..11] three-way
-// split 1 / 2 row tiles per group x {one, two per CU}, [12] one tile per CU, [13] relative extra per VALU row, [14..17] K split with ONE row
-// tile, [18] half tile per CU, [19..20] half-tile ping-pong one tile / full launch, [21..22] wave-owned split at 32 / 64 units per
-// workgroup, a full launch, [23..24] the same with ONE row tile, [25..26] (round 6) the 96-unit instantiation: a full launch, one row tile
-// (kNumCosts = 27; appended, so that a 25-value table of the round-5 layout is still a valid prefix)
+// The slots of the flat table (include/fsnp.h, fsnp_get_costs), in order: [0..7] K split full launch x {one, two per CU} at 8 / 16 / 32 / 64
+// units, [8..11] three-way split 1 / 2 row tiles per group x {one, two per CU}, [12] one tile per CU, [13] relative extra per VALU row,
+// [14..17] K split with ONE row tile, [18] half tile per CU, [19..20] half-tile ping-pong one tile / full launch, [21..22] wave-owned split
+// at 32 / 64 units per workgroup, a full launch, [23..24] the same with ONE row tile, [25..26] (round 6) the 96-unit instantiation: a full
+// launch, one row tile.  Slots are only appended, but every reader of a flat table takes all kNumCosts of them.
+static void cost_slots(CostTable& t, double* s[kNumCosts]) {
+    int n = 0;
+    for (int i = 0; i < 4; ++i) { s[n++] = &t.ksplit[i][0]; s[n++] = &t.ksplit[i][1]; }
+    for (int i = 0; i < 2; ++i) { s[n++] = &t.coopn[i][0]; s[n++] = &t.coopn[i][1]; }
+    s[n++] = &t.rowtile; s[n++] = &t.rowtile_ex;
+    for (int i = 0; i < 4; ++i) s[n++] = &t.ksplit1[i];
+    s[n++] = &t.rowtile16; s[n++] = &t.hp[0]; s[n++] = &t.hp[1];
+    s[n++] = &t.coopw[0][1]; s[n++] = &t.coopw[1][1]; s[n++] = &t.coopw[0][0]; s[n++] = &t.coopw[1][0]; s[n++] = &t.coopw[2][1]; s[n++] = &t.coopw[2][0];
+}
 void costs_to_array(const CostTable& t, double* out) {
-    for (int i = 0; i < 4; ++i) { out[2 * i] = t.ksplit[i][0]; out[2 * i + 1] = t.ksplit[i][1]; out[14 + i] = t.ksplit1[i]; }
-    for (int i = 0; i < 2; ++i) { out[8 + 2 * i] = t.coopn[i][0]; out[9 + 2 * i] = t.coopn[i][1]; }
-    out[12] = t.rowtile; out[13] = t.rowtile_ex; out[18] = t.rowtile16;
-    out[19] = t.hp[0]; out[20] = t.hp[1];
-    for (int i = 0; i < 2; ++i) { out[21 + i] = t.coopw[i][1]; out[23 + i] = t.coopw[i][0]; }
-    out[25] = t.coopw[2][1]; out[26] = t.coopw[2][0];
+    CostTable c = t;
+    double* s[kNumCosts];
+    cost_slots(c, s);
+    for (int i = 0; i < kNumCosts; ++i) out[i] = *s[i];
 }
 void costs_from_array(CostTable& t, const double* in) {
-    for (int i = 0; i < 4; ++i) { t.ksplit[i][0] = in[2 * i]; t.ksplit[i][1] = in[2 * i + 1]; t.ksplit1[i] = in[14 + i]; }
-    for (int i = 0; i < 2; ++i) { t.coopn[i][0] = in[8 + 2 * i]; t.coopn[i][1] = in[9 + 2 * i]; }
-    t.rowtile = in[12]; t.rowtile_ex = in[13]; t.rowtile16 = in[18];
-    t.hp[0] = in[19]; t.hp[1] = in[20];
-    for (int i = 0; i < 2; ++i) { t.coopw[i][1] = in[21 + i]; t.coopw[i][0] = in[23 + i]; }
-    t.coopw[2][1] = in[25]; t.coopw[2][0] = in[26];
+    double* s[kNumCosts];
+    cost_slots(t, s);
+    for (int i = 0; i < kNumCosts; ++i) *s[i] = in[i];
 }
 // the table a handle starts from: the built-in one scaled to the handle's cell and hidden size (measured at LSTM, H = 384)
 CostTable initial_costs(int sb_hidden, bool gru, bool sb_tcn) {
@@ -73,39 +77,53 @@ CostTable initial_costs(int sb_hidden, bool gru, bool sb_tcn) {
     }
     return t;
 }
+PlannerOptions planner_options(int seq_model, int sb_hidden, int nin, bool generic_sb, const PlannerSwitches& sw) {
+    PlannerOptions o;
+    const bool lstm = seq_model == FSNP_SEQ_LSTM && !generic_sb, H384 = sb_hidden == 384;
+    // one tile per CU: LSTM lstm.hip (H = 384, and 256 without VALU rows), GRU lstm_gru.hip (384); other sizes: column split only
+    o.rowtile_ok = !generic_sb && (H384 || (sb_hidden == 256 && seq_model != FSNP_SEQ_GRU));
+    o.lstm16_ok = sw.lstm16 && lstm && H384 && nin <= 40;             // half tiles (lstm16.hip): K = 40 only
+    o.hp_ok = lstm && (H384 || sb_hidden == 256);                      // half-tile ping-pong (lstm_hp.hip / lstm_hpw.hip)
+    o.coopw_ok = lstm && H384;                                         // wave-owned column split (lstm_coopw.hip)
+    o.lstm_coop = sw.lstm_coop; o.coop_hp = sw.coop_hp; o.coop_w = sw.coop_w; o.coop_occ = sw.coop_occ;
+    return o;
+}
+int describe_code(SbKind k, bool sb_tcn, bool hpw) {
+    return sb_tcn ? 3 : k == SbKind::Generic ? 11 : k == SbKind::HalfTilePingPong ? (hpw ? 14 : 12) : k == SbKind::WaveOwned ? 13 : (int)k;
+}
 static int units_index(int units) { return units <= 8 ? 0 : units <= 16 ? 1 : units <= 32 ? 2 : 3; }
-int chunk_workgroups(const PlannerCtx& h, const SbChunk& c) {
-    if (c.kind == 1) return c.num_tiles * (h.H / c.units);
-    if (c.kind == 2) return c.groups * (h.H / 128);
-    if (c.kind == 8) return c.num_tiles * (h.H / 16);
-    if (c.kind == 9) return c.num_tiles * (h.H / c.units);
-    return c.num_tiles;
+bool is_column_split(SbKind k) { return k == SbKind::KSplit || k == SbKind::ThreeWay || k == SbKind::HalfTilePingPong || k == SbKind::WaveOwned; }
+SbSplit chunk_split(const PlannerCtx& h, const SbChunk& c) {
+    switch (c.kind) {
+    case SbKind::KSplit: case SbKind::WaveOwned: return {h.H / c.units, c.num_tiles};
+    case SbKind::ThreeWay: return {h.H / 128, c.groups};
+    case SbKind::HalfTilePingPong: return {h.H / 16, c.num_tiles};
+    default: return {1, c.num_tiles};
+    }
+}
+int chunk_workgroups(const PlannerCtx& h, const SbChunk& c) { const SbSplit sp = chunk_split(h, c); return sp.S * sp.T; }
+static double one_to_full(double one, double full, int tiles, int cap) {     // `tiles` row tiles: one .. a full launch of `cap`, linear
+    if (cap <= 1) return one;
+    const double f = (double)(tiles - 1) / (cap - 1);
+    return one + (full - one) * (f < 1.0 ? f : 1.0);
 }
 double est_step_us(const PlannerCtx& h, const SbChunk& c) {
-    const int dbl = chunk_workgroups(h, c) > h.num_cus_real ? 1 : 0;
-    if (c.kind == 1) {
+    const SbSplit sp = chunk_split(h, c);
+    const int dbl = sp.S * sp.T > h.num_cus_real ? 1 : 0, cap = h.num_cus_real / sp.S;   // (cap: row tiles of a full launch)
+    switch (c.kind) {
+    case SbKind::KSplit: {
         const int ui = units_index(c.units);
-        const int cap = h.num_cus_real / (h.H / c.units);
         if (dbl || cap <= 1) return h.cost.ksplit[ui][dbl];
-        const double f = (double)(c.num_tiles - 1) / (cap - 1);              // 1 tile .. a full launch
-        return h.cost.ksplit1[ui] + (h.cost.ksplit[ui][0] - h.cost.ksplit1[ui]) * (f < 1.0 ? f : 1.0);
+        return one_to_full(h.cost.ksplit1[ui], h.cost.ksplit[ui][0], c.num_tiles, cap);
     }
-    if (c.kind == 2) return h.cost.coopn[c.rpg == 1 ? 0 : 1][dbl];
-    if (c.kind == 8) {
-        const int cap = h.num_cus_real / (h.H / 16);
-        if (cap <= 1) return h.cost.hp[0];
-        const double f = (double)(c.num_tiles - 1) / (cap - 1);
-        return h.cost.hp[0] + (h.cost.hp[1] - h.cost.hp[0]) * (f < 1.0 ? f : 1.0);
-    }
-    if (c.kind == 9) {
-        const int wi = c.units / 32 - 1, cap = h.num_cus_real / (h.H / c.units);
-        if (cap <= 1) return h.cost.coopw[wi][0];
-        const double f = (double)(c.num_tiles - 1) / (cap - 1);
-        return h.cost.coopw[wi][0] + (h.cost.coopw[wi][1] - h.cost.coopw[wi][0]) * (f < 1.0 ? f : 1.0);
-    }
+    case SbKind::ThreeWay: return h.cost.coopn[c.rpg == 1 ? 0 : 1][dbl];
+    case SbKind::HalfTilePingPong: return one_to_full(h.cost.hp[0], h.cost.hp[1], c.num_tiles, cap);
+    case SbKind::WaveOwned: return one_to_full(h.cost.coopw[c.units / 32 - 1][0], h.cost.coopw[c.units / 32 - 1][1], c.num_tiles, cap);
     // (bf16 ih-GEMM mode: the half-tile kernel streams 12 bf16 k-steps instead of 48 fp32 k-groups for layer 1's ih product - measured
     //  11.42 vs 14.16 ms at 4096 sequences, profiles/r04_bf16_half_tile_bench.jsonl: the fp32 entry scaled by that ratio)
-    if (c.kind == 4) return cdiv(c.num_tiles, h.num_cus) * h.cost.rowtile16 * (h.ih_bf16 == 1 ? 0.81 : 1.0);
+    case SbKind::HalfTile: return cdiv(c.num_tiles, h.num_cus) * h.cost.rowtile16 * (h.ih_bf16 == 1 ? 0.81 : 1.0);
+    default: break;
+    }
     // (the same for the one-tile-per-CU LSTM kernel: 155 us per round against 206 in fp32 - BASELINE configs[4], 20.9 vs 27.5 ms at
     //  B = 32, profiles/r04_bench_configs.md.  Without this the cheaper column-split kernels of round 5 made the planner leave the
     //  bf16 kernel for a half-tile round + three wave-owned launches at the fp32 kernel's price: 27.6 ms, profiles/r05_bench_configs.md)
@@ -113,9 +131,9 @@ double est_step_us(const PlannerCtx& h, const SbChunk& c) {
     return cdiv(c.num_tiles, h.num_cus) * h.cost.rowtile * bf * (1.0 + h.cost.rowtile_ex * c.ex);
 }
 static SbChunk rowtile_chunk(const PlannerCtx& h, int row0, int nrows) {
-    if (h.gru || h.H != 384) return SbChunk{0, row0, nrows, cdiv(nrows, 32), 0, 32, 0, 0, 0, 0, 0};   // VALU rows: LSTM at H = 384 only
+    if (h.gru || h.H != 384) return row_tile_chunk(row0, nrows, cdiv(nrows, 32));   // VALU rows: LSTM at H = 384 only
     const LstmPlan lp = plan_lstm_tiles(nrows, h.num_cus);
-    return SbChunk{0, row0, nrows, lp.num_tiles, lp.ex, lp.rows_per_slot_tile, 0, 0, 0, 0, 0};
+    return row_tile_chunk(row0, nrows, lp.num_tiles, lp.ex, lp.rows_per_slot_tile);
 }
 // Column-split launches for `nrows` sequences (any count): the cheapest sequence of launches by the cost table.  A launch
 // costs the same per step whether its kernel is full or not, so this is a shortest path over tile counts: best[t] = min over
@@ -127,24 +145,23 @@ static std::vector<SbChunk> plan_columns(const PlannerCtx& h, int row0, int nrow
     const int S3 = h.H / 128;
     if (h.H < 128 || h.num_cus_real / S3 <= 0) return out;   // fewer CUs than one group needs: no column-split plan
     const int T = cdiv(nrows, 32);
-    struct Shape { int kind, units, rpg, cap, dbl; };
+    struct Shape { SbKind kind; int units, rpg, cap, dbl; };
     std::vector<Shape> shapes;
     for (int occ = 1; occ <= (h.coop_occ >= 2 ? 2 : 1); ++occ) {          // two per CU: only shapes whose kernel fits twice
         const int slots = h.num_cus_real * occ;
         for (int u = 8; u <= 64; u *= 2)
             if (h.H % u == 0 && slots / (h.H / u) > 0 && h.occ_ksplit[units_index(u)] >= occ)
-                shapes.push_back({1, u, 0, slots / (h.H / u), occ - 1});
+                shapes.push_back({SbKind::KSplit, u, 0, slots / (h.H / u), occ - 1});
         for (int rpg = 1; rpg <= 2; ++rpg)
-            if (h.occ_coopn[rpg - 1] >= occ) shapes.push_back({2, 0, rpg, (slots / S3) * rpg, occ - 1});
+            if (h.occ_coopn[rpg - 1] >= occ) shapes.push_back({SbKind::ThreeWay, 0, rpg, (slots / S3) * rpg, occ - 1});
         // half-tile ping-pong (lstm_hp.hip): H / 16 workgroups per row tile
-        if (occ == 1 && h.hp_ok && h.coop_hp && slots / (h.H / 16) > 0) shapes.push_back({8, 16, 0, slots / (h.H / 16), 0});
+        if (occ == 1 && h.hp_ok && h.coop_hp && slots / (h.H / 16) > 0) shapes.push_back({SbKind::HalfTilePingPong, 16, 0, slots / (h.H / 16), 0});
         // wave-owned column split (lstm_coopw.hip): H / (32 NT) workgroups per row tile, one per CU
         for (int nt = 1; nt <= 3 && occ == 1 && h.coopw_ok && h.coop_w; ++nt)
-            if (h.H % (32 * nt) == 0 && slots / (h.H / (32 * nt)) > 0) shapes.push_back({9, 32 * nt, 0, slots / (h.H / (32 * nt)), 0});
+            if (h.H % (32 * nt) == 0 && slots / (h.H / (32 * nt)) > 0) shapes.push_back({SbKind::WaveOwned, 32 * nt, 0, slots / (h.H / (32 * nt)), 0});
     }
     auto shape_cost = [&](const Shape& sh, int n) {             // n tiles on this shape (n <= cap)
-        SbChunk c{sh.kind, 0, n * 32, n, 0, 32, sh.units, sh.kind == 2 ? cdiv(n, sh.rpg) : 0, sh.rpg, 0, 0};
-        return est_step_us(h, c) + 1.2;                         // + a launch (prologue / drain, amortised over ~100 steps): fewer chunks win near-ties
+        return est_step_us(h, column_chunk(sh.kind, 0, n * 32, n, sh.units, sh.rpg)) + 1.2;   // + a launch (prologue / drain, amortised over ~100 steps): fewer chunks win near-ties
     };
     std::vector<double> best(T + 1, 0.0);
     std::vector<int> pick(T + 1, -1);
@@ -152,7 +169,7 @@ static std::vector<SbChunk> plan_columns(const PlannerCtx& h, int row0, int nrow
         best[t] = 1e30;
         for (int i = 0; i < (int)shapes.size(); ++i) {
             const int n = t < shapes[i].cap ? t : shapes[i].cap;
-            if (shapes[i].kind == 2 && shapes[i].rpg == 2 && n < 2) continue;
+            if (shapes[i].kind == SbKind::ThreeWay && shapes[i].rpg == 2 && n < 2) continue;
             const double c = shape_cost(shapes[i], n) + best[t - n];
             if (c < best[t] - 1e-9) { best[t] = c; pick[t] = i; }
         }
@@ -170,8 +187,7 @@ static std::vector<SbChunk> plan_columns(const PlannerCtx& h, int row0, int nrow
     for (const auto& tk : taken) {
         const Shape& sh = shapes[tk.second];
         const int rows = tk.first * 32 < left ? tk.first * 32 : left;
-        SbChunk c{sh.kind, r0, rows, tk.first, 0, 32, sh.units, sh.kind == 2 ? cdiv(tk.first, sh.rpg) : 0, sh.rpg, 0, 0};
-        out.push_back(c);
+        out.push_back(column_chunk(sh.kind, r0, rows, tk.first, sh.units, sh.rpg));
         r0 += rows; left -= rows;
     }
     return out;
@@ -181,13 +197,13 @@ SbPlan plan_sb(const PlannerCtx& h, int num_rows) {
     SbPlan p;
     auto push = [&](SbChunk c) {
         c.slot0 = p.total_slots; p.total_slots += c.num_tiles * c.rps;
-        c.coop_tile0 = p.coop_tiles; if (c.kind == 1 || c.kind == 2 || c.kind == 8 || c.kind == 9) p.coop_tiles += c.num_tiles;
+        c.coop_tile0 = p.coop_tiles; if (is_column_split(c.kind)) p.coop_tiles += c.num_tiles;
         p.chunks.push_back(c);
     };
-    if (h.sb_tcn) { push(SbChunk{0, 0, num_rows, cdiv(num_rows, 32), 0, 32, 0, 0, 0, 0, 0}); return p; }   // no recurrent kernel
+    if (h.sb_tcn) { push(row_tile_chunk(0, num_rows, cdiv(num_rows, 32))); return p; }   // no recurrent kernel
     if (h.generic_sb) {                                        // the runtime-sized kernel: workgroups of rg sequences, one launch
         const int rg = lstm_generic_rows_per_group(h.H, h.NIN, num_rows, h.num_cus_real);
-        if (rg > 0) push(SbChunk{7, 0, num_rows, cdiv(num_rows, rg), 0, rg, 0, 0, rg, 0, 0});
+        if (rg > 0) push(generic_chunk(0, num_rows, rg));
         return p;
     }
     // (+ 1.2 us per launch, as inside plan_columns: prologue / drain amortised over ~100 steps - fewer launches win near-ties)
@@ -200,7 +216,7 @@ SbPlan plan_sb(const PlannerCtx& h, int num_rows) {
     if (!coop_on) {
         // (the exchange-free re-run of fsnp_set_verify: up to one round of 16-row half tiles costs half a round of 32-row tiles; plain
         //  FSNP_LSTM_COOP=0 handles keep the row-tile kernel, whose plans their users and tests know)
-        const SbChunk all16{4, 0, num_rows, cdiv(num_rows, 16), 0, 16, 0, 0, 0, 0, 0};
+        const SbChunk all16 = half_tile_chunk(0, num_rows, cdiv(num_rows, 16));
         if (h.half_tiles_without_coop && h.lstm16_ok && est_step_us(h, all16) < est_step_us(h, whole)) push(all16);
         else push(whole);
         return p;
@@ -218,7 +234,7 @@ SbPlan plan_sb(const PlannerCtx& h, int num_rows) {
         const double cw = est_step_us(h, whole) + 1.2;
         if (cw < best_cost) { best = {whole}; best_cost = cw; }
         if (q >= 1 && rem > 0) {
-            std::vector<SbChunk> comp{SbChunk{0, 0, q * full, q * h.num_cus, 0, 32, 0, 0, 0, 0, 0}};
+            std::vector<SbChunk> comp{row_tile_chunk(0, q * full, q * h.num_cus)};
             const std::vector<SbChunk> rc = plan_columns(h, q * full, rem);
             if (!rc.empty()) {
                 comp.insert(comp.end(), rc.begin(), rc.end());
@@ -232,11 +248,11 @@ SbPlan plan_sb(const PlannerCtx& h, int num_rows) {
     // 4096 sequences = 256 half tiles, one launch), alone or as one full round + a column-split remainder
     if (h.lstm16_ok) {                           // (fp32 and, round 4, the bf16 ih-GEMM mode)
         const int per_round = h.num_cus * 16;
-        const SbChunk all16{4, 0, num_rows, cdiv(num_rows, 16), 0, 16, 0, 0, 0, 0, 0};
+        const SbChunk all16 = half_tile_chunk(0, num_rows, cdiv(num_rows, 16));
         const double c_all = est_step_us(h, all16) + 1.2;
         if (c_all < best_cost) { best = {all16}; best_cost = c_all; }
         if (num_rows > per_round) {
-            std::vector<SbChunk> comp{SbChunk{4, 0, per_round, h.num_cus, 0, 16, 0, 0, 0, 0, 0}};
+            std::vector<SbChunk> comp{half_tile_chunk(0, per_round, h.num_cus)};
             const std::vector<SbChunk> rc = plan_columns(h, per_round, num_rows - per_round);
             if (!rc.empty()) {
                 comp.insert(comp.end(), rc.begin(), rc.end());
@@ -259,7 +275,7 @@ SbPlan plan_sb(const PlannerCtx& h, int num_rows) {
 // instead of 0.66 - profiles/r04_bench_configs.md): the planner defers only in the first case.
 int plan_first_deferred(const PlannerCtx& h, const SbPlan& plan, bool defer_small) {
     const int n = (int)plan.chunks.size();
-    auto fills_chip = [](const SbChunk& c) { return c.kind == 0 || c.kind == 4; };       // one (half) tile per CU, no exchange
+    auto fills_chip = [](const SbChunk& c) { return c.kind == SbKind::RowTile || c.kind == SbKind::HalfTile; };   // one (half) tile per CU
     if (n == 0 || h.sb_tcn) return n;
     int first = n;
     if (n > 1 && fills_chip(plan.chunks[0])) {
@@ -280,23 +296,16 @@ CoopFootprint coop_footprint_round_robin(int wgs, bool own_cu, int per_cu) {
     f.own_cu = own_cu ? 1 : 0; f.per_cu = per_cu;
     return f;
 }
-// S workgroups per row tile and T tiles (kind 2: groups) of a column-split chunk, as its kernel decodes them
-static void chunk_split(const PlannerCtx& h, const SbChunk& c, int& S, int& T) {
-    S = c.kind == 8 ? h.H / 16 : (c.kind == 1 || c.kind == 9) ? h.H / c.units : h.H / 128;
-    T = c.kind == 2 ? c.groups : c.num_tiles;
-}
 int chunk_coop_xcd(const PlannerCtx& h, const SbChunk& c) {
-    int S, T;
-    chunk_split(h, c, S, T);
+    const SbSplit sp = chunk_split(h, c);
     const int cpx = h.num_cus_real / kNumXcds;
-    return h.num_cus_real % kNumXcds == 0 && xcd_local_blocks_per_xcd(S, T, cpx) <= cpx ? cpx : 0;
+    return h.num_cus_real % kNumXcds == 0 && xcd_local_blocks_per_xcd(sp.S, sp.T, cpx) <= cpx ? cpx : 0;
 }
 CoopFootprint chunk_footprint(const PlannerCtx& h, const SbChunk& c, bool own_cu, int per_cu) {
     const int cpx = chunk_coop_xcd(h, c);
     if (!cpx) return coop_footprint_round_robin(chunk_workgroups(h, c), own_cu, per_cu);
-    int S, T;
-    chunk_split(h, c, S, T);
-    return coop_footprint_round_robin(kNumXcds * xcd_local_blocks_per_xcd(S, T, cpx), own_cu, per_cu);     // (its grid: 8 x that)
+    const SbSplit sp = chunk_split(h, c);
+    return coop_footprint_round_robin(kNumXcds * xcd_local_blocks_per_xcd(sp.S, sp.T, cpx), own_cu, per_cu);     // (its grid: 8 x that)
 }
 // `l` can always become fully resident beside `blocker`, which holds at most one CU per workgroup it was dealt on each XCD
 static bool always_resident(const CoopFootprint& blocker, const CoopFootprint& l, int cus_per_xcd) {

@@ -26,30 +26,55 @@ struct CostTable {
 // round of the row-tile kernel (8192) + 66 tiles on lstm_coopn.hip instead of two rounds; GRU (column-split only) =
 // chunks of <= 170 tiles.  Every chunk owns a slice of the row descriptors / per-row norm tables (slot0) and, if it is
 // column-split, of the exchange images and barrier counters (coop_tile0).
+// the kind of a chunk = which kernel runs it (the numbers are those fsnp_debug_plan_rows* report)
+enum class SbKind : int {
+    RowTile = 0,               // one 32-row tile per CU (lstm.hip / lstm_gru.hip; VALU rows: 32 + ex slots per tile)
+    KSplit = 1,                // column split: K split, 8 .. 64 hidden units per workgroup (lstm_coop.hip)
+    ThreeWay = 2,              // column split: 3 workgroups x 128 units share 1 - 2 row tiles (lstm_coopn.hip)
+    HalfTile = 4,              // one 16-row tile per CU (lstm16.hip; rps = 16)
+    Generic = 7,               // runtime-sized kernel, workgroups of rpg sequences (lstm_generic.hip)
+    HalfTilePingPong = 8,      // column split: H / 16 workgroups per row tile (lstm_hpw.hip, FSNP_HP_WAVE=0: lstm_hp.hip)
+    WaveOwned = 9,             // column split: 32 / 64 / 96 units per workgroup, one per CU (lstm_coopw.hip)
+};
+bool is_column_split(SbKind k);     // the kinds whose workgroups exchange state each step (exchange images, barrier counters)
+
 struct SbChunk {
-    int kind;                  // 0 = row tile, 1 = coop (K split), 2 = coopn, 4 = half tile (lstm16.hip: 16-row tiles, rps = 16),
-                               // 7 = runtime-sized (lstm_generic.hip), 8 = half-tile ping-pong (lstm_hp.hip), 9 = wave-owned column split
-                               // (lstm_coopw.hip: units = 32 or 64 per workgroup)
+    SbKind kind;
     int row0, nrows;           // sequences [row0, row0 + nrows)
     int num_tiles, ex, rps;    // tiles, VALU rows per tile, slots per tile (32 + ex)
     int units, groups, rpg;    // column-split parameters
     int slot0, coop_tile0;
 };
+inline SbChunk row_tile_chunk(int row0, int nrows, int tiles, int ex = 0, int rps = 32) { return {SbKind::RowTile, row0, nrows, tiles, ex, rps, 0, 0, 0, 0, 0}; }
+inline SbChunk half_tile_chunk(int row0, int nrows, int tiles) { return {SbKind::HalfTile, row0, nrows, tiles, 0, 16, 0, 0, 0, 0, 0}; }
+inline SbChunk generic_chunk(int row0, int nrows, int rpg) { return {SbKind::Generic, row0, nrows, (nrows + rpg - 1) / rpg, 0, rpg, 0, 0, rpg, 0, 0}; }
+// a column-split launch: `units` hidden units per workgroup (ThreeWay: 0, and cdiv(tiles, rpg) groups of rpg row tiles; others: rpg = 0)
+inline SbChunk column_chunk(SbKind kind, int row0, int nrows, int tiles, int units, int rpg) {
+    return {kind, row0, nrows, tiles, 0, 32, units, kind == SbKind::ThreeWay ? (tiles + rpg - 1) / rpg : 0, rpg, 0, 0};
+}
 struct SbPlan {
     std::vector<SbChunk> chunks;
     int total_slots = 0, coop_tiles = 0;
 };
 
-// what the planner needs to know of a handle (fsnp_abi.hip: pctx)
-struct PlannerCtx {
-    int H = 0, NIN = 0, num_cus = 256, num_cus_real = 256;
-    bool gru = false, sb_tcn = false, generic_sb = false, rowtile_ok = true, lstm16_ok = false, hp_ok = false, coopw_ok = false;
-    int ih_bf16 = 0, lstm_coop = 1, coop_occ = 1;
-    int occ_ksplit[4] = {1, 1, 1, 1}, occ_coopn[2] = {1, 1};
-    int coop_hp = 0, coop_w = 0, pipeline = 0;
-    bool half_tiles_without_coop = false;   // lstm_coop == 0 plans may still use the (exchange-free) half-tile kernel: fsnp_set_verify's re-run
+struct PlannerOptions {        // what a handle decides about its plans besides its sizes (fsnp_handle::planner)
+    bool rowtile_ok = true, lstm16_ok = false, hp_ok = false, coopw_ok = false;   // kernels that exist for the sub-band model
+    int lstm_coop = 1, coop_hp = 0, coop_w = 0, coop_occ = 1;                       // what the switches allow of them
+    int occ_ksplit[4] = {1, 1, 1, 1}, occ_coopn[2] = {1, 1};                        // workgroups per CU each instantiation fits
     double composite_gain = 0.97;
     CostTable cost{};
+};
+// FSNP_LSTM16, FSNP_LSTM_COOP, FSNP_COOP_HP, FSNP_COOP_W, FSNP_COOP_OCC as fsnp_create reads them (defaults: unset)
+struct PlannerSwitches { bool lstm16 = true; int lstm_coop = 1, coop_hp = 1, coop_w = 1, coop_occ = 2; };
+// which sub-band kernels exist for the model (seq_model: FSNP_SEQ_*; generic_sb: it runs on lstm_generic.hip) and what the switches
+// allow of them; the cost table and the occupancies keep their defaults
+PlannerOptions planner_options(int seq_model, int sb_hidden, int nin, bool generic_sb, const PlannerSwitches& sw);
+
+// what the planner needs to know of a handle (fsnp_abi.hip: pctx)
+struct PlannerCtx : PlannerOptions {
+    int H = 0, NIN = 0, num_cus = 256, num_cus_real = 256;
+    bool gru = false, sb_tcn = false, generic_sb = false; int ih_bf16 = 0;
+    bool half_tiles_without_coop = false;   // lstm_coop == 0 plans may still use the (exchange-free) half-tile kernel: fsnp_set_verify's re-run
 };
 
 CostTable default_costs();
@@ -59,9 +84,14 @@ void costs_to_array(const CostTable& t, double* out);
 void costs_from_array(CostTable& t, const double* in);
 // the table a handle starts from: the built-in one scaled to the handle's cell and hidden size (measured at LSTM, H = 384)
 CostTable initial_costs(int sb_hidden, bool gru, bool sb_tcn);
+// S workgroups per row tile and the T tiles (ThreeWay: groups) a launch of chunk c decodes: S * T workgroups (S = 1 unless column split)
+struct SbSplit { int S, T; };
+SbSplit chunk_split(const PlannerCtx& h, const SbChunk& c);
 int chunk_workgroups(const PlannerCtx& h, const SbChunk& c);
 double est_step_us(const PlannerCtx& h, const SbChunk& c);
 SbPlan plan_sb(const PlannerCtx& h, int num_rows);       // empty plan = "this device cannot run the model"
+// the kernel code fsnp_describe_plan reports for a chunk (include/fsnp.h); hpw: HalfTilePingPong launches run on lstm_hpw.hip
+int describe_code(SbKind k, bool sb_tcn, bool hpw);
 // pipelined serving loop (fsnp_set_pipeline): the first chunk that goes to the side stream (== chunks.size(): none; 0: the whole plan)
 int plan_first_deferred(const PlannerCtx& h, const SbPlan& plan, bool defer_small);
 

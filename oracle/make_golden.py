@@ -4,6 +4,7 @@ Run in the build container (needs /root/reference):
 
     python -m oracle.make_golden                   # writes tests/golden/*.npz
     python -m oracle.make_golden reference_facts   # writes tests/golden/reference/ (main_reference_facts)
+    python -m oracle.make_golden planner_plans     # writes tests/golden/planner_plans.json (built library only, no reference)
 
 Each fixture holds, for one (weights seed/profile, model args, input spec):
   out     - the reference's fp32 forward output (FullSubNet_Plus.forward,
@@ -340,10 +341,81 @@ def main_reference_facts():
     print(f"{FACTS_PATH}, {BASE_MODEL_PATH} [{os.path.getsize(BASE_MODEL_PATH) / 1024:.0f} KB]")
 
 
+PLANNER_PLANS_PATH = os.path.join(GOLDEN_DIR, "planner_plans.json")
+# the sequence counts tests/test_host.py plans, then every batch of 257-bin utterances up to B = 64
+PLANNER_ROWS = sorted({1, 31, 32, 160, 192, 257, 352, 514, 640, 1285, 1344, 1345, 1376, 1542, 2056, 2800, 3084, 3300, 3400, 3500,
+                       3855, 4096, 4112, 4256, 5397, 5440, 5441, 5654, 7967, 8192, 8224, 8481, 9252, 10280, 12336, 16448, 24672,
+                       65792} | {257 * b for b in range(1, 65)})
+# cost tables of test_planner_follows_the_cost_table_and_two_workgroups_per_cu (None: the built-in one)
+PLANNER_TABLES = {
+    "builtin": None,
+    "cheap2": [9, 12, 19, 25, 29, 38, 55, 70, 76, 95, 151, 190, 208, 0.11, 9, 19, 29, 55, 1000],
+    "slow_k": [100, 100, 100, 100, 100, 100, 100, 100, 76, 95, 151, 190, 208, 0.11, 100, 100, 100, 100, 1000],
+    "cheap_hp": [100] * 8 + [760, 950, 1510, 1900, 208, 0.11, 100, 100, 100, 100, 1000, 9, 11],
+    "cheap_w": [100] * 8 + [760, 950, 1510, 1900, 208, 0.11, 100, 100, 100, 100, 1000, 1e9, 1e9, 11, 19, 10, 18],
+}
+
+
+def planner_plans():
+    """What the host-only planner entry points of the built library return (no device, no reference): fsnp_debug_plan_rows2 over
+    PLANNER_ROWS x hidden x cell (gru 0 / 1 / 2) x column-split kernels off / on x workgroups per CU x PLANNER_TABLES, and
+    fsnp_debug_fullsubnet_pairing for B = 1 ... 512 at one / two full-band workgroups per CU.  Full plans for the built-in table at
+    hidden 256 and 384, a sha256 of the plans of every other configuration (key "hidden/gru/coop/occ/table")."""
+    import ctypes as ct
+    import hashlib
+    from fullsubnet_plus_amd import _lib
+    lib = _lib.load()
+    nc = _lib.NUM_COSTS
+    buf = (ct.c_int32 * (8 * 256))()
+    plans, digests = {}, {}
+    for name, table in PLANNER_TABLES.items():
+        arr = (ct.c_double * nc)(*(list(table) + [1e9] * (nc - len(table)))) if table else None
+        for hidden in (128, 256, 384, 512):
+            for gru in (0, 1, 2):
+                for coop in (0, 1):
+                    for occ in (1, 2):
+                        key = f"{hidden}/{gru}/{coop}/{occ}/{name}"
+                        got = []
+                        for rows in PLANNER_ROWS:
+                            n = lib.fsnp_debug_plan_rows2(rows, 256, hidden, gru, coop, 0.97, occ, arr, buf, 256)
+                            assert 0 <= n < 256, (key, rows, lib.fsnp_last_error())
+                            got.append(list(buf[:8 * n]))
+                        if table is None and hidden in (256, 384):
+                            plans[key] = got
+                        else:
+                            digests[key] = hashlib.sha256(json.dumps(got).encode()).hexdigest()
+    out = (ct.c_int32 * (9 * 16))()
+    pairing = {}
+    for fb_per_cu in (1, 2):
+        recs = []
+        for batch in range(1, 513):
+            n = lib.fsnp_debug_fullsubnet_pairing(batch, 256, fb_per_cu, None, out, 16)
+            assert 0 <= n < 16, (batch, lib.fsnp_last_error())
+            recs.append(list(out[:9 * n]))
+        pairing[str(fb_per_cu)] = recs
+    return {"rows": PLANNER_ROWS, "plans": plans, "sha256": digests, "fullsubnet_pairing": pairing}
+
+
+def main_planner_plans():
+    """tests/golden/planner_plans.json: planner_plans() of the library as built in this tree."""
+    got = planner_plans()
+    with open(PLANNER_PLANS_PATH, "w") as f:
+        f.write("{\n")
+        f.write(f' "rows": {json.dumps(got["rows"], separators=(",", ":"))},\n')
+        for part in ("plans", "sha256", "fullsubnet_pairing"):      # one configuration per line
+            lines = [f"  {json.dumps(k)}:{json.dumps(v, separators=(',', ':'))}" for k, v in got[part].items()]
+            f.write(f' "{part}": {{\n' + ",\n".join(lines) + "\n }" + (",\n" if part != "fullsubnet_pairing" else "\n"))
+        f.write("}\n")
+    print(f"{PLANNER_PLANS_PATH} [{os.path.getsize(PLANNER_PLANS_PATH) / 1024:.0f} KB]")
+
+
 def main():
     only = set(sys.argv[1:])
     if only == {"reference_facts"}:
         main_reference_facts()
+        return
+    if only == {"planner_plans"}:
+        main_planner_plans()
         return
     if not only or any(n.startswith("fsn_") for n in only):
         main_fsn(only)

@@ -1264,6 +1264,22 @@ def test_fullsubnet_pipelined_pairs_fit_every_xcd():
     assert _pairing(64, 2, cheap_hp)[0]["side_by_side"] == 1                                               # (24 + 8 at two per CU)
 
 
+def test_planner_output_matches_the_pinned_plans():
+    """tests/golden/planner_plans.json (oracle/make_golden.py planner_plans): every plan of fsnp_debug_plan_rows2 over the grid of
+    sequence counts, hidden sizes, cells, column-split switch, workgroups per CU and cost tables, and every fsnp_debug_fullsubnet_pairing
+    record for B = 1 ... 512, as the library computed them when the fixture was written.  A change to the planner's choices shows here."""
+    import json
+    from oracle.make_golden import PLANNER_PLANS_PATH, planner_plans
+    with open(PLANNER_PLANS_PATH) as f:
+        want = json.load(f)
+    got = planner_plans()
+    assert got["rows"] == want["rows"]
+    for part in ("plans", "sha256", "fullsubnet_pairing"):
+        assert got[part].keys() == want[part].keys(), part
+        bad = [k for k in want[part] if got[part][k] != want[part][k]]
+        assert not bad, (part, bad[:8])
+
+
 def test_oracle_is_only_reachable_from_the_allowed_places():
     """The oracle is test infrastructure: the product package never imports it, bench.py only inside its cpu_baseline
     leg, __graft_entry__ only inside build() (import check of the checker) and smoke()."""
