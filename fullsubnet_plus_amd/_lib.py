@@ -102,7 +102,15 @@ SYMBOLS = {
     "fsnp_version": (ctypes.c_char_p, []),
 }
 
-ABI_VERSION = 11         # FSNP_ABI_VERSION of the include/fsnp.h these signatures were written against
+# every symbol include/fsnp_lengths.h declares (batches of clips of different lengths, ABI 12)
+LENGTHS_SYMBOLS = {
+    "fsnp_forward_lengths": (c_i32, [c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(c_i64 * 3 * 3), ctypes.POINTER(c_i32), c_vp, c_i32, c_i32,
+                                     c_vp]),
+    "fsnp_forward_complex_lengths": (c_i32, [c_vp, c_vp, ctypes.POINTER(c_i64 * 3), ctypes.POINTER(c_i32), c_vp, c_i32, c_i32, c_vp]),
+    "fsnp_enhance_wave_lengths": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i64, ctypes.POINTER(c_i32), c_i32, c_i32, c_vp]),
+}
+
+ABI_VERSION = 12         # FSNP_ABI_VERSION of the include/fsnp.h these signatures were written against
 
 _lib = None
 
@@ -123,7 +131,7 @@ def load(build_if_missing=True):
     if not os.path.exists(path):
         raise RuntimeError(f"{path} is missing: run `python -m fullsubnet_plus_amd._build`")
     lib = ctypes.CDLL(path)
-    for name, (res, args) in SYMBOLS.items():
+    for name, (res, args) in list(SYMBOLS.items()) + list(LENGTHS_SYMBOLS.items()):
         fn = getattr(lib, name)          # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

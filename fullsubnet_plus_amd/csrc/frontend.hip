@@ -53,7 +53,8 @@ __device__ __forceinline__ void repack_tile_stats(TileFn tile, double* __restric
 }
 
 __global__ __launch_bounds__(256) void fe_repack_kernel(StridedIn in, float* __restrict__ raw, double* __restrict__ colsum,
-                                                        double* __restrict__ tot, int B, int T, int Tp, int F, int FP) {
+                                                        double* __restrict__ tot, int B, int T, int Tp, int F, int FP,
+                                                        const int* __restrict__ lens) {
     __shared__ float tile[32][33];
     __shared__ double red[8][33];
     __shared__ double wred[8];
@@ -63,15 +64,16 @@ __global__ __launch_bounds__(256) void fe_repack_kernel(StridedIn in, float* __r
     const float* __restrict__ src = in.p[branch] + (long)b * in.sb[branch];
     const long sF = in.sf[branch], sT = in.st[branch];
     const bool f_fast = sF <= sT;
+    const int Tb = lens ? lens[b] : T;       // frames past a clip's own length are never read: they are the look-ahead pad's zeros
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int r = ty + 8 * i;
         if (f_fast) {
             const int f = f0 + tx, t = t0 + r;
-            tile[r][tx] = (f < F && t < T) ? src[f * sF + t * sT] : 0.0f;
+            tile[r][tx] = (f < F && t < Tb) ? src[f * sF + t * sT] : 0.0f;
         } else {
             const int t = t0 + tx, f = f0 + r;
-            tile[tx][r] = (f < F && t < T) ? src[f * sF + t * sT] : 0.0f;
+            tile[tx][r] = (f < F && t < Tb) ? src[f * sF + t * sT] : 0.0f;
         }
     }
     __syncthreads();
@@ -94,7 +96,7 @@ __global__ __launch_bounds__(256) void fe_repack_kernel(StridedIn in, float* __r
 __global__ __launch_bounds__(256) void fe_repack_complex_kernel(const float2* __restrict__ x, long sb, long sf, long st,
                                                                 float* __restrict__ raw, double* __restrict__ colsum,
                                                                 double* __restrict__ tot, int nbr, int B, int T, int Tp,
-                                                                int F, int FP) {
+                                                                int F, int FP, const int* __restrict__ lens) {
     __shared__ float2 tile[32][33];
     __shared__ double red[8][33];
     __shared__ double wred[8];
@@ -103,15 +105,16 @@ __global__ __launch_bounds__(256) void fe_repack_complex_kernel(const float2* __
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     const float2* __restrict__ src = x + (long)b * sb;
     const bool f_fast = sf <= st;
+    const int Tb = lens ? lens[b] : T;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int r = ty + 8 * i;
         if (f_fast) {
             const int f = f0 + tx, t = t0 + r;
-            tile[r][tx] = (f < F && t < T) ? src[f * sf + t * st] : make_float2(0.f, 0.f);
+            tile[r][tx] = (f < F && t < Tb) ? src[f * sf + t * st] : make_float2(0.f, 0.f);
         } else {
             const int t = t0 + tx, f = f0 + r;
-            tile[tx][r] = (f < F && t < T) ? src[f * sf + t * st] : make_float2(0.f, 0.f);
+            tile[tx][r] = (f < F && t < Tb) ? src[f * sf + t * st] : make_float2(0.f, 0.f);
         }
     }
     __syncthreads();
@@ -159,7 +162,7 @@ __global__ __launch_bounds__(64) void fe_frame_kernel(const float* __restrict__ 
 
 // one workgroup per (branch, utt): chunked prefix scan over frames
 __global__ __launch_bounds__(256) void fe_scan_kernel(const double* __restrict__ frame, NormMD* __restrict__ md,
-                                                      int B, int Tp, int F, int norm_type) {
+                                                      int B, int Tp, int F, int norm_type, const int* __restrict__ tpb) {
     __shared__ double cs[256], cq[256];
     const long base = ((long)blockIdx.y * B + blockIdx.x) * Tp;
     const int tid = threadIdx.x;
@@ -173,7 +176,8 @@ __global__ __launch_bounds__(256) void fe_scan_kernel(const double* __restrict__
     if (!cumulative) {
         double ts = 0.0, tq = 0.0;
         for (int i = 0; i < 256; ++i) { ts += cs[i]; tq += cq[i]; }
-        const NormMD r = norm_md(norm_type, ts, tq, (double)F * Tp);
+        // (frames past the clip are zeros: they add nothing to the sums, only the count is the clip's own)
+        const NormMD r = norm_md(norm_type, ts, tq, (double)F * utt_frames(tpb, blockIdx.x, Tp));
         for (int t = lo; t < hi; ++t) md[base + t] = r;
     } else {
         double ps = 0.0, pq = 0.0;
@@ -190,9 +194,10 @@ __global__ __launch_bounds__(256) void fe_scan_kernel(const double* __restrict__
 static int fsum_rows_per_wg(int B) { return B >= 8 ? 32 : B >= 4 ? 16 : B >= 2 ? 8 : 4; }
 // (blockDim = the smallest multiple of 64 that covers F up to 512: see sb_offline_stats_kernel)
 __global__ __launch_bounds__(512) void fe_fsum_kernel(const float* __restrict__ raw, const NormMD* __restrict__ md,
-                                                      double* __restrict__ fsum, int B, int Tp, int F, int FP, int rows) {
+                                                      double* __restrict__ fsum, int B, int Tp, int F, int FP, int rows,
+                                                      const int* __restrict__ tpb) {
     const long ub = (long)blockIdx.z * B + blockIdx.y;
-    const int t0 = blockIdx.x * rows, t1 = min(t0 + rows, Tp);
+    const int t0 = blockIdx.x * rows, t1 = min(t0 + rows, utt_frames(tpb, blockIdx.y, Tp));
     for (int f = threadIdx.x; f < F; f += blockDim.x) {
         double s = 0.0;
         for (int t = t0; t < t1; ++t) {
@@ -207,6 +212,7 @@ struct GateArgs {
     FrontendWeights w;
     const float* raw; NormMD* md; const double* fsum; const double* tot; float* gate;
     int B, Tp, F, FP;
+    const int* tpb;            // nullptr, or per-utterance frames (Dims::tpb): the pooled means / max / valid-conv outputs cover those
     int offline_norm;          // FSNP_NORM_OFFLINE_*: (m, d) come from `tot` here and are WRITTEN to md for every frame; fsum = raw column
                                // sums.  -1: cumulative norms - md and fsum (of the normalised input) were produced by fe_scan / fe_fsum
 };
@@ -230,6 +236,7 @@ __global__ __launch_bounds__(kGateThreads) void fe_gate_kernel(GateArgs g) {
     const long ub = (long)branch * g.B + b;
     const int tid = threadIdx.x;
     const int kmax = max(max(g.w.ksize[0], g.w.ksize[1]), g.w.ksize[2]);
+    const int Tv = utt_frames(g.tpb, b, Tp);   // this utterance's frames: everything past them is padding the reference never saw
 
     const int att = g.w.attention;
     float* sqmax = edge;               // [FP] CBAM: max over t (edge is unused then)
@@ -238,13 +245,13 @@ __global__ __launch_bounds__(kGateThreads) void fe_gate_kernel(GateArgs g) {
     const bool offline = g.offline_norm >= 0;
     NormMD mu{0.0f, 1.0f};
     if (offline) {
-        mu = norm_md(g.offline_norm, g.tot[ub * 2], g.tot[ub * 2 + 1], (double)F * Tp);
+        mu = norm_md(g.offline_norm, g.tot[ub * 2], g.tot[ub * 2 + 1], (double)F * Tv);
         for (int t = tid; t < Tp; t += NTHR) g.md[ub * Tp + t] = mu;
     }
     if (att == FSNP_ATT_TSSE) {
         for (int i = tid; i < 2 * (kmax - 1) * F; i += NTHR) {
             const int side = i / ((kmax - 1) * F), r = (i / F) % (kmax - 1), f = i % F;
-            const int t = side == 0 ? r : Tp - 1 - r;                    // r-th frame from the start / from the end
+            const int t = side == 0 ? r : Tv - 1 - r;                    // r-th frame from the start / from the end
             const NormMD m = offline ? mu : g.md[ub * Tp + t];
             edge[(side * MAXK + r) * FP + f] = (g.raw[(ub * Tp + t) * FP + f] - m.m) / m.d;
         }
@@ -252,15 +259,15 @@ __global__ __launch_bounds__(kGateThreads) void fe_gate_kernel(GateArgs g) {
     }
     // sum over t of the normalised input: sum_t (x - m) / d = (column sum - T' m) / d for the offline norms
     auto total_of = [&](int f) -> double {
-        return offline ? (g.fsum[ub * FP + f] - (double)Tp * (double)mu.m) / (double)mu.d : g.fsum[ub * FP + f];
+        return offline ? (g.fsum[ub * FP + f] - (double)Tv * (double)mu.m) / (double)mu.d : g.fsum[ub * FP + f];
     };
     if (att != FSNP_ATT_TSSE) {
         for (int f = tid; f < F; f += NTHR) {
             // SE / ECA / CBAM squeeze = mean over time (attention_model.py:31, :349, :320)
-            sq[f] = (float)(total_of(f) / (double)Tp);
+            sq[f] = (float)(total_of(f) / (double)Tv);
             if (att == FSNP_ATT_CBAM) {                      // + max over time (attention_model.py:321)
                 float mx = -3.4e38f;
-                for (int t = 0; t < Tp; ++t) {
+                for (int t = 0; t < Tv; ++t) {
                     const NormMD m = offline ? mu : g.md[ub * Tp + t];
                     mx = fmaxf(mx, (g.raw[(ub * Tp + t) * FP + f] - m.m) / m.d);
                 }
@@ -282,7 +289,7 @@ __global__ __launch_bounds__(kGateThreads) void fe_gate_kernel(GateArgs g) {
                 acc += (double)wk[j] * (S - pj - sj);
                 if (j + 1 < K) { pj += (double)first[j * FP]; sj -= (double)last[(K - 2 - j) * FP]; }
             }
-            const float feat = (float)(acc / (double)(Tp - K + 1)) + g.w.conv_b[branch][c][f];
+            const float feat = (float)(acc / (double)(Tv - K + 1)) + g.w.conv_b[branch][c][f];
             feat3[c * FP + f] = fmaxf(feat, 0.f);
         }
         __syncthreads();
@@ -441,7 +448,7 @@ void launch_frontend(const Dims& d, int norm_type, const float* const in[3], con
     if (is_complex) {
         hipLaunchKernelGGL(fe_repack_complex_kernel, dim3(cdiv(d.FP, 32), cdiv(d.Tp, 32), d.B), dim3(256), 0, s,
                            reinterpret_cast<const float2*>(in[0]), (long)strides[0][0], (long)strides[0][1],
-                           (long)strides[0][2], buf.raw, colsum, buf.tot, 3, d.B, d.T, d.Tp, d.F, d.FP);
+                           (long)strides[0][2], buf.raw, colsum, buf.tot, 3, d.B, d.T, d.Tp, d.F, d.FP, d.lens);
     } else {
         StridedIn si;
         for (int i = 0; i < 3; ++i) {
@@ -449,19 +456,19 @@ void launch_frontend(const Dims& d, int norm_type, const float* const in[3], con
             si.sb[i] = strides[i][0]; si.sf[i] = strides[i][1]; si.st[i] = strides[i][2];
         }
         hipLaunchKernelGGL(fe_repack_kernel, dim3(cdiv(d.FP, 32), cdiv(d.Tp, 32), 3 * d.B), dim3(256), 0, s, si, buf.raw, colsum, buf.tot,
-                           d.B, d.T, d.Tp, d.F, d.FP);
+                           d.B, d.T, d.Tp, d.F, d.FP, d.lens);
     }
     if (!offline) {
         hipLaunchKernelGGL(fe_frame_kernel, dim3(d.Tp, d.B, 3), dim3(64), 0, s, buf.raw, buf.frame, d.B, d.Tp, d.F, d.FP);
-        hipLaunchKernelGGL(fe_scan_kernel, dim3(d.B, 3), dim3(256), 0, s, buf.frame, buf.md, d.B, d.Tp, d.F, norm_type);
+        hipLaunchKernelGGL(fe_scan_kernel, dim3(d.B, 3), dim3(256), 0, s, buf.frame, buf.md, d.B, d.Tp, d.F, norm_type, d.tpb);
         const int frows = fsum_rows_per_wg(d.B);
         const int fthreads = d.F <= 256 ? 256 : d.F >= 512 ? 512 : (d.F + 63) / 64 * 64;
         hipLaunchKernelGGL(fe_fsum_kernel, dim3(cdiv(d.Tp, frows), d.B, 3), dim3(fthreads), 0, s, buf.raw, buf.md, buf.fsum,
-                           d.B, d.Tp, d.F, d.FP, frows);
+                           d.B, d.Tp, d.F, d.FP, frows, d.tpb);
     }
     GateArgs g;
     g.w = w; g.raw = buf.raw; g.md = buf.md; g.fsum = buf.fsum; g.tot = buf.tot; g.gate = buf.gate;
-    g.B = d.B; g.Tp = d.Tp; g.F = d.F; g.FP = d.FP;
+    g.B = d.B; g.Tp = d.Tp; g.F = d.F; g.FP = d.FP; g.tpb = d.tpb;
     g.offline_norm = offline ? norm_type : -1;
     // 37 FP floats of dynamic LDS: beyond 64 KiB (num_freqs > 440) the kernel needs the opt-in; beyond a CU's LDS the launch fails
     // loudly (hipGetLastError in fsnp_forward)
@@ -481,7 +488,7 @@ void launch_frontend_mag(const Dims& d, int norm_type, const float* mag, const i
     if (is_complex) {
         hipLaunchKernelGGL(fe_repack_complex_kernel, dim3(cdiv(d.FP, 32), cdiv(d.Tp, 32), d.B), dim3(256), 0, s,
                            reinterpret_cast<const float2*>(mag), (long)strides[0], (long)strides[1], (long)strides[2],
-                           buf.raw, nullptr, nullptr, 1, d.B, d.T, d.Tp, d.F, d.FP);
+                           buf.raw, nullptr, nullptr, 1, d.B, d.T, d.Tp, d.F, d.FP, d.lens);
     } else {
         StridedIn si;
         for (int i = 0; i < 3; ++i) {
@@ -489,10 +496,10 @@ void launch_frontend_mag(const Dims& d, int norm_type, const float* mag, const i
             si.sb[i] = strides[0]; si.sf[i] = strides[1]; si.st[i] = strides[2];
         }
         hipLaunchKernelGGL(fe_repack_kernel, dim3(cdiv(d.FP, 32), cdiv(d.Tp, 32), d.B), dim3(256), 0, s, si, buf.raw, nullptr, nullptr,
-                           d.B, d.T, d.Tp, d.F, d.FP);
+                           d.B, d.T, d.Tp, d.F, d.FP, d.lens);
     }
     hipLaunchKernelGGL(fe_frame_kernel, dim3(d.Tp, d.B, 1), dim3(64), 0, s, buf.raw, buf.frame, d.B, d.Tp, d.F, d.FP);
-    hipLaunchKernelGGL(fe_scan_kernel, dim3(d.B, 1), dim3(256), 0, s, buf.frame, buf.md, d.B, d.Tp, d.F, norm_type);
+    hipLaunchKernelGGL(fe_scan_kernel, dim3(d.B, 1), dim3(256), 0, s, buf.frame, buf.md, d.B, d.Tp, d.F, norm_type, d.tpb);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -510,17 +517,17 @@ void launch_attention_stage(const Dims& d, const FrontendWeights& w, const float
     StridedIn si;
     for (int i = 0; i < 3; ++i) { si.p[i] = in; si.sb[i] = strides[0]; si.sf[i] = strides[1]; si.st[i] = strides[2]; }
     hipLaunchKernelGGL(fe_repack_kernel, dim3(cdiv(d.FP, 32), cdiv(d.Tp, 32), d.B), dim3(256), 0, s, si, buf.raw, nullptr, nullptr,
-                       d.B, d.T, d.Tp, d.F, d.FP);
+                       d.B, d.T, d.Tp, d.F, d.FP, nullptr);
     const long nmd = (long)d.B * d.Tp;
     hipLaunchKernelGGL(fe_identity_md_kernel, dim3((unsigned)((nmd + 255) / 256)), dim3(256), 0, s, buf.md, nmd);
     const int frows = fsum_rows_per_wg(d.B);
     const int fthreads = d.F <= 256 ? 256 : d.F >= 512 ? 512 : (d.F + 63) / 64 * 64;
-    hipLaunchKernelGGL(fe_fsum_kernel, dim3(cdiv(d.Tp, frows), d.B, 1), dim3(fthreads), 0, s, buf.raw, buf.md, buf.fsum, d.B, d.Tp, d.F, d.FP, frows);
+    hipLaunchKernelGGL(fe_fsum_kernel, dim3(cdiv(d.Tp, frows), d.B, 1), dim3(fthreads), 0, s, buf.raw, buf.md, buf.fsum, d.B, d.Tp, d.F, d.FP, frows, nullptr);
     GateArgs g;
     g.w = w;
     g.w.subband_num = 1;
     g.raw = buf.raw; g.md = buf.md; g.fsum = buf.fsum; g.tot = buf.tot; g.gate = buf.gate;
-    g.B = d.B; g.Tp = d.Tp; g.F = d.F; g.FP = d.FP;
+    g.B = d.B; g.Tp = d.Tp; g.F = d.F; g.FP = d.FP; g.tpb = nullptr;
     g.offline_norm = -1;
     static PerDeviceOnce gate_once;
     gate_once.run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fe_gate_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256); });
@@ -534,7 +541,7 @@ void launch_repack_plane(const Dims& d, const float* in, const int64_t strides[3
     StridedIn si;
     for (int i = 0; i < 3; ++i) { si.p[i] = in; si.sb[i] = strides[0]; si.sf[i] = strides[1]; si.st[i] = strides[2]; }
     hipLaunchKernelGGL(fe_repack_kernel, dim3(cdiv(d.FP, 32), cdiv(d.Tp, 32), d.B), dim3(256), 0, s, si, raw, nullptr, nullptr,
-                       d.B, d.T, d.Tp, d.F, d.FP);
+                       d.B, d.T, d.Tp, d.F, d.FP, nullptr);
 }
 
 }  // namespace fsnp

@@ -201,6 +201,63 @@ __global__ __launch_bounds__(256) void prologue_kernel(PrologueArgs a) {
     weight_watch_block(a.segs, a.nseg, a.watch_acc, 0, a.err_host, b - a.zero_blocks - a.rows_blocks, a.watch_blocks);
 }
 
+// ---- clips of different lengths (fsnp_forward_lengths).  The host's lengths reach the workspace as kernel arguments - no copy from
+// pageable memory, nothing to synchronise, the caller may reuse its buffer when the call returns - 256 utterances per launch:
+// lens[b] = lengths[b], tpb[b] = lengths[b] + look_ahead (Dims::lens / Dims::tpb)
+constexpr int kLengthsPerLaunch = 256;
+struct LengthArgs { int* lens; int* tpb; int b0, n, LA; int v[kLengthsPerLaunch]; };
+__global__ __launch_bounds__(kLengthsPerLaunch) void set_lengths_kernel(LengthArgs a) {
+    const int i = threadIdx.x;
+    if (i < a.n) { a.lens[a.b0 + i] = a.v[i]; a.tpb[a.b0 + i] = a.v[i] + a.LA; }
+}
+static void launch_set_lengths(const int32_t* lengths, int B, int LA, int* lens, int* tpb, hipStream_t s) {
+    for (int b0 = 0; b0 < B; b0 += kLengthsPerLaunch) {
+        LengthArgs a{};
+        a.lens = lens; a.tpb = tpb; a.b0 = b0; a.n = std::min(kLengthsPerLaunch, B - b0); a.LA = LA;
+        for (int i = 0; i < a.n; ++i) a.v[i] = lengths[b0 + i];
+        hipLaunchKernelGGL(set_lengths_kernel, dim3(1), dim3(kLengthsPerLaunch), 0, s, a);
+    }
+}
+// frames [lengths[b], T) of every row of utterance b of the [B][rows_per_utt][T] mask are written as 0 (the sub-band model ran over
+// them: causal, so the frames before lengths[b] never saw them, but what it wrote there is no part of the clip)
+__global__ __launch_bounds__(256) void zero_tails_kernel(float* __restrict__ out, const int* __restrict__ lens, int rows_per_utt, int T,
+                                                         long total) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const long row = i / T;
+        const int t = (int)(i - row * T);
+        if (t >= lens[row / rows_per_utt]) out[i] = 0.0f;
+    }
+}
+static void launch_zero_tails(float* out, const int* lens, int B, int rows_per_utt, int T, hipStream_t s) {
+    const long total = (long)B * rows_per_utt * T;
+    const int blocks = (int)std::min<long>((total + 255) / 256, 4096);
+    hipLaunchKernelGGL(zero_tails_kernel, dim3(blocks), dim3(256), 0, s, out, lens, rows_per_utt, T, total);
+}
+
+int check_lengths(const fsnp_handle* h, const int32_t* lengths, int batch, int frames, const char* where) {
+    if (!lengths) { set_error("%s: null lengths", where); return 1; }
+    const bool fsn = h->model == FSNP_MODEL_FULLSUBNET;
+    // out of scope, refused rather than mis-computed: the ECA channel regrouping of subband_num > 1, and the sub-band TCN stack (its
+    // GroupNorm is per sub-band sequence, which would need a length per slot)
+    if (!fsn && h->cfg.subband_num > 1) { set_error("%s: per-utterance lengths are not supported with subband_num = %d > 1", where, h->cfg.subband_num); return 2; }
+    if (h->sb_tcn) { set_error("%s: per-utterance lengths are not supported with the sub-band sequence_model \"TCN\"", where); return 2; }
+    int kmax = 1;
+    for (int c = 0; c < 3; ++c) kmax = std::max(kmax, (int)h->cfg.kersize[c]);
+    const bool tsse = !fsn && h->cfg.attention == FSNP_ATT_TSSE;
+    for (int b = 0; b < batch; ++b) {
+        if (lengths[b] < 1 || lengths[b] > frames) {
+            set_error("%s: utterance %d: length %d outside [1, %d]", where, b, (int)lengths[b], frames);
+            return 2;
+        }
+        if (tsse && lengths[b] + h->cfg.look_ahead < kmax) {
+            set_error("%s: utterance %d: too few frames: length %d + look_ahead %d = %d < largest TSSE kernel %d", where, b, (int)lengths[b],
+                      (int)h->cfg.look_ahead, (int)lengths[b] + h->cfg.look_ahead, kmax);
+            return 2;
+        }
+    }
+    return 0;
+}
+
 // Column-split launches need all their workgroups co-resident.  Two of them running at once (two handles / two streams
 // of one process) could each hold part of the chip and wait for peers that cannot be scheduled, so within a process
 // they are chained per device: each one waits for the previous one's completion event.  Other kernels always finish,
@@ -392,7 +449,9 @@ static int rows_per_utt(const fsnp_handle* h, int mode) {
     return mode == FSNP_MODE_PARITY ? h->F / h->cfg.num_groups_in_drop_band : h->F;
 }
 
-static Workspace plan_workspace(const fsnp_handle* h, int B, int T, int mode) {
+// ragged: the forward takes per-utterance lengths (fsnp_forward_lengths): room for them behind everything else, so that every other
+// offset, and the size of a forward without lengths, are what they are without it
+static Workspace plan_workspace(const fsnp_handle* h, int B, int T, int mode, bool ragged = false) {
     Workspace w{};
     const size_t Tp = (size_t)T + h->cfg.look_ahead;
     const bool fsn = h->model == FSNP_MODEL_FULLSUBNET;
@@ -432,6 +491,7 @@ static Workspace plan_workspace(const fsnp_handle* h, int B, int T, int mode) {
     w.sbt_gn = take(h->sb_tcn ? (size_t)8 * 2 * nrows_pad * kGnStride * 8 : 0);
     w.zero_end = o;
     w.dbg_tcn0 = take(h->debug ? (size_t)B * Tp * h->FP * 4 : 0);
+    w.lens = take(ragged ? (size_t)2 * B * 4 : 0);
     w.total = o;
     return w;
 }
@@ -1055,7 +1115,7 @@ size_t fsnp_workspace_bytes(const fsnp_handle* h, int32_t batch, int32_t frames,
 
 static int forward_impl(fsnp_handle* h, const float* mag, const float* real, const float* imag, bool is_complex,
                         const int64_t strides[3][3], float* out, int32_t batch, int32_t frames,
-                        int32_t mode, int32_t batch_offset, int32_t global_batch, void* hip_stream) {
+                        int32_t mode, int32_t batch_offset, int32_t global_batch, void* hip_stream, const int32_t* lengths = nullptr) {
     if (batch <= 0 || frames <= 0) { set_error("fsnp_forward: empty input (B=%d, T=%d)", batch, frames); return 2; }
     if (!h || !mag || !out || !strides) { set_error("fsnp_forward: null argument"); return 1; }
     const bool fsn = h->model == FSNP_MODEL_FULLSUBNET;
@@ -1076,6 +1136,10 @@ static int forward_impl(fsnp_handle* h, const float* mag, const float* real, con
     for (int c = 0; c < 3; ++c) kmax = kmax > h->cfg.kersize[c] ? kmax : h->cfg.kersize[c];
     if (!fsn && h->cfg.attention == FSNP_ATT_TSSE && d.Tp < kmax) { set_error("too few frames: T + look_ahead = %d < largest TSSE kernel %d", d.Tp, kmax); return 2; }
     if ((double)3 * d.B * d.Tp * d.FP * 2 > 2.0e9) { set_error("batch too large for 32-bit gather offsets; split the batch"); return 2; }
+    if (lengths) {
+        if (mode != FSNP_MODE_FULL) { set_error("fsnp_forward_lengths: per-utterance lengths need FULL mode"); return 2; }
+        if (const int rc = check_lengths(h, lengths, batch, frames, "fsnp_forward_lengths")) return rc;
+    }
     const int fb_units = (fsn && !h->generic_fb) ? fb_coop_units(h, batch) : 0;
     if (fsn && !h->generic_fb && fb_units == 0) { set_error("FullSubNet: at most %d utterances per call (full-band LSTM residency); split the batch", 32 * (h->num_cus_real / 16)); return 2; }
 
@@ -1088,7 +1152,7 @@ static int forward_impl(fsnp_handle* h, const float* mag, const float* real, con
                   num_rows, h->num_cus_real, h->gru ? "GRU" : "LSTM", h->H / 128);
         return 2;
     }
-    const Workspace w = plan_workspace(h, batch, frames, mode);
+    const Workspace w = plan_workspace(h, batch, frames, mode, lengths != nullptr);
     if (order_after_last_forward(h, s)) return 4;
     if (ensure_workspace(h, w.total, s)) return 4;
     // pipelined mode: alternate between the two workspace halves; the half about to be rebuilt was last read by the
@@ -1143,6 +1207,11 @@ static int forward_impl(fsnp_handle* h, const float* mag, const float* real, con
         hipLaunchKernelGGL(prologue_kernel, dim3(pa.zero_blocks + pa.rows_blocks + pa.watch_blocks), dim3(256), 0, st, pa);
         return 0;
     };
+    if (lengths) {
+        int* lens = reinterpret_cast<int*>(base + w.lens);
+        launch_set_lengths(lengths, batch, d.LA, lens, lens + batch, s);
+        d.lens = lens; d.tpb = lens + batch;
+    }
     if (prologue(s)) return 4;
 
     if (!fsn) {
@@ -1203,6 +1272,7 @@ static int forward_impl(fsnp_handle* h, const float* mag, const float* real, con
         ga.NFBN = h->cfg.fb_num_neighbors;
         launch_sb_gather(ga, s);
         Dims ds = d;
+        ds.lens = ds.tpb = nullptr;       // (per-utterance lengths are refused with a sub-band TCN: check_lengths)
         ds.B = num_slots; ds.F = h->NIN; ds.FP = h->XS;
         TcnBuffers tb{};
         tb.att = fptr(w.sbt_x0); tb.x = fptr(w.sbt_x); tb.y1 = fptr(w.sbt_y1); tb.y2 = fptr(w.sbt_y2);
@@ -1277,6 +1347,14 @@ static int forward_impl(fsnp_handle* h, const float* mag, const float* real, con
         if (const int vr = verify_sample(h, plan, d, a, sbuf, defer_all ? h->side_stream : s)) return vr;
         if (defer_all) FSNP_HIP_CHECK(hipEventRecord(h->ev_side[slot], h->side_stream));       // the snapshot reads this workspace half too
     }
+    if (lengths) {
+        // behind the last sub-band launch that writes the mask (the side stream's, when the pipelined loop deferred any: those follow the
+        // caller's stream's chunks), and behind the verification pass / the sampled check's snapshot, which compare what the model wrote
+        const bool on_side = !verify_now && (defer_all || ndefer > 0);
+        hipStream_t ts = on_side ? h->side_stream : s;
+        launch_zero_tails(out, d.lens, batch, h->cfg.output_size * rows_per_utt(h, mode), frames, ts);
+        if (on_side) FSNP_HIP_CHECK(hipEventRecord(h->ev_side[slot], h->side_stream));     // (it reads this workspace half's lengths)
+    }
     FSNP_HIP_CHECK(hipGetLastError());
     h->last_ws = w; h->last_dims = d; h->have_last = true; h->last_base = base;
     return mark_forward_done(h, s);
@@ -1297,6 +1375,21 @@ int fsnp_forward_complex(fsnp_handle* h, const float* noisy, const int64_t strid
     return forward_impl(h, noisy, nullptr, nullptr, true, st, out, batch, frames, mode, batch_offset, global_batch, hip_stream);
 }
 
+int fsnp_forward_lengths(fsnp_handle* h, const float* mag, const float* real, const float* imag, const int64_t strides[3][3],
+                         const int32_t* lengths, float* out, int32_t batch, int32_t frames, void* hip_stream) {
+    if (!lengths) { set_error("fsnp_forward_lengths: null lengths"); return 1; }
+    return forward_impl(h, mag, real, imag, false, strides, out, batch, frames, FSNP_MODE_FULL, 0, batch, hip_stream, lengths);
+}
+
+int fsnp_forward_complex_lengths(fsnp_handle* h, const float* noisy, const int64_t strides[3], const int32_t* lengths, float* out,
+                                 int32_t batch, int32_t frames, void* hip_stream) {
+    if (!strides || !lengths) { set_error("fsnp_forward_complex_lengths: null argument"); return 1; }
+    int64_t st[3][3];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) st[i][j] = strides[j];
+    return forward_impl(h, noisy, nullptr, nullptr, true, st, out, batch, frames, FSNP_MODE_FULL, 0, batch, hip_stream, lengths);
+}
+
 int fsnp_reserve(fsnp_handle* h, int32_t max_batch, int32_t max_frames, int32_t mode, int32_t max_samples, void* hip_stream) {
     if (!h || max_batch <= 0 || max_frames <= 0 || max_samples < 0) { set_error("fsnp_reserve: bad argument"); return 1; }
     if (mode != FSNP_MODE_FULL && mode != FSNP_MODE_PARITY) { set_error("unknown mode %d", mode); return 2; }
@@ -1310,7 +1403,7 @@ int fsnp_reserve(fsnp_handle* h, int32_t max_batch, int32_t max_frames, int32_t 
     size_t need = 0;
     for (int b = 1; b <= max_batch; ++b) {
         if (mode == FSNP_MODE_PARITY && b <= h->cfg.num_groups_in_drop_band) continue;
-        need = std::max(need, plan_workspace(h, b, max_frames, mode).total);
+        need = std::max(need, plan_workspace(h, b, max_frames, mode, mode == FSNP_MODE_FULL).total);   // (FULL: room for lengths too)
     }
     if (ensure_workspace(h, need, s)) return 4;
     if (max_samples > 0) {

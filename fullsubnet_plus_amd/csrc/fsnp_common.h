@@ -23,7 +23,14 @@ struct Dims {
     int NSB;  // 2*sb_num_neighbors+1 (31)
     int NIN;  // LSTM input size (34)
     int LA;   // look_ahead
+    // clips of different lengths (fsnp_forward_lengths): device [B] arrays in the workspace, nullptr = every utterance is T frames long.
+    // lens[b] = lengths[b]; tpb[b] = lengths[b] + look_ahead, the frames every per-utterance reduction, halo and count covers
+    const int* lens = nullptr;
+    const int* tpb = nullptr;
 };
+
+// frames of utterance b that count (its own lengths[b] + look_ahead), or the batch's Tp
+__device__ __forceinline__ int utt_frames(const int* tpb, int b, int Tp) { return tpb ? tpb[b] : Tp; }
 
 // One (m_t, d_t) pair: normalised = (x - m) / d.
 struct NormMD { float m, d; };
@@ -148,6 +155,10 @@ void launch_linear_act(const float* A, int lda, const float* W, int ldw, const f
 void launch_stft_pad(const float* wav, long wav_stride, float* xp, long xp_stride, int B, int L, int n_fft, hipStream_t s);
 void launch_istft_ola(const float* frames, const float* window, float* wav, long wav_stride, int B, int T, int L, int n_fft,
                       hipStream_t s);
+// the same per row of a batch of clips of different lengths: samples[b] host values (kernel arguments, up to 256 rows per launch)
+void launch_stft_pad_lengths(const float* wav, long wav_stride, float* xp, long xp_stride, int B, const int* samples, int n_fft, hipStream_t s);
+void launch_istft_ola_lengths(const float* frames, const float* window, float* wav, long wav_stride, int B, int T, int L, const int* samples,
+                              int n_fft, hipStream_t s);
 void stft_build_matrices(int n_fft, float* fwd /*[N2 pad 384][n_fft]*/, float* inv /*[n_fft pad 384][K pad 16]*/,
                          float* window /*[n_fft]*/);
 

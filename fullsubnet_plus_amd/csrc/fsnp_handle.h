@@ -19,7 +19,9 @@ struct WeightSpec {
 struct Workspace {
     // offsets in bytes from the workspace base
     size_t att, fb, raw, x, y1, y2, gate, md, md_utt, md_row, rows, fb_rows, frame, sbt_x0, sbt_x, sbt_fb, sbt_y1, sbt_y2, zero_begin,
-        fsum, fe_tot, gn, sb_acc, coop_hx, coop_bar, coop_abort, fb_hx, fb_bar, sbt_gn, zero_end, dbg_tcn0, total;
+        fsum, fe_tot, gn, sb_acc, coop_hx, coop_bar, coop_abort, fb_hx, fb_bar, sbt_gn, zero_end, dbg_tcn0,
+        lens,   // fsnp_forward_lengths only (0 bytes otherwise): int32 [2][B] = lengths[b], lengths[b] + look_ahead
+        total;
 };
 
 struct TimingRec {
@@ -169,6 +171,9 @@ void build_specs(fsnp_handle* h);
 // cross-stream ordering of a handle's shared buffers (fsnp_abi.hip)
 int order_after_last_forward(fsnp_handle* h, hipStream_t s);
 int mark_forward_done(fsnp_handle* h, hipStream_t s);
+// clips of different lengths: 0 when lengths[0 .. batch) (host, frames per utterance) is acceptable for a forward of `frames` frames on
+// this handle, else 2 with the error set (naming the utterance).  Nothing is launched.
+int check_lengths(const fsnp_handle* h, const int32_t* lengths, int batch, int frames, const char* where);
 // fsnp_stft_abi.hip
 struct StftPlan {
     int n_fft, hop, F, N2, sp;          // sp = padded float stride of one internal spectrum row (multiple of 4)

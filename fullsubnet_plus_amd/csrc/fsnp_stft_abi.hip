@@ -143,4 +143,53 @@ int fsnp_enhance_wave(fsnp_handle* h, const float* wav, int64_t wav_stride, floa
     return mark_forward_done(h, s);
 }
 
+int fsnp_enhance_wave_lengths(fsnp_handle* h, const float* wav, int64_t wav_stride, float* out, int64_t out_stride, const int32_t* samples,
+                              int32_t batch, int32_t max_samples, void* hip_stream) {
+    if (!h || !wav || !out || !samples) { set_error("fsnp_enhance_wave_lengths: null argument"); return 1; }
+    if (batch <= 0) { set_error("fsnp_enhance_wave_lengths: empty input"); return 2; }
+    if (!h->committed) { set_error("fsnp_enhance_wave_lengths: weights not committed (call fsnp_commit_weights)"); return 2; }
+    if (h->cfg.output_size != 2) { set_error("fsnp_enhance_wave_lengths: the cIRM epilogue needs output_size = 2 (this handle: %d)", h->cfg.output_size); return 2; }
+    if (ensure_stft(h)) return 2;
+    const StftPlan p = stft_plan(h);
+    if (max_samples <= p.hop) { set_error("fsnp_enhance_wave_lengths: need more than n_fft/2 = %d samples (reflect padding)", p.hop); return 2; }
+    // every check of the forward too, before anything is enqueued: each clip's frame count is its own STFT's, T_b = 1 + samples[b] / hop
+    const int T = 1 + max_samples / p.hop;
+    std::vector<int32_t> frames(batch);
+    for (int b = 0; b < batch; ++b) {
+        if (samples[b] <= p.hop || samples[b] > max_samples) {
+            set_error("fsnp_enhance_wave_lengths: utterance %d: %d samples outside (n_fft/2 = %d, %d]", b, (int)samples[b], p.hop, max_samples);
+            return 2;
+        }
+        frames[b] = 1 + samples[b] / p.hop;
+    }
+    if (const int rc = check_lengths(h, frames.data(), batch, T, "fsnp_enhance_wave_lengths")) return rc;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    FSNP_ON_DEVICE(h);
+    const long xs = (long)align_up((size_t)max_samples + p.n_fft, 4);
+    const size_t xp_b = align_up((size_t)batch * xs * 4, 256), spec_b = align_up((size_t)batch * T * p.sp * 4 + 256, 256);
+    const size_t mask_b = align_up((size_t)batch * 2 * p.F * T * 4, 256), fr_b = (size_t)batch * T * p.n_fft * 4;
+    if (order_after_last_forward(h, s)) return 4;
+    if (ensure_io(h, xp_b + 2 * spec_b + mask_b + fr_b, s)) return 4;
+    float* xp = reinterpret_cast<float*>(h->io);
+    float* noisy = reinterpret_cast<float*>(h->io + xp_b);
+    float* enh = reinterpret_cast<float*>(h->io + xp_b + spec_b);
+    float* mask = reinterpret_cast<float*>(h->io + xp_b + 2 * spec_b);
+    float* fr = reinterpret_cast<float*>(h->io + xp_b + 2 * spec_b + mask_b);
+    // as fsnp_enhance_wave, with the reflect padding at each clip's end (frames past T_b see zeros: the forward never reads them)
+    launch_stft_pad_lengths(wav, wav_stride, xp, xs, batch, samples, p.n_fft, s);
+    launch_linear_act(xp, p.hop, h->d_stft + p.o_fwd, p.n_fft, h->d_stft + p.o_zero, noisy, p.sp, p.n_fft, p.N2, batch, T,
+                      FSNP_ACT_NONE, h->num_cus, s, xs, p.n_fft);
+    const int64_t cst[3] = {(int64_t)T * (p.sp / 2), 1, p.sp / 2};
+    const int rc = fsnp_forward_complex_lengths(h, noisy, cst, frames.data(), mask, batch, T, hip_stream);
+    if (rc) return rc;
+    if (h->pipeline && fsnp_flush(h, hip_stream)) return 4;
+    FSNP_HIP_CHECK(hipMemsetAsync(enh, 0, spec_b, s));
+    launch_apply_cirm(mask, noisy, cst, enh, cst, batch, p.F, T, s);      // (mask frames >= T_b are 0: decompress_cIRM(0) = 0)
+    launch_linear_act(enh, p.sp, h->d_stft + p.o_inv, p.inv_ld, h->d_stft + p.o_zero, fr, p.n_fft, p.N2, p.n_fft, batch, T,
+                      FSNP_ACT_NONE, h->num_cus, s, (long)T * p.sp, p.N2);
+    launch_istft_ola_lengths(fr, h->d_stft + p.o_win, out, out_stride, batch, T, max_samples, samples, p.n_fft, s);
+    FSNP_HIP_CHECK(hipGetLastError());
+    return mark_forward_done(h, s);
+}
+
 }  // extern "C"

@@ -70,6 +70,82 @@ void launch_istft_ola(const float* frames, const float* window, float* wav, long
                        wav_stride, T, L, n_fft, total);
 }
 
+// ---- clips of different lengths in one batch (fsnp_enhance_wave_lengths): row b is its own samples[b] long.  The sample counts travel
+// as kernel arguments (no copy to the device, nothing to synchronise), 256 rows per launch.
+constexpr int kLenRows = 256;
+struct RowLengths { int v[kLenRows]; };
+
+// reflect padding at each row's own end (torch.stft of the clip alone), zeros behind it
+__global__ __launch_bounds__(256) void stft_pad_lengths_kernel(const float* __restrict__ wav, long wav_stride, float* __restrict__ xp,
+                                                               long xp_stride, int half, long total, RowLengths len) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int b = (int)(i / xp_stride);
+    const int p = (int)(i - (long)b * xp_stride);
+    const int L = len.v[b];
+    float v = 0.0f;
+    if (p < L + 2 * half) {
+        int j = p - half;
+        if (j < 0) j = -j;
+        if (j >= L) j = 2 * (L - 1) - j;
+        v = wav[(long)b * wav_stride + j];
+    }
+    xp[i] = v;
+}
+
+void launch_stft_pad_lengths(const float* wav, long wav_stride, float* xp, long xp_stride, int B, const int* samples, int n_fft, hipStream_t s) {
+    for (int b0 = 0; b0 < B; b0 += kLenRows) {
+        const int rows = B - b0 < kLenRows ? B - b0 : kLenRows;
+        RowLengths len{};
+        for (int r = 0; r < rows; ++r) len.v[r] = samples[b0 + r];
+        const long total = (long)rows * xp_stride;
+        hipLaunchKernelGGL(stft_pad_lengths_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, wav + (long)b0 * wav_stride,
+                           wav_stride, xp + (long)b0 * xp_stride, xp_stride, n_fft / 2, total, len);
+    }
+}
+
+// overlap-add and window-envelope division over row b's own 1 + samples[b] / hop frames (torch.istft(..., length=samples[b]) of the
+// clip alone: frame T_b, which still overlaps the clip's last samples, is not part of it); samples past samples[b] are written as 0
+__global__ __launch_bounds__(256) void istft_ola_lengths_kernel(const float* __restrict__ frames, const float* __restrict__ window,
+                                                                float* __restrict__ wav, long wav_stride, int T, int L, int n_fft,
+                                                                long total, RowLengths len) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;      // (b, sample)
+    if (i >= total) return;
+    const int b = (int)(i / L), n = (int)(i % L);
+    const int hop = n_fft / 2;
+    const int Lb = len.v[b], Tb = 1 + Lb / hop;
+    float out = 0.0f;
+    if (n < Lb) {
+        const int p = n + hop;
+        const int t1 = p / hop, t0 = t1 - 1;
+        float num = 0.0f, den = 0.0f;
+        if (t1 < Tb) {
+            const int k = p - t1 * hop;
+            num += frames[((long)b * T + t1) * n_fft + k];
+            den += window[k] * window[k];
+        }
+        if (t0 >= 0 && t0 < Tb) {
+            const int k = p - t0 * hop;
+            num += frames[((long)b * T + t0) * n_fft + k];
+            den += window[k] * window[k];
+        }
+        out = den > 1e-11f ? num / den : 0.0f;
+    }
+    wav[(long)b * wav_stride + n] = out;
+}
+
+void launch_istft_ola_lengths(const float* frames, const float* window, float* wav, long wav_stride, int B, int T, int L, const int* samples,
+                              int n_fft, hipStream_t s) {
+    for (int b0 = 0; b0 < B; b0 += kLenRows) {
+        const int rows = B - b0 < kLenRows ? B - b0 : kLenRows;
+        RowLengths len{};
+        for (int r = 0; r < rows; ++r) len.v[r] = samples[b0 + r];
+        const long total = (long)rows * L;
+        hipLaunchKernelGGL(istft_ola_lengths_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, frames + (long)b0 * T * n_fft,
+                           window, wav + (long)b0 * wav_stride, wav_stride, T, L, n_fft, total, len);
+    }
+}
+
 // Host: GEMM operands (zero padded as tcn_gemm_kernel expects: rows to a multiple of 384, K to a multiple of 16).
 //   fwd [2F pad 384][n_fft]      : row 2f = w[n] cos(2 pi f n / N), row 2f+1 = -w[n] sin(2 pi f n / N)
 //   inv [n_fft pad 384][2F pad 16]: row n, column 2f = c_f w[n] cos(2 pi f n / N) / N, column 2f+1 = -c_f w[n] sin(...) / N

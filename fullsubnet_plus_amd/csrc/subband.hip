@@ -41,9 +41,11 @@ __global__ __launch_bounds__(512) void sb_offline_stats_kernel(const float* __re
                                                                const float* __restrict__ fb, long fb_bs, int nfb,
                                                                const float* __restrict__ refl_w,
                                                                const float* __restrict__ refl_wfb,
-                                                               double* __restrict__ acc, int Tp, int F, int FP, int rows) {
+                                                               double* __restrict__ acc, int Tp, int F, int FP, int rows,
+                                                               const int* __restrict__ tpb) {
     __shared__ double red[16];
-    const int b = blockIdx.y, t0 = blockIdx.x * rows, t1 = min(t0 + rows, Tp);
+    // (clips of different lengths: the frames past utterance b's own are not part of its tensor)
+    const int b = blockIdx.y, t0 = blockIdx.x * rows, t1 = min(t0 + rows, utt_frames(tpb, b, Tp));
     double s = 0.0, q = 0.0;
     for (int f = threadIdx.x; f < F; f += blockDim.x) {
         const double wr = refl_w[f], wfb = refl_wfb[f];
@@ -72,10 +74,11 @@ __global__ __launch_bounds__(512) void sb_offline_stats_kernel(const float* __re
     }
 }
 
+// count = elements of one utterance's tensor; with per-utterance frames (tpb) it is per_frame * tpb[b]
 __global__ void sb_offline_final_kernel(const double* __restrict__ acc, NormMD* __restrict__ md_utt, int B,
-                                        double count, int norm_type) {
+                                        double count, int norm_type, double per_frame, const int* __restrict__ tpb) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < B) md_utt[b] = sb_norm_md(norm_type, acc[b * 2], acc[b * 2 + 1], count);
+    if (b < B) md_utt[b] = sb_norm_md(norm_type, acc[b * 2], acc[b * 2 + 1], tpb ? per_frame * tpb[b] : count);
 }
 
 // cumulative norms: one workgroup per sub-band sequence.  Every thread sums the NIN features of its frames
@@ -134,9 +137,9 @@ void launch_subband_stats(const Dims& d, int norm_type, const SubbandBuffers& bu
         const int rows = sb_rows_per_wg(d.B);
         const int threads = d.F <= 256 ? 256 : d.F >= 512 ? 512 : (d.F + 63) / 64 * 64;
         hipLaunchKernelGGL(sb_offline_stats_kernel, dim3(cdiv(d.Tp, rows), d.B), dim3(threads), 0, s, buf.att_mag, buf.fb,
-                           fb_bs, (d.NIN - d.NSB) / (2 * buf.NFBN + 1), buf.refl_w, buf.refl_wfb, buf.acc, d.Tp, d.F, d.FP, rows);
+                           fb_bs, (d.NIN - d.NSB) / (2 * buf.NFBN + 1), buf.refl_w, buf.refl_wfb, buf.acc, d.Tp, d.F, d.FP, rows, d.tpb);
         hipLaunchKernelGGL(sb_offline_final_kernel, dim3(cdiv(d.B, 64)), dim3(64), 0, s, buf.acc, buf.md_utt, d.B,
-                           (double)d.F * d.NIN * d.Tp, norm_type);
+                           (double)d.F * d.NIN * d.Tp, norm_type, (double)d.F * d.NIN, d.tpb);
     } else {
         hipLaunchKernelGGL(sb_cumulative_kernel, dim3(num_slots), dim3(256), 0, s, buf.att_mag, buf.fb, fb_bs,
                            rows, buf.md_row, num_slots, d.Tp, d.F, d.FP, (d.NSB - 1) / 2, buf.NFBN, d.NIN, norm_type);

@@ -44,7 +44,14 @@ struct GemmArgs {
     int ntiles_n, row_tiles, row_tiles_all;    // launch geometry: column tiles, row tiles per branch, row tiles of all branches
     const float* c2; long c2_bs;               // tcn_gemm_dma_kernel<EPI_RESIDUAL>: [branch][Npad] sum_k gamma_k W[n][k] (GroupNorm folded)
     int relu_out;                              // EPI_RESIDUAL: 1 = store max(x, 0) (the last block: only ReLU -> Linear reads it, sequence_model.py:109-111)
+    const int* tpb;                            // nullptr, or [utt] frames of each utterance's GroupNorm plane (Dims::tpb): EPI_PRELU_STATS
+                                               // sums rows t < tpb[utt] only, PRO_GN / the EPI_RESIDUAL fold divide by CH * tpb[utt]
 };
+
+// elements of utterance utt's GroupNorm plane: gn_count = CH * Tp for the whole batch, CH * tpb[utt] with per-utterance frames
+__device__ __forceinline__ double gn_count_of(double gn_count, int Tp, const int* tpb, int utt) {
+    return tpb ? gn_count / Tp * tpb[utt] : gn_count;
+}
 
 // XCD-aware workgroup order (cdna_hip_programming.md T1).  The dispatcher places workgroup id L on XCD L % 8, and every XCD
 // has its own 4 MiB L2.  With a plain (column tile, row tile) grid the 5-8 workgroups that share one 128-row A tile land on
@@ -101,8 +108,9 @@ __global__ __launch_bounds__(256) void tcn_gemm_kernel(GemmArgs g) {
     const float* beta = nullptr;
     if constexpr (PRO == PRO_GN) {
         const double* st = g.gn_in + ((long)branch * g.B + utt) * kGnStride;
-        const double m = st[0] / g.gn_count;
-        const double var = st[1] / g.gn_count - m * m;
+        const double cnt = gn_count_of(g.gn_count, g.Tp, g.tpb, utt);
+        const double m = st[0] / cnt;
+        const double var = st[1] / cnt - m * m;
         mean = (float)m;
         rstd = (float)(1.0 / sqrt((var > 0 ? var : 0) + (double)g.gn_eps));
         gamma = g.gamma + branch * g.gb_bs;
@@ -236,6 +244,7 @@ __global__ __launch_bounds__(256) void tcn_gemm_kernel(GemmArgs g) {
     double s = 0.0, q = 0.0;
     float slope = 0.f;
     if constexpr (EPI == EPI_PRELU_STATS) slope = g.prelu[branch * g.prelu_bs];
+    const int t_stats = utt_frames(g.tpb, utt, g.Tp);     // (EPI_PRELU_STATS) rows of the utterance's GroupNorm plane
 #pragma unroll
     for (int j = 0; j < NTILE; ++j) {
         const int col = n0 + j * 32 + (lane & 31);
@@ -248,8 +257,10 @@ __global__ __launch_bounds__(256) void tcn_gemm_kernel(GemmArgs g) {
                 float v = acc[j][r] + bias;
                 if constexpr (EPI == EPI_PRELU_STATS) {
                     v = v >= 0.f ? v : slope * v;
-                    s += (double)v;
-                    q += (double)v * (double)v;
+                    if (t < t_stats) {
+                        s += (double)v;
+                        q += (double)v * (double)v;
+                    }
                 }
                 if constexpr (EPI == EPI_RESIDUAL) {
                     v += g.R[branch * g.r_bs + ((long)utt * g.Tp + t) * g.ldr + col];
@@ -279,15 +290,19 @@ __global__ __launch_bounds__(256) void tcn_gemm_kernel(GemmArgs g) {
 
 // ------------------------------------------------------------------------------------------------
 // ---- epilogues shared by tcn_gemm_dma_kernel and tcn_gemm_sk_kernel: per-plane scalars, one output element, the statistics tail
-struct EpiCtx { float slope, rstd, mr; };
+struct EpiCtx { float slope, rstd, mr; int t_stats; };     // t_stats (EPI_PRELU_STATS): rows of the utterance's GroupNorm plane
 template <int EPI>
 __device__ __forceinline__ EpiCtx epi_ctx(const GemmArgs& g, int branch, int utt) {
-    EpiCtx e{0.f, 1.f, 0.f};
-    if constexpr (EPI == EPI_PRELU_STATS) e.slope = g.prelu[branch * g.prelu_bs];
+    EpiCtx e{0.f, 1.f, 0.f, g.Tp};
+    if constexpr (EPI == EPI_PRELU_STATS) {
+        e.slope = g.prelu[branch * g.prelu_bs];
+        e.t_stats = utt_frames(g.tpb, utt, g.Tp);      // (loaded here, under the first DMA round trips, like the other plane scalars)
+    }
     if constexpr (EPI == EPI_RESIDUAL) {
         const double* stt = g.gn_in + ((long)branch * g.B + utt) * kGnStride;
-        const double m = stt[0] / g.gn_count;
-        const double var = stt[1] / g.gn_count - m * m;
+        const double cnt = gn_count_of(g.gn_count, g.Tp, g.tpb, utt);
+        const double m = stt[0] / cnt;
+        const double var = stt[1] / cnt - m * m;
         const double rs = 1.0 / sqrt((var > 0 ? var : 0) + (double)g.gn_eps);
         e.rstd = (float)rs;
         e.mr = (float)(m * rs);
@@ -512,7 +527,7 @@ __global__ __launch_bounds__(256) void tcn_gemm_dma_kernel(GemmArgs g) {
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
             const int rl = (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
-            const bool counted = col_ok && t0 + wave * 32 + rl < g.Tp;
+            const bool counted = col_ok && t0 + wave * 32 + rl < ec.t_stats;
             slice[rl * 64 + j * 32 + (lane & 31)] = epi_stage_value<EPI>(ec, acc[j][q], cb[j], g.act, counted, s, q2);
         }
     }
@@ -661,7 +676,7 @@ __global__ __launch_bounds__(256) void tcn_gemm_sk_kernel(GemmArgs g) {
 #pragma unroll
         for (int qq = 0; qq < 4; ++qq) {
             const int rl = qq + 4 * (lane >> 5);
-            const bool counted = col_ok && t0 + wave * 8 + rl < g.Tp;
+            const bool counted = col_ok && t0 + wave * 8 + rl < ec.t_stats;
             slice[rl * 64 + j * 32 + (lane & 31)] = epi_stage_value<EPI>(ec, sum[j][qq], cb[j], g.act, counted, s, q2);
         }
     }
@@ -814,7 +829,7 @@ __global__ __launch_bounds__(256) void tcn_gemm_dma64_kernel(GemmArgs g) {
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
             const int rl = (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
-            const bool counted = col_ok && t0 + wr * 32 + rl < g.Tp;
+            const bool counted = col_ok && t0 + wr * 32 + rl < ec.t_stats;
             tile[(wr * 32 + rl) * 64 + wc * 32 + (lane & 31)] = epi_stage_value<EPI>(ec, acc[q], cb, g.act, counted, s, q2);
         }
     }
@@ -926,6 +941,7 @@ struct DwArgs {
     long cb_bs, w_bs, prelu_bs;
     int CH, Tp, B, dil;
     double gn_count; float gn_eps;
+    const int* tpb;                              // nullptr, or per-utterance frames (Dims::tpb): statistics, count and halo end there
     int chunks, planes;                          // DW_ROWS-row chunks per (utterance, branch) plane; planes = B * branches
 };
 constexpr int DW_ROWS = 8;
@@ -938,9 +954,13 @@ __global__ __launch_bounds__(256) void tcn_dwconv_kernel(DwArgs g) {
     if (!xcd_decode(blockIdx.x, g.chunks, g.planes, plane, chunk)) return;
     const int branch = plane / g.B, utt = plane % g.B, t0 = chunk * DW_ROWS;
     const double* st = g.gn_in + ((long)branch * g.B + utt) * kGnStride;
-    const double m = st[0] / g.gn_count;
-    const double var = st[1] / g.gn_count - m * m;
+    const double cnt = gn_count_of(g.gn_count, g.Tp, g.tpb, utt);
+    const double m = st[0] / cnt;
+    const double var = st[1] / cnt - m * m;
     const float mean = (float)m;
+    // the utterance's own frames: the conv's zero padding starts there (the NON-causal halo reads up to dilation frames ahead), and
+    // frames past it are left out of the GroupNorm2 statistics
+    const int tv = utt_frames(g.tpb, utt, g.Tp);
     const float rstd = (float)(1.0 / sqrt((var > 0 ? var : 0) + (double)g.gn_eps));
     const float slope = g.prelu[branch * g.prelu_bs];
     const float* __restrict__ Y1 = g.Y1 + branch * g.y_bs + (long)utt * g.Tp * g.CH;
@@ -957,7 +977,7 @@ __global__ __launch_bounds__(256) void tcn_dwconv_kernel(DwArgs g) {
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             const int tt = t + (j - 1) * g.dil;
-            if (tt < 0 || tt >= g.Tp) continue;     // zero padding of the NORMALISED tensor
+            if (tt < 0 || tt >= tv) continue;       // zero padding of the NORMALISED tensor
             const float4 y = *reinterpret_cast<const float4*>(Y1 + (long)tt * g.CH + c);
             const float4 wj = *reinterpret_cast<const float4*>(g.w + branch * g.w_bs + (long)j * g.CH + c);
             acc.x += wj.x * ((y.x - mean) * rstd * ga.x + be.x);
@@ -970,6 +990,7 @@ __global__ __launch_bounds__(256) void tcn_dwconv_kernel(DwArgs g) {
         acc.z = acc.z >= 0.f ? acc.z : slope * acc.z;
         acc.w = acc.w >= 0.f ? acc.w : slope * acc.w;
         *reinterpret_cast<float4*>(Y2 + (long)t * g.CH + c) = acc;
+        if (t >= tv) continue;
         s += (double)acc.x + (double)acc.y + (double)acc.z + (double)acc.w;
         q += (double)acc.x * acc.x + (double)acc.y * acc.y + (double)acc.z * acc.z + (double)acc.w * acc.w;
     }
@@ -1007,7 +1028,7 @@ void launch_tcn(const Dims& d, int fb_act, const TcnWeights& w, const TcnBuffers
             g.C = buf.y1; g.c_bs = y_bs; g.ldc = d.CH;
             g.gn_out = gn_slot(blk, 0);
             g.prelu = w.a1 + blk; g.prelu_bs = w.NB;
-            g.K = d.F; g.N = d.CH; g.Tp = d.Tp; g.B = d.B;
+            g.K = d.F; g.N = d.CH; g.Tp = d.Tp; g.B = d.B; g.tpb = d.tpb;
             if (!(dma && launch_gemm_dma<EPI_PRELU_STATS>(g, d.CH, row_tiles, w.num_cus, s, branches, w.gemm_dma == 1)))
                 launch_gemm<PRO_NONE, EPI_PRELU_STATS>(g, d.CH, row_tiles, w.num_cus, s, branches);
         }
@@ -1020,7 +1041,7 @@ void launch_tcn(const Dims& d, int fb_act, const TcnWeights& w, const TcnBuffers
             g.w = w.dw + (long)blk * 3 * d.CH; g.w_bs = (long)w.NB * 3 * d.CH;
             g.prelu = w.a2 + blk; g.prelu_bs = w.NB;
             g.CH = d.CH; g.Tp = d.Tp; g.B = d.B; g.dil = w.dilation[blk];
-            g.gn_count = gn_count; g.gn_eps = 1e-8f;
+            g.gn_count = gn_count; g.gn_eps = 1e-8f; g.tpb = d.tpb;
             g.chunks = cdiv(d.Tp, DW_ROWS); g.planes = d.B * branches;
             hipLaunchKernelGGL(tcn_dwconv_kernel, dim3(xcd_grid(g.chunks, g.planes)), dim3(256), 0, s, g);
         }
@@ -1034,7 +1055,7 @@ void launch_tcn(const Dims& d, int fb_act, const TcnWeights& w, const TcnBuffers
             g.gn_in = gn_slot(blk, 1);
             g.gamma = w.g2w + (long)blk * d.CH; g.beta = w.g2b + (long)blk * d.CH; g.gb_bs = (long)w.NB * d.CH;
             g.K = d.CH; g.N = d.F; g.Tp = d.Tp; g.B = d.B;
-            g.gn_count = gn_count; g.gn_eps = 1e-8f;
+            g.gn_count = gn_count; g.gn_eps = 1e-8f; g.tpb = d.tpb;
             // the last block's output is only read through ReLU (-> Linear): store it ReLU'd, so that the Linear's operand needs no
             // prologue and can go global -> LDS by DMA like the others (final Linear 39 -> 29.5 us at B = 32)
             g.relu_out = (relu_fused && blk == w.NB - 1) ? 1 : 0;

@@ -15,6 +15,7 @@ The modules below only *hold parameters* with the reference's names; no torch op
 anything in ``forward``.  CPU tensors are rejected: there is deliberately no CPU fallback.
 """
 import ctypes
+import operator
 import weakref
 
 import torch
@@ -185,6 +186,26 @@ def _reference_style_init(m):
     elif isinstance(m, (nn.LSTM, nn.GRU)):
         for p in m.parameters():
             (nn.init.orthogonal_ if p.dim() >= 2 else nn.init.normal_)(p.data)
+
+
+def _host_lengths(lengths, batch, what):
+    """Per-utterance lengths (a Python sequence or a CPU integer tensor) -> ctypes int32[batch].  They are read on the host and
+    reach the device as kernel arguments: a CUDA tensor is refused, because reading it would synchronise."""
+    if isinstance(lengths, torch.Tensor):
+        if lengths.device.type != "cpu":
+            raise ValueError(f"{what}: lengths must be a CPU tensor or a Python sequence, not a {lengths.device} tensor "
+                             "(reading it would synchronise the device)")
+        if lengths.is_floating_point() or lengths.is_complex() or lengths.dtype == torch.bool:
+            raise TypeError(f"{what}: lengths must hold integers, got {lengths.dtype}")
+        vals = [int(v) for v in lengths.reshape(-1).tolist()]
+    else:
+        vals = [operator.index(v) for v in lengths]
+    if len(vals) != batch:
+        raise ValueError(f"{what}: {len(vals)} lengths for a batch of {batch}")
+    for b, v in enumerate(vals):
+        if not -2 ** 31 <= v < 2 ** 31:
+            raise ValueError(f"{what}: utterance {b}: length {v} is not an int32")
+    return (ctypes.c_int32 * batch)(*vals)
 
 
 def _resolve_device(device):
@@ -410,9 +431,10 @@ class _HipModel(nn.Module):
             raise RuntimeError("no HIP handle yet: run a forward on a CUDA tensor first")
         return self._hip.handle
 
-    def _forward_impl(self, ins, batch_offset, global_batch, complex_in=False):
+    def _forward_impl(self, ins, batch_offset, global_batch, complex_in=False, lengths=None):
         """ins: 1 (FullSubNet) or 3 (FullSubNet+) tensors [B, 1, F, T], or - complex_in - ONE complex64 [B, F, T]
-        tensor (the STFT itself, fsnp_forward_complex); returns the cIRM tensor."""
+        tensor (the STFT itself, fsnp_forward_complex); returns the cIRM tensor.  lengths: None, or frames per utterance
+        (fsnp_forward_lengths / fsnp_forward_complex_lengths)."""
         noisy_mag = ins[0]
         if complex_in:
             assert noisy_mag.dim() == 3 and noisy_mag.dtype == torch.complex64
@@ -428,6 +450,13 @@ class _HipModel(nn.Module):
             raise RuntimeError("fullsubnet_plus_amd runs on MI355X (HIP) only; move the model and inputs to 'cuda'. "
                                "There is deliberately no CPU fallback.")
         device = noisy_mag.device
+        if lengths is not None:
+            if int(batch_offset) != 0 or global_batch is not None:
+                raise ValueError("lengths: sharded batches (batch_offset / global_batch) are not supported with per-utterance lengths")
+            if batch_size > 1 and self.batch_mode == "parity":
+                raise ValueError("lengths: per-utterance lengths need per-utterance semantics; set model.batch_mode = \"full\" "
+                                 "(batch_mode \"parity\" mixes the utterances of a batch, feature.py:263)")
+            lengths = _host_lengths(lengths, batch_size, f"{self.__class__.__name__}.forward")
         gb = batch_size if global_batch is None else int(global_batch)
         parity = gb > 1 and self.batch_mode == "parity"
         if parity:
@@ -456,9 +485,13 @@ class _HipModel(nn.Module):
             cst = (ctypes.c_int64 * 3)(*noisy_mag.stride())
             for attempt in (0, 1):
                 with torch.cuda.device(device):
-                    rc = lib.fsnp_forward_complex(self._handle, torch.view_as_real(noisy_mag).data_ptr(), ctypes.byref(cst),
-                                                  out.data_ptr(), batch_size, num_frames, mode, int(batch_offset), gb,
-                                                  ctypes.c_void_p(stream))
+                    if lengths is not None:
+                        rc = lib.fsnp_forward_complex_lengths(self._handle, torch.view_as_real(noisy_mag).data_ptr(), ctypes.byref(cst),
+                                                              lengths, out.data_ptr(), batch_size, num_frames, ctypes.c_void_p(stream))
+                    else:
+                        rc = lib.fsnp_forward_complex(self._handle, torch.view_as_real(noisy_mag).data_ptr(), ctypes.byref(cst),
+                                                      out.data_ptr(), batch_size, num_frames, mode, int(batch_offset), gb,
+                                                      ctypes.c_void_p(stream))
                 if rc != _lib.ERR_STALE_WEIGHTS or attempt:
                     break
                 self._stale_weights_noticed(device)
@@ -471,9 +504,13 @@ class _HipModel(nn.Module):
         ptrs = [t.data_ptr() for t in ins] + [None] * (3 - len(ins))
         for attempt in (0, 1):
             with torch.cuda.device(device):
-                rc = lib.fsnp_forward(self._handle, ptrs[0], ptrs[1], ptrs[2],
-                                      ctypes.byref(strides), out.data_ptr(), batch_size, num_frames,
-                                      mode, int(batch_offset), gb, ctypes.c_void_p(stream))
+                if lengths is not None:
+                    rc = lib.fsnp_forward_lengths(self._handle, ptrs[0], ptrs[1], ptrs[2], ctypes.byref(strides), lengths,
+                                                  out.data_ptr(), batch_size, num_frames, ctypes.c_void_p(stream))
+                else:
+                    rc = lib.fsnp_forward(self._handle, ptrs[0], ptrs[1], ptrs[2],
+                                          ctypes.byref(strides), out.data_ptr(), batch_size, num_frames,
+                                          mode, int(batch_offset), gb, ctypes.c_void_p(stream))
             if rc != _lib.ERR_STALE_WEIGHTS or attempt:
                 break
             self._stale_weights_noticed(device)       # the watch flagged an EARLIER forward: re-pack, say so, run this one
@@ -590,23 +627,24 @@ class _HipModel(nn.Module):
         with torch.cuda.device(self._hip.device):
             _lib.check(_lib.load().fsnp_flush(self._handle, ctypes.c_void_p(stream)), "fsnp_flush")
 
-    def forward_complex(self, noisy_complex, batch_offset=0, global_batch=None):
+    def forward_complex(self, noisy_complex, batch_offset=0, global_batch=None, lengths=None):
         """the forward fed with the complex64 STFT itself ([B, F, T], any strides - torch.stft's
         output is consumed in place); mag / real / imag are derived inside the HIP repack kernel instead of by the
-        three torch ops of inferencer.py:143-147.  Same result as forward(|X|, X.real, X.imag)."""
-        return self._checked(lambda: self._forward_impl([noisy_complex], batch_offset, global_batch, complex_in=True),
+        three torch ops of inferencer.py:143-147.  Same result as forward(|X|, X.real, X.imag, lengths=lengths)."""
+        return self._checked(lambda: self._forward_impl([noisy_complex], batch_offset, global_batch, complex_in=True, lengths=lengths),
                              noisy_complex.device)
 
-    def enhance(self, noisy_complex):
+    def enhance(self, noisy_complex, lengths=None):
         """SURVEY.md 8(f-1) + (f-3): model forward + decompress_cIRM + complex multiply, all in HIP - lines 143-157 of
         fullsubnet_plus/inferencer/inferencer.py (`full_band_crm_mask` of fullsubnet/inferencer/inferencer.py for the
         original FullSubNet): noisy_complex [B,F,T] complex64 (torch.stft output, any strides) -> enhanced complex
-        [B,F,T] ready for torch.istft.  Always keeps all bins (batch_mode "full")."""
+        [B,F,T] ready for torch.istft.  Always keeps all bins (batch_mode "full").  lengths: frames per utterance (see
+        forward); frames past them come out as 0."""
         assert noisy_complex.dim() == 3 and noisy_complex.is_complex()
         assert self.output_size == 2, "the cIRM epilogue needs the two mask channels (decompress_cIRM, acoustics/mask.py:60-63)"
         mode, self.batch_mode = self.batch_mode, "full"
         try:
-            mask = self.forward_complex(noisy_complex)
+            mask = self.forward_complex(noisy_complex, lengths=lengths)
         finally:
             self.batch_mode = mode
         if self._pipeline:
@@ -650,19 +688,26 @@ class _HipModel(nn.Module):
                                       out.stride(0), B, T, int(length), ctypes.c_void_p(stream)), "fsnp_istft")
         return out
 
-    def enhance_wave(self, noisy):
+    def enhance_wave(self, noisy, lengths=None):
         """The reference inferencer's inner loop in ONE call (fullsubnet_plus/inferencer/inferencer.py:142-158,
         `mag_complex_full_band_crm_mask`; `full_band_crm_mask` of fullsubnet/inferencer/inferencer.py for the original
         FullSubNet): noisy waveform [B, samples] -> enhanced waveform [B, samples]; STFT, model (all bins), cIRM
-        decompression, complex multiply and iSTFT all run in HIP on the caller's stream."""
+        decompression, complex multiply and iSTFT all run in HIP on the caller's stream.  lengths: None, or SAMPLES per
+        utterance (a Python sequence or a CPU integer tensor): row b is then enhance_wave(noisy[b:b+1, :lengths[b]]) of that
+        clip alone, and 0 past lengths[b]."""
         assert self.output_size == 2, "the cIRM epilogue needs the two mask channels (decompress_cIRM, acoustics/mask.py:60-63)"
+        samples = None if lengths is None else _host_lengths(lengths, noisy.shape[0], f"{self.__class__.__name__}.enhance_wave")
         wav, lib, stream = self._wave_args(noisy)
         B, L = wav.shape
         out = torch.empty((B, L), dtype=torch.float32, device=wav.device)
         def run():
             with torch.cuda.device(wav.device):
-                _lib.check(lib.fsnp_enhance_wave(self._handle, wav.data_ptr(), wav.stride(0), out.data_ptr(), out.stride(0), B, L,
-                                                 ctypes.c_void_p(stream)), "fsnp_enhance_wave")
+                if samples is not None:
+                    _lib.check(lib.fsnp_enhance_wave_lengths(self._handle, wav.data_ptr(), wav.stride(0), out.data_ptr(), out.stride(0),
+                                                             samples, B, L, ctypes.c_void_p(stream)), "fsnp_enhance_wave_lengths")
+                else:
+                    _lib.check(lib.fsnp_enhance_wave(self._handle, wav.data_ptr(), wav.stride(0), out.data_ptr(), out.stride(0), B, L,
+                                                     ctypes.c_void_p(stream)), "fsnp_enhance_wave")
             return out
         return self._checked(run, wav.device)
 
@@ -964,15 +1009,18 @@ class FullSubNet_Plus(_HipModel):
         return cfg
 
     # ------------------------------------------------------------------ forward
-    def forward(self, noisy_mag, noisy_real, noisy_imag, batch_offset=0, global_batch=None):
+    def forward(self, noisy_mag, noisy_real, noisy_imag, batch_offset=0, global_batch=None, lengths=None):
         """
         Shapes:
             noisy_mag / noisy_real / noisy_imag: [B, 1, F, T] fp32 CUDA tensors (any strides)
             return: [B, 2, F, T]   (B == 1 or batch_mode == "full")
                     [B, 2, F//2, T] with the reference's drop_band row order (B > 1, batch_mode == "parity")
         batch_offset / global_batch: only for sharded batches (fullsubnet_plus_amd.dist).
+        lengths: None, or frames per utterance (a Python sequence or a CPU integer tensor, 1 <= lengths[b] <= T) for a batch of
+            clips of different lengths (batch_mode "full" only): row b is then, at frames [0, lengths[b]), the forward of
+            x[b:b+1, ..., :lengths[b]] alone, and exactly 0 at frames [lengths[b], T).  Input frames past lengths[b] are never read.
         """
-        return self._checked(lambda: self._forward_impl([noisy_mag, noisy_real, noisy_imag], batch_offset, global_batch),
+        return self._checked(lambda: self._forward_impl([noisy_mag, noisy_real, noisy_imag], batch_offset, global_batch, lengths=lengths),
                              noisy_mag.device)
 
 
@@ -1056,10 +1104,10 @@ class FullSubNet(_HipModel):
         cfg.sequence_model = _lib.SEQUENCE_MODELS[self.sequence_model]
         return cfg
 
-    def forward(self, noisy_mag, batch_offset=0, global_batch=None):
+    def forward(self, noisy_mag, batch_offset=0, global_batch=None, lengths=None):
         """noisy_mag [B, 1, F, T] fp32 CUDA tensor (any strides) -> cIRM [B, 2, F, T] (see FullSubNet_Plus.forward
-        for batch_mode and the sharding arguments)."""
-        return self._checked(lambda: self._forward_impl([noisy_mag], batch_offset, global_batch), noisy_mag.device)
+        for batch_mode, the sharding arguments and lengths)."""
+        return self._checked(lambda: self._forward_impl([noisy_mag], batch_offset, global_batch, lengths=lengths), noisy_mag.device)
 
 
 Model = FullSubNet_Plus  # the name BASELINE.json's north_star uses
