@@ -1,6 +1,8 @@
-// fsnp_abi.hip - C ABI of libfsnp_hip.so (include/fsnp.h): handle life cycle, workspace management, the forward orchestration and
-// the tuning / test hooks.  Host code only; kernels live in frontend.hip / tcn.hip / subband.hip / lstm*.hip; the planner in
-// planner.cpp, weight packing in fsnp_weights.hip, the STFT entry points in fsnp_stft_abi.hip (shared declarations: fsnp_handle.h).
+// fsnp_abi.hip - C ABI of libfsnp_hip.so (include/fsnp.h): handle life cycle, workspace management, cost calibration and the forward
+// orchestration (its sub-band launches, and the per-device chain of column-split launches).  Host code only; kernels live in
+// forward_kernels.hip / frontend.hip / tcn.hip / subband.hip / lstm*.hip; the exchange checks in fsnp_verify.hip, the planner in
+// planner.cpp, weight packing in fsnp_weights.hip, the STFT entry points in fsnp_stft_abi.hip, the include/fsnp_debug.h hooks in
+// fsnp_debug_abi.hip (shared declarations: fsnp_handle.h).
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -16,7 +18,6 @@
 #include "lstm_common.h"
 #include "planner.h"
 #include "fsnp_handle.h"
-#include "weight_watch.h"
 
 namespace fsnp {
 
@@ -85,153 +86,12 @@ int take_device_errors(fsnp_handle* h, const char* where) {
 }
 
 // what the planner needs to know of a handle
-static PlannerCtx pctx(const fsnp_handle* h) {
+PlannerCtx pctx(const fsnp_handle* h) {
     PlannerCtx c;
     static_cast<PlannerOptions&>(c) = h->planner;
     c.H = h->H; c.NIN = h->NIN; c.num_cus = h->num_cus; c.num_cus_real = h->num_cus_real;
     c.gru = h->gru != 0; c.sb_tcn = h->sb_tcn != 0; c.generic_sb = h->generic_sb; c.ih_bf16 = h->ih_bf16;
     return c;
-}
-
-
-// Row slots of the sub-band problem.  Tile i owns `rt` slots (32 MFMA rows + ex VALU rows) and gets
-// base (+1 for the first rem tiles) consecutive sequences; slot -> (utterance, frequency, output offset).
-__global__ void build_rows_kernel(RowDesc* rows, int num_rows, int num_tiles, int rt, int F, int T, int mode,
-                                  int batch_offset, int global_batch, int dense_out, int n_base, int groups, int OC) {
-    const int slot = blockIdx.x * blockDim.x + threadIdx.x;
-    if (slot >= num_tiles * rt) return;
-    const int tile = slot / rt, sl = slot % rt;
-    const int base = num_rows / num_tiles, rem = num_rows % num_tiles;
-    const int cnt = base + (tile < rem ? 1 : 0);
-    const int n = n_base + tile * base + (tile < rem ? tile : rem) + sl;      // n_base: first sequence of this chunk
-    RowDesc r{0, 0, 0, 0};
-    if (sl < cnt) {
-        r.valid = 1;
-        if (dense_out) {               // fsnp_lstm2_fc: x[n][t][:] -> out[n][o][t], o < OC = output_size (fullsubnet_plus.py:104,206)
-            r.b = n; r.f = 0; r.out_off = n * OC * T;
-        } else if (mode == FSNP_MODE_FULL) {
-            r.b = n / F; r.f = n % F;
-            r.out_off = ((r.b * OC) * F + r.f) * T;
-        } else {                       // drop_band (feature.py:254-285) with G = num_groups_in_drop_band groups:
-            // global sample s keeps bins p + G i (p = s % G, i < (F - F % G) / G); output rows = group 0's samples, group 1's, ...
-            const int G = groups, Fh = F / G;
-            r.b = n / Fh;
-            const int i = n % Fh;
-            const int s = batch_offset + r.b, p = s % G;
-            int orow = s / G;
-            for (int q = 0; q < p; ++q) orow += (global_batch - q + G - 1) / G;     // samples of the groups in front
-            r.f = p + G * i;
-            r.out_off = ((orow * OC) * Fh + i) * T;
-        }
-    }
-    rows[slot] = r;
-}
-
-// Zeroes the accumulator / exchange / barrier region of the workspace.  A kernel rather than hipMemsetAsync: a memset
-// node captured into the hipGraph was NOT re-executed reliably on replay (ROCm 7.2: stale barrier counters and
-// accumulators after the first launch - tests/test_gpu_parity.py::test_b32_batch_independence caught it).
-__global__ __launch_bounds__(256) void zero_region_kernel(uint4* __restrict__ p, size_t n16) {
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += stride) p[i] = make_uint4(0u, 0u, 0u, 0u);
-}
-static void launch_zero_region(void* p, size_t bytes, hipStream_t s) {      // bytes is a multiple of 256
-    const size_t n16 = bytes / 16;
-    if (n16 == 0) return;
-    const int blocks = (int)((n16 + 255) / 256 < 2048 ? (n16 + 255) / 256 : 2048);
-    hipLaunchKernelGGL(zero_region_kernel, dim3(blocks), dim3(256), 0, s, reinterpret_cast<uint4*>(p), n16);
-}
-
-// ---- the forward's prologue as ONE launch (round 5; it used to be a zeroing kernel, a build_rows launch per chunk and, with a weight
-// watch, the fingerprint kernel - three to six dependent launches of ~5 us each in front of a 250 us full-band stage at B = 1):
-// blocks [0, zb) zero the accumulator / exchange / counter region, [zb, zb + rb) describe the sub-band rows of every chunk, the rest
-// fingerprint the watched source tensors (fsnp_watch_weights).
-struct PrologueChunk { int slot0, nrows, tiles, rt, row0, blocks; };
-struct PrologueArgs {
-    uint4* zero; size_t n16; int zero_blocks;
-    RowDesc* rows; PrologueChunk chunk[8]; int nchunks, rows_blocks;
-    int F, T, mode, batch_offset, global_batch, groups, OC;
-    const WatchSeg* segs; int nseg, watch_blocks; unsigned long long* watch_acc; unsigned* err_host;
-};
-__device__ __forceinline__ void build_rows_slot(RowDesc* rows, int slot, int num_rows, int num_tiles, int rt, int F, int T, int mode,
-                                                int batch_offset, int global_batch, int n_base, int groups, int OC) {
-    const int tile = slot / rt, sl = slot % rt;
-    const int base = num_rows / num_tiles, rem = num_rows % num_tiles;
-    const int cnt = base + (tile < rem ? 1 : 0);
-    const int n = n_base + tile * base + (tile < rem ? tile : rem) + sl;
-    RowDesc r{0, 0, 0, 0};
-    if (sl < cnt) {
-        r.valid = 1;
-        if (mode == FSNP_MODE_FULL) {
-            r.b = n / F; r.f = n % F;
-            r.out_off = ((r.b * OC) * F + r.f) * T;
-        } else {                       // drop_band: see build_rows_kernel
-            const int G = groups, Fh = F / G;
-            r.b = n / Fh;
-            const int i = n % Fh;
-            const int s = batch_offset + r.b, p = s % G;
-            int orow = s / G;
-            for (int q = 0; q < p; ++q) orow += (global_batch - q + G - 1) / G;
-            r.f = p + G * i;
-            r.out_off = ((orow * OC) * Fh + i) * T;
-        }
-    }
-    rows[slot] = r;
-}
-__global__ __launch_bounds__(256) void prologue_kernel(PrologueArgs a) {
-    const int b = blockIdx.x;
-    if (b < a.zero_blocks) {
-        const size_t stride = (size_t)a.zero_blocks * 256;
-        for (size_t i = (size_t)b * 256 + threadIdx.x; i < a.n16; i += stride) a.zero[i] = make_uint4(0u, 0u, 0u, 0u);
-        return;
-    }
-    int rb = b - a.zero_blocks;
-    if (rb < a.rows_blocks) {
-        for (int c = 0; c < a.nchunks; ++c) {
-            const PrologueChunk k = a.chunk[c];
-            if (rb < k.blocks) {
-                const int slot = rb * 256 + threadIdx.x;
-                if (slot < k.tiles * k.rt)
-                    build_rows_slot(a.rows + k.slot0, slot, k.nrows, k.tiles, k.rt, a.F, a.T, a.mode, a.batch_offset, a.global_batch, k.row0, a.groups, a.OC);
-                return;
-            }
-            rb -= k.blocks;
-        }
-        return;
-    }
-    weight_watch_block(a.segs, a.nseg, a.watch_acc, 0, a.err_host, b - a.zero_blocks - a.rows_blocks, a.watch_blocks);
-}
-
-// ---- clips of different lengths (fsnp_forward_lengths).  The host's lengths reach the workspace as kernel arguments - no copy from
-// pageable memory, nothing to synchronise, the caller may reuse its buffer when the call returns - 256 utterances per launch:
-// lens[b] = lengths[b], tpb[b] = lengths[b] + look_ahead (Dims::lens / Dims::tpb)
-constexpr int kLengthsPerLaunch = 256;
-struct LengthArgs { int* lens; int* tpb; int b0, n, LA; int v[kLengthsPerLaunch]; };
-__global__ __launch_bounds__(kLengthsPerLaunch) void set_lengths_kernel(LengthArgs a) {
-    const int i = threadIdx.x;
-    if (i < a.n) { a.lens[a.b0 + i] = a.v[i]; a.tpb[a.b0 + i] = a.v[i] + a.LA; }
-}
-static void launch_set_lengths(const int32_t* lengths, int B, int LA, int* lens, int* tpb, hipStream_t s) {
-    for (int b0 = 0; b0 < B; b0 += kLengthsPerLaunch) {
-        LengthArgs a{};
-        a.lens = lens; a.tpb = tpb; a.b0 = b0; a.n = std::min(kLengthsPerLaunch, B - b0); a.LA = LA;
-        for (int i = 0; i < a.n; ++i) a.v[i] = lengths[b0 + i];
-        hipLaunchKernelGGL(set_lengths_kernel, dim3(1), dim3(kLengthsPerLaunch), 0, s, a);
-    }
-}
-// frames [lengths[b], T) of every row of utterance b of the [B][rows_per_utt][T] mask are written as 0 (the sub-band model ran over
-// them: causal, so the frames before lengths[b] never saw them, but what it wrote there is no part of the clip)
-__global__ __launch_bounds__(256) void zero_tails_kernel(float* __restrict__ out, const int* __restrict__ lens, int rows_per_utt, int T,
-                                                         long total) {
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-        const long row = i / T;
-        const int t = (int)(i - row * T);
-        if (t >= lens[row / rows_per_utt]) out[i] = 0.0f;
-    }
-}
-static void launch_zero_tails(float* out, const int* lens, int B, int rows_per_utt, int T, hipStream_t s) {
-    const long total = (long)B * rows_per_utt * T;
-    const int blocks = (int)std::min<long>((total + 255) / 256, 4096);
-    hipLaunchKernelGGL(zero_tails_kernel, dim3(blocks), dim3(256), 0, s, out, lens, rows_per_utt, T, total);
 }
 
 int check_lengths(const fsnp_handle* h, const int32_t* lengths, int batch, int frames, const char* where) {
@@ -326,7 +186,7 @@ static void launch_coop_chained(int dev, hipStream_t s, F launch, const void* ow
 // (lstm_hp.hip) addresses its input through ONE buffer descriptor with 32-bit BYTE offsets (2 GiB), the other kernels with 32-bit
 // FLOAT offsets from a 64-bit pointer (8 GiB): beyond 2 GiB the planner is told not to use it (its loads would
 // otherwise return zeros - out of the descriptor's range - and the sequences run on zero input without any error).
-static SbPlan plan_sb(const fsnp_handle* h, int num_rows, double gather_bytes = 0.0) {
+SbPlan plan_sb(const fsnp_handle* h, int num_rows, double gather_bytes) {
     PlannerCtx c = pctx(h);
     if (gather_bytes >= 2147483644.0) c.coop_hp = 0;
     return plan_sb(c, num_rows);
@@ -336,19 +196,19 @@ static double forward_gather_bytes(const fsnp_handle* h, int B, int T) {
     const double nbr = h->model == FSNP_MODEL_FULLSUBNET ? 1 : 3;
     return 2.0 * ((double)align_up((size_t)(nbr * B * ((double)T + h->cfg.look_ahead) * h->FP * 4), 256));
 }
-static int chunk_workgroups(const fsnp_handle* h, const SbChunk& c) { return chunk_workgroups(pctx(h), c); }
+int chunk_workgroups(const fsnp_handle* h, const SbChunk& c) { return chunk_workgroups(pctx(h), c); }
 // where a sub-band chunk's workgroups go; one per CU (owned or not: the least a launch that does not own its CUs is sure to get)
 static CoopFootprint sb_chunk_footprint(const fsnp_handle* h, const SbChunk& c, bool own_cu) { return chunk_footprint(pctx(h), c, own_cu, 1); }
 // Launches chunks [first, last) of the plan on stream s.  `bar` = per-tile arrival counters followed (at bar +
 // plan.coop_tiles, 64-byte aligned by the caller) by the launch-abort word.
-static void launch_sb_lstm(const fsnp_handle* h, const SbPlan& plan, const LstmArgs& a, float* hx, unsigned* bar, unsigned* abort_word,
-                           hipStream_t s, hipEvent_t after_first = nullptr, int first_chunk = 0, int last_chunk = -1) {
+void launch_sb_lstm(const fsnp_handle* h, const SbPlan& plan, const LstmArgs& a, float* hx, unsigned* bar, unsigned* abort_word,
+                    hipStream_t s, hipEvent_t after_first, int first_chunk, int last_chunk) {
     const size_t hx_floats_per_tile = lstm_coop_exchange_bytes(h->H, 1) / 4;
     const int nchunks = (int)plan.chunks.size();
     if (last_chunk < 0 || last_chunk > nchunks) last_chunk = nchunks;
     for (int ci = first_chunk; ci < last_chunk; ++ci) {
         const SbChunk& c = plan.chunks[ci];
-        if (ci == 1 && after_first) { (void)hipEventRecord(after_first, s); after_first = nullptr; }
+        if (ci == first_chunk + 1 && after_first) { (void)hipEventRecord(after_first, s); after_first = nullptr; }
         LstmArgs ca = a;
         ca.rows = a.rows + c.slot0;
         ca.num_rows = c.nrows; ca.num_tiles = c.num_tiles; ca.ex = c.ex;
@@ -369,7 +229,7 @@ static void launch_sb_lstm(const fsnp_handle* h, const SbPlan& plan, const LstmA
         // lands on one of its CUs runs at ~0.6x (and each GEMM launch lasts as long as its slowest workgroup: stage 1.25 -> 1.85 ms),
         // so the chunk claims its CUs' whole LDS and the GEMM workgroups go to the other CUs
         // (never for a launch planned with two workgroups per CU: they would no longer be co-resident)
-        ca.coop_own_cu = (h->side_stream && s == h->side_stream && chunk_workgroups(h, c) <= h->num_cus_real) ? 160 * 1024 - 256 : 0;
+        ca.coop_own_cu = (h->side_stream && s == h->side_stream && chunk_workgroups(h, c) <= h->num_cus_real) ? kOwnCuLds : 0;
         ca.coop_err = h->d_err;
         ca.coop_abort = abort_word;
         ca.coop_units = c.units; ca.coop_groups = c.groups; ca.coop_rows_per_group = c.rpg;
@@ -385,15 +245,12 @@ static void launch_sb_lstm(const fsnp_handle* h, const SbPlan& plan, const LstmA
             }
         }, h, &fp, h->num_cus_real / kNumXcds, h->coop_chain_stats);
     }
-    if (after_first && last_chunk == nchunks) (void)hipEventRecord(after_first, s);
+    if (after_first) (void)hipEventRecord(after_first, s);      // (a range of one chunk)
 }
-static void launch_build_rows(const SbPlan& plan, RowDesc* rows, int F, int T, int mode, int batch_offset, int global_batch,
-                              int dense_out, int groups, int out_channels, hipStream_t s) {
-    for (const SbChunk& c : plan.chunks) {
-        const int slots = c.num_tiles * c.rps;
-        hipLaunchKernelGGL(build_rows_kernel, dim3(cdiv(slots, 256)), dim3(256), 0, s, rows + c.slot0, c.nrows, c.num_tiles, c.rps,
-                           F, T, mode, batch_offset, global_batch, dense_out, c.row0, groups, out_channels);
-    }
+void take_coop_chain_stats(fsnp_handle* h, int64_t out[2], bool reset) {
+    std::lock_guard<std::mutex> lk(g_coop_mu);
+    out[0] = h->coop_chain_stats[0]; out[1] = h->coop_chain_stats[1];
+    if (reset) h->coop_chain_stats[0] = h->coop_chain_stats[1] = 0;
 }
 // full-band LSTM of the original FullSubNet: B sequences, always the cooperative kernel (units in {8, 16, 32})
 static int fb_row_tiles(int B) { return cdiv(B, 32); }
@@ -404,16 +261,15 @@ static int fb_coop_units(const fsnp_handle* h, int B) {
 
 // Pipelined serving loop (fsnp_set_pipeline): which chunks of a plan go to the side stream (planner.cpp plan_first_deferred)
 //   returns: first deferred chunk (== chunks.size(): nothing is deferred; 0: the whole plan)
-static int plan_first_deferred(const fsnp_handle* h, const SbPlan& plan) { return plan_first_deferred(pctx(h), plan, h->defer_small != 0); }
+int plan_first_deferred(const fsnp_handle* h, const SbPlan& plan) { return plan_first_deferred(pctx(h), plan, h->defer_small != 0); }
 // which kernel runs the full-band LSTM of a `batch`-utterance FullSubNet forward, in what shape (fsnp_debug_fullband_launch)
-struct FbShape { int kernel, tiles, rows_per_tile, units; };      // kernel: 0 = lstm_coop_seq (K split), 1 = lstm_fbv (VALU), 2 = lstm_generic
-static FbShape fb_shape(const fsnp_handle* h, int batch) {
+FbShape fb_shape(const fsnp_handle* h, int batch) {
     if (h->generic_fb) {               // (runtime-sized kernel for a full-band model no K-split instantiation exists for: workgroups of rg sequences)
         const int rg = lstm_generic_rows_per_group(h->CH, h->F, batch, h->num_cus_real);
-        return {2, rg > 0 ? cdiv(batch, rg) : 0, rg, 0};
+        return {FbKernel::Generic, rg > 0 ? cdiv(batch, rg) : 0, rg, 0};
     }
-    if (h->fb_valu && lstm_fbv_available(h->fbw, batch, h->num_cus_real)) return {1, fb_row_tiles(batch), 32, 0};
-    return {0, fb_row_tiles(batch), 32, fb_coop_units(h, batch)};
+    if (h->fb_valu && lstm_fbv_available(h->fbw, batch, h->num_cus_real)) return {FbKernel::Valu, fb_row_tiles(batch), 32, 0};
+    return {FbKernel::KSplitSeq, fb_row_tiles(batch), 32, fb_coop_units(h, batch)};
 }
 // the full-band LSTM launch of the original FullSubNet (lstm_coop_seq, never owns its CUs): round robin, at the occupancy measured at commit
 static CoopFootprint fb_coop_footprint(const PlannerCtx& c, int CH, int batch, int fb_per_cu) {
@@ -425,8 +281,8 @@ static int fb_units_index(int units) { return units == 8 ? 0 : units == 16 ? 1 :
 // The side-by-side decision of the pipelined FullSubNet loop at `batch` utterances (full mode): for every chunk of the plan that goes to
 // the side stream, may the next forward's full-band LSTM run beside it?  Records of 9 ints (fsnp_debug.h: fsnp_debug_pipeline_pairing).
 //   fb_per_cu: measured occupancy at 8 / 16 / 32 units per workgroup; fb_valu: the full-band LSTM runs on lstm_fbv instead (chained: B <= 4)
-static int pipeline_pairing(const PlannerCtx& c, bool defer_small, int F, int CH, int batch, const int fb_per_cu[3], bool fb_valu,
-                            int32_t* out, int max_records) {
+int pipeline_pairing(const PlannerCtx& c, bool defer_small, int F, int CH, int batch, const int fb_per_cu[3], bool fb_valu,
+                     int32_t* out, int max_records) {
     const SbPlan plan = plan_sb(c, batch * F);
     const int first = plan_first_deferred(c, plan, defer_small), cpx = c.num_cus_real % kNumXcds == 0 ? c.num_cus_real / kNumXcds : 0;
     const int u = lstm_coop_pick_units(CH, fb_row_tiles(batch), c.num_cus_real, 8);
@@ -445,7 +301,7 @@ static int pipeline_pairing(const PlannerCtx& c, bool defer_small, int F, int CH
     return n;
 }
 
-static int rows_per_utt(const fsnp_handle* h, int mode) {
+int rows_per_utt(const fsnp_handle* h, int mode) {
     return mode == FSNP_MODE_PARITY ? h->F / h->cfg.num_groups_in_drop_band : h->F;
 }
 
@@ -501,7 +357,7 @@ static Workspace plan_workspace(const fsnp_handle* h, int B, int T, int mode, bo
 // whose clip lengths vary never stalls other streams while it climbs to its high-water mark (fsnp_reserve jumps there at once).
 // The old buffer is released behind everything that may still read it: earlier forwards on `s` (in order), their deferred
 // chunks on the side stream (an event), forwards on another stream (forward_impl orders `s` behind them before it gets here).
-static int ensure_workspace(fsnp_handle* h, size_t bytes, hipStream_t s) {
+int ensure_workspace(fsnp_handle* h, size_t bytes, hipStream_t s) {
     bytes = align_up(bytes, 4096);
     if (bytes <= h->ws_bytes) return 0;
     unsigned char* nw = nullptr;
@@ -535,7 +391,7 @@ int mark_forward_done(fsnp_handle* h, hipStream_t s) {
 
 // hipEvents for the per-forward timing records come from a pool; records that nobody reads are folded into the
 // accumulators once 256 have piled up (they completed long ago), so timing never grows without bound.
-static int drain_timing(fsnp_handle* h) {
+int drain_timing(fsnp_handle* h) {
     for (auto& r : h->timing_recs) {
         float fb = 0, lstm = 0, all = 0, first = 0;
         // a forward that failed half way leaves events unrecorded: such a record is dropped, not counted
@@ -563,19 +419,6 @@ static int take_timing_rec(fsnp_handle* h, TimingRec& rec) {
 }
 
 
-static double lstm_flops_per_step(const fsnp_handle* h) {
-    if (h->sb_tcn) return 8 * (2.0 * h->NIN * h->CH + 2.0 * h->CH * 3 + 2.0 * h->CH * h->NIN) + 2.0 * h->NIN * h->cfg.output_size;
-    const double H = h->H, NIN = h->NIN, OUT = h->cfg.output_size, G = h->NG;
-    return 2.0 * G * H * (NIN + H) + 2.0 * G * H * (2 * H) + 2.0 * H * OUT;
-}
-static double tcn_flops_per_frame(const fsnp_handle* h) {
-    const double F = h->F, CH = h->CH;
-    return h->NB * (2.0 * F * CH + 2.0 * CH * 3 + 2.0 * CH * F) + 2.0 * F * F;
-}
-static double fb_lstm_flops_per_frame(const fsnp_handle* h) {   // original FullSubNet: LSTM(F, CH) x 2 + Linear(CH, F)
-    const double F = h->F, CH = h->CH;
-    return 2.0 * h->NG * CH * (F + CH) + 2.0 * h->NG * CH * (2 * CH) + 2.0 * CH * F;
-}
 
 // The fused recurrent model + Linear on a dense input x [num_seq][steps][NIN] with a given plan (fsnp_lstm2_fc, calibration).
 static int run_dense_plan(fsnp_handle* h, const SbPlan& plan, const float* x, float* out, int num_seq, int steps, hipStream_t s) {
@@ -591,7 +434,7 @@ static int run_dense_plan(fsnp_handle* h, const SbPlan& plan, const float* x, fl
     RowDesc* rows = reinterpret_cast<RowDesc*>(h->ws);
     h->have_last = false;   // the workspace no longer holds a forward's stages
     if (coop) FSNP_HIP_CHECK(hipMemsetAsync(h->ws + coop_off, 0, coop_bytes, s));
-    launch_build_rows(plan, rows, 1, steps, 0, 0, 1, 1, 2, h->cfg.output_size, s);
+    launch_build_rows(plan, rows, dense_rows(steps, h->cfg.output_size), s);
     LstmArgs a{};
     a.rows = rows; a.dense = x; a.dense_stride = h->NIN; a.out = out; a.out_stride_o = steps;
     a.num_rows = num_seq; a.Tp = steps; a.LA = 0; a.FP = 0; a.F = 1; a.NSBN = 0; a.act = h->cfg.sb_act;
@@ -617,7 +460,7 @@ struct CalKey {
 static std::mutex g_cal_mu;
 static std::map<CalKey, CostTable> g_cal_cache;
 
-static int calibrate_costs(fsnp_handle* h, bool adopt = true, CostTable* measured = nullptr) {
+int calibrate_costs(fsnp_handle* h, bool adopt, CostTable* measured) {
     if (adopt && (h->planner.cost.calibrated || !h->calibrate)) return 0;
     if (h->sb_tcn || h->generic_sb || !h->committed) return 0;
     int occ_sig = h->planner.coop_occ;
@@ -741,209 +584,6 @@ static int calibrate_costs(fsnp_handle* h, bool adopt = true, CostTable* measure
     if (adopt) h->planner.cost = t;
     std::lock_guard<std::mutex> lk(g_cal_mu);
     g_cal_cache[key] = t;
-    return 0;
-}
-
-// ---- fsnp_set_verify: the sequences a plan hands to column-split kernels, run again on the one-tile-per-CU kernel (no inter-workgroup
-// exchange at all) into a scratch mask and compared on the device.  The kernels sum K in different orders, so "equal" is a tolerance:
-// |a - b| <= 1e-4 + 1e-3 |b| (kernel-to-kernel differences are ~1e-6; one corrupted exchange element moves the mask by 1e-2 and more).
-__global__ __launch_bounds__(256) void verify_compare_kernel(const float* __restrict__ out, const float* __restrict__ ref, const RowDesc* __restrict__ rows,
-                                                             int num_slots, int T, int OC, long stride_o, unsigned* err_host,
-                                                             unsigned long long* first_key) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)num_slots * OC * T) return;
-    const int t = (int)(i % T), o = (int)((i / T) % OC), slot = (int)(i / ((long)OC * T));
-    const RowDesc rd = rows[slot];
-    if (!rd.valid) return;
-    const size_t at = (size_t)rd.out_off + (size_t)o * stride_o + t;
-    const float a = out[at], b = ref[at];
-    if (!(fabsf(a - b) <= 1e-4f + 1e-3f * fabsf(b))) {
-        // 20 bits of utterance, 20 of bin, 24 of frame: nothing the entry points accept wraps (the 8 / 10 / 14-bit key did)
-        const unsigned long long key = ((unsigned long long)(unsigned)rd.b << 44) | ((unsigned long long)((unsigned)rd.f & 0xFFFFFu) << 24) |
-                                       (unsigned long long)((unsigned)t & 0xFFFFFFu);
-        __hip_atomic_fetch_min(first_key, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_fetch_or(err_host, kErrVerify, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-}
-static bool plan_has_exchange(const SbPlan& plan) {
-    for (const SbChunk& c : plan.chunks) if (is_column_split(c.kind)) return true;
-    return false;
-}
-// `a` = the arguments of the forward's own sub-band launches (its rows / md_row belong to `plan`); out_elems = floats of the mask tensor
-static int verify_pass(fsnp_handle* h, const SbPlan& plan, const Dims& d, int mode, int batch_offset, int global_batch, const LstmArgs& a,
-                       const SubbandBuffers& sbuf, size_t out_elems, hipStream_t s) {
-    const bool cumulative = h->cfg.norm_type == FSNP_NORM_CUMULATIVE_LAPLACE || h->cfg.norm_type == FSNP_NORM_CUMULATIVE_LAYER;
-    // the exchange-free plan of exactly the column-split chunks' sequences; consecutive chunks (B = 8: three launches over rows
-    // [0, 2056)) are re-run as ONE range - one round of half tiles instead of one per launch
-    SbPlan vp;
-    PlannerCtx pc = pctx(h);
-    pc.lstm_coop = 0;
-    pc.half_tiles_without_coop = true;
-    pc.ih_bf16 = 0;                          // (the re-run is fp32 whatever fsnp_set_precision says: below)
-    bool bad = false;
-    int run0 = 0, run_n = 0;
-    auto flush = [&]() {
-        if (run_n == 0) return;
-        const SbPlan one = plan_sb(pc, run_n);
-        for (SbChunk k : one.chunks) {
-            if (k.kind != SbKind::RowTile && k.kind != SbKind::HalfTile) { bad = true; return; }
-            k.row0 += run0; k.slot0 = vp.total_slots; k.coop_tile0 = 0;
-            vp.total_slots += k.num_tiles * k.rps;
-            vp.chunks.push_back(k);
-        }
-        run_n = 0;
-    };
-    for (const SbChunk& c : plan.chunks) {
-        const bool exch = is_column_split(c.kind);
-        if (exch && run_n > 0 && c.row0 == run0 + run_n) { run_n += c.nrows; continue; }
-        flush();
-        if (exch) { run0 = c.row0; run_n = c.nrows; }
-    }
-    flush();
-    if (bad) { set_error("fsnp_set_verify: no exchange-free kernel for this model"); return 2; }
-    if (vp.chunks.empty()) return 0;
-    const size_t out_b = align_up(out_elems * 4, 256), rows_b = align_up((size_t)vp.total_slots * sizeof(RowDesc), 256);
-    const size_t md_b = cumulative ? align_up((size_t)vp.total_slots * d.Tp * sizeof(NormMD), 256) : 0;
-    const size_t need = out_b + rows_b + md_b;
-    if (need > h->verify_bytes) {
-        if (h->verify_out) FSNP_HIP_CHECK(hipFreeAsync(h->verify_out, s));
-        h->verify_out = nullptr; h->verify_bytes = 0;
-        FSNP_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&h->verify_out), need, s));
-        h->verify_bytes = need;
-    }
-    unsigned char* vb = reinterpret_cast<unsigned char*>(h->verify_out);
-    RowDesc* vrows = reinterpret_cast<RowDesc*>(vb + out_b);
-    NormMD* vmd = cumulative ? reinterpret_cast<NormMD*>(vb + out_b + rows_b) : nullptr;
-    launch_build_rows(vp, vrows, h->F, d.T, mode, batch_offset, global_batch, 0, h->cfg.num_groups_in_drop_band, h->cfg.output_size, s);
-    if (cumulative) {
-        SubbandBuffers vs = sbuf;
-        vs.md_row = vmd;
-        launch_subband_stats(d, h->cfg.norm_type, vs, vrows, vp.total_slots, s);      // (cumulative norms: per-slot tables only)
-    }
-    LstmArgs va = a;
-    va.rows = vrows; va.md_row = vmd; va.out = reinterpret_cast<float*>(vb);
-    // the column-split kernels are fp32 in every precision mode, so their check is too: under fsnp_set_precision(h, 1) the row-tile /
-    // half-tile kernels would otherwise run their bf16 ih-GEMM here and differ from a CORRECT exchange by ~1e-3 - a false alarm
-    const int keep_bf16 = h->lw.ih_bf16;
-    h->lw.ih_bf16 = 0;
-    launch_sb_lstm(h, vp, va, nullptr, nullptr, nullptr, s);
-    h->lw.ih_bf16 = keep_bf16;
-    const long n = (long)vp.total_slots * h->cfg.output_size * d.T;
-    if (!h->verify_key) FSNP_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&h->verify_key), 8));
-    FSNP_HIP_CHECK(hipMemsetAsync(h->verify_key, 0xFF, 8, s));
-    hipLaunchKernelGGL(verify_compare_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a.out, reinterpret_cast<const float*>(vb), vrows,
-                       vp.total_slots, d.T, h->cfg.output_size, a.out_stride_o, h->d_err, h->verify_key);
-    FSNP_HIP_CHECK(hipGetLastError());
-    h->verify_runs += 1;
-    return 0;
-}
-
-// ---- fsnp_set_verify_sample: ONE row tile of a column-split launch, recomputed off the critical path.
-// The sampled tile's normalised input and the mask values its launch wrote are SNAPSHOT on the launch's own stream (two tiny kernels);
-// the recomputation - the exchange-free half-tile kernel on the snapshot, two workgroups, as long as a whole round: ~13 ms at 2 s clips -
-// and the comparison run on a stream of their own and touch nothing but private buffers, so the caller may free / overwrite the mask and
-// later forwards may rebuild the workspace meanwhile.  A mismatch flags the handle (code 7) whenever it is found: the report names the
-// sampled forward's (utterance, bin, frame), the call that notices it is a later one.
-__global__ __launch_bounds__(256) void vs_copy_kernel(const float* __restrict__ out, const RowDesc* __restrict__ rows, RowDesc* __restrict__ rows_copy,
-                                                      float* __restrict__ snap, int num_slots, int T, int OC, long stride_o) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < num_slots) rows_copy[i] = rows[i];
-    if (i >= num_slots * OC * T) return;
-    const int t = i % T, o = (i / T) % OC, slot = i / (OC * T);
-    const RowDesc rd = rows[slot];
-    snap[i] = rd.valid ? out[(size_t)rd.out_off + (size_t)o * stride_o + t] : 0.0f;
-}
-__global__ __launch_bounds__(256) void vs_compare_kernel(const float* __restrict__ snap, const float* __restrict__ ref, const RowDesc* __restrict__ rows,
-                                                         int num_slots, int T, int OC, unsigned* err_host, unsigned long long* first_key) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= num_slots * OC * T) return;
-    const int t = i % T, slot = i / (OC * T);
-    const RowDesc rd = rows[slot];
-    if (!rd.valid) return;
-    const float a = snap[i], b = ref[i];                        // ref: the dense run's [slot][o][t]
-    if (!(fabsf(a - b) <= 1e-4f + 1e-3f * fabsf(b))) {
-        const unsigned long long key = ((unsigned long long)(unsigned)rd.b << 44) | ((unsigned long long)((unsigned)rd.f & 0xFFFFFu) << 24) |
-                                       (unsigned long long)((unsigned)t & 0xFFFFFFu);
-        __hip_atomic_fetch_min(first_key, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_fetch_or(err_host, kErrVerify, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-}
-// a plan that can be sampled: column-split launches only, each leaving a CU free ON EVERY XCD.  The recomputation's two workgroups own
-// their CUs for ~13 ms (one each on two XCDs), and the dispatcher deals a launch's workgroups to the XCDs by index, not by room: B = 8's
-// 252-workgroup launches put 32 on some XCDs - the 32nd waited for the sample to end and the launch (all of whose workgroups must be
-// resident) with it: +7.7 ms per sampled forward (profiles/r06_verify_sample.md).  Such plans (B = 3, B = 8) are not sampled.
-static bool plan_can_be_sampled(const fsnp_handle* h, const SbPlan& plan) {
-    if (plan.chunks.empty() || !h->planner.lstm16_ok || h->num_cus_real % 8 != 0) return false;
-    const int cpx = h->num_cus_real / 8;
-    const PlannerCtx pc = pctx(h);
-    for (const SbChunk& c : plan.chunks) {
-        if (!is_column_split(c.kind) || c.rps != 32) return false;
-        const CoopFootprint f = chunk_footprint(pc, c, true, 1);         // (launch_sb_lstm: XCD-local placement where it fits, else round robin)
-        if (*std::max_element(f.per_xcd, f.per_xcd + kNumXcds) > cpx - 1) return false;
-    }
-    return true;
-}
-// `st` = the stream the plan's launches were enqueued on (the caller's, or the side stream in the pipelined loop)
-static int verify_sample(fsnp_handle* h, const SbPlan& plan, const Dims& d, const LstmArgs& a, const SubbandBuffers& sbuf, hipStream_t st) {
-    if (h->vs_busy) {
-        const hipError_t q = hipEventQuery(h->ev_vs_done);
-        if (q == hipErrorNotReady) { (void)hipGetLastError(); h->vs_skipped += 1; return 0; }      // the previous sample is still being recomputed
-        h->vs_busy = false;
-    }
-    const long long n = h->vs_runs;
-    const SbChunk& c = plan.chunks[(size_t)(n % (long long)plan.chunks.size())];
-    const int tile = (int)((n / (long long)plan.chunks.size()) % c.num_tiles), nslots = 32;
-    const int OC = h->cfg.output_size, T = d.T, Tp = d.Tp, NIN = h->NIN;
-    const size_t x_b = align_up((size_t)nslots * Tp * NIN * 4, 256), o_b = align_up((size_t)nslots * OC * T * 4, 256);
-    const size_t r_b = align_up((size_t)nslots * sizeof(RowDesc), 256);
-    const size_t need = x_b + 2 * o_b + 2 * r_b + 256;
-    if (!h->vs_stream) {
-        FSNP_HIP_CHECK(hipStreamCreateWithFlags(&h->vs_stream, hipStreamNonBlocking));
-        FSNP_HIP_CHECK(hipEventCreateWithFlags(&h->ev_vs_snap, hipEventDisableTiming));
-        FSNP_HIP_CHECK(hipEventCreateWithFlags(&h->ev_vs_done, hipEventDisableTiming));
-    }
-    if (need > h->vs_bytes) {                 // (no sample in flight here: the buffer is idle)
-        if (h->vs_buf) FSNP_HIP_CHECK(hipFreeAsync(h->vs_buf, st));
-        h->vs_buf = nullptr; h->vs_bytes = 0;
-        FSNP_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&h->vs_buf), need, st));
-        h->vs_bytes = need;
-    }
-    float* vx = reinterpret_cast<float*>(h->vs_buf);
-    float* vsnap = reinterpret_cast<float*>(h->vs_buf + x_b);
-    float* vref = reinterpret_cast<float*>(h->vs_buf + x_b + o_b);
-    RowDesc* vrows_src = reinterpret_cast<RowDesc*>(h->vs_buf + x_b + 2 * o_b);
-    RowDesc* vrows = reinterpret_cast<RowDesc*>(h->vs_buf + x_b + 2 * o_b + r_b);
-    unsigned long long* vkey = reinterpret_cast<unsigned long long*>(h->vs_buf + x_b + 2 * o_b + 2 * r_b);
-    const size_t slot0 = (size_t)c.slot0 + (size_t)tile * c.rps;
-    // ---- snapshot, behind the launches it samples
-    SbGatherArgs ga{};
-    ga.att_mag = a.att_mag; ga.fb_rel = a.fb_rel; ga.fb_branch_stride = a.fb_branch_stride;
-    ga.rows = a.rows + slot0; ga.md_utt = a.md_utt; ga.md_row = a.md_row ? a.md_row + slot0 * Tp : nullptr;
-    ga.x = vx; ga.xstride = NIN;
-    ga.num_slots = nslots; ga.Tp = Tp; ga.FP = d.FP; ga.F = d.F; ga.NSBN = h->cfg.sb_num_neighbors; ga.NIN = NIN; ga.NFBN = h->cfg.fb_num_neighbors;
-    launch_sb_gather(ga, st);
-    const int nout = nslots * OC * T;
-    hipLaunchKernelGGL(vs_copy_kernel, dim3(cdiv(nout, 256)), dim3(256), 0, st, a.out, a.rows + slot0, vrows_src, vsnap, nslots, T, OC, a.out_stride_o);
-    FSNP_HIP_CHECK(hipMemsetAsync(vkey, 0xFF, 8, st));
-    FSNP_HIP_CHECK(hipEventRecord(h->ev_vs_snap, st));
-    // ---- recomputation and comparison, on their own stream
-    hipStream_t vs = h->vs_stream;
-    FSNP_HIP_CHECK(hipStreamWaitEvent(vs, h->ev_vs_snap, 0));
-    hipLaunchKernelGGL(build_rows_kernel, dim3(1), dim3(256), 0, vs, vrows, nslots, 2, 16, 1, T, 0, 0, 1, 1, 0, 2, OC);
-    LstmArgs va{};
-    va.rows = vrows; va.dense = vx; va.dense_stride = NIN; va.out = vref; va.out_stride_o = T;
-    va.num_rows = nslots; va.num_tiles = 2; va.Tp = Tp; va.LA = d.LA; va.FP = 0; va.F = 1; va.NSBN = 0; va.act = h->cfg.sb_act;
-    va.coop_own_cu = 1;                      // its two workgroups share the chip with the following forwards: they own their CUs (lstm16.hip: OWN)
-    const int keep_bf16 = h->lw.ih_bf16;     // the column-split kernels are fp32 in every precision mode: so is their check
-    h->lw.ih_bf16 = 0;
-    launch_lstm16(h->lw, va, vs);
-    h->lw.ih_bf16 = keep_bf16;
-    hipLaunchKernelGGL(vs_compare_kernel, dim3(cdiv(nout, 256)), dim3(256), 0, vs, vsnap, vref, vrows_src, nslots, T, OC, h->d_err, vkey);
-    FSNP_HIP_CHECK(hipGetLastError());
-    FSNP_HIP_CHECK(hipEventRecord(h->ev_vs_done, vs));
-    h->vs_busy = true;
-    h->vs_runs += 1;
-    h->verify_key_sampled = vkey;
     return 0;
 }
 
@@ -1113,9 +753,12 @@ size_t fsnp_workspace_bytes(const fsnp_handle* h, int32_t batch, int32_t frames,
     return plan_workspace(h, batch, frames, mode).total;
 }
 
-static int forward_impl(fsnp_handle* h, const float* mag, const float* real, const float* imag, bool is_complex,
-                        const int64_t strides[3][3], float* out, int32_t batch, int32_t frames,
-                        int32_t mode, int32_t batch_offset, int32_t global_batch, void* hip_stream, const int32_t* lengths = nullptr) {
+// ---- the forward, as a list of steps over one Forward
+
+// every refusal of a forward, in this order; fills d.  Nothing is launched.
+static int check_forward_args(fsnp_handle* h, const float* mag, const float* real, const float* imag, bool is_complex, const int64_t strides[3][3],
+                              const float* out, int batch, int frames, int mode, int batch_offset, int global_batch, const int32_t* lengths,
+                              Dims& d) {
     if (batch <= 0 || frames <= 0) { set_error("fsnp_forward: empty input (B=%d, T=%d)", batch, frames); return 2; }
     if (!h || !mag || !out || !strides) { set_error("fsnp_forward: null argument"); return 1; }
     const bool fsn = h->model == FSNP_MODEL_FULLSUBNET;
@@ -1128,8 +771,6 @@ static int forward_impl(fsnp_handle* h, const float* mag, const float* real, con
         return 2;
     }
     if (batch_offset < 0 || global_batch < batch_offset + batch) { set_error("bad batch_offset/global_batch"); return 2; }
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    Dims d;
     d.B = batch; d.T = frames; d.LA = h->cfg.look_ahead; d.Tp = frames + d.LA; d.F = h->F; d.FP = h->FP;
     d.CH = h->CH; d.H = h->H; d.NSB = h->NSB; d.NIN = h->NIN;
     int kmax = 1;
@@ -1140,224 +781,241 @@ static int forward_impl(fsnp_handle* h, const float* mag, const float* real, con
         if (mode != FSNP_MODE_FULL) { set_error("fsnp_forward_lengths: per-utterance lengths need FULL mode"); return 2; }
         if (const int rc = check_lengths(h, lengths, batch, frames, "fsnp_forward_lengths")) return rc;
     }
-    const int fb_units = (fsn && !h->generic_fb) ? fb_coop_units(h, batch) : 0;
-    if (fsn && !h->generic_fb && fb_units == 0) { set_error("FullSubNet: at most %d utterances per call (full-band LSTM residency); split the batch", 32 * (h->num_cus_real / 16)); return 2; }
+    if (fsn && !h->generic_fb && fb_coop_units(h, batch) == 0) { set_error("FullSubNet: at most %d utterances per call (full-band LSTM residency); split the batch", 32 * (h->num_cus_real / 16)); return 2; }
+    return 0;
+}
 
-    FSNP_ON_DEVICE(h);
-    if (calibrate_costs(h)) return 4;            // first planning call of the process for this kind of handle only (~0.1 s)
-    const int num_rows = batch * rows_per_utt(h, mode);
-    const SbPlan plan = plan_sb(h, num_rows, forward_gather_bytes(h, batch, frames));
-    if (plan.chunks.empty()) {
-        set_error("no kernel plan for %d sub-band sequences on this device (%d CUs): the %s sub-band model needs at least %d",
-                  num_rows, h->num_cus_real, h->gru ? "GRU" : "LSTM", h->H / 128);
-        return 2;
-    }
-    const Workspace w = plan_workspace(h, batch, frames, mode, lengths != nullptr);
-    if (order_after_last_forward(h, s)) return 4;
-    if (ensure_workspace(h, w.total, s)) return 4;
+// one forward: its stream, plan, workspace half and the buffers its steps share
+struct Forward {
+    fsnp_handle* h; hipStream_t s; Dims d; int mode, batch_offset, global_batch;
+    SbPlan plan; Workspace w; int slot; unsigned char* base; RowDesc* rows; SubbandBuffers sbuf; TimingRec rec;
+    float* fptr(size_t off) const { return reinterpret_cast<float*>(base + off); }
+};
+
+// orders the forward behind everything that used its workspace half, and starts its timing record
+static int bind_workspace(Forward& f, bool ragged) {
+    fsnp_handle* h = f.h;
+    f.w = plan_workspace(h, f.d.B, f.d.T, f.mode, ragged);
+    if (order_after_last_forward(h, f.s)) return 4;
+    if (ensure_workspace(h, f.w.total, f.s)) return 4;
     // pipelined mode: alternate between the two workspace halves; the half about to be rebuilt was last read by the
     // deferred remainder chunks of the forward before the previous one
-    const int slot = h->pipeline ? h->ws_slot : 0;
+    f.slot = h->pipeline ? h->ws_slot : 0;
     if (h->pipeline) {
         h->ws_slot ^= 1;
-        if (h->side_used[slot]) FSNP_HIP_CHECK(hipStreamWaitEvent(s, h->ev_side[slot], 0));
+        if (h->side_used[f.slot]) FSNP_HIP_CHECK(hipStreamWaitEvent(f.s, h->ev_side[f.slot], 0));
     }
-    unsigned char* base = h->ws + (size_t)slot * h->ws_bytes;
-    auto fptr = [&](size_t off) { return reinterpret_cast<float*>(base + off); };
-
-    TimingRec rec{};
+    f.base = h->ws + (size_t)f.slot * h->ws_bytes;
     if (h->timing) {
-        if (take_timing_rec(h, rec)) return 4;
-        h->timing_recs.push_back(rec);          // owned by the handle from here on (no leak on an early return)
-        FSNP_HIP_CHECK(hipEventRecord(rec.e[0], s));
+        if (take_timing_rec(h, f.rec)) return 4;
+        h->timing_recs.push_back(f.rec);        // owned by the handle from here on (no leak on an early return)
+        FSNP_HIP_CHECK(hipEventRecord(f.rec.e[0], f.s));
     }
-    const int num_slots = plan.total_slots;
-    RowDesc* rows = reinterpret_cast<RowDesc*>(base + w.rows);
+    f.rows = reinterpret_cast<RowDesc*>(f.base + f.w.rows);
     const bool cumulative = h->cfg.norm_type == FSNP_NORM_CUMULATIVE_LAPLACE || h->cfg.norm_type == FSNP_NORM_CUMULATIVE_LAYER;
-    SubbandBuffers sbuf;
-    sbuf.att_mag = fptr(w.att); sbuf.fb = fptr(w.fb); sbuf.refl_w = h->d_refl_w; sbuf.refl_wfb = h->d_refl_wfb;
+    SubbandBuffers& sbuf = f.sbuf;
+    sbuf.att_mag = f.fptr(f.w.att); sbuf.fb = f.fptr(f.w.fb); sbuf.refl_w = h->d_refl_w; sbuf.refl_wfb = h->d_refl_wfb;
     sbuf.NFBN = h->cfg.fb_num_neighbors;
-    sbuf.acc = reinterpret_cast<double*>(base + w.sb_acc);
-    sbuf.md_utt = reinterpret_cast<NormMD*>(base + w.md_utt);
-    sbuf.md_row = cumulative ? reinterpret_cast<NormMD*>(base + w.md_row) : nullptr;
-    // the prologue of both models, one launch: zero the accumulators / exchange images / counters, describe the sub-band rows, and
-    // - fsnp_watch_weights - fingerprint the caller's source tensors (a .data edit since the pack flags the handle)
-    auto prologue = [&](hipStream_t st) -> int {
-        const bool watch = h->watch_nseg > 0 && (h->watch_calls++ % h->watch_every) == 0;
-        if (plan.chunks.size() > 8) {                     // (more chunks than the argument block holds: the separate kernels)
-            launch_zero_region(base + w.zero_begin, w.zero_end - w.zero_begin, st);
-            launch_build_rows(plan, rows, h->F, frames, mode, batch_offset, global_batch, 0, h->cfg.num_groups_in_drop_band, h->cfg.output_size, st);
-            return watch ? launch_weight_watch(h, st, false) : 0;
-        }
-        PrologueArgs pa{};
-        pa.zero = reinterpret_cast<uint4*>(base + w.zero_begin);
-        pa.n16 = (w.zero_end - w.zero_begin) / 16;
-        pa.zero_blocks = (int)std::min<size_t>((pa.n16 + 255) / 256, 2048);
-        pa.rows = rows;
-        for (const SbChunk& c : plan.chunks) {
-            PrologueChunk& k = pa.chunk[pa.nchunks++];
-            k.slot0 = c.slot0; k.nrows = c.nrows; k.tiles = c.num_tiles; k.rt = c.rps; k.row0 = c.row0; k.blocks = cdiv(c.num_tiles * c.rps, 256);
-            pa.rows_blocks += k.blocks;
-        }
-        pa.F = h->F; pa.T = frames; pa.mode = mode; pa.batch_offset = batch_offset; pa.global_batch = global_batch;
-        pa.groups = h->cfg.num_groups_in_drop_band; pa.OC = h->cfg.output_size;
-        pa.segs = static_cast<const WatchSeg*>(h->watch_segs); pa.nseg = watch ? h->watch_nseg : 0;
-        pa.watch_blocks = watch ? std::min(h->watch_nseg, kWatchBlocks) : 0;
-        pa.watch_acc = h->watch_acc; pa.err_host = h->d_err;
-        hipLaunchKernelGGL(prologue_kernel, dim3(pa.zero_blocks + pa.rows_blocks + pa.watch_blocks), dim3(256), 0, st, pa);
-        return 0;
-    };
-    if (lengths) {
-        int* lens = reinterpret_cast<int*>(base + w.lens);
-        launch_set_lengths(lengths, batch, d.LA, lens, lens + batch, s);
-        d.lens = lens; d.tpb = lens + batch;
-    }
-    if (prologue(s)) return 4;
+    sbuf.acc = reinterpret_cast<double*>(f.base + f.w.sb_acc);
+    sbuf.md_utt = reinterpret_cast<NormMD*>(f.base + f.w.md_utt);
+    sbuf.md_row = cumulative ? reinterpret_cast<NormMD*>(f.base + f.w.md_row) : nullptr;
+    return 0;
+}
 
-    if (!fsn) {
-        FrontendBuffers fbuf;
-        fbuf.raw = fptr(w.raw); fbuf.frame = reinterpret_cast<double*>(base + w.frame);
-        fbuf.md = reinterpret_cast<NormMD*>(base + w.md); fbuf.fsum = reinterpret_cast<double*>(base + w.fsum);
-        fbuf.tot = reinterpret_cast<double*>(base + w.fe_tot);
-        fbuf.gate = fptr(w.gate); fbuf.att = fptr(w.att);
-        const float* in[3] = {mag, real, imag};
-        TcnBuffers tbuf;
-        tbuf.att = fptr(w.att); tbuf.x = fptr(w.x); tbuf.y1 = fptr(w.y1); tbuf.y2 = fptr(w.y2);
-        tbuf.gn = reinterpret_cast<double*>(base + w.gn); tbuf.fb = fptr(w.fb);
-        tbuf.dbg_tcn0 = h->debug ? fptr(w.dbg_tcn0) : nullptr;
-        // the caller's tensors are read by the repack kernel only; everything up to the LSTM then stays in the workspace
-        launch_frontend(d, h->cfg.norm_type, in, strides, is_complex, h->fw, fbuf, s);
-        launch_tcn(d, h->cfg.fb_act, h->tw, tbuf, s);
-        launch_subband_stats(d, h->cfg.norm_type, sbuf, rows, num_slots, s);
-    } else {
-        // fullsubnet.py:82-90: pad, norm(noisy_mag), 2-layer LSTM(F -> CH), Linear(CH, F) + fb_act
-        FrontendBuffers fbuf{};
-        fbuf.raw = fptr(w.att); fbuf.frame = reinterpret_cast<double*>(base + w.frame);
-        fbuf.md = reinterpret_cast<NormMD*>(base + w.md);
-        launch_frontend_mag(d, h->cfg.norm_type, mag, strides[0], is_complex, fbuf, s);
-        const FbShape fbs = fb_shape(h, batch);
-        const int fb_rg = fbs.rows_per_tile, fb_tiles = fbs.tiles;
-        RowDesc* fb_rows = reinterpret_cast<RowDesc*>(base + w.fb_rows);
-        hipLaunchKernelGGL(build_rows_kernel, dim3(cdiv(fb_tiles * fb_rg, 256)), dim3(256), 0, s, fb_rows, batch, fb_tiles, fb_rg,
-                           1, frames, 0, 0, 1, 1, 0, 2, 2);
-        LstmArgs fa{};
-        fa.rows = fb_rows; fa.dense = fptr(w.att); fa.dense_stride = d.FP; fa.md_seq = fbuf.md;
-        fa.seq_out = fptr(w.y1);
-        fa.num_rows = batch; fa.num_tiles = fb_tiles; fa.Tp = d.Tp; fa.LA = 0; fa.FP = d.FP; fa.F = d.F;
-        fa.coop_hx = fptr(w.fb_hx); fa.coop_bar = reinterpret_cast<unsigned*>(base + w.fb_bar); fa.coop_err = h->d_err;
-        fa.coop_abort = reinterpret_cast<unsigned*>(base + w.coop_abort) + 16;
-        fa.coop_units = fb_units; fa.coop_chaos = h->coop_chaos;
-        const int chp = (int)align_up(d.CH, 4);           // row stride of the h1 sequence (a float4 multiple; pad columns written as zeros)
-        fa.seq_stride = chp;
-        if (fbs.kernel == 2) { fa.coop_rows_per_group = fb_rg; launch_lstm_generic(h->fbw, fa, true, s); }
-        else if (fbs.kernel == 1) launch_coop_chained(h->device, s, [&] { launch_lstm_fbv(h->fbw, fa, s); });   // B <= 4: VALU
-        else {
-            const CoopFootprint fp = fb_coop_footprint(pctx(h), h->CH, batch, h->occ_fb[fb_units_index(fb_units)]);
-            launch_coop_chained(h->device, s, [&] { launch_lstm_coop_seq(h->fbw, fa, s); }, h, &fp, h->num_cus_real / kNumXcds, h->coop_chain_stats);
-        }
-        launch_linear_act(fptr(w.y1), chp, h->fsn_wf, h->fsn_kp, h->fsn_bf, fptr(w.fb), d.FP, d.CH, d.F, d.B, d.Tp,
-                          h->cfg.fb_act, h->num_cus, s);
-        launch_subband_stats(d, h->cfg.norm_type, sbuf, rows, num_slots, s);
+// the prologue of both models, one launch: zero the accumulators / exchange images / counters, describe the sub-band rows, and
+// - fsnp_watch_weights - fingerprint the caller's source tensors (a .data edit since the pack flags the handle)
+static int launch_prologue(Forward& f) {
+    fsnp_handle* h = f.h;
+    const bool watch = h->watch_nseg > 0 && (h->watch_calls++ % h->watch_every) == 0;
+    const RowLayout l{h->F, f.d.T, f.mode, f.batch_offset, f.global_batch, 0, h->cfg.num_groups_in_drop_band, h->cfg.output_size};
+    if ((int)f.plan.chunks.size() > kPrologueChunks) {      // (more chunks than the argument block holds: the separate kernels)
+        launch_zero_region(f.base + f.w.zero_begin, f.w.zero_end - f.w.zero_begin, f.s);
+        launch_build_rows(f.plan, f.rows, l, f.s);
+        return watch ? launch_weight_watch(h, f.s, false) : 0;
     }
-    if (h->timing) FSNP_HIP_CHECK(hipEventRecord(rec.e[1], s));
+    launch_prologue_kernel(h, f.plan, f.rows, l, f.base + f.w.zero_begin, f.w.zero_end - f.w.zero_begin, watch, f.s);
+    return 0;
+}
 
-    if (h->sb_tcn) {
-        // sequence_model="TCN": materialise the normalised sub-band input, run the TCN stack over the sub-band sequences
-        // (one "utterance" per sequence: GroupNorm(1, 512) statistics are per sequence), Linear(34, 2), scatter
-        SbGatherArgs ga{};
-        ga.att_mag = fptr(w.att); ga.fb_rel = (int)((w.fb - w.att) / 4); ga.fb_branch_stride = d.B * d.Tp * d.FP;
-        ga.rows = rows; ga.md_utt = sbuf.md_utt; ga.md_row = sbuf.md_row;
-        ga.x = fptr(w.sbt_x0); ga.xstride = h->XS;
-        ga.num_slots = num_slots; ga.Tp = d.Tp; ga.FP = d.FP; ga.F = d.F; ga.NSBN = h->cfg.sb_num_neighbors; ga.NIN = h->NIN;
-        ga.NFBN = h->cfg.fb_num_neighbors;
-        launch_sb_gather(ga, s);
-        Dims ds = d;
-        ds.lens = ds.tpb = nullptr;       // (per-utterance lengths are refused with a sub-band TCN: check_lengths)
-        ds.B = num_slots; ds.F = h->NIN; ds.FP = h->XS;
-        TcnBuffers tb{};
-        tb.att = fptr(w.sbt_x0); tb.x = fptr(w.sbt_x); tb.y1 = fptr(w.sbt_y1); tb.y2 = fptr(w.sbt_y2);
-        tb.gn = reinterpret_cast<double*>(base + w.sbt_gn); tb.fb = fptr(w.sbt_fb);
-        h->sbt.num_cus = h->num_cus;
-        launch_tcn(ds, h->cfg.sb_act, h->sbt, tb, s, 1);
-        launch_sb_scatter(fptr(w.sbt_fb), h->XS, rows, out, (long)rows_per_utt(h, mode) * frames, num_slots, d.Tp, d.LA, h->cfg.output_size, s);
-        if (h->timing) {
-            FSNP_HIP_CHECK(hipEventRecord(rec.e[2], s));
-            FSNP_HIP_CHECK(hipEventRecord(rec.e[3], s));
-        }
-        FSNP_HIP_CHECK(hipGetLastError());
-        h->last_ws = w; h->last_dims = d; h->have_last = true; h->last_base = base;
-        return mark_forward_done(h, s);
+// FullSubNet+: the three attention branches and the full-band TCN stacks
+static void run_fullband_plus(Forward& f, const float* const in[3], const int64_t strides[3][3], bool is_complex) {
+    fsnp_handle* h = f.h;
+    const Workspace& w = f.w;
+    FrontendBuffers fbuf;
+    fbuf.raw = f.fptr(w.raw); fbuf.frame = reinterpret_cast<double*>(f.base + w.frame);
+    fbuf.md = reinterpret_cast<NormMD*>(f.base + w.md); fbuf.fsum = reinterpret_cast<double*>(f.base + w.fsum);
+    fbuf.tot = reinterpret_cast<double*>(f.base + w.fe_tot);
+    fbuf.gate = f.fptr(w.gate); fbuf.att = f.fptr(w.att);
+    TcnBuffers tbuf;
+    tbuf.att = f.fptr(w.att); tbuf.x = f.fptr(w.x); tbuf.y1 = f.fptr(w.y1); tbuf.y2 = f.fptr(w.y2);
+    tbuf.gn = reinterpret_cast<double*>(f.base + w.gn); tbuf.fb = f.fptr(w.fb);
+    tbuf.dbg_tcn0 = h->debug ? f.fptr(w.dbg_tcn0) : nullptr;
+    // the caller's tensors are read by the repack kernel only; everything up to the LSTM then stays in the workspace
+    launch_frontend(f.d, h->cfg.norm_type, in, strides, is_complex, h->fw, fbuf, f.s);
+    launch_tcn(f.d, h->cfg.fb_act, h->tw, tbuf, f.s);
+}
+
+// FullSubNet (fullsubnet.py:82-90): pad, norm(noisy_mag), 2-layer LSTM(F -> CH), Linear(CH, F) + fb_act
+static void run_fullband_fullsubnet(Forward& f, const float* mag, const int64_t strides[3], bool is_complex) {
+    fsnp_handle* h = f.h;
+    const Workspace& w = f.w;
+    const Dims& d = f.d;
+    hipStream_t s = f.s;
+    FrontendBuffers fbuf{};
+    fbuf.raw = f.fptr(w.att); fbuf.frame = reinterpret_cast<double*>(f.base + w.frame);
+    fbuf.md = reinterpret_cast<NormMD*>(f.base + w.md);
+    launch_frontend_mag(d, h->cfg.norm_type, mag, strides, is_complex, fbuf, s);
+    const FbShape fbs = fb_shape(h, d.B);
+    RowDesc* fb_rows = reinterpret_cast<RowDesc*>(f.base + w.fb_rows);
+    launch_build_rows(fb_rows, {d.B, fbs.tiles, fbs.rows_per_tile, 0}, dense_rows(d.T, 2), s);
+    LstmArgs fa{};
+    fa.rows = fb_rows; fa.dense = f.fptr(w.att); fa.dense_stride = d.FP; fa.md_seq = fbuf.md;
+    fa.seq_out = f.fptr(w.y1);
+    fa.num_rows = d.B; fa.num_tiles = fbs.tiles; fa.Tp = d.Tp; fa.LA = 0; fa.FP = d.FP; fa.F = d.F;
+    fa.coop_hx = f.fptr(w.fb_hx); fa.coop_bar = reinterpret_cast<unsigned*>(f.base + w.fb_bar); fa.coop_err = h->d_err;
+    fa.coop_abort = reinterpret_cast<unsigned*>(f.base + w.coop_abort) + 16;
+    fa.coop_units = h->generic_fb ? 0 : fb_coop_units(h, d.B); fa.coop_chaos = h->coop_chaos;
+    const int chp = (int)align_up(d.CH, 4);           // row stride of the h1 sequence (a float4 multiple; pad columns written as zeros)
+    fa.seq_stride = chp;
+    switch (fbs.kernel) {
+    case FbKernel::Generic: fa.coop_rows_per_group = fbs.rows_per_tile; launch_lstm_generic(h->fbw, fa, true, s); break;
+    case FbKernel::Valu: launch_coop_chained(h->device, s, [&] { launch_lstm_fbv(h->fbw, fa, s); }); break;      // B <= 4
+    case FbKernel::KSplitSeq: {
+        const CoopFootprint fp = fb_coop_footprint(pctx(h), h->CH, d.B, h->occ_fb[fb_units_index(fa.coop_units)]);
+        launch_coop_chained(h->device, s, [&] { launch_lstm_coop_seq(h->fbw, fa, s); }, h, &fp, h->num_cus_real / kNumXcds, h->coop_chain_stats);
+        break;
     }
+    }
+    launch_linear_act(f.fptr(w.y1), chp, h->fsn_wf, h->fsn_kp, h->fsn_bf, f.fptr(w.fb), d.FP, d.CH, d.F, d.B, d.Tp, h->cfg.fb_act, h->num_cus, s);
+}
+
+// sequence_model="TCN": materialise the normalised sub-band input, run the TCN stack over the sub-band sequences
+// (one "utterance" per sequence: GroupNorm(1, 512) statistics are per sequence), Linear(34, 2), scatter
+static int run_subband_tcn(Forward& f, float* out) {
+    fsnp_handle* h = f.h;
+    const Workspace& w = f.w;
+    const Dims& d = f.d;
+    const int num_slots = f.plan.total_slots;
+    SbGatherArgs ga{};
+    ga.att_mag = f.fptr(w.att); ga.fb_rel = (int)((w.fb - w.att) / 4); ga.fb_branch_stride = d.B * d.Tp * d.FP;
+    ga.rows = f.rows; ga.md_utt = f.sbuf.md_utt; ga.md_row = f.sbuf.md_row;
+    ga.x = f.fptr(w.sbt_x0); ga.xstride = h->XS;
+    ga.num_slots = num_slots; ga.Tp = d.Tp; ga.FP = d.FP; ga.F = d.F; ga.NSBN = h->cfg.sb_num_neighbors; ga.NIN = h->NIN;
+    ga.NFBN = h->cfg.fb_num_neighbors;
+    launch_sb_gather(ga, f.s);
+    Dims ds = d;
+    ds.lens = ds.tpb = nullptr;       // (per-utterance lengths are refused with a sub-band TCN: check_lengths)
+    ds.B = num_slots; ds.F = h->NIN; ds.FP = h->XS;
+    TcnBuffers tb{};
+    tb.att = f.fptr(w.sbt_x0); tb.x = f.fptr(w.sbt_x); tb.y1 = f.fptr(w.sbt_y1); tb.y2 = f.fptr(w.sbt_y2);
+    tb.gn = reinterpret_cast<double*>(f.base + w.sbt_gn); tb.fb = f.fptr(w.sbt_fb);
+    h->sbt.num_cus = h->num_cus;
+    launch_tcn(ds, h->cfg.sb_act, h->sbt, tb, f.s, 1);
+    launch_sb_scatter(f.fptr(w.sbt_fb), h->XS, f.rows, out, (long)rows_per_utt(h, f.mode) * d.T, num_slots, d.Tp, d.LA, h->cfg.output_size, f.s);
+    if (h->timing) {
+        FSNP_HIP_CHECK(hipEventRecord(f.rec.e[2], f.s));
+        FSNP_HIP_CHECK(hipEventRecord(f.rec.e[3], f.s));
+    }
+    return 0;
+}
+
+// The recurrent sub-band model.  Chunks [0, k) of the plan run on the caller's stream, [k, n) on the side stream behind them:
+// k = n unless the pipelined loop defers the column-split remainder chunks behind a row-tile chunk (after it: next to it they would only
+// fight for its CUs), where they overlap the next forward's full-band stages, or a plan that STARTS with a column-split launch (small
+// batches: k = 0), whose launches leave CUs idle too (B = 1: 216 of 256 busy, latency-bound).  fsnp_set_verify: every Nth forward with a
+// column-split launch is checked against the exchange-free kernel on the caller's stream (nothing deferred then).
+static int dispatch_subband_lstm(Forward& f, float* out, const int32_t* lengths) {
+    fsnp_handle* h = f.h;
+    const Dims& d = f.d;
+    const SbPlan& plan = f.plan;
+    hipStream_t s = f.s, side = h->side_stream;
     LstmArgs a{};
-    a.att_mag = fptr(w.att); a.fb = fptr(w.fb);
-    a.fb_rel = (int)((w.fb - w.att) / 4);
+    a.att_mag = f.fptr(f.w.att); a.fb = f.fptr(f.w.fb);
+    a.fb_rel = (int)((f.w.fb - f.w.att) / 4);
     a.fb_branch_stride = d.B * d.Tp * d.FP;
-    a.rows = rows; a.md_utt = sbuf.md_utt; a.md_row = sbuf.md_row; a.dense = nullptr;
+    a.rows = f.rows; a.md_utt = f.sbuf.md_utt; a.md_row = f.sbuf.md_row; a.dense = nullptr;
     a.out = out;
-    a.out_stride_o = (long)rows_per_utt(h, mode) * frames;
-    a.num_rows = num_rows; a.Tp = d.Tp; a.LA = d.LA; a.FP = d.FP; a.F = d.F; a.NSBN = h->cfg.sb_num_neighbors;
+    a.out_stride_o = (long)rows_per_utt(h, f.mode) * d.T;
+    a.num_rows = d.B * rows_per_utt(h, f.mode); a.Tp = d.Tp; a.LA = d.LA; a.FP = d.FP; a.F = d.F; a.NSBN = h->cfg.sb_num_neighbors;
     a.NFBN = h->cfg.fb_num_neighbors;
     a.act = h->cfg.sb_act;
-    unsigned* bar = reinterpret_cast<unsigned*>(base + w.coop_bar);
-    unsigned* abort_word = reinterpret_cast<unsigned*>(base + w.coop_abort);
-    // pipelined mode: column-split remainder chunks behind a row-tile chunk go to the side stream (after the row-tile
-    // chunk: next to it they would only fight for its CUs), where they overlap the next forward's full-band stages
-    // A plan that STARTS with a column-split launch (small batches) goes to the side stream whole: those launches leave CUs
-    // idle too (B = 1: 216 of 256 busy, latency-bound), and the next forward's full-band stages fit beside them.
-    int ndefer = 0;
-    bool defer_all = false;
-    // fsnp_set_verify: every Nth forward with a column-split launch is checked against the exchange-free kernel (nothing deferred then)
+    float* hx = f.fptr(f.w.coop_hx);
+    unsigned* bar = reinterpret_cast<unsigned*>(f.base + f.w.coop_bar);
+    unsigned* abort_word = reinterpret_cast<unsigned*>(f.base + f.w.coop_abort);
     const bool verify_now = h->verify_every > 0 && plan_has_exchange(plan) && (h->verify_calls++ % h->verify_every) == 0;
     // fsnp_set_verify_sample: every Nth forward of a plan made of column-split launches only, one row tile is recomputed off the critical path
     const bool sample_now = !verify_now && h->vs_every > 0 && plan_can_be_sampled(h, plan) && (h->vs_calls++ % h->vs_every) == 0;
     a.coop_corrupt = h->corrupt_exchange; h->corrupt_exchange = 0;
-    if (verify_now) {
-        launch_sb_lstm(h, plan, a, fptr(w.coop_hx), bar, abort_word, s, h->timing ? rec.e[3] : nullptr);
-        if (h->timing) FSNP_HIP_CHECK(hipEventRecord(rec.e[2], s));
-        const size_t out_elems = (size_t)(mode == FSNP_MODE_PARITY ? global_batch : batch) * h->cfg.output_size * rows_per_utt(h, mode) * frames;
-        if (const int vr = verify_pass(h, plan, d, mode, batch_offset, global_batch, a, sbuf, out_elems, s)) return vr;
-    } else if (h->pipeline) {
-        const int first = plan_first_deferred(h, plan);
-        if (first == 0) defer_all = true;
-        else if (first < (int)plan.chunks.size()) ndefer = first;
+    const int n = (int)plan.chunks.size(), k = verify_now || !h->pipeline ? n : plan_first_deferred(h, plan);
+    hipEvent_t after_first = h->timing ? f.rec.e[3] : nullptr;      // recorded on the stream of chunk 0, behind it
+    if (k > 0) launch_sb_lstm(h, plan, a, hx, bar, abort_word, s, after_first, 0, k);
+    if (k < n) {
+        FSNP_HIP_CHECK(hipEventRecord(h->ev_main, s));
+        FSNP_HIP_CHECK(hipStreamWaitEvent(side, h->ev_main, 0));
+        launch_sb_lstm(h, plan, a, hx, bar, abort_word, side, k == 0 ? after_first : nullptr, k, n);
+    }
+    if (h->timing) FSNP_HIP_CHECK(hipEventRecord(f.rec.e[2], k < n ? side : s));
+    if (k < n) {
+        FSNP_HIP_CHECK(hipEventRecord(h->ev_side[f.slot], side));
+        h->side_used[f.slot] = true;
     }
     if (verify_now) {
-        // (launched above)
-    } else if (defer_all) {
-        FSNP_HIP_CHECK(hipEventRecord(h->ev_main, s));
-        FSNP_HIP_CHECK(hipStreamWaitEvent(h->side_stream, h->ev_main, 0));
-        launch_sb_lstm(h, plan, a, fptr(w.coop_hx), bar, abort_word, h->side_stream, h->timing ? rec.e[3] : nullptr);
-        if (h->timing) FSNP_HIP_CHECK(hipEventRecord(rec.e[2], h->side_stream));
-        FSNP_HIP_CHECK(hipEventRecord(h->ev_side[slot], h->side_stream));
-        h->side_used[slot] = true;
-    } else if (ndefer == 0) {
-        launch_sb_lstm(h, plan, a, fptr(w.coop_hx), bar, abort_word, s, h->timing ? rec.e[3] : nullptr);
-        if (h->timing) FSNP_HIP_CHECK(hipEventRecord(rec.e[2], s));
-    } else {
-        launch_sb_lstm(h, plan, a, fptr(w.coop_hx), bar, abort_word, s, (h->timing && ndefer > 1) ? rec.e[3] : nullptr, 0, ndefer);
-        if (h->timing && ndefer == 1) FSNP_HIP_CHECK(hipEventRecord(rec.e[3], s));      // "after the first chunk"
-        FSNP_HIP_CHECK(hipEventRecord(h->ev_main, s));
-        FSNP_HIP_CHECK(hipStreamWaitEvent(h->side_stream, h->ev_main, 0));
-        launch_sb_lstm(h, plan, a, fptr(w.coop_hx), bar, abort_word, h->side_stream, nullptr, ndefer, -1);
-        if (h->timing) FSNP_HIP_CHECK(hipEventRecord(rec.e[2], h->side_stream));
-        FSNP_HIP_CHECK(hipEventRecord(h->ev_side[slot], h->side_stream));
-        h->side_used[slot] = true;
+        const size_t out_elems = (size_t)(f.mode == FSNP_MODE_PARITY ? f.global_batch : d.B) * h->cfg.output_size * rows_per_utt(h, f.mode) * d.T;
+        if (const int vr = verify_pass(h, plan, d, f.mode, f.batch_offset, f.global_batch, a, f.sbuf, out_elems, s)) return vr;
     }
     if (sample_now) {        // (a plan of column-split launches only runs on ONE stream: the side stream when the pipelined loop defers it, else s)
-        if (const int vr = verify_sample(h, plan, d, a, sbuf, defer_all ? h->side_stream : s)) return vr;
-        if (defer_all) FSNP_HIP_CHECK(hipEventRecord(h->ev_side[slot], h->side_stream));       // the snapshot reads this workspace half too
+        if (const int vr = verify_sample(h, plan, d, a, f.sbuf, k == 0 ? side : s)) return vr;
+        if (k == 0) FSNP_HIP_CHECK(hipEventRecord(h->ev_side[f.slot], side));       // the snapshot reads this workspace half too
     }
     if (lengths) {
         // behind the last sub-band launch that writes the mask (the side stream's, when the pipelined loop deferred any: those follow the
         // caller's stream's chunks), and behind the verification pass / the sampled check's snapshot, which compare what the model wrote
-        const bool on_side = !verify_now && (defer_all || ndefer > 0);
-        hipStream_t ts = on_side ? h->side_stream : s;
-        launch_zero_tails(out, d.lens, batch, h->cfg.output_size * rows_per_utt(h, mode), frames, ts);
-        if (on_side) FSNP_HIP_CHECK(hipEventRecord(h->ev_side[slot], h->side_stream));     // (it reads this workspace half's lengths)
+        launch_zero_tails(out, d.lens, d.B, h->cfg.output_size * rows_per_utt(h, f.mode), d.T, k < n ? side : s);
+        if (k < n) FSNP_HIP_CHECK(hipEventRecord(h->ev_side[f.slot], side));     // (it reads this workspace half's lengths)
     }
+    return 0;
+}
+
+static int finish_forward(Forward& f) {
     FSNP_HIP_CHECK(hipGetLastError());
-    h->last_ws = w; h->last_dims = d; h->have_last = true; h->last_base = base;
-    return mark_forward_done(h, s);
+    f.h->last_ws = f.w; f.h->last_dims = f.d; f.h->have_last = true; f.h->last_base = f.base;
+    return mark_forward_done(f.h, f.s);
+}
+
+static int forward_impl(fsnp_handle* h, const float* mag, const float* real, const float* imag, bool is_complex,
+                        const int64_t strides[3][3], float* out, int32_t batch, int32_t frames,
+                        int32_t mode, int32_t batch_offset, int32_t global_batch, void* hip_stream, const int32_t* lengths = nullptr) {
+    Forward f{};
+    if (const int rc = check_forward_args(h, mag, real, imag, is_complex, strides, out, batch, frames, mode, batch_offset, global_batch,
+                                          lengths, f.d))
+        return rc;
+    FSNP_ON_DEVICE(h);
+    if (calibrate_costs(h)) return 4;            // first planning call of the process for this kind of handle only (~0.1 s)
+    f.h = h; f.s = static_cast<hipStream_t>(hip_stream); f.mode = mode; f.batch_offset = batch_offset; f.global_batch = global_batch;
+    const int num_rows = batch * rows_per_utt(h, mode);
+    f.plan = plan_sb(h, num_rows, forward_gather_bytes(h, batch, frames));
+    if (f.plan.chunks.empty()) {
+        set_error("no kernel plan for %d sub-band sequences on this device (%d CUs): the %s sub-band model needs at least %d",
+                  num_rows, h->num_cus_real, h->gru ? "GRU" : "LSTM", h->H / 128);
+        return 2;
+    }
+    if (const int rc = bind_workspace(f, lengths != nullptr)) return rc;
+    if (lengths) {
+        int* lens = reinterpret_cast<int*>(f.base + f.w.lens);
+        launch_set_lengths(lengths, batch, f.d.LA, lens, lens + batch, f.s);
+        f.d.lens = lens; f.d.tpb = lens + batch;
+    }
+    if (launch_prologue(f)) return 4;
+    if (h->model == FSNP_MODEL_FULLSUBNET) {
+        run_fullband_fullsubnet(f, mag, strides[0], is_complex);
+    } else {
+        const float* in[3] = {mag, real, imag};
+        run_fullband_plus(f, in, strides, is_complex);
+    }
+    launch_subband_stats(f.d, h->cfg.norm_type, f.sbuf, f.rows, f.plan.total_slots, f.s);
+    if (h->timing) FSNP_HIP_CHECK(hipEventRecord(f.rec.e[1], f.s));
+    if (const int rc = h->sb_tcn ? run_subband_tcn(f, out) : dispatch_subband_lstm(f, out, lengths)) return rc;
+    return finish_forward(f);
 }
 
 int fsnp_forward(fsnp_handle* h, const float* mag, const float* real, const float* imag,
@@ -1526,276 +1184,6 @@ int fsnp_fullband_model(fsnp_handle* h, int32_t branch, const float* in, const i
     return 0;
 }
 
-int fsnp_read_stage(fsnp_handle* h, const char* name, float* host_out, int64_t numel) {
-    if (!h || !name || !host_out) { set_error("fsnp_read_stage: null argument"); return 1; }
-    if (!h->have_last) { set_error("fsnp_read_stage: no forward has run"); return 2; }
-    const Dims& d = h->last_dims;
-    const Workspace& w = h->last_ws;
-    const size_t plane = (size_t)d.B * d.Tp * d.FP;       // one branch, padded rows
-    const std::string n = name;
-    const float* src = nullptr;
-    bool is_gate = false;
-    static const char* tags[3] = {"mag", "real", "imag"};
-    for (int b = 0; b < h->NFB; ++b) {
-        if (n == std::string("att_") + tags[b]) src = reinterpret_cast<float*>(h->last_base + w.att) + b * plane;
-        if (n == std::string("fb_") + tags[b]) src = reinterpret_cast<float*>(h->last_base + w.fb) + b * plane;
-        if (h->NFB == 3 && n == std::string("gate_") + tags[b]) { src = reinterpret_cast<float*>(h->last_base + w.gate) + (size_t)b * d.B * d.FP; is_gate = true; }
-    }
-    if (n == "tcn0_mag") {
-        if (!h->debug) { set_error("tcn0_mag needs FSNP_DEBUG_STAGES=1 at fsnp_create time"); return 2; }
-        src = reinterpret_cast<float*>(h->last_base + w.dbg_tcn0);
-    }
-    if (!src) { set_error("unknown stage %s", name); return 2; }
-    const int64_t rows = is_gate ? d.B : (int64_t)d.B * d.Tp;
-    if (numel != rows * d.F) { set_error("stage %s has %lld elements, caller asked %lld", name, (long long)(rows * d.F), (long long)numel); return 2; }
-    FSNP_ON_DEVICE(h);
-    FSNP_HIP_CHECK(hipDeviceSynchronize());
-    FSNP_HIP_CHECK(hipMemcpy2D(host_out, (size_t)d.F * 4, src, (size_t)d.FP * 4, (size_t)d.F * 4, (size_t)rows, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-int fsnp_set_timing(fsnp_handle* h, int32_t enable) {
-    if (!h) { set_error("null handle"); return 1; }
-    h->timing = enable != 0;
-    return 0;
-}
-
-int fsnp_get_timing(fsnp_handle* h, double ms[4], int64_t count[4], int32_t reset) {
-    if (!h || !ms || !count) { set_error("fsnp_get_timing: null argument"); return 1; }
-    FSNP_ON_DEVICE(h);
-    if (drain_timing(h)) return 1;
-    for (int i = 0; i < 4; ++i) { ms[i] = h->acc_ms[i]; count[i] = h->acc_cnt[i]; }
-    if (reset) for (int i = 0; i < 4; ++i) { h->acc_ms[i] = 0; h->acc_cnt[i] = 0; }
-    return 0;
-}
-
-int fsnp_debug_plan_rows(int32_t num_rows, int32_t num_cus, int32_t hidden, int32_t gru, int32_t coop, double composite_gain,
-                         int32_t* out, int32_t max_chunks) {
-    return fsnp_debug_plan_rows2(num_rows, num_cus, hidden, gru, coop, composite_gain, 1, nullptr, out, max_chunks);
-}
-
-// the planner of a handle on a chip of num_cus CUs (host only): fsnp_create's kernels for an LSTM / GRU of 34 sub-band inputs, no switch set;
-// test overrides: never the runtime-sized kernel, a one-tile-per-CU kernel at every size but gru = 1 (round-1 shape; gru = 2: the GRU with one)
-static PlannerCtx host_ctx(int32_t num_cus, int32_t hidden, int32_t gru, int32_t coop, double composite_gain, int32_t workgroups_per_cu,
-                           const double* costs) {
-    PlannerSwitches sw;
-    sw.lstm_coop = coop; sw.coop_occ = workgroups_per_cu >= 2 ? 2 : 1;
-    PlannerCtx h;
-    static_cast<PlannerOptions&>(h) = planner_options(gru ? FSNP_SEQ_GRU : FSNP_SEQ_LSTM, hidden, 34, false, sw);
-    h.rowtile_ok = gru != 1;
-    h.H = hidden; h.NIN = 34; h.num_cus = num_cus; h.num_cus_real = num_cus; h.gru = gru != 0; h.composite_gain = composite_gain;
-    for (int i = 0; i < 4; ++i) h.occ_ksplit[i] = h.coop_occ;
-    for (int i = 0; i < 2; ++i) h.occ_coopn[i] = h.coop_occ;
-    h.cost = default_costs();
-    if (costs) costs_from_array(h.cost, costs);
-    if (gru == 2) h.cost.rowtile *= 0.75;
-    return h;
-}
-
-int fsnp_debug_plan_rows2(int32_t num_rows, int32_t num_cus, int32_t hidden, int32_t gru, int32_t coop, double composite_gain,
-                          int32_t workgroups_per_cu, const double* costs, int32_t* out, int32_t max_chunks) {
-    if (!out || num_rows <= 0 || num_cus <= 0 || hidden < 128 || hidden % 128 != 0 || max_chunks <= 0) { set_error("fsnp_debug_plan_rows: bad argument"); return -1; }
-    const PlannerCtx h = host_ctx(num_cus, hidden, gru, coop, composite_gain, workgroups_per_cu, costs);
-    const SbPlan plan = plan_sb(h, num_rows);
-    int n = 0;
-    for (const SbChunk& c : plan.chunks) {
-        if (n >= max_chunks) break;
-        int32_t* o = out + 8 * n;
-        o[0] = (int)c.kind; o[1] = c.row0; o[2] = c.nrows; o[3] = c.num_tiles; o[4] = c.ex; o[5] = c.kind == SbKind::KSplit || c.kind == SbKind::WaveOwned ? c.units : c.groups;
-        o[6] = c.rpg; o[7] = c.slot0;
-        ++n;
-    }
-    return n;
-}
-
-int fsnp_debug_coop_side_by_side(const int32_t a_per_xcd[8], int32_t a_own_cu, int32_t a_per_cu, const int32_t b_per_xcd[8],
-                                 int32_t b_own_cu, int32_t b_per_cu, int32_t cus_per_xcd) {
-    if (!a_per_xcd || !b_per_xcd) { set_error("fsnp_debug_coop_side_by_side: null argument"); return -1; }
-    CoopFootprint a{}, b{};
-    for (int x = 0; x < kNumXcds; ++x) {
-        if (a_per_xcd[x] < 0 || b_per_xcd[x] < 0) { set_error("fsnp_debug_coop_side_by_side: negative workgroup count"); return -1; }
-        a.per_xcd[x] = a_per_xcd[x]; b.per_xcd[x] = b_per_xcd[x];
-    }
-    a.own_cu = a_own_cu != 0; a.per_cu = a_per_cu; b.own_cu = b_own_cu != 0; b.per_cu = b_per_cu;
-    return coop_side_by_side(a, b, cus_per_xcd) ? 1 : 0;
-}
-
-int fsnp_debug_fullsubnet_pairing(int32_t batch, int32_t num_cus, int32_t fb_workgroups_per_cu, const double* costs, int32_t* out,
-                                  int32_t max_records) {
-    if (!out || batch <= 0 || num_cus <= 0 || max_records <= 0) { set_error("fsnp_debug_fullsubnet_pairing: bad argument"); return -1; }
-    const PlannerCtx c = host_ctx(num_cus, 384, 0, 1, 0.97, 1, costs);       // FullSubNet's sub-band model: LSTM, hidden 384
-    const int per_cu[3] = {fb_workgroups_per_cu, fb_workgroups_per_cu, fb_workgroups_per_cu};
-    return pipeline_pairing(c, true, 257, 512, batch, per_cu, batch <= 4, out, max_records);
-}
-
-int fsnp_debug_pipeline_pairing(const fsnp_handle* h, int32_t batch, int32_t* out, int32_t max_records) {
-    if (!h || !out || batch <= 0 || max_records <= 0) { set_error("fsnp_debug_pipeline_pairing: bad argument"); return -1; }
-    if (!h->committed) { set_error("fsnp_debug_pipeline_pairing: weights not committed (the decision depends on the kernels' occupancy)"); return -1; }
-    if (h->model != FSNP_MODEL_FULLSUBNET || h->generic_fb || h->sb_tcn) return 0;      // no column-split launch on the caller's stream
-    const bool valu = h->fb_valu && lstm_fbv_available(h->fbw, batch, h->num_cus_real);
-    return pipeline_pairing(pctx(h), h->defer_small != 0, h->F, h->CH, batch, h->occ_fb, valu, out, max_records);
-}
-
-int fsnp_debug_fullband_launch(const fsnp_handle* h, int32_t batch, int32_t out[4]) {
-    if (!h || !out || batch <= 0) { set_error("fsnp_debug_fullband_launch: bad argument"); return 1; }
-    if (h->model != FSNP_MODEL_FULLSUBNET) { set_error("fsnp_debug_fullband_launch: FullSubNet+ has no full-band LSTM"); return 2; }
-    const FbShape f = fb_shape(h, batch);
-    out[0] = f.kernel; out[1] = f.tiles; out[2] = f.rows_per_tile; out[3] = f.units;
-    return 0;
-}
-
-int fsnp_debug_coop_chain_stats(fsnp_handle* h, int64_t out[2], int32_t reset) {
-    if (!h || !out) { set_error("fsnp_debug_coop_chain_stats: null argument"); return 1; }
-    std::lock_guard<std::mutex> lk(g_coop_mu);
-    out[0] = h->coop_chain_stats[0]; out[1] = h->coop_chain_stats[1];
-    if (reset) h->coop_chain_stats[0] = h->coop_chain_stats[1] = 0;
-    return 0;
-}
-
-int fsnp_get_costs(const fsnp_handle* h, double out[FSNP_NUM_COSTS], int32_t* calibrated, int32_t* occ) {
-    if (!h || !out) { set_error("fsnp_get_costs: null argument"); return 1; }
-    static_assert(kNumCosts == FSNP_NUM_COSTS, "planner.h and fsnp.h agree on the flat table");
-    costs_to_array(h->planner.cost, out);
-    if (calibrated) *calibrated = h->planner.cost.calibrated;
-    if (occ) *occ = h->planner.coop_occ;
-    return 0;
-}
-
-int fsnp_measure_costs(fsnp_handle* h, double out[FSNP_NUM_COSTS]) {
-    if (!h || !out) { set_error("fsnp_measure_costs: null argument"); return 1; }
-    if (!h->committed) { set_error("fsnp_measure_costs: weights not committed"); return 2; }
-    if (h->sb_tcn) { set_error("fsnp_measure_costs: the sub-band model of this handle is a TCN (no recurrent kernels)"); return 2; }
-    FSNP_ON_DEVICE(h);
-    CostTable t = h->planner.cost;
-    if (calibrate_costs(h, false, &t)) return 4;
-    costs_to_array(t, out);
-    return 0;
-}
-
-int fsnp_debug_set_costs(fsnp_handle* h, const double* costs, int32_t workgroups_per_cu) {
-    if (!h || (workgroups_per_cu != 1 && workgroups_per_cu != 2)) { set_error("fsnp_debug_set_costs: bad argument"); return 1; }
-    if (!h->committed) { set_error("fsnp_debug_set_costs: commit the weights first (the kernels' occupancy is checked then)"); return 2; }
-    h->planner.cost = initial_costs(h->H, h->gru != 0, h->sb_tcn != 0);
-    if (costs) costs_from_array(h->planner.cost, costs);
-    h->planner.cost.calibrated = 1;          // pinned: the lazy calibration will not replace it
-    h->planner.coop_occ = workgroups_per_cu;
-    return 0;
-}
-
-int fsnp_describe_plan(const fsnp_handle* h, int32_t batch, int32_t mode, int32_t* out, int32_t max_chunks) {
-    if (!h || !out || batch <= 0 || max_chunks <= 0) { set_error("fsnp_describe_plan: bad argument"); return -1; }
-    const SbPlan plan = plan_sb(h, batch * rows_per_utt(h, mode));
-    int n = 0;
-    for (const SbChunk& c : plan.chunks) {
-        if (n >= max_chunks) break;
-        out[4 * n + 0] = describe_code(c.kind, h->sb_tcn != 0, h->lw.hp_wave && lstm_hpw_available(h->lw));
-        out[4 * n + 1] = c.nrows; out[4 * n + 2] = c.num_tiles; out[4 * n + 3] = c.ex;
-        ++n;
-    }
-    return n;
-}
-
-int fsnp_describe_plan_ex(const fsnp_handle* h, int32_t batch, int32_t mode, int32_t* out, int32_t max_chunks) {
-    if (!h || !out || batch <= 0 || max_chunks <= 0) { set_error("fsnp_describe_plan_ex: bad argument"); return -1; }
-    int32_t base[4 * 64];
-    const int n = fsnp_describe_plan(h, batch, mode, base, max_chunks < 64 ? max_chunks : 64);
-    if (n < 0) return n;
-    const SbPlan plan = plan_sb(h, batch * rows_per_utt(h, mode));
-    const int first_deferred = plan_first_deferred(h, plan);
-    for (int i = 0; i < n; ++i) {
-        const SbChunk& c = plan.chunks[i];
-        for (int k = 0; k < 4; ++k) out[7 * i + k] = base[4 * i + k];
-        // arithmetic of THIS chunk: the bf16 variants exist for the one-tile-per-CU LSTM kernel only (lstm.hip) and the half-tile kernel (lstm16.hip);
-        // sequences that the plan hands to any other kernel run in fp32 whatever fsnp_set_precision says
-        int prec = 0;
-        if (!h->sb_tcn && !h->gru && c.kind == SbKind::RowTile) prec = h->ih_bf16 == 1 ? 1 : 0;
-        if (!h->sb_tcn && !h->gru && c.kind == SbKind::HalfTile && h->ih_bf16 == 1 && h->lw.wpack16_bf) prec = 1;       // half-tile kernel: bf16 ih-GEMM too (round 4)
-        out[7 * i + 4] = prec;
-        out[7 * i + 5] = h->sb_tcn ? 0 : chunk_workgroups(h, c);
-        out[7 * i + 6] = i >= first_deferred ? 1 : 0;        // the pipelined loop runs this launch on the side stream
-    }
-    return n;
-}
-
-int fsnp_debug_lstm_profile(fsnp_handle* h, const float* x, float* out, int32_t num_seq, int32_t steps,
-                            uint64_t* host_stamps, int64_t num_stamps) {
-    if (!h || !x || !out || !host_stamps) { set_error("fsnp_debug_lstm_profile: null argument"); return 1; }
-    if (!h->committed) { set_error("fsnp_debug_lstm_profile: weights not committed"); return 2; }
-    if (num_stamps != (int64_t)steps * 8) { set_error("fsnp_debug_lstm_profile: need steps*8 stamps"); return 2; }
-    if (h->gru || h->sb_tcn || h->H != 384) { set_error("fsnp_debug_lstm_profile: row-tile kernel only (LSTM, hidden 384)"); return 2; }
-    FSNP_ON_DEVICE(h);
-    const LstmPlan lp = plan_lstm_tiles(num_seq, h->num_cus);
-    const int num_slots = lp.num_tiles * lp.rows_per_slot_tile;
-    const size_t stamp_off = align_up((size_t)num_slots * sizeof(RowDesc), 256);
-    if (ensure_workspace(h, stamp_off + ((size_t)num_stamps + (size_t)lp.num_tiles * 256) * 8, nullptr)) return 4;
-    FSNP_HIP_CHECK(hipDeviceSynchronize());
-    RowDesc* rows = reinterpret_cast<RowDesc*>(h->ws);
-    unsigned long long* dprof = reinterpret_cast<unsigned long long*>(h->ws + stamp_off);
-    h->have_last = false;
-    hipLaunchKernelGGL(build_rows_kernel, dim3(cdiv(num_slots, 256)), dim3(256), 0, 0, rows, num_seq, lp.num_tiles,
-                       lp.rows_per_slot_tile, 1, steps, 0, 0, 1, 1, 0, 2, 2);
-    LstmArgs a{};
-    a.rows = rows; a.dense = x; a.out = out; a.out_stride_o = steps;
-    a.num_rows = num_seq; a.num_tiles = lp.num_tiles; a.ex = lp.ex; a.Tp = steps; a.LA = 0; a.F = 1;
-    a.act = h->cfg.sb_act; a.prof = dprof;
-    launch_lstm(h->lw, a, 0);
-    FSNP_HIP_CHECK(hipDeviceSynchronize());
-    FSNP_HIP_CHECK(hipMemcpy(host_stamps, dprof, (size_t)num_stamps * 8, hipMemcpyDeviceToHost));
-    return 0;
-}
-
-int fsnp_debug_pp_profile(fsnp_handle* h, const float* x, float* out, int32_t num_seq, int32_t steps, int32_t tiles_per_group,
-                          uint64_t* host_stamps, int64_t num_stamps) {
-    if (!h || !x || !out || !host_stamps) { set_error("fsnp_debug_pp_profile: null argument"); return 1; }
-    if (!h->committed || (!h->planner.hp_ok && tiles_per_group == 0)) { set_error("fsnp_debug_pp_profile: no half-tile ping-pong kernel for this handle"); return 2; }
-    // tiles_per_group: 0 = the half-tile ping-pong kernel (lstm_hp.hip: 2 halves x 16 stamps per step); 32 / 64 = the wave-owned column
-    // split (lstm_coopw.hip) at that many units per workgroup (16 stamps per step: 8 per layer phase)
-    const bool hp = tiles_per_group == 0, cw = tiles_per_group == 32 || tiles_per_group == 64 || tiles_per_group == 96;
-    if ((!hp && !cw) || num_stamps != (int64_t)steps * (hp ? 32 : 16)) { set_error("fsnp_debug_pp_profile: tiles_per_group must be 0 (half-tile ping-pong kernel, steps * 32 stamps) or 32 / 64 (wave-owned column split, steps * 16 stamps)"); return 2; }
-    if (cw && !h->planner.coopw_ok) { set_error("fsnp_debug_pp_profile: no wave-owned column split for this handle"); return 2; }
-    const int tiles = cdiv(num_seq, 32), groups = tiles, S = hp ? h->H / 16 : h->H / tiles_per_group;
-    if (num_seq <= 0 || groups * S > h->num_cus_real) { set_error("fsnp_debug_pp_profile: the launch must fit the chip"); return 2; }
-    FSNP_ON_DEVICE(h);
-    SbPlan plan;
-    plan.chunks = {hp ? column_chunk(SbKind::HalfTilePingPong, 0, num_seq, tiles, 16, 0) : column_chunk(SbKind::WaveOwned, 0, num_seq, tiles, tiles_per_group, 0)};
-    plan.total_slots = tiles * 32; plan.coop_tiles = tiles;
-    const size_t rows_b = align_up((size_t)plan.total_slots * sizeof(RowDesc), 256), hx_b = align_up(lstm_coop_exchange_bytes(h->H, tiles), 256);
-    const size_t bar_b = align_up(coop_counter_bytes(tiles), 256), st_b = (size_t)num_stamps * 8;
-    if (order_after_last_forward(h, nullptr)) return 4;
-    if (ensure_workspace(h, rows_b + hx_b + bar_b + 256 + st_b, nullptr)) return 4;
-    FSNP_HIP_CHECK(hipDeviceSynchronize());
-    h->have_last = false;
-    RowDesc* rows = reinterpret_cast<RowDesc*>(h->ws);
-    FSNP_HIP_CHECK(hipMemsetAsync(h->ws + rows_b, 0, hx_b + bar_b + 256 + st_b, nullptr));
-    launch_build_rows(plan, rows, 1, steps, 0, 0, 1, 1, 2, h->cfg.output_size, nullptr);
-    LstmArgs a{};
-    a.rows = rows; a.dense = x; a.dense_stride = h->NIN; a.out = out; a.out_stride_o = steps;
-    a.num_rows = num_seq; a.Tp = steps; a.LA = 0; a.FP = 0; a.F = 1; a.NSBN = 0; a.act = h->cfg.sb_act;
-    a.prof = reinterpret_cast<unsigned long long*>(h->ws + rows_b + hx_b + bar_b + 256);
-    launch_sb_lstm(h, plan, a, reinterpret_cast<float*>(h->ws + rows_b), reinterpret_cast<unsigned*>(h->ws + rows_b + hx_b),
-                   reinterpret_cast<unsigned*>(h->ws + rows_b + hx_b + bar_b), nullptr);
-    FSNP_HIP_CHECK(hipDeviceSynchronize());
-    FSNP_HIP_CHECK(hipMemcpy(host_stamps, a.prof, st_b, hipMemcpyDeviceToHost));
-    return fsnp_check_errors(h);
-}
-
-int fsnp_debug_launch_clock(fsnp_handle* h, double out[FSNP_LAUNCH_CLOCK_VALUES]) {
-    if (!h || !out) { set_error("fsnp_debug_launch_clock: null argument"); return 1; }
-    unsigned long long c[8] = {};
-    if (!h->d_clk) { set_error("fsnp_debug_launch_clock: no completed launch of the one-tile-per-CU LSTM kernel on this handle"); return 2; }
-    FSNP_ON_DEVICE(h);
-    FSNP_HIP_CHECK(hipMemcpy(c, h->d_clk, sizeof(c), hipMemcpyDeviceToHost));
-    const unsigned long long t0 = c[0], r0 = c[1], t1 = c[2], r1 = c[3];
-    if (r0 == 0 || r1 <= r0 || t1 <= t0) { set_error("fsnp_debug_launch_clock: no completed launch of the one-tile-per-CU LSTM kernel on this handle"); return 2; }
-    out[0] = (double)(t1 - t0); out[1] = (double)(r1 - r0);
-    out[2] = (double)(r1 - r0) * 1e-5;                          // 100 MHz ticks -> ms
-    out[3] = (double)(t1 - t0) / (double)(r1 - r0) * 100.0;     // s_memtime ticks per microsecond
-    out[4] = (double)c[4] * 1e-5;                               // the slowest workgroup of the launch, ms
-    out[5] = c[6] == ~0ull ? 0.0 : (double)c[6] * 1e-5;         // the fastest
-    out[6] = (double)c[5];                                      // the largest s_memtime tick count of a workgroup
-    return 0;
-}
-
 int fsnp_set_precision(fsnp_handle* h, int32_t ih_bf16) {
     if (!h || ih_bf16 < 0 || ih_bf16 > 1) { set_error("fsnp_set_precision: 0 (fp32) or 1 (bf16 ih-GEMM, BASELINE.json configs[4])"); return 1; }
     if (ih_bf16 && (h->gru || h->sb_tcn)) { set_error("fsnp_set_precision: the bf16 ih-GEMM variant exists for the LSTM sub-band model only"); return 2; }
@@ -1810,38 +1198,6 @@ int fsnp_poll_errors(fsnp_handle* h) {
     if (!h) { set_error("null handle"); return 1; }
     return take_device_errors(h, "fsnp_poll_errors");
 }
-
-int fsnp_set_verify(fsnp_handle* h, int32_t every) {
-    if (!h || every < 0) { set_error("fsnp_set_verify: every must be >= 0 (0 = off)"); return 1; }
-    if (every > 0 && (!h->planner.rowtile_ok || h->sb_tcn || h->generic_sb)) {
-        set_error("fsnp_set_verify: this model has no exchange-free (one-tile-per-CU) kernel to verify against");
-        return 2;
-    }
-    h->verify_every = every; h->verify_calls = 0;
-    return 0;
-}
-
-int fsnp_set_verify_sample(fsnp_handle* h, int32_t every) {
-    if (!h || every < 0) { set_error("fsnp_set_verify_sample: every must be >= 0 (0 = off)"); return 1; }
-    if (every == h->vs_every) return 0;            // (idempotent: a binding may state its setting in front of every forward)
-    h->vs_every = every; h->vs_calls = 0;
-    return 0;
-}
-
-int64_t fsnp_verify_count(const fsnp_handle* h) { return h ? (int64_t)h->verify_runs : -1; }
-
-int fsnp_debug_verify_sample_stats(const fsnp_handle* h, int64_t out[3]) {
-    if (!h || !out) { set_error("fsnp_debug_verify_sample_stats: null argument"); return 1; }
-    out[0] = h->vs_runs; out[1] = h->vs_skipped; out[2] = h->vs_calls;
-    return 0;
-}
-
-int fsnp_debug_corrupt_exchange(fsnp_handle* h, int32_t step) {
-    if (!h || step < 0) { set_error("fsnp_debug_corrupt_exchange: step must be >= 0 (0 = off)"); return 1; }
-    h->corrupt_exchange = step;
-    return 0;
-}
-
 int fsnp_set_pipeline(fsnp_handle* h, int32_t enable) {
     if (!h || (enable != 0 && enable != 1)) { set_error("fsnp_set_pipeline: 0 or 1"); return 1; }
     if (enable == h->pipeline) return 0;
@@ -1924,125 +1280,6 @@ int64_t fsnp_dump_config(const fsnp_handle* h, char* buf, int64_t cap) {
         buf[n] = 0;
     }
     return (int64_t)o.size() + 1;
-}
-
-int fsnp_debug_inject_error(fsnp_handle* h) {
-    if (!h) { set_error("null handle"); return 1; }
-    *reinterpret_cast<volatile unsigned*>(h->d_err) |= kErrTimeout;
-    return 0;
-}
-
-int fsnp_debug_set_chaos(fsnp_handle* h, int32_t seed) {
-    if (!h) { set_error("null handle"); return 1; }
-    h->coop_chaos = seed;
-    return 0;
-}
-
-int fsnp_debug_set_gemm_dma(fsnp_handle* h, int32_t mode) {
-    if (!h || mode < 0 || mode > 3) { set_error("fsnp_debug_set_gemm_dma: mode must be 0 (general GEMM kernel), 1 (DMA kernels where they apply), 2 (as 1, never the small-batch split-K kernel) or 3 (the 128-row DMA kernel only)"); return 1; }
-    h->tw.gemm_dma = mode;
-    return 0;
-}
-
-int fsnp_debug_set_lstm_coop(fsnp_handle* h, int32_t mode) {
-    if (!h || mode < 0 || mode > 4 || mode == 3) { set_error("fsnp_debug_set_lstm_coop: mode must be 0 (off), 1 (auto), 2 (auto, serial K-split schedule, no half-tile ping-pong kernel) or 4 (auto + the half-tile ping-pong kernel even where FSNP_COOP_HP=0)"); return 1; }
-    h->planner.lstm_coop = mode != 0;
-    h->coop_skew = mode != 2;
-    h->planner.coop_hp = mode == 4 ? 1 : mode == 1 ? h->coop_hp_cfg : 0;
-    h->fb_valu = mode == 1 || mode == 4;   // (FullSubNet: modes 0 and 2 keep the full-band LSTM on the K-split kernel, whatever the batch - mode 0 is
-                                           // what the sync error policy retries with after a time-out, so it must not come back to the same exchange)
-    h->planner.cost.calibrated = h->calibrate ? 0 : h->planner.cost.calibrated;    // the K-split costs depend on the schedule: measure again
-    if (!h->planner.cost.calibrated) h->planner.cost = initial_costs(h->H, h->gru != 0, h->sb_tcn != 0);
-    return 0;
-}
-
-int fsnp_debug_set_lstm_waves(fsnp_handle* h, int32_t waves) {
-    if (!h || (waves != 0 && waves != 4 && waves != 12)) { set_error("fsnp_debug_set_lstm_waves: waves must be 0 (auto), 4 or 12"); return 1; }
-    h->lstm_waves = waves;
-    h->lw.waves = waves;
-    return 0;
-}
-
-int fsnp_debug_set_num_cus(fsnp_handle* h, int32_t num_cus) {
-    if (!h || num_cus <= 0) { set_error("fsnp_debug_set_num_cus: bad argument"); return 1; }
-    h->num_cus = num_cus;
-    h->tw.num_cus = num_cus;
-    return 0;
-}
-
-int fsnp_debug_lstm_pack(int32_t hidden, int32_t input_size, int32_t kx, int32_t waves, const float* wih0, const float* whh0,
-                         const float* wih1, const float* whh1, float* out, int64_t out_floats) {
-    if (!wih0 || !whh0 || !wih1 || !whh1 || !out) { set_error("fsnp_debug_lstm_pack: null argument"); return 1; }
-    if (waves <= 0 || hidden % (32 * waves) != 0 || kx % 8 != 0 || input_size > kx) { set_error("fsnp_debug_lstm_pack: bad sizes"); return 2; }
-    if ((int64_t)lstm_pack_floats(hidden, kx, waves) != out_floats) {
-        set_error("fsnp_debug_lstm_pack: need %lld floats", (long long)lstm_pack_floats(hidden, kx, waves));
-        return 2;
-    }
-    lstm_pack_weights(hidden, input_size, kx, waves, wih0, whh0, wih1, whh1, out);
-    return 0;
-}
-
-int fsnp_debug_lstm_coop_pack(int32_t hidden, int32_t input_size, int32_t kx, int32_t units, const float* wih0, const float* whh0,
-                              const float* wih1, const float* whh1, float* out, int64_t out_floats) {
-    if (!wih0 || !whh0 || !wih1 || !whh1 || !out) { set_error("fsnp_debug_lstm_coop_pack: null argument"); return 1; }
-    if ((units != 8 && units != 16 && units != 32 && units != 64) || hidden % 64 != 0 || kx % 8 != 0 || input_size > kx) {
-        set_error("fsnp_debug_lstm_coop_pack: bad sizes");
-        return 2;
-    }
-    if ((int64_t)lstm_coop_pack_floats(hidden, kx, units) != out_floats) {
-        set_error("fsnp_debug_lstm_coop_pack: need %lld floats", (long long)lstm_coop_pack_floats(hidden, kx, units));
-        return 2;
-    }
-    lstm_coop_pack_weights(hidden, input_size, kx, units, wih0, whh0, wih1, whh1, out);
-    return 0;
-}
-
-int fsnp_debug_lstm_hpw_pack(int32_t hidden, int32_t input_size, int32_t kx, const float* wih0, const float* whh0, const float* wih1,
-                             const float* whh1, float* out, int64_t out_floats) {
-    if (!wih0 || !whh0 || !wih1 || !whh1 || !out) { set_error("fsnp_debug_lstm_hpw_pack: null argument"); return 1; }
-    if (hidden % 16 != 0 || kx % 4 != 0 || kx > 64 || input_size > kx) { set_error("fsnp_debug_lstm_hpw_pack: bad sizes"); return 2; }
-    if (out_floats != (int64_t)lstm_hpw_pack_floats(hidden, kx)) {
-        set_error("fsnp_debug_lstm_hpw_pack: need %lld floats", (long long)lstm_hpw_pack_floats(hidden, kx));
-        return 2;
-    }
-    lstm_hpw_pack_weights(hidden, input_size, kx, wih0, whh0, wih1, whh1, out);
-    return 0;
-}
-
-int fsnp_debug_lstm_coopw_pack(int32_t hidden, int32_t input_size, int32_t kx, const float* wih0, const float* whh0, const float* wih1,
-                               const float* whh1, float* out, int64_t out_floats) {
-    if (!wih0 || !whh0 || !wih1 || !whh1 || !out) { set_error("fsnp_debug_lstm_coopw_pack: null argument"); return 1; }
-    if (hidden % 32 != 0 || kx % 8 != 0 || input_size > kx) { set_error("fsnp_debug_lstm_coopw_pack: bad sizes"); return 2; }
-    if ((int64_t)lstm_coopw_pack_floats(hidden, kx) != out_floats) {
-        set_error("fsnp_debug_lstm_coopw_pack: need %lld floats", (long long)lstm_coopw_pack_floats(hidden, kx));
-        return 2;
-    }
-    lstm_coopw_pack_weights(hidden, input_size, kx, wih0, whh0, wih1, whh1, out);
-    return 0;
-}
-
-int fsnp_debug_lstm_fbv_pack(int32_t hidden, int32_t input_size, const float* wih0, const float* whh0, const float* wih1, const float* whh1,
-                             float* out, int64_t out_floats) {
-    if (!wih0 || !whh0 || !wih1 || !whh1 || !out) { set_error("fsnp_debug_lstm_fbv_pack: null argument"); return 1; }
-    if (hidden != 512 || input_size < 1 || input_size > 288) { set_error("fsnp_debug_lstm_fbv_pack: hidden 512, <= 288 inputs"); return 2; }
-    if ((int64_t)lstm_fbv_pack_floats(hidden) != out_floats) {
-        set_error("fsnp_debug_lstm_fbv_pack: need %lld floats", (long long)lstm_fbv_pack_floats(hidden));
-        return 2;
-    }
-    lstm_fbv_pack_weights(hidden, input_size, wih0, whh0, wih1, whh1, out);
-    return 0;
-}
-
-double fsnp_lstm_flops(const fsnp_handle* h, int64_t num_seq, int32_t steps) {
-    if (!h) return 0;
-    return (double)num_seq * steps * lstm_flops_per_step(h);
-}
-
-double fsnp_forward_flops(const fsnp_handle* h, int32_t batch, int32_t frames, int32_t mode) {
-    if (!h) return 0;
-    const double Tp = frames + h->cfg.look_ahead;
-    const double full_band = h->model == FSNP_MODEL_FULLSUBNET ? fb_lstm_flops_per_frame(h) : 3.0 * tcn_flops_per_frame(h);
-    return batch * Tp * (rows_per_utt(h, mode) * lstm_flops_per_step(h) + full_band);
 }
 
 }  // extern "C"

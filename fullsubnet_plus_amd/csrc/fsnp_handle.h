@@ -1,6 +1,7 @@
 // fsnp_handle.h - the handle behind the C ABI (include/fsnp.h) and the helpers its translation units share:
-// fsnp_abi.hip (create / forward orchestration / workspace / tuning hooks), fsnp_weights.hip (strict weight loading + packing),
-// fsnp_stft_abi.hip (STFT / iSTFT / waveform entry points).  Host code only.
+// fsnp_abi.hip (create / forward orchestration / workspace / calibration), forward_kernels.hip (the forward's small kernels),
+// fsnp_verify.hip (exchange verification), fsnp_debug_abi.hip (include/fsnp_debug.h: test and tuning hooks), fsnp_weights.hip
+// (strict weight loading + packing), fsnp_stft_abi.hip (STFT / iSTFT / waveform entry points).  Host declarations only.
 #pragma once
 #include <map>
 #include <string>
@@ -44,7 +45,7 @@ struct DeviceGuard {
 
 }  // namespace fsnp
 
-using namespace fsnp;      // (internal header of three host translation units)
+using namespace fsnp;      // (internal header of the host translation units)
 
 struct fsnp_handle {
     fsnp_config cfg{};
@@ -158,7 +159,7 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 // bits of the host-mapped error word (fsnp_handle::d_err[0])
 constexpr unsigned kErrTimeout = 1u, kErrStaleWeights = 2u, kErrVerify = 4u;
 // fsnp_weights.hip: fingerprint of the watched source tensors on stream s (no-op without a watch); the device function is shared with
-// the forward's prologue kernel (fsnp_abi.hip), which runs the same blocks beside its zeroing / row-descriptor blocks
+// the forward's prologue kernel (forward_kernels.hip), which runs the same blocks beside its zeroing / row-descriptor blocks
 int launch_weight_watch(fsnp_handle* h, hipStream_t s, bool baseline);
 struct WatchSeg { const unsigned* p; unsigned n; unsigned long long first; };      // (device function: weight_watch.h)
 constexpr int kWatchSeg = 8192;              // elements per segment of the watched tensors (8 uint4 loads per thread of a 256-thread block)
@@ -174,6 +175,48 @@ int mark_forward_done(fsnp_handle* h, hipStream_t s);
 // clips of different lengths: 0 when lengths[0 .. batch) (host, frames per utterance) is acceptable for a forward of `frames` frames on
 // this handle, else 2 with the error set (naming the utterance).  Nothing is launched.
 int check_lengths(const fsnp_handle* h, const int32_t* lengths, int batch, int frames, const char* where);
+// fsnp_abi.hip: workspace (grown stream-ordered on s), timing records, the planner's view of a handle and its calibration
+int ensure_workspace(fsnp_handle* h, size_t bytes, hipStream_t s);
+int drain_timing(fsnp_handle* h);
+PlannerCtx pctx(const fsnp_handle* h);
+int rows_per_utt(const fsnp_handle* h, int mode);
+SbPlan plan_sb(const fsnp_handle* h, int num_rows, double gather_bytes = 0.0);     // gather_bytes: the furthest byte a launch reads
+int chunk_workgroups(const fsnp_handle* h, const SbChunk& c);
+int plan_first_deferred(const fsnp_handle* h, const SbPlan& plan);     // pipelined loop: first chunk on the side stream
+int calibrate_costs(fsnp_handle* h, bool adopt = true, CostTable* measured = nullptr);
+// the sub-band launches of chunks [first_chunk, last_chunk) on s (-1: to the end; after_first: recorded behind the range's first chunk),
+// and the count of this handle's column-split launches that ran beside [0] / were chained behind [1] one of its own on another stream
+void launch_sb_lstm(const fsnp_handle* h, const SbPlan& plan, const LstmArgs& a, float* hx, unsigned* bar, unsigned* abort_word,
+                    hipStream_t s, hipEvent_t after_first = nullptr, int first_chunk = 0, int last_chunk = -1);
+void take_coop_chain_stats(fsnp_handle* h, int64_t out[2], bool reset);
+constexpr int kOwnCuLds = 160 * 1024 - 256;     // LDS a column-split launch claims to keep its CUs to itself (LstmArgs::coop_own_cu)
+// the full-band LSTM launch of a FullSubNet forward (fsnp_debug_fullband_launch reports the kernel's number), and the side-by-side
+// decision of the pipelined FullSubNet loop (fsnp_debug_pipeline_pairing)
+enum class FbKernel { KSplitSeq = 0, Valu = 1, Generic = 2 };     // lstm_coop_seq, lstm_fbv, lstm_generic
+struct FbShape { FbKernel kernel; int tiles, rows_per_tile, units; };
+FbShape fb_shape(const fsnp_handle* h, int batch);
+int pipeline_pairing(const PlannerCtx& c, bool defer_small, int F, int CH, int batch, const int fb_per_cu[3], bool fb_valu,
+                     int32_t* out, int max_records);
+// forward_kernels.hip: row descriptors of rows [row0, row0 + num_rows) on num_tiles tiles of rows_per_tile slots, for the forward's
+// mask (F bins, mode, drop_band groups) or a dense [n][OC][T] output; the forward's prologue (one launch for up to kPrologueChunks
+// chunks, else zero_region + build_rows + launch_weight_watch); per-utterance lengths and the zeroed mask tails past them
+struct RowTiles { int num_rows, num_tiles, rows_per_tile, row0; };
+struct RowLayout { int F, T, mode, batch_offset, global_batch, dense_out, groups, OC; };
+inline RowLayout dense_rows(int T, int OC) { return {1, T, 0, 0, 1, 1, 2, OC}; }
+void launch_build_rows(RowDesc* rows, const RowTiles& t, const RowLayout& l, hipStream_t s);
+void launch_build_rows(const SbPlan& plan, RowDesc* rows, const RowLayout& l, hipStream_t s);     // every chunk of the plan
+void launch_zero_region(void* p, size_t bytes, hipStream_t s);
+constexpr int kPrologueChunks = 8;
+void launch_prologue_kernel(const fsnp_handle* h, const SbPlan& plan, RowDesc* rows, const RowLayout& l, void* zero, size_t zero_bytes,
+                            bool watch, hipStream_t s);
+void launch_set_lengths(const int32_t* lengths, int B, int LA, int* lens, int* tpb, hipStream_t s);
+void launch_zero_tails(float* out, const int* lens, int B, int rows_per_utt, int T, hipStream_t s);
+// fsnp_verify.hip: fsnp_set_verify (verify_pass, on the forward's stream behind its launches) and fsnp_set_verify_sample
+bool plan_has_exchange(const SbPlan& plan);
+int verify_pass(fsnp_handle* h, const SbPlan& plan, const Dims& d, int mode, int batch_offset, int global_batch, const LstmArgs& a,
+                const SubbandBuffers& sbuf, size_t out_elems, hipStream_t s);
+bool plan_can_be_sampled(const fsnp_handle* h, const SbPlan& plan);
+int verify_sample(fsnp_handle* h, const SbPlan& plan, const Dims& d, const LstmArgs& a, const SubbandBuffers& sbuf, hipStream_t st);
 // fsnp_stft_abi.hip
 struct StftPlan {
     int n_fft, hop, F, N2, sp;          // sp = padded float stride of one internal spectrum row (multiple of 4)

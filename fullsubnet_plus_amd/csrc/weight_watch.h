@@ -1,4 +1,4 @@
-// weight_watch.h - device side of fsnp_watch_weights (fsnp_weights.hip), shared with the forward's prologue kernel (fsnp_abi.hip).
+// weight_watch.h - device side of fsnp_watch_weights (fsnp_weights.hip), shared with the forward's prologue kernel (forward_kernels.hip).
 // A 64-bit fingerprint of the caller's source tensors: sum over all elements of bits(x_i) * (2 i + 1) mod 2^64 (i = position in the
 // concatenation): any single changed element changes it, the sum is order-independent (integer adds), so blocks accumulate with one
 // atomic each and the LAST block to finish compares with the baseline taken at registration.
@@ -7,7 +7,7 @@
 
 namespace fsnp {
 
-// (256 threads per block; `block` of `nblocks` - the blocks may be part of a larger launch: fsnp_abi.hip prologue_kernel)
+// (256 threads per block; `block` of `nblocks` - the blocks may be part of a larger launch: forward_kernels.hip prologue_kernel)
 __device__ __forceinline__ void weight_watch_block(const WatchSeg* __restrict__ segs, int nseg, unsigned long long* acc, int baseline, unsigned* err_host,
                                    int block, int nblocks) {
     // (segments are <= kWatchSeg = 8192 elements)
