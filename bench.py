@@ -13,11 +13,15 @@ Inputs (the STFT of seeded noise, exactly the tensors the reference inferencer h
 inferencer.py:142-147) are resident in HBM before the timed region; the STFT itself is outside it
 on both sides.
 
-Rank 0 prints ONE JSON line.  Extra objects:
-  roofline     - dominant kernel = fused sub-band LSTM: algorithmic FLOPs per launch / its average
-                 duration measured with hipEvents on the forward's own stream (inside libfsnp_hip).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps once and prints the line; its
+`roofline` object (dominant kernel = fused sub-band LSTM: algorithmic FLOPs per launch / its average duration
+measured with hipEvents on the forward's own stream, inside libfsnp_hip) comes from those same steps.
+`--full` adds everything that takes time of its own:
+  repeats      - every timed loop run --repeats (3) times, the MEDIAN run reported, all of them listed;
+  alt / dropin - the same K steps in the other loop mode and with the module's default error_check="sync";
+  box          - the fp32-MFMA probe before and after the loops, sclk / power sampled during them, rocm-smi after;
   cpu_baseline - oracle/fsnp_torch.py (torch-CPU restatement of the reference, kind "port") timed on
-                 this box's host cores on a bounded sample (rank 0, N=1 only).
+                 this box's host cores on a bounded sample (rank 0), and the cIRM checked against it.
 """
 import argparse
 import json
@@ -62,14 +66,17 @@ def parse():
                     help="1 (default) = the serving loop: fsnp_set_pipeline, the remainder chunk of forward i (the 32 of 8224 "
                          "sequences that do not fit the chip-filling launch) overlaps the full-band stages of forward i+1; all "
                          "K forwards are complete (fsnp_flush + synchronize) inside the timed region.  0 = every forward runs "
-                         "strictly back to back.  The other mode is timed too and reported as `alt_ms_per_step`")
-    ap.add_argument("--no-alt", action="store_true", help="skip the extra timing of the other loop mode (profiling runs)")
-    ap.add_argument("--repeats", type=int, default=3,
-                    help="every timed loop (K steps, barrier + synchronise on both sides) is run this many times; the line reports the "
-                         "MEDIAN run (`ms_per_step`, `value`, `roofline`) and all of them (`ms_per_step_runs`): one 0.6 s region "
-                         "cannot tell a clock ramp or a slow box from a regression (VERDICT r05)")
+                         "strictly back to back.  With --full the other mode is timed too and reported as `alt_ms_per_step`")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: repeated timed loops, the other loop mode and the "
+                         "drop-in call, the box probes and clock sampling, the CPU baseline and the cIRM check against it")
+    ap.add_argument("--no-alt", action="store_true", help="--full: skip the extra timing of the other loop mode (profiling runs)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="every timed loop (K steps, barrier + synchronise on both sides) is run this many times (default: 1, "
+                         "with --full 3); the line reports the MEDIAN run (`ms_per_step`, `value`, `roofline`) and all of them "
+                         "(`ms_per_step_runs`): one 0.6 s region cannot tell a clock ramp or a slow box from a regression (VERDICT r05)")
     ap.add_argument("--probe-ms", type=float, default=50.0,
-                    help="length of the fp32-MFMA peak probe (fsnp_debug_box_probe) run before and after the timed loops; 0 = off")
+                    help="--full: length of the fp32-MFMA peak probe (fsnp_debug_box_probe) run before and after the timed loops; 0 = off")
     ap.add_argument("--strong", action="store_true",
                     help="N > 1: ALSO time BASELINE.json configs[2] as worded - ONE global batch of batch x N utterances lives on rank 0; "
                          "a step = scatter the STFT shards + forward + gather the masks to rank 0 (reported as `strong`, next to the "
@@ -77,7 +84,7 @@ def parse():
     ap.add_argument("--verify-sample", type=int, default=None,
                     help="fsnp_set_verify_sample for every loop (default: the module's policy - 16 in the drop-in loop's error_check='sync', off "
                          "in the deferred loops); 0 = off everywhere")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the cIRM check against it")
     ap.add_argument("--cpu-budget-s", type=float, default=15.0)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed loops, write what the last timed step returned as DIR/<name>.npy (float32; at most "
@@ -85,6 +92,8 @@ def parse():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
     return args
 
 
@@ -356,8 +365,8 @@ def main():
         sysfs_dir = box_mod.sysfs_device(pci_address(dev))
         idle_state = box_mod.read_sysfs(sysfs_dir)
         # what this box's matrix pipes hold, right before the timed loops (the first forward above has woken the clocks)
-        probe_before = box_mod.probe(args.probe_ms, stream_ptr) if args.probe_ms > 0 else None
-        sampler = box_mod.Sampler(sysfs_dir) if sysfs_dir else None
+        probe_before = box_mod.probe(args.probe_ms, stream_ptr) if args.full and args.probe_ms > 0 else None
+        sampler = box_mod.Sampler(sysfs_dir) if args.full and sysfs_dir else None
         if sampler:
             sampler.start()
 
@@ -370,18 +379,19 @@ def main():
                     [r[1]["lstm_first_chunk_ms"] / max(r[1]["count"], 1) for r in runs])
 
         pipelined = bool(args.pipeline) and not args.wave
-        alt_elapsed, alt_timing, _, alt_runs, _ = timed_runs(not pipelined) if not (args.wave or args.no_alt) else (None, None, None, None, None)
+        other_loops = args.full and not (args.wave or args.no_alt)
+        alt_elapsed, alt_timing, _, alt_runs, _ = timed_runs(not pipelined) if other_loops else (None, None, None, None, None)
         # the drop-in default: what a maintainer who edits the one TOML line gets - error_check="sync" (every forward waits for its
         # own launches and polls the error word before it returns), no pipelined loop
         dropin_elapsed, dropin_runs = None, None
-        if not (args.wave or args.no_alt) and world == 1:
+        if other_loops and world == 1:
             model.error_check = "sync"
             dropin_elapsed, _, _, dropin_runs, _ = timed_runs(False)
             model.error_check = "deferred"
         elapsed, timing, out, main_runs, launch_runs = timed_runs(pipelined)
         launch_clock = model.launch_clock()                     # the clocks of the LAST dominant-kernel launch (None: no such launch)
         sampled = sampler.stop() if sampler else {"samples": 0, "note": "no readable /sys/class/drm/card*/device for this GPU"}
-        probe_after = box_mod.probe(args.probe_ms, stream_ptr) if args.probe_ms > 0 else None
+        probe_after = box_mod.probe(args.probe_ms, stream_ptr) if args.full and args.probe_ms > 0 else None
 
         strong = None
         if args.strong and dist is not None and not args.wave and not fsn:
@@ -402,8 +412,10 @@ def main():
         # ... and the roofline block below describes THAT rank's kernels (the N > 1 line carries the slowest rank's roofline)
         timing = {"count": 1, "lstm_ms": float(every[slow][1]), "lstm_first_chunk_ms": float(every[slow][2]),
                   "fullband_ms": float(every[slow][3]), "forward_ms": float(every[slow][4])}
-        rank_probe = [{"rank": r, "mfma_tflops_before": float(every[r][5]), "mfma_tflops_after": float(every[r][6]),
-                       "clock_mhz_after": float(every[r][7]), "ms_per_step": rank_ms[r]} for r in range(world)]
+        probed = probe_after is not None                     # (the same on every rank: it follows the arguments)
+        rank_probe = [{"rank": r, "mfma_tflops_before": float(every[r][5]) if probe_before else None,
+                       "mfma_tflops_after": float(every[r][6]) if probed else None,
+                       "clock_mhz_after": float(every[r][7]) if probed else None, "ms_per_step": rank_ms[r]} for r in range(world)]
         # batch-split plumbing: gather every rank's masks once (outside the timed region)
         g0 = time.perf_counter()
         gathered = torch.empty((world * out.shape[0],) + tuple(out.shape[1:]), dtype=out.dtype, device=dev)
@@ -497,10 +509,10 @@ def main():
     }
     result["box"] = {
         "mfma_peak_tflops": box_peak, "spec_peak_tflops": PEAK_FP32_MFMA_TFLOPS,
-        "probe": "fsnp_debug_box_probe: v_mfma_f32_32x32x2_f32 only, one wave per SIMD on every CU, %g ms, random operands; run right "
-                 "before and right after the timed loops" % args.probe_ms,
+        "probe": ("fsnp_debug_box_probe: v_mfma_f32_32x32x2_f32 only, one wave per SIMD on every CU, %g ms, random operands; run right "
+                  "before and right after the timed loops" % args.probe_ms) if probes else "not run (it runs with --full and --probe-ms > 0)",
         "probe_before": probe_before, "probe_after": probe_after,
-        "idle_before": idle_state, "during_timed_loops": sampled,
+        "idle_before": idle_state, "during_timed_loops": sampled if args.full else None,
         "hostname": socket.gethostname(), "gpu": torch.cuda.get_device_name(dev), "gpu_unique_id": box_mod.gpu_unique_id(sysfs_dir),
     }
     if rank_probe is not None:
@@ -513,7 +525,7 @@ def main():
                           "world_size_seen": dist.get_world_size(), "same_device": bool(args.same_device),
                           "gathered_shape": list(gathered.shape),
                           "per_rank_ms_per_step": {"min": min(rank_ms), "max": max(rank_ms)}, "roofline_of_rank": slow}
-    if rank == 0 and not args.no_cpu_baseline:           # (rank 0 only; at N > 1 the other ranks wait in destroy_process_group)
+    if rank == 0 and args.full and not args.no_cpu_baseline:    # (rank 0 only; at N > 1 the other ranks wait in destroy_process_group)
         base, ref_outs = cpu_baseline(sd, cpu_in, args.cpu_budget_s, args.norm, fsn)
         ref_path = next((p for p in (os.path.join(ROOT, "profiles", f"r0{n}_cli_e2e.json") for n in (6, 5, 4)) if os.path.exists(p)),
                         os.path.join(ROOT, "profiles", "r04_cli_e2e.json"))    # the REAL reference class timed on a GPU box's host cores
@@ -537,8 +549,8 @@ def main():
         result["dumped_outputs"] = dump_outputs({"enhanced_wave" if args.wave else "cirm_mask": out}, args.dump_outputs,
                                                 f".rank{rank}" if world > 1 else "")
     if rank == 0:
-        from fullsubnet_plus_amd import box as box_mod2
-        result["box"]["rocm_smi_after"] = box_mod2.smi_snapshot()
+        if args.full:
+            result["box"]["rocm_smi_after"] = box_mod.smi_snapshot()
         print(json.dumps(result), flush=True)
     if dist is not None:
         dist.barrier()                       # (rank 0 ran the CPU baseline meanwhile)

@@ -25,7 +25,7 @@ def _run(cmd, timeout=600):
 
 def test_bench_plain_gpus2_self_launches_two_ranks():
     res = _run([sys.executable, "bench.py", "--gpus", "2", "--same-device", "--dist-backend", "gloo", "--steps", "2",
-                "--warmup", "1", "--batch", "4", "--cpu-budget-s", "2", "--strong"])
+                "--warmup", "1", "--batch", "4", "--cpu-budget-s", "2", "--strong", "--full"])
     assert res.returncode == 0, res.stderr[-3000:]
     line = [l for l in res.stdout.splitlines() if l.startswith("{")][-1]
     r = json.loads(line)
@@ -55,7 +55,8 @@ def test_bench_four_ranks_on_one_device():
         port = sk.getsockname()[1]
     res = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=4", "--master-addr", "127.0.0.1",
                 "--master-port", str(port), "bench.py", "--gpus", "4", "--same-device", "--dist-backend", "gloo", "--steps", "2",
-                "--warmup", "1", "--batch", "2", "--no-cpu-baseline", "--no-alt", "--strong", "--repeats", "1", "--probe-ms", "5"], timeout=900)
+                "--warmup", "1", "--batch", "2", "--full", "--no-cpu-baseline", "--no-alt", "--strong", "--repeats", "1", "--probe-ms", "5"],
+               timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     r = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
     # round 6: the same launch also times BASELINE.json configs[2] as worded - ONE global batch on rank 0, scatter + forward + gather - next
@@ -76,6 +77,21 @@ def test_bench_refuses_more_gpus_than_visible():
     res = _run([sys.executable, "bench.py", "--gpus", str(n + 1), "--steps", "1", "--warmup", "0", "--no-cpu-baseline"])
     assert res.returncode != 0
     assert "visible" in (res.stderr + res.stdout)
+
+
+def test_bench_plain_run_times_the_steps_once(tmp_path):
+    """Without --full the line carries the headline of ONE timed loop and nothing that needs a run of its own: no repeats, no
+    other loop mode, no box probe, no CPU baseline; the roofline comes from the timed steps themselves."""
+    res = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "4",
+                "--dump-outputs", str(tmp_path)])
+    assert res.returncode == 0, res.stderr[-3000:]
+    r = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
+    assert r["ms_per_step_runs"] == [r["ms_per_step"]] and r["ms_per_step"] > 0 and r["value"] > 0
+    assert r["alt_ms_per_step"] is None and r["dropin_ms_per_step"] is None and r["roofline"]["alt_fullband_ms"] is None
+    assert r["box"]["probe_before"] is None and r["box"]["probe_after"] is None and r["box"]["during_timed_loops"] is None
+    assert "cpu_baseline" not in r and "cirm_rel_err" not in r and "rocm_smi_after" not in r["box"]
+    assert r["roofline"]["avg_launch_ms"] > 0 and r["roofline"]["forward_ms"] > 0
+    assert np.load(tmp_path / "cirm_mask.npy").shape == (4, 2, 257, r["config"]["frames_per_clip"])
 
 
 @pytest.mark.parametrize("mode", ["full", "parity"])

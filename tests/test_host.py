@@ -1305,6 +1305,17 @@ def test_oracle_is_only_reachable_from_the_allowed_places():
     assert oracle_imports(os.path.join(ROOT, "__graft_entry__.py")) <= {"build", "smoke"}
 
 
+def test_bench_repeats_the_timed_loop_only_with_full(monkeypatch):
+    """A plain bench run times its steps once; --full repeats every timed loop three times unless --repeats says otherwise."""
+    import sys
+
+    import bench
+    for argv, repeats in ((["--steps", "5"], 1), (["--steps", "5", "--full"], 3), (["--full", "--repeats", "2"], 2), (["--repeats", "4"], 4)):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        args = bench.parse()
+        assert args.repeats == repeats and args.full == ("--full" in argv), argv
+
+
 def test_header_is_plain_c_and_library_links_from_c(tmp_path):
     """include/fsnp.h compiles as C99 with -Wall -Werror -pedantic, libfsnp_hip.so links from a plain C program, and the
     error paths reachable without a GPU return codes + messages (tests/c_abi/abi_check.c)."""

@@ -1,35 +1,36 @@
 #!/bin/bash
 # round 6: one line of box-variance evidence per GPU box (profiles/r06_box_variance.md is built from these).
 # Usage (from the build container): gpurun -- "bash tools/gpu_r06_box.sh <tag> [suite]"
-#   - the headline exactly as the driver runs it (bench.py --gpus 1 --steps 20 --warmup 5) -> gpurun_out/r06_box_<tag>.json
+#   - the headline and all that --full adds (bench.py --gpus 1 --steps 20 --warmup 5 --full) -> $OUT/r06_box_<tag>.json
 #     (its `box` object: fp32-MFMA probe before / after, sclk / power sampled during the timed loops, rocm-smi after)
 #   - rocm-smi's own view of the box, and five more 50 ms probes 1 s apart (is the probe itself stable on this box?)
 #   - [suite] the whole GPU suite first
 set -u
 TAG=${1:-x}
-mkdir -p gpurun_out
+OUT=$(realpath -m "${OUT:-out}"); export OUT    # every output of this script
+mkdir -p "$OUT"
 export TMPDIR=/tmp
 if [ "${2:-}" = "suite" ]; then
   {
     echo "commit: ${FSNP_HEAD:-unknown}   library stamp: $(cut -c1-16 fullsubnet_plus_amd/libfsnp_hip.so.stamp)   $(date -u +%FT%TZ)"
     timeout 2400 python -m pytest tests -m gpu -q --tb=short -p no:cacheprovider --durations=15 2>&1 | tail -45
-  } | tee gpurun_out/r06_pytest_gpu_$TAG.log
-  timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | tee gpurun_out/r06_smoke_$TAG.log
+  } | tee "$OUT"/r06_pytest_gpu_$TAG.log
+  timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | tee "$OUT"/r06_smoke_$TAG.log
 fi
 {
   echo "== host: $(hostname)  $(date -u +%FT%TZ)"
   (rocm-smi --showclocks --showpower --showmaxpower --showperflevel --showtemp 2>&1 || true) | grep -v "^$" | head -60
   ls /sys/class/drm/ 2>&1 | head -20
   for d in /sys/class/drm/card*/device; do echo "$d vendor=$(cat $d/vendor 2>/dev/null) perf=$(cat $d/power_dpm_force_performance_level 2>/dev/null)"; ls $d/hwmon/hwmon*/ 2>/dev/null | tr '\n' ' '; echo; done
-} > gpurun_out/r06_box_${TAG}_smi.txt 2>&1
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 2> gpurun_out/r06_box_${TAG}.err | tail -1 > gpurun_out/r06_box_${TAG}.json
-python - "$TAG" <<'PY' 2>&1 | tee gpurun_out/r06_box_${TAG}_probes.txt
-import json, sys, time
+} > "$OUT"/r06_box_${TAG}_smi.txt 2>&1
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full 2> "$OUT"/r06_box_${TAG}.err | tail -1 > "$OUT"/r06_box_${TAG}.json
+python - "$TAG" <<'PY' 2>&1 | tee "$OUT"/r06_box_${TAG}_probes.txt
+import json, os, sys, time
 import torch
 from fullsubnet_plus_amd import box
 tag = sys.argv[1]
 try:
-    r = json.load(open(f"gpurun_out/r06_box_{tag}.json"))
+    r = json.load(open(f"{os.environ['OUT']}/r06_box_{tag}.json"))
     b = r["box"]
     print(f"{tag}: {r['value']:.0f} frames/s  ms/step {r['ms_per_step']:.3f} runs {['%.3f' % x for x in r['ms_per_step_runs']]}  "
           f"back-to-back {r['alt_ms_per_step']:.3f}  drop-in {r['dropin_ms_per_step']:.3f}")

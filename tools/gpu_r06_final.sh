@@ -6,10 +6,11 @@
 #   3. the configuration table, RCCL at N = 1, phase profiles of the B = 1 and B = 2 sub-band kernels, the cost table, verification overhead
 #   4. [ref] the unmodified reference CLI end to end (reference staged under the git-ignored _refstage/ for this one call)
 #   5. the whole GPU suite again (run B): two green runs on one HEAD
-# The pytest logs carry the commit and a digest of the kernel sources at start and end of each run.  Everything -> gpurun_out/.
+# The pytest logs carry the commit and a digest of the kernel sources at start and end of each run.  Everything -> $OUT (default: out/).
 set -u
 REF=${1:-}          # (saved: the column-split timing loop below re-uses the positional parameters)
-mkdir -p gpurun_out
+OUT=$(realpath -m "${OUT:-out}"); export OUT    # every output of this script
+mkdir -p "$OUT"
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 digest() { cat fullsubnet_plus_amd/csrc/*.hip fullsubnet_plus_amd/csrc/*.h fullsubnet_plus_amd/csrc/*.cpp include/fsnp.h include/fsnp_debug.h | sha256sum | cut -c1-16; }
@@ -18,18 +19,18 @@ suite() {   # $1 = log name
     echo "commit: ${FSNP_HEAD:-unknown}   csrc sha256[:16] at start: $(digest)   library stamp: $(cut -c1-16 fullsubnet_plus_amd/libfsnp_hip.so.stamp)   $(date -u +%FT%TZ)"
     timeout 2400 python -m pytest tests -m gpu -q --tb=short -p no:cacheprovider --durations=25 2>&1 | tail -50
     echo "csrc sha256[:16] at end: $(digest)"
-  } | tee gpurun_out/$1
+  } | tee "$OUT"/$1
 }
 suite pytest_gpu_runA.log
-timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 | tee gpurun_out/smoke.log
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 2>&1 | tail -1 > gpurun_out/bench.log
+timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 | tee "$OUT"/smoke.log
+timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full 2>&1 | tail -1 > "$OUT"/bench.log
 cd /tmp
 prof() {   # $1 = output csv name, rest = bench.py arguments
   local name=$1; shift
-  rm -rf $R/gpurun_out/prof
-  timeout 600 rocprofv3 --kernel-trace --stats -f csv -d $R/gpurun_out/prof -o trace -- python $R/bench.py --gpus 1 --no-cpu-baseline --no-alt "$@" > $R/gpurun_out/prof_$name.log 2>&1
-  f=$(find $R/gpurun_out/prof -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $R/gpurun_out/$name.csv
-  rm -rf $R/gpurun_out/prof
+  rm -rf "$OUT"/prof
+  timeout 600 rocprofv3 --kernel-trace --stats -f csv -d "$OUT"/prof -o trace -- python $R/bench.py --gpus 1 --full --no-cpu-baseline --no-alt "$@" > "$OUT"/prof_$name.log 2>&1
+  f=$(find "$OUT"/prof -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" "$OUT"/$name.csv
+  rm -rf "$OUT"/prof
 }
 prof kernel_stats --steps 5 --warmup 2
 prof kernel_stats_serial_loop --steps 5 --warmup 2 --pipeline 0
@@ -38,15 +39,15 @@ prof kernel_stats_b2 --batch 2 --steps 10 --warmup 2 --pipeline 0
 i=0
 for ctr in "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES" "FETCH_SIZE" "WRITE_SIZE" "SQ_INSTS_VALU_MFMA_MOPS_F32 TCC_HIT_sum TCC_MISS_sum"; do
   i=$((i+1))
-  timeout 600 rocprofv3 --pmc $ctr -f csv -d $R/gpurun_out/pmc$i -o pmc -- python $R/bench.py --gpus 1 --steps 3 --warmup 1 --no-cpu-baseline --no-alt --pipeline 0 > $R/gpurun_out/pmc$i.log 2>&1
+  timeout 600 rocprofv3 --pmc $ctr -f csv -d "$OUT"/pmc$i -o pmc -- python $R/bench.py --gpus 1 --steps 3 --warmup 1 --full --no-cpu-baseline --no-alt --pipeline 0 > "$OUT"/pmc$i.log 2>&1
 done
 cd $R
-python - <<'PY' | tee gpurun_out/pmc_summary.txt
-import csv, glob, collections, json
+python - <<'PY' | tee "$OUT"/pmc_summary.txt
+import csv, glob, collections, json, os
 vals = {}
 for i in (1, 2, 3, 4):
     agg = collections.defaultdict(lambda: [0.0, 0])
-    for f in glob.glob(f"gpurun_out/pmc{i}/**/*counter_collection.csv", recursive=True):
+    for f in glob.glob(f"{os.environ['OUT']}/pmc{i}/**/*counter_collection.csv", recursive=True):
         for r in csv.DictReader(open(f)):
             k = (r["Kernel_Name"][:70], r["Counter_Name"])
             agg[k][0] += float(r["Counter_Value"]); agg[k][1] += 1
@@ -66,16 +67,16 @@ if {"FETCH_SIZE", "WRITE_SIZE", "SQ_VALU_MFMA_BUSY_CYCLES", "GRBM_GUI_ACTIVE"} <
            "traffic_bytes_per_launch": (2 * vals["FETCH_SIZE"] + vals["WRITE_SIZE"]) * 1024,
            "kernel_source_sha256": __import__("hashlib").sha256(b"".join(open("fullsubnet_plus_amd/csrc/" + n, "rb").read() for n in ("lstm.hip", "lstm_common.h", "fsnp_common.h"))).hexdigest(),
            "SQ_INSTS_VALU_MFMA_MOPS_F32_per_launch": vals.get("SQ_INSTS_VALU_MFMA_MOPS_F32")}
-    json.dump(out, open("gpurun_out/lstm_pmc.json", "w"), indent=1)
+    json.dump(out, open(os.path.join(os.environ["OUT"], "lstm_pmc.json"), "w"), indent=1)
 PY
-rm -rf gpurun_out/prof gpurun_out/pmc1 gpurun_out/pmc2 gpurun_out/pmc3 gpurun_out/pmc4
+rm -rf "$OUT"/prof "$OUT"/pmc1 "$OUT"/pmc2 "$OUT"/pmc3 "$OUT"/pmc4
 # matrix-pipe counters of the small-batch sub-band kernels (busy on OCCUPIED CUs) -> profiles/r06_small_batch_pmc.txt
 cd /tmp
-: > $R/gpurun_out/small_batch_pmc.txt
+: > "$OUT"/small_batch_pmc.txt
 for B in 1 2 4 8; do
   rm -rf /tmp/pmc
-  timeout 300 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES -f csv -d /tmp/pmc -o pmc -- python $R/bench.py --gpus 1 --batch $B --steps 3 --warmup 1 --no-cpu-baseline --no-alt --pipeline 0 --probe-ms 0 > /dev/null 2>&1
-  python - $B <<'PY' | tee -a $R/gpurun_out/small_batch_pmc.txt
+  timeout 300 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES -f csv -d /tmp/pmc -o pmc -- python $R/bench.py --gpus 1 --batch $B --steps 3 --warmup 1 --full --no-cpu-baseline --no-alt --pipeline 0 --probe-ms 0 > /dev/null 2>&1
+  python - $B <<'PY' | tee -a "$OUT"/small_batch_pmc.txt
 import csv, glob, collections, sys
 agg = collections.defaultdict(lambda: collections.defaultdict(lambda: [0.0, 0]))
 wgs = {}
@@ -101,25 +102,25 @@ for k, c in agg.items():
 PY
 done
 cd $R
-: > gpurun_out/b_final.log
+: > "$OUT"/b_final.log
 for args in "--batch 1" "--batch 2" "--batch 3" "--batch 4" "--batch 5" "--batch 6" "--batch 7" "--batch 8" "--batch 10" "--batch 12" "--batch 16" "--batch 21" "--batch 31" "--batch 40" "--batch 64" "--seconds 10" "--seconds 10 --norm cumulative_layer_norm" "--mode parity" "--mode parity --precision bf16_ih" "--precision bf16_ih" "--batch 16 --precision bf16_ih" "--wave" "--model fullsubnet" "--model fullsubnet --batch 1" "--model fullsubnet --batch 4" "--model fullsubnet --batch 8" "--model fullsubnet --batch 16" "--sequence-model GRU" "--sequence-model GRU --batch 1" "--sequence-model TCN"; do
-  timeout 400 python bench.py $args --steps 10 --warmup 2 --no-cpu-baseline --probe-ms 0 2>&1 | tail -1 >> gpurun_out/b_final.log
+  timeout 400 python bench.py $args --steps 10 --warmup 2 --full --no-cpu-baseline --probe-ms 0 2>&1 | tail -1 >> "$OUT"/b_final.log
 done
 python tools/make_config_table.py r06 > /dev/null
-python tools/dump_costs.py > gpurun_out/dump_costs.log 2>&1
-timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node=1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 10 --warmup 3 --no-cpu-baseline 2>&1 | tail -1 > gpurun_out/bench_rccl_n1.log
-timeout 120 python tools/pp_phase_profile.py 257 64 0 2>&1 | grep -v amdgpu > gpurun_out/hp_phase_profile.txt
-timeout 120 python tools/pp_phase_profile.py 514 64 32 2>&1 | grep -v amdgpu > gpurun_out/coopw_phase_profile.txt
-timeout 120 python tools/pp_phase_profile.py 1285 64 64 2>&1 | grep -v amdgpu >> gpurun_out/coopw_phase_profile.txt
-timeout 120 python tools/pp_phase_profile.py 2048 64 96 2>&1 | grep -v amdgpu >> gpurun_out/coopw_phase_profile.txt
+python tools/dump_costs.py > "$OUT"/dump_costs.log 2>&1
+timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node=1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 10 --warmup 3 --no-cpu-baseline 2>&1 | tail -1 > "$OUT"/bench_rccl_n1.log
+timeout 120 python tools/pp_phase_profile.py 257 64 0 2>&1 | grep -v amdgpu > "$OUT"/hp_phase_profile.txt
+timeout 120 python tools/pp_phase_profile.py 514 64 32 2>&1 | grep -v amdgpu > "$OUT"/coopw_phase_profile.txt
+timeout 120 python tools/pp_phase_profile.py 1285 64 64 2>&1 | grep -v amdgpu >> "$OUT"/coopw_phase_profile.txt
+timeout 120 python tools/pp_phase_profile.py 2048 64 96 2>&1 | grep -v amdgpu >> "$OUT"/coopw_phase_profile.txt
 {
   echo "== per-step times of the column-split kernels (tools/time_lstm.py, 128 steps)"
   for pair in "514 32" "672 32" "1285 64" "1344 64" "2048 96" "32 32" "32 64" "32 96"; do set -- $pair; COOPW=$2 timeout 120 python tools/time_lstm.py $1 128 5 2>&1 | tail -1; done
   for n in 514 1285 2056; do NOCOOPW=1 timeout 120 python tools/time_lstm.py $n 128 5 2>&1 | tail -1; timeout 120 python tools/time_lstm.py $n 128 5 2>&1 | tail -1; done
   HP=1 timeout 100 python tools/time_lstm.py 257 128 5 2>&1 | tail -1
   FSNP_HP_WAVE=0 HP=1 timeout 100 python tools/time_lstm.py 257 128 5 2>&1 | tail -1 | sed "s/^/FSNP_HP_WAVE=0 (lstm_hp.hip) /"
-} > gpurun_out/column_split_times.txt 2>&1
-python - <<'PY' | tee gpurun_out/verify_overhead.txt
+} > "$OUT"/column_split_times.txt 2>&1
+python - <<'PY' | tee "$OUT"/verify_overhead.txt
 # exchange verification (fsnp_set_verify): per-forward overhead at N = 64 and the cost of one verified forward, B = 1 and B = 32
 import time, torch
 from fullsubnet_plus_amd import FullSubNet_Plus
@@ -138,11 +139,11 @@ for B in (1, 32):
     m.check_errors()
     print(f"B={B}: plain {res[0]:.3f} ms, verify_every=64 {res[64]:.3f} ms (+{res[64]-res[0]:.3f}), every forward verified {res[1]:.3f} ms; verification passes run: {m.verify_count()}")
 PY
-python - <<'PY' | tee gpurun_out/b_final.txt
-import json
-r = json.loads(open("gpurun_out/bench.log").read())
+python - <<'PY' | tee "$OUT"/b_final.txt
+import json, os
+r = json.loads(open(os.path.join(os.environ["OUT"], "bench.log")).read())
 print("HEADLINE %.0f frames/s %.3f ms (b2b %.3f, drop-in %.3f) frac %.4f lstm %.3f ms stage %.3f ms fullband %.3f (alt %.3f) cpu %.0f err %.2e checked %d utterances" % (r["value"], r["ms_per_step"], r["alt_ms_per_step"], r["dropin_ms_per_step"], r["roofline"]["frac"], r["roofline"]["avg_launch_ms"], r["roofline"]["subband_stage_ms"], r["roofline"]["fullband_ms"], r["roofline"]["alt_fullband_ms"], r["cpu_baseline"]["value"], r["cirm_rel_err"], len(r["cirm_checked_utterances"])))
-for l in open("gpurun_out/b_final.log"):
+for l in open(os.path.join(os.environ["OUT"], "b_final.log")):
     try:
         r = json.loads(l)
     except Exception:
@@ -152,14 +153,14 @@ for l in open("gpurun_out/b_final.log"):
     print("%-62s | %8.0f frames/s %8.3f ms (b2b %s drop-in %s) sub-band %7.3f fullband %6.3f (alt %s) | %s | %s" % (r["config"]["workload"][:62], r["value"], r["ms_per_step"],
           "%.3f" % alt if alt else "-", "%.3f" % di if di else "-", r["roofline"]["subband_stage_ms"], r["roofline"]["fullband_ms"], "%.3f" % r["roofline"]["alt_fullband_ms"] if r["roofline"].get("alt_fullband_ms") else "-", r["dtype"][:8], plan))
 try:
-    r = json.loads(open("gpurun_out/bench_rccl_n1.log").read())
+    r = json.loads(open(os.path.join(os.environ["OUT"], "bench_rccl_n1.log")).read())
     print("bench_rccl_n1 %.3f ms/step" % r["ms_per_step"], r.get("dist"), r.get("gather_ms"))
 except Exception as e:
     print("bench_rccl_n1 ??", e)
 PY
 if [ -n "$REF" ] && [ -d "$REF" ]; then
-  timeout 900 python tools/cli_e2e.py "$REF" 2>&1 | tail -15 | tee gpurun_out/cli_e2e_stdout.log
+  timeout 900 python tools/cli_e2e.py "$REF" 2>&1 | tail -15 | tee "$OUT"/cli_e2e_stdout.log
 fi
 suite pytest_gpu_runB.log
-head -16 gpurun_out/kernel_stats.csv | cut -c1-170
+head -16 "$OUT"/kernel_stats.csv | cut -c1-170
 echo "== done"

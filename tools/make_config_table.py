@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""gpurun_out/bench.log + gpurun_out/b_final.log (tools/gpu_rNN_final.sh) -> profiles/rNN_bench_configs.md; usage: make_config_table.py r03"""
+"""$OUT/bench.log + $OUT/b_final.log (tools/gpu_rNN_final.sh, OUT default: out/) -> profiles/rNN_bench_configs.md; usage: make_config_table.py r03"""
 import json
 import os
 import sys
@@ -7,15 +7,16 @@ import sys
 TAG = sys.argv[1] if len(sys.argv) > 1 else "r03"
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OUT = os.environ.get("OUT", os.path.join(ROOT, "out"))
 rows = []
-for line in open(os.path.join(ROOT, "gpurun_out", "b_final.log")):
+for line in open(os.path.join(OUT, "b_final.log")):
     try:
         r = json.loads(line)
     except Exception:
         continue
     plan = " + ".join("%s ×%d%s" % (c["kernel"].split(" ")[0], c["sequences"], "*" if c.get("deferred_when_pipelined") else "") for c in r["roofline"]["subband_plan"])
     rows.append((r["metric"].split("), ")[1], r["config"]["workload"], r["value"], r["ms_per_step"], r["alt_ms_per_step"], r["dtype"], plan, r.get("dropin_ms_per_step")))
-h = json.load(open(os.path.join(ROOT, "gpurun_out", "bench.log")))
+h = json.load(open(os.path.join(OUT, "bench.log")))
 hp = " + ".join("%s ×%d" % (c["kernel"].split(" ")[0], c["sequences"]) for c in h["roofline"]["subband_plan"])
 out = [f"# {TAG} - bench.py on one MI355X: every configuration measured at the end of round {int(TAG[1:])} (gpurun, `tools/gpu_{TAG}_final.sh`)", "",
        "fp32 unless stated; frames/s = B·T / wall time of the whole forward, inputs resident in HBM.  `ms/step` = the default loop of",
