@@ -102,15 +102,17 @@ SYMBOLS = {
     "fsnp_version": (ctypes.c_char_p, []),
 }
 
-# every symbol include/fsnp_lengths.h declares (batches of clips of different lengths, ABI 12)
+# every symbol include/fsnp_lengths.h declares (batches of clips of different lengths, ABI 12; fsnp_apply_cirm_lengths ABI 13)
 LENGTHS_SYMBOLS = {
     "fsnp_forward_lengths": (c_i32, [c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(c_i64 * 3 * 3), ctypes.POINTER(c_i32), c_vp, c_i32, c_i32,
                                      c_vp]),
     "fsnp_forward_complex_lengths": (c_i32, [c_vp, c_vp, ctypes.POINTER(c_i64 * 3), ctypes.POINTER(c_i32), c_vp, c_i32, c_i32, c_vp]),
     "fsnp_enhance_wave_lengths": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_i64, ctypes.POINTER(c_i32), c_i32, c_i32, c_vp]),
+    "fsnp_apply_cirm_lengths": (c_i32, [c_vp, c_vp, ctypes.POINTER(c_i64 * 3), c_vp, ctypes.POINTER(c_i64 * 3), ctypes.POINTER(c_i32),
+                                        c_i32, c_i32, c_i32, c_vp]),
 }
 
-ABI_VERSION = 12         # FSNP_ABI_VERSION of the include/fsnp.h these signatures were written against
+ABI_VERSION = 13         # FSNP_ABI_VERSION of the include/fsnp.h these signatures were written against
 
 _lib = None
 

@@ -410,6 +410,18 @@ __global__ __launch_bounds__(256) void fe_apply_kernel(const float* __restrict__
 
 // ------------------------------------------------------------------------------------------------
 // decompress_cIRM (mask.py:60-63) + complex multiply (inferencer.py:152-157)
+__device__ __forceinline__ float2 cirm_times(const float* __restrict__ mask, long re_at, long plane, float2 x) {
+    float m[2];
+#pragma unroll
+    for (int o = 0; o < 2; ++o) {
+        float v = mask[re_at + o * plane];
+        const float lim = 9.9f, K = 10.0f;
+        v = v >= lim ? lim : (v <= -lim ? -lim : v);
+        m[o] = -K * logf((K - v) / (K + v));
+    }
+    return make_float2(m[0] * x.x - m[1] * x.y, m[1] * x.x + m[0] * x.y);
+}
+
 __global__ __launch_bounds__(256) void apply_cirm_kernel(const float* __restrict__ mask, const float2* __restrict__ noisy,
                                                          long sb, long sf, long st, float2* __restrict__ out, long ob,
                                                          long of, long ot, int B, int F, int T) {
@@ -419,16 +431,8 @@ __global__ __launch_bounds__(256) void apply_cirm_kernel(const float* __restrict
         const int f = (int)(i % F);
         const int t = (int)((i / F) % T);
         const int b = (int)(i / ((long)F * T));
-        float m[2];
-#pragma unroll
-        for (int o = 0; o < 2; ++o) {
-            float v = mask[(((long)b * 2 + o) * F + f) * T + t];
-            const float lim = 9.9f, K = 10.0f;
-            v = v >= lim ? lim : (v <= -lim ? -lim : v);
-            m[o] = -K * logf((K - v) / (K + v));
-        }
         const float2 x = noisy[b * sb + f * sf + t * st];
-        out[b * ob + f * of + t * ot] = make_float2(m[0] * x.x - m[1] * x.y, m[1] * x.x + m[0] * x.y);
+        out[b * ob + f * of + t * ot] = cirm_times(mask, ((long)b * 2 * F + f) * T + t, (long)F * T, x);
     }
 }
 
@@ -439,6 +443,37 @@ void launch_apply_cirm(const float* mask, const float* noisy, const int64_t stri
     hipLaunchKernelGGL(apply_cirm_kernel, dim3(blocks), dim3(256), 0, s, mask, reinterpret_cast<const float2*>(noisy),
                        strides[0], strides[1], strides[2], reinterpret_cast<float2*>(out), out_strides[0], out_strides[1],
                        out_strides[2], B, F, T);
+}
+
+// the same for clips of different lengths: rows b0 ... b0 + rows - 1 of the batch, row b's frames >= len.v[b - b0] written as 0
+// without reading the mask or the input there (the contract lets the input past a length hold anything, NaN included)
+__global__ __launch_bounds__(256) void apply_cirm_lengths_kernel(const float* __restrict__ mask, const float2* __restrict__ noisy,
+                                                                 long sb, long sf, long st, float2* __restrict__ out, long ob,
+                                                                 long of, long ot, int b0, int rows, int F, int T, RowLengths len) {
+    const long total = (long)rows * T * F;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const int f = (int)(i % F);
+        const int t = (int)((i / F) % T);
+        const int r = (int)(i / ((long)F * T));
+        const long b = (long)b0 + r;
+        float2 y = make_float2(0.0f, 0.0f);
+        if (t < len.v[r]) y = cirm_times(mask, (b * 2 * F + f) * T + t, (long)F * T, noisy[b * sb + f * sf + t * st]);
+        out[b * ob + f * of + t * ot] = y;
+    }
+}
+
+void launch_apply_cirm_lengths(const float* mask, const float* noisy, const int64_t strides[3], float* out,
+                               const int64_t out_strides[3], int B, int F, int T, const int* lengths, hipStream_t s) {
+    for (int b0 = 0; b0 < B; b0 += kLenRows) {
+        const int rows = B - b0 < kLenRows ? B - b0 : kLenRows;
+        RowLengths len{};
+        for (int r = 0; r < rows; ++r) len.v[r] = lengths[b0 + r];
+        const long total = (long)rows * T * F;
+        const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+        hipLaunchKernelGGL(apply_cirm_lengths_kernel, dim3(blocks), dim3(256), 0, s, mask, reinterpret_cast<const float2*>(noisy),
+                           strides[0], strides[1], strides[2], reinterpret_cast<float2*>(out), out_strides[0], out_strides[1],
+                           out_strides[2], b0, rows, F, T, len);
+    }
 }
 
 void launch_frontend(const Dims& d, int norm_type, const float* const in[3], const int64_t strides[3][3], bool is_complex,

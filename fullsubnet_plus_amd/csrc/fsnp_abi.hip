@@ -1086,6 +1086,20 @@ int fsnp_apply_cirm(const float* mask, const float* noisy, const int64_t strides
     return 0;
 }
 
+int fsnp_apply_cirm_lengths(const float* mask, const float* noisy, const int64_t strides[3], float* out, const int64_t out_strides[3],
+                            const int32_t* lengths, int32_t batch, int32_t freqs, int32_t frames, void* hip_stream) {
+    if (!mask || !noisy || !out || !strides || !out_strides || !lengths) { set_error("fsnp_apply_cirm_lengths: null argument"); return 1; }
+    if (batch <= 0 || freqs <= 0 || frames <= 0) { set_error("fsnp_apply_cirm_lengths: empty input"); return 2; }
+    for (int b = 0; b < batch; ++b)
+        if (lengths[b] < 1 || lengths[b] > frames) {
+            set_error("fsnp_apply_cirm_lengths: utterance %d: length %d outside [1, %d]", b, (int)lengths[b], (int)frames);
+            return 2;
+        }
+    launch_apply_cirm_lengths(mask, noisy, strides, out, out_strides, batch, freqs, frames, lengths, static_cast<hipStream_t>(hip_stream));
+    FSNP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 int fsnp_lstm2_fc(fsnp_handle* h, const float* x, float* out, int32_t num_seq, int32_t steps, void* hip_stream) {
     if (!h || !x || !out) { set_error("fsnp_lstm2_fc: null argument"); return 1; }
     if (!h->committed) { set_error("fsnp_lstm2_fc: weights not committed"); return 2; }

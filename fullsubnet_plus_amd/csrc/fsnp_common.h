@@ -97,6 +97,13 @@ void launch_repack_plane(const Dims& d, const float* in, const int64_t strides[3
 void launch_tm_to_bft(const float* tm, float* out, int B, int T, int Tp, int F, int FP, hipStream_t s);       // stages.hip
 void launch_apply_cirm(const float* mask, const float* noisy, const int64_t strides[3], float* out,
                        const int64_t out_strides[3], int B, int F, int T, hipStream_t s);
+// per-row host values as a kernel argument (clips of different lengths: no copy to the device, nothing to synchronise), kLenRows
+// rows per launch; what the launchers of such kernels (apply_cirm, stft pad, istft overlap-add) loop over
+constexpr int kLenRows = 256;
+struct RowLengths { int v[kLenRows]; };
+// launch_apply_cirm for clips of different lengths: lengths[b] HOST frames of row b, frames >= lengths[b] of `out` written as 0
+void launch_apply_cirm_lengths(const float* mask, const float* noisy, const int64_t strides[3], float* out,
+                               const int64_t out_strides[3], int B, int F, int T, const int* lengths, hipStream_t s);
 // is_complex: in[0] is the interleaved complex64 STFT buffer (strides[0] in complex elements); mag / real / imag are
 // derived inside the repack kernel
 // (buf.fsum and buf.tot must be zero when this is called: the repack kernel accumulates the offline norms' statistics into them)

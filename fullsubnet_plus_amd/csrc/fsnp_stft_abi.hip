@@ -184,7 +184,7 @@ int fsnp_enhance_wave_lengths(fsnp_handle* h, const float* wav, int64_t wav_stri
     if (rc) return rc;
     if (h->pipeline && fsnp_flush(h, hip_stream)) return 4;
     FSNP_HIP_CHECK(hipMemsetAsync(enh, 0, spec_b, s));
-    launch_apply_cirm(mask, noisy, cst, enh, cst, batch, p.F, T, s);      // (mask frames >= T_b are 0: decompress_cIRM(0) = 0)
+    launch_apply_cirm_lengths(mask, noisy, cst, enh, cst, batch, p.F, T, frames.data(), s);      // frames >= T_b: 0
     launch_linear_act(enh, p.sp, h->d_stft + p.o_inv, p.inv_ld, h->d_stft + p.o_zero, fr, p.n_fft, p.N2, p.n_fft, batch, T,
                       FSNP_ACT_NONE, h->num_cus, s, (long)T * p.sp, p.N2);
     launch_istft_ola_lengths(fr, h->d_stft + p.o_win, out, out_stride, batch, T, max_samples, samples, p.n_fft, s);

@@ -71,9 +71,7 @@ void launch_istft_ola(const float* frames, const float* window, float* wav, long
 }
 
 // ---- clips of different lengths in one batch (fsnp_enhance_wave_lengths): row b is its own samples[b] long.  The sample counts travel
-// as kernel arguments (no copy to the device, nothing to synchronise), 256 rows per launch.
-constexpr int kLenRows = 256;
-struct RowLengths { int v[kLenRows]; };
+// as kernel arguments (RowLengths: no copy to the device, nothing to synchronise), kLenRows rows per launch.
 
 // reflect padding at each row's own end (torch.stft of the clip alone), zeros behind it
 __global__ __launch_bounds__(256) void stft_pad_lengths_kernel(const float* __restrict__ wav, long wav_stride, float* __restrict__ xp,

@@ -639,9 +639,11 @@ class _HipModel(nn.Module):
         fullsubnet_plus/inferencer/inferencer.py (`full_band_crm_mask` of fullsubnet/inferencer/inferencer.py for the
         original FullSubNet): noisy_complex [B,F,T] complex64 (torch.stft output, any strides) -> enhanced complex
         [B,F,T] ready for torch.istft.  Always keeps all bins (batch_mode "full").  lengths: frames per utterance (see
-        forward); frames past them come out as 0."""
+        forward); frames past them come out as exactly 0 whatever the input holds there (fsnp_apply_cirm_lengths)."""
         assert noisy_complex.dim() == 3 and noisy_complex.is_complex()
         assert self.output_size == 2, "the cIRM epilogue needs the two mask channels (decompress_cIRM, acoustics/mask.py:60-63)"
+        if lengths is not None:
+            lengths = _host_lengths(lengths, noisy_complex.shape[0], f"{self.__class__.__name__}.enhance")
         mode, self.batch_mode = self.batch_mode, "full"
         try:
             mask = self.forward_complex(noisy_complex, lengths=lengths)
@@ -649,7 +651,7 @@ class _HipModel(nn.Module):
             self.batch_mode = mode
         if self._pipeline:
             self.flush()            # the mask's deferred rows (pipelined mode) are complete on this stream only after a flush
-        return self._apply_cirm(mask, noisy_complex)
+        return self._apply_cirm(mask, noisy_complex, lengths)
 
     # ------------------------------------------------------------------ STFT / iSTFT in HIP
     def _wave_args(self, wav):
@@ -711,7 +713,8 @@ class _HipModel(nn.Module):
             return out
         return self._checked(run, wav.device)
 
-    def _apply_cirm(self, mask, noisy_complex):
+    def _apply_cirm(self, mask, noisy_complex, lengths=None):
+        """lengths: None, or the ctypes int32[B] of _host_lengths (frames >= lengths[b] of row b are written as 0)."""
         B, F, T = noisy_complex.shape
         out = torch.empty_strided((B, F, T), noisy_complex.stride(), dtype=torch.complex64, device=noisy_complex.device)
         xr, orr = torch.view_as_real(noisy_complex), torch.view_as_real(out)
@@ -719,8 +722,13 @@ class _HipModel(nn.Module):
         ost = (ctypes.c_int64 * 3)(*out.stride())
         stream = torch.cuda.current_stream(noisy_complex.device).cuda_stream
         with torch.cuda.device(noisy_complex.device):
-            _lib.check(_lib.load().fsnp_apply_cirm(mask.data_ptr(), xr.data_ptr(), ctypes.byref(st), orr.data_ptr(),
-                                                   ctypes.byref(ost), B, F, T, ctypes.c_void_p(stream)), "fsnp_apply_cirm")
+            if lengths is not None:
+                _lib.check(_lib.load().fsnp_apply_cirm_lengths(mask.data_ptr(), xr.data_ptr(), ctypes.byref(st), orr.data_ptr(),
+                                                               ctypes.byref(ost), lengths, B, F, T, ctypes.c_void_p(stream)),
+                           "fsnp_apply_cirm_lengths")
+            else:
+                _lib.check(_lib.load().fsnp_apply_cirm(mask.data_ptr(), xr.data_ptr(), ctypes.byref(st), orr.data_ptr(),
+                                                       ctypes.byref(ost), B, F, T, ctypes.c_void_p(stream)), "fsnp_apply_cirm")
         return out
 
     # ------------------------------------------------------------------ test / bench helpers

@@ -299,12 +299,12 @@ const char* fsnp_last_error(void);
 const char* fsnp_version(void);
 /* Binding sanity: FSNP_ABI_VERSION of the header the library was built from and sizeof(fsnp_config) as it sees it; a
  * binding compares both with its own idea before the first real call (fullsubnet_plus_amd/_lib.py does). */
-#define FSNP_ABI_VERSION 12
+#define FSNP_ABI_VERSION 13
 int32_t fsnp_abi_version(void);
 int32_t fsnp_config_size(void);
 
 #ifdef __cplusplus
 }
 #endif
-#include "fsnp_lengths.h"    /* batches of clips of different lengths (ABI 12) */
+#include "fsnp_lengths.h"    /* batches of clips of different lengths (ABI 12, fsnp_apply_cirm_lengths ABI 13) */
 #endif /* FSNP_H */

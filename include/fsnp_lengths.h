@@ -1,6 +1,6 @@
 /*
- * fsnp_lengths.h - batches of clips of different lengths (ABI 12): the forward, the STFT-domain forward and the waveform path with
- * a length per utterance.  Part of the public surface of libfsnp_hip.so next to fsnp.h (which includes this header), same
+ * fsnp_lengths.h - batches of clips of different lengths (ABI 13): the forward, the STFT-domain forward, the cIRM epilogue and the
+ * waveform path with a length per utterance.  Part of the public surface of libfsnp_hip.so next to fsnp.h (which includes this header), same
  * FSNP_ABI_VERSION.  What "a batch of clips of different lengths" computes, and why the caller cannot get it by zero padding, is
  * in DESIGN.md ("Clips of different lengths"); how to batch a directory of clips with it is in INTEGRATION.md.
  */
@@ -30,10 +30,17 @@ int fsnp_forward_lengths(fsnp_handle* h, const float* mag, const float* real, co
                          const int32_t* lengths, float* out, int32_t batch, int32_t frames, void* hip_stream);
 int fsnp_forward_complex_lengths(fsnp_handle* h, const float* noisy, const int64_t strides[3], const int32_t* lengths, float* out,
                                  int32_t batch, int32_t frames, void* hip_stream);
+/* fsnp_apply_cirm (fsnp.h) of clips of different lengths: row b is lengths[b] frames long (HOST int32 [batch], 1 <= lengths[b] <=
+ * frames, read during the call and passed as kernel arguments).  Element (b, f, t) of `out` is fsnp_apply_cirm's at t < lengths[b] and
+ * exactly 0 at t >= lengths[b]; neither `mask` nor `noisy` is read there (they may hold anything, NaN included).  Code 2, naming the
+ * utterance, for a length outside [1, frames]. */
+int fsnp_apply_cirm_lengths(const float* mask, const float* noisy, const int64_t strides[3], float* out, const int64_t out_strides[3],
+                            const int32_t* lengths, int32_t batch, int32_t freqs, int32_t frames, void* hip_stream);
 /* fsnp_enhance_wave of clips of different lengths: row b of wav holds samples[b] samples (HOST int32 [batch], read during the call),
  * n_fft / 2 < samples[b] <= max_samples.  The STFT reflects at each clip's own end and gives it T_b = 1 + samples[b] / hop frames, the
  * model runs as fsnp_forward_complex_lengths with those, the iSTFT overlap-adds and normalises over those T_b frames only and trims to
- * samples[b]; out row b at samples >= samples[b] is written as 0.  Row b equals fsnp_enhance_wave of that clip alone. */
+ * samples[b] (the cIRM epilogue is fsnp_apply_cirm_lengths with those T_b); out row b at samples >= samples[b] is written as 0.  Row b
+ * equals fsnp_enhance_wave of that clip alone. */
 int fsnp_enhance_wave_lengths(fsnp_handle* h, const float* wav, int64_t wav_stride, float* out, int64_t out_stride,
                               const int32_t* samples, int32_t batch, int32_t max_samples, void* hip_stream);
 

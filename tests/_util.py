@@ -88,3 +88,72 @@ def rel_err(a, b):
     a = np.asarray(a, dtype=np.float64)
     b = np.asarray(b, dtype=np.float64)
     return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
+
+
+# ------------------------------------------------------------------------------------------------ clips of different lengths
+def edge_lengths(T, look_ahead, min_len, edges=(8, 32, 64, 128, 256), extra=()):
+    """Clip lengths L (frames) that put L + look_ahead - the frames a clip's per-utterance reductions end at - one below, at and one
+    above every edge (a multiple of a kernel's sub-tile, row tile or chunk) that fits in [min_len, T], plus min_len, T and `extra`
+    (kept where they fit).  Sorted, without repeats."""
+    out = {min_len, T}
+    for e in edges:
+        for d in (-1, 0, 1):
+            out.add(e + d - look_ahead)
+    out.update(extra)
+    return sorted(L for L in out if min_len <= L <= T)
+
+
+def garbage_tails(ts, lengths, seed):
+    """Contiguous copies of [B, 1, F, T] tensors with huge values and NaN at frames >= lengths[b]."""
+    g = torch.Generator().manual_seed(seed)
+    out = []
+    for t in ts:
+        t = t.contiguous().clone()
+        for b, n in enumerate(lengths):
+            if n < t.shape[-1]:
+                tail = t[b, :, :, n:]
+                tail.copy_(torch.randn(tail.shape, generator=g) * 1e6)
+                tail[..., 0, 0] = float("nan")
+        out.append(t)
+    return out
+
+
+def oracle_kwargs(args):
+    """fsnp_torch.forward / forward_full keyword arguments of a FullSubNet+ model's arguments."""
+    return dict(look_ahead=args["look_ahead"], sb_num_neighbors=args["sb_num_neighbors"], fb_num_neighbors=args["fb_num_neighbors"],
+                norm_type=args["norm_type"], num_groups_in_drop_band=args["num_groups_in_drop_band"],
+                channel_attention_model=args.get("channel_attention_model", "TSSE"), subband_num=args.get("subband_num", 1),
+                fb_output_activate_function=args["fb_output_activate_function"],
+                sb_output_activate_function=args["sb_output_activate_function"], output_size=args.get("output_size", 2))
+
+
+def fullsubnet_oracle_kwargs(args):
+    """fsnp_torch.forward_fullsubnet_full keyword arguments of an original FullSubNet's model arguments."""
+    return {k: args[k] for k in ("look_ahead", "sb_num_neighbors", "fb_num_neighbors", "norm_type", "num_groups_in_drop_band",
+                                 "fb_output_activate_function", "sb_output_activate_function")}
+
+
+def oracle_rows(fn, ts, lengths):
+    """Row b of each [B, ...] tensor in ts trimmed to its lengths[b] (last axis) and passed through fn, one call per distinct length
+    (the rows of one length stacked: every reduction of a "full" forward is per utterance) -> list of [1, ...] results, row by row."""
+    by_len = {}
+    for b, n in enumerate(lengths):
+        by_len.setdefault(int(n), []).append(b)
+    rows = [None] * len(lengths)
+    for n, bs in by_len.items():
+        out = fn(*[t[bs][..., :n] for t in ts])
+        for i, b in enumerate(bs):
+            rows[b] = out[i:i + 1]
+    return rows
+
+
+def check_rows(got, want_rows, lengths, tol):
+    """got [B, ..., T] (CPU); want_rows[b] = the reference's [1, ..., lengths[b]].  Per row: rel_err on the clip < tol, exactly 0 past it,
+    no NaN anywhere.  Returns the per-row errors."""
+    assert not torch.isnan(got).any()
+    errs = []
+    for b, n in enumerate(lengths):
+        errs.append(rel_err(got[b:b + 1, ..., :n].numpy(), want_rows[b].numpy()))
+        assert torch.count_nonzero(got[b, ..., n:]) == 0, f"row {b}: frames past its length {n} are not 0"
+    assert max(errs) < tol, (max(errs), int(np.argmax(errs)), errs)
+    return errs

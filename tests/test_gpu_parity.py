@@ -754,8 +754,8 @@ def test_dma_gemm_equals_general_gemm(profile, B, T):
 
 
 def test_b32_10s_full_vs_oracle():
-    """BASELINE configs[3] at its benchmarked shape (batch 32 x 10 s clips, T = 626, look-ahead 2): first and last
-    utterance against the oracle (the last one again holds the remainder kernel's rows), plus batch independence of a
+    """BASELINE configs[3] at its benchmarked shape (batch 32 x 10 s clips, T = 626, look-ahead 2): every utterance against the
+    oracle (the last one holds the remainder kernel's rows; a row-indexing slip once hit 8 rows of 32), plus batch independence of a
     middle one against a B = 1 run of the HIP path (a different kernel plan)."""
     sd = make_state_dict(0, "default")
     mag, real, imag = make_inputs(32, 10.0, 300)
@@ -764,12 +764,14 @@ def test_b32_10s_full_vs_oracle():
     assert full.shape == (32, 2, 257, 626)
     torch.set_num_threads(min(16, os.cpu_count() or 1))
     errs = {}
-    for b in (0, 31):
-        want = fsnp_torch.forward_full(sd, mag[b:b + 1], real[b:b + 1], imag[b:b + 1]).numpy()
-        errs[b] = rel_err(full[b:b + 1].numpy(), want)
+    for b0 in range(0, 32, 8):          # the oracle is per utterance in "full" mode: eight rows per call
+        want = fsnp_torch.forward_full(sd, mag[b0:b0 + 8], real[b0:b0 + 8], imag[b0:b0 + 8]).numpy()
+        for i in range(8):
+            errs[b0 + i] = rel_err(full[b0 + i:b0 + i + 1].numpy(), want[i:i + 1])
     one = m(*_cuda((mag[17:18], real[17:18], imag[17:18]))).cpu()
     indep = rel_err(one.numpy(), full[17:18].numpy())
-    _record("b32_10s_full_vs_oracle_utt_0_31", rel_0=errs[0], rel_31=errs[31], b1_vs_batch_row17=indep)
+    worst = max(errs, key=errs.get)
+    _record("b32_10s_full_vs_oracle_all_rows", rel_max=errs[worst], worst_row=worst, b1_vs_batch_row17=indep)
     assert max(errs.values()) < TOL, errs
     assert indep < 1e-5, indep
 
