@@ -112,6 +112,18 @@ LENGTHS_SYMBOLS = {
                                         c_i32, c_i32, c_i32, c_vp]),
 }
 
+# every symbol include/fsnp_stream.h declares (stream sessions of the original FullSubNet; same ABI version)
+STREAM_SYMBOLS = {
+    "fsnp_stream_create": (c_i32, [c_vp, c_i32, c_i32, ctypes.POINTER(c_vp)]),
+    "fsnp_stream_destroy": (None, [c_vp]),
+    "fsnp_stream_push": (c_i32, [c_vp, c_vp, ctypes.POINTER(c_i64 * 3), ctypes.POINTER(c_i32), c_vp, c_i32, c_vp]),
+    "fsnp_stream_reset": (c_i32, [c_vp, ctypes.POINTER(c_i32), c_i32, c_vp]),
+    "fsnp_stream_state_bytes": (c_i64, [c_vp]),
+    "fsnp_stream_get_state": (c_i32, [c_vp, c_i32, c_vp, c_vp]),
+    "fsnp_stream_set_state": (c_i32, [c_vp, c_i32, c_vp, c_vp]),
+    "fsnp_stream_frames": (c_i32, [c_vp, c_i32, ctypes.POINTER(c_i64)]),
+}
+
 ABI_VERSION = 13         # FSNP_ABI_VERSION of the include/fsnp.h these signatures were written against
 
 _lib = None
@@ -133,7 +145,7 @@ def load(build_if_missing=True):
     if not os.path.exists(path):
         raise RuntimeError(f"{path} is missing: run `python -m fullsubnet_plus_amd._build`")
     lib = ctypes.CDLL(path)
-    for name, (res, args) in list(SYMBOLS.items()) + list(LENGTHS_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(LENGTHS_SYMBOLS.items()) + list(STREAM_SYMBOLS.items()):
         fn = getattr(lib, name)          # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

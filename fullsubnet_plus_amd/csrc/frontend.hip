@@ -537,6 +537,46 @@ void launch_frontend_mag(const Dims& d, int norm_type, const float* mag, const i
     hipLaunchKernelGGL(fe_scan_kernel, dim3(d.B, 1), dim3(256), 0, s, buf.frame, buf.md, d.B, d.Tp, d.F, norm_type, d.tpb);
 }
 
+// ---- streaming (include/fsnp_stream.h): the cumulative norm of one push, continued from the slot's carried sums.  One thread per slot
+// walks the push's frames in order: the prefix of step t covers F * (P + t + 1) entries, P = frames the slot had before this push, and
+// the sums stay fp64 and are added frame by frame whatever the chunking (an hour-long stream keeps its first minute).  Frames past the
+// slot's count get the identity (they are never used); cnt = 0 writes nothing back.
+__global__ __launch_bounds__(64) void fe_scan_stream_kernel(const double* __restrict__ frame, NormMD* __restrict__ md,
+                                                            const StreamMeta* __restrict__ meta, double* __restrict__ sums, long sum_stride,
+                                                            int S, int n, int F, int norm_type) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= S) return;
+    const StreamMeta m = meta[b];
+    double* sm = sums + (long)b * sum_stride;
+    double ps = sm[0], pq = sm[1];
+    const long base = (long)b * n;
+    for (int t = 0; t < n; ++t) {
+        if (t < m.cnt) {
+            ps += frame[(base + t) * 2];
+            pq += frame[(base + t) * 2 + 1];
+            md[base + t] = norm_md(norm_type, ps, pq, (double)F * (double)(m.p + t + 1));
+        } else {
+            md[base + t] = NormMD{0.0f, 1.0f};
+        }
+    }
+    if (m.cnt > 0) { sm[0] = ps; sm[1] = pq; }
+}
+
+// d: B = slots, T = Tp = the push's n, lens = frames per slot of this push (device)
+void launch_frontend_mag_stream(const Dims& d, int norm_type, const float* mag, const int64_t strides[3], const FrontendBuffers& buf,
+                                const StreamMeta* meta, double* sums, long sum_stride, hipStream_t s) {
+    StridedIn si;
+    for (int i = 0; i < 3; ++i) {
+        si.p[i] = mag;
+        si.sb[i] = strides[0]; si.sf[i] = strides[1]; si.st[i] = strides[2];
+    }
+    hipLaunchKernelGGL(fe_repack_kernel, dim3(cdiv(d.FP, 32), cdiv(d.Tp, 32), d.B), dim3(256), 0, s, si, buf.raw, nullptr, nullptr,
+                       d.B, d.T, d.Tp, d.F, d.FP, d.lens);
+    hipLaunchKernelGGL(fe_frame_kernel, dim3(d.Tp, d.B, 1), dim3(64), 0, s, buf.raw, buf.frame, d.B, d.Tp, d.F, d.FP);
+    hipLaunchKernelGGL(fe_scan_stream_kernel, dim3(cdiv(d.B, 64)), dim3(64), 0, s, buf.frame, buf.md, meta, sums, sum_stride, d.B, d.Tp,
+                       d.F, norm_type);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Stage-level entry (fsnp_channel_attention): ONE branch's channel attention on a caller's [B, F, T] tensor, as the reference calls the
 // submodule - `self.channel_attention(fb_input)` (fullsubnet_plus.py:160-165; ChannelTimeSenseSELayer.forward attention_model.py:78-101,

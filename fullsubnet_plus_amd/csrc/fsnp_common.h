@@ -113,6 +113,18 @@ void launch_frontend(const Dims& d, int norm_type, const float* const in[3], con
 void launch_frontend_mag(const Dims& d, int norm_type, const float* mag, const int64_t strides[3], bool is_complex,
                          const FrontendBuffers& buf, hipStream_t s);
 
+// streaming (include/fsnp_stream.h): per-slot push facts in the workspace, written by the push's prologue kernel
+struct StreamMeta { long long p; int cnt, pad; };      // frames the slot had before this push, frames it gets now
+// launch_frontend_mag of one push: repack (frames >= cnt[slot] never read), per-frame sums, and the cumulative norm's (m_t, d_t) table
+// continued from the slot's carried fp64 sums (sums: slot 0's {sum, sum of squares}, sum_stride doubles between slots; updated)
+void launch_frontend_mag_stream(const Dims& d, int norm_type, const float* mag, const int64_t strides[3], const FrontendBuffers& buf,
+                                const StreamMeta* meta, double* sums, long sum_stride, hipStream_t s);
+// launch_subband_stats (cumulative norms) of one push: md_row[row][n] continued from the carried per-(slot, f) sums ([f][2] per slot)
+struct SubbandBuffers;
+struct RowDesc;
+void launch_subband_stats_stream(const Dims& d, int norm_type, const SubbandBuffers& buf, const RowDesc* rows, int num_rows,
+                                 const StreamMeta* meta, double* sums, long sum_stride, hipStream_t s);
+
 // ---------------------------------------------------------------------------------------------
 // tcn.hip : 8 x TCNBlock + ReLU + Linear + activation for the three full-band branches at once
 struct TcnWeights {
@@ -276,11 +288,19 @@ struct LstmArgs {
     unsigned long long* clk;   // one-tile-per-CU LSTM kernel (lstm.hip) only, optional (device memory, 8 words): workgroup 0 writes {s_memtime,
                                // s_memrealtime} when it starts into clk[0..1] and when it ends into clk[2..3]; every workgroup folds its duration into
                                // clk[4] (max, 100 MHz ticks), clk[5] (max, s_memtime ticks), clk[6] (min, 100 MHz ticks): fsnp_debug_launch_clock
+    // streaming (include/fsnp_stream.h; launch_lstm_stream, launch_lstm_generic_stream): rows[].valid holds the row's step count of this
+    // push (Tp = the push's n, the stride of every per-frame table), rows[].b the slot
+    float* st_sb;              // sub-band state of slot 0: [f][layer][h|c][H]
+    float* st_fb;              // full-band state of slot 0: [layer][h|c][H]
+    long st_stride;            // floats between the states of consecutive slots
 };
 
 struct LstmPlan { int num_tiles, ex, rows_per_slot_tile; };
 LstmPlan plan_lstm_tiles(int num_rows, int num_cus);
 void launch_lstm(const LstmWeights& w, const LstmArgs& a, hipStream_t s);
+// streaming: the row-tile kernel from the rows' carried state (a.st_sb), rows[].valid steps per row, 32 rows per tile (ex = 0)
+void launch_lstm_stream(const LstmWeights& w, const LstmArgs& a, hipStream_t s);
+bool lstm_stream_available(const LstmWeights& w);
 // lstm16.hip: the same decomposition on 16-row tiles (v_mfma_f32_16x16x4_f32): 4096 sequences per round of 256 workgroups
 void launch_lstm16(const LstmWeights& w, const LstmArgs& a, hipStream_t s);
 size_t lstm16_pack_floats(int H, int KX);
@@ -329,6 +349,9 @@ void lstm_fbv_pack_weights(int H, int NIN, const float* wih0, const float* whh0,
 void launch_lstm_generic(const LstmWeights& w, const LstmArgs& a, bool seq, hipStream_t s);
 size_t lstm_generic_pack_floats(int H, int NIN);
 void lstm_generic_pack_weights(int H, int NIN, const float* wih0, const float* whh0, const float* wih1, const float* whh1, float* out);
+// streaming: the seq kernel from the rows' carried state (a.st_fb), rows[].valid steps per row; commit-time check as lstm_generic_check
+void launch_lstm_generic_stream(const LstmWeights& w, const LstmArgs& a, hipStream_t s);
+int lstm_generic_stream_check(int H, int NIN);
 int lstm_generic_rows_per_group(int H, int NIN, int num_seq, int num_cus);   // 0 = the sizes do not fit a CU's LDS
 int lstm_generic_check(int H, int NIN, bool seq);   // commit time: LDS opt-in + residency of every instantiation; != 0 (error set) on failure
 // lstm_coopn.hip: 3 workgroups x 128 hidden units share 1-2 row tiles (43..170 row tiles)

@@ -416,7 +416,7 @@ int fsnp_commit_weights(fsnp_handle* h) {
     const int fsn_kp = (int)align_up(CH, 16), fsn_np = (int)align_up(F, 384);
     if (fsn) {
         const Rnn4 fbw = expand("fb_model.sequence_model.", CH, F);
-        if (h->generic_fb) {
+        if (h->generic_fb || !h->gru) {        // (LSTM: also what a stream session's full-band pushes run on - launch_lstm_generic_stream)
             o_fbgen = alloc(lstm_generic_pack_floats(CH, F));
             lstm_generic_pack_weights(CH, F, fbw.wih0.data(), fbw.whh0.data(), fbw.wih1.data(), fbw.whh1.data(), blob.data() + o_fbgen);
         }

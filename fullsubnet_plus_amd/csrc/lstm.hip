@@ -665,6 +665,230 @@ void launch_lstm(const LstmWeights& w, const LstmArgs& a, hipStream_t s) {
     }
 }
 
+// -------------------------------------------------------------------------------------------------
+// Streaming (include/fsnp_stream.h): lstm2_fc_kernel<HID, KX, 2, EX = 0, PROF = false, NW = 4, BF = false> - same LDS images, same weight
+// stream (LstmWeights::wpack), same k-group loops (mfma_groups<NT, 0>), same cells - as a kernel of its own, so that the whole-clip
+// instantiations stay byte for byte what they were.  What differs:
+//   * rows[].valid is the row's STEP COUNT of this push (Tp = the push's n is only the stride of the per-frame tables); the tile runs
+//     the largest count of its rows;
+//   * the rows' (h0, c0, h1, c1) enter and leave through the structures the kernel already has - c in lstm_cell's lane-local register
+//     pairs, h in the LDS A images - with lstm_cell's own (row, unit) mapping: a lane moves exactly the elements it updates, and per
+//     register 32 lanes cover 128 consecutive bytes of one row's vector of the kernel-independent state [slot][f][layer][h|c][HID];
+//   * a row's state is stored after its OWN last step (inside the time loop only in tiles whose rows end at different steps - a tile
+//     that straddles two slots with different counts; what such a row computes afterwards is never stored or written out);
+//   * output column t is step t (no look-ahead shift), written while t < the row's count.
+template <int ST, int UW, int HID, bool LOAD>
+__device__ __forceinline__ void stream_state_io(f32x2 (&c0)[ST][8], f32x2 (&c1)[ST][8], float* __restrict__ H0, float* __restrict__ H1,
+                                                const RowDesc* __restrict__ rows_s, float* __restrict__ state, long slot_stride, int done,
+                                                int wave, int lane) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const RowDesc rd = rows_s[row];
+        const bool on = LOAD ? rd.valid > 0 : rd.valid == done;
+        float* __restrict__ p = state + (size_t)rd.b * slot_stride + (size_t)rd.f * 4 * HID;
+#pragma unroll
+        for (int s = 0; s < ST; ++s) {
+            const int k = wave * UW + s * 32 + (lane & 31);
+            const int hi = (((k >> 3) * 64) + ((k & 1) * 32)) * 4 + ((k >> 1) & 3) + row * 4;
+            if constexpr (LOAD) {
+                H0[hi] = on ? p[k] : 0.0f;
+                c0[s][r >> 1][r & 1] = on ? p[HID + k] : 0.0f;
+                H1[hi] = on ? p[2 * HID + k] : 0.0f;
+                c1[s][r >> 1][r & 1] = on ? p[3 * HID + k] : 0.0f;
+            } else if (on) {
+                p[k] = H0[hi];
+                p[HID + k] = c0[s][r >> 1][r & 1];
+                p[2 * HID + k] = H1[hi];
+                p[3 * HID + k] = c1[s][r >> 1][r & 1];
+            }
+        }
+    }
+}
+
+template <int HID, int KX>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
+void lstm2_fc_stream_kernel(LstmWeights w, LstmArgs a) {
+    constexpr int NW = 4, NTHR = 256, OUT = 2;
+    constexpr int UW = HID / NW, ST = UW / 32, NT = 4 * ST;
+    constexpr int KGX = KX / 8, KGH = HID / 8, KG0 = KGX + KGH, KGT = KG0 + 2 * KGH;
+    static_assert(UW % 32 == 0 && KGH % 4 == 0, "hidden/4 must be a multiple of 32");
+
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    float4* Xs = reinterpret_cast<float4*>(smem_raw);   // [KGX][64]   A image of x_t
+    float4* H0s = Xs + KGX * 64;                         // [KGH][64]   h0
+    float4* H1s = H0s + KGH * 64;                        // [KGH][64]   h1
+    float4* Wfc4 = H1s + KGH * 64;                       // [OUT][KGH][2]
+    RowDesc* rows_s = reinterpret_cast<RowDesc*>(Wfc4 + OUT * KGH * 2);  // [32]
+    float* Bs = reinterpret_cast<float*>(rows_s + 32);                   // [2][NW][NT][32]
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int slot0 = blockIdx.x * 32;
+    const int Tp = a.Tp;
+
+    for (int i = tid; i < (KGX + 2 * KGH) * 64; i += NTHR) Xs[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int i = tid; i < OUT * KGH * 2; i += NTHR) {
+        const int o = i / (KGH * 2), kg = (i >> 1) % KGH, kh = i & 1;
+        const float* wr = w.wfc + (size_t)o * HID + kg * 8 + kh;
+        Wfc4[i] = make_float4(wr[0], wr[2], wr[4], wr[6]);
+    }
+    if (tid < 32) rows_s[tid] = a.rows[slot0 + tid];
+    for (int i = tid; i < 2 * NW * NT * 32; i += NTHR) {
+        const int col = i & 31, n = (i >> 5) % NT, wv = (i / (32 * NT)) % NW, layer = i / (32 * NT * NW);
+        Bs[i] = w.bias[layer * 4 * HID + (n / ST) * HID + wv * UW + (n % ST) * 32 + col];
+    }
+    __syncthreads();
+
+    // steps of this tile, and whether some row ends before the tile does (both uniform)
+    int nsteps = 0, cmin = 1 << 30;
+    for (int r = 0; r < 32; ++r) {
+        const int v = rows_s[r].valid;
+        nsteps = v > nsteps ? v : nsteps;
+        if (v > 0) cmin = v < cmin ? v : cmin;
+    }
+    nsteps = __builtin_amdgcn_readfirstlane(nsteps);
+    const bool mixed = __builtin_amdgcn_readfirstlane(cmin < nsteps ? 1 : 0) != 0;
+    if (nsteps <= 0) return;                                  // (uniform; the host never launches an empty tile)
+
+    // ---- gather plan: row = tid & 31, features j = (tid >> 5) + 8 i; 32-bit float offsets from att_mag; -1 = zero
+    constexpr int JSTEP = NTHR / 32, NG = (KX + JSTEP - 1) / JSTEP;
+    const int grow = tid & 31;
+    int goff[NG], xdst[NG];
+    const float* __restrict__ gbase = a.att_mag;
+    const int gstep = a.FP;
+    const NormMD* md_row;
+    {
+        const RowDesc rd = rows_s[grow];
+#pragma unroll
+        for (int i = 0; i < NG; ++i) {
+            const int j = (tid >> 5) + JSTEP * i;
+            goff[i] = j >= KX ? -2 : (rd.valid > 0 && j < w.NIN)
+                          ? sb_feature_offset(j, rd.f, rd.b * Tp * a.FP, a.F, a.NSBN, a.NFBN, a.fb_rel, a.fb_branch_stride) : -1;
+            xdst[i] = a_frag_index(grow, j < KX ? j : 0);
+        }
+        md_row = a.md_row + (size_t)(slot0 + grow) * Tp;      // (rows without steps: never dereferenced through goff >= 0)
+    }
+    float* Xf = reinterpret_cast<float*>(Xs);
+    {   // x(0)
+        const NormMD m0 = rows_s[grow].valid > 0 ? md_row[0] : NormMD{0.0f, 1.0f};
+#pragma unroll
+        for (int i = 0; i < NG; ++i)
+            if (goff[i] != -2) Xf[xdst[i]] = goff[i] >= 0 ? (gbase[goff[i]] - m0.m) / m0.d : 0.0f;
+    }
+
+    const float* __restrict__ bias_l0 = Bs + ((0 * NW + wave) * NT) * 32 + (lane & 31);
+    const float* __restrict__ bias_l1 = Bs + ((1 * NW + wave) * NT) * 32 + (lane & 31);
+    f32x2 c0[ST][8], c1[ST][8];
+    stream_state_io<ST, UW, HID, true>(c0, c1, reinterpret_cast<float*>(H0s), reinterpret_cast<float*>(H1s), rows_s, a.st_sb, a.st_stride, 0,
+                                       wave, lane);
+
+    WStream ws;
+    ws.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(w.wpack) + (size_t)wave * KGT * NT * 256, 0, KGT * NT * 1024, 0x00020000);
+    ws.voff = lane * 16;
+    float4 breg[NT];
+#pragma unroll
+    for (int n = 0; n < NT; ++n) breg[n] = wload<NT>(ws, 0, n);
+    int gnext = 1;
+    float accx[1][NT];                                        // (no VALU rows: mfma_groups<NT, 0> never touches it)
+    auto run_groups = [&](f32x16 (&acc_)[NT], const float4* A_, int ng) {
+        mfma_groups<NT, 0>(acc_, accx, breg, A_, A_, ng, ws, gnext, KGT);
+    };
+
+    // FC lane mapping: 8 rows x 2 outputs x 4 k-parts per wave
+    const int fc_row = (wave & 3) * 8 + (lane & 7);
+    const int fc_o = (lane >> 3) & 1;
+    const int fc_kp = lane >> 4;
+    const RowDesc fc_rd = rows_s[fc_row];
+    auto fc_store = [&](int t_of_h) {
+        constexpr int KGP = KGH / 4;
+        float sum = 0.0f;
+#pragma unroll 4
+        for (int kk = 0; kk < KGP; ++kk) {
+            const int kg = fc_kp * KGP + kk;
+#pragma unroll
+            for (int kh = 0; kh < 2; ++kh) {
+                const float4 h4 = H1s[kg * 64 + kh * 32 + fc_row];
+                const float4 w4 = Wfc4[(fc_o * KGH + kg) * 2 + kh];
+                sum += h4.x * w4.x + h4.y * w4.y + h4.z * w4.z + h4.w * w4.w;
+            }
+        }
+        sum += __shfl_xor(sum, 16);
+        sum += __shfl_xor(sum, 32);
+        if (fc_kp == 0 && t_of_h < fc_rd.valid)
+            a.out[(size_t)fc_rd.out_off + (size_t)fc_o * a.out_stride_o + t_of_h] = apply_act(sum + w.bfc[fc_o], a.act);
+    };
+
+    __syncthreads();
+
+    for (int t = 0; t < nsteps; ++t) {
+        // prefetch x(t+1) (consumed after the layer-0 MFMA phase); past a row's own count it reads the zeros / identity the push's
+        // repack and prefix kernels wrote there, and whatever the full-band stages left: that row's results are dropped
+        float xr[NG];
+        NormMD mdn = {0.0f, 1.0f};
+        const bool have_next = (t + 1 < nsteps);
+        if (have_next) {
+            if (rows_s[grow].valid > 0) mdn = md_row[t + 1];
+#pragma unroll
+            for (int i = 0; i < NG; ++i) xr[i] = goff[i] >= 0 ? gbase[goff[i] + (t + 1) * gstep] : 0.0f;
+        }
+
+        f32x16 acc[NT];
+        // ---------------- layer 0: [x_t | h0_{t-1}] ----------------
+#pragma unroll
+        for (int n = 0; n < NT; ++n)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[n][r] = bias_l0[n * 32];
+        run_groups(acc, Xs + lane, KG0);
+        __syncthreads();
+        lstm_cell<ST, UW>(acc, c0, reinterpret_cast<float*>(H0s), wave, lane);
+        if (have_next) {
+#pragma unroll
+            for (int i = 0; i < NG; ++i)
+                if (goff[i] != -2) Xf[xdst[i]] = goff[i] >= 0 ? (xr[i] - mdn.m) / mdn.d : 0.0f;
+        }
+        if (t > 0) fc_store(t - 1);
+        __syncthreads();
+        // ---------------- layer 1: [h1_{t-1} | h0_t] ----------------
+#pragma unroll
+        for (int n = 0; n < NT; ++n)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[n][r] = bias_l1[n * 32];
+        run_groups(acc, H1s + lane, KGH);
+        run_groups(acc, H0s + lane, KGH);
+        __syncthreads();
+        lstm_cell<ST, UW>(acc, c1, reinterpret_cast<float*>(H1s), wave, lane);
+        if (t + 1 == nsteps || mixed)
+            stream_state_io<ST, UW, HID, false>(c0, c1, reinterpret_cast<float*>(H0s), reinterpret_cast<float*>(H1s), rows_s, a.st_sb,
+                                                a.st_stride, t + 1, wave, lane);
+    }
+    __syncthreads();
+    fc_store(nsteps - 1);
+}
+
+template <int HID, int KX>
+static void launch_lstm_stream_one(const LstmWeights& w, const LstmArgs& a, hipStream_t s) {
+    constexpr int KGX = KX / 8, KGH = HID / 8, NT = 4 * (HID / 4 / 32);
+    const size_t smem = (size_t)(KGX + 2 * KGH) * 64 * 16 + (size_t)2 * KGH * 2 * 16 + 32 * sizeof(RowDesc) + (size_t)2 * 4 * NT * 32 * 4;
+    auto kern = lstm2_fc_stream_kernel<HID, KX>;
+    static PerDeviceOnce attr_once;
+    attr_once.run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); });
+    hipLaunchKernelGGL(kern, dim3(a.num_tiles), dim3(256), smem, s, w, a);
+}
+
+bool lstm_stream_available(const LstmWeights& w) {
+    return !w.gru && w.OUT == 2 && (w.H == 384 || w.H == 256) && (w.KX == 40 || w.KX == 64) && w.wpack != nullptr;
+}
+
+// a.rows: a.num_tiles * 32 row slots (valid = steps of the row in this push, b = slot); a.st_sb / a.st_stride: the carried state
+void launch_lstm_stream(const LstmWeights& w, const LstmArgs& a, hipStream_t s) {
+    if (a.num_tiles <= 0) return;
+    if (w.H == 256) { if (w.KX == 64) launch_lstm_stream_one<256, 64>(w, a, s); else launch_lstm_stream_one<256, 40>(w, a, s); }
+    else if (w.KX == 64) launch_lstm_stream_one<384, 64>(w, a, s);
+    else launch_lstm_stream_one<384, 40>(w, a, s);
+}
+
 // Tile plan: a tile = 32 MFMA rows + up to ex VALU rows.  All tiles cost the same time whatever their
 // row count, so the makespan is rounds = ceil(tiles / CUs); pick the smallest ex in {0,1,2,4} that
 // minimises rounds, then spread the rows evenly over rounds * CUs tiles.

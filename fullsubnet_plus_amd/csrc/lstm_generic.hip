@@ -35,8 +35,11 @@ inline size_t gen_smem_floats(int RG, int H, int NIN) { return (size_t)RG * (gen
 // 1024 threads: the kernel is bound by the latency of its weight stream (every column reads K weights from L2 per step) and LDS
 // allows one workgroup per CU, so the workgroup itself brings the 16 waves that hide it.
 constexpr int kGenThreads = 1024;
-template <int RG, bool SEQ>
-__global__ __launch_bounds__(kGenThreads) void lstm2_generic_kernel(LstmWeights w, LstmArgs a) {
+// STREAM (include/fsnp_stream.h, SEQ only): h0, h1, c0, c1 of the rows start from the carried state a.st_fb ([slot = row.b][layer][h|c][H]),
+// row r runs rows[r].valid steps (its cell update and its output stop there; the workgroup runs the largest count of its rows) and
+// the state is written back at the end.
+template <int RG, bool SEQ, bool STREAM>
+__device__ __forceinline__ void lstm2_generic_body(const LstmWeights& w, const LstmArgs& a) {
     constexpr int NTHR = kGenThreads;
     extern __shared__ __attribute__((aligned(16))) float gsm[];
     const int H = w.H, NIN = w.NIN, OUT = w.OUT, G4 = 4 * H;
@@ -56,6 +59,18 @@ __global__ __launch_bounds__(kGenThreads) void lstm2_generic_kernel(LstmWeights 
     if (tid < RG) rows_s[tid] = a.rows[slot0 + tid];
     for (int i = tid; i < RG * (NINP + 8 * HP); i += NTHR) gsm[i] = 0.0f;
     __syncthreads();
+    int nsteps = Tp;
+    if constexpr (STREAM) {
+        nsteps = 0;
+        for (int r = 0; r < RG; ++r) nsteps = rows_s[r].valid > nsteps ? rows_s[r].valid : nsteps;
+        for (int i = tid; i < RG * 4 * H; i += NTHR) {               // state vector q of row r: h0, c0, h1, c1
+            const int r = i / (4 * H), q = (i / H) % 4, u = i % H;
+            const RowDesc rd = rows_s[r];
+            float* dst = q == 0 ? h0 : q == 1 ? c0 : q == 2 ? h1 : c1;
+            if (rd.valid > 0) dst[r * HP + u] = a.st_fb[(size_t)rd.b * a.st_stride + q * H + u];
+        }
+        __syncthreads();
+    }
 
     const bool dense = a.dense != nullptr;
     const float* __restrict__ gbase = dense ? a.dense : a.att_mag;
@@ -99,6 +114,7 @@ __global__ __launch_bounds__(kGenThreads) void lstm2_generic_kernel(LstmWeights 
             for (int r = 0; r < RG; ++r) acc[r] = fmaf(wv, op[r * ld + k], acc[r]);
         }
     };
+    int tcur = 0;
     // one layer: pre = bias + W [opA | opB], then the cell update of every (row, unit) into (c, h)
     auto layer = [&](const float* wT, const float* bias, const float* opA, int ldA, int KA, const float* opB, int KB, float* c, float* h) {
         for (int col = tid; col < G4; col += NTHR) {
@@ -114,6 +130,7 @@ __global__ __launch_bounds__(kGenThreads) void lstm2_generic_kernel(LstmWeights 
         __syncthreads();
         for (int i = tid; i < RG * H; i += NTHR) {
             const int r = i / H, u = i % H;
+            if (STREAM && tcur >= rows_s[r].valid) continue;       // this row's steps are over: its state stays
             const float* p = pre + r * 4 * HP;
             float hv;
             if (gru) {           // r = s(a_r), z = s(a_z), n = tanh(a_nx + r a_nh), h' = (1 - z) n + z h      (torch.nn.GRU)
@@ -131,13 +148,14 @@ __global__ __launch_bounds__(kGenThreads) void lstm2_generic_kernel(LstmWeights 
         __syncthreads();
     };
 
-    for (int t = 0; t < Tp; ++t) {
+    for (int t = 0; t < nsteps; ++t) {
+        tcur = t;
         // ---- x_t of the RG rows, normalised
         for (int i = tid; i < RG * NIN; i += NTHR) {
             const int r = i / NIN, j = i % NIN;
             const RowDesc rd = rows_s[r];
             float v = 0.0f;
-            if (rd.valid) {
+            if (STREAM ? t < rd.valid : rd.valid != 0) {
                 NormMD md = {0.0f, 1.0f};
                 if (a.md_seq != nullptr) md = a.md_seq[(size_t)rd.b * Tp + t];
                 else if (!dense && a.md_row != nullptr) md = a.md_row[(size_t)(slot0 + r) * Tp + t];
@@ -156,7 +174,7 @@ __global__ __launch_bounds__(kGenThreads) void lstm2_generic_kernel(LstmWeights 
             for (int i = tid; i < RG * ss; i += NTHR) {
                 const int r = i / ss, u = i % ss;
                 const RowDesc rd = rows_s[r];
-                if (rd.valid) a.seq_out[((size_t)rd.b * Tp + t) * ss + u] = u < H ? h1[r * HP + u] : 0.0f;
+                if (STREAM ? t < rd.valid : rd.valid != 0) a.seq_out[((size_t)rd.b * Tp + t) * ss + u] = u < H ? h1[r * HP + u] : 0.0f;
             }
         } else {
             for (int item = wave; item < RG * OUT; item += NTHR / 64) {        // Linear(H, OUT): a wave per (row, output), K across the lanes
@@ -173,6 +191,23 @@ __global__ __launch_bounds__(kGenThreads) void lstm2_generic_kernel(LstmWeights 
         // (the next step's first write to h1 / xs is behind the barriers of its own layers; xs is rewritten right away, but its
         //  last readers - layer 0 - are two barriers back)
     }
+    if constexpr (STREAM) {
+        for (int i = tid; i < RG * 4 * H; i += NTHR) {               // (every layer ends with a barrier: the state is final)
+            const int r = i / (4 * H), q = (i / H) % 4, u = i % H;
+            const RowDesc rd = rows_s[r];
+            const float* src = q == 0 ? h0 : q == 1 ? c0 : q == 2 ? h1 : c1;
+            if (rd.valid > 0) a.st_fb[(size_t)rd.b * a.st_stride + q * H + u] = src[r * HP + u];
+        }
+    }
+}
+
+template <int RG, bool SEQ>
+__global__ __launch_bounds__(kGenThreads) void lstm2_generic_kernel(LstmWeights w, LstmArgs a) {
+    lstm2_generic_body<RG, SEQ, false>(w, a);
+}
+template <int RG>
+__global__ __launch_bounds__(kGenThreads) void lstm2_generic_stream_kernel(LstmWeights w, LstmArgs a) {
+    lstm2_generic_body<RG, true, true>(w, a);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -256,6 +291,56 @@ int lstm_generic_check(int H, int NIN, bool seq) {
         return 2;
     }
     return 0;
+}
+
+template <int RG>
+static hipError_t generic_stream_prepare(size_t smem) {
+    auto k = lstm2_generic_stream_kernel<RG>;
+    static PerDeviceOnce once;
+    static hipError_t attr_err[64] = {};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const int di = dev >= 0 && dev < 64 ? dev : 0;
+    once.run([&] { attr_err[di] = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024); });
+    if (attr_err[di] != hipSuccess) return attr_err[di];
+    if (smem == 0) return hipSuccess;
+    int blocks = 0;
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, reinterpret_cast<const void*>(k), kGenThreads, smem);
+    if (e != hipSuccess) return e;
+    return blocks >= 1 ? hipSuccess : hipErrorLaunchOutOfResources;
+}
+
+// session-creation check of the streaming instantiations (as lstm_generic_check at commit)
+int lstm_generic_stream_check(int H, int NIN) {
+    hipError_t e = hipSuccess;
+    for (int rg = 1; rg <= 8 && e == hipSuccess; rg *= 2) {
+        const size_t smem = gen_smem_floats(rg, H, NIN) * 4;
+        if (smem > (size_t)150 * 1024) continue;
+        e = rg == 8 ? generic_stream_prepare<8>(smem) : rg == 4 ? generic_stream_prepare<4>(smem) : rg == 2 ? generic_stream_prepare<2>(smem)
+                                                                                                          : generic_stream_prepare<1>(smem);
+    }
+    if (e != hipSuccess) {
+        set_error("streaming full-band kernel (hidden %d, %d inputs): a 1024-thread workgroup with its LDS does not fit a CU of this device: %s",
+                  H, NIN, hipGetErrorString(e));
+        return 2;
+    }
+    return 0;
+}
+
+template <int RG>
+static void launch_generic_stream_rg(const LstmWeights& w, const LstmArgs& a, hipStream_t s) {
+    if (generic_stream_prepare<RG>(0) != hipSuccess) set_error("lstm_generic: LDS opt-in of the streaming kernel failed on this device");
+    hipLaunchKernelGGL((lstm2_generic_stream_kernel<RG>), dim3(a.num_tiles), dim3(kGenThreads), gen_smem_floats(RG, w.H, w.NIN) * 4, s, w, a);
+}
+
+void launch_lstm_generic_stream(const LstmWeights& w, const LstmArgs& a, hipStream_t s) {
+    if (a.num_tiles <= 0) return;
+    switch (a.coop_rows_per_group) {
+        case 8: launch_generic_stream_rg<8>(w, a, s); break;
+        case 4: launch_generic_stream_rg<4>(w, a, s); break;
+        case 2: launch_generic_stream_rg<2>(w, a, s); break;
+        default: launch_generic_stream_rg<1>(w, a, s); break;
+    }
 }
 
 // a.num_tiles workgroups of a.coop_rows_per_group (1, 2, 4 or 8) sequences each; a.rows holds num_tiles * rows-per-group slots

@@ -146,6 +146,49 @@ void launch_subband_stats(const Dims& d, int norm_type, const SubbandBuffers& bu
     }
 }
 
+// ---- streaming (include/fsnp_stream.h): sb_cumulative_kernel of one push, continued from the carried sums of the row's (slot, f).
+// One thread per sub-band row, serial over the push's frames (neighbouring threads read neighbouring bins: coalesced): the entry count of
+// step t is nin * (P + t + 1), the sums stay fp64 and are added frame by frame whatever the chunking.  rows[].valid = frames of this push.
+__global__ __launch_bounds__(256) void sb_cumulative_stream_kernel(const float* __restrict__ att_mag, const float* __restrict__ fb, long fb_bs,
+                                                                   const RowDesc* __restrict__ rows, NormMD* __restrict__ md_row,
+                                                                   const StreamMeta* __restrict__ meta, double* __restrict__ sums,
+                                                                   long sum_stride, int num_rows, int n, int F, int FP, int nsbn, int nfbn,
+                                                                   int nin, int norm_type) {
+    const int row = blockIdx.x * 256 + threadIdx.x;
+    if (row >= num_rows) return;
+    const RowDesc rd = rows[row];
+    if (rd.valid <= 0) return;
+    const long long p0 = meta[rd.b].p;
+    double* sm = sums + (long)rd.b * sum_stride + 2 * rd.f;
+    double s = sm[0], q = sm[1];
+    const int nsb = 2 * nsbn + 1;
+    for (int t = 0; t < n; ++t) {
+        if (t >= rd.valid) { md_row[(long)row * n + t] = NormMD{0.0f, 1.0f}; continue; }
+        const long base = ((long)rd.b * n + t) * FP;
+        double fs = 0.0, fq = 0.0;
+        for (int j = 0; j < nsb; ++j) {
+            const double v = att_mag[base + reflect_index(rd.f - nsbn + j, F)];
+            fs += v; fq += v * v;
+        }
+        for (int j = nsb; j < nin; ++j) {
+            const double v = att_mag[sb_feature_offset(j, rd.f, 0, F, nsbn, nfbn, (int)(fb - att_mag), (int)fb_bs) + base];
+            fs += v; fq += v * v;
+        }
+        s += fs; q += fq;
+        md_row[(long)row * n + t] = sb_norm_md(norm_type, s, q, (double)nin * (double)(p0 + t + 1));
+    }
+    sm[0] = s; sm[1] = q;
+}
+
+// d: B = slots, Tp = the push's n
+void launch_subband_stats_stream(const Dims& d, int norm_type, const SubbandBuffers& buf, const RowDesc* rows, int num_rows,
+                                 const StreamMeta* meta, double* sums, long sum_stride, hipStream_t s) {
+    if (num_rows <= 0) return;
+    hipLaunchKernelGGL(sb_cumulative_stream_kernel, dim3(cdiv(num_rows, 256)), dim3(256), 0, s, buf.att_mag, buf.fb,
+                       (long)d.B * d.Tp * d.FP, rows, buf.md_row, meta, sums, sum_stride, num_rows, d.Tp, d.F, d.FP, (d.NSB - 1) / 2,
+                       buf.NFBN, d.NIN, norm_type);
+}
+
 // ---- sequence_model="TCN" (sequence_model.py:47-58): the sub-band model is a TCN stack over [N, 34, T'], so the
 // sub-band input of fullsubnet_plus.py:167-202 IS materialised here, time-major [slot][t][xstride], normalised.
 __global__ __launch_bounds__(256) void sb_gather_kernel(SbGatherArgs a) {

@@ -1031,6 +1031,11 @@ class FullSubNet_Plus(_HipModel):
         return self._checked(lambda: self._forward_impl([noisy_mag, noisy_real, noisy_imag], batch_offset, global_batch, lengths=lengths),
                              noisy_mag.device)
 
+    def open_stream(self, slots, max_chunk=16, device="cuda"):
+        """FullSubNet+ is not streamable (see fullsubnet_plus_amd.stream): always raises NotImplementedError with the reason."""
+        from .stream import PLUS_REASON
+        raise NotImplementedError(f"{self.__class__.__name__}.open_stream: {PLUS_REASON}")
+
 
 class _FullBandLSTMParams(_StageHolder):
     """Parameter holder named like SequenceModel(sequence_model="LSTM") of the original FullSubNet's full-band model
@@ -1116,6 +1121,17 @@ class FullSubNet(_HipModel):
         """noisy_mag [B, 1, F, T] fp32 CUDA tensor (any strides) -> cIRM [B, 2, F, T] (see FullSubNet_Plus.forward
         for batch_mode, the sharding arguments and lengths)."""
         return self._checked(lambda: self._forward_impl([noisy_mag], batch_offset, global_batch, lengths=lengths), noisy_mag.device)
+
+    def open_stream(self, slots, max_chunk=16, device="cuda"):
+        """-> fullsubnet_plus_amd.stream.Stream: `slots` independent live streams that are fed a few frames per push and carry the
+        recurrent state and the cumulative norms' sums between pushes (include/fsnp_stream.h).  A clip pushed in any chunking, followed
+        by tail(), gives forward()'s mask of that clip delayed by look_ahead columns.  Needs a cumulative norm and LSTM cells
+        (NotImplementedError with the reason otherwise, before any GPU is touched)."""
+        from .stream import Stream, refusal
+        why = refusal(self)
+        if why is not None:
+            raise NotImplementedError(f"{self.__class__.__name__}.open_stream: {why}")
+        return Stream(self, slots, max_chunk, _resolve_device(device))
 
 
 Model = FullSubNet_Plus  # the name BASELINE.json's north_star uses

@@ -1,0 +1,199 @@
+"""Stream sessions of the original FullSubNet (include/fsnp_stream.h): chunked forwards that carry their state.
+
+    stream = model.open_stream(slots=8, max_chunk=16)
+    mask = stream.push(noisy_mag)            # [8, 1, F, n] -> [8, 2, F, n]; column j = cIRM of frame P + j - look_ahead
+    ...
+    mask = stream.tail()                     # look_ahead zero frames: the masks of the last look_ahead frames
+"""
+import ctypes
+
+import torch
+
+from . import _lib
+
+PLUS_REASON = ("FullSubNet+ cannot be streamed exactly: its full-band TCN blocks are not causal and normalise with GroupNorm(1, C) over "
+               "the whole clip, and TSSE pools over all of time; stream the original FullSubNet (fullsubnet_plus_amd.FullSubNet) with a "
+               "cumulative norm")
+
+
+def refusal(model):
+    """Why `model` (a FullSubNet) cannot be streamed, or None.  Decided from the constructor arguments alone: no GPU is touched."""
+    if model.norm_type not in ("cumulative_laplace_norm", "cumulative_layer_norm"):
+        return (f"norm_type {model.norm_type!r} needs the whole clip's total; streaming needs cumulative_laplace_norm or "
+                "cumulative_layer_norm")
+    if model.sequence_model != "LSTM":
+        return f"sequence_model {model.sequence_model!r} is not built for streaming (LSTM only)"
+    nin = (model.sb_num_neighbors * 2 + 1) + (model.fb_num_neighbors * 2 + 1)
+    if model.sb_model_hidden_size not in (256, 384) or nin > 64:
+        return (f"sb_model_hidden_size {model.sb_model_hidden_size} with {nin} sub-band inputs is outside the row-tile kernel "
+                "(hidden 256 / 384, <= 64 inputs): not built for streaming")
+    return None
+
+
+class Stream:
+    """`slots` independent live streams on one FullSubNet (FullSubNet.open_stream).  Everything runs on the current CUDA stream; a push
+    allocates nothing but its output tensor and never synchronises (under the model's error_check="sync" it then waits and polls, as
+    forward does)."""
+
+    def __init__(self, model, slots, max_chunk, device):
+        why = refusal(model)
+        if why is not None:
+            raise NotImplementedError(f"{model.__class__.__name__}.open_stream: {why}")
+        self.model, self.slots, self.max_chunk, self.device = model, int(slots), int(max_chunk), device
+        self.look_ahead, self.num_freqs = model.look_ahead, model.num_freqs
+        self._lib = model._ensure_handle(device)
+        self._owner = model._hip.handle.value
+        sp = ctypes.c_void_p()
+        with torch.cuda.device(device):
+            _lib.check(self._lib.fsnp_stream_create(model._hip.handle, self.slots, self.max_chunk, ctypes.byref(sp)), "fsnp_stream_create")
+        self._st = sp
+        self.state_bytes = int(self._lib.fsnp_stream_state_bytes(sp))
+        self._backup = None
+
+    # ------------------------------------------------------------------ plumbing
+    def _session(self):
+        if self._st is None:
+            raise RuntimeError("this stream is closed")
+        h = self.model._hip.handle
+        if h is None or h.value != self._owner:
+            raise RuntimeError("the model's HIP handle was re-created (device change or copy) since open_stream: open a new stream")
+        return self._st
+
+    def _cuda_stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def close(self):
+        st, self._st = self._st, None
+        h = self.model._hip.handle
+        if st is not None and h is not None and h.value == self._owner:      # (a destroyed handle took nothing of the session with it)
+            with torch.cuda.device(self.device):
+                self._lib.fsnp_stream_destroy(st)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    # ------------------------------------------------------------------ the session
+    def push(self, noisy_mag, counts=None):
+        """noisy_mag [slots, 1, F, n] fp32 CUDA tensor (any strides), n <= max_chunk; counts: None (n frames for every slot) or frames
+        per slot (a Python sequence or a CPU integer tensor, 0 <= counts[b] <= n; input past counts[b] is never read) -> [slots, 2, F, n]:
+        column j < counts[b] of slot b is the model's output of step P + j (the cIRM of frame P + j - look_ahead; exactly 0 while
+        P + j < look_ahead), columns >= counts[b] are exactly 0."""
+        st = self._session()
+        assert noisy_mag.dim() == 4 and noisy_mag.shape[1] == 1, f"{self.model.__class__.__name__} takes the mag feature as inputs."
+        S, _, F, n = noisy_mag.shape
+        assert S == self.slots, f"expected {self.slots} slots, got {S}"
+        assert F == self.num_freqs, f"expected {self.num_freqs} frequency bins, got {F}"
+        if not noisy_mag.is_cuda:
+            raise RuntimeError("fullsubnet_plus_amd runs on MI355X (HIP) only; move the model and inputs to 'cuda'. "
+                               "There is deliberately no CPU fallback.")
+        assert noisy_mag.device == self.device
+        x = noisy_mag if noisy_mag.dtype == torch.float32 else noisy_mag.float()
+        cnt = None if counts is None else _lib_counts(counts, S)
+        sb, _, sf, stt = x.stride()
+        strides = (ctypes.c_int64 * 3)(sb, sf, stt)
+        model, lib = self.model, self._lib
+        sync = model.error_check == "sync"
+
+        def run():
+            out = torch.empty((S, 2, F, n), dtype=torch.float32, device=self.device)
+            for attempt in (0, 1):
+                with torch.cuda.device(self.device):
+                    rc = lib.fsnp_stream_push(st, x.data_ptr(), ctypes.byref(strides), cnt, out.data_ptr(), n, self._cuda_stream())
+                if rc != _lib.ERR_STALE_WEIGHTS or attempt:
+                    break
+                model._stale_weights_noticed(self.device)      # the watch flagged an EARLIER call: re-pack, say so, run this push
+            _lib.check(rc, "fsnp_stream_push")
+            return out
+
+        if not sync:
+            return run()
+        # error_check="sync": a push whose weight watch fires ran on the OLD weights and has advanced the state; keep what it started from
+        watched = model.__dict__.get("_fsnp_watched", False)
+        if watched:
+            self._save_states()
+        out = run()
+        torch.cuda.current_stream(self.device).synchronize()
+        rc = lib.fsnp_poll_errors(model._handle)
+        if rc == _lib.ERR_STALE_WEIGHTS and watched:
+            self._restore_states()
+            model._hip.packed_key = None
+            model._ensure_handle(self.device)
+            out = run()
+            torch.cuda.current_stream(self.device).synchronize()
+            rc = lib.fsnp_poll_errors(model._handle)
+        _lib.check(rc, "fsnp_stream_push")
+        return out
+
+    def _save_states(self):
+        if self._backup is None:
+            self._backup = torch.empty((self.slots, self.state_bytes), dtype=torch.uint8, device=self.device)
+        for b in range(self.slots):
+            with torch.cuda.device(self.device):
+                _lib.check(self._lib.fsnp_stream_get_state(self._st, b, self._backup[b].data_ptr(), self._cuda_stream()), "fsnp_stream_get_state")
+
+    def _restore_states(self):
+        for b in range(self.slots):
+            with torch.cuda.device(self.device):
+                _lib.check(self._lib.fsnp_stream_set_state(self._st, b, self._backup[b].data_ptr(), self._cuda_stream()), "fsnp_stream_set_state")
+
+    def tail(self, slots=None):
+        """Push look_ahead all-zero frames (the reference's own pad) into `slots` (None: all): the masks of the last look_ahead frames.
+        -> [slots, 2, F, look_ahead] (an empty tensor for look_ahead = 0)."""
+        la = self.look_ahead
+        if la == 0:
+            return torch.zeros((self.slots, 2, self.num_freqs, 0), dtype=torch.float32, device=self.device)
+        if la > self.max_chunk:
+            raise ValueError(f"tail: look_ahead {la} > max_chunk {self.max_chunk}")
+        zeros = torch.zeros((self.slots, 1, self.num_freqs, la), dtype=torch.float32, device=self.device)
+        counts = None if slots is None else [la if b in set(int(v) for v in slots) else 0 for b in range(self.slots)]
+        return self.push(zeros, counts)
+
+    def reset(self, slots=None):
+        """Stream-ordered zeroing of the state of `slots` (None: all): the next push starts a fresh clip there."""
+        st = self._session()
+        if slots is None:
+            arr, num = None, 0
+        else:
+            vals = [int(v) for v in slots]
+            arr, num = (ctypes.c_int32 * max(len(vals), 1))(*vals), len(vals)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.fsnp_stream_reset(st, arr, num, self._cuda_stream()), "fsnp_stream_reset")
+
+    def state(self, slot):
+        """-> torch.uint8 CUDA tensor [state_bytes]: the slot's whole state (kernel-independent layout, include/fsnp_stream.h)."""
+        st = self._session()
+        buf = torch.empty(self.state_bytes, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.fsnp_stream_get_state(st, int(slot), buf.data_ptr(), self._cuda_stream()), "fsnp_stream_get_state")
+        return buf
+
+    def load_state(self, slot, tensor):
+        """Load what state() of a slot of any session of a model of the same sizes returned."""
+        st = self._session()
+        if tensor.dtype != torch.uint8 or tensor.numel() != self.state_bytes:
+            raise ValueError(f"load_state: expected a torch.uint8 tensor of {self.state_bytes} bytes, got {tensor.dtype} x {tensor.numel()}")
+        t = tensor.to(self.device).contiguous()
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.fsnp_stream_set_state(st, int(slot), t.data_ptr(), self._cuda_stream()), "fsnp_stream_set_state")
+
+    def frames(self, slot):
+        """Frames pushed into `slot` since its last reset (host-side count; after load_state the first call waits for that copy)."""
+        st = self._session()
+        v = ctypes.c_int64()
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.fsnp_stream_frames(st, int(slot), ctypes.byref(v)), "fsnp_stream_frames")
+        return int(v.value)
+
+
+def _lib_counts(counts, slots):
+    from .model import _host_lengths
+    return _host_lengths(counts, slots, "Stream.push")

@@ -45,6 +45,40 @@ def analyse(flags=("-fno-slp-vectorize",)):
     return res
 
 
+def analyse_stream(text=None, flags=("-fno-slp-vectorize",)):
+    """lstm2_fc_stream_kernel (lstm.hip; the streaming instantiations of the row-tile kernel), per instantiation: the same k-group loop
+    facts as analyse() - to be compared with the whole-clip instantiation KX.._EX0_PROF0_NW4_BF0 of the same sizes - and where the
+    kernel's scratch accesses are (none may sit inside a k-group loop)."""
+    if text is None:
+        with tempfile.TemporaryDirectory() as td:
+            out = os.path.join(td, "lstm.s")
+            subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", *flags, "-S", "--cuda-device-only", SRC, "-o", out],
+                           check=True, capture_output=True)
+            text = open(out).read()
+    res = {}
+    for m in re.finditer(r"^(_ZN4fsnp22lstm2_fc_stream_kernelI\w+):[^\n]*\n(.*?)s_endpgm", text, re.S | re.M):
+        name, body = m.group(1), m.group(2).split("\n")
+        tag = re.search(r"Li(\d+)ELi(\d+)E", name)
+        key = (f"H{tag.group(1)}_" if tag.group(1) != "384" else "") + f"KX{tag.group(2)}_STREAM"
+        loops = []
+        for i, l in enumerate(body):
+            if "Inner Loop Header: Depth=2" not in l:
+                continue
+            lab = None
+            for k in range(i, max(i - 4, 0), -1):
+                mm = re.match(r"^(\.LBB\d+_\d+):", body[k])
+                if mm:
+                    lab = mm.group(1)
+                    break
+            end = next(k for k in range(i, len(body)) if re.search(r"s_cbranch_\w+ " + re.escape(lab) + r"\b", body[k]))
+            seg = body[i:end]
+            cnt = lambda pat: sum(1 for x in seg if re.search(pat, x))
+            loops.append(dict(mfma=cnt(r"v_mfma"), scratch=cnt(r"scratch_"), drain=cnt(r"vmcnt\(0\)"),
+                              gload=cnt(r"global_load_dwordx4|buffer_load_dwordx4"), valu=cnt(r"\bv_fma|\bv_fmac"), lines=len(seg)))
+        res[key] = dict(loops=[l for l in loops if l["mfma"] > 0], scratch_total=sum(1 for x in body if "scratch_" in x))
+    return res
+
+
 def analyse_column_split(flags=("-fno-slp-vectorize",)):
     """Whole-kernel invariants of the column-split kernels (lstm_coop.hip, lstm_coopn.hip), per instantiation:
     scratch accesses from the first MFMA on (i.e. inside the time loop), flat accesses (reported only), cache-maintenance
@@ -242,6 +276,10 @@ if __name__ == "__main__":
         print(k, v)
     for k, loops in analyse_half_tile().items():
         for l in loops:
+            print(k, l)
+    for k, v in analyse_stream().items():
+        print(k, "scratch accesses in the whole kernel:", v["scratch_total"])
+        for l in v["loops"]:
             print(k, l)
     r = analyse()
     bad = 0

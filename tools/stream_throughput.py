@@ -1,0 +1,76 @@
+"""What streaming the original FullSubNet costs: time per push for S slots x n frames per push on one MI355X, next to the whole-clip
+forward of the same S clips of 2 s measured in the same run on the unchanged offline path.
+
+For every S in --slots and n in --chunks: median time per push (each timed run = --pushes pushes after a warm-up, median of --runs
+runs), streams served in real time (= 16 ms * n / time per push * S; a frame is 16 ms of audio at hop 256 / 16 kHz) and the cost per
+frame relative to forward(..., lengths=None) of the S clips.  Prints one JSON line per cell and one for each offline forward.  Not part
+of bench.py.
+
+    python tools/stream_throughput.py [--slots 1 8 32 64] [--chunks 1 4 16 64] [--runs 5] [--pushes 8]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from fullsubnet_plus_amd import FullSubNet  # noqa: E402
+from fullsubnet_plus_amd.synthetic import FULLSUBNET_MODEL_ARGS, make_inputs, make_state_dict_fullsubnet  # noqa: E402
+
+FRAME_MS = 16.0
+
+
+def timed(fn, runs):
+    fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(runs):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        out.append(time.perf_counter() - t0)
+    return statistics.median(out)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--slots", type=int, nargs="+", default=[1, 8, 32, 64])
+    ap.add_argument("--chunks", type=int, nargs="+", default=[1, 4, 16, 64])
+    ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--pushes", type=int, default=8)
+    a = ap.parse_args()
+
+    model = FullSubNet(**dict(FULLSUBNET_MODEL_ARGS, norm_type="cumulative_laplace_norm"))
+    model.load_state_dict(make_state_dict_fullsubnet(0, "default"), strict=True)
+    model = model.to("cuda").eval()
+    model.batch_mode = "full"
+    model.error_check = "deferred"
+
+    with torch.no_grad():
+        for S in a.slots:
+            mag = make_inputs(S, 2.0, 3)[0].contiguous().cuda()          # [S, 1, F, 126]
+            T = mag.shape[-1]
+            off = timed(lambda: model(mag), a.runs)
+            off_frame = off / T
+            print(json.dumps({"slots": S, "offline_frames": T, "offline_ms": round(off * 1e3, 3), "offline_us_per_frame": round(off_frame * 1e6, 2)}))
+            for n in a.chunks:
+                x = mag[..., :n].contiguous() if n <= T else mag.repeat(1, 1, 1, (n + T - 1) // T)[..., :n].contiguous()
+                with model.open_stream(S, max_chunk=n) as st:
+                    def run():
+                        for _ in range(a.pushes):
+                            st.push(x)
+                    per_push = timed(run, a.runs) / a.pushes
+                print(json.dumps({"slots": S, "chunk": n, "ms_per_push": round(per_push * 1e3, 4),
+                                  "us_per_frame": round(per_push / n * 1e6, 2),
+                                  "real_time_streams": round(FRAME_MS * 1e-3 * n / per_push * S, 1),
+                                  "per_frame_vs_offline": round(per_push / n / off_frame, 3)}))
+    model.check_errors()
+
+
+if __name__ == "__main__":
+    main()
