@@ -124,6 +124,20 @@ STREAM_SYMBOLS = {
     "fsnp_stream_frames": (c_i32, [c_vp, c_i32, ctypes.POINTER(c_i64)]),
 }
 
+# every symbol include/fsnp_wave_stream.h declares (waveform sessions: samples in, samples out; same ABI version)
+WAVE_STREAM_SYMBOLS = {
+    "fsnp_wave_stream_create": (c_i32, [c_vp, c_i32, c_i32, ctypes.POINTER(c_vp)]),
+    "fsnp_wave_stream_destroy": (None, [c_vp]),
+    "fsnp_wave_stream_push": (c_i32, [c_vp, c_vp, c_i64, ctypes.POINTER(c_i32), c_vp, c_i64, c_i32, c_vp]),
+    "fsnp_wave_stream_finish": (c_i32, [c_vp, ctypes.POINTER(c_i32), c_i32, c_vp, c_i64, c_vp]),
+    "fsnp_wave_stream_reset": (c_i32, [c_vp, ctypes.POINTER(c_i32), c_i32, c_vp]),
+    "fsnp_wave_stream_delay": (c_i32, [c_vp]),
+    "fsnp_wave_stream_state_bytes": (c_i64, [c_vp]),
+    "fsnp_wave_stream_get_state": (c_i32, [c_vp, c_i32, c_vp, c_vp]),
+    "fsnp_wave_stream_set_state": (c_i32, [c_vp, c_i32, c_vp, c_vp]),
+    "fsnp_wave_stream_samples": (c_i32, [c_vp, c_i32, ctypes.POINTER(c_i64)]),
+}
+
 ABI_VERSION = 13         # FSNP_ABI_VERSION of the include/fsnp.h these signatures were written against
 
 _lib = None
@@ -145,7 +159,7 @@ def load(build_if_missing=True):
     if not os.path.exists(path):
         raise RuntimeError(f"{path} is missing: run `python -m fullsubnet_plus_amd._build`")
     lib = ctypes.CDLL(path)
-    for name, (res, args) in list(SYMBOLS.items()) + list(LENGTHS_SYMBOLS.items()) + list(STREAM_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(LENGTHS_SYMBOLS.items()) + list(STREAM_SYMBOLS.items()) + list(WAVE_STREAM_SYMBOLS.items()):
         fn = getattr(lib, name)          # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

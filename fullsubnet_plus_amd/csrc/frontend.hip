@@ -410,18 +410,6 @@ __global__ __launch_bounds__(256) void fe_apply_kernel(const float* __restrict__
 
 // ------------------------------------------------------------------------------------------------
 // decompress_cIRM (mask.py:60-63) + complex multiply (inferencer.py:152-157)
-__device__ __forceinline__ float2 cirm_times(const float* __restrict__ mask, long re_at, long plane, float2 x) {
-    float m[2];
-#pragma unroll
-    for (int o = 0; o < 2; ++o) {
-        float v = mask[re_at + o * plane];
-        const float lim = 9.9f, K = 10.0f;
-        v = v >= lim ? lim : (v <= -lim ? -lim : v);
-        m[o] = -K * logf((K - v) / (K + v));
-    }
-    return make_float2(m[0] * x.x - m[1] * x.y, m[1] * x.x + m[0] * x.y);
-}
-
 __global__ __launch_bounds__(256) void apply_cirm_kernel(const float* __restrict__ mask, const float2* __restrict__ noisy,
                                                          long sb, long sf, long st, float2* __restrict__ out, long ob,
                                                          long of, long ot, int B, int F, int T) {

@@ -104,6 +104,21 @@ struct RowLengths { int v[kLenRows]; };
 // launch_apply_cirm for clips of different lengths: lengths[b] HOST frames of row b, frames >= lengths[b] of `out` written as 0
 void launch_apply_cirm_lengths(const float* mask, const float* noisy, const int64_t strides[3], float* out,
                                const int64_t out_strides[3], int B, int F, int T, const int* lengths, hipStream_t s);
+// one bin of it: the compressed mask planes at mask[re_at], mask[re_at + plane] times the complex x (shared by the whole-clip kernels of
+// frontend.hip and the waveform sessions of stft_stream.hip)
+#ifdef __HIPCC__
+__device__ __forceinline__ float2 cirm_times(const float* __restrict__ mask, long re_at, long plane, float2 x) {
+    float m[2];
+#pragma unroll
+    for (int o = 0; o < 2; ++o) {
+        float v = mask[re_at + o * plane];
+        const float lim = 9.9f, K = 10.0f;
+        v = v >= lim ? lim : (v <= -lim ? -lim : v);
+        m[o] = -K * logf((K - v) / (K + v));
+    }
+    return make_float2(m[0] * x.x - m[1] * x.y, m[1] * x.x + m[0] * x.y);
+}
+#endif
 // is_complex: in[0] is the interleaved complex64 STFT buffer (strides[0] in complex elements); mag / real / imag are
 // derived inside the repack kernel
 // (buf.fsum and buf.tot must be zero when this is called: the repack kernel accumulates the offline norms' statistics into them)
@@ -178,6 +193,48 @@ void launch_istft_ola(const float* frames, const float* window, float* wav, long
 void launch_stft_pad_lengths(const float* wav, long wav_stride, float* xp, long xp_stride, int B, const int* samples, int n_fft, hipStream_t s);
 void launch_istft_ola_lengths(const float* frames, const float* window, float* wav, long wav_stride, int B, int T, int L, const int* samples,
                               int n_fft, hipStream_t s);
+// stft_stream.hip : waveform sessions (include/fsnp_wave_stream.h) - the streaming halves of the two transforms around one mag push.
+// Per slot a wave record [ carry fp32 [n_fft + 1] | ring complex64 [look_ahead][F] | tail fp32 [hop] | fifo fp32 [hop] | samples int64 ]:
+//   carry  the newest n_fft + 1 input samples, carry[i] = sample P - (n_fft + 1) + i (0 before the clip's start)
+//   ring   the noisy spectra of the newest look_ahead frames, frame g in row g % look_ahead (they wait for their masks)
+//   tail   the second half of the newest enhanced frame (already windowed by the inverse DFT matrix)
+//   fifo   finished output samples that have not been emitted yet, fifo[q] = sample max(P - D, 0) + q, 0 behind them
+struct WaveMeta { long long p; int c, fin; };      // samples the slot had before this call, samples it gets now, 1 = it is finished now
+struct WaveArgs {
+    unsigned char* state;                          // wave record of slot 0
+    size_t stride, o_ring, o_tail, o_fifo, o_count;   // bytes between slots, byte offsets inside a record (the carry is at 0)
+    WaveMeta* meta;                                // [S], written by the gather kernel for the kernels behind it
+    int S, F, hop, LA, sp, FP, nrow;               // nrow: frame rows per slot in every per-frame buffer of this call
+};
+// what a call does to a slot, from {P, c, fin} alone.  Frame t is complete once (t + 1) hop samples have arrived (frame 0: hop + 1, it
+// reflects wav[1 .. hop]); the mask of frame t is the model's output of step t + look_ahead; finish adds the clip's last frame and steps
+// the model through look_ahead zero frames
+struct WaveStep {
+    long long nf;      // frames the slot had before this call (= steps of the model so far)
+    long long e_old;   // enhanced frames it had: max(nf - look_ahead, 0)
+    int ks, km;        // new spectra, new model steps (km = ks, finish: 1 and 1 + look_ahead)
+    int j0, ke;        // first step of this call that has a frame (step j is frame nf + j - look_ahead), enhanced frames of this call
+};
+__host__ __device__ inline WaveStep wave_step(long long P, int c, int fin, int hop, int LA) {
+    WaveStep w;
+    w.nf = P <= hop ? 0 : P / hop;
+    if (fin) { w.ks = 1; w.km = 1 + LA; }
+    else { const long long pn = P + c; w.ks = (int)((pn <= hop ? 0 : pn / hop) - w.nf); w.km = w.ks; }
+    w.j0 = w.nf < LA ? (int)(LA - w.nf) : 0;
+    w.ke = w.km > w.j0 ? w.km - w.j0 : 0;
+    w.e_old = w.nf > LA ? w.nf - LA : 0;
+    return w;
+}
+struct WaveCounts { int v[512]; };                 // per slot: samples of a push, or 1 = finish this slot (ONE kernel argument block)
+// frame rows xfr [S][nrow][n_fft] of the newly complete frames (zeros behind them), the carry and the sample count advanced, meta written
+void launch_wave_gather(const WaveArgs& a, const WaveCounts& c, int fin, const float* wav, long wav_stride, float* xfr, hipStream_t s);
+// mag [S][nrow][FP] = |spec| of the new spectra (as the whole-clip complex forward takes it), zero frames behind them up to km
+void launch_wave_mag(const WaveArgs& a, const float* spec, float* mag, hipStream_t s);
+// enh [S][nrow][sp] row e = cIRM of step j0 + e times the noisy spectrum of its frame (this call's or the ring's); the ring advanced
+void launch_wave_apply(const WaveArgs& a, const float* mask, const float* spec, float* enh, hipStream_t s);
+// overlap-add with the window-envelope division over the frames fr [S][nrow][n_fft], into the fifo and out [S][ncols]: column j is
+// sample P + j - D (finish: L - D + j), exactly 0 where that is negative and past the slot's count (finish: in rows not finished)
+void launch_wave_ola(const WaveArgs& a, const float* fr, const float* window, float* out, long out_stride, int ncols, hipStream_t s);
 void stft_build_matrices(int n_fft, float* fwd /*[N2 pad 384][n_fft]*/, float* inv /*[n_fft pad 384][K pad 16]*/,
                          float* window /*[n_fft]*/);
 

@@ -1,7 +1,8 @@
 // fsnp_handle.h - the handle behind the C ABI (include/fsnp.h) and the helpers its translation units share:
 // fsnp_abi.hip (create / forward orchestration / workspace / calibration), forward_kernels.hip (the forward's small kernels),
 // fsnp_verify.hip (exchange verification), fsnp_debug_abi.hip (include/fsnp_debug.h: test and tuning hooks), fsnp_weights.hip
-// (strict weight loading + packing), fsnp_stft_abi.hip (STFT / iSTFT / waveform entry points).  Host declarations only.
+// (strict weight loading + packing), fsnp_stft_abi.hip (STFT / iSTFT / waveform entry points), fsnp_stream_abi.hip and
+// fsnp_wave_stream_abi.hip (stream and wave sessions).  Host declarations only.
 #pragma once
 #include <map>
 #include <string>
@@ -226,5 +227,9 @@ struct StftPlan {
 StftPlan stft_plan(const fsnp_handle* h);
 int ensure_stft(fsnp_handle* h);
 int ensure_io(fsnp_handle* h, size_t bytes, hipStream_t s);
+// fsnp_stream_abi.hip: the per-slot counts of one push travel as ONE kernel argument block (2 KB), and the push behind its checks
+constexpr int kStreamMaxSlots = 512;
+struct StreamCounts { int v[kStreamMaxSlots]; };
+int stream_push_body(fsnp_stream* st, const float* mag, const int64_t strides[3], const StreamCounts& c, float* out, int n, hipStream_t s);
 
 }  // namespace fsnp

@@ -35,9 +35,6 @@ struct fsnp_stream {
 
 namespace fsnp {
 
-constexpr int kStreamMaxSlots = 512;               // counts travel as ONE kernel argument block (2 KB)
-struct StreamCounts { int v[kStreamMaxSlots]; };
-
 // the streaming path's own plan: tiles of 32 rows over the active slots' F rows each, in rounds of one tile per CU
 struct StreamPlan { int rows, tiles, rounds; };
 static StreamPlan plan_stream(int active_slots, int F, int num_cus) {
@@ -88,6 +85,73 @@ __global__ __launch_bounds__(256) void stream_epilogue_kernel(float* __restrict_
         const StreamMeta m = meta[i / per_slot];
         if (j >= m.cnt || m.p + j < LA) out[i] = 0.0f;
     }
+}
+
+// One push behind its checks (fsnp_stream_push, and the waveform sessions of fsnp_wave_stream_abi.hip with the frames each slot
+// completed): mag is device memory with strides, c.v[slot] in [0, n] frames of every slot, out contiguous [slots, 2, F, n].
+int stream_push_body(fsnp_stream* st, const float* mag, const int64_t strides[3], const StreamCounts& c, float* out, int n, hipStream_t s) {
+    fsnp_handle* h = st->h;
+    int nact = 0;
+    for (int b = 0; b < st->S; ++b) nact += c.v[b] > 0;
+    FSNP_ON_DEVICE(h);
+    st->last_stream = s;
+    const int S = st->S, F = h->F;
+    auto fptr = [&](size_t off) { return reinterpret_cast<float*>(st->ws + off); };
+    RowDesc* rows = reinterpret_cast<RowDesc*>(st->ws + st->w_rows);
+    RowDesc* fb_rows = reinterpret_cast<RowDesc*>(st->ws + st->w_fb_rows);
+    StreamMeta* meta = reinterpret_cast<StreamMeta*>(st->ws + st->w_meta);
+    int* cnt = reinterpret_cast<int*>(st->ws + st->w_cnt);
+    float* state_f = reinterpret_cast<float*>(st->state);
+    double* state_d = reinterpret_cast<double*>(st->state);
+
+    if (h->watch_nseg > 0 && (h->watch_calls++ % h->watch_every) == 0)
+        if (launch_weight_watch(h, s, false)) return 4;
+    hipLaunchKernelGGL(stream_prologue_kernel, dim3(cdiv(st->rows_pad, 256)), dim3(256), 0, s, c, S, nact, F, n, rows, st->rows_pad, fb_rows,
+                       st->fb_rows_pad, meta, cnt, st->state, st->state_bytes, st->o_count);
+    if (nact > 0) {
+        Dims d{};
+        d.B = S; d.T = n; d.Tp = n; d.F = F; d.FP = h->FP; d.CH = h->CH; d.H = h->H; d.NSB = h->NSB; d.NIN = h->NIN; d.LA = 0;
+        d.lens = cnt;
+        FrontendBuffers fbuf{};
+        fbuf.raw = fptr(st->w_raw); fbuf.frame = reinterpret_cast<double*>(st->ws + st->w_frame);
+        fbuf.md = reinterpret_cast<NormMD*>(st->ws + st->w_md);
+        launch_frontend_mag_stream(d, h->cfg.norm_type, mag, strides, fbuf, meta, state_d + st->o_fbsum / 8, (long)(st->state_bytes / 8), s);
+
+        const int rg = lstm_generic_rows_per_group(h->CH, F, nact, h->num_cus_real);
+        const int chp = (int)align_up(h->CH, 4);
+        LstmArgs fa{};
+        fa.rows = fb_rows; fa.dense = fptr(st->w_raw); fa.dense_stride = h->FP; fa.md_seq = fbuf.md;
+        fa.seq_out = fptr(st->w_y1); fa.seq_stride = chp;
+        fa.num_rows = nact; fa.num_tiles = cdiv(nact, rg); fa.coop_rows_per_group = rg;
+        fa.Tp = n; fa.LA = 0; fa.FP = h->FP; fa.F = F;
+        fa.st_fb = state_f + st->o_fb / 4; fa.st_stride = (long)(st->state_bytes / 4);
+        launch_lstm_generic_stream(h->fbw, fa, s);
+        launch_linear_act(fptr(st->w_y1), chp, h->fsn_wf, h->fsn_kp, h->fsn_bf, fptr(st->w_fb), h->FP, h->CH, F, S, n, h->cfg.fb_act, h->num_cus, s);
+
+        const StreamPlan plan = plan_stream(nact, F, h->num_cus);
+        SubbandBuffers sbuf{};
+        sbuf.att_mag = fptr(st->w_raw); sbuf.fb = fptr(st->w_fb); sbuf.NFBN = h->cfg.fb_num_neighbors;
+        sbuf.md_row = reinterpret_cast<NormMD*>(st->ws + st->w_md_row);
+        launch_subband_stats_stream(d, h->cfg.norm_type, sbuf, rows, plan.rows, meta, state_d + st->o_sbsum / 8, (long)(st->state_bytes / 8), s);
+
+        LstmArgs a{};
+        a.att_mag = fptr(st->w_raw); a.fb = fptr(st->w_fb);
+        a.fb_rel = (int)((st->w_fb - st->w_raw) / 4);
+        a.fb_branch_stride = S * n * h->FP;
+        a.rows = rows; a.md_row = sbuf.md_row;
+        a.out = out; a.out_stride_o = (long)F * n;
+        a.num_rows = plan.rows; a.num_tiles = plan.tiles; a.ex = 0;
+        a.Tp = n; a.LA = 0; a.FP = h->FP; a.F = F; a.NSBN = h->cfg.sb_num_neighbors; a.NFBN = h->cfg.fb_num_neighbors;
+        a.act = h->cfg.sb_act;
+        a.st_sb = state_f; a.st_stride = (long)(st->state_bytes / 4);
+        launch_lstm_stream(h->lw, a, s);
+    }
+    const long total = (long)S * 2 * F * n;
+    hipLaunchKernelGGL(stream_epilogue_kernel, dim3((unsigned)std::min<long>((total + 255) / 256, 4096)), dim3(256), 0, s, out, meta,
+                       h->cfg.look_ahead, 2 * F * n, n, total);
+    FSNP_HIP_CHECK(hipGetLastError());
+    for (int b = 0; b < S; ++b) st->frames[b] += c.v[b];
+    return 0;
 }
 
 }  // namespace fsnp
@@ -182,75 +246,14 @@ int fsnp_stream_push(fsnp_stream* st, const float* mag, const int64_t strides[3]
     fsnp_handle* h = st->h;
     if (n < 1 || n > st->N) { set_error("fsnp_stream_push: n = %d outside [1, max_chunk = %d]", n, st->N); return 2; }
     StreamCounts c{};
-    int nact = 0;
     for (int b = 0; b < st->S; ++b) {
         const int v = counts ? counts[b] : n;
         if (v < 0 || v > n) { set_error("fsnp_stream_push: slot %d: count %d outside [0, n = %d]", b, v, n); return 2; }
         c.v[b] = v;
-        nact += v > 0;
     }
     if (!h->committed) { set_error("fsnp_stream_push: weights not committed (call fsnp_commit_weights)"); return 2; }
     if (const int ec = take_device_errors(h, "an earlier call on this handle failed")) return ec;
-    FSNP_ON_DEVICE(h);
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    st->last_stream = s;
-    const int S = st->S, F = h->F;
-    auto fptr = [&](size_t off) { return reinterpret_cast<float*>(st->ws + off); };
-    RowDesc* rows = reinterpret_cast<RowDesc*>(st->ws + st->w_rows);
-    RowDesc* fb_rows = reinterpret_cast<RowDesc*>(st->ws + st->w_fb_rows);
-    StreamMeta* meta = reinterpret_cast<StreamMeta*>(st->ws + st->w_meta);
-    int* cnt = reinterpret_cast<int*>(st->ws + st->w_cnt);
-    float* state_f = reinterpret_cast<float*>(st->state);
-    double* state_d = reinterpret_cast<double*>(st->state);
-
-    if (h->watch_nseg > 0 && (h->watch_calls++ % h->watch_every) == 0)
-        if (launch_weight_watch(h, s, false)) return 4;
-    hipLaunchKernelGGL(stream_prologue_kernel, dim3(cdiv(st->rows_pad, 256)), dim3(256), 0, s, c, S, nact, F, n, rows, st->rows_pad, fb_rows,
-                       st->fb_rows_pad, meta, cnt, st->state, st->state_bytes, st->o_count);
-    if (nact > 0) {
-        Dims d{};
-        d.B = S; d.T = n; d.Tp = n; d.F = F; d.FP = h->FP; d.CH = h->CH; d.H = h->H; d.NSB = h->NSB; d.NIN = h->NIN; d.LA = 0;
-        d.lens = cnt;
-        FrontendBuffers fbuf{};
-        fbuf.raw = fptr(st->w_raw); fbuf.frame = reinterpret_cast<double*>(st->ws + st->w_frame);
-        fbuf.md = reinterpret_cast<NormMD*>(st->ws + st->w_md);
-        launch_frontend_mag_stream(d, h->cfg.norm_type, mag, strides, fbuf, meta, state_d + st->o_fbsum / 8, (long)(st->state_bytes / 8), s);
-
-        const int rg = lstm_generic_rows_per_group(h->CH, F, nact, h->num_cus_real);
-        const int chp = (int)align_up(h->CH, 4);
-        LstmArgs fa{};
-        fa.rows = fb_rows; fa.dense = fptr(st->w_raw); fa.dense_stride = h->FP; fa.md_seq = fbuf.md;
-        fa.seq_out = fptr(st->w_y1); fa.seq_stride = chp;
-        fa.num_rows = nact; fa.num_tiles = cdiv(nact, rg); fa.coop_rows_per_group = rg;
-        fa.Tp = n; fa.LA = 0; fa.FP = h->FP; fa.F = F;
-        fa.st_fb = state_f + st->o_fb / 4; fa.st_stride = (long)(st->state_bytes / 4);
-        launch_lstm_generic_stream(h->fbw, fa, s);
-        launch_linear_act(fptr(st->w_y1), chp, h->fsn_wf, h->fsn_kp, h->fsn_bf, fptr(st->w_fb), h->FP, h->CH, F, S, n, h->cfg.fb_act, h->num_cus, s);
-
-        const StreamPlan plan = plan_stream(nact, F, h->num_cus);
-        SubbandBuffers sbuf{};
-        sbuf.att_mag = fptr(st->w_raw); sbuf.fb = fptr(st->w_fb); sbuf.NFBN = h->cfg.fb_num_neighbors;
-        sbuf.md_row = reinterpret_cast<NormMD*>(st->ws + st->w_md_row);
-        launch_subband_stats_stream(d, h->cfg.norm_type, sbuf, rows, plan.rows, meta, state_d + st->o_sbsum / 8, (long)(st->state_bytes / 8), s);
-
-        LstmArgs a{};
-        a.att_mag = fptr(st->w_raw); a.fb = fptr(st->w_fb);
-        a.fb_rel = (int)((st->w_fb - st->w_raw) / 4);
-        a.fb_branch_stride = S * n * h->FP;
-        a.rows = rows; a.md_row = sbuf.md_row;
-        a.out = out; a.out_stride_o = (long)F * n;
-        a.num_rows = plan.rows; a.num_tiles = plan.tiles; a.ex = 0;
-        a.Tp = n; a.LA = 0; a.FP = h->FP; a.F = F; a.NSBN = h->cfg.sb_num_neighbors; a.NFBN = h->cfg.fb_num_neighbors;
-        a.act = h->cfg.sb_act;
-        a.st_sb = state_f; a.st_stride = (long)(st->state_bytes / 4);
-        launch_lstm_stream(h->lw, a, s);
-    }
-    const long total = (long)S * 2 * F * n;
-    hipLaunchKernelGGL(stream_epilogue_kernel, dim3((unsigned)std::min<long>((total + 255) / 256, 4096)), dim3(256), 0, s, out, meta,
-                       h->cfg.look_ahead, 2 * F * n, n, total);
-    FSNP_HIP_CHECK(hipGetLastError());
-    for (int b = 0; b < S; ++b) st->frames[b] += c.v[b];
-    return 0;
+    return stream_push_body(st, mag, strides, c, out, n, static_cast<hipStream_t>(hip_stream));
 }
 
 int fsnp_stream_reset(fsnp_stream* st, const int32_t* slots, int32_t num, void* hip_stream) {

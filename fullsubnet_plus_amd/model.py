@@ -1036,6 +1036,11 @@ class FullSubNet_Plus(_HipModel):
         from .stream import PLUS_REASON
         raise NotImplementedError(f"{self.__class__.__name__}.open_stream: {PLUS_REASON}")
 
+    def open_wave_stream(self, slots, max_samples=4096, device="cuda"):
+        """FullSubNet+ is not streamable (see fullsubnet_plus_amd.stream): always raises NotImplementedError with the reason."""
+        from .stream import PLUS_REASON
+        raise NotImplementedError(f"{self.__class__.__name__}.open_wave_stream: {PLUS_REASON}")
+
 
 class _FullBandLSTMParams(_StageHolder):
     """Parameter holder named like SequenceModel(sequence_model="LSTM") of the original FullSubNet's full-band model
@@ -1132,6 +1137,17 @@ class FullSubNet(_HipModel):
         if why is not None:
             raise NotImplementedError(f"{self.__class__.__name__}.open_stream: {why}")
         return Stream(self, slots, max_chunk, _resolve_device(device))
+
+    def open_wave_stream(self, slots, max_samples=4096, device="cuda"):
+        """-> fullsubnet_plus_amd.stream.WaveStream: `slots` independent live audio streams, blocks of up to max_samples samples in, as
+        many enhanced samples out at the fixed delay (2 + look_ahead) * hop (include/fsnp_wave_stream.h).  All push outputs of a clip
+        followed by finish(), without the first `delay` samples, are enhance_wave() of that clip alone.  The refusals of open_stream
+        apply (NotImplementedError with the reason, before any GPU is touched)."""
+        from .stream import WaveStream, wave_refusal
+        why = wave_refusal(self)
+        if why is not None:
+            raise NotImplementedError(f"{self.__class__.__name__}.open_wave_stream: {why}")
+        return WaveStream(self, slots, max_samples, _resolve_device(device))
 
 
 Model = FullSubNet_Plus  # the name BASELINE.json's north_star uses

@@ -4,6 +4,13 @@
     mask = stream.push(noisy_mag)            # [8, 1, F, n] -> [8, 2, F, n]; column j = cIRM of frame P + j - look_ahead
     ...
     mask = stream.tail()                     # look_ahead zero frames: the masks of the last look_ahead frames
+
+and the same for waveforms (include/fsnp_wave_stream.h): samples in, samples out at the fixed delay (2 + look_ahead) * hop.
+
+    wave = model.open_wave_stream(slots=8, max_samples=4096)
+    out = wave.push(block)                   # [8, n] -> [8, n]; column j = enhanced sample P + j - wave.delay (0 before the clip's start)
+    ...
+    out = wave.finish()                      # [8, wave.delay]: the clips' last samples; the slots are reset
 """
 import ctypes
 
@@ -27,6 +34,19 @@ def refusal(model):
     if model.sb_model_hidden_size not in (256, 384) or nin > 64:
         return (f"sb_model_hidden_size {model.sb_model_hidden_size} with {nin} sub-band inputs is outside the row-tile kernel "
                 "(hidden 256 / 384, <= 64 inputs): not built for streaming")
+    return None
+
+
+def wave_refusal(model):
+    """Why `model` (a FullSubNet) cannot stream waveforms, or None: refusal(), and what enhance_wave demands.  No GPU is touched."""
+    why = refusal(model)
+    if why is not None:
+        return why
+    if model.output_size != 2:
+        return f"the cIRM epilogue needs output_size = 2 (this model: {model.output_size})"
+    hop = model.num_freqs - 1
+    if model.num_freqs < 3 or hop & (hop - 1):
+        return "num_freqs - 1 must be a power of two (n_fft = 2 (num_freqs - 1))"
     return None
 
 
@@ -194,6 +214,190 @@ class Stream:
         return int(v.value)
 
 
-def _lib_counts(counts, slots):
+def _lib_counts(counts, slots, what="Stream.push"):
     from .model import _host_lengths
-    return _host_lengths(counts, slots, "Stream.push")
+    return _host_lengths(counts, slots, what)
+
+
+def _slot_array(slots):
+    """None (every slot) or slot indices -> (ctypes int32 array or None, count)"""
+    if slots is None:
+        return None, 0
+    vals = [int(v) for v in slots]
+    return (ctypes.c_int32 * max(len(vals), 1))(*vals), len(vals)
+
+
+class WaveStream:
+    """`slots` independent live audio streams on one FullSubNet (FullSubNet.open_wave_stream): blocks of samples in, the same number of
+    enhanced samples out, `delay` = (2 + look_ahead) * hop samples late.  All push outputs of a clip followed by its finish() output,
+    without the first `delay` samples, are enhance_wave() of that clip alone, whatever the block sizes.  Everything runs on the current
+    CUDA stream; a push allocates nothing but its output tensor and never synchronises (under the model's error_check="sync" it then
+    waits and polls, as forward does)."""
+
+    def __init__(self, model, slots, max_samples, device):
+        why = wave_refusal(model)
+        if why is not None:
+            raise NotImplementedError(f"{model.__class__.__name__}.open_wave_stream: {why}")
+        self.model, self.slots, self.max_samples, self.device = model, int(slots), int(max_samples), device
+        self.look_ahead, self.hop = model.look_ahead, model.num_freqs - 1
+        self._lib = model._ensure_handle(device)
+        self._owner = model._hip.handle.value
+        sp = ctypes.c_void_p()
+        with torch.cuda.device(device):
+            _lib.check(self._lib.fsnp_wave_stream_create(model._hip.handle, self.slots, self.max_samples, ctypes.byref(sp)),
+                       "fsnp_wave_stream_create")
+        self._st = sp
+        self.delay = int(self._lib.fsnp_wave_stream_delay(sp))
+        self.state_bytes = int(self._lib.fsnp_wave_stream_state_bytes(sp))
+        self._backup = None
+
+    # ------------------------------------------------------------------ plumbing
+    def _session(self):
+        if self._st is None:
+            raise RuntimeError("this stream is closed")
+        h = self.model._hip.handle
+        if h is None or h.value != self._owner:
+            raise RuntimeError("the model's HIP handle was re-created (device change or copy) since open_wave_stream: open a new stream")
+        return self._st
+
+    def _cuda_stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def close(self):
+        st, self._st = self._st, None
+        h = self.model._hip.handle
+        if st is not None and h is not None and h.value == self._owner:
+            with torch.cuda.device(self.device):
+                self._lib.fsnp_wave_stream_destroy(st)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _guarded(self, run, what):
+        """run() -> (rc, out) enqueues one call.  As Stream.push: the watch's verdict on an EARLIER call is answered by a re-pack and one
+        more try; under error_check="sync" a call the watch flags ran on the old weights, so the states it started from are put back."""
+        model, lib = self.model, self._lib
+
+        def attempt():
+            for again in (0, 1):
+                rc, out = run()
+                if rc != _lib.ERR_STALE_WEIGHTS or again:
+                    break
+                model._stale_weights_noticed(self.device)
+            _lib.check(rc, what)
+            return out
+
+        if model.error_check != "sync":
+            return attempt()
+        watched = model.__dict__.get("_fsnp_watched", False)
+        if watched:
+            self._save_states()
+        out = attempt()
+        torch.cuda.current_stream(self.device).synchronize()
+        rc = lib.fsnp_poll_errors(model._handle)
+        if rc == _lib.ERR_STALE_WEIGHTS and watched:
+            self._restore_states()
+            model._hip.packed_key = None
+            model._ensure_handle(self.device)
+            out = attempt()
+            torch.cuda.current_stream(self.device).synchronize()
+            rc = lib.fsnp_poll_errors(model._handle)
+        _lib.check(rc, what)
+        return out
+
+    def _save_states(self):
+        if self._backup is None:
+            self._backup = torch.empty((self.slots, self.state_bytes), dtype=torch.uint8, device=self.device)
+        for b in range(self.slots):
+            with torch.cuda.device(self.device):
+                _lib.check(self._lib.fsnp_wave_stream_get_state(self._st, b, self._backup[b].data_ptr(), self._cuda_stream()),
+                           "fsnp_wave_stream_get_state")
+
+    def _restore_states(self):
+        for b in range(self.slots):
+            with torch.cuda.device(self.device):
+                _lib.check(self._lib.fsnp_wave_stream_set_state(self._st, b, self._backup[b].data_ptr(), self._cuda_stream()),
+                           "fsnp_wave_stream_set_state")
+
+    # ------------------------------------------------------------------ the session
+    def push(self, wav, counts=None):
+        """wav [slots, n] fp32 CUDA tensor (rows of any stride), n <= max_samples; counts: None (n samples for every slot) or samples per
+        slot (a Python sequence or a CPU integer tensor, 0 <= counts[b] <= n; input past counts[b] is never read) -> [slots, n]: column
+        j < counts[b] of slot b is enhanced sample P + j - delay of its clip (exactly 0 while P + j < delay), columns >= counts[b] are
+        exactly 0."""
+        st = self._session()
+        assert wav.dim() == 2, "WaveStream.push takes [slots, n] samples"
+        S, n = wav.shape
+        assert S == self.slots, f"expected {self.slots} slots, got {S}"
+        if not wav.is_cuda:
+            raise RuntimeError("fullsubnet_plus_amd runs on MI355X (HIP) only; move the model and inputs to 'cuda'. "
+                               "There is deliberately no CPU fallback.")
+        assert wav.device == self.device
+        x = wav if wav.dtype == torch.float32 else wav.float()
+        if n > 1 and x.stride(1) != 1:
+            x = x.contiguous()
+        cnt = None if counts is None else _lib_counts(counts, S, "WaveStream.push")
+
+        def run():
+            out = torch.empty((S, n), dtype=torch.float32, device=self.device)
+            with torch.cuda.device(self.device):
+                rc = self._lib.fsnp_wave_stream_push(st, x.data_ptr(), x.stride(0), cnt, out.data_ptr(), n, n, self._cuda_stream())
+            return rc, out
+
+        return self._guarded(run, "fsnp_wave_stream_push")
+
+    def finish(self, slots=None):
+        """End the clips of `slots` (None: all) -> [slots, delay]: each clip's last `delay` samples (exactly 0 where the clip is shorter);
+        rows of slots not listed, and of slots that hold no samples, are exactly 0.  The finished slots are reset: their next push starts
+        a fresh clip.  A slot that holds 1 .. hop samples is refused, as enhance_wave refuses such a clip."""
+        st = self._session()
+        arr, num = _slot_array(slots)
+
+        def run():
+            out = torch.empty((self.slots, self.delay), dtype=torch.float32, device=self.device)
+            with torch.cuda.device(self.device):
+                rc = self._lib.fsnp_wave_stream_finish(st, arr, num, out.data_ptr(), self.delay, self._cuda_stream())
+            return rc, out
+
+        return self._guarded(run, "fsnp_wave_stream_finish")
+
+    def reset(self, slots=None):
+        """Stream-ordered zeroing of the state of `slots` (None: all): the next push starts a fresh clip there."""
+        st = self._session()
+        arr, num = _slot_array(slots)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.fsnp_wave_stream_reset(st, arr, num, self._cuda_stream()), "fsnp_wave_stream_reset")
+
+    def state(self, slot):
+        """-> torch.uint8 CUDA tensor [state_bytes]: the slot's whole state (kernel-independent layout, include/fsnp_wave_stream.h)."""
+        st = self._session()
+        buf = torch.empty(self.state_bytes, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.fsnp_wave_stream_get_state(st, int(slot), buf.data_ptr(), self._cuda_stream()), "fsnp_wave_stream_get_state")
+        return buf
+
+    def load_state(self, slot, tensor):
+        """Load what state() of a slot of any wave session of a model of the same sizes returned.  A migration call: it waits once for the
+        copy, to learn the slot's sample count."""
+        st = self._session()
+        if tensor.dtype != torch.uint8 or tensor.numel() != self.state_bytes:
+            raise ValueError(f"load_state: expected a torch.uint8 tensor of {self.state_bytes} bytes, got {tensor.dtype} x {tensor.numel()}")
+        t = tensor.to(self.device).contiguous()
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.fsnp_wave_stream_set_state(st, int(slot), t.data_ptr(), self._cuda_stream()), "fsnp_wave_stream_set_state")
+
+    def samples(self, slot):
+        """Samples pushed into `slot` since its last reset or finish (host-side count)."""
+        st = self._session()
+        v = ctypes.c_int64()
+        _lib.check(self._lib.fsnp_wave_stream_samples(st, int(slot), ctypes.byref(v)), "fsnp_wave_stream_samples")
+        return int(v.value)

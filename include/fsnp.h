@@ -308,4 +308,5 @@ int32_t fsnp_config_size(void);
 #endif
 #include "fsnp_lengths.h"    /* batches of clips of different lengths (ABI 12, fsnp_apply_cirm_lengths ABI 13) */
 #include "fsnp_stream.h"     /* streaming the original FullSubNet: chunked forwards that carry their state */
+#include "fsnp_wave_stream.h" /* the same for waveforms: samples in, samples out at a fixed delay */
 #endif /* FSNP_H */
