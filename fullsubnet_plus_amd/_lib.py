@@ -138,6 +138,13 @@ WAVE_STREAM_SYMBOLS = {
     "fsnp_wave_stream_samples": (c_i32, [c_vp, c_i32, ctypes.POINTER(c_i64)]),
 }
 
+# every symbol include/fsnp_stream_live.h declares (live sessions: per-step kernels for a few streams; same ABI version)
+LIVE_STREAM_SYMBOLS = {
+    "fsnp_stream_create_live": (c_i32, [c_vp, c_i32, c_i32, ctypes.POINTER(c_vp)]),
+    "fsnp_wave_stream_create_live": (c_i32, [c_vp, c_i32, c_i32, ctypes.POINTER(c_vp)]),
+    "fsnp_stream_is_live": (c_i32, [c_vp]),
+}
+
 ABI_VERSION = 13         # FSNP_ABI_VERSION of the include/fsnp.h these signatures were written against
 
 _lib = None
@@ -159,7 +166,8 @@ def load(build_if_missing=True):
     if not os.path.exists(path):
         raise RuntimeError(f"{path} is missing: run `python -m fullsubnet_plus_amd._build`")
     lib = ctypes.CDLL(path)
-    for name, (res, args) in list(SYMBOLS.items()) + list(LENGTHS_SYMBOLS.items()) + list(STREAM_SYMBOLS.items()) + list(WAVE_STREAM_SYMBOLS.items()):
+    for name, (res, args) in (list(SYMBOLS.items()) + list(LENGTHS_SYMBOLS.items()) + list(STREAM_SYMBOLS.items()) + list(WAVE_STREAM_SYMBOLS.items())
+                              + list(LIVE_STREAM_SYMBOLS.items())):
         fn = getattr(lib, name)          # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

@@ -411,6 +411,34 @@ void launch_lstm_generic_stream(const LstmWeights& w, const LstmArgs& a, hipStre
 int lstm_generic_stream_check(int H, int NIN);
 int lstm_generic_rows_per_group(int H, int NIN, int num_seq, int num_cus);   // 0 = the sizes do not fit a CU's LDS
 int lstm_generic_check(int H, int NIN, bool seq);   // commit time: LDS opt-in + residency of every instantiation; != 0 (error set) on failure
+// lstm_step.hip: live stream sessions (include/fsnp_stream_live.h) - one launch per layer and time step, cut by columns over the chip;
+// stream order is the only synchronisation.  rows[].valid = the row's step count of this push, t = the step, par = t & 1 = the parity
+// of the h buffers this step READS (it writes the other one, and h_t / c_t in place into the slot records)
+struct LiveSbArgs {
+    const RowDesc* rows;       // [tiles * 32]
+    int tiles, t, par, Tp;     // Tp = the push's n: stride of the per-frame tables
+    const float* att_mag; int fb_rel, fb_branch_stride, FP, F, NSBN, NFBN;
+    const NormMD* md_row;      // [rows][Tp]
+    float* st; long st_stride; // sub-band state of slot 0 ([f][layer][h|c][H]), floats between slots
+    float* h0[2]; float* h1[2];   // [parity]: per row tile an A-fragment image of 32 x H (a_frag_index)
+    float* out; long out_stride_o; int act;
+};
+struct LiveFbArgs {
+    const RowDesc* rows;       // [num_rows]: the active slots
+    int num_rows, t, par, Tp;
+    const float* dense; int dense_stride; const NormMD* md_seq;
+    float* st; long st_stride; // full-band state of slot 0 ([layer][h|c][CH])
+    float* h0[2]; float* h1[2];   // [parity][slot][CH]
+    float* seq_out; int seq_stride;
+};
+bool live_sb_available(const LstmWeights& w);
+size_t live_sb_h_floats(int H, int tiles);        // floats of ONE of the four sub-band h buffers
+int live_fb_rows_per_group(int H, int NIN);       // 0 = the sizes do not fit a CU's LDS
+int live_fb_check(int H, int NIN);                // session creation: LDS opt-in + residency; != 0 (error set) on failure
+void launch_live_load(const LiveSbArgs& sb, const LiveFbArgs& fb, int H, int CH, hipStream_t s);   // slot records -> parity-0 h buffers
+void launch_live_sb_step(const LstmWeights& w, const LiveSbArgs& a, int layer, hipStream_t s);
+void launch_live_sb_out(const LstmWeights& w, const LiveSbArgs& a, hipStream_t s);                 // Linear(H, 2) + sb_act of step t
+void launch_live_fb_step(const LstmWeights& w, const LiveFbArgs& a, int layer, hipStream_t s);
 // lstm_coopn.hip: 3 workgroups x 128 hidden units share 1-2 row tiles (43..170 row tiles)
 void launch_lstm_coopn(const LstmWeights& w, const LstmArgs& a, hipStream_t s);
 size_t lstm_coopn_pack_floats(int H, int KX);

@@ -231,5 +231,8 @@ int ensure_io(fsnp_handle* h, size_t bytes, hipStream_t s);
 constexpr int kStreamMaxSlots = 512;
 struct StreamCounts { int v[kStreamMaxSlots]; };
 int stream_push_body(fsnp_stream* st, const float* mag, const int64_t strides[3], const StreamCounts& c, float* out, int n, hipStream_t s);
+// session creation behind fsnp_stream_create (live = 0) and fsnp_stream_create_live (live = 1: pushes run on lstm_step.hip, max_chunk <= kLiveMaxChunk)
+constexpr int kLiveMaxChunk = 16;
+int stream_create(fsnp_handle* h, int32_t slots, int32_t max_chunk, int live, const char* where, fsnp_stream** out);
 
 }  // namespace fsnp

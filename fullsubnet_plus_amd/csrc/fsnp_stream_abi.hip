@@ -13,6 +13,11 @@
 //   launch_subband_stats_stream  the sub-band cumulative norm continued from the carried per-(slot, f) sums (subband.hip)
 //   launch_lstm_stream           the fp32 MFMA row-tile kernel from the carried (h0, c0, h1, c1) (lstm.hip), tiles of 32 rows
 //   stream_epilogue_kernel       columns past a slot's count and columns of steps before look_ahead written as exactly 0
+// A LIVE session (include/fsnp_stream_live.h, max_chunk <= 16) keeps every stage but the two recurrent launches, which become launches per
+// layer and step (lstm_step.hip): the slot records' h into the session's parity-0 buffers, then for t < the largest count full-band
+// layer 0, layer 1 - Linear, sub-band statistics - and sub-band layer 0, layer 1, Linear(H, 2) per step.  Always, whatever the number of
+// active slots or n: a slot's bits do not depend on its neighbours.  Same records, same workspace rules, 4 (H x rows_pad x 32 + S x CH)
+// floats of h buffers more.
 #include <algorithm>
 #include <vector>
 
@@ -28,6 +33,8 @@ struct fsnp_stream {
     size_t ws_bytes = 0;
     size_t w_raw = 0, w_fb = 0, w_y1 = 0, w_md = 0, w_frame = 0, w_md_row = 0, w_rows = 0, w_fb_rows = 0, w_meta = 0, w_cnt = 0;
     int rows_pad = 0, fb_rows_pad = 0;
+    int live = 0;                     // 1 = a live session (include/fsnp_stream_live.h): every push runs on the per-step kernels of lstm_step.hip
+    size_t w_sbh = 0, w_fbh = 0;      // live: sub-band h images [h0 | h1][parity][tile], full-band h vectors [h0 | h1][parity][slot][CH]
     std::vector<int64_t> frames;      // host mirror of the slots' frame counts
     std::vector<char> frames_known;   // 0: the count came with fsnp_stream_set_state (read back on demand)
     hipStream_t last_stream = nullptr;
@@ -125,10 +132,34 @@ int stream_push_body(fsnp_stream* st, const float* mag, const int64_t strides[3]
         fa.num_rows = nact; fa.num_tiles = cdiv(nact, rg); fa.coop_rows_per_group = rg;
         fa.Tp = n; fa.LA = 0; fa.FP = h->FP; fa.F = F;
         fa.st_fb = state_f + st->o_fb / 4; fa.st_stride = (long)(st->state_bytes / 4);
-        launch_lstm_generic_stream(h->fbw, fa, s);
+        int nmax = 0;
+        for (int b = 0; b < S; ++b) nmax = std::max(nmax, c.v[b]);
+        const StreamPlan plan = plan_stream(nact, F, h->num_cus);
+        LiveSbArgs la{};
+        LiveFbArgs lf{};
+        if (st->live) {
+            const size_t sbh = live_sb_h_floats(h->H, st->rows_pad / 32), fbh = (size_t)S * h->CH;
+            la.rows = rows; la.tiles = plan.tiles; la.Tp = n;
+            la.att_mag = fptr(st->w_raw); la.fb_rel = (int)((st->w_fb - st->w_raw) / 4); la.fb_branch_stride = S * n * h->FP;
+            la.FP = h->FP; la.F = F; la.NSBN = h->cfg.sb_num_neighbors; la.NFBN = h->cfg.fb_num_neighbors;
+            la.md_row = reinterpret_cast<NormMD*>(st->ws + st->w_md_row);
+            la.st = state_f; la.st_stride = (long)(st->state_bytes / 4);
+            for (int p = 0; p < 2; ++p) { la.h0[p] = fptr(st->w_sbh) + p * sbh; la.h1[p] = fptr(st->w_sbh) + (2 + p) * sbh; }
+            la.out = out; la.out_stride_o = (long)F * n; la.act = h->cfg.sb_act;
+            lf.rows = fb_rows; lf.num_rows = nact; lf.Tp = n;
+            lf.dense = fptr(st->w_raw); lf.dense_stride = h->FP; lf.md_seq = fbuf.md;
+            lf.st = state_f + st->o_fb / 4; lf.st_stride = (long)(st->state_bytes / 4);
+            for (int p = 0; p < 2; ++p) { lf.h0[p] = fptr(st->w_fbh) + p * fbh; lf.h1[p] = fptr(st->w_fbh) + (2 + p) * fbh; }
+            lf.seq_out = fptr(st->w_y1); lf.seq_stride = chp;
+            launch_live_load(la, lf, h->H, h->CH, s);
+            for (int t = 0; t < nmax; ++t) {
+                lf.t = t; lf.par = t & 1;
+                launch_live_fb_step(h->fbw, lf, 0, s);
+                launch_live_fb_step(h->fbw, lf, 1, s);
+            }
+        } else launch_lstm_generic_stream(h->fbw, fa, s);
         launch_linear_act(fptr(st->w_y1), chp, h->fsn_wf, h->fsn_kp, h->fsn_bf, fptr(st->w_fb), h->FP, h->CH, F, S, n, h->cfg.fb_act, h->num_cus, s);
 
-        const StreamPlan plan = plan_stream(nact, F, h->num_cus);
         SubbandBuffers sbuf{};
         sbuf.att_mag = fptr(st->w_raw); sbuf.fb = fptr(st->w_fb); sbuf.NFBN = h->cfg.fb_num_neighbors;
         sbuf.md_row = reinterpret_cast<NormMD*>(st->ws + st->w_md_row);
@@ -144,7 +175,14 @@ int stream_push_body(fsnp_stream* st, const float* mag, const int64_t strides[3]
         a.Tp = n; a.LA = 0; a.FP = h->FP; a.F = F; a.NSBN = h->cfg.sb_num_neighbors; a.NFBN = h->cfg.fb_num_neighbors;
         a.act = h->cfg.sb_act;
         a.st_sb = state_f; a.st_stride = (long)(st->state_bytes / 4);
-        launch_lstm_stream(h->lw, a, s);
+        if (st->live) {
+            for (int t = 0; t < nmax; ++t) {
+                la.t = t; la.par = t & 1;
+                launch_live_sb_step(h->lw, la, 0, s);
+                launch_live_sb_step(h->lw, la, 1, s);
+                launch_live_sb_out(h->lw, la, s);
+            }
+        } else launch_lstm_stream(h->lw, a, s);
     }
     const long total = (long)S * 2 * F * n;
     hipLaunchKernelGGL(stream_epilogue_kernel, dim3((unsigned)std::min<long>((total + 255) / 256, 4096)), dim3(256), 0, s, out, meta,
@@ -160,38 +198,46 @@ static const char* norm_name(int t) {
     return t == FSNP_NORM_OFFLINE_LAPLACE ? "offline_laplace_norm" : t == FSNP_NORM_OFFLINE_GAUSSIAN ? "offline_gaussian_norm" : "?";
 }
 
-extern "C" {
+namespace fsnp {
 
-int fsnp_stream_create(fsnp_handle* h, int32_t slots, int32_t max_chunk, fsnp_stream** out) {
-    if (!h || !out) { set_error("fsnp_stream_create: null argument"); return 1; }
+// fsnp_stream_create / fsnp_stream_create_live (and the mag session inside a wave session): `where` names the entry point in every message
+int stream_create(fsnp_handle* h, int32_t slots, int32_t max_chunk, int live, const char* where, fsnp_stream** out) {
+    if (!h || !out) { set_error("%s: null argument", where); return 1; }
     *out = nullptr;
     if (h->model != FSNP_MODEL_FULLSUBNET) {
-        set_error("fsnp_stream_create: FullSubNet+ cannot be streamed exactly: its full-band TCN blocks are not causal and normalise with "
-                  "GroupNorm(1, C) over the whole clip, and TSSE pools over all of time; stream the original FullSubNet");
+        set_error("%s: FullSubNet+ cannot be streamed exactly: its full-band TCN blocks are not causal and normalise with "
+                  "GroupNorm(1, C) over the whole clip, and TSSE pools over all of time; stream the original FullSubNet", where);
         return 2;
     }
     if (h->cfg.norm_type != FSNP_NORM_CUMULATIVE_LAPLACE && h->cfg.norm_type != FSNP_NORM_CUMULATIVE_LAYER) {
-        set_error("fsnp_stream_create: norm_type %s needs the whole clip's total; streaming needs cumulative_laplace_norm or cumulative_layer_norm",
+        set_error("%s: norm_type %s needs the whole clip's total; streaming needs cumulative_laplace_norm or cumulative_layer_norm", where,
                   norm_name(h->cfg.norm_type));
         return 2;
     }
-    if (h->gru || h->sb_tcn) { set_error("fsnp_stream_create: sequence_model \"%s\" is not built for streaming (LSTM only)", h->gru ? "GRU" : "TCN"); return 2; }
-    if (!h->committed) { set_error("fsnp_stream_create: weights not committed (call fsnp_commit_weights)"); return 2; }
+    if (h->gru || h->sb_tcn) { set_error("%s: sequence_model \"%s\" is not built for streaming (LSTM only)", where, h->gru ? "GRU" : "TCN"); return 2; }
+    if (!h->committed) { set_error("%s: weights not committed (call fsnp_commit_weights)", where); return 2; }
     if (h->generic_sb || !lstm_stream_available(h->lw)) {
-        set_error("fsnp_stream_create: sb_model_hidden_size %d with %d sub-band inputs is outside the row-tile kernel (hidden 256 / 384, <= 64 inputs): not built for streaming",
+        set_error("%s: sb_model_hidden_size %d with %d sub-band inputs is outside the row-tile kernel (hidden 256 / 384, <= 64 inputs): not built for streaming", where,
                   h->H, h->NIN);
         return 2;
     }
     const int max_slots = std::min(32 * (h->num_cus_real / 16), kStreamMaxSlots);
-    if (slots < 1 || slots > max_slots) { set_error("fsnp_stream_create: %d slots; a session holds 1 ... %d (full-band LSTM residency of a whole-clip forward)", slots, max_slots); return 2; }
-    if (max_chunk < 1) { set_error("fsnp_stream_create: max_chunk %d < 1", max_chunk); return 2; }
-    if ((double)slots * max_chunk * h->FP * 2 * 2 > 2.0e9) { set_error("fsnp_stream_create: slots x max_chunk too large for 32-bit gather offsets"); return 2; }
+    if (slots < 1 || slots > max_slots) { set_error("%s: %d slots; a session holds 1 ... %d (full-band LSTM residency of a whole-clip forward)", where, slots, max_slots); return 2; }
+    if (max_chunk < 1) { set_error("%s: max_chunk %d < 1", where, max_chunk); return 2; }
+    if (live && max_chunk > kLiveMaxChunk) {
+        set_error("%s: max_chunk %d > %d: a live session costs a handful of launches per frame by design; longer chunks belong to a default "
+                  "session (fsnp_stream_create)", where, max_chunk, kLiveMaxChunk);
+        return 2;
+    }
+    if (live && !live_sb_available(h->lw)) { set_error("%s: the 16-unit column-split weight image of the sub-band LSTM is not packed for these sizes", where); return 2; }
+    if ((double)slots * max_chunk * h->FP * 2 * 2 > 2.0e9) { set_error("%s: slots x max_chunk too large for 32-bit gather offsets", where); return 2; }
     FSNP_ON_DEVICE(h);
-    if (lstm_generic_rows_per_group(h->CH, h->F, 1, 1) == 0) { set_error("fsnp_stream_create: fb_model_hidden_size %d is too large for the streaming full-band kernel (LDS)", h->CH); return 2; }
+    if (lstm_generic_rows_per_group(h->CH, h->F, 1, 1) == 0) { set_error("%s: fb_model_hidden_size %d is too large for the streaming full-band kernel (LDS)", where, h->CH); return 2; }
     if (lstm_generic_stream_check(h->CH, h->F)) return 2;
+    if (live && live_fb_check(h->CH, h->F)) return 2;
 
     fsnp_stream* st = new fsnp_stream();
-    st->h = h; st->S = slots; st->N = max_chunk;
+    st->h = h; st->S = slots; st->N = max_chunk; st->live = live;
     const size_t F = h->F, H = h->H, CH = h->CH;
     st->o_fb = F * 4 * H * 4;
     st->o_sbsum = align_up(st->o_fb + 4 * CH * 4, 8);
@@ -213,13 +259,17 @@ int fsnp_stream_create(fsnp_handle* h, int32_t slots, int32_t max_chunk, fsnp_st
     st->w_fb_rows = take((size_t)st->fb_rows_pad * sizeof(RowDesc));
     st->w_meta = take(S * sizeof(StreamMeta));
     st->w_cnt = take(S * 4);
+    if (live) {
+        st->w_sbh = take(4 * live_sb_h_floats(h->H, st->rows_pad / 32) * 4);
+        st->w_fbh = take(4 * S * CH * 4);
+    }
     st->ws_bytes = o;
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&st->state), st->state_bytes * S);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&st->ws), st->ws_bytes);
     if (e == hipSuccess) e = hipMemset(st->state, 0, st->state_bytes * S);
     if (e == hipSuccess) e = hipMemset(st->ws, 0, st->ws_bytes);
     if (e != hipSuccess) {
-        set_error("fsnp_stream_create: %s (state %zu bytes x %d slots, workspace %zu bytes)", hipGetErrorString(e), st->state_bytes, slots, st->ws_bytes);
+        set_error("%s: %s (state %zu bytes x %d slots, workspace %zu bytes)", where, hipGetErrorString(e), st->state_bytes, slots, st->ws_bytes);
         if (st->state) (void)hipFree(st->state);
         if (st->ws) (void)hipFree(st->ws);
         delete st;
@@ -230,6 +280,20 @@ int fsnp_stream_create(fsnp_handle* h, int32_t slots, int32_t max_chunk, fsnp_st
     *out = st;
     return 0;
 }
+
+}  // namespace fsnp
+
+extern "C" {
+
+int fsnp_stream_create(fsnp_handle* h, int32_t slots, int32_t max_chunk, fsnp_stream** out) {
+    return stream_create(h, slots, max_chunk, 0, "fsnp_stream_create", out);
+}
+
+int fsnp_stream_create_live(fsnp_handle* h, int32_t slots, int32_t max_chunk, fsnp_stream** out) {
+    return stream_create(h, slots, max_chunk, 1, "fsnp_stream_create_live", out);
+}
+
+int fsnp_stream_is_live(const fsnp_stream* st) { return st ? st->live : 0; }
 
 void fsnp_stream_destroy(fsnp_stream* st) {
     if (!st) return;

@@ -104,23 +104,21 @@ int wave_reset(fsnp_wave_stream* w, const int32_t* slots, int32_t num, void* hip
     return 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-int fsnp_wave_stream_create(fsnp_handle* h, int32_t slots, int32_t max_samples, fsnp_wave_stream** out) {
-    if (!h || !out) { set_error("fsnp_wave_stream_create: null argument"); return 1; }
+// fsnp_wave_stream_create (live = 0) / fsnp_wave_stream_create_live (live = 1: the mag session inside is a live one)
+int wave_create(fsnp_handle* h, int32_t slots, int32_t max_samples, int live, const char* where, fsnp_wave_stream** out) {
+    if (!h || !out) { set_error("%s: null argument", where); return 1; }
     *out = nullptr;
-    if (h->cfg.output_size != 2) { set_error("fsnp_wave_stream_create: the cIRM epilogue needs output_size = 2 (this handle: %d)", h->cfg.output_size); return 2; }
-    if (max_samples < 1) { set_error("fsnp_wave_stream_create: max_samples %d < 1", max_samples); return 2; }
+    if (h->cfg.output_size != 2) { set_error("%s: the cIRM epilogue needs output_size = 2 (this handle: %d)", where, h->cfg.output_size); return 2; }
+    if (max_samples < 1) { set_error("%s: max_samples %d < 1", where, max_samples); return 2; }
     if (h->F < 3 || ((h->F - 1) & (h->F - 2)) != 0 || h->F - 1 > 4096) {
-        set_error("fsnp_wave_stream_create: num_freqs - 1 must be a power of two up to 4096 (n_fft = 2 (num_freqs - 1))");
+        set_error("%s: num_freqs - 1 must be a power of two up to 4096 (n_fft = 2 (num_freqs - 1))", where);
         return 2;
     }
     const int hop = h->F - 1, LA = h->cfg.look_ahead;
     const int NF = std::max(max_samples / hop + 1, 1 + LA);
     fsnp_stream* mag = nullptr;
-    if (const int rc = fsnp_stream_create(h, slots, NF, &mag)) return rc;      // every refusal of a mag session, with its reason
+    // every refusal of a mag session, with its reason (live: frames per push = max(max_samples / hop + 1, 1 + look_ahead) <= 16)
+    if (const int rc = live ? stream_create(h, slots, NF, 1, where, &mag) : fsnp_stream_create(h, slots, NF, &mag)) return rc;
     if (ensure_stft(h)) { fsnp_stream_destroy(mag); return 2; }
     fsnp_wave_stream* w = new fsnp_wave_stream();
     w->h = h; w->mag = mag; w->S = slots; w->max_samples = max_samples; w->NF = NF; w->hop = hop; w->LA = LA; w->D = (2 + LA) * hop;
@@ -149,8 +147,8 @@ int fsnp_wave_stream_create(fsnp_handle* h, int32_t slots, int32_t max_samples, 
     if (e == hipSuccess) e = hipMemset(w->state, 0, w->rec_bytes * S);
     if (e == hipSuccess) e = hipMemset(w->ws, 0, w->ws_bytes);      // (pad columns of the spectrum rows stay 0 for good)
     if (e != hipSuccess) {
-        set_error("fsnp_wave_stream_create: %s (wave state %zu bytes x %d slots, workspace %zu bytes)", hipGetErrorString(e), w->rec_bytes,
-                  slots, w->ws_bytes);
+        set_error("%s: %s (wave state %zu bytes x %d slots, workspace %zu bytes)", where, hipGetErrorString(e), w->rec_bytes, slots,
+                  w->ws_bytes);
         if (w->state) (void)hipFree(w->state);
         if (w->ws) (void)hipFree(w->ws);
         fsnp_stream_destroy(mag);
@@ -160,6 +158,18 @@ int fsnp_wave_stream_create(fsnp_handle* h, int32_t slots, int32_t max_samples, 
     w->samples.assign(S, 0);
     *out = w;
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fsnp_wave_stream_create(fsnp_handle* h, int32_t slots, int32_t max_samples, fsnp_wave_stream** out) {
+    return wave_create(h, slots, max_samples, 0, "fsnp_wave_stream_create", out);
+}
+
+int fsnp_wave_stream_create_live(fsnp_handle* h, int32_t slots, int32_t max_samples, fsnp_wave_stream** out) {
+    return wave_create(h, slots, max_samples, 1, "fsnp_wave_stream_create_live", out);
 }
 
 void fsnp_wave_stream_destroy(fsnp_wave_stream* w) {

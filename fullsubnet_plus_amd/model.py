@@ -1031,12 +1031,12 @@ class FullSubNet_Plus(_HipModel):
         return self._checked(lambda: self._forward_impl([noisy_mag, noisy_real, noisy_imag], batch_offset, global_batch, lengths=lengths),
                              noisy_mag.device)
 
-    def open_stream(self, slots, max_chunk=16, device="cuda"):
+    def open_stream(self, slots, max_chunk=16, device="cuda", live=False):
         """FullSubNet+ is not streamable (see fullsubnet_plus_amd.stream): always raises NotImplementedError with the reason."""
         from .stream import PLUS_REASON
         raise NotImplementedError(f"{self.__class__.__name__}.open_stream: {PLUS_REASON}")
 
-    def open_wave_stream(self, slots, max_samples=4096, device="cuda"):
+    def open_wave_stream(self, slots, max_samples=4096, device="cuda", live=False):
         """FullSubNet+ is not streamable (see fullsubnet_plus_amd.stream): always raises NotImplementedError with the reason."""
         from .stream import PLUS_REASON
         raise NotImplementedError(f"{self.__class__.__name__}.open_wave_stream: {PLUS_REASON}")
@@ -1127,27 +1127,35 @@ class FullSubNet(_HipModel):
         for batch_mode, the sharding arguments and lengths)."""
         return self._checked(lambda: self._forward_impl([noisy_mag], batch_offset, global_batch, lengths=lengths), noisy_mag.device)
 
-    def open_stream(self, slots, max_chunk=16, device="cuda"):
+    def open_stream(self, slots, max_chunk=16, device="cuda", live=False):
         """-> fullsubnet_plus_amd.stream.Stream: `slots` independent live streams that are fed a few frames per push and carry the
         recurrent state and the cumulative norms' sums between pushes (include/fsnp_stream.h).  A clip pushed in any chunking, followed
         by tail(), gives forward()'s mask of that clip delayed by look_ahead columns.  Needs a cumulative norm and LSTM cells
-        (NotImplementedError with the reason otherwise, before any GPU is touched)."""
+        (NotImplementedError with the reason otherwise, before any GPU is touched).
+
+        live=True opens a LIVE session (include/fsnp_stream_live.h): the mode for a few calls fed one hop at a time.  Its pushes run the
+        two recurrent models as one short launch per layer and step, cut by columns over the whole chip, where a default session keeps
+        one launch each resident over the chunk (one 32-row tile per CU, one workgroup for the full-band model of one slot).  Same
+        interface and state records (state() of one mode loads into the other); max_chunk <= 16.  Measured on one MI355X
+        (profiles/stream_throughput.md, ms per push at n = 1, default -> live): 1 slot 0.47 -> 0.14, 8 slots 0.48 -> 0.26, 32 slots
+        0.72 -> 0.57, 64 slots 0.97 -> 1.03: open a live session up to 32 slots, a default one from 64 slots on or for longer chunks."""
         from .stream import Stream, refusal
         why = refusal(self)
         if why is not None:
             raise NotImplementedError(f"{self.__class__.__name__}.open_stream: {why}")
-        return Stream(self, slots, max_chunk, _resolve_device(device))
+        return Stream(self, slots, max_chunk, _resolve_device(device), live=live)
 
-    def open_wave_stream(self, slots, max_samples=4096, device="cuda"):
+    def open_wave_stream(self, slots, max_samples=4096, device="cuda", live=False):
         """-> fullsubnet_plus_amd.stream.WaveStream: `slots` independent live audio streams, blocks of up to max_samples samples in, as
         many enhanced samples out at the fixed delay (2 + look_ahead) * hop (include/fsnp_wave_stream.h).  All push outputs of a clip
         followed by finish(), without the first `delay` samples, are enhance_wave() of that clip alone.  The refusals of open_stream
-        apply (NotImplementedError with the reason, before any GPU is touched)."""
+        apply (NotImplementedError with the reason, before any GPU is touched).  live=True: the model inside runs as a live session
+        (see open_stream); max_samples / hop + 1 frames per push must then be <= 16, e.g. max_samples = hop for one hop per push."""
         from .stream import WaveStream, wave_refusal
         why = wave_refusal(self)
         if why is not None:
             raise NotImplementedError(f"{self.__class__.__name__}.open_wave_stream: {why}")
-        return WaveStream(self, slots, max_samples, _resolve_device(device))
+        return WaveStream(self, slots, max_samples, _resolve_device(device), live=live)
 
 
 Model = FullSubNet_Plus  # the name BASELINE.json's north_star uses

@@ -11,6 +11,9 @@ and the same for waveforms (include/fsnp_wave_stream.h): samples in, samples out
     out = wave.push(block)                   # [8, n] -> [8, n]; column j = enhanced sample P + j - wave.delay (0 before the clip's start)
     ...
     out = wave.finish()                      # [8, wave.delay]: the clips' last samples; the slots are reset
+
+Both take live=True (include/fsnp_stream_live.h): the session mode for a few streams fed one hop at a time, on per-step kernels that
+fill the chip at one slot.  Same interface, same state records; max_chunk <= 16.
 """
 import ctypes
 
@@ -55,7 +58,7 @@ class Stream:
     allocates nothing but its output tensor and never synchronises (under the model's error_check="sync" it then waits and polls, as
     forward does)."""
 
-    def __init__(self, model, slots, max_chunk, device):
+    def __init__(self, model, slots, max_chunk, device, live=False):
         why = refusal(model)
         if why is not None:
             raise NotImplementedError(f"{model.__class__.__name__}.open_stream: {why}")
@@ -65,8 +68,13 @@ class Stream:
         self._owner = model._hip.handle.value
         sp = ctypes.c_void_p()
         with torch.cuda.device(device):
-            _lib.check(self._lib.fsnp_stream_create(model._hip.handle, self.slots, self.max_chunk, ctypes.byref(sp)), "fsnp_stream_create")
+            if live:
+                _lib.check(self._lib.fsnp_stream_create_live(model._hip.handle, self.slots, self.max_chunk, ctypes.byref(sp)),
+                           "fsnp_stream_create_live")
+            else:
+                _lib.check(self._lib.fsnp_stream_create(model._hip.handle, self.slots, self.max_chunk, ctypes.byref(sp)), "fsnp_stream_create")
         self._st = sp
+        self.live = bool(self._lib.fsnp_stream_is_live(sp))      # what the library made, not what was asked for
         self.state_bytes = int(self._lib.fsnp_stream_state_bytes(sp))
         self._backup = None
 
@@ -234,7 +242,7 @@ class WaveStream:
     CUDA stream; a push allocates nothing but its output tensor and never synchronises (under the model's error_check="sync" it then
     waits and polls, as forward does)."""
 
-    def __init__(self, model, slots, max_samples, device):
+    def __init__(self, model, slots, max_samples, device, live=False):
         why = wave_refusal(model)
         if why is not None:
             raise NotImplementedError(f"{model.__class__.__name__}.open_wave_stream: {why}")
@@ -244,9 +252,11 @@ class WaveStream:
         self._owner = model._hip.handle.value
         sp = ctypes.c_void_p()
         with torch.cuda.device(device):
-            _lib.check(self._lib.fsnp_wave_stream_create(model._hip.handle, self.slots, self.max_samples, ctypes.byref(sp)),
-                       "fsnp_wave_stream_create")
+            create, what = ((self._lib.fsnp_wave_stream_create_live, "fsnp_wave_stream_create_live") if live
+                            else (self._lib.fsnp_wave_stream_create, "fsnp_wave_stream_create"))
+            _lib.check(create(model._hip.handle, self.slots, self.max_samples, ctypes.byref(sp)), what)
         self._st = sp
+        self.live = bool(live)
         self.delay = int(self._lib.fsnp_wave_stream_delay(sp))
         self.state_bytes = int(self._lib.fsnp_wave_stream_state_bytes(sp))
         self._backup = None

@@ -309,4 +309,5 @@ int32_t fsnp_config_size(void);
 #include "fsnp_lengths.h"    /* batches of clips of different lengths (ABI 12, fsnp_apply_cirm_lengths ABI 13) */
 #include "fsnp_stream.h"     /* streaming the original FullSubNet: chunked forwards that carry their state */
 #include "fsnp_wave_stream.h" /* the same for waveforms: samples in, samples out at a fixed delay */
+#include "fsnp_stream_live.h" /* live sessions: a few slots fed one hop at a time, on per-step kernels that fill the chip */
 #endif /* FSNP_H */

@@ -12,6 +12,12 @@ of bench.py.
 audio (one frame of the model per push) next to the mag push of n = 1 frame at the same S in the same run; one JSON line per S.
 
     python tools/stream_throughput.py --wave [--slots 1 32] [--runs 5] [--pushes 8]
+
+--live adds a live session (open_stream(..., live=True): per-step kernels that fill the chip at one slot) beside the default one in every
+cell it takes (n <= 16), timed in the same run right after it: "live_ms_per_push", the spread of both modes' runs (min and max of the
+--runs timed runs, per push) and "live_speedup" = default / live.  With --wave the wave session is timed in both modes as well.
+
+    python tools/stream_throughput.py --live [--slots 1 8 32 64] [--chunks 1 4 16]
 """
 import argparse
 import json
@@ -30,7 +36,11 @@ from fullsubnet_plus_amd.synthetic import FULLSUBNET_MODEL_ARGS, make_inputs, ma
 FRAME_MS = 16.0
 
 
-def timed(fn, runs):
+LIVE_MAX_CHUNK = 16
+
+
+def timed_all(fn, runs):
+    """every timed run's seconds (after one warm-up run)"""
     fn()
     torch.cuda.synchronize()
     out = []
@@ -39,7 +49,11 @@ def timed(fn, runs):
         fn()
         torch.cuda.synchronize()
         out.append(time.perf_counter() - t0)
-    return statistics.median(out)
+    return out
+
+
+def timed(fn, runs):
+    return statistics.median(timed_all(fn, runs))
 
 
 def wave_mode(model, a):
@@ -59,14 +73,24 @@ def wave_mode(model, a):
                 for blk in blocks:
                     ws.push(blk)
             wave_push = timed(run_wave, a.runs) / a.pushes
-        print(json.dumps({"slots": S, "samples_per_push": hop, "wave_ms_per_push": round(wave_push * 1e3, 4),
-                          "mag_ms_per_push": round(mag_push * 1e3, 4), "wave_minus_mag_ms": round((wave_push - mag_push) * 1e3, 4),
-                          "real_time_streams": round(FRAME_MS * 1e-3 / wave_push * S, 1)}))
+        rec = {"slots": S, "samples_per_push": hop, "wave_ms_per_push": round(wave_push * 1e3, 4),
+               "mag_ms_per_push": round(mag_push * 1e3, 4), "wave_minus_mag_ms": round((wave_push - mag_push) * 1e3, 4),
+               "real_time_streams": round(FRAME_MS * 1e-3 / wave_push * S, 1)}
+        if a.live:
+            with model.open_wave_stream(S, max_samples=hop, live=True) as ws:
+                def run_live():
+                    for blk in blocks:
+                        ws.push(blk)
+                live_push = timed(run_live, a.runs) / a.pushes
+            rec.update({"live_wave_ms_per_push": round(live_push * 1e3, 4), "live_speedup": round(wave_push / live_push, 2),
+                        "live_real_time_streams": round(FRAME_MS * 1e-3 / live_push * S, 1)})
+        print(json.dumps(rec))
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--wave", action="store_true", help="time wave sessions (hop-sized pushes) next to the mag push of one frame")
+    ap.add_argument("--live", action="store_true", help="time a live session beside the default one in every cell of n <= 16 frames")
     ap.add_argument("--slots", type=int, nargs="+", default=[1, 8, 32, 64])
     ap.add_argument("--chunks", type=int, nargs="+", default=[1, 4, 16, 64])
     ap.add_argument("--runs", type=int, default=5)
@@ -96,11 +120,22 @@ def main():
                     def run():
                         for _ in range(a.pushes):
                             st.push(x)
-                    per_push = timed(run, a.runs) / a.pushes
-                print(json.dumps({"slots": S, "chunk": n, "ms_per_push": round(per_push * 1e3, 4),
-                                  "us_per_frame": round(per_push / n * 1e6, 2),
-                                  "real_time_streams": round(FRAME_MS * 1e-3 * n / per_push * S, 1),
-                                  "per_frame_vs_offline": round(per_push / n / off_frame, 3)}))
+                    runs = [t / a.pushes for t in timed_all(run, a.runs)]
+                per_push = statistics.median(runs)
+                rec = {"slots": S, "chunk": n, "ms_per_push": round(per_push * 1e3, 4),
+                       "us_per_frame": round(per_push / n * 1e6, 2),
+                       "real_time_streams": round(FRAME_MS * 1e-3 * n / per_push * S, 1),
+                       "per_frame_vs_offline": round(per_push / n / off_frame, 3)}
+                if a.live and n <= LIVE_MAX_CHUNK:
+                    with model.open_stream(S, max_chunk=n, live=True) as st:
+                        live_runs = [t / a.pushes for t in timed_all(run, a.runs)]
+                    live = statistics.median(live_runs)
+                    rec.update({"ms_per_push_min_max": [round(min(runs) * 1e3, 4), round(max(runs) * 1e3, 4)],
+                                "live_ms_per_push": round(live * 1e3, 4),
+                                "live_ms_per_push_min_max": [round(min(live_runs) * 1e3, 4), round(max(live_runs) * 1e3, 4)],
+                                "live_speedup": round(per_push / live, 2),
+                                "live_real_time_streams": round(FRAME_MS * 1e-3 * n / live * S, 1)})
+                print(json.dumps(rec))
     model.check_errors()
 
 
