@@ -15,13 +15,14 @@ The modules below only *hold parameters* with the reference's names; no torch op
 anything in ``forward``.  CPU tensors are rejected: there is deliberately no CPU fallback.
 """
 import ctypes
-import operator
+import warnings
 import weakref
 
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, _policy
+from ._args import _host_lengths
 
 _TCN_DILATIONS = (1, 2, 5, 9, 1, 2, 5, 9)
 
@@ -186,26 +187,6 @@ def _reference_style_init(m):
     elif isinstance(m, (nn.LSTM, nn.GRU)):
         for p in m.parameters():
             (nn.init.orthogonal_ if p.dim() >= 2 else nn.init.normal_)(p.data)
-
-
-def _host_lengths(lengths, batch, what):
-    """Per-utterance lengths (a Python sequence or a CPU integer tensor) -> ctypes int32[batch].  They are read on the host and
-    reach the device as kernel arguments: a CUDA tensor is refused, because reading it would synchronise."""
-    if isinstance(lengths, torch.Tensor):
-        if lengths.device.type != "cpu":
-            raise ValueError(f"{what}: lengths must be a CPU tensor or a Python sequence, not a {lengths.device} tensor "
-                             "(reading it would synchronise the device)")
-        if lengths.is_floating_point() or lengths.is_complex() or lengths.dtype == torch.bool:
-            raise TypeError(f"{what}: lengths must hold integers, got {lengths.dtype}")
-        vals = [int(v) for v in lengths.reshape(-1).tolist()]
-    else:
-        vals = [operator.index(v) for v in lengths]
-    if len(vals) != batch:
-        raise ValueError(f"{what}: {len(vals)} lengths for a batch of {batch}")
-    for b, v in enumerate(vals):
-        if not -2 ** 31 <= v < 2 ** 31:
-            raise ValueError(f"{what}: utterance {b}: length {v} is not an int32")
-    return (ctypes.c_int32 * batch)(*vals)
 
 
 def _resolve_device(device):
@@ -483,81 +464,67 @@ class _HipModel(nn.Module):
         mode = _lib.MODE_PARITY if parity else _lib.MODE_FULL
         if complex_in:
             cst = (ctypes.c_int64 * 3)(*noisy_mag.stride())
-            for attempt in (0, 1):
+
+            def enqueue():
                 with torch.cuda.device(device):
                     if lengths is not None:
-                        rc = lib.fsnp_forward_complex_lengths(self._handle, torch.view_as_real(noisy_mag).data_ptr(), ctypes.byref(cst),
-                                                              lengths, out.data_ptr(), batch_size, num_frames, ctypes.c_void_p(stream))
-                    else:
-                        rc = lib.fsnp_forward_complex(self._handle, torch.view_as_real(noisy_mag).data_ptr(), ctypes.byref(cst),
-                                                      out.data_ptr(), batch_size, num_frames, mode, int(batch_offset), gb,
-                                                      ctypes.c_void_p(stream))
-                if rc != _lib.ERR_STALE_WEIGHTS or attempt:
-                    break
-                self._stale_weights_noticed(device)
-            _lib.check(rc, "fsnp_forward_complex")
+                        return lib.fsnp_forward_complex_lengths(self._handle, torch.view_as_real(noisy_mag).data_ptr(), ctypes.byref(cst),
+                                                                lengths, out.data_ptr(), batch_size, num_frames, ctypes.c_void_p(stream))
+                    return lib.fsnp_forward_complex(self._handle, torch.view_as_real(noisy_mag).data_ptr(), ctypes.byref(cst),
+                                                    out.data_ptr(), batch_size, num_frames, mode, int(batch_offset), gb,
+                                                    ctypes.c_void_p(stream))
+            _policy.enqueue_retrying_stale(enqueue, self._stale_weights_noticed, "fsnp_forward_complex")
             return out
         strides = (ctypes.c_int64 * 3 * 3)()
         for i, t in enumerate(ins):
             sb, _, sf, st = t.stride()
             strides[i][0], strides[i][1], strides[i][2] = sb, sf, st
         ptrs = [t.data_ptr() for t in ins] + [None] * (3 - len(ins))
-        for attempt in (0, 1):
+
+        def enqueue():
             with torch.cuda.device(device):
                 if lengths is not None:
-                    rc = lib.fsnp_forward_lengths(self._handle, ptrs[0], ptrs[1], ptrs[2], ctypes.byref(strides), lengths,
-                                                  out.data_ptr(), batch_size, num_frames, ctypes.c_void_p(stream))
-                else:
-                    rc = lib.fsnp_forward(self._handle, ptrs[0], ptrs[1], ptrs[2],
-                                          ctypes.byref(strides), out.data_ptr(), batch_size, num_frames,
-                                          mode, int(batch_offset), gb, ctypes.c_void_p(stream))
-            if rc != _lib.ERR_STALE_WEIGHTS or attempt:
-                break
-            self._stale_weights_noticed(device)       # the watch flagged an EARLIER forward: re-pack, say so, run this one
-        _lib.check(rc, "fsnp_forward")
+                    return lib.fsnp_forward_lengths(self._handle, ptrs[0], ptrs[1], ptrs[2], ctypes.byref(strides), lengths,
+                                                    out.data_ptr(), batch_size, num_frames, ctypes.c_void_p(stream))
+                return lib.fsnp_forward(self._handle, ptrs[0], ptrs[1], ptrs[2],
+                                        ctypes.byref(strides), out.data_ptr(), batch_size, num_frames,
+                                        mode, int(batch_offset), gb, ctypes.c_void_p(stream))
+        _policy.enqueue_retrying_stale(enqueue, self._stale_weights_noticed, "fsnp_forward")
         return out
 
-    def _stale_weights_noticed(self, device):
-        import warnings
+    def _stale_weights_noticed(self):
+        """The weight watch flagged an EARLIER call (_policy.enqueue_retrying_stale): say so and re-pack."""
         warnings.warn("fullsubnet_plus_amd: parameters were modified in place through .data after they were packed; forwards since "
                       "that edit ran on the OLD weights (error_check='deferred' does not wait for the watch).  Re-packing now; call "
                       "model.refresh_weights() after such edits", RuntimeWarning)
-        self._hip.packed_key = None
-        self._ensure_handle(device)
+        self._repack()
 
-    def _checked(self, run, device):
-        """Runs `run()` (one forward) under the handle's error policy (see error_check in _init_hip)."""
-        out = run()
-        if self.error_check != "sync":
-            return out
+    def _repack(self):
+        self._hip.packed_key = None
+        self._ensure_handle(self._hip.device)
+
+    def _wait_and_poll(self):
+        """Wait for everything enqueued on the handle's device's current stream -> fsnp_poll_errors' code."""
         if self._pipeline:
             self.flush()
-        torch.cuda.current_stream(device).synchronize()
+        torch.cuda.current_stream(self._hip.device).synchronize()
+        return _lib.load().fsnp_poll_errors(self._handle)
+
+    def _checked(self, run):
+        """Runs `run()` (one forward) under the handle's error policy (see error_check in _init_hip, and _policy)."""
+        return _policy.run_checked(run, "fsnp_forward", sync=self.error_check == "sync", wait_and_poll=self._wait_and_poll,
+                                   repack=self._repack, fallback=self._one_tile_per_cu)
+
+    def _one_tile_per_cu(self, run):
+        """_policy.run_checked's fallback after a timed-out or wrongly verified exchange: the batch once more on the kernel without one
+        (a model that has no such kernel still defers its column-split chunks when pipelined: _wait_and_poll's flush)."""
         lib = _lib.load()
-        rc = lib.fsnp_poll_errors(self._handle)
-        if rc == 0:
-            return out
-        if rc == _lib.ERR_STALE_WEIGHTS:
-            # the weight watch: a parameter was edited through .data since the pack - this forward ran on the old weights.
-            # Re-pack and run it again; the caller never sees the stale result (same contract as a timed-out launch).
-            self._hip.packed_key = None
-            out = run()
-            if self._pipeline:
-                self.flush()
-            torch.cuda.current_stream(device).synchronize()
-            _lib.check(lib.fsnp_poll_errors(self._handle), "fsnp_forward (after re-packing the weights)")
-            return out
-        msg = _lib.last_error()
-        import warnings
-        warnings.warn(f"fullsubnet_plus_amd: {msg}; re-running this batch on the one-tile-per-CU kernel", RuntimeWarning)
+        warnings.warn(f"fullsubnet_plus_amd: {_lib.last_error()}; re-running this batch on the one-tile-per-CU kernel", RuntimeWarning)
         prev = self.__dict__.get("_lstm_coop_mode", 1)
         _lib.check(lib.fsnp_debug_set_lstm_coop(self._handle, 0), "fsnp_debug_set_lstm_coop")
         try:
             out = run()
-            if self._pipeline:
-                self.flush()        # a model without a one-tile-per-CU kernel still defers its column-split chunks
-            torch.cuda.current_stream(device).synchronize()
-            _lib.check(lib.fsnp_poll_errors(self._handle), "fsnp_forward (retry)")
+            _lib.check(self._wait_and_poll(), "fsnp_forward (retry)")
         finally:
             lib.fsnp_debug_set_lstm_coop(self._handle, prev)      # the mode the caller had set (debug_set_lstm_coop), not always 1
         return out
@@ -631,8 +598,7 @@ class _HipModel(nn.Module):
         """the forward fed with the complex64 STFT itself ([B, F, T], any strides - torch.stft's
         output is consumed in place); mag / real / imag are derived inside the HIP repack kernel instead of by the
         three torch ops of inferencer.py:143-147.  Same result as forward(|X|, X.real, X.imag, lengths=lengths)."""
-        return self._checked(lambda: self._forward_impl([noisy_complex], batch_offset, global_batch, complex_in=True, lengths=lengths),
-                             noisy_complex.device)
+        return self._checked(lambda: self._forward_impl([noisy_complex], batch_offset, global_batch, complex_in=True, lengths=lengths))
 
     def enhance(self, noisy_complex, lengths=None):
         """SURVEY.md 8(f-1) + (f-3): model forward + decompress_cIRM + complex multiply, all in HIP - lines 143-157 of
@@ -696,22 +662,27 @@ class _HipModel(nn.Module):
         FullSubNet): noisy waveform [B, samples] -> enhanced waveform [B, samples]; STFT, model (all bins), cIRM
         decompression, complex multiply and iSTFT all run in HIP on the caller's stream.  lengths: None, or SAMPLES per
         utterance (a Python sequence or a CPU integer tensor): row b is then enhance_wave(noisy[b:b+1, :lengths[b]]) of that
-        clip alone, and 0 past lengths[b]."""
+        clip alone, and 0 past lengths[b].  Follows error_check like forward: under "deferred", too, a `.data` edit that the weight
+        watch flagged on an earlier call is answered by a RuntimeWarning, a re-pack and the edited weights' result."""
         assert self.output_size == 2, "the cIRM epilogue needs the two mask channels (decompress_cIRM, acoustics/mask.py:60-63)"
         samples = None if lengths is None else _host_lengths(lengths, noisy.shape[0], f"{self.__class__.__name__}.enhance_wave")
         wav, lib, stream = self._wave_args(noisy)
         B, L = wav.shape
         out = torch.empty((B, L), dtype=torch.float32, device=wav.device)
-        def run():
+        what = "fsnp_enhance_wave" if samples is None else "fsnp_enhance_wave_lengths"
+
+        def enqueue():
             with torch.cuda.device(wav.device):
                 if samples is not None:
-                    _lib.check(lib.fsnp_enhance_wave_lengths(self._handle, wav.data_ptr(), wav.stride(0), out.data_ptr(), out.stride(0),
-                                                             samples, B, L, ctypes.c_void_p(stream)), "fsnp_enhance_wave_lengths")
-                else:
-                    _lib.check(lib.fsnp_enhance_wave(self._handle, wav.data_ptr(), wav.stride(0), out.data_ptr(), out.stride(0), B, L,
-                                                     ctypes.c_void_p(stream)), "fsnp_enhance_wave")
+                    return lib.fsnp_enhance_wave_lengths(self._handle, wav.data_ptr(), wav.stride(0), out.data_ptr(), out.stride(0),
+                                                         samples, B, L, ctypes.c_void_p(stream))
+                return lib.fsnp_enhance_wave(self._handle, wav.data_ptr(), wav.stride(0), out.data_ptr(), out.stride(0), B, L,
+                                             ctypes.c_void_p(stream))
+
+        def run():
+            _policy.enqueue_retrying_stale(enqueue, self._stale_weights_noticed, what)
             return out
-        return self._checked(run, wav.device)
+        return self._checked(run)
 
     def _apply_cirm(self, mask, noisy_complex, lengths=None):
         """lengths: None, or the ctypes int32[B] of _host_lengths (frames >= lengths[b] of row b are written as 0)."""
@@ -1028,8 +999,7 @@ class FullSubNet_Plus(_HipModel):
             clips of different lengths (batch_mode "full" only): row b is then, at frames [0, lengths[b]), the forward of
             x[b:b+1, ..., :lengths[b]] alone, and exactly 0 at frames [lengths[b], T).  Input frames past lengths[b] are never read.
         """
-        return self._checked(lambda: self._forward_impl([noisy_mag, noisy_real, noisy_imag], batch_offset, global_batch, lengths=lengths),
-                             noisy_mag.device)
+        return self._checked(lambda: self._forward_impl([noisy_mag, noisy_real, noisy_imag], batch_offset, global_batch, lengths=lengths))
 
     def open_stream(self, slots, max_chunk=16, device="cuda", live=False):
         """FullSubNet+ is not streamable (see fullsubnet_plus_amd.stream): always raises NotImplementedError with the reason."""
@@ -1125,7 +1095,7 @@ class FullSubNet(_HipModel):
     def forward(self, noisy_mag, batch_offset=0, global_batch=None, lengths=None):
         """noisy_mag [B, 1, F, T] fp32 CUDA tensor (any strides) -> cIRM [B, 2, F, T] (see FullSubNet_Plus.forward
         for batch_mode, the sharding arguments and lengths)."""
-        return self._checked(lambda: self._forward_impl([noisy_mag], batch_offset, global_batch, lengths=lengths), noisy_mag.device)
+        return self._checked(lambda: self._forward_impl([noisy_mag], batch_offset, global_batch, lengths=lengths))
 
     def open_stream(self, slots, max_chunk=16, device="cuda", live=False):
         """-> fullsubnet_plus_amd.stream.Stream: `slots` independent live streams that are fed a few frames per push and carry the

@@ -19,7 +19,8 @@ import ctypes
 
 import torch
 
-from . import _lib
+from . import _lib, _policy
+from ._args import _host_lengths
 
 PLUS_REASON = ("FullSubNet+ cannot be streamed exactly: its full-band TCN blocks are not causal and normalise with GroupNorm(1, C) over "
                "the whole clip, and TSSE pools over all of time; stream the original FullSubNet (fullsubnet_plus_amd.FullSubNet) with a "
@@ -53,30 +54,31 @@ def wave_refusal(model):
     return None
 
 
-class Stream:
-    """`slots` independent live streams on one FullSubNet (FullSubNet.open_stream).  Everything runs on the current CUDA stream; a push
-    allocates nothing but its output tensor and never synchronises (under the model's error_check="sync" it then waits and polls, as
-    forward does)."""
+def _slot_array(slots):
+    """None (every slot) or slot indices -> (ctypes int32 array or None, count)"""
+    if slots is None:
+        return None, 0
+    vals = [int(v) for v in slots]
+    return (ctypes.c_int32 * max(len(vals), 1))(*vals), len(vals)
 
-    def __init__(self, model, slots, max_chunk, device, live=False):
-        why = refusal(model)
-        if why is not None:
-            raise NotImplementedError(f"{model.__class__.__name__}.open_stream: {why}")
-        self.model, self.slots, self.max_chunk, self.device = model, int(slots), int(max_chunk), device
-        self.look_ahead, self.num_freqs = model.look_ahead, model.num_freqs
-        self._lib = model._ensure_handle(device)
+
+class _Session:
+    """What Stream and WaveStream share: the C session behind the symbols `_prefix`_*, its lifetime, the slots' state records, and the
+    model's error policy (_policy) around every call that enqueues work.  `live` is the subclass's to set."""
+    _prefix = _opener = None         # "fsnp_stream" / "fsnp_wave_stream"; the FullSubNet method that opens one, for messages
+
+    def __init__(self, model, slots, limit, device, live):
+        self.model, self.slots, self.device, self.look_ahead = model, int(slots), device, model.look_ahead
+        lib = self._lib = model._ensure_handle(device)
         self._owner = model._hip.handle.value
+        for name in ("destroy", "reset", "get_state", "set_state", "state_bytes"):
+            setattr(self, "_" + name, getattr(lib, f"{self._prefix}_{name}"))
+        create = f"{self._prefix}_create_live" if live else f"{self._prefix}_create"
         sp = ctypes.c_void_p()
         with torch.cuda.device(device):
-            if live:
-                _lib.check(self._lib.fsnp_stream_create_live(model._hip.handle, self.slots, self.max_chunk, ctypes.byref(sp)),
-                           "fsnp_stream_create_live")
-            else:
-                _lib.check(self._lib.fsnp_stream_create(model._hip.handle, self.slots, self.max_chunk, ctypes.byref(sp)), "fsnp_stream_create")
-        self._st = sp
-        self.live = bool(self._lib.fsnp_stream_is_live(sp))      # what the library made, not what was asked for
-        self.state_bytes = int(self._lib.fsnp_stream_state_bytes(sp))
-        self._backup = None
+            _lib.check(getattr(lib, create)(model._hip.handle, self.slots, int(limit), ctypes.byref(sp)), create)
+        self._st, self._backup = sp, None
+        self.state_bytes = int(self._state_bytes(sp))
 
     # ------------------------------------------------------------------ plumbing
     def _session(self):
@@ -84,7 +86,7 @@ class Stream:
             raise RuntimeError("this stream is closed")
         h = self.model._hip.handle
         if h is None or h.value != self._owner:
-            raise RuntimeError("the model's HIP handle was re-created (device change or copy) since open_stream: open a new stream")
+            raise RuntimeError(f"the model's HIP handle was re-created (device change or copy) since {self._opener}: open a new stream")
         return self._st
 
     def _cuda_stream(self):
@@ -95,7 +97,7 @@ class Stream:
         h = self.model._hip.handle
         if st is not None and h is not None and h.value == self._owner:      # (a destroyed handle took nothing of the session with it)
             with torch.cuda.device(self.device):
-                self._lib.fsnp_stream_destroy(st)
+                self._destroy(st)
 
     def __del__(self):
         try:
@@ -109,7 +111,85 @@ class Stream:
     def __exit__(self, *exc):
         self.close()
 
-    # ------------------------------------------------------------------ the session
+    def _guarded(self, enqueue, out, what):
+        """enqueue() -> rc enqueues one library call that fills `out`.  Under error_check="sync" a call that the weight watch flags ran on
+        the OLD weights and has advanced the states: they are put back to what it started from before it runs again."""
+        model = self.model
+        if model.error_check != "sync":      # a live push is host time: "deferred" is this one call, with nothing built around it
+            _policy.enqueue_retrying_stale(enqueue, model._stale_weights_noticed, what)
+            return out
+
+        def run():
+            _policy.enqueue_retrying_stale(enqueue, model._stale_weights_noticed, what)
+            return out
+        # only watched parameters can be flagged (an unwatched model registers none with fsnp_watch_weights), so a session without
+        # save / restore never sees the code that would run its push twice
+        watched = model.__dict__.get("_fsnp_watched", False)
+        return _policy.run_checked(run, what, sync=True, wait_and_poll=self._wait_and_poll, repack=model._repack,
+                                   save=self._save_states if watched else None, restore=self._restore_states if watched else None)
+
+    def _wait_and_poll(self):
+        torch.cuda.current_stream(self.device).synchronize()
+        return self._lib.fsnp_poll_errors(self.model._handle)
+
+    def _save_states(self):
+        if self._backup is None:
+            self._backup = torch.empty((self.slots, self.state_bytes), dtype=torch.uint8, device=self.device)
+        for b in range(self.slots):
+            with torch.cuda.device(self.device):
+                _lib.check(self._get_state(self._st, b, self._backup[b].data_ptr(), self._cuda_stream()), f"{self._prefix}_get_state")
+
+    def _restore_states(self):
+        for b in range(self.slots):
+            with torch.cuda.device(self.device):
+                _lib.check(self._set_state(self._st, b, self._backup[b].data_ptr(), self._cuda_stream()), f"{self._prefix}_set_state")
+
+    def _counter(self, name, slot):
+        st = self._session()
+        v = ctypes.c_int64()
+        with torch.cuda.device(self.device):
+            _lib.check(getattr(self._lib, f"{self._prefix}_{name}")(st, int(slot), ctypes.byref(v)), f"{self._prefix}_{name}")
+        return int(v.value)
+
+    # ------------------------------------------------------------------ the slots' state
+    def reset(self, slots=None):
+        """Stream-ordered zeroing of the state of `slots` (None: all): the next push starts a fresh clip there."""
+        st = self._session()
+        arr, num = _slot_array(slots)
+        with torch.cuda.device(self.device):
+            _lib.check(self._reset(st, arr, num, self._cuda_stream()), f"{self._prefix}_reset")
+
+    def state(self, slot):
+        """-> torch.uint8 CUDA tensor [state_bytes]: the slot's whole state (kernel-independent layout: the session's header, include/fsnp_stream.h
+        or include/fsnp_wave_stream.h)."""
+        st = self._session()
+        buf = torch.empty(self.state_bytes, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._get_state(st, int(slot), buf.data_ptr(), self._cuda_stream()), f"{self._prefix}_get_state")
+        return buf
+
+    def load_state(self, slot, tensor):
+        """Load what state() of a slot of any session of a model of the same sizes returned."""
+        st = self._session()
+        if tensor.dtype != torch.uint8 or tensor.numel() != self.state_bytes:
+            raise ValueError(f"load_state: expected a torch.uint8 tensor of {self.state_bytes} bytes, got {tensor.dtype} x {tensor.numel()}")
+        t = tensor.to(self.device).contiguous()
+        with torch.cuda.device(self.device):
+            _lib.check(self._set_state(st, int(slot), t.data_ptr(), self._cuda_stream()), f"{self._prefix}_set_state")
+
+
+class Stream(_Session):
+    """`slots` independent live streams on one FullSubNet.  Open one through FullSubNet.open_stream, which refuses a model that cannot be
+    streamed before any GPU is touched.  Everything runs on the current CUDA stream; a push
+    allocates nothing but its output tensor and never synchronises (under the model's error_check="sync" it then waits and polls, as
+    forward does)."""
+    _prefix, _opener = "fsnp_stream", "open_stream"
+
+    def __init__(self, model, slots, max_chunk, device, live=False):
+        super().__init__(model, slots, max_chunk, device, live)
+        self.max_chunk, self.num_freqs = int(max_chunk), model.num_freqs
+        self.live = bool(self._lib.fsnp_stream_is_live(self._st))      # what the library made, not what was asked for
+
     def push(self, noisy_mag, counts=None):
         """noisy_mag [slots, 1, F, n] fp32 CUDA tensor (any strides), n <= max_chunk; counts: None (n frames for every slot) or frames
         per slot (a Python sequence or a CPU integer tensor, 0 <= counts[b] <= n; input past counts[b] is never read) -> [slots, 2, F, n]:
@@ -125,53 +205,15 @@ class Stream:
                                "There is deliberately no CPU fallback.")
         assert noisy_mag.device == self.device
         x = noisy_mag if noisy_mag.dtype == torch.float32 else noisy_mag.float()
-        cnt = None if counts is None else _lib_counts(counts, S)
+        cnt = None if counts is None else _host_lengths(counts, S, "Stream.push")
         sb, _, sf, stt = x.stride()
         strides = (ctypes.c_int64 * 3)(sb, sf, stt)
-        model, lib = self.model, self._lib
-        sync = model.error_check == "sync"
+        out = torch.empty((S, 2, F, n), dtype=torch.float32, device=self.device)
 
-        def run():
-            out = torch.empty((S, 2, F, n), dtype=torch.float32, device=self.device)
-            for attempt in (0, 1):
-                with torch.cuda.device(self.device):
-                    rc = lib.fsnp_stream_push(st, x.data_ptr(), ctypes.byref(strides), cnt, out.data_ptr(), n, self._cuda_stream())
-                if rc != _lib.ERR_STALE_WEIGHTS or attempt:
-                    break
-                model._stale_weights_noticed(self.device)      # the watch flagged an EARLIER call: re-pack, say so, run this push
-            _lib.check(rc, "fsnp_stream_push")
-            return out
-
-        if not sync:
-            return run()
-        # error_check="sync": a push whose weight watch fires ran on the OLD weights and has advanced the state; keep what it started from
-        watched = model.__dict__.get("_fsnp_watched", False)
-        if watched:
-            self._save_states()
-        out = run()
-        torch.cuda.current_stream(self.device).synchronize()
-        rc = lib.fsnp_poll_errors(model._handle)
-        if rc == _lib.ERR_STALE_WEIGHTS and watched:
-            self._restore_states()
-            model._hip.packed_key = None
-            model._ensure_handle(self.device)
-            out = run()
-            torch.cuda.current_stream(self.device).synchronize()
-            rc = lib.fsnp_poll_errors(model._handle)
-        _lib.check(rc, "fsnp_stream_push")
-        return out
-
-    def _save_states(self):
-        if self._backup is None:
-            self._backup = torch.empty((self.slots, self.state_bytes), dtype=torch.uint8, device=self.device)
-        for b in range(self.slots):
+        def enqueue():
             with torch.cuda.device(self.device):
-                _lib.check(self._lib.fsnp_stream_get_state(self._st, b, self._backup[b].data_ptr(), self._cuda_stream()), "fsnp_stream_get_state")
-
-    def _restore_states(self):
-        for b in range(self.slots):
-            with torch.cuda.device(self.device):
-                _lib.check(self._lib.fsnp_stream_set_state(self._st, b, self._backup[b].data_ptr(), self._cuda_stream()), "fsnp_stream_set_state")
+                return self._lib.fsnp_stream_push(st, x.data_ptr(), ctypes.byref(strides), cnt, out.data_ptr(), n, self._cuda_stream())
+        return self._guarded(enqueue, out, "fsnp_stream_push")
 
     def tail(self, slots=None):
         """Push look_ahead all-zero frames (the reference's own pad) into `slots` (None: all): the masks of the last look_ahead frames.
@@ -185,160 +227,25 @@ class Stream:
         counts = None if slots is None else [la if b in set(int(v) for v in slots) else 0 for b in range(self.slots)]
         return self.push(zeros, counts)
 
-    def reset(self, slots=None):
-        """Stream-ordered zeroing of the state of `slots` (None: all): the next push starts a fresh clip there."""
-        st = self._session()
-        if slots is None:
-            arr, num = None, 0
-        else:
-            vals = [int(v) for v in slots]
-            arr, num = (ctypes.c_int32 * max(len(vals), 1))(*vals), len(vals)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.fsnp_stream_reset(st, arr, num, self._cuda_stream()), "fsnp_stream_reset")
-
-    def state(self, slot):
-        """-> torch.uint8 CUDA tensor [state_bytes]: the slot's whole state (kernel-independent layout, include/fsnp_stream.h)."""
-        st = self._session()
-        buf = torch.empty(self.state_bytes, dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.fsnp_stream_get_state(st, int(slot), buf.data_ptr(), self._cuda_stream()), "fsnp_stream_get_state")
-        return buf
-
-    def load_state(self, slot, tensor):
-        """Load what state() of a slot of any session of a model of the same sizes returned."""
-        st = self._session()
-        if tensor.dtype != torch.uint8 or tensor.numel() != self.state_bytes:
-            raise ValueError(f"load_state: expected a torch.uint8 tensor of {self.state_bytes} bytes, got {tensor.dtype} x {tensor.numel()}")
-        t = tensor.to(self.device).contiguous()
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.fsnp_stream_set_state(st, int(slot), t.data_ptr(), self._cuda_stream()), "fsnp_stream_set_state")
-
     def frames(self, slot):
         """Frames pushed into `slot` since its last reset (host-side count; after load_state the first call waits for that copy)."""
-        st = self._session()
-        v = ctypes.c_int64()
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.fsnp_stream_frames(st, int(slot), ctypes.byref(v)), "fsnp_stream_frames")
-        return int(v.value)
+        return self._counter("frames", slot)
 
 
-def _lib_counts(counts, slots, what="Stream.push"):
-    from .model import _host_lengths
-    return _host_lengths(counts, slots, what)
-
-
-def _slot_array(slots):
-    """None (every slot) or slot indices -> (ctypes int32 array or None, count)"""
-    if slots is None:
-        return None, 0
-    vals = [int(v) for v in slots]
-    return (ctypes.c_int32 * max(len(vals), 1))(*vals), len(vals)
-
-
-class WaveStream:
-    """`slots` independent live audio streams on one FullSubNet (FullSubNet.open_wave_stream): blocks of samples in, the same number of
+class WaveStream(_Session):
+    """`slots` independent live audio streams on one FullSubNet (open one through FullSubNet.open_wave_stream, which refuses a model that
+    cannot stream waveforms before any GPU is touched): blocks of samples in, the same number of
     enhanced samples out, `delay` = (2 + look_ahead) * hop samples late.  All push outputs of a clip followed by its finish() output,
     without the first `delay` samples, are enhance_wave() of that clip alone, whatever the block sizes.  Everything runs on the current
     CUDA stream; a push allocates nothing but its output tensor and never synchronises (under the model's error_check="sync" it then
     waits and polls, as forward does)."""
+    _prefix, _opener = "fsnp_wave_stream", "open_wave_stream"
 
     def __init__(self, model, slots, max_samples, device, live=False):
-        why = wave_refusal(model)
-        if why is not None:
-            raise NotImplementedError(f"{model.__class__.__name__}.open_wave_stream: {why}")
-        self.model, self.slots, self.max_samples, self.device = model, int(slots), int(max_samples), device
-        self.look_ahead, self.hop = model.look_ahead, model.num_freqs - 1
-        self._lib = model._ensure_handle(device)
-        self._owner = model._hip.handle.value
-        sp = ctypes.c_void_p()
-        with torch.cuda.device(device):
-            create, what = ((self._lib.fsnp_wave_stream_create_live, "fsnp_wave_stream_create_live") if live
-                            else (self._lib.fsnp_wave_stream_create, "fsnp_wave_stream_create"))
-            _lib.check(create(model._hip.handle, self.slots, self.max_samples, ctypes.byref(sp)), what)
-        self._st = sp
-        self.live = bool(live)
-        self.delay = int(self._lib.fsnp_wave_stream_delay(sp))
-        self.state_bytes = int(self._lib.fsnp_wave_stream_state_bytes(sp))
-        self._backup = None
+        super().__init__(model, slots, max_samples, device, live)
+        self.max_samples, self.hop = int(max_samples), model.num_freqs - 1
+        self.delay, self.live = int(self._lib.fsnp_wave_stream_delay(self._st)), bool(live)
 
-    # ------------------------------------------------------------------ plumbing
-    def _session(self):
-        if self._st is None:
-            raise RuntimeError("this stream is closed")
-        h = self.model._hip.handle
-        if h is None or h.value != self._owner:
-            raise RuntimeError("the model's HIP handle was re-created (device change or copy) since open_wave_stream: open a new stream")
-        return self._st
-
-    def _cuda_stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def close(self):
-        st, self._st = self._st, None
-        h = self.model._hip.handle
-        if st is not None and h is not None and h.value == self._owner:
-            with torch.cuda.device(self.device):
-                self._lib.fsnp_wave_stream_destroy(st)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def _guarded(self, run, what):
-        """run() -> (rc, out) enqueues one call.  As Stream.push: the watch's verdict on an EARLIER call is answered by a re-pack and one
-        more try; under error_check="sync" a call the watch flags ran on the old weights, so the states it started from are put back."""
-        model, lib = self.model, self._lib
-
-        def attempt():
-            for again in (0, 1):
-                rc, out = run()
-                if rc != _lib.ERR_STALE_WEIGHTS or again:
-                    break
-                model._stale_weights_noticed(self.device)
-            _lib.check(rc, what)
-            return out
-
-        if model.error_check != "sync":
-            return attempt()
-        watched = model.__dict__.get("_fsnp_watched", False)
-        if watched:
-            self._save_states()
-        out = attempt()
-        torch.cuda.current_stream(self.device).synchronize()
-        rc = lib.fsnp_poll_errors(model._handle)
-        if rc == _lib.ERR_STALE_WEIGHTS and watched:
-            self._restore_states()
-            model._hip.packed_key = None
-            model._ensure_handle(self.device)
-            out = attempt()
-            torch.cuda.current_stream(self.device).synchronize()
-            rc = lib.fsnp_poll_errors(model._handle)
-        _lib.check(rc, what)
-        return out
-
-    def _save_states(self):
-        if self._backup is None:
-            self._backup = torch.empty((self.slots, self.state_bytes), dtype=torch.uint8, device=self.device)
-        for b in range(self.slots):
-            with torch.cuda.device(self.device):
-                _lib.check(self._lib.fsnp_wave_stream_get_state(self._st, b, self._backup[b].data_ptr(), self._cuda_stream()),
-                           "fsnp_wave_stream_get_state")
-
-    def _restore_states(self):
-        for b in range(self.slots):
-            with torch.cuda.device(self.device):
-                _lib.check(self._lib.fsnp_wave_stream_set_state(self._st, b, self._backup[b].data_ptr(), self._cuda_stream()),
-                           "fsnp_wave_stream_set_state")
-
-    # ------------------------------------------------------------------ the session
     def push(self, wav, counts=None):
         """wav [slots, n] fp32 CUDA tensor (rows of any stride), n <= max_samples; counts: None (n samples for every slot) or samples per
         slot (a Python sequence or a CPU integer tensor, 0 <= counts[b] <= n; input past counts[b] is never read) -> [slots, n]: column
@@ -355,15 +262,13 @@ class WaveStream:
         x = wav if wav.dtype == torch.float32 else wav.float()
         if n > 1 and x.stride(1) != 1:
             x = x.contiguous()
-        cnt = None if counts is None else _lib_counts(counts, S, "WaveStream.push")
+        cnt = None if counts is None else _host_lengths(counts, S, "WaveStream.push")
+        out = torch.empty((S, n), dtype=torch.float32, device=self.device)
 
-        def run():
-            out = torch.empty((S, n), dtype=torch.float32, device=self.device)
+        def enqueue():
             with torch.cuda.device(self.device):
-                rc = self._lib.fsnp_wave_stream_push(st, x.data_ptr(), x.stride(0), cnt, out.data_ptr(), n, n, self._cuda_stream())
-            return rc, out
-
-        return self._guarded(run, "fsnp_wave_stream_push")
+                return self._lib.fsnp_wave_stream_push(st, x.data_ptr(), x.stride(0), cnt, out.data_ptr(), n, n, self._cuda_stream())
+        return self._guarded(enqueue, out, "fsnp_wave_stream_push")
 
     def finish(self, slots=None):
         """End the clips of `slots` (None: all) -> [slots, delay]: each clip's last `delay` samples (exactly 0 where the clip is shorter);
@@ -371,43 +276,18 @@ class WaveStream:
         a fresh clip.  A slot that holds 1 .. hop samples is refused, as enhance_wave refuses such a clip."""
         st = self._session()
         arr, num = _slot_array(slots)
+        out = torch.empty((self.slots, self.delay), dtype=torch.float32, device=self.device)
 
-        def run():
-            out = torch.empty((self.slots, self.delay), dtype=torch.float32, device=self.device)
+        def enqueue():
             with torch.cuda.device(self.device):
-                rc = self._lib.fsnp_wave_stream_finish(st, arr, num, out.data_ptr(), self.delay, self._cuda_stream())
-            return rc, out
-
-        return self._guarded(run, "fsnp_wave_stream_finish")
-
-    def reset(self, slots=None):
-        """Stream-ordered zeroing of the state of `slots` (None: all): the next push starts a fresh clip there."""
-        st = self._session()
-        arr, num = _slot_array(slots)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.fsnp_wave_stream_reset(st, arr, num, self._cuda_stream()), "fsnp_wave_stream_reset")
-
-    def state(self, slot):
-        """-> torch.uint8 CUDA tensor [state_bytes]: the slot's whole state (kernel-independent layout, include/fsnp_wave_stream.h)."""
-        st = self._session()
-        buf = torch.empty(self.state_bytes, dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.fsnp_wave_stream_get_state(st, int(slot), buf.data_ptr(), self._cuda_stream()), "fsnp_wave_stream_get_state")
-        return buf
+                return self._lib.fsnp_wave_stream_finish(st, arr, num, out.data_ptr(), self.delay, self._cuda_stream())
+        return self._guarded(enqueue, out, "fsnp_wave_stream_finish")
 
     def load_state(self, slot, tensor):
         """Load what state() of a slot of any wave session of a model of the same sizes returned.  A migration call: it waits once for the
         copy, to learn the slot's sample count."""
-        st = self._session()
-        if tensor.dtype != torch.uint8 or tensor.numel() != self.state_bytes:
-            raise ValueError(f"load_state: expected a torch.uint8 tensor of {self.state_bytes} bytes, got {tensor.dtype} x {tensor.numel()}")
-        t = tensor.to(self.device).contiguous()
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.fsnp_wave_stream_set_state(st, int(slot), t.data_ptr(), self._cuda_stream()), "fsnp_wave_stream_set_state")
+        super().load_state(slot, tensor)
 
     def samples(self, slot):
         """Samples pushed into `slot` since its last reset or finish (host-side count)."""
-        st = self._session()
-        v = ctypes.c_int64()
-        _lib.check(self._lib.fsnp_wave_stream_samples(st, int(slot), ctypes.byref(v)), "fsnp_wave_stream_samples")
-        return int(v.value)
+        return self._counter("samples", slot)

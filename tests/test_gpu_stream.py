@@ -314,3 +314,32 @@ def test_refusals_and_weight_edits():
     e1, e2 = rel_err(o1[0, ..., 2:].cpu().numpy(), w1[..., :2].numpy()), rel_err(o2[0].cpu().numpy(), w2[..., 2:].numpy())
     print(f"weight edit between pushes: before {e1:.3e}, after (edited weights) {e2:.3e}")
     assert e1 < TOL and e2 < TOL
+
+
+def test_deferred_weight_edit_is_answered_by_the_push_after_the_flagged_one():
+    """The error_check="deferred" twin of the weight-edit case above.  Nothing waits for the weight watch: the push after a .data edit runs
+    on the OLD weights and is flagged (its output is not asserted); the push after that one is told, warns, re-packs and - like every
+    push from then on - returns the edited weights' masks."""
+    args = _args("cumulative_layer_norm")
+    sd = make_state_dict_fullsubnet(28, "default")
+    m = _model(args, sd, "deferred")
+    clip = make_spec(1, 6, 902)[0]
+    with m.open_stream(1, max_chunk=4) as st:
+        o1 = st.push(clip[..., :2].contiguous().cuda())
+        with torch.no_grad():
+            m.sb_model.fc_output_layer.weight.data.mul_(2.0)
+            m.sb_model.fc_output_layer.bias.data.mul_(2.0)
+        st.push(clip[..., 2:4].contiguous().cuda())                # the flagged push
+        torch.cuda.synchronize()
+        with pytest.warns(RuntimeWarning, match="through .data"):
+            o3 = st.push(torch.cat([clip[..., 4:], torch.zeros(1, 1, F, 2)], dim=-1).cuda())
+        assert st.frames(0) == 8
+        m.check_errors()
+    sd2 = dict(sd)
+    sd2["sb_model.fc_output_layer.weight"] = sd["sb_model.fc_output_layer.weight"] * 2.0
+    sd2["sb_model.fc_output_layer.bias"] = sd["sb_model.fc_output_layer.bias"] * 2.0
+    w2 = fsnp_torch.forward_fullsubnet_full(sd2, clip, **stream_kwargs(args))[0]
+    assert torch.count_nonzero(o1) == 0                             # steps 0 and 1: look_ahead 2
+    err = rel_err(o3[0].cpu().numpy(), w2[..., 2:].numpy())         # steps 4 .. 7: the masks of frames 2 .. 5
+    print(f"deferred weight edit: after the warning (edited weights) {err:.3e}")
+    assert err < TOL, err

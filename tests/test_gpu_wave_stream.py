@@ -325,3 +325,31 @@ def test_refusals_and_weight_edits():
     e2 = float((got[D + 3 * HOP:] - w2[3 * HOP:]).abs().max() / w2.abs().max())
     print(f"weight edit between pushes: before {e1:.3e}, after (edited weights) {e2:.3e}")
     assert e1 < TOL and e2 < TOL
+
+
+def test_deferred_enhance_wave_answers_a_flagged_weight_edit_like_forward():
+    """error_check="deferred": the enhance_wave after a .data edit runs on the OLD weights and is flagged; the next one warns, re-packs and
+    returns the edited weights' waveform, as forward and the pushes do (it used to raise code 6)."""
+    args = _args("cumulative_layer_norm")
+    sd = make_state_dict_fullsubnet(37, "default")
+    m = _model(args, sd)
+    assert m.error_check == "deferred"
+    clip = wave_clip(8 * HOP + 5, 2601)
+    x = clip[None].cuda()
+    m.enhance_wave(x)
+    with torch.no_grad():
+        m.sb_model.fc_output_layer.weight.data.mul_(2.0)
+        m.sb_model.fc_output_layer.bias.data.mul_(2.0)
+    m.enhance_wave(x)                                              # the flagged call
+    torch.cuda.synchronize()
+    with pytest.warns(RuntimeWarning, match="through .data"):
+        got = m.enhance_wave(x)
+    sd2 = dict(sd)
+    sd2["sb_model.fc_output_layer.weight"] = sd["sb_model.fc_output_layer.weight"] * 2.0
+    sd2["sb_model.fc_output_layer.bias"] = sd["sb_model.fc_output_layer.bias"] * 2.0
+    err = _err(got[0].cpu(), _oracle(sd2, clip, args))
+    print(f"deferred enhance_wave after a weight edit: rel err (edited weights) {err:.3e}")
+    assert err < TOL, err
+    m.refresh_weights()
+    assert torch.equal(m.enhance_wave(x), got)
+    m.check_errors()
