@@ -145,6 +145,19 @@ LIVE_STREAM_SYMBOLS = {
     "fsnp_stream_is_live": (c_i32, [c_vp]),
 }
 
+# every symbol include/fsnp_spec_stream.h declares (spectrum sessions: STFT frames in, enhanced frames out; same ABI version)
+SPEC_STREAM_SYMBOLS = {
+    "fsnp_spec_stream_create": (c_i32, [c_vp, c_i32, c_i32, ctypes.POINTER(c_vp)]),
+    "fsnp_spec_stream_create_live": (c_i32, [c_vp, c_i32, c_i32, ctypes.POINTER(c_vp)]),
+    "fsnp_spec_stream_destroy": (None, [c_vp]),
+    "fsnp_spec_stream_push": (c_i32, [c_vp, c_vp, ctypes.POINTER(c_i64 * 3), ctypes.POINTER(c_i32), c_vp, ctypes.POINTER(c_i64 * 3), c_i32, c_vp]),
+    "fsnp_spec_stream_reset": (c_i32, [c_vp, ctypes.POINTER(c_i32), c_i32, c_vp]),
+    "fsnp_spec_stream_state_bytes": (c_i64, [c_vp]),
+    "fsnp_spec_stream_get_state": (c_i32, [c_vp, c_i32, c_vp, c_vp]),
+    "fsnp_spec_stream_set_state": (c_i32, [c_vp, c_i32, c_vp, c_vp]),
+    "fsnp_spec_stream_frames": (c_i32, [c_vp, c_i32, ctypes.POINTER(c_i64)]),
+}
+
 ABI_VERSION = 13         # FSNP_ABI_VERSION of the include/fsnp.h these signatures were written against
 
 _lib = None
@@ -167,7 +180,7 @@ def load(build_if_missing=True):
         raise RuntimeError(f"{path} is missing: run `python -m fullsubnet_plus_amd._build`")
     lib = ctypes.CDLL(path)
     for name, (res, args) in (list(SYMBOLS.items()) + list(LENGTHS_SYMBOLS.items()) + list(STREAM_SYMBOLS.items()) + list(WAVE_STREAM_SYMBOLS.items())
-                              + list(LIVE_STREAM_SYMBOLS.items())):
+                              + list(LIVE_STREAM_SYMBOLS.items()) + list(SPEC_STREAM_SYMBOLS.items())):
         fn = getattr(lib, name)          # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

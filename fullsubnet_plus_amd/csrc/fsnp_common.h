@@ -235,6 +235,23 @@ void launch_wave_apply(const WaveArgs& a, const float* mask, const float* spec, 
 // overlap-add with the window-envelope division over the frames fr [S][nrow][n_fft], into the fifo and out [S][ncols]: column j is
 // sample P + j - D (finish: L - D + j), exactly 0 where that is negative and past the slot's count (finish: in rows not finished)
 void launch_wave_ola(const WaveArgs& a, const float* fr, const float* window, float* out, long out_stride, int ncols, hipStream_t s);
+// spec_stream.hip : spectrum sessions (include/fsnp_spec_stream.h) - the two short launches around one mag push.  Per slot a ring
+// complex64 [look_ahead][F] behind the mag-stream record: the noisy spectra of the newest look_ahead frames, frame g in row
+// g % look_ahead (they wait for their masks).  Strides in complex elements for (slot, f, frame).
+struct SpecCounts { int v[512]; };                 // frames per slot of a push (ONE kernel argument block)
+struct SpecArgs {
+    unsigned char* ring;                           // ring of slot 0
+    size_t ring_stride;                            // bytes between slots
+    const StreamMeta* meta;                        // [S] {P, count} of this push, written by the mag push's prologue kernel
+    int S, F, FP, LA, n;
+};
+// mag [S][n][FP] = hypotf(re, im) of the c.v[slot] new frames of every slot (zeros behind them and in the pad bins; input frames
+// >= c.v[slot] are never read)
+void launch_spec_mag(const SpecArgs& a, const SpecCounts& c, const float* spec, const int64_t strides[3], float* mag, hipStream_t s);
+// out column j < count = cIRM of step P + j (mask [S][2][F][n]) times the noisy frame P + j - look_ahead (the ring's or this push's),
+// exactly 0 where there is no such frame yet and in columns >= count; then the ring takes the newest min(count, look_ahead) frames
+void launch_spec_apply(const SpecArgs& a, const float* mask, const float* spec, const int64_t strides[3], float* out,
+                       const int64_t out_strides[3], hipStream_t s);
 void stft_build_matrices(int n_fft, float* fwd /*[N2 pad 384][n_fft]*/, float* inv /*[n_fft pad 384][K pad 16]*/,
                          float* window /*[n_fft]*/);
 

@@ -1,8 +1,8 @@
 // fsnp_handle.h - the handle behind the C ABI (include/fsnp.h) and the helpers its translation units share:
 // fsnp_abi.hip (create / forward orchestration / workspace / calibration), forward_kernels.hip (the forward's small kernels),
 // fsnp_verify.hip (exchange verification), fsnp_debug_abi.hip (include/fsnp_debug.h: test and tuning hooks), fsnp_weights.hip
-// (strict weight loading + packing), fsnp_stft_abi.hip (STFT / iSTFT / waveform entry points), fsnp_stream_abi.hip and
-// fsnp_wave_stream_abi.hip (stream and wave sessions).  Host declarations only.
+// (strict weight loading + packing), fsnp_stft_abi.hip (STFT / iSTFT / waveform entry points), fsnp_stream_abi.hip,
+// fsnp_wave_stream_abi.hip and fsnp_spec_stream_abi.hip (stream, wave and spectrum sessions).  Host declarations only.
 #pragma once
 #include <map>
 #include <string>
@@ -234,5 +234,8 @@ int stream_push_body(fsnp_stream* st, const float* mag, const int64_t strides[3]
 // session creation behind fsnp_stream_create (live = 0) and fsnp_stream_create_live (live = 1: pushes run on lstm_step.hip, max_chunk <= kLiveMaxChunk)
 constexpr int kLiveMaxChunk = 16;
 int stream_create(fsnp_handle* h, int32_t slots, int32_t max_chunk, int live, const char* where, fsnp_stream** out);
+// where a session's prologue kernel publishes {P, count} of every slot of a push ([slots], device: the session's workspace), for the
+// kernels a spectrum session (fsnp_spec_stream_abi.hip) runs behind stream_push_body
+const StreamMeta* stream_meta(const fsnp_stream* st);
 
 }  // namespace fsnp

@@ -281,6 +281,8 @@ int stream_create(fsnp_handle* h, int32_t slots, int32_t max_chunk, int live, co
     return 0;
 }
 
+const StreamMeta* stream_meta(const fsnp_stream* st) { return reinterpret_cast<const StreamMeta*>(st->ws + st->w_meta); }
+
 }  // namespace fsnp
 
 extern "C" {

@@ -1011,6 +1011,11 @@ class FullSubNet_Plus(_HipModel):
         from .stream import PLUS_REASON
         raise NotImplementedError(f"{self.__class__.__name__}.open_wave_stream: {PLUS_REASON}")
 
+    def open_spec_stream(self, slots, max_chunk=16, device="cuda", live=False):
+        """FullSubNet+ is not streamable (see fullsubnet_plus_amd.stream): always raises NotImplementedError with the reason."""
+        from .stream import PLUS_REASON
+        raise NotImplementedError(f"{self.__class__.__name__}.open_spec_stream: {PLUS_REASON}")
+
 
 class _FullBandLSTMParams(_StageHolder):
     """Parameter holder named like SequenceModel(sequence_model="LSTM") of the original FullSubNet's full-band model
@@ -1126,6 +1131,19 @@ class FullSubNet(_HipModel):
         if why is not None:
             raise NotImplementedError(f"{self.__class__.__name__}.open_wave_stream: {why}")
         return WaveStream(self, slots, max_samples, _resolve_device(device), live=live)
+
+    def open_spec_stream(self, slots, max_chunk=16, device="cuda", live=False):
+        """-> fullsubnet_plus_amd.stream.SpecStream: `slots` independent live streams for a caller who owns the STFT (any window, any
+        overlap): up to max_chunk noisy complex64 frames in, as many enhanced frames out, look_ahead frames late
+        (include/fsnp_spec_stream.h).  The noisy frames wait for their masks inside the slot's state, which state() / load_state carry
+        whole.  A clip pushed in any chunking, followed by tail(), gives [look_ahead zero columns | enhance() of that clip alone].  The
+        refusals of open_stream apply (NotImplementedError with the reason, before any GPU is touched).  live=True: the model inside
+        runs as a live session (see open_stream); max_chunk <= 16."""
+        from .stream import SpecStream, spec_refusal
+        why = spec_refusal(self)
+        if why is not None:
+            raise NotImplementedError(f"{self.__class__.__name__}.open_spec_stream: {why}")
+        return SpecStream(self, slots, max_chunk, _resolve_device(device), live=live)
 
 
 Model = FullSubNet_Plus  # the name BASELINE.json's north_star uses

@@ -12,7 +12,14 @@ and the same for waveforms (include/fsnp_wave_stream.h): samples in, samples out
     ...
     out = wave.finish()                      # [8, wave.delay]: the clips' last samples; the slots are reset
 
-Both take live=True (include/fsnp_stream_live.h): the session mode for a few streams fed one hop at a time, on per-step kernels that
+and for a caller who owns the STFT (include/fsnp_spec_stream.h): noisy complex frames in, enhanced complex frames out, look_ahead late.
+
+    spec = model.open_spec_stream(slots=8, max_chunk=16)
+    enh = spec.push(noisy_complex)           # [8, F, n] complex64 -> [8, F, n]; column j = enhanced frame P + j - look_ahead
+    ...
+    enh = spec.tail()                        # look_ahead zero frames: the last look_ahead enhanced frames
+
+All three take live=True (include/fsnp_stream_live.h): the session mode for a few streams fed one hop at a time, on per-step kernels that
 fill the chip at one slot.  Same interface, same state records; max_chunk <= 16.
 """
 import ctypes
@@ -54,6 +61,16 @@ def wave_refusal(model):
     return None
 
 
+def spec_refusal(model):
+    """Why `model` (a FullSubNet) cannot stream spectra, or None: refusal(), and the cIRM epilogue's output_size.  No GPU is touched."""
+    why = refusal(model)
+    if why is not None:
+        return why
+    if model.output_size != 2:
+        return f"the cIRM epilogue needs output_size = 2 (this model: {model.output_size})"
+    return None
+
+
 def _slot_array(slots):
     """None (every slot) or slot indices -> (ctypes int32 array or None, count)"""
     if slots is None:
@@ -63,9 +80,9 @@ def _slot_array(slots):
 
 
 class _Session:
-    """What Stream and WaveStream share: the C session behind the symbols `_prefix`_*, its lifetime, the slots' state records, and the
+    """What Stream, WaveStream and SpecStream share: the C session behind the symbols `_prefix`_*, its lifetime, the slots' state records, and the
     model's error policy (_policy) around every call that enqueues work.  `live` is the subclass's to set."""
-    _prefix = _opener = None         # "fsnp_stream" / "fsnp_wave_stream"; the FullSubNet method that opens one, for messages
+    _prefix = _opener = None         # "fsnp_stream" / "fsnp_wave_stream" / "fsnp_spec_stream"; the FullSubNet method that opens one, for messages
 
     def __init__(self, model, slots, limit, device, live):
         self.model, self.slots, self.device, self.look_ahead = model, int(slots), device, model.look_ahead
@@ -160,8 +177,8 @@ class _Session:
             _lib.check(self._reset(st, arr, num, self._cuda_stream()), f"{self._prefix}_reset")
 
     def state(self, slot):
-        """-> torch.uint8 CUDA tensor [state_bytes]: the slot's whole state (kernel-independent layout: the session's header, include/fsnp_stream.h
-        or include/fsnp_wave_stream.h)."""
+        """-> torch.uint8 CUDA tensor [state_bytes]: the slot's whole state (kernel-independent layout: the session's header, include/fsnp_stream.h,
+        include/fsnp_wave_stream.h or include/fsnp_spec_stream.h)."""
         st = self._session()
         buf = torch.empty(self.state_bytes, dtype=torch.uint8, device=self.device)
         with torch.cuda.device(self.device):
@@ -291,3 +308,65 @@ class WaveStream(_Session):
     def samples(self, slot):
         """Samples pushed into `slot` since its last reset or finish (host-side count)."""
         return self._counter("samples", slot)
+
+
+class SpecStream(_Session):
+    """`slots` independent live streams on one FullSubNet for a caller who owns the STFT (open one through FullSubNet.open_spec_stream,
+    which refuses a model that cannot be streamed before any GPU is touched): noisy complex64 frames in, as many enhanced frames out,
+    look_ahead frames late.  The noisy frames wait for their masks inside the slot's state, so state() / load_state move a call whole.
+    All push outputs of a clip followed by its tail() output, without the first look_ahead columns, are enhance() of that clip alone,
+    whatever the chunking.  Everything runs on the current CUDA stream; a push allocates nothing but its output tensor and never
+    synchronises (under the model's error_check="sync" it then waits and polls, as forward does)."""
+    _prefix, _opener = "fsnp_spec_stream", "open_spec_stream"
+
+    def __init__(self, model, slots, max_chunk, device, live=False):
+        super().__init__(model, slots, max_chunk, device, live)
+        self.max_chunk, self.num_freqs, self.live = int(max_chunk), model.num_freqs, bool(live)
+
+    def push(self, noisy_complex, counts=None, out=None):
+        """noisy_complex [slots, F, n] complex64 CUDA tensor (any strides: torch.stft's output as it is), n <= max_chunk; counts: None
+        (n frames for every slot) or frames per slot (a Python sequence or a CPU integer tensor, 0 <= counts[b] <= n; input past
+        counts[b] is never read) -> [slots, F, n] complex64: column j < counts[b] of slot b is the enhanced frame P + j - look_ahead
+        (exactly 0 while P + j < look_ahead), columns >= counts[b] are exactly 0.  out: None (a new tensor in torch.stft's memory order,
+        bins fastest) or a [slots, F, n] complex64 CUDA tensor of any strides that does not overlap the input."""
+        st = self._session()
+        assert noisy_complex.dim() == 3 and noisy_complex.is_complex(), "SpecStream.push takes [slots, F, n] complex frames"
+        S, F, n = noisy_complex.shape
+        assert S == self.slots, f"expected {self.slots} slots, got {S}"
+        assert F == self.num_freqs, f"expected {self.num_freqs} frequency bins, got {F}"
+        if not noisy_complex.is_cuda:
+            raise RuntimeError("fullsubnet_plus_amd runs on MI355X (HIP) only; move the model and inputs to 'cuda'. "
+                               "There is deliberately no CPU fallback.")
+        assert noisy_complex.device == self.device
+        x = noisy_complex if noisy_complex.dtype == torch.complex64 else noisy_complex.to(torch.complex64)
+        x = x.resolve_conj()
+        cnt = None if counts is None else _host_lengths(counts, S, "SpecStream.push")
+        if out is None:
+            out = torch.empty((S, n, F), dtype=torch.complex64, device=self.device).transpose(1, 2)
+        else:
+            assert out.shape == x.shape and out.dtype == torch.complex64 and out.device == self.device and not out.is_conj(), \
+                f"out must be a [{S}, {F}, {n}] complex64 tensor on {self.device}"
+        strides = (ctypes.c_int64 * 3)(*x.stride())
+        out_strides = (ctypes.c_int64 * 3)(*out.stride())
+
+        def enqueue():
+            with torch.cuda.device(self.device):
+                return self._lib.fsnp_spec_stream_push(st, x.data_ptr(), ctypes.byref(strides), cnt, out.data_ptr(),
+                                                       ctypes.byref(out_strides), n, self._cuda_stream())
+        return self._guarded(enqueue, out, "fsnp_spec_stream_push")
+
+    def tail(self, slots=None):
+        """Push look_ahead all-zero frames (the reference's own pad) into `slots` (None: all): the last look_ahead enhanced frames.
+        -> [slots, F, look_ahead] (an empty tensor for look_ahead = 0)."""
+        la = self.look_ahead
+        if la == 0:
+            return torch.zeros((self.slots, self.num_freqs, 0), dtype=torch.complex64, device=self.device)
+        if la > self.max_chunk:
+            raise ValueError(f"tail: look_ahead {la} > max_chunk {self.max_chunk}")
+        zeros = torch.zeros((self.slots, self.num_freqs, la), dtype=torch.complex64, device=self.device)
+        counts = None if slots is None else [la if b in set(int(v) for v in slots) else 0 for b in range(self.slots)]
+        return self.push(zeros, counts)
+
+    def frames(self, slot):
+        """Frames pushed into `slot` since its last reset (host-side count; after load_state the first call waits for that copy)."""
+        return self._counter("frames", slot)

@@ -18,6 +18,14 @@ cell it takes (n <= 16), timed in the same run right after it: "live_ms_per_push
 --runs timed runs, per push) and "live_speedup" = default / live.  With --wave the wave session is timed in both modes as well.
 
     python tools/stream_throughput.py --live [--slots 1 8 32 64] [--chunks 1 4 16]
+
+--spec times spectrum sessions (FullSubNet.open_spec_stream: noisy STFT frames in, enhanced frames out).  Per cell and in one process:
+the mag push alone, the loop a caller of a mag session writes around it to get enhanced frames (X.abs(), a per-slot list of the noisy
+frames that wait look_ahead steps for their masks, a concatenate-and-slice per slot, the cIRM epilogue with lengths), and the spectrum
+push that does the same on the device.  One JSON line per cell and session mode (--live adds the live sessions, n <= 16): medians with
+min and max of the --runs timed runs, per push.
+
+    python tools/stream_throughput.py --spec --live [--slots 1 8 64] [--chunks 1 4]
 """
 import argparse
 import json
@@ -31,6 +39,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from fullsubnet_plus_amd import FullSubNet  # noqa: E402
+from fullsubnet_plus_amd._args import _host_lengths  # noqa: E402
 from fullsubnet_plus_amd.synthetic import FULLSUBNET_MODEL_ARGS, make_inputs, make_state_dict_fullsubnet, make_wave  # noqa: E402
 
 FRAME_MS = 16.0
@@ -87,9 +96,70 @@ def wave_mode(model, a):
         print(json.dumps(rec))
 
 
+def recipe_push(model, st, X, counts, lengths, delay):
+    """One push of a mag session with the other half of a spectrum session written out in torch: -> enhanced [S, F, n] complex64.
+    delay[b]: the noisy frames of slot b that have no mask yet, complex [F, <= look_ahead] (frames P - w .. P - 1)."""
+    S, F, n = X.shape
+    la = st.look_ahead
+    mask = st.push(X.abs().unsqueeze(1), counts)              # column j of slot b = cIRM of frame P_b + j - look_ahead
+    aligned = torch.zeros((S, n, F), dtype=torch.complex64, device=X.device).transpose(1, 2)
+    for b in range(S):
+        c = counts[b]
+        if c == 0:
+            continue
+        w = delay[b].shape[1]
+        buf = torch.cat([delay[b], X[b, :, :c]], dim=1)       # frames P - w .. P + c - 1
+        lead = la - w                                         # columns of steps before look_ahead: the mask is exactly 0 there
+        if c > lead:
+            aligned[b, :, lead:c] = buf[:, :c - lead]
+        delay[b] = buf[:, max(w + c - la, 0):]
+    return model._apply_cirm(mask, aligned, lengths)          # fsnp_apply_cirm_lengths: exactly 0 past counts[b]
+
+
+def spec_mode(model, a):
+    """the mag push, the recipe around it and the spectrum push, per cell and session mode"""
+    F = model.num_freqs
+
+    def ms(runs):
+        return {"median": round(statistics.median(runs) * 1e3, 4), "min": round(min(runs) * 1e3, 4), "max": round(max(runs) * 1e3, 4)}
+
+    for S in a.slots:
+        _, re, im = make_inputs(S, 2.0, 3)
+        full = torch.complex(re[:, 0], im[:, 0]).cuda()
+        for n in a.chunks:
+            reps = (n + full.shape[-1] - 1) // full.shape[-1]
+            X = full.repeat(1, 1, reps)[:, :, :n].transpose(1, 2).contiguous().transpose(1, 2)      # torch.stft's order: bins fastest
+            mag = X.abs().unsqueeze(1)
+            counts = [n] * S
+            lengths = _host_lengths(counts, S, "stream_throughput")
+            for live in ([False, True] if a.live and n <= LIVE_MAX_CHUNK else [False]):
+                with model.open_stream(S, max_chunk=n, live=live) as st:
+                    def run_mag():
+                        for _ in range(a.pushes):
+                            st.push(mag)
+                    mag_runs = [t / a.pushes for t in timed_all(run_mag, a.runs)]
+                    st.reset()
+                    delay = {b: torch.empty((F, 0), dtype=torch.complex64, device="cuda") for b in range(S)}
+
+                    def run_recipe():
+                        for _ in range(a.pushes):
+                            recipe_push(model, st, X, counts, lengths, delay)
+                    recipe_runs = [t / a.pushes for t in timed_all(run_recipe, a.runs)]
+                with model.open_spec_stream(S, max_chunk=n, live=live) as ss:
+                    def run_spec():
+                        for _ in range(a.pushes):
+                            ss.push(X)
+                    spec_runs = [t / a.pushes for t in timed_all(run_spec, a.runs)]
+                m, r, p = (statistics.median(v) for v in (mag_runs, recipe_runs, spec_runs))
+                print(json.dumps({"slots": S, "chunk": n, "live": live, "mag_ms_per_push": ms(mag_runs), "recipe_ms_per_push": ms(recipe_runs),
+                                  "spec_ms_per_push": ms(spec_runs), "spec_minus_mag_ms": round((p - m) * 1e3, 4),
+                                  "recipe_over_spec": round(r / p, 2), "spec_at_or_below_recipe_max": bool(p <= max(recipe_runs))}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--wave", action="store_true", help="time wave sessions (hop-sized pushes) next to the mag push of one frame")
+    ap.add_argument("--spec", action="store_true", help="time spectrum sessions next to the mag push and the host-side loop they replace")
     ap.add_argument("--live", action="store_true", help="time a live session beside the default one in every cell of n <= 16 frames")
     ap.add_argument("--slots", type=int, nargs="+", default=[1, 8, 32, 64])
     ap.add_argument("--chunks", type=int, nargs="+", default=[1, 4, 16, 64])
@@ -106,6 +176,10 @@ def main():
     with torch.no_grad():
         if a.wave:
             wave_mode(model, a)
+            model.check_errors()
+            return
+        if a.spec:
+            spec_mode(model, a)
             model.check_errors()
             return
         for S in a.slots:
