@@ -105,7 +105,7 @@ struct RowLengths { int v[kLenRows]; };
 void launch_apply_cirm_lengths(const float* mask, const float* noisy, const int64_t strides[3], float* out,
                                const int64_t out_strides[3], int B, int F, int T, const int* lengths, hipStream_t s);
 // one bin of it: the compressed mask planes at mask[re_at], mask[re_at + plane] times the complex x (shared by the whole-clip kernels of
-// frontend.hip and the waveform sessions of stft_stream.hip)
+// frontend.hip and the ring push of spec_stream.hip)
 #ifdef __HIPCC__
 __device__ __forceinline__ float2 cirm_times(const float* __restrict__ mask, long re_at, long plane, float2 x) {
     float m[2];
@@ -129,7 +129,10 @@ void launch_frontend_mag(const Dims& d, int norm_type, const float* mag, const i
                          const FrontendBuffers& buf, hipStream_t s);
 
 // streaming (include/fsnp_stream.h): per-slot push facts in the workspace, written by the push's prologue kernel
-struct StreamMeta { long long p; int cnt, pad; };      // frames the slot had before this push, frames it gets now
+struct StreamMeta { long long p; int cnt, pad; };      // frames the slot had before this push, frames (= model steps) it gets now
+// one host value per slot of a session's call (frames, samples, spectra; finish: 1 = this slot ends), ONE kernel argument block of 2 KB
+constexpr int kStreamMaxSlots = 512;
+struct SlotCounts { int v[kStreamMaxSlots]; };
 // launch_frontend_mag of one push: repack (frames >= cnt[slot] never read), per-frame sums, and the cumulative norm's (m_t, d_t) table
 // continued from the slot's carried fp64 sums (sums: slot 0's {sum, sum of squares}, sum_stride doubles between slots; updated)
 void launch_frontend_mag_stream(const Dims& d, int norm_type, const float* mag, const int64_t strides[3], const FrontendBuffers& buf,
@@ -193,22 +196,39 @@ void launch_istft_ola(const float* frames, const float* window, float* wav, long
 void launch_stft_pad_lengths(const float* wav, long wav_stride, float* xp, long xp_stride, int B, const int* samples, int n_fft, hipStream_t s);
 void launch_istft_ola_lengths(const float* frames, const float* window, float* wav, long wav_stride, int B, int T, int L, const int* samples,
                               int n_fft, hipStream_t s);
-// stft_stream.hip : waveform sessions (include/fsnp_wave_stream.h) - the streaming halves of the two transforms around one mag push.
+// spec_stream.hip : the look-ahead ring and the two short launches around one mag push that a spectrum session (include/fsnp_spec_stream.h)
+// and a wave session (include/fsnp_wave_stream.h) share.  Per slot a ring complex64 [look_ahead][F]: the noisy spectra of the newest
+// look_ahead frames, frame g in row g % look_ahead (they wait for their masks: the mask of frame t is the model's output of step
+// t + look_ahead).  Strides in complex elements for (slot, f, frame).
+struct SpecArgs {
+    unsigned char* ring;                           // ring of slot 0
+    size_t ring_stride;                            // bytes between slots
+    const StreamMeta* meta;                        // [S] {P, steps} of this push, written by the mag push's prologue kernel
+    int S, F, FP, LA, n;
+};
+// mag [S][n][FP] = hypotf(re, im) of the c.v[slot] new spectra of every slot (zeros behind them and in the pad bins; input frames
+// >= c.v[slot] are never read)
+void launch_spec_mag(const SpecArgs& a, const SlotCounts& c, const float* spec, const int64_t strides[3], float* mag, hipStream_t s);
+// out column j < steps = cIRM of step P + j (mask [S][2][F][n]) times the noisy frame P + j - look_ahead (the ring's or this push's),
+// exactly 0 where there is no such frame yet and in columns >= steps; then the ring takes the newest min(c.v[slot], look_ahead) spectra
+void launch_spec_apply(const SpecArgs& a, const SlotCounts& c, const float* mask, const float* spec, const int64_t strides[3], float* out,
+                       const int64_t out_strides[3], hipStream_t s);
+// stft_stream.hip : waveform sessions (include/fsnp_wave_stream.h) - the streaming halves of the two transforms around one ring push.
 // Per slot a wave record [ carry fp32 [n_fft + 1] | ring complex64 [look_ahead][F] | tail fp32 [hop] | fifo fp32 [hop] | samples int64 ]:
 //   carry  the newest n_fft + 1 input samples, carry[i] = sample P - (n_fft + 1) + i (0 before the clip's start)
-//   ring   the noisy spectra of the newest look_ahead frames, frame g in row g % look_ahead (they wait for their masks)
+//   ring   the look-ahead ring of spec_stream.hip (the kernels here never touch it)
 //   tail   the second half of the newest enhanced frame (already windowed by the inverse DFT matrix)
 //   fifo   finished output samples that have not been emitted yet, fifo[q] = sample max(P - D, 0) + q, 0 behind them
 struct WaveMeta { long long p; int c, fin; };      // samples the slot had before this call, samples it gets now, 1 = it is finished now
 struct WaveArgs {
     unsigned char* state;                          // wave record of slot 0
-    size_t stride, o_ring, o_tail, o_fifo, o_count;   // bytes between slots, byte offsets inside a record (the carry is at 0)
-    WaveMeta* meta;                                // [S], written by the gather kernel for the kernels behind it
-    int S, F, hop, LA, sp, FP, nrow;               // nrow: frame rows per slot in every per-frame buffer of this call
+    size_t stride, o_tail, o_fifo, o_count;        // bytes between slots, byte offsets inside a record (the carry is at 0)
+    WaveMeta* meta;                                // [S], written by the gather kernel for the overlap-add behind it
+    int S, hop, LA, nrow;                          // nrow: frame rows per slot in every per-frame buffer of this call
 };
 // what a call does to a slot, from {P, c, fin} alone.  Frame t is complete once (t + 1) hop samples have arrived (frame 0: hop + 1, it
 // reflects wav[1 .. hop]); the mask of frame t is the model's output of step t + look_ahead; finish adds the clip's last frame and steps
-// the model through look_ahead zero frames
+// the model through look_ahead zero frames.  The mag session inside gets km frames per call, so its frame count is nf.
 struct WaveStep {
     long long nf;      // frames the slot had before this call (= steps of the model so far)
     long long e_old;   // enhanced frames it had: max(nf - look_ahead, 0)
@@ -225,33 +245,13 @@ __host__ __device__ inline WaveStep wave_step(long long P, int c, int fin, int h
     w.e_old = w.nf > LA ? w.nf - LA : 0;
     return w;
 }
-struct WaveCounts { int v[512]; };                 // per slot: samples of a push, or 1 = finish this slot (ONE kernel argument block)
-// frame rows xfr [S][nrow][n_fft] of the newly complete frames (zeros behind them), the carry and the sample count advanced, meta written
-void launch_wave_gather(const WaveArgs& a, const WaveCounts& c, int fin, const float* wav, long wav_stride, float* xfr, hipStream_t s);
-// mag [S][nrow][FP] = |spec| of the new spectra (as the whole-clip complex forward takes it), zero frames behind them up to km
-void launch_wave_mag(const WaveArgs& a, const float* spec, float* mag, hipStream_t s);
-// enh [S][nrow][sp] row e = cIRM of step j0 + e times the noisy spectrum of its frame (this call's or the ring's); the ring advanced
-void launch_wave_apply(const WaveArgs& a, const float* mask, const float* spec, float* enh, hipStream_t s);
-// overlap-add with the window-envelope division over the frames fr [S][nrow][n_fft], into the fifo and out [S][ncols]: column j is
-// sample P + j - D (finish: L - D + j), exactly 0 where that is negative and past the slot's count (finish: in rows not finished)
+// c.v[slot]: samples of a push, or (fin) 1 = finish this slot.  Frame rows xfr [S][nrow][n_fft] of the newly complete frames (zeros
+// behind them), the carry and the sample count advanced, meta written
+void launch_wave_gather(const WaveArgs& a, const SlotCounts& c, int fin, const float* wav, long wav_stride, float* xfr, hipStream_t s);
+// overlap-add with the window-envelope division over the frames fr [S][nrow][n_fft] (row j = the frame of step j of this call), into the
+// fifo and out [S][ncols]: column j is sample P + j - D (finish: L - D + j), exactly 0 where that is negative and past the slot's count
+// (finish: in rows not finished)
 void launch_wave_ola(const WaveArgs& a, const float* fr, const float* window, float* out, long out_stride, int ncols, hipStream_t s);
-// spec_stream.hip : spectrum sessions (include/fsnp_spec_stream.h) - the two short launches around one mag push.  Per slot a ring
-// complex64 [look_ahead][F] behind the mag-stream record: the noisy spectra of the newest look_ahead frames, frame g in row
-// g % look_ahead (they wait for their masks).  Strides in complex elements for (slot, f, frame).
-struct SpecCounts { int v[512]; };                 // frames per slot of a push (ONE kernel argument block)
-struct SpecArgs {
-    unsigned char* ring;                           // ring of slot 0
-    size_t ring_stride;                            // bytes between slots
-    const StreamMeta* meta;                        // [S] {P, count} of this push, written by the mag push's prologue kernel
-    int S, F, FP, LA, n;
-};
-// mag [S][n][FP] = hypotf(re, im) of the c.v[slot] new frames of every slot (zeros behind them and in the pad bins; input frames
-// >= c.v[slot] are never read)
-void launch_spec_mag(const SpecArgs& a, const SpecCounts& c, const float* spec, const int64_t strides[3], float* mag, hipStream_t s);
-// out column j < count = cIRM of step P + j (mask [S][2][F][n]) times the noisy frame P + j - look_ahead (the ring's or this push's),
-// exactly 0 where there is no such frame yet and in columns >= count; then the ring takes the newest min(count, look_ahead) frames
-void launch_spec_apply(const SpecArgs& a, const float* mask, const float* spec, const int64_t strides[3], float* out,
-                       const int64_t out_strides[3], hipStream_t s);
 void stft_build_matrices(int n_fft, float* fwd /*[N2 pad 384][n_fft]*/, float* inv /*[n_fft pad 384][K pad 16]*/,
                          float* window /*[n_fft]*/);
 

@@ -2,7 +2,7 @@
 // fsnp_abi.hip (create / forward orchestration / workspace / calibration), forward_kernels.hip (the forward's small kernels),
 // fsnp_verify.hip (exchange verification), fsnp_debug_abi.hip (include/fsnp_debug.h: test and tuning hooks), fsnp_weights.hip
 // (strict weight loading + packing), fsnp_stft_abi.hip (STFT / iSTFT / waveform entry points), fsnp_stream_abi.hip,
-// fsnp_wave_stream_abi.hip and fsnp_spec_stream_abi.hip (stream, wave and spectrum sessions).  Host declarations only.
+// fsnp_wave_stream_abi.hip and fsnp_spec_stream_abi.hip (stream, wave and spectrum sessions, and the slot helpers they share).  Host only.
 #pragma once
 #include <map>
 #include <string>
@@ -227,15 +227,79 @@ struct StftPlan {
 StftPlan stft_plan(const fsnp_handle* h);
 int ensure_stft(fsnp_handle* h);
 int ensure_io(fsnp_handle* h, size_t bytes, hipStream_t s);
-// fsnp_stream_abi.hip: the per-slot counts of one push travel as ONE kernel argument block (2 KB), and the push behind its checks
-constexpr int kStreamMaxSlots = 512;
-struct StreamCounts { int v[kStreamMaxSlots]; };
-int stream_push_body(fsnp_stream* st, const float* mag, const int64_t strides[3], const StreamCounts& c, float* out, int n, hipStream_t s);
-// session creation behind fsnp_stream_create (live = 0) and fsnp_stream_create_live (live = 1: pushes run on lstm_step.hip, max_chunk <= kLiveMaxChunk)
+// ---- stream, wave and spectrum sessions (fsnp_stream_abi.hip, fsnp_wave_stream_abi.hip, fsnp_spec_stream_abi.hip) ----
+// argument checks of their entry points: `where` names the entry point in every message; 0, or 2 with the error set
+inline int check_slot(const char* where, int slot, int S) {
+    if (slot < 0 || slot >= S) { set_error("%s: slot %d outside [0, %d)", where, slot, S); return 2; }
+    return 0;
+}
+inline int check_slots(const char* where, const int32_t* slots, int32_t num, int S) {      // slots = NULL: every slot
+    if (!slots) return 0;
+    if (num < 0) { set_error("%s: num = %d", where, num); return 2; }
+    for (int i = 0; i < num; ++i)
+        if (const int rc = check_slot(where, slots[i], S)) return rc;
+    return 0;
+}
+inline int read_counts(const char* where, const int32_t* counts, int S, int n, SlotCounts& c) {      // counts = NULL: n for every slot
+    for (int b = 0; b < S; ++b) {
+        const int v = counts ? counts[b] : n;
+        if (v < 0 || v > n) { set_error("%s: slot %d: count %d outside [0, n = %d]", where, b, v, n); return 2; }
+        c.v[b] = v;
+    }
+    return 0;
+}
+// what every call that enqueues a push asks last: committed weights, and no error left behind by an earlier call on the handle
+inline int push_preamble(fsnp_handle* h, const char* where) {
+    if (!h->committed) { set_error("%s: weights not committed (call fsnp_commit_weights)", where); return 2; }
+    return take_device_errors(h, "an earlier call on this handle failed");
+}
+// One device array of per-slot records [S][bytes]: the mag record, the wave record, the look-ahead ring.  Zero bytes (a ring at
+// look_ahead = 0) is an array without memory on which every call does nothing.  The caller is on the handle's device.
+struct SlotRecords {
+    unsigned char* base = nullptr;
+    size_t bytes = 0;      // one slot
+    int S = 0;
+    unsigned char* slot(int b) const { return base + (size_t)b * bytes; }
+    hipError_t create(size_t slot_bytes, int slots) {      // zeroed
+        bytes = slot_bytes; S = slots;
+        if (!bytes) return hipSuccess;
+        const hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), bytes * S);
+        return e != hipSuccess ? e : hipMemset(base, 0, bytes * S);
+    }
+    void free() { if (base) (void)hipFree(base); base = nullptr; }      // (hipFree waits for the device: pushes still in flight finish first)
+    int reset(const int32_t* slots, int32_t num, hipStream_t s) {      // stream-ordered zeroing of checked slots (NULL: all)
+        if (!bytes) return 0;
+        if (!slots) { FSNP_HIP_CHECK(hipMemsetAsync(base, 0, bytes * S, s)); return 0; }
+        for (int i = 0; i < num; ++i) FSNP_HIP_CHECK(hipMemsetAsync(slot(slots[i]), 0, bytes, s));
+        return 0;
+    }
+    int get(int b, void* blob, size_t at, hipStream_t s) const {      // slot b -> blob + at (device memory)
+        if (bytes) FSNP_HIP_CHECK(hipMemcpyAsync(static_cast<unsigned char*>(blob) + at, slot(b), bytes, hipMemcpyDeviceToDevice, s));
+        return 0;
+    }
+    int set(int b, const void* blob, size_t at, hipStream_t s) {      // blob + at -> slot b
+        if (bytes) FSNP_HIP_CHECK(hipMemcpyAsync(slot(b), static_cast<const unsigned char*>(blob) + at, bytes, hipMemcpyDeviceToDevice, s));
+        return 0;
+    }
+};
+// fsnp_stream_abi.hip: one mag push behind its checks, and session creation behind fsnp_stream_create (live = 0) and
+// fsnp_stream_create_live (live = 1: pushes run on lstm_step.hip, max_chunk <= kLiveMaxChunk)
+int stream_push_body(fsnp_stream* st, const float* mag, const int64_t strides[3], const SlotCounts& c, float* out, int n, hipStream_t s);
 constexpr int kLiveMaxChunk = 16;
 int stream_create(fsnp_handle* h, int32_t slots, int32_t max_chunk, int live, const char* where, fsnp_stream** out);
-// where a session's prologue kernel publishes {P, count} of every slot of a push ([slots], device: the session's workspace), for the
-// kernels a spectrum session (fsnp_spec_stream_abi.hip) runs behind stream_push_body
-const StreamMeta* stream_meta(const fsnp_stream* st);
+// one ring push behind its checks - what a spectrum session's push is, and what a wave session runs between
+// its two transforms.  |spec| -> mag push of `mag` -> cIRM of every step times its waiting spectrum -> the ring advanced.
+//   ring        the look-ahead ring of slot 0 ([look_ahead][F] complex64), ring_stride bytes between slots
+//   mag, mask   scratch [S][n][FP] and [S][2][F][n]
+//   spec, out   complex64 with strides (slot, f, frame) in complex elements; out column j = the enhanced frame of step j, exactly 0
+//               where the step has no frame or the slot no such step
+//   write_idle  a call in which no slot steps still writes out (all zeros: a spectrum push owes them to its caller; a wave call, which
+//               then transforms nothing back, does not and launches nothing for them)
+//   spectra     per slot, the new spectra in spec; steps = the mag push's counts: the same, but 1 and 1 + look_ahead for a wave slot
+//               that is finished (its ring then takes the clip's last spectrum, and the reset that ends finish clears it)
+struct SpecRing { unsigned char* ring; size_t ring_stride; int look_ahead; };
+int spec_push_body(fsnp_stream* mag_session, const SpecRing& ring, float* mag, float* mask, const float* spec, const int64_t strides[3],
+                   const SlotCounts& spectra, const SlotCounts& steps, float* out, const int64_t out_strides[3], bool write_idle, int n,
+                   hipStream_t s);
 
 }  // namespace fsnp

@@ -1,23 +1,26 @@
 // fsnp_stream_abi.hip - include/fsnp_stream.h: stream sessions of the original FullSubNet (chunked forwards that carry their state).
 //
-// A session owns, per slot, one contiguous kernel-independent state record
+// A session owns, per slot, one contiguous kernel-independent state record (a SlotRecords array, fsnp_handle.h)
 //   [ sub-band  fp32 [F][layer][h|c][H] | full-band fp32 [layer][h|c][CH] | sub-band norm fp64 [F][sum, sumsq] |
 //     full-band norm fp64 [sum, sumsq] | frames int64 ]
 // and a workspace of its own for one push of `max_chunk` frames (allocated and zeroed at creation: a push allocates nothing and
-// synchronises nothing).  One push on the caller's stream:
-//   stream_prologue_kernel   counts (kernel arguments) -> per-slot {P, count}, the slots' frame counts advanced, the row lists of the
-//                            active slots (slots without frames are in no row list)
+// synchronises nothing).  One push on the caller's stream (stream_push_body, which wave and spectrum sessions reach through
+// spec_push_body below):
+//   stream_prologue_kernel       counts (kernel arguments) -> per-slot {P, count}, the slots' frame counts advanced, the row lists of the
+//                                active slots (slots without frames are in no row list)
 //   launch_frontend_mag_stream   repack + per-frame sums + the full-band cumulative norm continued from the carried sums (frontend.hip)
-//   launch_lstm_generic_stream   full-band LSTM(F -> CH x 2) from the carried (h, c), every slot count (lstm_generic.hip)
+//   full-band recurrent part     chunked_fullband / live_fullband
 //   launch_linear_act            Linear(CH, F) + fb_act, as the whole-clip forward
 //   launch_subband_stats_stream  the sub-band cumulative norm continued from the carried per-(slot, f) sums (subband.hip)
-//   launch_lstm_stream           the fp32 MFMA row-tile kernel from the carried (h0, c0, h1, c1) (lstm.hip), tiles of 32 rows
+//   sub-band recurrent part      chunked_subband / live_subband
 //   stream_epilogue_kernel       columns past a slot's count and columns of steps before look_ahead written as exactly 0
-// A LIVE session (include/fsnp_stream_live.h, max_chunk <= 16) keeps every stage but the two recurrent launches, which become launches per
-// layer and step (lstm_step.hip): the slot records' h into the session's parity-0 buffers, then for t < the largest count full-band
-// layer 0, layer 1 - Linear, sub-band statistics - and sub-band layer 0, layer 1, Linear(H, 2) per step.  Always, whatever the number of
-// active slots or n: a slot's bits do not depend on its neighbours.  Same records, same workspace rules, 4 (H x rows_pad x 32 + S x CH)
-// floats of h buffers more.
+// The recurrent parts of a default session are one launch each (chunked_*): launch_lstm_generic_stream, the full-band LSTM(F -> CH x 2)
+// from the carried (h, c) at every slot count (lstm_generic.hip), and launch_lstm_stream, the fp32 MFMA row-tile kernel from the carried
+// (h0, c0, h1, c1) in tiles of 32 rows (lstm.hip).  A LIVE session (include/fsnp_stream_live.h, max_chunk <= 16) runs them as launches per
+// layer and step (live_*, lstm_step.hip): the slot records' h into the session's parity-0 buffers, then for t < the largest count
+// full-band layer 0, layer 1 - Linear, sub-band statistics - and sub-band layer 0, layer 1, Linear(H, 2) per step.  Always, whatever the
+// number of active slots or n: a slot's bits do not depend on its neighbours.  Same records, same workspace rules, 4 (H x rows_pad x 32
+// + S x CH) floats of h buffers more.
 #include <algorithm>
 #include <vector>
 
@@ -26,9 +29,8 @@
 struct fsnp_stream {
     fsnp_handle* h = nullptr;
     int S = 0, N = 0;                 // slots, max_chunk
-    size_t state_bytes = 0;           // one slot
-    size_t o_fb = 0, o_sbsum = 0, o_fbsum = 0, o_count = 0;       // byte offsets inside a slot's state
-    unsigned char* state = nullptr;   // [S][state_bytes]
+    SlotRecords rec;                  // the slots' state records
+    size_t o_fb = 0, o_sbsum = 0, o_fbsum = 0, o_count = 0;       // byte offsets inside a record
     unsigned char* ws = nullptr;
     size_t ws_bytes = 0;
     size_t w_raw = 0, w_fb = 0, w_y1 = 0, w_md = 0, w_frame = 0, w_md_row = 0, w_rows = 0, w_fb_rows = 0, w_meta = 0, w_cnt = 0;
@@ -38,6 +40,8 @@ struct fsnp_stream {
     std::vector<int64_t> frames;      // host mirror of the slots' frame counts
     std::vector<char> frames_known;   // 0: the count came with fsnp_stream_set_state (read back on demand)
     hipStream_t last_stream = nullptr;
+    template <class T> T* at(size_t off) const { return reinterpret_cast<T*>(ws + off); }      // inside the workspace
+    float* state_f() const { return reinterpret_cast<float*>(rec.base); }
 };
 
 namespace fsnp {
@@ -52,7 +56,7 @@ static StreamPlan plan_stream(int active_slots, int F, int num_cus) {
     return p;
 }
 
-__global__ __launch_bounds__(256) void stream_prologue_kernel(StreamCounts c, int S, int nact, int F, int n, RowDesc* __restrict__ rows,
+__global__ __launch_bounds__(256) void stream_prologue_kernel(SlotCounts c, int S, int nact, int F, int n, RowDesc* __restrict__ rows,
                                                               int rows_pad, RowDesc* __restrict__ fb_rows, int fb_rows_pad,
                                                               StreamMeta* __restrict__ meta, int* __restrict__ cnt,
                                                               unsigned char* __restrict__ state, size_t state_bytes, size_t o_count) {
@@ -94,101 +98,140 @@ __global__ __launch_bounds__(256) void stream_epilogue_kernel(float* __restrict_
     }
 }
 
-// One push behind its checks (fsnp_stream_push, and the waveform sessions of fsnp_wave_stream_abi.hip with the frames each slot
-// completed): mag is device memory with strides, c.v[slot] in [0, n] frames of every slot, out contiguous [slots, 2, F, n].
-int stream_push_body(fsnp_stream* st, const float* mag, const int64_t strides[3], const StreamCounts& c, float* out, int n, hipStream_t s) {
+// the arguments of the two recurrent launches of a default session's push: launch_lstm_generic_stream (full-band, every slot from its
+// carried (h, c)) and launch_lstm_stream (sub-band row tiles, every row from its carried (h0, c0, h1, c1))
+struct ChunkedArgs { LstmArgs fb, sb; };
+static ChunkedArgs chunked_args(const fsnp_stream* st, int n, int nact, const StreamPlan& plan, float* out) {
+    const fsnp_handle* h = st->h;
+    const int rg = lstm_generic_rows_per_group(h->CH, h->F, nact, h->num_cus_real);
+    ChunkedArgs c{};
+    LstmArgs& fa = c.fb;
+    fa.rows = st->at<RowDesc>(st->w_fb_rows); fa.dense = st->at<float>(st->w_raw); fa.dense_stride = h->FP; fa.md_seq = st->at<NormMD>(st->w_md);
+    fa.seq_out = st->at<float>(st->w_y1); fa.seq_stride = (int)align_up(h->CH, 4);
+    fa.num_rows = nact; fa.num_tiles = cdiv(nact, rg); fa.coop_rows_per_group = rg;
+    fa.Tp = n; fa.LA = 0; fa.FP = h->FP; fa.F = h->F;
+    fa.st_fb = st->state_f() + st->o_fb / 4; fa.st_stride = (long)(st->rec.bytes / 4);
+    LstmArgs& a = c.sb;
+    a.att_mag = st->at<float>(st->w_raw); a.fb = st->at<float>(st->w_fb);
+    a.fb_rel = (int)((st->w_fb - st->w_raw) / 4);
+    a.fb_branch_stride = st->S * n * h->FP;
+    a.rows = st->at<RowDesc>(st->w_rows); a.md_row = st->at<NormMD>(st->w_md_row);
+    a.out = out; a.out_stride_o = (long)h->F * n;
+    a.num_rows = plan.rows; a.num_tiles = plan.tiles; a.ex = 0;
+    a.Tp = n; a.LA = 0; a.FP = h->FP; a.F = h->F; a.NSBN = h->cfg.sb_num_neighbors; a.NFBN = h->cfg.fb_num_neighbors;
+    a.act = h->cfg.sb_act;
+    a.st_sb = st->state_f(); a.st_stride = (long)(st->rec.bytes / 4);
+    return c;
+}
+
+// the arguments of a live session's launches per layer and step (lstm_step.hip); t and par are the caller's to set
+struct LiveArgs { LiveFbArgs fb; LiveSbArgs sb; };
+static LiveArgs live_args(const fsnp_stream* st, int n, int nact, const StreamPlan& plan, float* out) {
+    const fsnp_handle* h = st->h;
+    const int S = st->S;
+    const size_t sbh = live_sb_h_floats(h->H, st->rows_pad / 32), fbh = (size_t)S * h->CH;
+    LiveArgs l{};
+    LiveSbArgs& la = l.sb;
+    la.rows = st->at<RowDesc>(st->w_rows); la.tiles = plan.tiles; la.Tp = n;
+    la.att_mag = st->at<float>(st->w_raw); la.fb_rel = (int)((st->w_fb - st->w_raw) / 4); la.fb_branch_stride = S * n * h->FP;
+    la.FP = h->FP; la.F = h->F; la.NSBN = h->cfg.sb_num_neighbors; la.NFBN = h->cfg.fb_num_neighbors;
+    la.md_row = st->at<NormMD>(st->w_md_row);
+    la.st = st->state_f(); la.st_stride = (long)(st->rec.bytes / 4);
+    for (int p = 0; p < 2; ++p) { la.h0[p] = st->at<float>(st->w_sbh) + p * sbh; la.h1[p] = st->at<float>(st->w_sbh) + (2 + p) * sbh; }
+    la.out = out; la.out_stride_o = (long)h->F * n; la.act = h->cfg.sb_act;
+    LiveFbArgs& lf = l.fb;
+    lf.rows = st->at<RowDesc>(st->w_fb_rows); lf.num_rows = nact; lf.Tp = n;
+    lf.dense = st->at<float>(st->w_raw); lf.dense_stride = h->FP; lf.md_seq = st->at<NormMD>(st->w_md);
+    lf.st = st->state_f() + st->o_fb / 4; lf.st_stride = (long)(st->rec.bytes / 4);
+    for (int p = 0; p < 2; ++p) { lf.h0[p] = st->at<float>(st->w_fbh) + p * fbh; lf.h1[p] = st->at<float>(st->w_fbh) + (2 + p) * fbh; }
+    lf.seq_out = st->at<float>(st->w_y1); lf.seq_stride = (int)align_up(h->CH, 4);
+    return l;
+}
+
+// One push behind its checks (fsnp_stream_push, and spec_push_body for spectrum and wave sessions): mag is device memory with strides,
+// c.v[slot] in [0, n] frames of every slot, out contiguous [slots, 2, F, n].
+int stream_push_body(fsnp_stream* st, const float* mag, const int64_t strides[3], const SlotCounts& c, float* out, int n, hipStream_t s) {
     fsnp_handle* h = st->h;
-    int nact = 0;
-    for (int b = 0; b < st->S; ++b) nact += c.v[b] > 0;
+    const int S = st->S, F = h->F;
+    int nact = 0, nmax = 0;
+    for (int b = 0; b < S; ++b) { nact += c.v[b] > 0; nmax = std::max(nmax, c.v[b]); }
     FSNP_ON_DEVICE(h);
     st->last_stream = s;
-    const int S = st->S, F = h->F;
-    auto fptr = [&](size_t off) { return reinterpret_cast<float*>(st->ws + off); };
-    RowDesc* rows = reinterpret_cast<RowDesc*>(st->ws + st->w_rows);
-    RowDesc* fb_rows = reinterpret_cast<RowDesc*>(st->ws + st->w_fb_rows);
-    StreamMeta* meta = reinterpret_cast<StreamMeta*>(st->ws + st->w_meta);
-    int* cnt = reinterpret_cast<int*>(st->ws + st->w_cnt);
-    float* state_f = reinterpret_cast<float*>(st->state);
-    double* state_d = reinterpret_cast<double*>(st->state);
+    RowDesc* rows = st->at<RowDesc>(st->w_rows);
+    StreamMeta* meta = st->at<StreamMeta>(st->w_meta);
+    int* cnt = st->at<int>(st->w_cnt);
+    double* state_d = reinterpret_cast<double*>(st->rec.base);
+    const long sum_stride = (long)(st->rec.bytes / 8);
 
     if (h->watch_nseg > 0 && (h->watch_calls++ % h->watch_every) == 0)
         if (launch_weight_watch(h, s, false)) return 4;
-    hipLaunchKernelGGL(stream_prologue_kernel, dim3(cdiv(st->rows_pad, 256)), dim3(256), 0, s, c, S, nact, F, n, rows, st->rows_pad, fb_rows,
-                       st->fb_rows_pad, meta, cnt, st->state, st->state_bytes, st->o_count);
+    hipLaunchKernelGGL(stream_prologue_kernel, dim3(cdiv(st->rows_pad, 256)), dim3(256), 0, s, c, S, nact, F, n, rows, st->rows_pad,
+                       st->at<RowDesc>(st->w_fb_rows), st->fb_rows_pad, meta, cnt, st->rec.base, st->rec.bytes, st->o_count);
     if (nact > 0) {
         Dims d{};
         d.B = S; d.T = n; d.Tp = n; d.F = F; d.FP = h->FP; d.CH = h->CH; d.H = h->H; d.NSB = h->NSB; d.NIN = h->NIN; d.LA = 0;
         d.lens = cnt;
         FrontendBuffers fbuf{};
-        fbuf.raw = fptr(st->w_raw); fbuf.frame = reinterpret_cast<double*>(st->ws + st->w_frame);
-        fbuf.md = reinterpret_cast<NormMD*>(st->ws + st->w_md);
-        launch_frontend_mag_stream(d, h->cfg.norm_type, mag, strides, fbuf, meta, state_d + st->o_fbsum / 8, (long)(st->state_bytes / 8), s);
+        fbuf.raw = st->at<float>(st->w_raw); fbuf.frame = st->at<double>(st->w_frame); fbuf.md = st->at<NormMD>(st->w_md);
+        launch_frontend_mag_stream(d, h->cfg.norm_type, mag, strides, fbuf, meta, state_d + st->o_fbsum / 8, sum_stride, s);
 
-        const int rg = lstm_generic_rows_per_group(h->CH, F, nact, h->num_cus_real);
-        const int chp = (int)align_up(h->CH, 4);
-        LstmArgs fa{};
-        fa.rows = fb_rows; fa.dense = fptr(st->w_raw); fa.dense_stride = h->FP; fa.md_seq = fbuf.md;
-        fa.seq_out = fptr(st->w_y1); fa.seq_stride = chp;
-        fa.num_rows = nact; fa.num_tiles = cdiv(nact, rg); fa.coop_rows_per_group = rg;
-        fa.Tp = n; fa.LA = 0; fa.FP = h->FP; fa.F = F;
-        fa.st_fb = state_f + st->o_fb / 4; fa.st_stride = (long)(st->state_bytes / 4);
-        int nmax = 0;
-        for (int b = 0; b < S; ++b) nmax = std::max(nmax, c.v[b]);
         const StreamPlan plan = plan_stream(nact, F, h->num_cus);
-        LiveSbArgs la{};
-        LiveFbArgs lf{};
+        ChunkedArgs chunked;      // (only the session's own set is filled and read)
+        LiveArgs live;
         if (st->live) {
-            const size_t sbh = live_sb_h_floats(h->H, st->rows_pad / 32), fbh = (size_t)S * h->CH;
-            la.rows = rows; la.tiles = plan.tiles; la.Tp = n;
-            la.att_mag = fptr(st->w_raw); la.fb_rel = (int)((st->w_fb - st->w_raw) / 4); la.fb_branch_stride = S * n * h->FP;
-            la.FP = h->FP; la.F = F; la.NSBN = h->cfg.sb_num_neighbors; la.NFBN = h->cfg.fb_num_neighbors;
-            la.md_row = reinterpret_cast<NormMD*>(st->ws + st->w_md_row);
-            la.st = state_f; la.st_stride = (long)(st->state_bytes / 4);
-            for (int p = 0; p < 2; ++p) { la.h0[p] = fptr(st->w_sbh) + p * sbh; la.h1[p] = fptr(st->w_sbh) + (2 + p) * sbh; }
-            la.out = out; la.out_stride_o = (long)F * n; la.act = h->cfg.sb_act;
-            lf.rows = fb_rows; lf.num_rows = nact; lf.Tp = n;
-            lf.dense = fptr(st->w_raw); lf.dense_stride = h->FP; lf.md_seq = fbuf.md;
-            lf.st = state_f + st->o_fb / 4; lf.st_stride = (long)(st->state_bytes / 4);
-            for (int p = 0; p < 2; ++p) { lf.h0[p] = fptr(st->w_fbh) + p * fbh; lf.h1[p] = fptr(st->w_fbh) + (2 + p) * fbh; }
-            lf.seq_out = fptr(st->w_y1); lf.seq_stride = chp;
-            launch_live_load(la, lf, h->H, h->CH, s);
+            live = live_args(st, n, nact, plan, out);
+            launch_live_load(live.sb, live.fb, h->H, h->CH, s);
             for (int t = 0; t < nmax; ++t) {
-                lf.t = t; lf.par = t & 1;
-                launch_live_fb_step(h->fbw, lf, 0, s);
-                launch_live_fb_step(h->fbw, lf, 1, s);
+                live.fb.t = t; live.fb.par = t & 1;
+                launch_live_fb_step(h->fbw, live.fb, 0, s);
+                launch_live_fb_step(h->fbw, live.fb, 1, s);
             }
-        } else launch_lstm_generic_stream(h->fbw, fa, s);
-        launch_linear_act(fptr(st->w_y1), chp, h->fsn_wf, h->fsn_kp, h->fsn_bf, fptr(st->w_fb), h->FP, h->CH, F, S, n, h->cfg.fb_act, h->num_cus, s);
+        } else {
+            chunked = chunked_args(st, n, nact, plan, out);
+            launch_lstm_generic_stream(h->fbw, chunked.fb, s);
+        }
+        launch_linear_act(st->at<float>(st->w_y1), (int)align_up(h->CH, 4), h->fsn_wf, h->fsn_kp, h->fsn_bf, st->at<float>(st->w_fb), h->FP, h->CH,
+                          F, S, n, h->cfg.fb_act, h->num_cus, s);
 
         SubbandBuffers sbuf{};
-        sbuf.att_mag = fptr(st->w_raw); sbuf.fb = fptr(st->w_fb); sbuf.NFBN = h->cfg.fb_num_neighbors;
-        sbuf.md_row = reinterpret_cast<NormMD*>(st->ws + st->w_md_row);
-        launch_subband_stats_stream(d, h->cfg.norm_type, sbuf, rows, plan.rows, meta, state_d + st->o_sbsum / 8, (long)(st->state_bytes / 8), s);
+        sbuf.att_mag = st->at<float>(st->w_raw); sbuf.fb = st->at<float>(st->w_fb); sbuf.NFBN = h->cfg.fb_num_neighbors;
+        sbuf.md_row = st->at<NormMD>(st->w_md_row);
+        launch_subband_stats_stream(d, h->cfg.norm_type, sbuf, rows, plan.rows, meta, state_d + st->o_sbsum / 8, sum_stride, s);
 
-        LstmArgs a{};
-        a.att_mag = fptr(st->w_raw); a.fb = fptr(st->w_fb);
-        a.fb_rel = (int)((st->w_fb - st->w_raw) / 4);
-        a.fb_branch_stride = S * n * h->FP;
-        a.rows = rows; a.md_row = sbuf.md_row;
-        a.out = out; a.out_stride_o = (long)F * n;
-        a.num_rows = plan.rows; a.num_tiles = plan.tiles; a.ex = 0;
-        a.Tp = n; a.LA = 0; a.FP = h->FP; a.F = F; a.NSBN = h->cfg.sb_num_neighbors; a.NFBN = h->cfg.fb_num_neighbors;
-        a.act = h->cfg.sb_act;
-        a.st_sb = state_f; a.st_stride = (long)(st->state_bytes / 4);
         if (st->live) {
             for (int t = 0; t < nmax; ++t) {
-                la.t = t; la.par = t & 1;
-                launch_live_sb_step(h->lw, la, 0, s);
-                launch_live_sb_step(h->lw, la, 1, s);
-                launch_live_sb_out(h->lw, la, s);
+                live.sb.t = t; live.sb.par = t & 1;
+                launch_live_sb_step(h->lw, live.sb, 0, s);
+                launch_live_sb_step(h->lw, live.sb, 1, s);
+                launch_live_sb_out(h->lw, live.sb, s);
             }
-        } else launch_lstm_stream(h->lw, a, s);
+        } else launch_lstm_stream(h->lw, chunked.sb, s);
     }
     const long total = (long)S * 2 * F * n;
     hipLaunchKernelGGL(stream_epilogue_kernel, dim3((unsigned)std::min<long>((total + 255) / 256, 4096)), dim3(256), 0, s, out, meta,
                        h->cfg.look_ahead, 2 * F * n, n, total);
     FSNP_HIP_CHECK(hipGetLastError());
     for (int b = 0; b < S; ++b) st->frames[b] += c.v[b];
+    return 0;
+}
+
+// One ring push behind its checks (fsnp_handle.h): the mag push between the two launches of spec_stream.hip, whose apply kernel finds
+// {P, steps} of every slot where the prologue kernel above left them.
+int spec_push_body(fsnp_stream* st, const SpecRing& ring, float* mag, float* mask, const float* spec, const int64_t strides[3],
+                   const SlotCounts& spectra, const SlotCounts& steps, float* out, const int64_t out_strides[3], bool write_idle, int n,
+                   hipStream_t s) {
+    fsnp_handle* h = st->h;
+    SpecArgs a{};
+    a.ring = ring.ring; a.ring_stride = ring.ring_stride; a.meta = st->at<StreamMeta>(st->w_meta);
+    a.S = st->S; a.F = h->F; a.FP = h->FP; a.LA = ring.look_ahead; a.n = n;
+    int total = 0;
+    for (int b = 0; b < st->S; ++b) total += steps.v[b];
+    FSNP_ON_DEVICE(h);
+    if (total > 0) launch_spec_mag(a, spectra, spec, strides, mag, s);
+    const int64_t mst[3] = {(int64_t)n * h->FP, 1, h->FP};             // mag [S][n][FP] as (slot, f, frame)
+    if (const int rc = stream_push_body(st, mag, mst, steps, mask, n, s)) return rc;
+    if (total > 0 || write_idle) launch_spec_apply(a, spectra, mask, spec, strides, out, out_strides, s);
+    FSNP_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
@@ -243,7 +286,7 @@ int stream_create(fsnp_handle* h, int32_t slots, int32_t max_chunk, int live, co
     st->o_sbsum = align_up(st->o_fb + 4 * CH * 4, 8);
     st->o_fbsum = st->o_sbsum + F * 2 * 8;
     st->o_count = st->o_fbsum + 2 * 8;
-    st->state_bytes = align_up(st->o_count + 8, 16);
+    const size_t state_bytes = align_up(st->o_count + 8, 16);
     size_t o = 0;
     auto take = [&](size_t bytes) { size_t r = o; o = align_up(o + bytes, 256); return r; };
     const size_t S = slots, N = max_chunk, chp = align_up(CH, 4);
@@ -264,13 +307,12 @@ int stream_create(fsnp_handle* h, int32_t slots, int32_t max_chunk, int live, co
         st->w_fbh = take(4 * S * CH * 4);
     }
     st->ws_bytes = o;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&st->state), st->state_bytes * S);
+    hipError_t e = st->rec.create(state_bytes, slots);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&st->ws), st->ws_bytes);
-    if (e == hipSuccess) e = hipMemset(st->state, 0, st->state_bytes * S);
     if (e == hipSuccess) e = hipMemset(st->ws, 0, st->ws_bytes);
     if (e != hipSuccess) {
-        set_error("%s: %s (state %zu bytes x %d slots, workspace %zu bytes)", where, hipGetErrorString(e), st->state_bytes, slots, st->ws_bytes);
-        if (st->state) (void)hipFree(st->state);
+        set_error("%s: %s (state %zu bytes x %d slots, workspace %zu bytes)", where, hipGetErrorString(e), state_bytes, slots, st->ws_bytes);
+        st->rec.free();
         if (st->ws) (void)hipFree(st->ws);
         delete st;
         return 4;
@@ -280,8 +322,6 @@ int stream_create(fsnp_handle* h, int32_t slots, int32_t max_chunk, int live, co
     *out = st;
     return 0;
 }
-
-const StreamMeta* stream_meta(const fsnp_stream* st) { return reinterpret_cast<const StreamMeta*>(st->ws + st->w_meta); }
 
 }  // namespace fsnp
 
@@ -300,8 +340,7 @@ int fsnp_stream_is_live(const fsnp_stream* st) { return st ? st->live : 0; }
 void fsnp_stream_destroy(fsnp_stream* st) {
     if (!st) return;
     fsnp::DeviceGuard g(st->h->device);
-    // (hipFree waits for the device: pushes still in flight finish first)
-    if (st->state) (void)hipFree(st->state);
+    st->rec.free();
     if (st->ws) (void)hipFree(st->ws);
     delete st;
 }
@@ -309,59 +348,43 @@ void fsnp_stream_destroy(fsnp_stream* st) {
 int fsnp_stream_push(fsnp_stream* st, const float* mag, const int64_t strides[3], const int32_t* counts, float* out, int32_t n,
                      void* hip_stream) {
     if (!st || !mag || !strides || !out) { set_error("fsnp_stream_push: null argument"); return 1; }
-    fsnp_handle* h = st->h;
     if (n < 1 || n > st->N) { set_error("fsnp_stream_push: n = %d outside [1, max_chunk = %d]", n, st->N); return 2; }
-    StreamCounts c{};
-    for (int b = 0; b < st->S; ++b) {
-        const int v = counts ? counts[b] : n;
-        if (v < 0 || v > n) { set_error("fsnp_stream_push: slot %d: count %d outside [0, n = %d]", b, v, n); return 2; }
-        c.v[b] = v;
-    }
-    if (!h->committed) { set_error("fsnp_stream_push: weights not committed (call fsnp_commit_weights)"); return 2; }
-    if (const int ec = take_device_errors(h, "an earlier call on this handle failed")) return ec;
+    SlotCounts c{};
+    if (const int rc = read_counts("fsnp_stream_push", counts, st->S, n, c)) return rc;
+    if (const int rc = push_preamble(st->h, "fsnp_stream_push")) return rc;
     return stream_push_body(st, mag, strides, c, out, n, static_cast<hipStream_t>(hip_stream));
 }
 
 int fsnp_stream_reset(fsnp_stream* st, const int32_t* slots, int32_t num, void* hip_stream) {
     if (!st) { set_error("fsnp_stream_reset: null argument"); return 1; }
-    if (slots) {
-        if (num < 0) { set_error("fsnp_stream_reset: num = %d", num); return 2; }
-        for (int i = 0; i < num; ++i)
-            if (slots[i] < 0 || slots[i] >= st->S) { set_error("fsnp_stream_reset: slot %d outside [0, %d)", slots[i], st->S); return 2; }
-    }
+    if (const int rc = check_slots("fsnp_stream_reset", slots, num, st->S)) return rc;
     FSNP_ON_DEVICE(st->h);
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     st->last_stream = s;
+    if (const int rc = st->rec.reset(slots, num, s)) return rc;
     if (!slots) {
-        FSNP_HIP_CHECK(hipMemsetAsync(st->state, 0, st->state_bytes * st->S, s));
         std::fill(st->frames.begin(), st->frames.end(), 0);
         std::fill(st->frames_known.begin(), st->frames_known.end(), 1);
-        return 0;
-    }
-    for (int i = 0; i < num; ++i) {
-        FSNP_HIP_CHECK(hipMemsetAsync(st->state + (size_t)slots[i] * st->state_bytes, 0, st->state_bytes, s));
-        st->frames[slots[i]] = 0; st->frames_known[slots[i]] = 1;
-    }
+    } else
+        for (int i = 0; i < num; ++i) { st->frames[slots[i]] = 0; st->frames_known[slots[i]] = 1; }
     return 0;
 }
 
-int64_t fsnp_stream_state_bytes(const fsnp_stream* st) { return st ? (int64_t)st->state_bytes : 0; }
+int64_t fsnp_stream_state_bytes(const fsnp_stream* st) { return st ? (int64_t)st->rec.bytes : 0; }
 
 int fsnp_stream_get_state(fsnp_stream* st, int32_t slot, void* dev_dst, void* hip_stream) {
     if (!st || !dev_dst) { set_error("fsnp_stream_get_state: null argument"); return 1; }
-    if (slot < 0 || slot >= st->S) { set_error("fsnp_stream_get_state: slot %d outside [0, %d)", slot, st->S); return 2; }
+    if (const int rc = check_slot("fsnp_stream_get_state", slot, st->S)) return rc;
     FSNP_ON_DEVICE(st->h);
-    FSNP_HIP_CHECK(hipMemcpyAsync(dev_dst, st->state + (size_t)slot * st->state_bytes, st->state_bytes, hipMemcpyDeviceToDevice,
-                                  static_cast<hipStream_t>(hip_stream)));
-    return 0;
+    return st->rec.get(slot, dev_dst, 0, static_cast<hipStream_t>(hip_stream));
 }
 
 int fsnp_stream_set_state(fsnp_stream* st, int32_t slot, const void* dev_src, void* hip_stream) {
     if (!st || !dev_src) { set_error("fsnp_stream_set_state: null argument"); return 1; }
-    if (slot < 0 || slot >= st->S) { set_error("fsnp_stream_set_state: slot %d outside [0, %d)", slot, st->S); return 2; }
+    if (const int rc = check_slot("fsnp_stream_set_state", slot, st->S)) return rc;
     FSNP_ON_DEVICE(st->h);
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    FSNP_HIP_CHECK(hipMemcpyAsync(st->state + (size_t)slot * st->state_bytes, dev_src, st->state_bytes, hipMemcpyDeviceToDevice, s));
+    if (const int rc = st->rec.set(slot, dev_src, 0, s)) return rc;
     st->last_stream = s;
     st->frames[slot] = 0; st->frames_known[slot] = 0;
     return 0;
@@ -369,11 +392,11 @@ int fsnp_stream_set_state(fsnp_stream* st, int32_t slot, const void* dev_src, vo
 
 int fsnp_stream_frames(fsnp_stream* st, int32_t slot, int64_t* pushed) {
     if (!st || !pushed) { set_error("fsnp_stream_frames: null argument"); return 1; }
-    if (slot < 0 || slot >= st->S) { set_error("fsnp_stream_frames: slot %d outside [0, %d)", slot, st->S); return 2; }
+    if (const int rc = check_slot("fsnp_stream_frames", slot, st->S)) return rc;
     if (!st->frames_known[slot]) {       // loaded with fsnp_stream_set_state: the count lives in the record (+ what was pushed since)
         FSNP_ON_DEVICE(st->h);
         long long v = 0;
-        FSNP_HIP_CHECK(hipMemcpyAsync(&v, st->state + (size_t)slot * st->state_bytes + st->o_count, 8, hipMemcpyDeviceToHost, st->last_stream));
+        FSNP_HIP_CHECK(hipMemcpyAsync(&v, st->rec.slot(slot) + st->o_count, 8, hipMemcpyDeviceToHost, st->last_stream));
         FSNP_HIP_CHECK(hipStreamSynchronize(st->last_stream));
         st->frames[slot] = v; st->frames_known[slot] = 1;
     }

@@ -1,33 +1,32 @@
 // fsnp_wave_stream_abi.hip - include/fsnp_wave_stream.h: waveform sessions of the original FullSubNet (samples in, samples out).
 //
-// A session is a mag-stream session (fsnp_stream_abi.hip) of max_samples / hop + 1 frames per push with, per slot, a wave record
-// behind the mag-stream record (layout: fsnp_common.h, WaveArgs) and a workspace of its own, allocated and zeroed at creation.  One
-// push on the caller's stream, nothing allocated, nothing synchronised:
+// A wave session is a spectrum session between two transforms.  It holds a mag-stream session (fsnp_stream_abi.hip) of
+// max_samples / hop + 1 frames per push with, per slot, a wave record behind the mag-stream record (layout: fsnp_common.h, WaveArgs;
+// the look-ahead ring lies inside it) and a workspace of its own, allocated and zeroed at creation.  One push on the caller's stream,
+// nothing allocated, nothing synchronised:
 //   wave_gather_kernel   the rows of the newly complete frames from the carried samples + the new ones, the carry and the count advanced
-//   launch_linear_act    forward DFT (the handle's d_stft matrices, window folded in) -> spectra
-//   wave_mag_kernel      |spectrum|, as the whole-clip complex forward takes it
-//   stream_push_body     the mag push with the frames each slot completed as its counts
-//   wave_apply_kernel    cIRM of step j times the noisy spectrum of frame P_f + j - look_ahead (this push's or the ring's); ring advanced
+//   launch_linear_act    forward DFT (the handle's d_stft matrices, window folded in) -> spectra, one workspace row per frame
+//   spec_push_body       the ring push of a spectrum session on those rows, the frames each slot completed as its counts: |X|, the mag
+//                        push, cIRM of step j times the noisy spectrum of frame P_f + j - look_ahead into row j (zeros where there is
+//                        none), ring advanced
 //   launch_linear_act    inverse DFT -> windowed frames
 //   wave_ola_kernel      overlap-add + envelope division into the fifo, this push's c samples out (zeros before D and past c)
-// fsnp_wave_stream_finish runs the same chain with the clip's last frame (reflected at the end) and look_ahead zero frames into the model,
-// emits the remaining D samples and resets the slots.  The host mirrors every slot's sample count, so frames per slot are known without
-// asking the device.
+// fsnp_wave_stream_finish runs the same chain with the clip's last frame (reflected at the end) and look_ahead zero frames into the model
+// (one spectrum, 1 + look_ahead steps), emits the remaining D samples and resets the slots.  The host mirrors every slot's sample count,
+// so frames per slot are known without asking the device.
 #include <algorithm>
 #include <vector>
 
 #include "fsnp_handle.h"
-
-static_assert(sizeof(WaveCounts) == sizeof(StreamCounts), "one count per slot of a mag session");
 
 struct fsnp_wave_stream {
     fsnp_handle* h = nullptr;
     fsnp_stream* mag = nullptr;       // the model's state and its push
     int S = 0, max_samples = 0, NF = 0, hop = 0, LA = 0, D = 0;
     StftPlan p{};
-    size_t mag_bytes = 0, rec_bytes = 0;                          // one slot: mag-stream record, wave record
+    size_t mag_bytes = 0;             // one slot's mag-stream record
+    SlotRecords rec;                  // the slots' wave records behind it
     size_t o_ring = 0, o_tail = 0, o_fifo = 0, o_count = 0;       // byte offsets inside a wave record (carry at 0)
-    unsigned char* state = nullptr;   // [S][rec_bytes]
     unsigned char* ws = nullptr;
     size_t ws_bytes = 0;
     size_t w_meta = 0, w_xfr = 0, w_spec = 0, w_mag = 0, w_mask = 0, w_enh = 0, w_fr = 0;
@@ -36,71 +35,51 @@ struct fsnp_wave_stream {
 
 namespace {
 
-WaveArgs wave_args(const fsnp_wave_stream* w, int nrow) {
-    WaveArgs a{};
-    a.state = w->state; a.stride = w->rec_bytes; a.o_ring = w->o_ring; a.o_tail = w->o_tail; a.o_fifo = w->o_fifo; a.o_count = w->o_count;
-    a.meta = reinterpret_cast<WaveMeta*>(w->ws + w->w_meta);
-    a.S = w->S; a.F = w->p.F; a.hop = w->hop; a.LA = w->LA; a.sp = w->p.sp; a.FP = w->h->FP; a.nrow = nrow;
-    return a;
-}
-
 // the chain of one push (fin = 0, c.v = samples per slot) or one finish (fin = 1, c.v = 1 for the slots that end): checks are done
-int wave_run(fsnp_wave_stream* w, const WaveCounts& c, int fin, const float* wav, long wav_stride, float* out, long out_stride, int ncols,
+int wave_run(fsnp_wave_stream* w, const SlotCounts& c, int fin, const float* wav, long wav_stride, float* out, long out_stride, int ncols,
              hipStream_t s) {
     fsnp_handle* h = w->h;
     const StftPlan& p = w->p;
-    StreamCounts fc{};
+    SlotCounts spectra{}, steps{};
     int nrow = 1, frames = 0;
     for (int b = 0; b < w->S; ++b) {
         const WaveStep st = wave_step(w->samples[b], fin ? 0 : c.v[b], fin ? c.v[b] : 0, w->hop, w->LA);
-        fc.v[b] = st.km;
-        nrow = std::max(nrow, fc.v[b]);
-        frames += fc.v[b];
+        spectra.v[b] = st.ks; steps.v[b] = st.km;
+        nrow = std::max(nrow, st.km);
+        frames += st.km;
     }
     FSNP_ON_DEVICE(h);
     auto fptr = [&](size_t off) { return reinterpret_cast<float*>(w->ws + off); };
-    const WaveArgs a = wave_args(w, nrow);
+    WaveArgs a{};
+    a.state = w->rec.base; a.stride = w->rec.bytes; a.o_tail = w->o_tail; a.o_fifo = w->o_fifo; a.o_count = w->o_count;
+    a.meta = reinterpret_cast<WaveMeta*>(w->ws + w->w_meta);
+    a.S = w->S; a.hop = w->hop; a.LA = w->LA; a.nrow = nrow;
     const int rows = w->S * nrow;
     launch_wave_gather(a, c, fin, wav, wav_stride, fptr(w->w_xfr), s);
-    if (frames > 0) {
+    if (frames > 0)
         launch_linear_act(fptr(w->w_xfr), p.n_fft, h->d_stft + p.o_fwd, p.n_fft, h->d_stft + p.o_zero, fptr(w->w_spec), p.sp, p.n_fft, p.N2, 1,
                           rows, FSNP_ACT_NONE, h->num_cus, s);
-        launch_wave_mag(a, fptr(w->w_spec), fptr(w->w_mag), s);
-    }
-    const int64_t mst[3] = {(int64_t)nrow * h->FP, 1, h->FP};         // mag [S][nrow][FP] as (slot, f, frame)
-    if (const int rc = stream_push_body(w->mag, fptr(w->w_mag), mst, fc, fptr(w->w_mask), nrow, s)) return rc;
-    if (frames > 0) {
-        launch_wave_apply(a, fptr(w->w_mask), fptr(w->w_spec), fptr(w->w_enh), s);
+    // spectra and enhanced spectra [S][nrow][sp] floats as complex (slot, f, frame); without frames there is nothing to transform back,
+    // so the ring push need not write the zero rows of such a call (write_idle = false)
+    const int64_t cst[3] = {(int64_t)nrow * (p.sp / 2), 1, p.sp / 2};
+    if (const int rc = spec_push_body(w->mag, SpecRing{w->rec.base + w->o_ring, w->rec.bytes, w->LA}, fptr(w->w_mag), fptr(w->w_mask),
+                                      fptr(w->w_spec), cst, spectra, steps, fptr(w->w_enh), cst, false, nrow, s))
+        return rc;
+    if (frames > 0)
         launch_linear_act(fptr(w->w_enh), p.sp, h->d_stft + p.o_inv, p.inv_ld, h->d_stft + p.o_zero, fptr(w->w_fr), p.n_fft, p.N2, p.n_fft, 1,
                           rows, FSNP_ACT_NONE, h->num_cus, s, 0, p.N2);
-    }
     launch_wave_ola(a, fptr(w->w_fr), h->d_stft + p.o_win, out, out_stride, ncols, s);
     FSNP_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
-int check_slots(const fsnp_wave_stream* w, const int32_t* slots, int32_t num, const char* where) {
-    if (!slots) return 0;
-    if (num < 0) { set_error("%s: num = %d", where, num); return 2; }
-    for (int i = 0; i < num; ++i)
-        if (slots[i] < 0 || slots[i] >= w->S) { set_error("%s: slot %d outside [0, %d)", where, slots[i], w->S); return 2; }
-    return 0;
-}
-
-// stream-ordered zeroing of both records of the slots (NULL = all), the host mirror with them
+// stream-ordered zeroing of both records of the (checked) slots (NULL = all), the host mirror with them
 int wave_reset(fsnp_wave_stream* w, const int32_t* slots, int32_t num, void* hip_stream) {
     if (const int rc = fsnp_stream_reset(w->mag, slots, num, hip_stream)) return rc;
     FSNP_ON_DEVICE(w->h);
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    if (!slots) {
-        FSNP_HIP_CHECK(hipMemsetAsync(w->state, 0, w->rec_bytes * w->S, s));
-        std::fill(w->samples.begin(), w->samples.end(), 0);
-        return 0;
-    }
-    for (int i = 0; i < num; ++i) {
-        FSNP_HIP_CHECK(hipMemsetAsync(w->state + (size_t)slots[i] * w->rec_bytes, 0, w->rec_bytes, s));
-        w->samples[slots[i]] = 0;
-    }
+    if (const int rc = w->rec.reset(slots, num, static_cast<hipStream_t>(hip_stream))) return rc;
+    if (!slots) std::fill(w->samples.begin(), w->samples.end(), 0);
+    else for (int i = 0; i < num; ++i) w->samples[slots[i]] = 0;
     return 0;
 }
 
@@ -129,7 +108,7 @@ int wave_create(fsnp_handle* h, int32_t slots, int32_t max_samples, int live, co
     w->o_tail = w->o_ring + (size_t)LA * p.F * 8;
     w->o_fifo = w->o_tail + (size_t)hop * 4;
     w->o_count = align_up(w->o_fifo + (size_t)hop * 4, 8);
-    w->rec_bytes = align_up(w->o_count + 8, 16);
+    const size_t rec_bytes = align_up(w->o_count + 8, 16);
     size_t o = 0;
     auto take = [&](size_t bytes) { size_t r = o; o = align_up(o + bytes, 256); return r; };
     const size_t S = slots, rows = S * NF;
@@ -142,14 +121,13 @@ int wave_create(fsnp_handle* h, int32_t slots, int32_t max_samples, int live, co
     w->w_fr = take(rows * p.n_fft * 4);
     w->ws_bytes = o;
     fsnp::DeviceGuard g(h->device);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&w->state), w->rec_bytes * S);
+    hipError_t e = w->rec.create(rec_bytes, slots);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&w->ws), w->ws_bytes);
-    if (e == hipSuccess) e = hipMemset(w->state, 0, w->rec_bytes * S);
     if (e == hipSuccess) e = hipMemset(w->ws, 0, w->ws_bytes);      // (pad columns of the spectrum rows stay 0 for good)
     if (e != hipSuccess) {
-        set_error("%s: %s (wave state %zu bytes x %d slots, workspace %zu bytes)", where, hipGetErrorString(e), w->rec_bytes, slots,
+        set_error("%s: %s (wave state %zu bytes x %d slots, workspace %zu bytes)", where, hipGetErrorString(e), rec_bytes, slots,
                   w->ws_bytes);
-        if (w->state) (void)hipFree(w->state);
+        w->rec.free();
         if (w->ws) (void)hipFree(w->ws);
         fsnp_stream_destroy(mag);
         delete w;
@@ -176,7 +154,7 @@ void fsnp_wave_stream_destroy(fsnp_wave_stream* w) {
     if (!w) return;
     {
         fsnp::DeviceGuard g(w->h->device);
-        if (w->state) (void)hipFree(w->state);
+        w->rec.free();
         if (w->ws) (void)hipFree(w->ws);
     }
     fsnp_stream_destroy(w->mag);
@@ -186,16 +164,10 @@ void fsnp_wave_stream_destroy(fsnp_wave_stream* w) {
 int fsnp_wave_stream_push(fsnp_wave_stream* w, const float* wav, int64_t wav_stride, const int32_t* counts, float* out, int64_t out_stride,
                           int32_t n, void* hip_stream) {
     if (!w || !wav || !out) { set_error("fsnp_wave_stream_push: null argument"); return 1; }
-    fsnp_handle* h = w->h;
     if (n < 1 || n > w->max_samples) { set_error("fsnp_wave_stream_push: n = %d outside [1, max_samples = %d]", n, w->max_samples); return 2; }
-    WaveCounts c{};
-    for (int b = 0; b < w->S; ++b) {
-        const int v = counts ? counts[b] : n;
-        if (v < 0 || v > n) { set_error("fsnp_wave_stream_push: slot %d: count %d outside [0, n = %d]", b, v, n); return 2; }
-        c.v[b] = v;
-    }
-    if (!h->committed) { set_error("fsnp_wave_stream_push: weights not committed (call fsnp_commit_weights)"); return 2; }
-    if (const int ec = take_device_errors(h, "an earlier call on this handle failed")) return ec;
+    SlotCounts c{};
+    if (const int rc = read_counts("fsnp_wave_stream_push", counts, w->S, n, c)) return rc;
+    if (const int rc = push_preamble(w->h, "fsnp_wave_stream_push")) return rc;
     if (const int rc = wave_run(w, c, 0, wav, (long)wav_stride, out, (long)out_stride, n, static_cast<hipStream_t>(hip_stream))) return rc;
     for (int b = 0; b < w->S; ++b) w->samples[b] += c.v[b];
     return 0;
@@ -203,9 +175,8 @@ int fsnp_wave_stream_push(fsnp_wave_stream* w, const float* wav, int64_t wav_str
 
 int fsnp_wave_stream_finish(fsnp_wave_stream* w, const int32_t* slots, int32_t num, float* out, int64_t out_stride, void* hip_stream) {
     if (!w || !out) { set_error("fsnp_wave_stream_finish: null argument"); return 1; }
-    fsnp_handle* h = w->h;
-    if (const int rc = check_slots(w, slots, num, "fsnp_wave_stream_finish")) return rc;
-    WaveCounts c{};
+    if (const int rc = check_slots("fsnp_wave_stream_finish", slots, num, w->S)) return rc;
+    SlotCounts c{};
     if (slots) for (int i = 0; i < num; ++i) c.v[slots[i]] = 1;
     else for (int b = 0; b < w->S; ++b) c.v[b] = 1;
     for (int b = 0; b < w->S; ++b) {
@@ -217,43 +188,39 @@ int fsnp_wave_stream_finish(fsnp_wave_stream* w, const int32_t* slots, int32_t n
             return 2;
         }
     }
-    if (!h->committed) { set_error("fsnp_wave_stream_finish: weights not committed (call fsnp_commit_weights)"); return 2; }
-    if (const int ec = take_device_errors(h, "an earlier call on this handle failed")) return ec;
+    if (const int rc = push_preamble(w->h, "fsnp_wave_stream_finish")) return rc;
     if (const int rc = wave_run(w, c, 1, nullptr, 0, out, (long)out_stride, w->D, static_cast<hipStream_t>(hip_stream))) return rc;
     return wave_reset(w, slots, num, hip_stream);
 }
 
 int fsnp_wave_stream_reset(fsnp_wave_stream* w, const int32_t* slots, int32_t num, void* hip_stream) {
     if (!w) { set_error("fsnp_wave_stream_reset: null argument"); return 1; }
-    if (const int rc = check_slots(w, slots, num, "fsnp_wave_stream_reset")) return rc;
+    if (const int rc = check_slots("fsnp_wave_stream_reset", slots, num, w->S)) return rc;
     return wave_reset(w, slots, num, hip_stream);
 }
 
 int fsnp_wave_stream_delay(const fsnp_wave_stream* w) { return w ? w->D : 0; }
 
-int64_t fsnp_wave_stream_state_bytes(const fsnp_wave_stream* w) { return w ? (int64_t)(w->mag_bytes + w->rec_bytes) : 0; }
+int64_t fsnp_wave_stream_state_bytes(const fsnp_wave_stream* w) { return w ? (int64_t)(w->mag_bytes + w->rec.bytes) : 0; }
 
 int fsnp_wave_stream_get_state(fsnp_wave_stream* w, int32_t slot, void* dev_dst, void* hip_stream) {
     if (!w || !dev_dst) { set_error("fsnp_wave_stream_get_state: null argument"); return 1; }
-    if (slot < 0 || slot >= w->S) { set_error("fsnp_wave_stream_get_state: slot %d outside [0, %d)", slot, w->S); return 2; }
+    if (const int rc = check_slot("fsnp_wave_stream_get_state", slot, w->S)) return rc;
     if (const int rc = fsnp_stream_get_state(w->mag, slot, dev_dst, hip_stream)) return rc;
     FSNP_ON_DEVICE(w->h);
-    FSNP_HIP_CHECK(hipMemcpyAsync(static_cast<unsigned char*>(dev_dst) + w->mag_bytes, w->state + (size_t)slot * w->rec_bytes, w->rec_bytes,
-                                  hipMemcpyDeviceToDevice, static_cast<hipStream_t>(hip_stream)));
-    return 0;
+    return w->rec.get(slot, dev_dst, w->mag_bytes, static_cast<hipStream_t>(hip_stream));
 }
 
 int fsnp_wave_stream_set_state(fsnp_wave_stream* w, int32_t slot, const void* dev_src, void* hip_stream) {
     if (!w || !dev_src) { set_error("fsnp_wave_stream_set_state: null argument"); return 1; }
-    if (slot < 0 || slot >= w->S) { set_error("fsnp_wave_stream_set_state: slot %d outside [0, %d)", slot, w->S); return 2; }
+    if (const int rc = check_slot("fsnp_wave_stream_set_state", slot, w->S)) return rc;
     if (const int rc = fsnp_stream_set_state(w->mag, slot, dev_src, hip_stream)) return rc;
     FSNP_ON_DEVICE(w->h);
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    const unsigned char* rec = static_cast<const unsigned char*>(dev_src) + w->mag_bytes;
-    FSNP_HIP_CHECK(hipMemcpyAsync(w->state + (size_t)slot * w->rec_bytes, rec, w->rec_bytes, hipMemcpyDeviceToDevice, s));
+    if (const int rc = w->rec.set(slot, dev_src, w->mag_bytes, s)) return rc;
     // a migration call: the frames a later push completes follow from the slot's sample count, which the host must know - one wait
     long long v = 0;
-    FSNP_HIP_CHECK(hipMemcpyAsync(&v, rec + w->o_count, 8, hipMemcpyDeviceToHost, s));
+    FSNP_HIP_CHECK(hipMemcpyAsync(&v, static_cast<const unsigned char*>(dev_src) + w->mag_bytes + w->o_count, 8, hipMemcpyDeviceToHost, s));
     FSNP_HIP_CHECK(hipStreamSynchronize(s));
     if (v < 0) { set_error("fsnp_wave_stream_set_state: slot %d: the loaded record holds a negative sample count", slot); return 2; }
     w->samples[slot] = v;
@@ -262,7 +229,7 @@ int fsnp_wave_stream_set_state(fsnp_wave_stream* w, int32_t slot, const void* de
 
 int fsnp_wave_stream_samples(fsnp_wave_stream* w, int32_t slot, int64_t* pushed) {
     if (!w || !pushed) { set_error("fsnp_wave_stream_samples: null argument"); return 1; }
-    if (slot < 0 || slot >= w->S) { set_error("fsnp_wave_stream_samples: slot %d outside [0, %d)", slot, w->S); return 2; }
+    if (const int rc = check_slot("fsnp_wave_stream_samples", slot, w->S)) return rc;
     *pushed = w->samples[slot];
     return 0;
 }

@@ -1,15 +1,17 @@
-// spec_stream.hip - the two short launches of a spectrum session's push (include/fsnp_spec_stream.h) around one mag push.
+// spec_stream.hip - the two short launches of a ring push (fsnp_stream_abi.hip, spec_push_body) around one mag push.
 //
-// The caller owns the STFT: noisy complex64 frames come in with strides (slot, f, frame) in complex elements, enhanced frames go out
-// the same way.  The mask of frame t is the model's output of step t + look_ahead, so the noisy spectra of the newest look_ahead
-// frames wait in a per-slot ring (frame g in row g % look_ahead) behind the mag-stream record.  The ring's position is the record's
-// own frame count, which the mag push's prologue kernel publishes as StreamMeta.p: the host mirrors nothing.
+// Noisy complex64 spectra come in with strides (slot, f, frame) in complex elements, enhanced spectra go out the same way: the caller's
+// tensors for a spectrum session (include/fsnp_spec_stream.h), the workspace rows between the two DFT GEMMs for a wave session
+// (include/fsnp_wave_stream.h).  The mask of frame t is the model's output of step t + look_ahead, so the noisy spectra of the newest
+// look_ahead frames wait in a per-slot ring (frame g in row g % look_ahead).  The ring's position is the mag record's own frame count,
+// which the mag push's prologue kernel publishes as StreamMeta.p together with the slot's steps of this push: the host mirrors nothing.
+// A slot brings as many spectra as it steps, except a wave slot that is finished: one spectrum, 1 + look_ahead steps.
 #include "fsnp_common.h"
 
 namespace fsnp {
 
 // hypotf as fe_repack_complex_kernel takes the magnitude of a complex forward's input; one thread per (slot, frame, padded bin)
-__global__ __launch_bounds__(256) void spec_mag_kernel(SpecArgs a, SpecCounts cnt, const float2* __restrict__ spec, long sb, long sf, long st,
+__global__ __launch_bounds__(256) void spec_mag_kernel(SpecArgs a, SlotCounts cnt, const float2* __restrict__ spec, long sb, long sf, long st,
                                                        float* __restrict__ mag, long total) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
@@ -22,16 +24,17 @@ __global__ __launch_bounds__(256) void spec_mag_kernel(SpecArgs a, SpecCounts cn
     mag[i] = v;
 }
 
-void launch_spec_mag(const SpecArgs& a, const SpecCounts& c, const float* spec, const int64_t strides[3], float* mag, hipStream_t s) {
+void launch_spec_mag(const SpecArgs& a, const SlotCounts& c, const float* spec, const int64_t strides[3], float* mag, hipStream_t s) {
     const long total = (long)a.S * a.n * a.FP;
     hipLaunchKernelGGL(spec_mag_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a, c, reinterpret_cast<const float2*>(spec),
                        (long)strides[0], (long)strides[1], (long)strides[2], mag, total);
 }
 
 // one thread per (slot, f): it alone touches bin f of the slot's ring, so reading the waiting spectra and replacing them needs no barrier
-// (spec and out carry no __restrict__: both are the caller's)
-__global__ __launch_bounds__(256) void spec_apply_kernel(SpecArgs a, const float* __restrict__ mask, const float2* spec, long sb, long sf,
-                                                         long st, float2* out, long ob, long of, long ot) {
+// (spec and out carry no __restrict__: both may be the caller's).  m.cnt = the slot's steps, cnt.v = its spectra: the ring takes what
+// came in, never the zero frames behind a finished clip's last one
+__global__ __launch_bounds__(256) void spec_apply_kernel(SpecArgs a, SlotCounts cnt, const float* __restrict__ mask, const float2* spec, long sb,
+                                                         long sf, long st, float2* out, long ob, long of, long ot) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= a.S * a.F) return;
     const int b = i / a.F, f = i - b * a.F;
@@ -48,13 +51,14 @@ __global__ __launch_bounds__(256) void spec_apply_kernel(SpecArgs a, const float
         }
         o[j * ot] = y;
     }
+    const int ks = cnt.v[b];
     if (a.LA > 0)
-        for (int j = m.cnt > a.LA ? m.cnt - a.LA : 0; j < m.cnt; ++j) ring[(int)((m.p + j) % a.LA) * a.F + f] = in[j * st];
+        for (int j = ks > a.LA ? ks - a.LA : 0; j < ks; ++j) ring[(int)((m.p + j) % a.LA) * a.F + f] = in[j * st];
 }
 
-void launch_spec_apply(const SpecArgs& a, const float* mask, const float* spec, const int64_t strides[3], float* out,
+void launch_spec_apply(const SpecArgs& a, const SlotCounts& c, const float* mask, const float* spec, const int64_t strides[3], float* out,
                        const int64_t out_strides[3], hipStream_t s) {
-    hipLaunchKernelGGL(spec_apply_kernel, dim3(cdiv(a.S * a.F, 256)), dim3(256), 0, s, a, mask, reinterpret_cast<const float2*>(spec),
+    hipLaunchKernelGGL(spec_apply_kernel, dim3(cdiv(a.S * a.F, 256)), dim3(256), 0, s, a, c, mask, reinterpret_cast<const float2*>(spec),
                        (long)strides[0], (long)strides[1], (long)strides[2], reinterpret_cast<float2*>(out), (long)out_strides[0],
                        (long)out_strides[1], (long)out_strides[2]);
 }

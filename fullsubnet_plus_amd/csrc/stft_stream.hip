@@ -1,12 +1,14 @@
-// stft_stream.hip - the streaming halves of stft.hip (include/fsnp_wave_stream.h): samples in, samples out around one mag push.
+// stft_stream.hip - the streaming halves of stft.hip (include/fsnp_wave_stream.h): samples in, samples out around one ring push.
 //
 // torch.stft(center=True, reflect) / torch.istft(length=L) of a clip that arrives in blocks, hop = n_fft / 2.  Frame t is centred at
 // t * hop and covers samples [(t - 1) hop, (t + 1) hop): it is complete once (t + 1) hop samples have arrived (frame 0 reflects
 // wav[1 .. hop] and needs hop + 1).  Output sample i = (fr[i / hop][hop + i % hop] + fr[i / hop + 1][i % hop]) / (the two w^2), so it
 // needs the ENHANCED frames i / hop and i / hop + 1, and the mask of frame t is the model's output of step t + look_ahead: the push that
 // brings input sample i + D, D = (2 + look_ahead) hop, always has them.  The two DFTs are the GEMMs of the whole-clip path
-// (launch_linear_act with the handle's matrices); the kernels here gather the frame rows, carry what a later push needs (layout:
-// fsnp_common.h, WaveArgs) and emit.  {P, c} of every slot: c as a kernel argument, P from the slot's record (WaveMeta).
+// (launch_linear_act with the handle's matrices) and what lies between them is a spectrum session's push (spec_push_body: |X|, the mag
+// push, cIRM times the waiting spectrum); the two kernels here gather the frame rows in front of it and overlap-add behind it, and carry
+// what a later push needs (layout: fsnp_common.h, WaveArgs).  {P, c} of every slot: c as a kernel argument, P from the slot's record
+// (WaveMeta).
 #include "fsnp_common.h"
 
 namespace fsnp {
@@ -14,7 +16,7 @@ namespace fsnp {
 __device__ __forceinline__ unsigned char* wave_rec(const WaveArgs& a, int b) { return a.state + (size_t)b * a.stride; }
 
 // one workgroup per slot; dynamic LDS: the old carry, n_fft + 1 floats (the carry is rewritten in place)
-__global__ __launch_bounds__(256) void wave_gather_kernel(WaveArgs a, WaveCounts cnt, int fin_call, const float* __restrict__ wav,
+__global__ __launch_bounds__(256) void wave_gather_kernel(WaveArgs a, SlotCounts cnt, int fin_call, const float* __restrict__ wav,
                                                           long wav_stride, float* __restrict__ xfr) {
     extern __shared__ float old[];
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -52,54 +54,8 @@ __global__ __launch_bounds__(256) void wave_gather_kernel(WaveArgs a, WaveCounts
         }
 }
 
-void launch_wave_gather(const WaveArgs& a, const WaveCounts& c, int fin, const float* wav, long wav_stride, float* xfr, hipStream_t s) {
+void launch_wave_gather(const WaveArgs& a, const SlotCounts& c, int fin, const float* wav, long wav_stride, float* xfr, hipStream_t s) {
     hipLaunchKernelGGL(wave_gather_kernel, dim3(a.S), dim3(256), (size_t)(2 * a.hop + 1) * sizeof(float), s, a, c, fin, wav, wav_stride, xfr);
-}
-
-// hypotf as fe_repack_complex_kernel takes the magnitude of a complex forward's input
-__global__ __launch_bounds__(256) void wave_mag_kernel(WaveArgs a, const float2* __restrict__ spec, float* __restrict__ mag, long total) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;            // (slot, row, f) over the padded row of FP
-    if (i >= total) return;
-    const int f = (int)(i % a.FP), j = (int)((i / a.FP) % a.nrow), b = (int)(i / ((long)a.FP * a.nrow));
-    const WaveMeta m = a.meta[b];
-    const WaveStep w = wave_step(m.p, m.c, m.fin, a.hop, a.LA);
-    if (j >= w.km) return;
-    float v = 0.0f;
-    if (j < w.ks && f < a.F) {
-        const float2 x = spec[((long)b * a.nrow + j) * (a.sp / 2) + f];
-        v = hypotf(x.x, x.y);
-    }
-    mag[i] = v;
-}
-
-void launch_wave_mag(const WaveArgs& a, const float* spec, float* mag, hipStream_t s) {
-    const long total = (long)a.S * a.nrow * a.FP;
-    hipLaunchKernelGGL(wave_mag_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a, reinterpret_cast<const float2*>(spec), mag, total);
-}
-
-// one thread per (slot, f): it alone touches bin f of the slot's ring, so reading the waiting spectra and replacing them needs no barrier
-__global__ __launch_bounds__(256) void wave_apply_kernel(WaveArgs a, const float* __restrict__ mask, const float2* __restrict__ spec,
-                                                         float2* __restrict__ enh) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= a.S * a.F) return;
-    const int b = i / a.F, f = i - b * a.F;
-    const WaveMeta m = a.meta[b];
-    const WaveStep w = wave_step(m.p, m.c, m.fin, a.hop, a.LA);
-    float2* ring = reinterpret_cast<float2*>(wave_rec(a, b) + a.o_ring);
-    const int sp2 = a.sp / 2;
-    const long row0 = (long)b * a.nrow;
-    for (int j = w.j0; j < w.km; ++j) {
-        const long long g = w.nf + j - a.LA;                           // the frame whose mask step j is
-        const float2 x = g < w.nf ? ring[(int)(g % a.LA) * a.F + f] : spec[(row0 + (g - w.nf)) * sp2 + f];
-        enh[(row0 + (j - w.j0)) * sp2 + f] = cirm_times(mask, ((long)b * 2 * a.F + f) * a.nrow + j, (long)a.F * a.nrow, x);
-    }
-    if (a.LA > 0 && !m.fin)
-        for (int j = w.ks > a.LA ? w.ks - a.LA : 0; j < w.ks; ++j) ring[(int)((w.nf + j) % a.LA) * a.F + f] = spec[(row0 + j) * sp2 + f];
-}
-
-void launch_wave_apply(const WaveArgs& a, const float* mask, const float* spec, float* enh, hipStream_t s) {
-    hipLaunchKernelGGL(wave_apply_kernel, dim3(cdiv(a.S * a.F, 256)), dim3(256), 0, s, a, mask, reinterpret_cast<const float2*>(spec),
-                       reinterpret_cast<float2*>(enh));
 }
 
 // one workgroup per slot; dynamic LDS: the old tail and the old fifo, hop floats each (both are rewritten in place).  The arithmetic of
@@ -121,7 +77,7 @@ __global__ __launch_bounds__(256) void wave_ola_kernel(WaveArgs a, const float* 
     const long long sent_old = m.p > D ? m.p - D : 0;                  // samples emitted before this call: the fifo holds [sent_old, done_old)
     for (int i = tid; i < hop; i += 256) { s_tail[i] = tail[i]; s_fifo[i] = fifo[i]; }
     __syncthreads();
-    auto frame = [&](long long e) { return fr + ((long)b * a.nrow + (e - e_old)) * N; };
+    auto frame = [&](long long e) { return fr + ((long)b * a.nrow + (e - e_old + w.j0)) * N; };      // row j = step j = frame nf + j - LA
     auto sample = [&](long long i) -> float {                          // sent_old <= i < (finish: L, else) (e_new - 1) hop
         if (i < done_old) return s_fifo[(int)(i - sent_old)];
         const long long t0 = i / hop, t1 = t0 + 1;

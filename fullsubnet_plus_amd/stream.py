@@ -23,6 +23,7 @@ All three take live=True (include/fsnp_stream_live.h): the session mode for a fe
 fill the chip at one slot.  Same interface, same state records; max_chunk <= 16.
 """
 import ctypes
+import gc
 
 import torch
 
@@ -48,19 +49,6 @@ def refusal(model):
     return None
 
 
-def wave_refusal(model):
-    """Why `model` (a FullSubNet) cannot stream waveforms, or None: refusal(), and what enhance_wave demands.  No GPU is touched."""
-    why = refusal(model)
-    if why is not None:
-        return why
-    if model.output_size != 2:
-        return f"the cIRM epilogue needs output_size = 2 (this model: {model.output_size})"
-    hop = model.num_freqs - 1
-    if model.num_freqs < 3 or hop & (hop - 1):
-        return "num_freqs - 1 must be a power of two (n_fft = 2 (num_freqs - 1))"
-    return None
-
-
 def spec_refusal(model):
     """Why `model` (a FullSubNet) cannot stream spectra, or None: refusal(), and the cIRM epilogue's output_size.  No GPU is touched."""
     why = refusal(model)
@@ -68,6 +56,17 @@ def spec_refusal(model):
         return why
     if model.output_size != 2:
         return f"the cIRM epilogue needs output_size = 2 (this model: {model.output_size})"
+    return None
+
+
+def wave_refusal(model):
+    """Why `model` (a FullSubNet) cannot stream waveforms, or None: spec_refusal(), and the hop enhance_wave demands.  No GPU is touched."""
+    why = spec_refusal(model)
+    if why is not None:
+        return why
+    hop = model.num_freqs - 1
+    if model.num_freqs < 3 or hop & (hop - 1):
+        return "num_freqs - 1 must be a power of two (n_fft = 2 (num_freqs - 1))"
     return None
 
 
@@ -85,6 +84,11 @@ class _Session:
     _prefix = _opener = None         # "fsnp_stream" / "fsnp_wave_stream" / "fsnp_spec_stream"; the FullSubNet method that opens one, for messages
 
     def __init__(self, model, slots, limit, device, live):
+        # A model dropped through a reference cycle (a kept traceback is enough) keeps its handle until a cyclic collection finds it,
+        # and destroying a handle waits for the device (hipFree).  Opening a session allocates and waits anyway, so the young
+        # generations are collected here - what the interpreter does by itself every few hundred allocations, never the whole heap -
+        # and no such finaliser is left to run inside one of this session's pushes, which never wait.
+        gc.collect(1)
         self.model, self.slots, self.device, self.look_ahead = model, int(slots), device, model.look_ahead
         lib = self._lib = model._ensure_handle(device)
         self._owner = model._hip.handle.value
@@ -195,7 +199,26 @@ class _Session:
             _lib.check(self._set_state(st, int(slot), t.data_ptr(), self._cuda_stream()), f"{self._prefix}_set_state")
 
 
-class Stream(_Session):
+class _FrameSession(_Session):
+    """What the two sessions fed in frames share (Stream, SpecStream: both have max_chunk and num_freqs)."""
+
+    def _tail(self, slots, dtype, lead_in, lead_out):
+        """push() of look_ahead all-zero frames lead_in + (look_ahead,) into `slots` (None: all); lead_out + (0,) for look_ahead = 0"""
+        la = self.look_ahead
+        if la == 0:
+            return torch.zeros(lead_out + (0,), dtype=dtype, device=self.device)
+        if la > self.max_chunk:
+            raise ValueError(f"tail: look_ahead {la} > max_chunk {self.max_chunk}")
+        zeros = torch.zeros(lead_in + (la,), dtype=dtype, device=self.device)
+        counts = None if slots is None else [la if b in set(int(v) for v in slots) else 0 for b in range(self.slots)]
+        return self.push(zeros, counts)
+
+    def frames(self, slot):
+        """Frames pushed into `slot` since its last reset (host-side count; after load_state the first call waits for that copy)."""
+        return self._counter("frames", slot)
+
+
+class Stream(_FrameSession):
     """`slots` independent live streams on one FullSubNet.  Open one through FullSubNet.open_stream, which refuses a model that cannot be
     streamed before any GPU is touched.  Everything runs on the current CUDA stream; a push
     allocates nothing but its output tensor and never synchronises (under the model's error_check="sync" it then waits and polls, as
@@ -235,18 +258,7 @@ class Stream(_Session):
     def tail(self, slots=None):
         """Push look_ahead all-zero frames (the reference's own pad) into `slots` (None: all): the masks of the last look_ahead frames.
         -> [slots, 2, F, look_ahead] (an empty tensor for look_ahead = 0)."""
-        la = self.look_ahead
-        if la == 0:
-            return torch.zeros((self.slots, 2, self.num_freqs, 0), dtype=torch.float32, device=self.device)
-        if la > self.max_chunk:
-            raise ValueError(f"tail: look_ahead {la} > max_chunk {self.max_chunk}")
-        zeros = torch.zeros((self.slots, 1, self.num_freqs, la), dtype=torch.float32, device=self.device)
-        counts = None if slots is None else [la if b in set(int(v) for v in slots) else 0 for b in range(self.slots)]
-        return self.push(zeros, counts)
-
-    def frames(self, slot):
-        """Frames pushed into `slot` since its last reset (host-side count; after load_state the first call waits for that copy)."""
-        return self._counter("frames", slot)
+        return self._tail(slots, torch.float32, (self.slots, 1, self.num_freqs), (self.slots, 2, self.num_freqs))
 
 
 class WaveStream(_Session):
@@ -255,7 +267,8 @@ class WaveStream(_Session):
     enhanced samples out, `delay` = (2 + look_ahead) * hop samples late.  All push outputs of a clip followed by its finish() output,
     without the first `delay` samples, are enhance_wave() of that clip alone, whatever the block sizes.  Everything runs on the current
     CUDA stream; a push allocates nothing but its output tensor and never synchronises (under the model's error_check="sync" it then
-    waits and polls, as forward does)."""
+    waits and polls, as forward does).  load_state takes what state() of a slot of any wave session of a model of the same sizes
+    returned and is a migration call here: it waits once for the copy, to learn the slot's sample count."""
     _prefix, _opener = "fsnp_wave_stream", "open_wave_stream"
 
     def __init__(self, model, slots, max_samples, device, live=False):
@@ -300,17 +313,12 @@ class WaveStream(_Session):
                 return self._lib.fsnp_wave_stream_finish(st, arr, num, out.data_ptr(), self.delay, self._cuda_stream())
         return self._guarded(enqueue, out, "fsnp_wave_stream_finish")
 
-    def load_state(self, slot, tensor):
-        """Load what state() of a slot of any wave session of a model of the same sizes returned.  A migration call: it waits once for the
-        copy, to learn the slot's sample count."""
-        super().load_state(slot, tensor)
-
     def samples(self, slot):
         """Samples pushed into `slot` since its last reset or finish (host-side count)."""
         return self._counter("samples", slot)
 
 
-class SpecStream(_Session):
+class SpecStream(_FrameSession):
     """`slots` independent live streams on one FullSubNet for a caller who owns the STFT (open one through FullSubNet.open_spec_stream,
     which refuses a model that cannot be streamed before any GPU is touched): noisy complex64 frames in, as many enhanced frames out,
     look_ahead frames late.  The noisy frames wait for their masks inside the slot's state, so state() / load_state move a call whole.
@@ -358,15 +366,4 @@ class SpecStream(_Session):
     def tail(self, slots=None):
         """Push look_ahead all-zero frames (the reference's own pad) into `slots` (None: all): the last look_ahead enhanced frames.
         -> [slots, F, look_ahead] (an empty tensor for look_ahead = 0)."""
-        la = self.look_ahead
-        if la == 0:
-            return torch.zeros((self.slots, self.num_freqs, 0), dtype=torch.complex64, device=self.device)
-        if la > self.max_chunk:
-            raise ValueError(f"tail: look_ahead {la} > max_chunk {self.max_chunk}")
-        zeros = torch.zeros((self.slots, self.num_freqs, la), dtype=torch.complex64, device=self.device)
-        counts = None if slots is None else [la if b in set(int(v) for v in slots) else 0 for b in range(self.slots)]
-        return self.push(zeros, counts)
-
-    def frames(self, slot):
-        """Frames pushed into `slot` since its last reset (host-side count; after load_state the first call waits for that copy)."""
-        return self._counter("frames", slot)
+        return self._tail(slots, torch.complex64, (self.slots, self.num_freqs), (self.slots, self.num_freqs))

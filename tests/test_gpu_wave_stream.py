@@ -100,6 +100,30 @@ def test_chunking_invariance_against_the_oracle(norm_type, look_ahead):
         _check(f"{norm_type} look_ahead={look_ahead} {nm}", torch.cat([got[b], fin[b]]), want, D)
 
 
+@pytest.mark.parametrize("live", [False, True])
+@pytest.mark.parametrize("look_ahead", [1, 4])
+def test_ring_shorter_equal_and_longer_than_a_push(look_ahead, live):
+    """The wave counterpart of the spectrum sessions' test of this name.  One clip of 8 hop + 33 samples in three slots of a session of
+    6 frames per push: pushes of hop (none, two, then one frame per push: the ring is longer than a push at look_ahead 4, as long at 1),
+    of 4 hop (as long at 4, shorter at 1) and of 5 hop + 3, whose first push holds steps without a frame and steps with one in the same
+    call (the first frame row the overlap-add reads is row look_ahead: j0 = 1 with 4 enhanced frames, j0 = 4 with 1).  Idle pushes in
+    between, then finish()."""
+    args, L = _args("cumulative_layer_norm", look_ahead=look_ahead), 8 * HOP + 33
+    sd = make_state_dict_fullsubnet(38, "default")
+    clip = wave_clip(L, 2701)
+    want = _oracle(sd, clip, args)
+    sizes = [HOP, 4 * HOP, 5 * HOP + 3]
+    m = _model(args, sd)
+    with m.open_wave_stream(3, max_samples=5 * HOP + 3, live=live) as ws:
+        D = ws.delay
+        assert D == (2 + look_ahead) * HOP and ws.live == live
+        got = _push_all(ws, [clip] * 3, [schedule(L, c) for c in sizes])
+        fin = ws.finish().cpu()
+        m.check_errors()
+    for b in range(3):
+        _check(f"look_ahead {look_ahead}, live {live}, pushes of {sizes[b]}", torch.cat([got[b], fin[b]]), want, D)
+
+
 # ------------------------------------------------------------------------------------------------ both ends of the clip
 def test_clip_ends():
     """One slot per length around the frame grid (the shortest clip a whole-clip call takes, exact multiples of hop, one sample either side);
