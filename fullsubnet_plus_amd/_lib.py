@@ -98,6 +98,10 @@ SYMBOLS = {
     "fsnp_debug_lstm_fbv_pack": (c_i32, [c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64]),
     "fsnp_debug_box_probe": (c_i32, [ctypes.c_double, ctypes.POINTER(ctypes.c_double * BOX_PROBE_VALUES), c_vp]),
     "fsnp_debug_launch_clock": (c_i32, [c_vp, ctypes.POINTER(ctypes.c_double * 7)]),
+    "fsnp_debug_weight_blob": (c_i32, [c_vp, c_vp, c_i64, ctypes.POINTER(c_i64)]),
+    "fsnp_debug_weight_blob_ptr": (c_vp, [c_vp]),
+    "fsnp_debug_commit_stats": (c_i32, [c_vp, ctypes.POINTER(c_i64 * 4)]),
+    "fsnp_debug_pack_emulate": (c_i32, [c_i32, ctypes.POINTER(c_i32), c_i32, ctypes.POINTER(c_vp), ctypes.POINTER(c_i64), c_i32, c_vp, c_i64]),
     "fsnp_last_error": (ctypes.c_char_p, []),
     "fsnp_version": (ctypes.c_char_p, []),
 }
@@ -158,6 +162,12 @@ SPEC_STREAM_SYMBOLS = {
     "fsnp_spec_stream_frames": (c_i32, [c_vp, c_i32, ctypes.POINTER(c_i64)]),
 }
 
+# every symbol include/fsnp_device_weights.h declares (weights handed over in device memory, packed on the GPU; same ABI version)
+DEVICE_WEIGHTS_SYMBOLS = {
+    "fsnp_set_weight_device": (c_i32, [c_vp, ctypes.c_char_p, c_vp, c_i64, c_vp]),
+    "fsnp_commit_weights_on": (c_i32, [c_vp, c_vp]),
+}
+
 ABI_VERSION = 13         # FSNP_ABI_VERSION of the include/fsnp.h these signatures were written against
 
 _lib = None
@@ -180,7 +190,7 @@ def load(build_if_missing=True):
         raise RuntimeError(f"{path} is missing: run `python -m fullsubnet_plus_amd._build`")
     lib = ctypes.CDLL(path)
     for name, (res, args) in (list(SYMBOLS.items()) + list(LENGTHS_SYMBOLS.items()) + list(STREAM_SYMBOLS.items()) + list(WAVE_STREAM_SYMBOLS.items())
-                              + list(LIVE_STREAM_SYMBOLS.items()) + list(SPEC_STREAM_SYMBOLS.items())):
+                              + list(LIVE_STREAM_SYMBOLS.items()) + list(SPEC_STREAM_SYMBOLS.items()) + list(DEVICE_WEIGHTS_SYMBOLS.items())):
         fn = getattr(lib, name)          # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

@@ -730,6 +730,9 @@ void fsnp_destroy(fsnp_handle* h) {
     if (h->ev_done) (void)hipEventDestroy(h->ev_done);
     if (h->d_stft) (void)hipFree(h->d_stft);
     if (h->d_weights) (void)hipFree(h->d_weights);
+    if (h->d_arena) (void)hipFree(h->d_arena);
+    if (h->ev_packed) (void)hipEventDestroy(h->ev_packed);
+    if (h->ev_arena) (void)hipEventDestroy(h->ev_arena);
     drop_weight_watch(h);
     if (h->verify_out) (void)hipFree(h->verify_out);
     if (h->verify_key) (void)hipFree(h->verify_key);
@@ -1139,6 +1142,7 @@ int fsnp_channel_attention(fsnp_handle* h, int32_t branch, const float* in, cons
     }
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     FSNP_ON_DEVICE(h);
+    if (order_after_weight_pack(h, s)) return 4;     // (the stage reads the blob: a device pack on another stream must have finished)
     const Dims d = stage_dims(h, batch, frames);
     const size_t plane = align_up((size_t)d.B * d.Tp * d.FP * 4, 256), md_b = align_up((size_t)d.B * d.Tp * sizeof(NormMD), 256);
     const size_t fsum_b = align_up((size_t)d.B * d.FP * 8, 256), tot_b = align_up((size_t)d.B * 2 * 8, 256), gate_b = align_up((size_t)d.B * d.FP * 4, 256);
@@ -1168,6 +1172,7 @@ int fsnp_fullband_model(fsnp_handle* h, int32_t branch, const float* in, const i
     if (const int rc = stage_args_ok("fsnp_fullband_model", h, branch, in, strides, out, batch, frames)) return rc;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     FSNP_ON_DEVICE(h);
+    if (order_after_weight_pack(h, s)) return 4;     // (the stage reads the blob: a device pack on another stream must have finished)
     const Dims d = stage_dims(h, batch, frames);
     const TcnWeights& t = h->tw;
     const size_t plane = align_up((size_t)d.B * d.Tp * d.FP * 4, 256), yplane = align_up((size_t)d.B * d.Tp * d.CH * 4, 256);

@@ -377,21 +377,11 @@ void launch_lstm_stream(const LstmWeights& w, const LstmArgs& a, hipStream_t s);
 bool lstm_stream_available(const LstmWeights& w);
 // lstm16.hip: the same decomposition on 16-row tiles (v_mfma_f32_16x16x4_f32): 4096 sequences per round of 256 workgroups
 void launch_lstm16(const LstmWeights& w, const LstmArgs& a, hipStream_t s);
-size_t lstm16_pack_floats(int H, int KX);
-size_t lstm16_pack_floats_bf16ih(int H, int KX);
-void lstm16_pack_weights_bf16ih(int H, int NIN, int KX, const float* wih0, const float* whh0, const float* wih1, const float* whh1, float* wpack);
-void lstm16_pack_weights(int H, int NIN, int KX, const float* wih0, const float* whh0, const float* wih1, const float* whh1, float* wpack);
 // lstm_gru.hip: the same decomposition for nn.GRU (three live gate tiles per k-group, no VALU rows)
 void launch_gru(const LstmWeights& w, const LstmArgs& a, hipStream_t s);
-size_t gru_pack_floats(int H, int KX, int NW);
-void gru_pack_weights(int H, int NIN, int KX, int NW, const float* wih0, const float* whh0, const float* wih1,
-                      const float* whh1, float* wpack);   // inputs: the four-slot [4H][cols] matrices (r, z, n_x | n_h)
 // lstm_coop.hip: column-split kernel for small batches (row_tiles * H/32 workgroups, all co-resident)
 void launch_lstm_coop(const LstmWeights& w, const LstmArgs& a, hipStream_t s);       // H = 384, KX = 40, Linear(H, 2) fused
 void launch_lstm_coop_seq(const LstmWeights& w, const LstmArgs& a, hipStream_t s);   // H = 512, KX = 264, h1 sequence out
-size_t lstm_coop_pack_floats(int H, int KX, int units);
-void lstm_coop_pack_weights(int H, int NIN, int KX, int units, const float* wih0, const float* whh0, const float* wih1,
-                            const float* whh1, float* wpack);
 size_t lstm_coop_exchange_bytes(int H, int row_tiles);
 // lstm_hp.hip: 16 units per workgroup (S = H / 16 workgroups per row tile, one XCD), waves split the gates, weights resident,
 // every row tile worked on as two half tiles of 16 sequences in turn (the hand-off of one half hidden behind the other)
@@ -401,28 +391,18 @@ bool lstm_hp_available(const LstmWeights& w);
 // lane-local cells), operands streamed L2 -> registers, no workgroup barrier in the time loop
 void launch_lstm_hpw(const LstmWeights& w, const LstmArgs& a, hipStream_t s);
 bool lstm_hpw_available(const LstmWeights& w);
-size_t lstm_hpw_pack_floats(int H, int KX);
-void lstm_hpw_pack_weights(int H, int NIN, int KX, const float* wih0, const float* whh0, const float* wih1, const float* whh1, float* out);
-size_t lstm_hp_pack_floats(int H, int KX);
-void lstm_hp_pack_weights(int H, int NIN, int KX, const float* wih0, const float* whh0, const float* wih1, const float* whh1, float* out);
 // lstm_coopw.hip: a wave owns 8 NT hidden units over the full K, S = H / (32 NT) workgroups per row tile (a.coop_units = 32 NT in
 // {32, 64}), layer-skewed schedule without workgroup barriers: 11 ... 42 row tiles per launch (B = 2 ... 8)
 void launch_lstm_coopw(const LstmWeights& w, const LstmArgs& a, hipStream_t s);
 bool lstm_coopw_available(const LstmWeights& w, int units);
 int lstm_coopw_occupancy(const LstmWeights& w, int units);
-size_t lstm_coopw_pack_floats(int H, int KX);
-void lstm_coopw_pack_weights(int H, int NIN, int KX, const float* wih0, const float* whh0, const float* wih1, const float* whh1, float* out);
 // lstm_fbv.hip: the full-band LSTM(num_freqs -> 512 x 2) of the original FullSubNet for 1 ... 4 utterances as matrix-VECTOR products
 // on the VALU (weights resident, H / 8 workgroups, serial schedule with one hand-off per step); h1 sequence out
 void launch_lstm_fbv(const LstmWeights& w, const LstmArgs& a, hipStream_t s);
 bool lstm_fbv_available(const LstmWeights& w, int batch, int num_cus);
-size_t lstm_fbv_pack_floats(int H);
-void lstm_fbv_pack_weights(int H, int NIN, const float* wih0, const float* whh0, const float* wih1, const float* whh1, float* out);
 // lstm_generic.hip: runtime-sized fp32-FMA kernel for the sizes no tuned kernel is instantiated for (any hidden size / input width);
 // a.num_tiles workgroups of a.coop_rows_per_group (1, 2, 4, 8) sequences; seq = the full-band model of the original FullSubNet
 void launch_lstm_generic(const LstmWeights& w, const LstmArgs& a, bool seq, hipStream_t s);
-size_t lstm_generic_pack_floats(int H, int NIN);
-void lstm_generic_pack_weights(int H, int NIN, const float* wih0, const float* whh0, const float* wih1, const float* whh1, float* out);
 // streaming: the seq kernel from the rows' carried state (a.st_fb), rows[].valid steps per row; commit-time check as lstm_generic_check
 void launch_lstm_generic_stream(const LstmWeights& w, const LstmArgs& a, hipStream_t s);
 int lstm_generic_stream_check(int H, int NIN);
@@ -458,22 +438,13 @@ void launch_live_sb_out(const LstmWeights& w, const LiveSbArgs& a, hipStream_t s
 void launch_live_fb_step(const LstmWeights& w, const LiveFbArgs& a, int layer, hipStream_t s);
 // lstm_coopn.hip: 3 workgroups x 128 hidden units share 1-2 row tiles (43..170 row tiles)
 void launch_lstm_coopn(const LstmWeights& w, const LstmArgs& a, hipStream_t s);
-size_t lstm_coopn_pack_floats(int H, int KX);
-void lstm_coopn_pack_weights(int H, int NIN, int KX, const float* wih0, const float* whh0, const float* wih1,
-                             const float* whh1, float* wpack);
 int lstm_coopn_plan(int H, int row_tiles, int num_cus, int* groups);   // rows tiles per group (0 = not applicable)
 int lstm_coop_pick_units(int H, int row_tiles, int num_cus, int min_units);   // 0 = not applicable
 // workgroups of one instantiation that fit a CU at once (hipOccupancyMaxActiveBlocksPerMultiprocessor; 0 = unknown)
 int lstm_coop_occupancy(const LstmWeights& w, int units);
 int lstm_coop_seq_occupancy(const LstmWeights& w, int units);     // the same for launch_lstm_coop_seq (full-band model, H = 512)
 int lstm_coopn_occupancy(const LstmWeights& w, int rows_per_group);
-size_t lstm_pack_floats(int H, int KX, int NW);  // size of wpack in floats
-// host-side packer: W_ih0 [4H][NIN], W_hh0 [4H][H], W_ih1 [4H][H], W_hh1 [4H][H] -> wpack
-size_t lstm_pack_floats_bf16ih(int H, int KX, int NW);
-void lstm_pack_weights_bf16ih(int H, int NIN, int KX, int NW, const float* wih0, const float* whh0, const float* wih1,
-                              const float* whh1, const float* bias0, float* wpack);
-void lstm_pack_weights(int H, int NIN, int KX, int NW, const float* wih0, const float* whh0, const float* wih1,
-                       const float* whh1, float* wpack);
+// (the weight images of all these kernels - sizes, layouts, host and device packers - are stated in weight_layouts.h)
 
 // ---------------------------------------------------------------------------------------------
 void set_error(const char* fmt, ...);

@@ -8,6 +8,7 @@
 #include "lstm_common.h"
 #include "planner.h"
 #include "fsnp_handle.h"
+#include "weight_layouts.h"
 
 static double lstm_flops_per_step(const fsnp_handle* h) {
     if (h->sb_tcn) return 8 * (2.0 * h->NIN * h->CH + 2.0 * h->CH * 3 + 2.0 * h->CH * h->NIN) + 2.0 * h->NIN * h->cfg.output_size;
@@ -352,11 +353,11 @@ int fsnp_debug_lstm_pack(int32_t hidden, int32_t input_size, int32_t kx, int32_t
                          const float* wih1, const float* whh1, float* out, int64_t out_floats) {
     if (!wih0 || !whh0 || !wih1 || !whh1 || !out) { set_error("fsnp_debug_lstm_pack: null argument"); return 1; }
     if (waves <= 0 || hidden % (32 * waves) != 0 || kx % 8 != 0 || input_size > kx) { set_error("fsnp_debug_lstm_pack: bad sizes"); return 2; }
-    if ((int64_t)lstm_pack_floats(hidden, kx, waves) != out_floats) {
-        set_error("fsnp_debug_lstm_pack: need %lld floats", (long long)lstm_pack_floats(hidden, kx, waves));
+    if (rnn_image_floats(PK_ROWTILE, hidden, input_size, kx, waves) != out_floats) {
+        set_error("fsnp_debug_lstm_pack: need %lld floats", (long long)rnn_image_floats(PK_ROWTILE, hidden, input_size, kx, waves));
         return 2;
     }
-    lstm_pack_weights(hidden, input_size, kx, waves, wih0, whh0, wih1, whh1, out);
+    pack_rnn_host(PK_ROWTILE, hidden, input_size, kx, waves, wih0, whh0, wih1, whh1, out);
     return 0;
 }
 
@@ -367,11 +368,11 @@ int fsnp_debug_lstm_coop_pack(int32_t hidden, int32_t input_size, int32_t kx, in
         set_error("fsnp_debug_lstm_coop_pack: bad sizes");
         return 2;
     }
-    if ((int64_t)lstm_coop_pack_floats(hidden, kx, units) != out_floats) {
-        set_error("fsnp_debug_lstm_coop_pack: need %lld floats", (long long)lstm_coop_pack_floats(hidden, kx, units));
+    if (rnn_image_floats(PK_KSPLIT, hidden, input_size, kx, units) != out_floats) {
+        set_error("fsnp_debug_lstm_coop_pack: need %lld floats", (long long)rnn_image_floats(PK_KSPLIT, hidden, input_size, kx, units));
         return 2;
     }
-    lstm_coop_pack_weights(hidden, input_size, kx, units, wih0, whh0, wih1, whh1, out);
+    pack_rnn_host(PK_KSPLIT, hidden, input_size, kx, units, wih0, whh0, wih1, whh1, out);
     return 0;
 }
 
@@ -379,11 +380,11 @@ int fsnp_debug_lstm_hpw_pack(int32_t hidden, int32_t input_size, int32_t kx, con
                              const float* whh1, float* out, int64_t out_floats) {
     if (!wih0 || !whh0 || !wih1 || !whh1 || !out) { set_error("fsnp_debug_lstm_hpw_pack: null argument"); return 1; }
     if (hidden % 16 != 0 || kx % 4 != 0 || kx > 64 || input_size > kx) { set_error("fsnp_debug_lstm_hpw_pack: bad sizes"); return 2; }
-    if (out_floats != (int64_t)lstm_hpw_pack_floats(hidden, kx)) {
-        set_error("fsnp_debug_lstm_hpw_pack: need %lld floats", (long long)lstm_hpw_pack_floats(hidden, kx));
+    if (out_floats != rnn_image_floats(PK_HPW, hidden, input_size, kx, 0)) {
+        set_error("fsnp_debug_lstm_hpw_pack: need %lld floats", (long long)rnn_image_floats(PK_HPW, hidden, input_size, kx, 0));
         return 2;
     }
-    lstm_hpw_pack_weights(hidden, input_size, kx, wih0, whh0, wih1, whh1, out);
+    pack_rnn_host(PK_HPW, hidden, input_size, kx, 0, wih0, whh0, wih1, whh1, out);
     return 0;
 }
 
@@ -391,11 +392,11 @@ int fsnp_debug_lstm_coopw_pack(int32_t hidden, int32_t input_size, int32_t kx, c
                                const float* whh1, float* out, int64_t out_floats) {
     if (!wih0 || !whh0 || !wih1 || !whh1 || !out) { set_error("fsnp_debug_lstm_coopw_pack: null argument"); return 1; }
     if (hidden % 32 != 0 || kx % 8 != 0 || input_size > kx) { set_error("fsnp_debug_lstm_coopw_pack: bad sizes"); return 2; }
-    if ((int64_t)lstm_coopw_pack_floats(hidden, kx) != out_floats) {
-        set_error("fsnp_debug_lstm_coopw_pack: need %lld floats", (long long)lstm_coopw_pack_floats(hidden, kx));
+    if (rnn_image_floats(PK_COOPW, hidden, input_size, kx, 0) != out_floats) {
+        set_error("fsnp_debug_lstm_coopw_pack: need %lld floats", (long long)rnn_image_floats(PK_COOPW, hidden, input_size, kx, 0));
         return 2;
     }
-    lstm_coopw_pack_weights(hidden, input_size, kx, wih0, whh0, wih1, whh1, out);
+    pack_rnn_host(PK_COOPW, hidden, input_size, kx, 0, wih0, whh0, wih1, whh1, out);
     return 0;
 }
 
@@ -403,11 +404,11 @@ int fsnp_debug_lstm_fbv_pack(int32_t hidden, int32_t input_size, const float* wi
                              float* out, int64_t out_floats) {
     if (!wih0 || !whh0 || !wih1 || !whh1 || !out) { set_error("fsnp_debug_lstm_fbv_pack: null argument"); return 1; }
     if (hidden != 512 || input_size < 1 || input_size > 288) { set_error("fsnp_debug_lstm_fbv_pack: hidden 512, <= 288 inputs"); return 2; }
-    if ((int64_t)lstm_fbv_pack_floats(hidden) != out_floats) {
-        set_error("fsnp_debug_lstm_fbv_pack: need %lld floats", (long long)lstm_fbv_pack_floats(hidden));
+    if (rnn_image_floats(PK_FBV, hidden, input_size, 0, 0) != out_floats) {
+        set_error("fsnp_debug_lstm_fbv_pack: need %lld floats", (long long)rnn_image_floats(PK_FBV, hidden, input_size, 0, 0));
         return 2;
     }
-    lstm_fbv_pack_weights(hidden, input_size, wih0, whh0, wih1, whh1, out);
+    pack_rnn_host(PK_FBV, hidden, input_size, 0, 0, wih0, whh0, wih1, whh1, out);
     return 0;
 }
 
@@ -421,6 +422,86 @@ double fsnp_forward_flops(const fsnp_handle* h, int32_t batch, int32_t frames, i
     const double Tp = frames + h->cfg.look_ahead;
     const double full_band = h->model == FSNP_MODEL_FULLSUBNET ? fb_lstm_flops_per_frame(h) : 3.0 * tcn_flops_per_frame(h);
     return batch * Tp * (rows_per_utt(h, mode) * lstm_flops_per_step(h) + full_band);
+}
+
+int fsnp_debug_weight_blob(fsnp_handle* h, void* host_dst, int64_t bytes, int64_t* needed) {
+    if (!h) { set_error("fsnp_debug_weight_blob: null handle"); return 1; }
+    if (!h->committed || !h->d_weights) { set_error("fsnp_debug_weight_blob: weights not committed"); return 2; }
+    const int64_t need = (int64_t)(h->blob_floats * sizeof(float));
+    if (needed) *needed = need;
+    if (!host_dst) return 0;                      // (a size query)
+    if (bytes < need) { set_error("fsnp_debug_weight_blob: need %lld bytes", (long long)need); return 2; }
+    FSNP_ON_DEVICE(h);
+    FSNP_HIP_CHECK(hipDeviceSynchronize());
+    FSNP_HIP_CHECK(hipMemcpy(host_dst, h->d_weights, (size_t)need, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+const void* fsnp_debug_weight_blob_ptr(const fsnp_handle* h) { return h ? h->d_weights : nullptr; }
+
+int fsnp_debug_commit_stats(const fsnp_handle* h, int64_t out[4]) {
+    if (!h || !out) { set_error("fsnp_debug_commit_stats: null argument"); return 1; }
+    for (int i = 0; i < 4; ++i) out[i] = h->commit_stats[i];
+    return 0;
+}
+
+int fsnp_debug_pack_emulate(int32_t kind, const int32_t* sizes, int32_t num_sizes, const float* const* sources, const int64_t* numels,
+                            int32_t num_sources, float* out, int64_t out_floats) {
+    if (!sizes || !sources || !numels || !out) { set_error("fsnp_debug_pack_emulate: null argument"); return 1; }
+    if (kind < 0 || kind >= PK_COUNT || num_sizes < 1 || num_sizes > 5) { set_error("fsnp_debug_pack_emulate: unknown kind / size count"); return 2; }
+    int p[5] = {0, 0, 0, 0, 0};
+    for (int i = 0; i < num_sizes; ++i) {
+        if (sizes[i] < 0) { set_error("fsnp_debug_pack_emulate: negative size"); return 2; }
+        p[i] = sizes[i];
+    }
+    const bool rnn = kind <= PK_SPREAD;
+    const int want_sources = rnn ? 8 : kind == PK_FOLDW ? 2 : kind == PK_FOLDC ? 4 : 1;
+    // the divisions of the layouts: a recurrent image is cut into whole fragments
+    bool ok = p[0] > 0 && num_sources == want_sources;
+    if (rnn && kind != PK_BIAS) ok = ok && p[1] > 0;
+    if (kind <= PK_FBV) ok = ok && p[0] % 8 == 0;
+    if (kind == PK_ROWTILE || kind == PK_ROWTILE_BF || kind == PK_GRU) ok = ok && p[3] > 0 && p[0] % (32 * p[3]) == 0 && p[2] % 8 == 0 && p[1] <= p[2];
+    if (kind == PK_ROWTILE_BF) ok = ok && p[1] < p[2] && p[0] % 16 == 0;
+    if (kind == PK_HALF || kind == PK_HALF_BF) ok = ok && p[0] % 64 == 0 && p[1] <= p[2];
+    if (kind == PK_KSPLIT) ok = ok && p[3] >= 8 && p[3] % 8 == 0 && p[0] % p[3] == 0 && p[0] % 16 == 0 && (4 * p[3]) % 32 == 0 && p[2] % 8 == 0 && p[1] <= p[2] && (coop_kgxp(p[2]) + p[0] / 8) % 4 == 0;
+    if (kind == PK_COOPN || kind == PK_COOPW) ok = ok && p[0] % 32 == 0 && p[2] % 8 == 0 && p[1] <= p[2];
+    if (kind == PK_HP || kind == PK_HPW) ok = ok && p[0] % 16 == 0 && p[1] <= 16 * gx16(p[2]);
+    if (kind == PK_FBV) ok = ok && p[0] == 512 && p[1] <= kFbvXP;
+    if (kind == PK_SPREAD) ok = ok && p[3] < 4;
+    if (kind == PK_PADMAT || kind == PK_FOLDW) ok = ok && p[1] > 0 && p[0] <= p[2] && p[1] <= p[3];
+    if (kind == PK_TRANSPOSE) ok = ok && p[1] > 0;
+    if (kind == PK_FOLDC) ok = ok && p[1] > 0 && p[0] <= p[2] && p[3] <= 1;
+    if (!ok) { set_error("fsnp_debug_pack_emulate: bad sizes / source count for kind %d", kind); return 2; }
+    PackJob J = make_job(kind, p[0], p[1], p[2], p[3], p[4]);
+    if (J.n != out_floats) { set_error("fsnp_debug_pack_emulate: need %lld floats", (long long)J.n); return 2; }
+    std::vector<float> arena;
+    for (int i = 0; i < num_sources; ++i) {
+        if (numels[i] < 0 || (numels[i] > 0 && !sources[i])) { set_error("fsnp_debug_pack_emulate: source %d is null / negative", i); return 1; }
+        J.s[i] = (long long)arena.size();
+        arena.insert(arena.end(), sources[i], sources[i] + numels[i]);
+    }
+    // every source offset the layout names lies inside its tensor
+    auto inside = [&](int a, long long i) { return a < num_sources && i >= 0 && i < numels[a]; };
+    if (kind == PK_FOLDC) {
+        if (numels[0] < (int64_t)p[0] * p[1] || numels[1] < p[1] || numels[2] < p[1] || numels[3] < p[0]) {
+            set_error("fsnp_debug_pack_emulate: a source of the fold is too small"); return 2;
+        }
+    } else {
+        for (long long u = 0; 4 * u < J.n; ++u) {
+            const int nj = pack_unit_bf16(J, u) ? 8 : 4;
+            for (int j = 0; j < nj; ++j) {
+                long long shift;
+                const PackRef r = pack_ref(J, u, j, &shift);
+                if (r.a < 0) continue;
+                if (!inside(r.a, shift + r.ia) || (r.op != OP_ONE && !inside(r.b, shift + r.ib))) {
+                    set_error("fsnp_debug_pack_emulate: kind %d, unit %lld: source offset outside its tensor", kind, u);
+                    return 3;
+                }
+            }
+        }
+    }
+    pack_image_host(J, arena.data(), out, J.n);
+    return 0;
 }
 
 }  // extern "C"

@@ -53,10 +53,27 @@ struct fsnp_handle {
     int device = 0;
     int F = 0, FP = 0, CH = 0, H = 0, NSB = 0, NIN = 0, KX = 0, NB = 0, Fr = 0;
     std::vector<WeightSpec> specs;
-    std::map<std::string, std::vector<float>> host_w;
+    // the parameters as the caller gave them, back to back in specs order: a host copy (fsnp_set_weight) and a device copy
+    // (fsnp_set_weight_device; one allocation, made on first use).  spec_src[i]: 0 = never given, 1 = the host copy is the newest,
+    // 2 = the device copy is, 3 = both hold it (a device-given tensor that a host-path commit downloaded)
+    std::vector<float> host_arena;
+    std::vector<long long> spec_off;         // float offset of spec i in either arena
+    std::vector<unsigned char> spec_src;
+    std::map<std::string, int> spec_index;
+    long long arena_floats = 0;
+    float* d_arena = nullptr;
+    hipEvent_t ev_arena = nullptr;           // recorded behind every arena copy on its own stream: a copy or a pack on another stream waits for it
+    hipStream_t arena_stream = nullptr;
+    bool arena_valid = false;
     bool committed = false;
 
     float* d_weights = nullptr;
+    size_t blob_floats = 0;                  // size of d_weights (depends on the configuration only)
+    std::vector<float> refl_host;            // device commit: the unfold multiplicities, uploaded from here (kept alive for the copy)
+    int64_t commit_stats[4] = {0, 0, 0, 0};  // fsnp_debug_commit_stats: path, bytes host -> device, bytes device -> host, pack kernels
+    hipEvent_t ev_packed = nullptr;          // end of the last device pack: stream-session pushes on another stream wait for it
+    hipStream_t packed_stream = nullptr;
+    bool packed_valid = false;
     FrontendWeights fw{};
     TcnWeights tw{};
     LstmWeights lw{};
@@ -173,6 +190,10 @@ void build_specs(fsnp_handle* h);
 // cross-stream ordering of a handle's shared buffers (fsnp_abi.hip)
 int order_after_last_forward(fsnp_handle* h, hipStream_t s);
 int mark_forward_done(fsnp_handle* h, hipStream_t s);
+// fsnp_weights.hip: orders `s` behind a device pack of the weights (fsnp_commit_weights_on) that ran on ANOTHER stream - for the
+// entry points that read the blob without going through order_after_last_forward (stream-session pushes, the stage calls
+// fsnp_channel_attention / fsnp_fullband_model)
+int order_after_weight_pack(fsnp_handle* h, hipStream_t s);
 // clips of different lengths: 0 when lengths[0 .. batch) (host, frames per utterance) is acceptable for a forward of `frames` frames on
 // this handle, else 2 with the error set (naming the utterance).  Nothing is launched.
 int check_lengths(const fsnp_handle* h, const int32_t* lengths, int batch, int frames, const char* where);

@@ -157,6 +157,7 @@ int stream_push_body(fsnp_stream* st, const float* mag, const int64_t strides[3]
     for (int b = 0; b < S; ++b) { nact += c.v[b] > 0; nmax = std::max(nmax, c.v[b]); }
     FSNP_ON_DEVICE(h);
     st->last_stream = s;
+    if (order_after_weight_pack(h, s)) return 4;      // (a device pack of the weights on another stream: fsnp_commit_weights_on)
     RowDesc* rows = st->at<RowDesc>(st->w_rows);
     StreamMeta* meta = st->at<StreamMeta>(st->w_meta);
     int* cnt = st->at<int>(st->w_cnt);

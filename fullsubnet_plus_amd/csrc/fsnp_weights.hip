@@ -1,6 +1,7 @@
 // fsnp_weights.hip - strict weight loading of the C ABI: the parameter tree a handle expects (reference names / shapes,
 // base_inferencer.py:100-107 loads with strict=True) and its packing into the device layouts of the kernels (MFMA fragment order,
-// transposed / zero-padded GEMM operands, GroupNorm folded into the sconv weights, summed biases).  Host code only.
+// transposed / zero-padded GEMM operands, GroupNorm folded into the sconv weights, summed biases) - on the host, or on the device
+// from tensors the caller handed over there (include/fsnp_device_weights.h; the layouts: weight_layouts.h, the kernels: weight_pack.hip).
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -8,6 +9,7 @@
 #include <vector>
 
 #include "fsnp_handle.h"
+#include "weight_layouts.h"
 #include "weight_watch.h"
 
 namespace fsnp {
@@ -17,7 +19,7 @@ static const char* kAtt[3] = {"channel_attention", "channel_attention_real", "ch
 static const char* kFb[3] = {"fb_model", "fb_model_real", "fb_model_imag"};
 static const char* kConvNames[3] = {"smallConv1d", "middleConv1d", "largeConv1d"};
 
-void build_specs(fsnp_handle* h) {
+static void list_specs(fsnp_handle* h) {
     auto add = [&](const std::string& n, int64_t numel) { h->specs.push_back({n, numel}); };
     const int F = h->F, CH = h->CH, H = h->H, Fr = h->Fr;
     const int att = h->cfg.attention;
@@ -108,6 +110,19 @@ void build_specs(fsnp_handle* h) {
     add("sb_model.fc_output_layer.bias", h->cfg.output_size);
 }
 
+void build_specs(fsnp_handle* h) {
+    list_specs(h);
+    long long at = 0;
+    for (size_t i = 0; i < h->specs.size(); ++i) {
+        h->spec_off.push_back(at);
+        h->spec_index[h->specs[i].name] = (int)i;
+        at += h->specs[i].numel;
+    }
+    h->arena_floats = at;
+    h->spec_src.assign(h->specs.size(), 0);
+    h->host_arena.assign((size_t)at, 0.0f);
+}
+
 // ---- fsnp_watch_weights: a 64-bit fingerprint of the caller's source tensors, taken on the device in front of every forward.
 // sum over all elements of bits(x_i) * (2 i + 1) mod 2^64 (i = position in the concatenation): any single changed element changes
 // it, the sum is order-independent (integer adds), so blocks accumulate with one atomic each and the LAST block to finish compares.
@@ -177,33 +192,70 @@ int fsnp_weight_info(const fsnp_handle* h, int index, const char** name, int64_t
     return 0;
 }
 
-int fsnp_set_weight(fsnp_handle* h, const char* name, const float* host_data, int64_t numel) {
-    if (!h || !name || !host_data) { set_error("fsnp_set_weight: null argument"); return 1; }
-    for (const auto& s : h->specs) {
-        if (s.name == name) {
-            if (s.numel != numel) {
-                set_error("size mismatch for %s: expected %lld elements, got %lld", name, (long long)s.numel, (long long)numel);
-                return 2;
-            }
-            h->host_w[s.name].assign(host_data, host_data + numel);
-            h->committed = false;
-            h->watch_nseg = 0;            // the watched tensors belonged to the previous weight set (fsnp_watch_weights again after the commit)
-            return 0;
-        }
-    }
-    set_error("unexpected key in state_dict: %s", name);
-    return 2;
+}  // extern "C"
+
+namespace fsnp {
+
+int order_after_weight_pack(fsnp_handle* h, hipStream_t s) {
+    if (h->packed_valid && h->packed_stream != s) FSNP_HIP_CHECK(hipStreamWaitEvent(s, h->ev_packed, 0));
+    return 0;
 }
 
-int fsnp_commit_weights(fsnp_handle* h) {
-    if (!h) { set_error("null handle"); return 1; }
-    for (const auto& s : h->specs)
-        if (!h->host_w.count(s.name)) { set_error("missing key in state_dict: %s", s.name.c_str()); return 2; }
+// name / size checks shared by the two setters: the spec's index, or -1 with the error set (code 2)
+static int find_spec(fsnp_handle* h, const char* name, int64_t numel) {
+    const auto it = h->spec_index.find(name);
+    if (it == h->spec_index.end()) { set_error("unexpected key in state_dict: %s", name); return -1; }
+    const WeightSpec& s = h->specs[it->second];
+    if (s.numel != numel) {
+        set_error("size mismatch for %s: expected %lld elements, got %lld", name, (long long)s.numel, (long long)numel);
+        return -1;
+    }
+    return it->second;
+}
+
+// the device-given tensors the host arena does not hold yet -> host arena (a host-path commit of device-given weights)
+static int download_device_given(fsnp_handle* h, int64_t* bytes) {
+    *bytes = 0;
+    bool any = false;
+    for (unsigned char v : h->spec_src) any = any || v == 2;
+    if (!any) return 0;
+    FSNP_ON_DEVICE(h);
+    FSNP_HIP_CHECK(hipDeviceSynchronize());           // (the arena copies run on the caller's streams)
+    for (size_t i = 0; i < h->specs.size(); ++i) {
+        if (h->spec_src[i] != 2) continue;
+        const size_t nb = (size_t)h->specs[i].numel * sizeof(float);
+        FSNP_HIP_CHECK(hipMemcpy(h->host_arena.data() + h->spec_off[i], h->d_arena + h->spec_off[i], nb, hipMemcpyDeviceToHost));
+        h->spec_src[i] = 3;
+        *bytes += (int64_t)nb;
+    }
+    return 0;
+}
+
+// Lays the blob out (the same walk for both paths: offsets and images depend on the configuration only), packs it - on the host from
+// the host arena and uploads it, or on the device from the device arena on stream s - and binds the kernels' pointers into it.
+static int commit_impl(fsnp_handle* h, bool on_device, hipStream_t s) {
     const int F = h->F, CH = h->CH, H = h->H, NB = h->NB, Fr = h->Fr;
-    std::vector<float> blob;
-    auto alloc = [&](size_t n) { size_t o = blob.size(); blob.resize(align_up(o + n, 64), 0.0f); return o; };
-    auto W = [&](const std::string& n) -> const std::vector<float>& { return h->host_w.at(n); };
-    auto put = [&](const std::string& n) { const auto& v = W(n); size_t o = alloc(v.size()); std::copy(v.begin(), v.end(), blob.begin() + o); return o; };
+    std::vector<PackJob> jobs;
+    size_t total = 0;
+    auto alloc = [&](size_t n) { const size_t o = total; total = align_up(o + n, 64); return o; };
+    auto off = [&](const std::string& n) { return h->spec_off[h->spec_index.at(n)]; };
+    auto numel = [&](const std::string& n) { return h->specs[h->spec_index.at(n)].numel; };
+    auto emit = [&](PackJob J, size_t o, size_t n) { J.out = (long long)o; J.n = (long long)n; if (n) jobs.push_back(J); };
+    auto put = [&](const std::string& n) {           // a plain copy
+        const int c = (int)numel(n);
+        const size_t o = alloc(c);
+        PackJob J = make_job(PK_PADMAT, 1, c, 1, c);
+        J.s[0] = off(n);
+        emit(J, o, c);
+        return o;
+    };
+    auto transposed = [&](const std::string& n, int R, int C) {      // [R][C] -> [C][R]
+        const size_t o = alloc((size_t)R * C);
+        PackJob J = make_job(PK_TRANSPOSE, R, C);
+        J.s[0] = off(n);
+        emit(J, o, (size_t)R * C);
+        return o;
+    };
 
     // ---- frontend (TSSE) : reference layouts are already what the kernels want
     size_t o_conv_w[3][3] = {}, o_conv_b[3][3] = {}, o_cat_w[3] = {}, o_cat_b[3] = {}, o_fc1w[3] = {}, o_fc1b[3] = {},
@@ -225,16 +277,8 @@ int fsnp_commit_weights(fsnp_handle* h) {
             o_cat_w[a] = put(p + ".conv.weight");            // the 3 taps of Conv1d(1,1,3) over the channel axis
             continue;
         }
-        {   // transposed copies: fc1 [Fr][F] -> [F][Fr], fc2 [F][Fr] -> [Fr][F]
-            const auto& w1 = W(p + ".fc1.weight");
-            o_fc1w[a] = alloc((size_t)F * Fr);
-            for (int o = 0; o < Fr; ++o)
-                for (int f = 0; f < F; ++f) blob[o_fc1w[a] + (size_t)f * Fr + o] = w1[(size_t)o * F + f];
-            const auto& w2 = W(p + ".fc2.weight");
-            o_fc2w[a] = alloc((size_t)Fr * F);
-            for (int o = 0; o < F; ++o)
-                for (int f = 0; f < Fr; ++f) blob[o_fc2w[a] + (size_t)f * F + o] = w2[(size_t)o * Fr + f];
-        }
+        o_fc1w[a] = transposed(p + ".fc1.weight", Fr, F);    // transposed copies: fc1 [Fr][F] -> [F][Fr], fc2 [F][Fr] -> [Fr][F]
+        o_fc2w[a] = transposed(p + ".fc2.weight", F, Fr);
         o_fc1b[a] = put(p + ".fc1.bias");
         o_fc2b[a] = put(p + ".fc2.bias");
     }
@@ -242,62 +286,59 @@ int fsnp_commit_weights(fsnp_handle* h) {
     // [N pad 384][K pad 16] GEMM operands, [model][block] major.  `cin` channels in / out of every TCNBlock, `fc_out` rows of
     // the final Linear(cin, fc_out).  Used for the three full-band models and for a sub-band TCN.
     struct TcnOff { size_t w1, b1, a1, g1w, g1b, dw, db, a2, g2w, g2b, w2, b2, w2g, c1, c2, wf, bf; int NB, N1P, K1P, N2P, K2P; };
+    bool regular = true;
     auto pack_tcn = [&](const std::vector<std::string>& models, int nb, int cin, int fc_out) {
         TcnOff t{};
         const size_t nm = models.size() ? models.size() : 1;
         t.NB = nb; t.N1P = (int)align_up(CH, 384); t.K1P = (int)align_up(cin, 16); t.N2P = (int)align_up(cin, 384); t.K2P = (int)align_up(CH, 16);
-        t.w1 = alloc(nm * nb * t.N1P * t.K1P); t.b1 = alloc(nm * nb * t.N1P); t.a1 = alloc(nm * nb + 1);
-        t.g1w = alloc(nm * nb * CH); t.g1b = alloc(nm * nb * CH);
-        t.dw = alloc(nm * nb * 3 * CH); t.db = alloc(nm * nb * CH); t.a2 = alloc(nm * nb + 1);
-        t.g2w = alloc(nm * nb * CH); t.g2b = alloc(nm * nb * CH);
-        t.w2 = alloc(nm * nb * t.N2P * t.K2P); t.b2 = alloc(nm * nb * t.N2P);
-        t.w2g = alloc(nm * nb * t.N2P * t.K2P); t.c1 = alloc(nm * nb * t.N2P); t.c2 = alloc(nm * nb * t.N2P);
-        t.wf = alloc(nm * t.N2P * t.K1P); t.bf = alloc(nm * t.N2P);
-        for (size_t b = 0; b < models.size(); ++b) {
-            for (int i = 0; i < nb; ++i) {
-                const std::string p = models[b] + ".sequence_model." + std::to_string(i);
-                const size_t bi = b * nb + i;
-                const auto& w1 = W(p + ".conv1x1.weight");           // [CH][cin][1]
-                for (int n = 0; n < CH; ++n)
-                    for (int k = 0; k < cin; ++k) blob[t.w1 + (bi * t.N1P + n) * t.K1P + k] = w1[(size_t)n * cin + k];
-                std::copy(W(p + ".conv1x1.bias").begin(), W(p + ".conv1x1.bias").end(), blob.begin() + t.b1 + bi * t.N1P);
-                blob[t.a1 + bi] = W(p + ".prelu1.weight")[0];
-                std::copy(W(p + ".norm1.weight").begin(), W(p + ".norm1.weight").end(), blob.begin() + t.g1w + bi * CH);
-                std::copy(W(p + ".norm1.bias").begin(), W(p + ".norm1.bias").end(), blob.begin() + t.g1b + bi * CH);
-                const auto& dw = W(p + ".depthwise_conv.weight");     // [CH][1][3] -> tap major
-                for (int c = 0; c < CH; ++c)
-                    for (int jj = 0; jj < 3; ++jj) blob[t.dw + (bi * 3 + jj) * CH + c] = dw[(size_t)c * 3 + jj];
-                std::copy(W(p + ".depthwise_conv.bias").begin(), W(p + ".depthwise_conv.bias").end(), blob.begin() + t.db + bi * CH);
-                blob[t.a2 + bi] = W(p + ".prelu2.weight")[0];
-                std::copy(W(p + ".norm2.weight").begin(), W(p + ".norm2.weight").end(), blob.begin() + t.g2w + bi * CH);
-                std::copy(W(p + ".norm2.bias").begin(), W(p + ".norm2.bias").end(), blob.begin() + t.g2b + bi * CH);
-                const auto& w2 = W(p + ".sconv.weight");              // [cin][CH][1]
-                for (int n = 0; n < cin; ++n)
-                    for (int k = 0; k < CH; ++k) blob[t.w2 + (bi * t.N2P + n) * t.K2P + k] = w2[(size_t)n * CH + k];
-                std::copy(W(p + ".sconv.bias").begin(), W(p + ".sconv.bias").end(), blob.begin() + t.b2 + bi * t.N2P);
-                // GroupNorm 2 folded into the sconv GEMM (tcn.hip tcn_gemm_dma_kernel): weights times gamma, and the two
-                // per-output constants of  sum_k ((a - m) r g_k + b_k) W[n][k] = r sum_k a g_k W[n][k] + c1[n] - r m c2[n]
-                const auto& g2 = W(p + ".norm2.weight");
-                const auto& be2 = W(p + ".norm2.bias");
-                const auto& sb2 = W(p + ".sconv.bias");
-                for (int n = 0; n < cin; ++n) {
-                    double s1 = sb2[n], s2 = 0.0;
-                    for (int k = 0; k < CH; ++k) {
-                        const double wv = w2[(size_t)n * CH + k];
-                        blob[t.w2g + (bi * t.N2P + n) * t.K2P + k] = (float)(wv * (double)g2[k]);
-                        s1 += (double)be2[k] * wv;
-                        s2 += (double)g2[k] * wv;
+        const int nimg = models.empty() ? 0 : (int)(nm * nb), nfc = models.empty() ? 0 : (int)nm;
+        // one image over all blocks of all models: block (b, i) of tensor `leaf` lies b * stride_out + i * stride_in floats behind
+        // block (0, 0) in the arena, because every block (and every model) holds the same tensors in the same order
+        auto blk = [&](size_t b, int i, const char* leaf) { return off(models[b] + ".sequence_model." + std::to_string(i) + leaf); };
+        auto fc = [&](size_t b, const char* leaf) { return off(models[b] + ".fc_output_layer" + leaf); };
+        auto image = [&](PackJob J, size_t size, std::initializer_list<const char*> leaves, bool per_block) {
+            const size_t o = alloc(size);
+            J.nsub = per_block ? nimg : nfc;
+            J.nb = per_block ? nb : 1;
+            if (J.nsub > 0) {
+                int k = 0;
+                for (const char* leaf : leaves) {
+                    J.s[k] = per_block ? blk(0, 0, leaf) : fc(0, leaf);
+                    if (per_block) {
+                        J.stride_in = nb > 1 ? blk(0, 1, leaf) - J.s[k] : 0;
+                        J.stride_out = nm > 1 ? blk(1, 0, leaf) - J.s[k] : 0;
+                        for (size_t b = 0; b < nm; ++b)
+                            for (int i = 0; i < nb; ++i) regular = regular && blk(b, i, leaf) == J.s[k] + (long long)b * J.stride_out + i * J.stride_in;
+                    } else {
+                        J.stride_out = nm > 1 ? fc(1, leaf) - J.s[k] : 0;
+                        for (size_t b = 0; b < nm; ++b) regular = regular && fc(b, leaf) == J.s[k] + (long long)b * J.stride_out;
                     }
-                    blob[t.c1 + bi * t.N2P + n] = (float)s1;
-                    blob[t.c2 + bi * t.N2P + n] = (float)s2;
+                    ++k;
                 }
             }
-            const auto& wf = W(models[b] + ".fc_output_layer.weight");   // [fc_out][cin]: top rows of a zero-padded [N2P][K1P]
-            for (int n = 0; n < fc_out; ++n)
-                for (int k = 0; k < cin; ++k) blob[t.wf + (b * t.N2P + n) * t.K1P + k] = wf[(size_t)n * cin + k];
-            const auto& bf = W(models[b] + ".fc_output_layer.bias");
-            std::copy(bf.begin(), bf.end(), blob.begin() + t.bf + b * t.N2P);
-        }
+            emit(J, o, size);
+            return o;
+        };
+        auto vec = [&](int len, int padded) { return make_job(PK_PADMAT, 1, len, 1, padded); };
+        t.w1 = image(make_job(PK_PADMAT, CH, cin, t.N1P, t.K1P), nm * nb * t.N1P * t.K1P, {".conv1x1.weight"}, true);       // [CH][cin][1]
+        t.b1 = image(vec(CH, t.N1P), nm * nb * t.N1P, {".conv1x1.bias"}, true);
+        t.a1 = image(vec(1, 1), nm * nb + 1, {".prelu1.weight"}, true);
+        t.g1w = image(vec(CH, CH), nm * nb * CH, {".norm1.weight"}, true);
+        t.g1b = image(vec(CH, CH), nm * nb * CH, {".norm1.bias"}, true);
+        t.dw = image(make_job(PK_TRANSPOSE, CH, 3), nm * nb * 3 * CH, {".depthwise_conv.weight"}, true);                     // [CH][1][3] -> tap major
+        t.db = image(vec(CH, CH), nm * nb * CH, {".depthwise_conv.bias"}, true);
+        t.a2 = image(vec(1, 1), nm * nb + 1, {".prelu2.weight"}, true);
+        t.g2w = image(vec(CH, CH), nm * nb * CH, {".norm2.weight"}, true);
+        t.g2b = image(vec(CH, CH), nm * nb * CH, {".norm2.bias"}, true);
+        t.w2 = image(make_job(PK_PADMAT, cin, CH, t.N2P, t.K2P), nm * nb * t.N2P * t.K2P, {".sconv.weight"}, true);         // [cin][CH][1]
+        t.b2 = image(vec(cin, t.N2P), nm * nb * t.N2P, {".sconv.bias"}, true);
+        // GroupNorm 2 folded into the sconv GEMM (tcn.hip tcn_gemm_dma_kernel): weights times gamma, and the two per-output
+        // constants (weight_layouts.h: PK_FOLDW, fold_row)
+        t.w2g = image(make_job(PK_FOLDW, cin, CH, t.N2P, t.K2P), nm * nb * t.N2P * t.K2P, {".sconv.weight", ".norm2.weight"}, true);
+        t.c1 = image(make_job(PK_FOLDC, cin, CH, t.N2P, 0), nm * nb * t.N2P, {".sconv.weight", ".norm2.weight", ".norm2.bias", ".sconv.bias"}, true);
+        t.c2 = image(make_job(PK_FOLDC, cin, CH, t.N2P, 1), nm * nb * t.N2P, {".sconv.weight", ".norm2.weight", ".norm2.bias", ".sconv.bias"}, true);
+        t.wf = image(make_job(PK_PADMAT, fc_out, cin, t.N2P, t.K1P), nm * t.N2P * t.K1P, {".weight"}, false);   // [fc_out][cin]: top rows of a zero-padded [N2P][K1P]
+        t.bf = image(vec(fc_out, t.N2P), nm * t.N2P, {".bias"}, false);
         return t;
     };
     auto bind_tcn = [&](TcnWeights& t, const TcnOff& o, const float* d) {
@@ -314,148 +355,127 @@ int fsnp_commit_weights(fsnp_handle* h) {
     for (int b = 0; b < nbr_w; ++b) fb_models.push_back(kFb[b]);
     const TcnOff fb_off = pack_tcn(fb_models, NB, F, F);
     const TcnOff sb_off = h->sb_tcn ? pack_tcn({"sb_model"}, 8, h->NIN, h->cfg.output_size) : TcnOff{};
-    // ---- recurrent models: MFMA B-fragment order + summed biases.  Every kernel sees FOUR column slots per hidden unit:
-    // LSTM i, f, g, o (the reference's gate order); GRU r, z, n_x, n_h with W_in only in the input rows of K and W_hn only
-    // in the hidden rows (zero blocks elsewhere), biases b_ir + b_hr, b_iz + b_hz, b_in, b_hn.
-    struct Rnn4 { std::vector<float> wih0, whh0, wih1, whh1, bias; };
-    auto expand = [&](const std::string& pre, int Hh, int nin) {
-        Rnn4 r;
-        const auto &a0 = W(pre + "weight_ih_l0"), &a1 = W(pre + "weight_hh_l0"), &a2 = W(pre + "weight_ih_l1"), &a3 = W(pre + "weight_hh_l1");
-        r.bias.assign((size_t)2 * 4 * Hh, 0.0f);
-        if (!h->gru) {
-            r.wih0 = a0; r.whh0 = a1; r.wih1 = a2; r.whh1 = a3;
-            for (int l = 0; l < 2; ++l) {
-                const auto& bi = W(pre + "bias_ih_l" + std::to_string(l));
-                const auto& bh = W(pre + "bias_hh_l" + std::to_string(l));
-                for (int i = 0; i < 4 * Hh; ++i) r.bias[(size_t)l * 4 * Hh + i] = bi[i] + bh[i];
-            }
-            return r;
-        }
-        auto spread = [&](const std::vector<float>& src, int cols, bool hidden) {   // [3H][cols] -> [4H][cols]
-            std::vector<float> dst((size_t)4 * Hh * cols, 0.0f);
-            std::copy(src.begin(), src.begin() + (size_t)2 * Hh * cols, dst.begin());                        // r, z
-            std::copy(src.begin() + (size_t)2 * Hh * cols, src.end(), dst.begin() + (size_t)(hidden ? 3 : 2) * Hh * cols);   // n
-            return dst;
-        };
-        r.wih0 = spread(a0, nin, false); r.whh0 = spread(a1, Hh, true);
-        r.wih1 = spread(a2, Hh, false); r.whh1 = spread(a3, Hh, true);
-        for (int l = 0; l < 2; ++l) {
-            const auto& bi = W(pre + "bias_ih_l" + std::to_string(l));
-            const auto& bh = W(pre + "bias_hh_l" + std::to_string(l));
-            float* b = r.bias.data() + (size_t)l * 4 * Hh;
-            for (int i = 0; i < 2 * Hh; ++i) b[i] = bi[i] + bh[i];
-            for (int i = 0; i < Hh; ++i) { b[2 * Hh + i] = bi[2 * Hh + i]; b[3 * Hh + i] = bh[2 * Hh + i]; }
-        }
-        return r;
+    if (!regular) { set_error("fsnp_commit_weights: the TCN blocks are not evenly spaced in the parameter list"); return 3; }
+    // ---- recurrent models: MFMA B-fragment order + summed biases, cut from the FOUR-slot view of the reference's matrices
+    // (weight_layouts.h: rnn_w, rnn_bias)
+    auto rnn = [&](int kind, const std::string& pre, int Hh, int nin, int kx, int P) {
+        PackJob J = make_job(kind, Hh, nin, kx, P, h->gru);
+        static const char* leaves[8] = {"weight_ih_l0", "weight_hh_l0", "weight_ih_l1", "weight_hh_l1", "bias_ih_l0", "bias_hh_l0", "bias_ih_l1", "bias_hh_l1"};
+        for (int i = 0; i < 8; ++i) J.s[i] = off(pre + leaves[i]);
+        const size_t o = alloc((size_t)J.n);
+        emit(J, o, (size_t)J.n);
+        return o;
     };
-    const Rnn4 sbw = h->sb_tcn ? Rnn4{} : expand("sb_model.sequence_model.", H, h->NIN);
+    const std::string sbp = "sb_model.sequence_model.";
+    auto sb = [&](int kind, int P = 0) { return rnn(kind, sbp, H, h->NIN, h->KX, P); };
     const bool tuned = !h->sb_tcn && !h->generic_sb;            // MFMA kernels exist for this cell / hidden size / input width
     size_t o_wgen = 0;
-    if (h->generic_sb) {                                        // runtime-sized kernel: transposed [layer][k][4H]
-        o_wgen = alloc(lstm_generic_pack_floats(H, h->NIN));
-        lstm_generic_pack_weights(H, h->NIN, sbw.wih0.data(), sbw.whh0.data(), sbw.wih1.data(), sbw.whh1.data(), blob.data() + o_wgen);
-    }
+    if (h->generic_sb) o_wgen = sb(PK_GENERIC);                 // runtime-sized kernel: transposed [layer][k][4H]
     size_t o_wpack = 0, o_wpack12 = 0, o_wpack_bf[2] = {0, 0};
     if (!h->gru && tuned && (H == 384 || H == 256)) {      // the row-tile kernel (and its bf16 variant) exists for LSTM only
-        o_wpack = alloc(lstm_pack_floats(H, h->KX, 4));
-        lstm_pack_weights(H, h->NIN, h->KX, 4, sbw.wih0.data(), sbw.whh0.data(), sbw.wih1.data(), sbw.whh1.data(), blob.data() + o_wpack);
-        if (H == 384) {
-            o_wpack12 = alloc(lstm_pack_floats(H, h->KX, 12));
-            lstm_pack_weights(H, h->NIN, h->KX, 12, sbw.wih0.data(), sbw.whh0.data(), sbw.wih1.data(), sbw.whh1.data(), blob.data() + o_wpack12);
-        }
-        for (int i = 0; i < 2 && h->KX == 40 && H == 384 && h->NIN < h->KX; ++i) {      // the bf16-ih variant is built for the default input width only (and needs a spare input column: its layer-0 bias rides there)
-            const int nw = i == 0 ? 4 : 12;
-            o_wpack_bf[i] = alloc(lstm_pack_floats_bf16ih(H, h->KX, nw));
-            lstm_pack_weights_bf16ih(H, h->NIN, h->KX, nw, sbw.wih0.data(), sbw.whh0.data(), sbw.wih1.data(), sbw.whh1.data(), sbw.bias.data(),
-                                     blob.data() + o_wpack_bf[i]);
-        }
+        o_wpack = sb(PK_ROWTILE, 4);
+        if (H == 384) o_wpack12 = sb(PK_ROWTILE, 12);
+        // the bf16-ih variant is built for the default input width only (and needs a spare input column: its layer-0 bias rides there)
+        for (int i = 0; i < 2 && h->KX == 40 && H == 384 && h->NIN < h->KX; ++i) o_wpack_bf[i] = sb(PK_ROWTILE_BF, i == 0 ? 4 : 12);
     }
     size_t o_wpack16 = 0, o_wpack16_bf = 0;
     bool have16_bf = false;
     if (h->planner.lstm16_ok) {
-        o_wpack16 = alloc(lstm16_pack_floats(H, h->KX));
-        lstm16_pack_weights(H, h->NIN, h->KX, sbw.wih0.data(), sbw.whh0.data(), sbw.wih1.data(), sbw.whh1.data(), blob.data() + o_wpack16);
+        o_wpack16 = sb(PK_HALF);
         if (h->KX == 40 && H == 384) {                 // bf16-ih stream of the half-tile kernel (configs[4], round 4)
-            o_wpack16_bf = alloc(lstm16_pack_floats_bf16ih(H, h->KX));
-            lstm16_pack_weights_bf16ih(H, h->NIN, h->KX, sbw.wih0.data(), sbw.whh0.data(), sbw.wih1.data(), sbw.whh1.data(), blob.data() + o_wpack16_bf);
+            o_wpack16_bf = sb(PK_HALF_BF);
             have16_bf = true;
         }
     }
     size_t o_wpack_gru = 0;
-    if (h->gru && tuned && H == 384) {
-        o_wpack_gru = alloc(gru_pack_floats(H, h->KX, 4));
-        gru_pack_weights(H, h->NIN, h->KX, 4, sbw.wih0.data(), sbw.whh0.data(), sbw.wih1.data(), sbw.whh1.data(), blob.data() + o_wpack_gru);
-    }
+    if (h->gru && tuned && H == 384) o_wpack_gru = sb(PK_GRU, 4);
     size_t o_wpack_coop[4] = {0, 0, 0, 0};
-    for (int ui = 0; ui < 4 && tuned; ++ui) {
-        const int units = 8 << ui;
-        o_wpack_coop[ui] = alloc(lstm_coop_pack_floats(H, h->KX, units));
-        lstm_coop_pack_weights(H, h->NIN, h->KX, units, sbw.wih0.data(), sbw.whh0.data(), sbw.wih1.data(), sbw.whh1.data(),
-                               blob.data() + o_wpack_coop[ui]);
-    }
+    for (int ui = 0; ui < 4 && tuned; ++ui) o_wpack_coop[ui] = sb(PK_KSPLIT, 8 << ui);
     size_t o_wpack_hp = 0, o_wpack_hpw = 0;
     if (h->planner.hp_ok) {
-        o_wpack_hp = alloc(lstm_hp_pack_floats(H, h->KX));
-        lstm_hp_pack_weights(H, h->NIN, h->KX, sbw.wih0.data(), sbw.whh0.data(), sbw.wih1.data(), sbw.whh1.data(), blob.data() + o_wpack_hp);
-        o_wpack_hpw = alloc(lstm_hpw_pack_floats(H, h->KX));
-        lstm_hpw_pack_weights(H, h->NIN, h->KX, sbw.wih0.data(), sbw.whh0.data(), sbw.wih1.data(), sbw.whh1.data(), blob.data() + o_wpack_hpw);
+        o_wpack_hp = sb(PK_HP);
+        o_wpack_hpw = sb(PK_HPW);
     }
     size_t o_wpack_coopw = 0;
-    if (h->planner.coopw_ok) {
-        o_wpack_coopw = alloc(lstm_coopw_pack_floats(H, h->KX));
-        lstm_coopw_pack_weights(H, h->NIN, h->KX, sbw.wih0.data(), sbw.whh0.data(), sbw.wih1.data(), sbw.whh1.data(), blob.data() + o_wpack_coopw);
-    }
-    const size_t o_wpack_coopn = alloc(tuned ? lstm_coopn_pack_floats(H, h->KX) : 0);
-    if (tuned)
-        lstm_coopn_pack_weights(H, h->NIN, h->KX, sbw.wih0.data(), sbw.whh0.data(), sbw.wih1.data(), sbw.whh1.data(),
-                                blob.data() + o_wpack_coopn);
+    if (h->planner.coopw_ok) o_wpack_coopw = sb(PK_COOPW);
+    const size_t o_wpack_coopn = tuned ? sb(PK_COOPN) : alloc(0);
     // ---- original FullSubNet: full-band recurrent model (cooperative kernel, KX = 264) + Linear(CH, F) as a GEMM operand
     constexpr int KXF = 264;
     size_t o_fbpack[3] = {0, 0, 0}, o_fbbias = 0, o_fsn_wf = 0, o_fsn_bf = 0, o_fbgen = 0, o_fbv = 0;
     bool have_fbv = false;
     const int fsn_kp = (int)align_up(CH, 16), fsn_np = (int)align_up(F, 384);
     if (fsn) {
-        const Rnn4 fbw = expand("fb_model.sequence_model.", CH, F);
-        if (h->generic_fb || !h->gru) {        // (LSTM: also what a stream session's full-band pushes run on - launch_lstm_generic_stream)
-            o_fbgen = alloc(lstm_generic_pack_floats(CH, F));
-            lstm_generic_pack_weights(CH, F, fbw.wih0.data(), fbw.whh0.data(), fbw.wih1.data(), fbw.whh1.data(), blob.data() + o_fbgen);
-        }
-        for (int ui = 0; ui < 3 && !h->generic_fb; ++ui) {
-            const int units = 8 << ui;
-            o_fbpack[ui] = alloc(lstm_coop_pack_floats(CH, KXF, units));
-            lstm_coop_pack_weights(CH, F, KXF, units, fbw.wih0.data(), fbw.whh0.data(), fbw.wih1.data(), fbw.whh1.data(),
-                                   blob.data() + o_fbpack[ui]);
-        }
+        const std::string fbp = "fb_model.sequence_model.";
+        // (LSTM: also what a stream session's full-band pushes run on - launch_lstm_generic_stream)
+        if (h->generic_fb || !h->gru) o_fbgen = rnn(PK_GENERIC, fbp, CH, F, 0, 0);
+        for (int ui = 0; ui < 3 && !h->generic_fb; ++ui) o_fbpack[ui] = rnn(PK_KSPLIT, fbp, CH, F, KXF, 8 << ui);
         if (!h->generic_fb && !h->gru && CH == 512 && F <= 288) {          // small batches: matrix-vector products on the VALU (lstm_fbv.hip)
-            o_fbv = alloc(lstm_fbv_pack_floats(CH));
-            lstm_fbv_pack_weights(CH, F, fbw.wih0.data(), fbw.whh0.data(), fbw.wih1.data(), fbw.whh1.data(), blob.data() + o_fbv);
+            o_fbv = rnn(PK_FBV, fbp, CH, F, 0, 0);
             have_fbv = true;
         }
-        o_fbbias = alloc(fbw.bias.size());
-        std::copy(fbw.bias.begin(), fbw.bias.end(), blob.begin() + o_fbbias);
+        o_fbbias = rnn(PK_BIAS, fbp, CH, F, 0, 0);
         o_fsn_wf = alloc((size_t)fsn_np * fsn_kp);
-        const auto& wf = W("fb_model.fc_output_layer.weight");          // [F][CH]
-        for (int n = 0; n < F; ++n)
-            for (int k = 0; k < CH; ++k) blob[o_fsn_wf + (size_t)n * fsn_kp + k] = wf[(size_t)n * CH + k];
+        PackJob J = make_job(PK_PADMAT, F, CH, fsn_np, fsn_kp);         // [F][CH]
+        J.s[0] = off("fb_model.fc_output_layer.weight");
+        emit(J, o_fsn_wf, (size_t)fsn_np * fsn_kp);
         o_fsn_bf = alloc(fsn_np);
-        const auto& bf = W("fb_model.fc_output_layer.bias");
-        std::copy(bf.begin(), bf.end(), blob.begin() + o_fsn_bf);
+        PackJob Jb = make_job(PK_PADMAT, 1, F, 1, fsn_np);
+        Jb.s[0] = off("fb_model.fc_output_layer.bias");
+        emit(Jb, o_fsn_bf, fsn_np);
     }
-    const size_t o_lbias = alloc(sbw.bias.size());
-    std::copy(sbw.bias.begin(), sbw.bias.end(), blob.begin() + o_lbias);
+    const size_t o_lbias = h->sb_tcn ? alloc(0) : sb(PK_BIAS);
     const size_t o_wfc = h->sb_tcn ? 0 : put("sb_model.fc_output_layer.weight");
     const size_t o_bfc = h->sb_tcn ? 0 : put("sb_model.fc_output_layer.bias");
-    // ---- unfold multiplicities w_r, by brute force over (f, j)
+    // ---- unfold multiplicities w_r, by brute force over (f, j): they depend on the configuration only, so
+    // both paths compute them on the host (once) and upload them
     const size_t o_refl = alloc(F), o_reflfb = alloc(F);
-    for (int f = 0; f < F; ++f) {
-        for (int j = 0; j < h->NSB; ++j) blob[o_refl + reflect_index(f - h->cfg.sb_num_neighbors + j, F)] += 1.0f;
-        for (int j = 0; j < 2 * h->cfg.fb_num_neighbors + 1; ++j) blob[o_reflfb + reflect_index(f - h->cfg.fb_num_neighbors + j, F)] += 1.0f;
+    const size_t refl_floats = total - o_refl;
+    if (h->refl_host.size() != refl_floats) {
+        h->refl_host.assign(refl_floats, 0.0f);
+        for (int f = 0; f < F; ++f) {
+            for (int j = 0; j < h->NSB; ++j) h->refl_host[reflect_index(f - h->cfg.sb_num_neighbors + j, F)] += 1.0f;
+            for (int j = 0; j < 2 * h->cfg.fb_num_neighbors + 1; ++j) h->refl_host[o_reflfb - o_refl + reflect_index(f - h->cfg.fb_num_neighbors + j, F)] += 1.0f;
+        }
     }
 
     FSNP_ON_DEVICE(h);
-    if (h->d_weights) { FSNP_HIP_CHECK(hipDeviceSynchronize()); FSNP_HIP_CHECK(hipFree(h->d_weights)); h->d_weights = nullptr; }
-    FSNP_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&h->d_weights), blob.size() * sizeof(float)));
-    FSNP_HIP_CHECK(hipMemcpy(h->d_weights, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice));
+    int64_t stats[4] = {on_device ? 1 : 0, 0, 0, 0};
+    if (!on_device) {
+        std::vector<float> blob(total, 0.0f);
+        for (const PackJob& J : jobs) pack_image_host(J, h->host_arena.data(), blob.data() + J.out, (long long)align_up((size_t)J.n, 64));
+        std::copy(h->refl_host.begin(), h->refl_host.end(), blob.begin() + o_refl);
+        if (h->d_weights) { FSNP_HIP_CHECK(hipDeviceSynchronize()); FSNP_HIP_CHECK(hipFree(h->d_weights)); h->d_weights = nullptr; }
+        FSNP_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&h->d_weights), blob.size() * sizeof(float)));
+        FSNP_HIP_CHECK(hipMemcpy(h->d_weights, blob.data(), blob.size() * sizeof(float), hipMemcpyHostToDevice));
+        h->blob_floats = total;
+        h->packed_valid = false;
+        stats[1] = (int64_t)(blob.size() * sizeof(float));
+    } else {
+        // Behind everything already enqueued for the handle: forwards on other streams (their event), a pipelined deferred chunk
+        // (the flush).  What these two do not see - a stream-session push or a sampled verification pass on a stream of its own -
+        // is covered by a device-wide wait in front of the overwrite, as on the host path; the first pack writes a fresh
+        // allocation and waits for nothing.
+        if (order_after_last_forward(h, s)) return 4;
+        if (h->pipeline && fsnp_flush(h, s)) return 4;
+        // the arena copies ran on another stream: wait for the event recorded behind the last of them
+        if (h->arena_valid && h->arena_stream != s) FSNP_HIP_CHECK(hipStreamWaitEvent(s, h->ev_arena, 0));
+        if (h->d_weights && h->blob_floats != total) { FSNP_HIP_CHECK(hipDeviceSynchronize()); FSNP_HIP_CHECK(hipFree(h->d_weights)); h->d_weights = nullptr; }
+        if (h->d_weights) FSNP_HIP_CHECK(hipDeviceSynchronize());
+        else FSNP_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&h->d_weights), total * sizeof(float)));
+        h->blob_floats = total;
+        h->committed = false;                                 // (a launch that fails leaves a partly written blob behind)
+        for (const PackJob& J : jobs) {
+            if (const int rc = launch_pack_image(J, h->d_arena, h->arena_floats, h->d_weights, (long long)align_up((size_t)J.n, 64), s)) return rc;
+            ++stats[3];
+        }
+        FSNP_HIP_CHECK(hipMemcpyAsync(h->d_weights + o_refl, h->refl_host.data(), refl_floats * sizeof(float), hipMemcpyHostToDevice, s));
+        stats[1] = (int64_t)(refl_floats * sizeof(float));
+        if (!h->ev_packed) FSNP_HIP_CHECK(hipEventCreateWithFlags(&h->ev_packed, hipEventDisableTiming));
+        FSNP_HIP_CHECK(hipEventRecord(h->ev_packed, s));
+        h->packed_stream = s; h->packed_valid = true;
+        if (mark_forward_done(h, s)) return 4;                // forwards on other streams wait for the pack
+    }
+    for (int i = 0; i < 4; ++i) if (i != 2) h->commit_stats[i] = stats[i];
     const float* d = h->d_weights;
     for (int a = 0; a < 3; ++a) {
         for (int c = 0; c < 3; ++c) { h->fw.conv_w[a][c] = d + o_conv_w[a][c]; h->fw.conv_b[a][c] = d + o_conv_b[a][c]; }
@@ -499,8 +519,74 @@ int fsnp_commit_weights(fsnp_handle* h) {
     if (h->generic_sb && lstm_generic_check(h->H, h->NIN, false)) return 2;
     if (h->generic_fb && lstm_generic_check(h->CH, h->F, true)) return 2;
     h->committed = true;
-    (void)Fr;
     return 0;
+}
+
+static int missing_key(const fsnp_handle* h) {
+    for (size_t i = 0; i < h->specs.size(); ++i)
+        if (!h->spec_src[i]) { set_error("missing key in state_dict: %s", h->specs[i].name.c_str()); return 2; }
+    return 0;
+}
+
+// fsnp_commit_weights / the mixed case of fsnp_commit_weights_on: whatever only the device arena holds comes down first
+static int commit_host(fsnp_handle* h) {
+    int64_t down = 0;
+    if (const int rc = download_device_given(h, &down)) return rc;
+    h->commit_stats[2] = down;
+    return commit_impl(h, false, nullptr);
+}
+
+}  // namespace fsnp
+
+extern "C" {
+
+int fsnp_set_weight(fsnp_handle* h, const char* name, const float* host_data, int64_t numel) {
+    if (!h || !name || !host_data) { set_error("fsnp_set_weight: null argument"); return 1; }
+    const int i = find_spec(h, name, numel);
+    if (i < 0) return 2;
+    std::copy(host_data, host_data + numel, h->host_arena.begin() + h->spec_off[i]);
+    h->spec_src[i] = 1;
+    h->committed = false;
+    h->watch_nseg = 0;            // the watched tensors belonged to the previous weight set (fsnp_watch_weights again after the commit)
+    return 0;
+}
+
+int fsnp_set_weight_device(fsnp_handle* h, const char* name, const float* dev_data, int64_t numel, void* hip_stream) {
+    if (!h || !name || !dev_data) { set_error("fsnp_set_weight_device: null argument"); return 1; }
+    const int i = find_spec(h, name, numel);
+    if (i < 0) return 2;
+    FSNP_ON_DEVICE(h);
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    if (!h->d_arena) FSNP_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&h->d_arena), (size_t)std::max<long long>(h->arena_floats, 1) * sizeof(float)));
+    if (!h->ev_arena) FSNP_HIP_CHECK(hipEventCreateWithFlags(&h->ev_arena, hipEventDisableTiming));
+    // the arena is written in the order of the calls, whatever streams they name, and never under a pack that still reads it
+    // (ev_arena is recorded behind every copy on the copy's own stream - never later on a stream the caller may have destroyed - and
+    //  a call on another stream waits for it first, so the event of the LAST copy stands for all of them)
+    if (h->arena_valid && h->arena_stream != s) FSNP_HIP_CHECK(hipStreamWaitEvent(s, h->ev_arena, 0));
+    if (const int rc = order_after_weight_pack(h, s)) return rc;
+    FSNP_HIP_CHECK(hipMemcpyAsync(h->d_arena + h->spec_off[i], dev_data, (size_t)numel * sizeof(float), hipMemcpyDeviceToDevice, s));
+    FSNP_HIP_CHECK(hipEventRecord(h->ev_arena, s));
+    h->arena_stream = s; h->arena_valid = true;
+    h->spec_src[i] = 2;
+    h->committed = false;
+    h->watch_nseg = 0;
+    return 0;
+}
+
+int fsnp_commit_weights(fsnp_handle* h) {
+    if (!h) { set_error("null handle"); return 1; }
+    if (const int rc = missing_key(h)) return rc;
+    return commit_host(h);
+}
+
+int fsnp_commit_weights_on(fsnp_handle* h, void* hip_stream) {
+    if (!h) { set_error("null handle"); return 1; }
+    if (const int rc = missing_key(h)) return rc;
+    bool all_device = true;
+    for (unsigned char v : h->spec_src) all_device = all_device && v >= 2;
+    if (!all_device) return commit_host(h);
+    h->commit_stats[2] = 0;
+    return commit_impl(h, true, static_cast<hipStream_t>(hip_stream));
 }
 
 }  // extern "C"

@@ -273,7 +273,7 @@ void lstm2_fc_kernel(LstmWeights w, LstmArgs a) {
     float4* Wfc4 = HE1s + KGH * 2 * EX;                  // [OUT][KGH][2]
     RowDesc* rows_s = reinterpret_cast<RowDesc*>(Wfc4 + OUT * KGH * 2);  // [RT]
     // BF (bf16-ih variant): the layer-0 bias is FOLDED into the product - input slot k = NIN (one of the zero-padded columns of the x
-    // image) holds the constant 1, the weight column k = NIN holds b_ih0 + b_hh0 (lstm_pack_weights_bf16ih) - so the table holds layer 1
+    // image) holds the constant 1, the weight column k = NIN holds b_ih0 + b_hh0 (weight_layouts.h, PK_ROWTILE_BF) - so the table holds layer 1
     // only: the 6 KB that frees are what the second (lo) bf16 image of h0_t needs to fit a CU's 160 KB next to the fp32 images
     constexpr int BL = BF ? 1 : 2;                                       // bias layers in LDS
     constexpr bool HILO = BF && EX == 0;                                 // h0_t as bf16 hi + lo (VALU-row tiles: hi only, the E images take the room)
@@ -531,85 +531,15 @@ void lstm2_fc_kernel(LstmWeights w, LstmArgs a) {
 }
 
 // -------------------------------------------------------------------------------------------------
-size_t lstm_pack_floats(int H, int KX, int NW) {
-    const int NT = 4 * (H / NW / 32);
-    const int KGT = KX / 8 + H / 8 + 2 * (H / 8);
-    return (size_t)NW * KGT * NT * 64 * 4;
-}
 
+// The weight image this kernel reads (packed by weight_layouts.h, PK_ROWTILE / PK_ROWTILE_BF; on the host or by weight_pack.hip):
 // [wave][k-group][tile][lane][k-pair]: wave wv owns hidden units [wv*H/NW, (wv+1)*H/NW); tile n = gate*ST + s
 // holds columns unit = wv*UW + 32 s + (lane & 31) of gate `gate`; k = 8 g + 2 p + (lane >> 5).
-void lstm_pack_weights(int H, int NIN, int KX, int NW, const float* wih0, const float* whh0, const float* wih1,
-                       const float* whh1, float* wpack) {
-    const int UW = H / NW, ST = UW / 32, NT = 4 * ST;
-    const int KGX = KX / 8, KGH = H / 8, KG0 = KGX + KGH, KGT = KG0 + 2 * KGH;
-    for (int wv = 0; wv < NW; ++wv)
-        for (int g = 0; g < KGT; ++g)
-            for (int n = 0; n < NT; ++n)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int p = 0; p < 4; ++p) {
-                        const int gate = n / ST, s = n % ST;
-                        const int wrow = gate * H + wv * UW + s * 32 + (lane & 31);
-                        float v = 0.0f;
-                        if (g < KG0) {
-                            const int k = 8 * g + 2 * p + (lane >> 5);
-                            if (k < KX) { if (k < NIN) v = wih0[(size_t)wrow * NIN + k]; }
-                            else v = whh0[(size_t)wrow * H + (k - KX)];
-                        } else {
-                            const int k = 8 * (g - KG0) + 2 * p + (lane >> 5);
-                            if (k < H) v = whh1[(size_t)wrow * H + k];
-                            else v = wih1[(size_t)wrow * H + (k - H)];
-                        }
-                        wpack[((((size_t)wv * KGT + g) * NT + n) * 64 + lane) * 4 + p] = v;
-                    }
-}
 
 // bf16-ih variant of the stream: layer 0 and the h1 part of layer 1 as above (fp32), then HID/16 bf16 k-steps of
 // W_ih1: lane l of step ks / tile n holds the 8 weights k = 16 ks + 8 (l>>5) + j of its column, 2 bytes each.
-size_t lstm_pack_floats_bf16ih(int H, int KX, int NW) {
-    const int NT = 4 * (H / NW / 32);
-    const int KGT = KX / 8 + H / 8 + H / 8 + H / 16;
-    return (size_t)NW * KGT * NT * 64 * 4;
-}
 
-static unsigned short host_bf16(float v) {
-    unsigned u;
-    memcpy(&u, &v, 4);
-    return (unsigned short)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
-
-// bias0 = b_ih0 + b_hh0 [4H]: packed as the weight column of input slot k = NIN, which the kernel feeds with the constant 1 (NIN < KX)
-void lstm_pack_weights_bf16ih(int H, int NIN, int KX, int NW, const float* wih0, const float* whh0, const float* wih1,
-                              const float* whh1, const float* bias0, float* wpack) {
-    const int UW = H / NW, ST = UW / 32, NT = 4 * ST;
-    const int KGX = KX / 8, KGH = H / 8, KG0 = KGX + KGH, KSB = H / 16, KGT = KG0 + KGH + KSB;
-    for (int wv = 0; wv < NW; ++wv)
-        for (int g = 0; g < KGT; ++g)
-            for (int n = 0; n < NT; ++n)
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int gate = n / ST, s = n % ST;
-                    const int wrow = gate * H + wv * UW + s * 32 + (lane & 31);
-                    float* dst = wpack + ((((size_t)wv * KGT + g) * NT + n) * 64 + lane) * 4;
-                    if (g < KG0 + KGH) {
-                        for (int p = 0; p < 4; ++p) {
-                            float v = 0.0f;
-                            if (g < KG0) {
-                                const int k = 8 * g + 2 * p + (lane >> 5);
-                                if (k < KX) { if (k < NIN) v = wih0[(size_t)wrow * NIN + k]; else if (k == NIN) v = bias0[wrow]; }
-                                else v = whh0[(size_t)wrow * H + (k - KX)];
-                            } else {
-                                const int k = 8 * (g - KG0) + 2 * p + (lane >> 5);
-                                v = whh1[(size_t)wrow * H + k];
-                            }
-                            dst[p] = v;
-                        }
-                    } else {
-                        const int ks = g - KG0 - KGH;
-                        unsigned short* d16 = reinterpret_cast<unsigned short*>(dst);
-                        for (int j = 0; j < 8; ++j) d16[j] = host_bf16(wih1[(size_t)wrow * H + 16 * ks + 8 * (lane >> 5) + j]);
-                    }
-                }
-}
+// b_ih0 + b_hh0 [4H] is packed as the weight column of input slot k = NIN, which the kernel feeds with the constant 1 (NIN < KX)
 
 template <int EX, int NW, bool BF, int KX, int HID = 384>
 static void launch_lstm_ex(const LstmWeights& w, const LstmArgs& a, hipStream_t s) {

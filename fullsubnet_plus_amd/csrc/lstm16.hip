@@ -299,81 +299,13 @@ void lstm2_fc16_kernel(LstmWeights w, LstmArgs a) {
 }
 
 // -------------------------------------------------------------------------------------------------
-size_t lstm16_pack_floats(int H, int KX) {
-    const int NT = 4 * (H / 4 / 16);
-    const int KGT = (KX + 15) / 16 + 3 * (H / 16);
-    return (size_t)4 * KGT * NT * 64 * 4;
-}
 
+// The weight image this kernel reads (packed by weight_layouts.h, PK_HALF / PK_HALF_BF; on the host or by weight_pack.hip):
 // [wave][k-group of 16][tile][lane][q]: tile n = gate * SB + s holds columns unit = wv UW + 16 s + (lane & 15) of gate `gate`;
 // component q of lane l is k = 16 g + 4 q + (l >> 4).  K order as lstm.hip: layer 0 = [x (zero padded to 16 KGX) | h0], layer 1 = [h1 | h0].
-void lstm16_pack_weights(int H, int NIN, int KX, const float* wih0, const float* whh0, const float* wih1, const float* whh1, float* wpack) {
-    const int UW = H / 4, SB = UW / 16, NT = 4 * SB;
-    const int KGX = (KX + 15) / 16, KGH = H / 16, KG0 = KGX + KGH, KGT = KG0 + 2 * KGH;
-    for (int wv = 0; wv < 4; ++wv)
-        for (int g = 0; g < KGT; ++g)
-            for (int n = 0; n < NT; ++n)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int q = 0; q < 4; ++q) {
-                        const int gate = n / SB, s = n % SB;
-                        const int wrow = gate * H + wv * UW + s * 16 + (lane & 15);
-                        float v = 0.0f;
-                        if (g < KGX) {
-                            const int k = 16 * g + 4 * q + (lane >> 4);
-                            if (k < NIN) v = wih0[(size_t)wrow * NIN + k];
-                        } else if (g < KG0) {
-                            v = whh0[(size_t)wrow * H + 16 * (g - KGX) + 4 * q + (lane >> 4)];
-                        } else if (g < KG0 + KGH) {
-                            v = whh1[(size_t)wrow * H + 16 * (g - KG0) + 4 * q + (lane >> 4)];
-                        } else {
-                            v = wih1[(size_t)wrow * H + 16 * (g - KG0 - KGH) + 4 * q + (lane >> 4)];
-                        }
-                        wpack[((((size_t)wv * KGT + g) * NT + n) * 64 + lane) * 4 + q] = v;
-                    }
-}
 
 // bf16-ih variant of the stream: layer 0 and the h1 part of layer 1 as above (fp32), then HID / 32 bf16 k-steps of W_ih1: lane l of
 // step ks / tile n holds the 8 weights k = 32 ks + 8 (l >> 4) + j of its column, 2 bytes each (16 bytes per lane, like an fp32 group)
-size_t lstm16_pack_floats_bf16ih(int H, int KX) {
-    const int NT = 4 * (H / 4 / 16);
-    const int KGT = (KX + 15) / 16 + 2 * (H / 16) + H / 32;
-    return (size_t)4 * KGT * NT * 64 * 4;
-}
-static unsigned short host_bf16_rne16(float v) {
-    unsigned u;
-    memcpy(&u, &v, 4);
-    return (unsigned short)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
-void lstm16_pack_weights_bf16ih(int H, int NIN, int KX, const float* wih0, const float* whh0, const float* wih1, const float* whh1, float* wpack) {
-    const int UW = H / 4, SB = UW / 16, NT = 4 * SB;
-    const int KGX = (KX + 15) / 16, KGH = H / 16, KG0 = KGX + KGH, KSB = H / 32, KGT = KG0 + KGH + KSB;
-    for (int wv = 0; wv < 4; ++wv)
-        for (int g = 0; g < KGT; ++g)
-            for (int n = 0; n < NT; ++n)
-                for (int lane = 0; lane < 64; ++lane) {
-                    const int gate = n / SB, s = n % SB;
-                    const int wrow = gate * H + wv * UW + s * 16 + (lane & 15);
-                    float* dst = wpack + ((((size_t)wv * KGT + g) * NT + n) * 64 + lane) * 4;
-                    if (g < KG0 + KGH) {
-                        for (int q = 0; q < 4; ++q) {
-                            float v = 0.0f;
-                            if (g < KGX) {
-                                const int k = 16 * g + 4 * q + (lane >> 4);
-                                if (k < NIN) v = wih0[(size_t)wrow * NIN + k];
-                            } else if (g < KG0) {
-                                v = whh0[(size_t)wrow * H + 16 * (g - KGX) + 4 * q + (lane >> 4)];
-                            } else {
-                                v = whh1[(size_t)wrow * H + 16 * (g - KG0) + 4 * q + (lane >> 4)];
-                            }
-                            dst[q] = v;
-                        }
-                    } else {
-                        const int ks = g - KG0 - KGH;
-                        unsigned short* d16 = reinterpret_cast<unsigned short*>(dst);
-                        for (int j = 0; j < 8; ++j) d16[j] = host_bf16_rne16(wih1[(size_t)wrow * H + 32 * ks + 8 * (lane >> 4) + j]);
-                    }
-                }
-}
 
 template <bool BF>
 static void launch_lstm16_bf(const LstmWeights& w, const LstmArgs& a, hipStream_t s) {

@@ -27,6 +27,7 @@
 
 #include "fsnp_common.h"
 #include "lstm_common.h"
+#include "weight_layouts.h"
 
 namespace fsnp {
 
@@ -764,50 +765,12 @@ __global__ __launch_bounds__(256) void lstm2_coop_skew_kernel(LstmWeights w, Lst
 }
 
 // ------------------------------------------------------------------------------------------------
-static int coop_kgxp(int KX) { return (KX / 8 + 3) / 4 * 4; }
 
-size_t lstm_coop_pack_floats(int H, int KX, int units) {
-    const int S = H / units, NT = units / 8;
-    const int GW = (coop_kgxp(KX) + H / 8) / 4 + H / 16;     // local k-groups per wave, both layers
-    return (size_t)S * 4 * GW * NT * 64 * 4;
-}
 
+// The weight image this kernel reads (packed by weight_layouts.h, PK_KSPLIT; on the host or by weight_pack.hip):
 // [cs][wave][local k-group i (layer 0: G0W groups, then layer 1: G1W groups)][tile n][lane][k-pair]; local group i of
 // wave w is global k-group 4 i + w of its layer: layer 0 = [x (KGXP groups, zero padded) | h0], layer 1 = [h1 | h0].
 // Column j = n * 32 + (lane & 31) of the workgroup is gate j / units, hidden unit cs * units + j % units.
-void lstm_coop_pack_weights(int H, int NIN, int KX, int units, const float* wih0, const float* whh0, const float* wih1,
-                            const float* whh1, float* wpack) {
-    const int S = H / units, NT = units / 8;
-    const int KGXP = coop_kgxp(KX), KGH = H / 8;
-    const int G0W = (KGXP + KGH) / 4, G1W = KGH / 2, GW = G0W + G1W;
-    for (int cs = 0; cs < S; ++cs)
-        for (int wave = 0; wave < 4; ++wave)
-            for (int i = 0; i < GW; ++i)
-                for (int n = 0; n < NT; ++n)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int p = 0; p < 4; ++p) {
-                            const int j = n * 32 + (lane & 31);
-                            const int gate = j / units, u = j % units;
-                            const int wrow = gate * H + cs * units + u;
-                            float v = 0.0f;
-                            if (i < G0W) {
-                                const int g = 4 * i + wave;
-                                if (g < KGXP) {
-                                    const int k = 8 * g + 2 * p + (lane >> 5);
-                                    if (k < NIN) v = wih0[(size_t)wrow * NIN + k];
-                                } else {
-                                    const int k = 8 * (g - KGXP) + 2 * p + (lane >> 5);
-                                    v = whh0[(size_t)wrow * H + k];
-                                }
-                            } else {
-                                const int g = 4 * (i - G0W) + wave;
-                                const int k = 8 * g + 2 * p + (lane >> 5);
-                                if (k < H) v = whh1[(size_t)wrow * H + k];
-                                else v = wih1[(size_t)wrow * H + (k - H)];
-                            }
-                            wpack[(((((size_t)cs * 4 + wave) * GW + i) * NT + n) * 64 + lane) * 4 + p] = v;
-                        }
-}
 
 // per row tile: 4 h images + Linear partials sized for the finest split (units = 8)
 size_t lstm_coop_exchange_bytes(int H, int row_tiles) {

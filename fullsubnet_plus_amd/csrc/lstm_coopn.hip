@@ -324,31 +324,9 @@ __global__ __launch_bounds__(256) void lstm2_coopn_kernel(LstmWeights w, LstmArg
 }
 
 // ------------------------------------------------------------------------------------------------
-size_t lstm_coopn_pack_floats(int H, int KX) { return (size_t)(H / 32) * (KX / 8 + 3 * (H / 8)) * 4 * 64 * 4; }
 
+// The weight image this kernel reads (packed by weight_layouts.h, PK_COOPN; on the host or by weight_pack.hip):
 // [32-unit block ub][k-group (layer 0: x | h0, then layer 1: h1 | h0)][gate][lane][k-pair]
-void lstm_coopn_pack_weights(int H, int NIN, int KX, const float* wih0, const float* whh0, const float* wih1,
-                             const float* whh1, float* wpack) {
-    const int KGX = KX / 8, KGH = H / 8, KG0 = KGX + KGH, KGT = KG0 + 2 * KGH;
-    for (int ub = 0; ub < H / 32; ++ub)
-        for (int g = 0; g < KGT; ++g)
-            for (int gate = 0; gate < 4; ++gate)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int p = 0; p < 4; ++p) {
-                        const int wrow = gate * H + ub * 32 + (lane & 31);
-                        float v = 0.0f;
-                        if (g < KG0) {
-                            const int k = 8 * g + 2 * p + (lane >> 5);
-                            if (k < KX) { if (k < NIN) v = wih0[(size_t)wrow * NIN + k]; }
-                            else v = whh0[(size_t)wrow * H + (k - KX)];
-                        } else {
-                            const int k = 8 * (g - KG0) + 2 * p + (lane >> 5);
-                            if (k < H) v = whh1[(size_t)wrow * H + k];
-                            else v = wih1[(size_t)wrow * H + (k - H)];
-                        }
-                        wpack[((((size_t)ub * KGT + g) * 4 + gate) * 64 + lane) * 4 + p] = v;
-                    }
-}
 
 // Plan for `row_tiles` 32-row tiles: R row tiles per group (1 or 2), G groups of S = 3 workgroups, all co-resident.
 // Returns R (0 = not applicable: more than 2 row tiles per group would be slower than the row-tile kernel).

@@ -460,32 +460,10 @@ __global__ __launch_bounds__(256) void lstm2_coopw_kernel(LstmWeights w, LstmArg
 }
 
 // ------------------------------------------------------------------------------------------------
-size_t lstm_coopw_pack_floats(int H, int KX) { return (size_t)(KX / 8 + 3 * (H / 8)) * (H / 8) * 256; }
 
+// The weight image this kernel reads (packed by weight_layouts.h, PK_COOPW; on the host or by weight_pack.hip):
 // [k-group g (layer 0: x | h0, then layer 1: h1 | h0)][8-unit block ub][lane][k-pair p]: the B operand of MFMA p of k-group g for
 // column c = lane & 31 of block ub is W[gate (c & 3)][unit 8 ub + (c >> 2)][k = 8 g' + 2 p + (lane >> 5)]
-void lstm_coopw_pack_weights(int H, int NIN, int KX, const float* wih0, const float* whh0, const float* wih1, const float* whh1,
-                             float* wpack) {
-    const int KGX = KX / 8, KGH = H / 8, KG0 = KGX + KGH, KGT = KG0 + 2 * KGH, NUB = H / 8;
-    for (int g = 0; g < KGT; ++g)
-        for (int ub = 0; ub < NUB; ++ub)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int p = 0; p < 4; ++p) {
-                    const int c = lane & 31;
-                    const size_t wrow = (size_t)(c & 3) * H + ub * 8 + (c >> 2);
-                    float v = 0.0f;
-                    if (g < KG0) {
-                        const int k = 8 * g + 2 * p + (lane >> 5);
-                        if (k < KX) { if (k < NIN) v = wih0[wrow * NIN + k]; }
-                        else v = whh0[wrow * H + (k - KX)];
-                    } else {
-                        const int k = 8 * (g - KG0) + 2 * p + (lane >> 5);
-                        if (k < H) v = whh1[wrow * H + k];
-                        else v = wih1[wrow * H + (k - H)];
-                    }
-                    wpack[(((size_t)g * NUB + ub) * 64 + lane) * 4 + p] = v;
-                }
-}
 
 bool lstm_coopw_available(const LstmWeights& w, int units) {
     return !w.gru && w.H == 384 && (w.KX == 40 || w.KX == 64) && (units == 32 || units == 64 || units == 96) && w.wpack_coopw != nullptr;

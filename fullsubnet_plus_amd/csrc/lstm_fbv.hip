@@ -20,12 +20,13 @@
 // (tests/test_gpu_fullsubnet.py), bitwise repeatable.  LSTM only (a GRU full-band model keeps the K-split kernel).
 #include "fsnp_common.h"
 #include "lstm_common.h"
+#include "weight_layouts.h"
 
 namespace fsnp {
 
 namespace {
-constexpr int kFbvXP = 288;                 // x part of layer 0's k range (num_freqs <= 288, zero padded)
-constexpr int kFbvK0 = 100, kFbvK1 = 128;   // weights per thread: layer 0 (8 slices x 100 = 288 + 512), layer 1 (8 x 128 = 512 + 512)
+// kFbvXP = 288, kFbvK0 = 100, kFbvK1 = 128 (weight_layouts.h): x part of layer 0's k range (num_freqs <= 288, zero padded); weights
+// per thread: layer 0 (8 slices x 100 = 288 + 512), layer 1 (8 x 128 = 512 + 512)
 }  // namespace
 
 template <int HID, int NB>
@@ -177,30 +178,10 @@ __global__ __launch_bounds__(256) void lstm2_fbv_kernel(LstmWeights w, LstmArgs 
 }
 
 // ------------------------------------------------------------------------------------------------
-size_t lstm_fbv_pack_floats(int H) { return (size_t)(H / 8) * (kFbvK0 + kFbvK1) * 256; }
 
+// The weight image this kernel reads (packed by weight_layouts.h, PK_FBV; on the host or by weight_pack.hip):
 // [column slice cs][fragment j4][thread tid][4]: thread (c = tid & 31, ks = tid >> 5) holds, for gate c & 3 of unit 8 cs + (c >> 2),
 // layer-0 weights of k = 100 ks + j over [x (288, zero padded beyond NIN) | h0] and layer-1 weights of k = 128 ks + j over [h0 | h1]
-void lstm_fbv_pack_weights(int H, int NIN, const float* wih0, const float* whh0, const float* wih1, const float* whh1, float* out) {
-    const int NF = (kFbvK0 + kFbvK1) / 4;
-    for (int cs = 0; cs < H / 8; ++cs)
-        for (int tid = 0; tid < 256; ++tid) {
-            const int c = tid & 31, ks = tid >> 5;
-            const size_t wrow = (size_t)(c & 3) * H + cs * 8 + (c >> 2);
-            for (int j = 0; j < kFbvK0 + kFbvK1; ++j) {
-                float v = 0.0f;
-                if (j < kFbvK0) {
-                    const int k = kFbvK0 * ks + j;
-                    if (k < kFbvXP) { if (k < NIN) v = wih0[wrow * NIN + k]; }
-                    else v = whh0[wrow * H + (k - kFbvXP)];
-                } else {
-                    const int k = kFbvK1 * ks + (j - kFbvK0);
-                    v = k < H ? wih1[wrow * H + k] : whh1[wrow * H + (k - H)];
-                }
-                out[(((size_t)cs * NF + j / 4) * 256 + tid) * 4 + (j & 3)] = v;
-            }
-        }
-}
 
 // The H / 8 = 64 workgroups hand h over to each other every step, so all of them must be resident at once; with ~230 weight registers
 // per thread ONE workgroup fits a CU: a device (or partition) with fewer CUs than workgroups would sit in the exchange until its 2 s

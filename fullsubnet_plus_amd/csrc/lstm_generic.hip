@@ -211,22 +211,9 @@ __global__ __launch_bounds__(kGenThreads) void lstm2_generic_stream_kernel(LstmW
 }
 
 // ------------------------------------------------------------------------------------------------
-size_t lstm_generic_pack_floats(int H, int NIN) { return (size_t)(NIN + H) * 4 * H + (size_t)2 * H * 4 * H; }
 
+// The weight image this kernel reads (packed by weight_layouts.h, PK_GENERIC; on the host or by weight_pack.hip):
 // wih0 [4H][NIN], whh0 [4H][H], wih1 [4H][H], whh1 [4H][H] (four-slot matrices) -> [layer][k][4H]: layer 0 k = [x | h0], layer 1 k = [h0 | h1]
-void lstm_generic_pack_weights(int H, int NIN, const float* wih0, const float* whh0, const float* wih1, const float* whh1, float* out) {
-    const size_t G4 = (size_t)4 * H;
-    float* l0 = out;
-    float* l1 = out + (size_t)(NIN + H) * G4;
-    for (size_t c = 0; c < G4; ++c) {
-        for (int k = 0; k < NIN; ++k) l0[(size_t)k * G4 + c] = wih0[c * NIN + k];
-        for (int k = 0; k < H; ++k) {
-            l0[(size_t)(NIN + k) * G4 + c] = whh0[c * H + k];
-            l1[(size_t)k * G4 + c] = wih1[c * H + k];
-            l1[(size_t)(H + k) * G4 + c] = whh1[c * H + k];
-        }
-    }
-}
 
 // sequences per workgroup: as many as LDS allows, fewer when there are few sequences (more CUs take part); 0 = does not fit at all
 int lstm_generic_rows_per_group(int H, int NIN, int num_seq, int num_cus) {

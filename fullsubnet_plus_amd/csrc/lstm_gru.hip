@@ -240,40 +240,11 @@ void gru2_fc_kernel(LstmWeights w, LstmArgs a) {
 }
 
 // -------------------------------------------------------------------------------------------------
-size_t gru_pack_floats(int H, int KX, int NW) {
-    const int NL = 3 * (H / NW / 32);
-    const int KGT = KX / 8 + H / 8 + 2 * (H / 8);
-    return (size_t)NW * KGT * NL * 64 * 4;
-}
 
+// The weight image this kernel reads (packed by weight_layouts.h, PK_GRU; on the host or by weight_pack.hip):
 // [wave][k-group][live tile][lane][k-pair] from the FOUR-SLOT matrices of fsnp_abi.hip's expand() (W_ih: slots r, z, n, 0;
 // W_hh: r, z, 0, n - each [4H][cols]): live tile n of a k-group is slot n / ST for n < 2 ST, else slot 2 in an input segment
 // and slot 3 in a hidden segment.  K order: layer 0 = [x (KX, zero padded) | h0], layer 1 = [h1 | h0] (as lstm.hip).
-void gru_pack_weights(int H, int NIN, int KX, int NW, const float* wih0, const float* whh0, const float* wih1, const float* whh1,
-                      float* wpack) {
-    const int UW = H / NW, ST = UW / 32, NL = 3 * ST;
-    const int KGX = KX / 8, KGH = H / 8, KG0 = KGX + KGH, KGT = KG0 + 2 * KGH;
-    for (int wv = 0; wv < NW; ++wv)
-        for (int g = 0; g < KGT; ++g) {
-            // segment of this k-group: source matrix, its column count, first column, hidden / input
-            const bool l0 = g < KG0;
-            const bool hidden = l0 ? g >= KGX : g < KG0 + KGH;
-            const float* src = l0 ? (hidden ? whh0 : wih0) : (hidden ? whh1 : wih1);
-            const int cols = l0 ? (hidden ? H : NIN) : H;
-            const int g0 = l0 ? (hidden ? KGX : 0) : (hidden ? KG0 : KG0 + KGH);
-            for (int n = 0; n < NL; ++n)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int p = 0; p < 4; ++p) {
-                        const int slot = n < 2 * ST ? n / ST : (hidden ? 3 : 2);
-                        const int s = n % ST;
-                        const int wrow = slot * H + wv * UW + s * 32 + (lane & 31);
-                        const int k = 8 * (g - g0) + 2 * p + (lane >> 5);
-                        float v = 0.0f;
-                        if (k < cols) v = src[(size_t)wrow * cols + k];
-                        wpack[((((size_t)wv * KGT + g) * NL + n) * 64 + lane) * 4 + p] = v;
-                    }
-        }
-}
 
 template <int KX>
 static void launch_gru_kx(const LstmWeights& w, const LstmArgs& a, hipStream_t s) {

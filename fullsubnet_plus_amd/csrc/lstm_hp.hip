@@ -463,26 +463,10 @@ void lstm2_coop_hp_kernel(LstmWeights w, LstmArgs a) {
 #undef FSNP_HP_STAMP
 
 // ------------------------------------------------------------------------------------------------
-size_t lstm_hp_pack_floats(int H, int KX) { return (size_t)(H / 16) * 4 * (hp_gx(KX) + 3 * (H / 16)) * 256; }
 
+// The weight image this kernel reads (packed by weight_layouts.h, PK_HP; on the host or by weight_pack.hip):
 // [column slice cs][gate][fragment: x k-groups | W_hh0 | W_hh1 | W_ih1][lane][4]: the B operand of MFMA j of a k-group is
 // W[gate * H + cs * 16 + (lane & 15)][k = 16 g + 4 j + (lane >> 4)]
-void lstm_hp_pack_weights(int H, int NIN, int KX, const float* wih0, const float* whh0, const float* wih1, const float* whh1, float* out) {
-    const int S = H / 16, GX = hp_gx(KX), GH = H / 16, NF = GX + 3 * GH;
-    for (int cs = 0; cs < S; ++cs)
-        for (int gate = 0; gate < 4; ++gate)
-            for (int f = 0; f < NF; ++f)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 4; ++j) {
-                        const size_t wrow = (size_t)gate * H + cs * 16 + (lane & 15);
-                        float v = 0.0f;
-                        if (f < GX) { const int k = 16 * f + 4 * j + (lane >> 4); if (k < NIN) v = wih0[wrow * NIN + k]; }
-                        else if (f < GX + GH) v = whh0[wrow * H + 16 * (f - GX) + 4 * j + (lane >> 4)];
-                        else if (f < GX + 2 * GH) v = whh1[wrow * H + 16 * (f - GX - GH) + 4 * j + (lane >> 4)];
-                        else v = wih1[wrow * H + 16 * (f - GX - 2 * GH) + 4 * j + (lane >> 4)];
-                        out[((((size_t)cs * 4 + gate) * NF + f) * 64 + lane) * 4 + j] = v;
-                    }
-}
 
 template <int HID, int KX>
 static void launch_hp_inst(const LstmWeights& w, const LstmArgs& a, hipStream_t s, int* occ) {

@@ -11,7 +11,7 @@
 //
 //   sub-band    grid (row tiles of 32) x (H / 16): a workgroup owns 16 hidden units = 64 gate columns = two 32 x 32 fp32 MFMA tiles
 //               (gates i|f and g|o) and splits K over its 4 waves; the weight image is the one the K-split column-split kernel
-//               already has (LstmWeights::wpack_coop[1], lstm_coop_pack_weights at 16 units: [slice][wave][k-group][tile][lane][4],
+//               already has (LstmWeights::wpack_coop[1], weight_layouts.h PK_KSPLIT at 16 units: [slice][wave][k-group][tile][lane][4],
 //               local group i of wave w = global k-group 4 i + w) - nothing is packed for this file.  h travels between the launches
 //               as per-tile images in MFMA A-fragment order (a_frag_index), so a wave's operand load is one coalesced 1 KiB read per
 //               k-group; x_t is gathered (sb_feature_offset) and normalised (md_row) into an LDS image of the same order.  The four

@@ -250,6 +250,11 @@ class _HipModel(nn.Module):
         self.error_check = "sync"
         # fsnp_watch_weights: every Nth forward starts with one fingerprint kernel over the parameters' storage (1 = every forward)
         self.weight_watch_every = 1
+        # how a (re-)pack hands the parameters to the library: "device" = tensors on the handle's device go over as device pointers
+        # and the blob is packed by kernels (fsnp_set_weight_device / fsnp_commit_weights_on; raises if a parameter lives elsewhere),
+        # "host" = every tensor is copied to the CPU and packed there (fsnp_set_weight / fsnp_commit_weights), "auto" = per tensor
+        # whatever its device allows.  The blob is byte-identical either way (profiles/device_weights.md has the timings).
+        self.weight_upload = "auto"
         # fsnp_set_verify_sample: every Nth forward of a small batch (a plan of column-split launches only) has one row tile recomputed on
         # an exchange-free kernel beside the following forwards.  None = the policy's default: 16 under error_check="sync", off under
         # "deferred" (throughput loops decide for themselves); an int = that value whatever the policy
@@ -377,7 +382,11 @@ class _HipModel(nn.Module):
             if self.__dict__.get("_verify_every"):
                 _lib.check(lib.fsnp_set_verify(hp, int(self.__dict__["_verify_every"])), "fsnp_set_verify")
         key = self._weights_key()
-        if key != st.packed_key:
+        if key != st.packed_key and self.weight_upload != "host":
+            self._upload_weights(lib, device)
+            self._watch_parameters(lib, device)
+            st.packed_key = self._weights_key()
+        elif key != st.packed_key:
             for name, tensor in self.state_dict().items():
                 t = tensor.detach().to("cpu", torch.float32).contiguous()
                 _lib.check(lib.fsnp_set_weight(st.handle, name.encode(), t.data_ptr(), t.numel()),
@@ -387,6 +396,39 @@ class _HipModel(nn.Module):
             self._watch_parameters(lib, device)
             st.packed_key = self._weights_key()
         return lib
+
+    def _upload_plan(self, device):
+        """[(name, tensor, "host" | "device")] over state_dict(): which setter each tensor goes through under self.weight_upload."""
+        mode = self.weight_upload
+        if mode not in ("auto", "host", "device"):
+            raise ValueError(f"weight_upload must be \"auto\", \"host\" or \"device\", got {mode!r}")
+        plan = []
+        for name, tensor in self.state_dict().items():
+            on_dev = mode != "host" and tensor.device == device
+            if mode == "device" and not on_dev:
+                raise RuntimeError(f"weight_upload=\"device\": {name} is on {tensor.device}, not on {device}")
+            plan.append((name, tensor, "device" if on_dev else "host"))
+        return plan
+
+    def _upload_weights(self, lib, device):
+        """The re-pack of weight_upload "auto" / "device": tensors on the handle's device go to fsnp_set_weight_device on the current
+        stream (converted there first if they are not contiguous fp32; the library copies them into its own arena in stream order, so
+        a temporary may be released right away), the others to fsnp_set_weight; fsnp_commit_weights_on then packs on the device
+        when every tensor came that way, else on the host."""
+        st = self._hip
+        stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        with torch.cuda.device(device):
+            for name, tensor, where in self._upload_plan(device):
+                if where == "device":
+                    t = tensor.detach()
+                    if t.dtype != torch.float32 or not t.is_contiguous():
+                        t = t.to(torch.float32).contiguous()
+                    _lib.check(lib.fsnp_set_weight_device(st.handle, name.encode(), t.data_ptr(), t.numel(), stream),
+                               f"fsnp_set_weight_device({name})")
+                else:
+                    t = tensor.detach().to("cpu", torch.float32).contiguous()
+                    _lib.check(lib.fsnp_set_weight(st.handle, name.encode(), t.data_ptr(), t.numel()), f"fsnp_set_weight({name})")
+            _lib.check(lib.fsnp_commit_weights_on(st.handle, stream), "fsnp_commit_weights_on")
 
     def _watch_parameters(self, lib, device):
         """fsnp_watch_weights over the parameters' own storage - possible when every parameter is contiguous fp32 on the handle's

@@ -311,4 +311,5 @@ int32_t fsnp_config_size(void);
 #include "fsnp_wave_stream.h" /* the same for waveforms: samples in, samples out at a fixed delay */
 #include "fsnp_stream_live.h" /* live sessions: a few slots fed one hop at a time, on per-step kernels that fill the chip */
 #include "fsnp_spec_stream.h" /* spectrum sessions: STFT frames in, enhanced STFT frames out (the caller owns the STFT) */
+#include "fsnp_device_weights.h" /* weights handed over in device memory and packed on the GPU */
 #endif /* FSNP_H */

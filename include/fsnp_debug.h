@@ -222,6 +222,26 @@ int fsnp_debug_box_probe(double target_ms, double out[FSNP_BOX_PROBE_VALUES], vo
 #define FSNP_LAUNCH_CLOCK_VALUES 7
 int fsnp_debug_launch_clock(fsnp_handle* h, double out[FSNP_LAUNCH_CLOCK_VALUES]);
 
+/* Device-side weight hand-over (fsnp_device_weights.h).
+ * fsnp_debug_weight_blob: the packed device blob of a committed handle -> host_dst (host memory of `bytes` bytes); *needed = its size
+ * in bytes (host_dst = NULL only asks for the size).  Synchronises the device.  fsnp_debug_weight_blob_ptr: its device address.
+ * fsnp_debug_commit_stats: the last commit - out[0] = path (0 host, 1 device), out[1] = bytes copied host to device, out[2] = bytes
+ * copied device to host, out[3] = pack kernels launched.
+ * fsnp_debug_pack_emulate: one weight image built on the HOST by the functions the device kernels run (csrc/weight_layouts.h), so a
+ * layout can be checked without a GPU.  kind = the image (PackKind in csrc/weight_layouts.h: 0 row-tile, 1 row-tile bf16-ih, 2 half-tile,
+ * 3 half-tile bf16-ih, 4 GRU, 5 K-split, 6 three-way split, 7 half-tile ping-pong, 8 its wave-owned kernel, 9 wave-owned column split,
+ * 10 full-band VALU, 11 runtime-sized transposed, 12 summed biases, 13 four-slot spread, 14 zero-padded matrix / plain copy,
+ * 15 transpose, 16 GroupNorm fold of the weights, 17 its per-row constants); sizes = up to 5 ints as listed there (recurrent kinds:
+ * hidden, inputs, KX, waves / units / matrix, gru); sources = the reference's tensors (recurrent kinds: weight_ih_l0, weight_hh_l0,
+ * weight_ih_l1, weight_hh_l1, bias_ih_l0, bias_hh_l0, bias_ih_l1, bias_hh_l1 - 3 gate blocks each when gru = 1; 14 / 15: the matrix;
+ * 16: W, gamma; 17: W, gamma, beta, bias) with numels[i] elements each.  Code 2: sizes the layout cannot take / out_floats is not the
+ * image's size (the message names it); code 3: the layout names a source offset outside its tensor. */
+int fsnp_debug_weight_blob(fsnp_handle* h, void* host_dst, int64_t bytes, int64_t* needed);
+const void* fsnp_debug_weight_blob_ptr(const fsnp_handle* h);
+int fsnp_debug_commit_stats(const fsnp_handle* h, int64_t out[4]);
+int fsnp_debug_pack_emulate(int32_t kind, const int32_t* sizes, int32_t num_sizes, const float* const* sources, const int64_t* numels,
+                            int32_t num_sources, float* out, int64_t out_floats);
+
 #ifdef __cplusplus
 }
 #endif
