@@ -90,6 +90,47 @@ def rel_err(a, b):
     return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
 
 
+# ------------------------------------------------------------------------------------------------ stage-level comparison
+STAGE_TAGS = ("att_mag", "att_real", "att_imag", "fb_mag", "fb_real", "fb_imag")
+STAGE_CAPS = {"att": 2e-5, "fb": 2e-4}       # what the suite already asserts at these stages (test_stages_vs_reference, the submodule test)
+
+
+def plane_errs(got, want):
+    """got, want [B, F, T'] -> (errs, where): errs[b] = max|got[b] - want[b]| / max|want[b]| over utterance b's OWN plane (a quiet clip
+    cannot hide behind a loud one of the same batch), where[b] = (bin, frame) of its worst element.  A non-finite element of `got` is
+    an infinite error at that element."""
+    got = np.asarray(got, dtype=np.float64)
+    want = np.asarray(want, dtype=np.float64)
+    assert got.shape == want.shape and got.ndim == 3, (got.shape, want.shape)
+    errs, where = [], []
+    for g, w in zip(got, want):
+        d = np.abs(g - w)
+        d[~np.isfinite(d)] = np.inf
+        k = int(np.argmax(d))
+        errs.append(float(d.flat[k] / max(np.abs(w).max(), 1e-30)))
+        where.append(tuple(int(i) for i in np.unravel_index(k, d.shape)))
+    return errs, where
+
+
+@torch.no_grad()
+def oracle_stages(sd, ins, args, dtype=torch.float64):
+    """The attention and full-band stages of fsnp_torch.forward alone (no sub-band model), evaluated in `dtype` with the state dict and
+    the inputs cast to it: ins = (mag, real, imag) [B, 1, F, T] -> {tag: [B, F, T + look_ahead]} for the tags of STAGE_TAGS."""
+    from oracle import fsnp_torch
+    assert args.get("subband_num", 1) == 1
+    p = {k: v.to(dtype) for k, v in sd.items() if k.startswith(("channel_attention", "fb_model"))}
+    kind, la = args.get("channel_attention_model", "TSSE"), args["look_ahead"]
+    out = {}
+    for tag, x in zip(("mag", "real", "imag"), ins):
+        x = torch.nn.functional.pad(x.to(dtype), [0, la])
+        B, _, F, T = x.shape
+        sfx = "" if tag == "mag" else "_" + tag
+        att = fsnp_torch.attention(fsnp_torch.NORMS[args["norm_type"]](x).reshape(B, F, T), p, "channel_attention" + sfx, kind)
+        out["att_" + tag] = att
+        out["fb_" + tag] = fsnp_torch.fb_sequence_model(att, p, "fb_model" + sfx, args["fb_output_activate_function"])
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ clips of different lengths
 def edge_lengths(T, look_ahead, min_len, edges=(8, 32, 64, 128, 256), extra=()):
     """Clip lengths L (frames) that put L + look_ahead - the frames a clip's per-utterance reductions end at - one below, at and one
