@@ -18,7 +18,8 @@ HEADERS = [os.path.join(CSRC, "fsnp_common.h"), os.path.join(CSRC, "lstm_common.
            os.path.join(os.path.dirname(HERE), "include", "fsnp.h"), os.path.join(os.path.dirname(HERE), "include", "fsnp_debug.h"),
            os.path.join(os.path.dirname(HERE), "include", "fsnp_lengths.h"), os.path.join(os.path.dirname(HERE), "include", "fsnp_stream.h"),
            os.path.join(os.path.dirname(HERE), "include", "fsnp_wave_stream.h"), os.path.join(os.path.dirname(HERE), "include", "fsnp_stream_live.h"),
-           os.path.join(os.path.dirname(HERE), "include", "fsnp_spec_stream.h"), os.path.join(os.path.dirname(HERE), "include", "fsnp_device_weights.h")]
+           os.path.join(os.path.dirname(HERE), "include", "fsnp_spec_stream.h"), os.path.join(os.path.dirname(HERE), "include", "fsnp_device_weights.h"),
+           os.path.join(os.path.dirname(HERE), "include", "fsnp_stft_geometry.h")]
 # -fno-slp-vectorize: the SLP pass pairs the LSTM kernel's per-tile VALU FMAs across tiles, which breaks the
 # refill-in-place weight pipeline and makes hipcc drain vmcnt(0) + copy 48 registers every k-group
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-fPIC"]

@@ -168,6 +168,12 @@ DEVICE_WEIGHTS_SYMBOLS = {
     "fsnp_commit_weights_on": (c_i32, [c_vp, c_vp]),
 }
 
+# every symbol include/fsnp_stft_geometry.h declares (the hop length of the waveform path; same ABI version)
+STFT_GEOMETRY_SYMBOLS = {
+    "fsnp_set_hop_length": (c_i32, [c_vp, c_i32]),
+    "fsnp_hop_length": (c_i32, [c_vp]),
+}
+
 ABI_VERSION = 13         # FSNP_ABI_VERSION of the include/fsnp.h these signatures were written against
 
 _lib = None
@@ -190,7 +196,8 @@ def load(build_if_missing=True):
         raise RuntimeError(f"{path} is missing: run `python -m fullsubnet_plus_amd._build`")
     lib = ctypes.CDLL(path)
     for name, (res, args) in (list(SYMBOLS.items()) + list(LENGTHS_SYMBOLS.items()) + list(STREAM_SYMBOLS.items()) + list(WAVE_STREAM_SYMBOLS.items())
-                              + list(LIVE_STREAM_SYMBOLS.items()) + list(SPEC_STREAM_SYMBOLS.items()) + list(DEVICE_WEIGHTS_SYMBOLS.items())):
+                              + list(LIVE_STREAM_SYMBOLS.items()) + list(SPEC_STREAM_SYMBOLS.items()) + list(DEVICE_WEIGHTS_SYMBOLS.items())
+                              + list(STFT_GEOMETRY_SYMBOLS.items())):
         fn = getattr(lib, name)          # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

@@ -1275,6 +1275,7 @@ int64_t fsnp_dump_config(const fsnp_handle* h, char* buf, int64_t cap) {
     add("model=%s num_freqs=%d look_ahead=%d sb_hidden=%d tcn_hidden=%d sub-band inputs=%d (kernels instantiated for K=%d) sequence_model=%s norm_type=%d attention=%d subband_num=%d\n",
         h->model == FSNP_MODEL_FULLSUBNET ? "FullSubNet" : "FullSubNet+", h->F, h->cfg.look_ahead, h->H, h->CH, h->NIN, h->KX,
         h->sb_tcn ? "TCN" : h->gru ? "GRU" : "LSTM", h->cfg.norm_type, h->cfg.attention, h->cfg.subband_num > 0 ? h->cfg.subband_num : 1);
+    add("waveform path: n_fft=%d hop_length=%d (win_length = n_fft, periodic Hann; fsnp_set_hop_length)\n", 2 * (h->F - 1), (int)fsnp_hop_length(h));
     add("weights committed=%d precision=%d (0 fp32, 1 bf16 ih-GEMM) pipeline=%d timing=%d workspace=%zu bytes x %d\n",
         (int)h->committed, h->ih_bf16, h->pipeline, (int)h->timing, h->ws_bytes, h->ws_slots);
     add("effective settings (environment variable as read at fsnp_create = value in force):\n");

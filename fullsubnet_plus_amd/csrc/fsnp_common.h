@@ -188,14 +188,14 @@ void launch_tcn(const Dims& d, int fb_act, const TcnWeights& w, const TcnBuffers
 void launch_linear_act(const float* A, int lda, const float* W, int ldw, const float* bias, float* C, int ldc, int K,
                        int N, int B, int Tp, int act, int num_cus, hipStream_t s, long a_utt_stride = 0, int a_cols = 0);
 // stft.hip : SURVEY.md 8(f-3) second half - torch.stft / torch.istft of audio_zen/acoustics/feature.py:10-56 as
-// reflect-pad + DFT GEMM and inverse-DFT GEMM + windowed overlap-add (n_fft = win_length, hop = n_fft / 2, hann)
+// reflect-pad + DFT GEMM and inverse-DFT GEMM + windowed overlap-add (n_fft = win_length, n_fft / 8 <= hop <= n_fft / 2, hann)
 void launch_stft_pad(const float* wav, long wav_stride, float* xp, long xp_stride, int B, int L, int n_fft, hipStream_t s);
-void launch_istft_ola(const float* frames, const float* window, float* wav, long wav_stride, int B, int T, int L, int n_fft,
+void launch_istft_ola(const float* frames, const float* window, float* wav, long wav_stride, int B, int T, int L, int n_fft, int hop,
                       hipStream_t s);
 // the same per row of a batch of clips of different lengths: samples[b] host values (kernel arguments, up to 256 rows per launch)
 void launch_stft_pad_lengths(const float* wav, long wav_stride, float* xp, long xp_stride, int B, const int* samples, int n_fft, hipStream_t s);
 void launch_istft_ola_lengths(const float* frames, const float* window, float* wav, long wav_stride, int B, int T, int L, const int* samples,
-                              int n_fft, hipStream_t s);
+                              int n_fft, int hop, hipStream_t s);
 // spec_stream.hip : the look-ahead ring and the two short launches around one mag push that a spectrum session (include/fsnp_spec_stream.h)
 // and a wave session (include/fsnp_wave_stream.h) share.  Per slot a ring complex64 [look_ahead][F]: the noisy spectra of the newest
 // look_ahead frames, frame g in row g % look_ahead (they wait for their masks: the mask of frame t is the model's output of step
@@ -214,45 +214,53 @@ void launch_spec_mag(const SpecArgs& a, const SlotCounts& c, const float* spec, 
 void launch_spec_apply(const SpecArgs& a, const SlotCounts& c, const float* mask, const float* spec, const int64_t strides[3], float* out,
                        const int64_t out_strides[3], hipStream_t s);
 // stft_stream.hip : waveform sessions (include/fsnp_wave_stream.h) - the streaming halves of the two transforms around one ring push.
-// Per slot a wave record [ carry fp32 [n_fft + 1] | ring complex64 [look_ahead][F] | tail fp32 [hop] | fifo fp32 [hop] | samples int64 ]:
+// Two lengths that coincide only in the default geometry are kept apart: `hop`, the distance between frames, and `half` = n_fft / 2,
+// the reflect padding and the distance from a frame's start to its centre (frame t covers samples [t hop - half, t hop + half)).
+// Per slot a wave record [ carry fp32 [n_fft + 1] | ring complex64 [look_ahead][F] | tail fp32 [n_fft - hop] | fifo fp32 [hop] | samples int64 ]:
 //   carry  the newest n_fft + 1 input samples, carry[i] = sample P - (n_fft + 1) + i (0 before the clip's start)
 //   ring   the look-ahead ring of spec_stream.hip (the kernels here never touch it)
-//   tail   the second half of the newest enhanced frame (already windowed by the inverse DFT matrix)
+//   tail   the partial overlap-add sums behind the finished samples: with e enhanced frames, tail[q] = the sum over those frames of their
+//          (already windowed) values at sample e hop - half + q; at hop = half that is the second half of the newest enhanced frame
 //   fifo   finished output samples that have not been emitted yet, fifo[q] = sample max(P - D, 0) + q, 0 behind them
 struct WaveMeta { long long p; int c, fin; };      // samples the slot had before this call, samples it gets now, 1 = it is finished now
 struct WaveArgs {
     unsigned char* state;                          // wave record of slot 0
     size_t stride, o_tail, o_fifo, o_count;        // bytes between slots, byte offsets inside a record (the carry is at 0)
     WaveMeta* meta;                                // [S], written by the gather kernel for the overlap-add behind it
-    int S, hop, LA, nrow;                          // nrow: frame rows per slot in every per-frame buffer of this call
+    int S, hop, half, LA, nrow;                    // nrow: frame rows per slot in every per-frame buffer of this call
+    int xl;                                        // floats between the gathered frame rows (n_fft padded to a float4)
 };
-// what a call does to a slot, from {P, c, fin} alone.  Frame t is complete once (t + 1) hop samples have arrived (frame 0: hop + 1, it
-// reflects wav[1 .. hop]); the mask of frame t is the model's output of step t + look_ahead; finish adds the clip's last frame and steps
-// the model through look_ahead zero frames.  The mag session inside gets km frames per call, so its frame count is nf.
+// what a call does to a slot, from {P, c, fin} alone.  Frame t is complete once t hop + half samples have arrived (frame 0: half + 1, it
+// reflects wav[1 .. half]), so P samples hold nf(P) = P <= half ? 0 : (P - half) / hop + 1 frames; the mask of frame t is the model's
+// output of step t + look_ahead; finish adds the clip's last 1 + L / hop - nf(L) <= ceil(half / hop) frames, each reflected at the clip's
+// end, and steps the model through look_ahead zero frames.  The mag session inside gets km frames per call, so its frame count is nf.
 struct WaveStep {
     long long nf;      // frames the slot had before this call (= steps of the model so far)
     long long e_old;   // enhanced frames it had: max(nf - look_ahead, 0)
-    int ks, km;        // new spectra, new model steps (km = ks, finish: 1 and 1 + look_ahead)
+    int ks, km;        // new spectra, new model steps (km = ks, finish: ks + look_ahead)
     int j0, ke;        // first step of this call that has a frame (step j is frame nf + j - look_ahead), enhanced frames of this call
 };
-__host__ __device__ inline WaveStep wave_step(long long P, int c, int fin, int hop, int LA) {
+__host__ __device__ inline long long wave_frames(long long P, int hop, int half) { return P <= half ? 0 : (P - half) / hop + 1; }
+__host__ __device__ inline WaveStep wave_step(long long P, int c, int fin, int hop, int half, int LA) {
     WaveStep w;
-    w.nf = P <= hop ? 0 : P / hop;
-    if (fin) { w.ks = 1; w.km = 1 + LA; }
-    else { const long long pn = P + c; w.ks = (int)((pn <= hop ? 0 : pn / hop) - w.nf); w.km = w.ks; }
+    w.nf = wave_frames(P, hop, half);
+    if (fin) { w.ks = (int)(1 + P / hop - w.nf); w.km = w.ks + LA; }
+    else { w.ks = (int)(wave_frames(P + c, hop, half) - w.nf); w.km = w.ks; }
     w.j0 = w.nf < LA ? (int)(LA - w.nf) : 0;
     w.ke = w.km > w.j0 ? w.km - w.j0 : 0;
     w.e_old = w.nf > LA ? w.nf - LA : 0;
     return w;
 }
-// c.v[slot]: samples of a push, or (fin) 1 = finish this slot.  Frame rows xfr [S][nrow][n_fft] of the newly complete frames (zeros
-// behind them), the carry and the sample count advanced, meta written
+// most frame rows one finish can need per slot
+inline int wave_finish_rows(int hop, int half, int LA) { return (half + hop - 1) / hop + LA; }
+// c.v[slot]: samples of a push, or (fin) 1 = finish this slot.  Frame rows xfr [S][nrow][xl] of the newly complete frames (zeros
+// behind them; the pad columns past n_fft are never written), the carry and the sample count advanced, meta written
 void launch_wave_gather(const WaveArgs& a, const SlotCounts& c, int fin, const float* wav, long wav_stride, float* xfr, hipStream_t s);
 // overlap-add with the window-envelope division over the frames fr [S][nrow][n_fft] (row j = the frame of step j of this call), into the
 // fifo and out [S][ncols]: column j is sample P + j - D (finish: L - D + j), exactly 0 where that is negative and past the slot's count
 // (finish: in rows not finished)
 void launch_wave_ola(const WaveArgs& a, const float* fr, const float* window, float* out, long out_stride, int ncols, hipStream_t s);
-void stft_build_matrices(int n_fft, float* fwd /*[N2 pad 384][n_fft]*/, float* inv /*[n_fft pad 384][K pad 16]*/,
+void stft_build_matrices(int n_fft, float* fwd /*[N2 pad 384][n_fft pad 16]*/, float* inv /*[n_fft pad 384][K pad 16]*/,
                          float* window /*[n_fft]*/);
 
 // ---------------------------------------------------------------------------------------------

@@ -143,7 +143,8 @@ struct fsnp_handle {
     int lstm_waves = 0;   // 0 = auto: 12 waves when the tile plan uses VALU rows, else 4
 
     // STFT / iSTFT around the model (stft.hip): DFT GEMM operands, built on first use, and an I/O workspace
-    float* d_stft = nullptr;     // [fwd (2F pad 384) x n_fft][inv (n_fft pad 384) x (2F pad 16)][window n_fft][zero bias 768]
+    float* d_stft = nullptr;     // [fwd (2F pad 384) x (n_fft pad 16)][inv (n_fft pad 384) x (2F pad 16)][window n_fft][zero bias]
+    int hop_length = 0;          // fsnp_set_hop_length (include/fsnp_stft_geometry.h); 0 = never set: n_fft / 2
     unsigned char* io = nullptr;
     size_t io_bytes = 0;
 
@@ -240,12 +241,18 @@ int verify_pass(fsnp_handle* h, const SbPlan& plan, const Dims& d, int mode, int
 bool plan_can_be_sampled(const fsnp_handle* h, const SbPlan& plan);
 int verify_sample(fsnp_handle* h, const SbPlan& plan, const Dims& d, const LstmArgs& a, const SubbandBuffers& sbuf, hipStream_t st);
 // fsnp_stft_abi.hip
+// The geometry rules (include/fsnp_stft_geometry.h): n_fft = 2 (F - 1), periodic Hann of n_fft, n_fft / 8 <= hop <= n_fft / 2, hop % 4 == 0
+// (frame row t of the forward DFT GEMM starts at float t * hop of the padded signal and is read as float4).  `half` = n_fft / 2 is the
+// reflect padding and the distance from a frame's start to its centre; it is the hop only in the default geometry.
 struct StftPlan {
-    int n_fft, hop, F, N2, sp;          // sp = padded float stride of one internal spectrum row (multiple of 4)
+    int n_fft, hop, half, F, N2, sp;    // sp = padded float stride of one internal spectrum row (multiple of 4)
     size_t o_fwd, o_inv, o_win, o_zero, total;   // float offsets inside d_stft
-    int inv_ld;
+    int fwd_ld, inv_ld;                 // row strides of the two DFT matrices: n_fft and 2F padded to the GEMM's k-tile (16)
+    int xl;                             // row stride of a wave session's gathered frames: n_fft padded to a float4
 };
 StftPlan stft_plan(const fsnp_handle* h);
+// 0, or 2 with the error set: the rule `hop` breaks for a handle of F bins.  Host arithmetic only.
+int check_hop_length(int F, int hop, const char* where);
 int ensure_stft(fsnp_handle* h);
 int ensure_io(fsnp_handle* h, size_t bytes, hipStream_t s);
 // ---- stream, wave and spectrum sessions (fsnp_stream_abi.hip, fsnp_wave_stream_abi.hip, fsnp_spec_stream_abi.hip) ----

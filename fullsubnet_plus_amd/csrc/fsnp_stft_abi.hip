@@ -9,18 +9,35 @@
 namespace fsnp {
 StftPlan stft_plan(const fsnp_handle* h) {
     StftPlan p{};
-    p.F = h->F; p.n_fft = 2 * (h->F - 1); p.hop = p.n_fft / 2; p.N2 = 2 * p.F; p.sp = (int)align_up(p.N2, 4);
-    p.inv_ld = (int)align_up(p.N2, 16);
+    p.F = h->F; p.n_fft = 2 * (h->F - 1); p.half = p.n_fft / 2; p.hop = h->hop_length ? h->hop_length : p.half;
+    p.N2 = 2 * p.F; p.sp = (int)align_up(p.N2, 4);
+    p.fwd_ld = (int)align_up(p.n_fft, 16); p.inv_ld = (int)align_up(p.N2, 16); p.xl = (int)align_up(p.n_fft, 4);
     p.o_fwd = 0;
-    p.o_inv = p.o_fwd + align_up(p.N2, 384) * (size_t)p.n_fft;
+    p.o_inv = p.o_fwd + align_up(p.N2, 384) * (size_t)p.fwd_ld;
     p.o_win = p.o_inv + align_up(p.n_fft, 384) * (size_t)p.inv_ld;
     p.o_zero = p.o_win + align_up(p.n_fft, 64);
     p.total = p.o_zero + align_up(p.N2 > p.n_fft ? p.N2 : p.n_fft, 384);
     return p;
 }
+// the rules of include/fsnp_stft_geometry.h
+int check_hop_length(int F, int hop, const char* where) {
+    const int n_fft = 2 * (F - 1);
+    if (F < 3) { set_error("%s: the waveform path needs num_freqs >= 3 (n_fft = 2 (num_freqs - 1)); this handle: %d", where, F); return 2; }
+    if (hop <= 0 || 2L * hop > n_fft || 8L * hop < n_fft) {
+        set_error("%s: hop_length %d outside [n_fft / 8, n_fft / 2] = [%d, %d] (n_fft = 2 (num_freqs - 1) = %d): above it frames no longer "
+                  "cover the clip's tail, below it is outside what the waveform path is built for", where, hop, (n_fft + 7) / 8, n_fft / 2, n_fft);
+        return 2;
+    }
+    if (hop % 4) {
+        set_error("%s: hop_length %d is not a multiple of 4: the forward DFT GEMM reads frame t at float t * hop_length of the padded signal "
+                  "as 16-byte vectors", where, hop);
+        return 2;
+    }
+    return 0;
+}
 int ensure_stft(fsnp_handle* h) {
+    if (check_hop_length(h->F, stft_plan(h).hop, "STFT")) return 2;       // (the default hop of a num_freqs - 1 that is no multiple of 4)
     if (h->d_stft) return 0;
-    if (h->F < 3 || ((h->F - 1) & (h->F - 2)) != 0) { set_error("STFT: num_freqs - 1 must be a power of two (n_fft = 2 (num_freqs - 1))"); return 2; }
     const StftPlan p = stft_plan(h);
     std::vector<float> host(p.total, 0.0f);
     stft_build_matrices(p.n_fft, host.data() + p.o_fwd, host.data() + p.o_inv, host.data() + p.o_win);
@@ -51,7 +68,7 @@ static void stft_into(fsnp_handle* h, const StftPlan& p, const float* wav, long 
                       int ldc, int B, int L, hipStream_t s) {
     const int T = 1 + L / p.hop;
     launch_stft_pad(wav, wav_stride, xp, xs, B, L, p.n_fft, s);
-    launch_linear_act(xp, p.hop, h->d_stft + p.o_fwd, p.n_fft, h->d_stft + p.o_zero, spec, ldc, p.n_fft, p.N2, B, T,
+    launch_linear_act(xp, p.hop, h->d_stft + p.o_fwd, p.fwd_ld, h->d_stft + p.o_zero, spec, ldc, p.n_fft, p.N2, B, T,
                       FSNP_ACT_NONE, h->num_cus, s, xs, p.n_fft);
 }
 // spectrum rows [B][T][sp] -> wav [B][L]
@@ -59,7 +76,7 @@ static void istft_from(fsnp_handle* h, const StftPlan& p, const float* spec, flo
                        int T, int L, hipStream_t s) {
     launch_linear_act(spec, p.sp, h->d_stft + p.o_inv, p.inv_ld, h->d_stft + p.o_zero, frames, p.n_fft, p.N2, p.n_fft, B, T,
                       FSNP_ACT_NONE, h->num_cus, s, (long)T * p.sp, p.N2);
-    launch_istft_ola(frames, h->d_stft + p.o_win, wav, wav_stride, B, T, L, p.n_fft, s);
+    launch_istft_ola(frames, h->d_stft + p.o_win, wav, wav_stride, B, T, L, p.n_fft, p.hop, s);
 }
 }  // namespace fsnp
 
@@ -70,7 +87,7 @@ int fsnp_stft(fsnp_handle* h, const float* wav, int64_t wav_stride, float* spec,
     if (batch <= 0) { set_error("fsnp_stft: empty input"); return 2; }
     if (ensure_stft(h)) return 2;
     const StftPlan p = stft_plan(h);
-    if (samples <= p.hop) { set_error("fsnp_stft: need more than n_fft/2 = %d samples (reflect padding)", p.hop); return 2; }
+    if (samples <= p.half) { set_error("fsnp_stft: need more than n_fft/2 = %d samples (reflect padding)", p.half); return 2; }
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     FSNP_ON_DEVICE(h);
     const long xs = (long)align_up((size_t)samples + p.n_fft, 4);
@@ -87,7 +104,7 @@ int fsnp_istft(fsnp_handle* h, const float* spec, const int64_t strides[3], floa
     if (batch <= 0 || frames <= 0 || samples <= 0) { set_error("fsnp_istft: empty input"); return 2; }
     if (ensure_stft(h)) return 2;
     const StftPlan p = stft_plan(h);
-    if ((long)(frames - 1) * p.hop + p.n_fft < (long)samples + p.hop) { set_error("fsnp_istft: %d frames do not cover %d samples", frames, samples); return 2; }
+    if ((long)(frames - 1) * p.hop + p.n_fft < (long)samples + p.half) { set_error("fsnp_istft: %d frames do not cover %d samples", frames, samples); return 2; }
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     FSNP_ON_DEVICE(h);
     const size_t spec_b = align_up((size_t)batch * frames * p.sp * 4 + 256, 256), fr_b = (size_t)batch * frames * p.n_fft * 4;
@@ -113,7 +130,7 @@ int fsnp_enhance_wave(fsnp_handle* h, const float* wav, int64_t wav_stride, floa
     if (h->cfg.output_size != 2) { set_error("fsnp_enhance_wave: the cIRM epilogue needs output_size = 2 (this handle: %d)", h->cfg.output_size); return 2; }
     if (ensure_stft(h)) return 2;
     const StftPlan p = stft_plan(h);
-    if (samples <= p.hop) { set_error("fsnp_enhance_wave: need more than n_fft/2 = %d samples (reflect padding)", p.hop); return 2; }
+    if (samples <= p.half) { set_error("fsnp_enhance_wave: need more than n_fft/2 = %d samples (reflect padding)", p.half); return 2; }
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     FSNP_ON_DEVICE(h);
     const int T = 1 + samples / p.hop;
@@ -151,13 +168,13 @@ int fsnp_enhance_wave_lengths(fsnp_handle* h, const float* wav, int64_t wav_stri
     if (h->cfg.output_size != 2) { set_error("fsnp_enhance_wave_lengths: the cIRM epilogue needs output_size = 2 (this handle: %d)", h->cfg.output_size); return 2; }
     if (ensure_stft(h)) return 2;
     const StftPlan p = stft_plan(h);
-    if (max_samples <= p.hop) { set_error("fsnp_enhance_wave_lengths: need more than n_fft/2 = %d samples (reflect padding)", p.hop); return 2; }
+    if (max_samples <= p.half) { set_error("fsnp_enhance_wave_lengths: need more than n_fft/2 = %d samples (reflect padding)", p.half); return 2; }
     // every check of the forward too, before anything is enqueued: each clip's frame count is its own STFT's, T_b = 1 + samples[b] / hop
     const int T = 1 + max_samples / p.hop;
     std::vector<int32_t> frames(batch);
     for (int b = 0; b < batch; ++b) {
-        if (samples[b] <= p.hop || samples[b] > max_samples) {
-            set_error("fsnp_enhance_wave_lengths: utterance %d: %d samples outside (n_fft/2 = %d, %d]", b, (int)samples[b], p.hop, max_samples);
+        if (samples[b] <= p.half || samples[b] > max_samples) {
+            set_error("fsnp_enhance_wave_lengths: utterance %d: %d samples outside (n_fft/2 = %d, %d]", b, (int)samples[b], p.half, max_samples);
             return 2;
         }
         frames[b] = 1 + samples[b] / p.hop;
@@ -177,7 +194,7 @@ int fsnp_enhance_wave_lengths(fsnp_handle* h, const float* wav, int64_t wav_stri
     float* fr = reinterpret_cast<float*>(h->io + xp_b + 2 * spec_b + mask_b);
     // as fsnp_enhance_wave, with the reflect padding at each clip's end (frames past T_b see zeros: the forward never reads them)
     launch_stft_pad_lengths(wav, wav_stride, xp, xs, batch, samples, p.n_fft, s);
-    launch_linear_act(xp, p.hop, h->d_stft + p.o_fwd, p.n_fft, h->d_stft + p.o_zero, noisy, p.sp, p.n_fft, p.N2, batch, T,
+    launch_linear_act(xp, p.hop, h->d_stft + p.o_fwd, p.fwd_ld, h->d_stft + p.o_zero, noisy, p.sp, p.n_fft, p.N2, batch, T,
                       FSNP_ACT_NONE, h->num_cus, s, xs, p.n_fft);
     const int64_t cst[3] = {(int64_t)T * (p.sp / 2), 1, p.sp / 2};
     const int rc = fsnp_forward_complex_lengths(h, noisy, cst, frames.data(), mask, batch, T, hip_stream);
@@ -187,9 +204,19 @@ int fsnp_enhance_wave_lengths(fsnp_handle* h, const float* wav, int64_t wav_stri
     launch_apply_cirm_lengths(mask, noisy, cst, enh, cst, batch, p.F, T, frames.data(), s);      // frames >= T_b: 0
     launch_linear_act(enh, p.sp, h->d_stft + p.o_inv, p.inv_ld, h->d_stft + p.o_zero, fr, p.n_fft, p.N2, p.n_fft, batch, T,
                       FSNP_ACT_NONE, h->num_cus, s, (long)T * p.sp, p.N2);
-    launch_istft_ola_lengths(fr, h->d_stft + p.o_win, out, out_stride, batch, T, max_samples, samples, p.n_fft, s);
+    launch_istft_ola_lengths(fr, h->d_stft + p.o_win, out, out_stride, batch, T, max_samples, samples, p.n_fft, p.hop, s);
     FSNP_HIP_CHECK(hipGetLastError());
     return mark_forward_done(h, s);
 }
+
+// ---------------------------------------------------------------------------------------------- include/fsnp_stft_geometry.h
+int fsnp_set_hop_length(fsnp_handle* h, int32_t hop_length) {
+    if (!h) { set_error("fsnp_set_hop_length: null handle"); return 1; }
+    if (const int rc = check_hop_length(h->F, hop_length, "fsnp_set_hop_length")) return rc;
+    h->hop_length = hop_length;
+    return 0;
+}
+
+int32_t fsnp_hop_length(const fsnp_handle* h) { return h ? stft_plan(h).hop : 0; }
 
 }  // extern "C"

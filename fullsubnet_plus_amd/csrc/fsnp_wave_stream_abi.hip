@@ -1,7 +1,7 @@
 // fsnp_wave_stream_abi.hip - include/fsnp_wave_stream.h: waveform sessions of the original FullSubNet (samples in, samples out).
 //
 // A wave session is a spectrum session between two transforms.  It holds a mag-stream session (fsnp_stream_abi.hip) of
-// max_samples / hop + 1 frames per push with, per slot, a wave record behind the mag-stream record (layout: fsnp_common.h, WaveArgs;
+// max(max_samples / hop + 1, ceil(n_fft / (2 hop)) + look_ahead) frames per call with, per slot, a wave record behind the mag-stream record (layout: fsnp_common.h, WaveArgs;
 // the look-ahead ring lies inside it) and a workspace of its own, allocated and zeroed at creation.  One push on the caller's stream,
 // nothing allocated, nothing synchronised:
 //   wave_gather_kernel   the rows of the newly complete frames from the carried samples + the new ones, the carry and the count advanced
@@ -11,8 +11,9 @@
 //                        none), ring advanced
 //   launch_linear_act    inverse DFT -> windowed frames
 //   wave_ola_kernel      overlap-add + envelope division into the fifo, this push's c samples out (zeros before D and past c)
-// fsnp_wave_stream_finish runs the same chain with the clip's last frame (reflected at the end) and look_ahead zero frames into the model
-// (one spectrum, 1 + look_ahead steps), emits the remaining D samples and resets the slots.  The host mirrors every slot's sample count,
+// fsnp_wave_stream_finish runs the same chain with the clip's last frames (1 + L / hop - nf(L) <= ceil(n_fft / (2 hop)) of them, each
+// reflected at the end) and look_ahead zero frames into the model, emits the remaining D samples and resets the slots.  The session keeps
+// the hop its handle had at creation (include/fsnp_stft_geometry.h).  The host mirrors every slot's sample count,
 // so frames per slot are known without asking the device.
 #include <algorithm>
 #include <vector>
@@ -22,7 +23,7 @@
 struct fsnp_wave_stream {
     fsnp_handle* h = nullptr;
     fsnp_stream* mag = nullptr;       // the model's state and its push
-    int S = 0, max_samples = 0, NF = 0, hop = 0, LA = 0, D = 0;
+    int S = 0, max_samples = 0, NF = 0, hop = 0, half = 0, LA = 0, D = 0;
     StftPlan p{};
     size_t mag_bytes = 0;             // one slot's mag-stream record
     SlotRecords rec;                  // the slots' wave records behind it
@@ -43,7 +44,7 @@ int wave_run(fsnp_wave_stream* w, const SlotCounts& c, int fin, const float* wav
     SlotCounts spectra{}, steps{};
     int nrow = 1, frames = 0;
     for (int b = 0; b < w->S; ++b) {
-        const WaveStep st = wave_step(w->samples[b], fin ? 0 : c.v[b], fin ? c.v[b] : 0, w->hop, w->LA);
+        const WaveStep st = wave_step(w->samples[b], fin ? 0 : c.v[b], fin ? c.v[b] : 0, w->hop, w->half, w->LA);
         spectra.v[b] = st.ks; steps.v[b] = st.km;
         nrow = std::max(nrow, st.km);
         frames += st.km;
@@ -53,11 +54,11 @@ int wave_run(fsnp_wave_stream* w, const SlotCounts& c, int fin, const float* wav
     WaveArgs a{};
     a.state = w->rec.base; a.stride = w->rec.bytes; a.o_tail = w->o_tail; a.o_fifo = w->o_fifo; a.o_count = w->o_count;
     a.meta = reinterpret_cast<WaveMeta*>(w->ws + w->w_meta);
-    a.S = w->S; a.hop = w->hop; a.LA = w->LA; a.nrow = nrow;
+    a.S = w->S; a.hop = w->hop; a.half = w->half; a.LA = w->LA; a.nrow = nrow; a.xl = p.xl;
     const int rows = w->S * nrow;
     launch_wave_gather(a, c, fin, wav, wav_stride, fptr(w->w_xfr), s);
     if (frames > 0)
-        launch_linear_act(fptr(w->w_xfr), p.n_fft, h->d_stft + p.o_fwd, p.n_fft, h->d_stft + p.o_zero, fptr(w->w_spec), p.sp, p.n_fft, p.N2, 1,
+        launch_linear_act(fptr(w->w_xfr), p.xl, h->d_stft + p.o_fwd, p.fwd_ld, h->d_stft + p.o_zero, fptr(w->w_spec), p.sp, p.n_fft, p.N2, 1,
                           rows, FSNP_ACT_NONE, h->num_cus, s);
     // spectra and enhanced spectra [S][nrow][sp] floats as complex (slot, f, frame); without frames there is nothing to transform back,
     // so the ring push need not write the zero rows of such a call (write_idle = false)
@@ -89,31 +90,37 @@ int wave_create(fsnp_handle* h, int32_t slots, int32_t max_samples, int live, co
     *out = nullptr;
     if (h->cfg.output_size != 2) { set_error("%s: the cIRM epilogue needs output_size = 2 (this handle: %d)", where, h->cfg.output_size); return 2; }
     if (max_samples < 1) { set_error("%s: max_samples %d < 1", where, max_samples); return 2; }
-    if (h->F < 3 || ((h->F - 1) & (h->F - 2)) != 0 || h->F - 1 > 4096) {
-        set_error("%s: num_freqs - 1 must be a power of two up to 4096 (n_fft = 2 (num_freqs - 1))", where);
+    if (h->F - 1 > 4096) { set_error("%s: num_freqs - 1 = %d > 4096: a slot's carry and overlap-add sums must fit one workgroup's LDS", where, h->F - 1); return 2; }
+    const StftPlan p = stft_plan(h);                  // the session keeps this geometry whatever the handle is told later
+    if (const int rc = check_hop_length(h->F, p.hop, where)) return rc;
+    const int hop = p.hop, half = p.half, LA = h->cfg.look_ahead;
+    const int fin_rows = wave_finish_rows(hop, half, LA);
+    const int NF = std::max(max_samples / hop + 1, fin_rows);
+    if (live && fin_rows > kLiveMaxChunk) {
+        set_error("%s: finishing a clip takes up to ceil(n_fft / (2 hop_length)) + look_ahead = %d frames in one call (n_fft %d, hop_length %d, "
+                  "look_ahead %d), a live session runs at most %d: open a default session (fsnp_wave_stream_create)", where, fin_rows,
+                  p.n_fft, hop, LA, kLiveMaxChunk);
         return 2;
     }
-    const int hop = h->F - 1, LA = h->cfg.look_ahead;
-    const int NF = std::max(max_samples / hop + 1, 1 + LA);
     fsnp_stream* mag = nullptr;
-    // every refusal of a mag session, with its reason (live: frames per push = max(max_samples / hop + 1, 1 + look_ahead) <= 16)
+    // every refusal of a mag session, with its reason (live: frames per push = max_samples / hop + 1 <= 16)
     if (const int rc = live ? stream_create(h, slots, NF, 1, where, &mag) : fsnp_stream_create(h, slots, NF, &mag)) return rc;
     if (ensure_stft(h)) { fsnp_stream_destroy(mag); return 2; }
     fsnp_wave_stream* w = new fsnp_wave_stream();
-    w->h = h; w->mag = mag; w->S = slots; w->max_samples = max_samples; w->NF = NF; w->hop = hop; w->LA = LA; w->D = (2 + LA) * hop;
-    w->p = stft_plan(h);
-    const StftPlan& p = w->p;
+    w->h = h; w->mag = mag; w->S = slots; w->max_samples = max_samples; w->NF = NF; w->hop = hop; w->half = half; w->LA = LA;
+    w->D = p.n_fft + LA * hop;
+    w->p = p;
     w->mag_bytes = (size_t)fsnp_stream_state_bytes(mag);
     w->o_ring = align_up((size_t)(p.n_fft + 1) * 4, 8);
     w->o_tail = w->o_ring + (size_t)LA * p.F * 8;
-    w->o_fifo = w->o_tail + (size_t)hop * 4;
+    w->o_fifo = w->o_tail + (size_t)(p.n_fft - hop) * 4;
     w->o_count = align_up(w->o_fifo + (size_t)hop * 4, 8);
     const size_t rec_bytes = align_up(w->o_count + 8, 16);
     size_t o = 0;
     auto take = [&](size_t bytes) { size_t r = o; o = align_up(o + bytes, 256); return r; };
     const size_t S = slots, rows = S * NF;
     w->w_meta = take(S * sizeof(WaveMeta));
-    w->w_xfr = take(rows * p.n_fft * 4);
+    w->w_xfr = take(rows * p.xl * 4);
     w->w_spec = take(rows * p.sp * 4);
     w->w_mag = take(rows * h->FP * 4);
     w->w_mask = take(rows * 2 * p.F * 4);
@@ -182,9 +189,9 @@ int fsnp_wave_stream_finish(fsnp_wave_stream* w, const int32_t* slots, int32_t n
     for (int b = 0; b < w->S; ++b) {
         if (!c.v[b]) continue;
         if (w->samples[b] == 0) { c.v[b] = 0; continue; }      // nothing to finish: a row of zeros
-        if (w->samples[b] <= w->hop) {
+        if (w->samples[b] <= w->half) {
             set_error("fsnp_wave_stream_finish: slot %d holds %lld samples: a clip needs more than n_fft/2 = %d (reflect padding)", b,
-                      (long long)w->samples[b], w->hop);
+                      (long long)w->samples[b], w->half);
             return 2;
         }
     }

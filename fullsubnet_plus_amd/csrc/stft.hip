@@ -11,6 +11,8 @@
 //          the output IS torch.stft's memory layout ([B][T][F] complex64).
 //   iSTFT: fr[t][n] = w[n]/N * sum_f c_f (Re X cos - Im X sin),  c_0 = c_{N/2} = 1, else 2 (C2R semantics);
 //          wav[i] = (sum_t fr[t][i + N/2 - t*hop]) / (sum_t w^2[i + N/2 - t*hop])   (torch.istft's envelope division).
+// Geometry (include/fsnp_stft_geometry.h): n_fft = 2 (F - 1), window = periodic hann(n_fft), N/8 <= hop <= N/2 with hop % 4 == 0 (the A
+// rows above are read as float4); T = 1 + L / hop frames, the reflect padding is N/2 whatever the hop.
 #include <cmath>
 
 #include "fsnp_common.h"
@@ -39,35 +41,56 @@ void launch_stft_pad(const float* wav, long wav_stride, float* xp, long xp_strid
                        L, n_fft / 2, total);
 }
 
-// hop = n_fft / 2: every output sample is covered by at most two frames
+// One output sample: overlap-add and envelope division over the frames t < T that cover it, t * hop - n_fft / 2 <= n < t * hop + n_fft / 2
+// (up to ceil(n_fft / hop) <= 8 of them), divided by the same frames' w^2 with torch.istft's guard.  HALF (hop = n_fft / 2): at most two
+// frames cover a sample; the arithmetic the default geometry has always had, kept as it was so that its results stay bit-identical.
+template <bool HALF>
+__device__ __forceinline__ float istft_ola_sample(const float* __restrict__ frames /*[T][n_fft] of one clip*/,
+                                                  const float* __restrict__ window, int n, int T, int n_fft, int hop) {
+    const int p = n + n_fft / 2;                               // position in the centre-padded signal
+    float num = 0.0f, den = 0.0f;
+    if constexpr (HALF) {
+        const int t1 = p / hop, t0 = t1 - 1;
+        if (t1 < T) {
+            const int k = p - t1 * hop;
+            num += frames[(long)t1 * n_fft + k];
+            den += window[k] * window[k];
+        }
+        if (t0 >= 0 && t0 < T) {
+            const int k = p - t0 * hop;
+            num += frames[(long)t0 * n_fft + k];
+            den += window[k] * window[k];
+        }
+    } else {
+        const int thi = p / hop < T ? p / hop : T - 1;         // newest frame that starts at or before p
+        const int tlo = p < n_fft ? 0 : (p - n_fft) / hop + 1; // oldest frame that still reaches p
+        for (int t = thi; t >= tlo; --t) {
+            const int k = p - t * hop;                         // 0 <= k < n_fft by the two bounds
+            num += frames[(long)t * n_fft + k];
+            den += window[k] * window[k];
+        }
+    }
+    return den > 1e-11f ? num / den : 0.0f;
+}
+
+template <bool HALF>
 __global__ __launch_bounds__(256) void istft_ola_kernel(const float* __restrict__ frames, const float* __restrict__ window,
-                                                        float* __restrict__ wav, long wav_stride, int T, int L, int n_fft,
+                                                        float* __restrict__ wav, long wav_stride, int T, int L, int n_fft, int hop,
                                                         long total) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;      // (b, sample)
     if (i >= total) return;
     const int b = (int)(i / L), n = (int)(i % L);
-    const int hop = n_fft / 2;
-    const int p = n + hop;                                     // position in the centre-padded signal
-    const int t1 = p / hop, t0 = t1 - 1;
-    float num = 0.0f, den = 0.0f;
-    if (t1 < T) {
-        const int k = p - t1 * hop;
-        num += frames[((long)b * T + t1) * n_fft + k];
-        den += window[k] * window[k];
-    }
-    if (t0 >= 0 && t0 < T) {
-        const int k = p - t0 * hop;
-        num += frames[((long)b * T + t0) * n_fft + k];
-        den += window[k] * window[k];
-    }
-    wav[(long)b * wav_stride + n] = den > 1e-11f ? num / den : 0.0f;
+    wav[(long)b * wav_stride + n] = istft_ola_sample<HALF>(frames + (long)b * T * n_fft, window, n, T, n_fft, hop);
 }
 
-void launch_istft_ola(const float* frames, const float* window, float* wav, long wav_stride, int B, int T, int L, int n_fft,
+void launch_istft_ola(const float* frames, const float* window, float* wav, long wav_stride, int B, int T, int L, int n_fft, int hop,
                       hipStream_t s) {
     const long total = (long)B * L;
-    hipLaunchKernelGGL(istft_ola_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, frames, window, wav,
-                       wav_stride, T, L, n_fft, total);
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (2 * hop == n_fft)
+        hipLaunchKernelGGL(istft_ola_kernel<true>, grid, dim3(256), 0, s, frames, window, wav, wav_stride, T, L, n_fft, hop, total);
+    else
+        hipLaunchKernelGGL(istft_ola_kernel<false>, grid, dim3(256), 0, s, frames, window, wav, wav_stride, T, L, n_fft, hop, total);
 }
 
 // ---- clips of different lengths in one batch (fsnp_enhance_wave_lengths): row b is its own samples[b] long.  The sample counts travel
@@ -104,52 +127,43 @@ void launch_stft_pad_lengths(const float* wav, long wav_stride, float* xp, long 
 
 // overlap-add and window-envelope division over row b's own 1 + samples[b] / hop frames (torch.istft(..., length=samples[b]) of the
 // clip alone: frame T_b, which still overlaps the clip's last samples, is not part of it); samples past samples[b] are written as 0
+template <bool HALF>
 __global__ __launch_bounds__(256) void istft_ola_lengths_kernel(const float* __restrict__ frames, const float* __restrict__ window,
                                                                 float* __restrict__ wav, long wav_stride, int T, int L, int n_fft,
-                                                                long total, RowLengths len) {
+                                                                int hop, long total, RowLengths len) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;      // (b, sample)
     if (i >= total) return;
     const int b = (int)(i / L), n = (int)(i % L);
-    const int hop = n_fft / 2;
     const int Lb = len.v[b], Tb = 1 + Lb / hop;
     float out = 0.0f;
-    if (n < Lb) {
-        const int p = n + hop;
-        const int t1 = p / hop, t0 = t1 - 1;
-        float num = 0.0f, den = 0.0f;
-        if (t1 < Tb) {
-            const int k = p - t1 * hop;
-            num += frames[((long)b * T + t1) * n_fft + k];
-            den += window[k] * window[k];
-        }
-        if (t0 >= 0 && t0 < Tb) {
-            const int k = p - t0 * hop;
-            num += frames[((long)b * T + t0) * n_fft + k];
-            den += window[k] * window[k];
-        }
-        out = den > 1e-11f ? num / den : 0.0f;
-    }
+    if (n < Lb) out = istft_ola_sample<HALF>(frames + (long)b * T * n_fft, window, n, Tb, n_fft, hop);
     wav[(long)b * wav_stride + n] = out;
 }
 
 void launch_istft_ola_lengths(const float* frames, const float* window, float* wav, long wav_stride, int B, int T, int L, const int* samples,
-                              int n_fft, hipStream_t s) {
+                              int n_fft, int hop, hipStream_t s) {
     for (int b0 = 0; b0 < B; b0 += kLenRows) {
         const int rows = B - b0 < kLenRows ? B - b0 : kLenRows;
         RowLengths len{};
         for (int r = 0; r < rows; ++r) len.v[r] = samples[b0 + r];
         const long total = (long)rows * L;
-        hipLaunchKernelGGL(istft_ola_lengths_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, frames + (long)b0 * T * n_fft,
-                           window, wav + (long)b0 * wav_stride, wav_stride, T, L, n_fft, total, len);
+        const dim3 grid((unsigned)((total + 255) / 256));
+        if (2 * hop == n_fft)
+            hipLaunchKernelGGL(istft_ola_lengths_kernel<true>, grid, dim3(256), 0, s, frames + (long)b0 * T * n_fft, window,
+                               wav + (long)b0 * wav_stride, wav_stride, T, L, n_fft, hop, total, len);
+        else
+            hipLaunchKernelGGL(istft_ola_lengths_kernel<false>, grid, dim3(256), 0, s, frames + (long)b0 * T * n_fft, window,
+                               wav + (long)b0 * wav_stride, wav_stride, T, L, n_fft, hop, total, len);
     }
 }
 
-// Host: GEMM operands (zero padded as tcn_gemm_kernel expects: rows to a multiple of 384, K to a multiple of 16).
-//   fwd [2F pad 384][n_fft]      : row 2f = w[n] cos(2 pi f n / N), row 2f+1 = -w[n] sin(2 pi f n / N)
+// Host: GEMM operands (zero padded as tcn_gemm_kernel expects: rows to a multiple of 384, K to a multiple of 16).  They depend on n_fft
+// only, not on the hop.
+//   fwd [2F pad 384][n_fft pad 16]: row 2f = w[n] cos(2 pi f n / N), row 2f+1 = -w[n] sin(2 pi f n / N)
 //   inv [n_fft pad 384][2F pad 16]: row n, column 2f = c_f w[n] cos(2 pi f n / N) / N, column 2f+1 = -c_f w[n] sin(...) / N
 void stft_build_matrices(int n_fft, float* fwd, float* inv, float* window) {
     const int F = n_fft / 2 + 1, N2 = 2 * F;
-    const int kp = (N2 + 15) / 16 * 16;
+    const int kp = (N2 + 15) / 16 * 16, np = (n_fft + 15) / 16 * 16;
     const double two_pi = 6.283185307179586476925286766559;
     for (int n = 0; n < n_fft; ++n) window[n] = (float)(0.5 - 0.5 * cos(two_pi * n / n_fft));   // torch.hann_window (periodic)
     for (int f = 0; f < F; ++f)
@@ -157,8 +171,8 @@ void stft_build_matrices(int n_fft, float* fwd, float* inv, float* window) {
             const long ph = ((long)f * n) % n_fft;             // exact phase reduction
             const double c = cos(two_pi * ph / n_fft), sn = sin(two_pi * ph / n_fft);
             const double w = 0.5 - 0.5 * cos(two_pi * n / n_fft);
-            fwd[(size_t)(2 * f) * n_fft + n] = (float)(w * c);
-            fwd[(size_t)(2 * f + 1) * n_fft + n] = (float)(-w * sn);
+            fwd[(size_t)(2 * f) * np + n] = (float)(w * c);
+            fwd[(size_t)(2 * f + 1) * np + n] = (float)(-w * sn);
             const double cf = (f == 0 || f == n_fft / 2) ? 1.0 : 2.0;
             inv[(size_t)n * kp + 2 * f] = (float)(cf * w * c / n_fft);
             inv[(size_t)n * kp + 2 * f + 1] = (float)(-cf * w * sn / n_fft);

@@ -381,6 +381,8 @@ class _HipModel(nn.Module):
             self.__dict__.pop("_vs_applied", None)
             if self.__dict__.get("_verify_every"):
                 _lib.check(lib.fsnp_set_verify(hp, int(self.__dict__["_verify_every"])), "fsnp_set_verify")
+            if "_hop_length" in self.__dict__:
+                _lib.check(lib.fsnp_set_hop_length(hp, self.__dict__["_hop_length"]), "fsnp_set_hop_length")
         key = self._weights_key()
         if key != st.packed_key and self.weight_upload != "host":
             self._upload_weights(lib, device)
@@ -591,6 +593,24 @@ class _HipModel(nn.Module):
         if self._hip.handle is not None:
             _lib.check(_lib.load().fsnp_set_verify(self._handle, int(every)), "fsnp_set_verify")
 
+    @property
+    def hop_length(self):
+        """The hop of the waveform path in samples (include/fsnp_stft_geometry.h), what the reference reads from [acoustics] of its TOML
+        next to n_fft = win_length = 2 (num_freqs - 1): stft, istft, enhance_wave (with and without lengths=), reserve(max_samples=...)
+        and open_wave_stream run at it.  Default num_freqs - 1 (n_fft / 2).  Assigning validates first and touches no GPU: ValueError
+        unless n_fft / 8 <= hop_length <= n_fft / 2 and hop_length % 4 == 0.  A wave session keeps the hop it was opened with."""
+        return self.__dict__.get("_hop_length", self.num_freqs - 1)
+
+    @hop_length.setter
+    def hop_length(self, hop):
+        from .stream import hop_refusal
+        why = hop_refusal(self.num_freqs, hop)
+        if why is not None:
+            raise ValueError(f"{self.__class__.__name__}.hop_length: {why}")
+        self.__dict__["_hop_length"] = int(hop)
+        if self._hip.handle is not None:
+            _lib.check(_lib.load().fsnp_set_hop_length(self._handle, int(hop)), "fsnp_set_hop_length")
+
     def verify_count(self):
         """-> verification passes run so far (fsnp_verify_count)."""
         return int(_lib.load().fsnp_verify_count(self._handle))
@@ -672,11 +692,11 @@ class _HipModel(nn.Module):
         return wav, self._ensure_handle(wav.device), torch.cuda.current_stream(wav.device).cuda_stream
 
     def stft(self, wav):
-        """audio_zen/acoustics/feature.py:10-31 (torch.stft, n_fft = 2 (F - 1), hop = n_fft / 2, hann, center) in HIP:
-        wav [B, samples] -> complex64 [B, F, T] with torch.stft's strides."""
+        """audio_zen/acoustics/feature.py:10-31 (torch.stft, n_fft = win_length = 2 (F - 1), hop_length = self.hop_length, hann, center)
+        in HIP: wav [B, samples] -> complex64 [B, F, T = 1 + samples // hop_length] with torch.stft's strides."""
         wav, lib, stream = self._wave_args(wav)
         B, L = wav.shape
-        T = 1 + L // (self.num_freqs - 1)
+        T = 1 + L // self.hop_length
         spec = torch.empty((B, T, self.num_freqs), dtype=torch.complex64, device=wav.device)
         with torch.cuda.device(wav.device):
             _lib.check(lib.fsnp_stft(self._handle, wav.data_ptr(), wav.stride(0), torch.view_as_real(spec).data_ptr(), B, L,
@@ -684,7 +704,7 @@ class _HipModel(nn.Module):
         return spec.permute(0, 2, 1)
 
     def istft(self, spec, length):
-        """feature.py:34-56 (torch.istft(..., length=length)) in HIP: complex64 [B, F, T] (any strides) -> [B, length]."""
+        """feature.py:34-56 (torch.istft(..., length=length), at self.hop_length) in HIP: complex64 [B, F, T] (any strides) -> [B, length]."""
         assert spec.dim() == 3 and spec.dtype == torch.complex64 and spec.shape[1] == self.num_freqs
         if not spec.is_cuda:
             raise RuntimeError("fullsubnet_plus_amd runs on MI355X (HIP) only; there is deliberately no CPU fallback.")
@@ -702,7 +722,8 @@ class _HipModel(nn.Module):
         """The reference inferencer's inner loop in ONE call (fullsubnet_plus/inferencer/inferencer.py:142-158,
         `mag_complex_full_band_crm_mask`; `full_band_crm_mask` of fullsubnet/inferencer/inferencer.py for the original
         FullSubNet): noisy waveform [B, samples] -> enhanced waveform [B, samples]; STFT, model (all bins), cIRM
-        decompression, complex multiply and iSTFT all run in HIP on the caller's stream.  lengths: None, or SAMPLES per
+        decompression, complex multiply and iSTFT all run in HIP on the caller's stream, the two transforms at self.hop_length
+        (1 + samples // hop_length model steps).  lengths: None, or SAMPLES per
         utterance (a Python sequence or a CPU integer tensor): row b is then enhance_wave(noisy[b:b+1, :lengths[b]]) of that
         clip alone, and 0 past lengths[b].  Follows error_check like forward: under "deferred", too, a `.data` edit that the weight
         watch flagged on an earlier call is answered by a RuntimeWarning, a re-pack and the edited weights' result."""
@@ -1164,10 +1185,12 @@ class FullSubNet(_HipModel):
 
     def open_wave_stream(self, slots, max_samples=4096, device="cuda", live=False):
         """-> fullsubnet_plus_amd.stream.WaveStream: `slots` independent live audio streams, blocks of up to max_samples samples in, as
-        many enhanced samples out at the fixed delay (2 + look_ahead) * hop (include/fsnp_wave_stream.h).  All push outputs of a clip
+        many enhanced samples out at the fixed delay n_fft + look_ahead * hop_length (include/fsnp_wave_stream.h; (2 + look_ahead) * hop
+        in the default geometry).  The session runs at the model's hop_length of this moment and keeps it.  All push outputs of a clip
         followed by finish(), without the first `delay` samples, are enhance_wave() of that clip alone.  The refusals of open_stream
         apply (NotImplementedError with the reason, before any GPU is touched).  live=True: the model inside runs as a live session
-        (see open_stream); max_samples / hop + 1 frames per push must then be <= 16, e.g. max_samples = hop for one hop per push."""
+        (see open_stream); max_samples / hop + 1 frames per push must then be <= 16, e.g. max_samples = hop for one hop per push, and so
+        must the ceil(n_fft / (2 hop)) + look_ahead frames of a finish."""
         from .stream import WaveStream, wave_refusal
         why = wave_refusal(self)
         if why is not None:

@@ -5,7 +5,7 @@
     ...
     mask = stream.tail()                     # look_ahead zero frames: the masks of the last look_ahead frames
 
-and the same for waveforms (include/fsnp_wave_stream.h): samples in, samples out at the fixed delay (2 + look_ahead) * hop.
+and the same for waveforms (include/fsnp_wave_stream.h): samples in, samples out at the fixed delay n_fft + look_ahead * hop_length.
 
     wave = model.open_wave_stream(slots=8, max_samples=4096)
     out = wave.push(block)                   # [8, n] -> [8, n]; column j = enhanced sample P + j - wave.delay (0 before the clip's start)
@@ -24,6 +24,7 @@ fill the chip at one slot.  Same interface, same state records; max_chunk <= 16.
 """
 import ctypes
 import gc
+import numbers
 
 import torch
 
@@ -60,13 +61,28 @@ def spec_refusal(model):
 
 
 def wave_refusal(model):
-    """Why `model` (a FullSubNet) cannot stream waveforms, or None: spec_refusal(), and the hop enhance_wave demands.  No GPU is touched."""
+    """Why `model` (a FullSubNet) cannot stream waveforms, or None: spec_refusal(), and the rules of include/fsnp_stft_geometry.h for the
+    model's hop_length (what its setter refuses: here only a default hop num_freqs - 1 that is no multiple of 4).  No GPU is touched."""
     why = spec_refusal(model)
     if why is not None:
         return why
-    hop = model.num_freqs - 1
-    if model.num_freqs < 3 or hop & (hop - 1):
-        return "num_freqs - 1 must be a power of two (n_fft = 2 (num_freqs - 1))"
+    return hop_refusal(model.num_freqs, model.hop_length)
+
+
+def hop_refusal(num_freqs, hop):
+    """Why the waveform path of a model of `num_freqs` bins cannot run at hop length `hop`, or None (include/fsnp_stft_geometry.h:
+    n_fft = 2 (num_freqs - 1), n_fft / 8 <= hop <= n_fft / 2, hop % 4 == 0).  Arithmetic only."""
+    if num_freqs < 3:
+        return f"the waveform path needs num_freqs >= 3 (n_fft = 2 (num_freqs - 1)); this model: {num_freqs}"
+    n_fft = 2 * (num_freqs - 1)
+    if isinstance(hop, bool) or not isinstance(hop, numbers.Integral):
+        return f"hop_length must be an integer number of samples, got {hop!r}"
+    if hop <= 0 or 2 * hop > n_fft or 8 * hop < n_fft:
+        return (f"hop_length {hop} outside [n_fft / 8, n_fft / 2] = [{(n_fft + 7) // 8}, {n_fft // 2}] (n_fft = 2 (num_freqs - 1) = {n_fft}): "
+                "above it frames no longer cover the clip's tail, below it is outside what the waveform path is built for")
+    if hop % 4:
+        return (f"hop_length {hop} is not a multiple of 4: the forward DFT GEMM reads frame t at float t * hop_length of the padded signal "
+                "as 16-byte vectors")
     return None
 
 
@@ -264,7 +280,8 @@ class Stream(_FrameSession):
 class WaveStream(_Session):
     """`slots` independent live audio streams on one FullSubNet (open one through FullSubNet.open_wave_stream, which refuses a model that
     cannot stream waveforms before any GPU is touched): blocks of samples in, the same number of
-    enhanced samples out, `delay` = (2 + look_ahead) * hop samples late.  All push outputs of a clip followed by its finish() output,
+    enhanced samples out, `delay` = n_fft + look_ahead * hop_length samples late ((2 + look_ahead) * hop_length in the default geometry).
+    `hop_length` is the model's when the session was opened; later assignments to model.hop_length do not touch the session.  All push outputs of a clip followed by its finish() output,
     without the first `delay` samples, are enhance_wave() of that clip alone, whatever the block sizes.  Everything runs on the current
     CUDA stream; a push allocates nothing but its output tensor and never synchronises (under the model's error_check="sync" it then
     waits and polls, as forward does).  load_state takes what state() of a slot of any wave session of a model of the same sizes
@@ -272,8 +289,9 @@ class WaveStream(_Session):
     _prefix, _opener = "fsnp_wave_stream", "open_wave_stream"
 
     def __init__(self, model, slots, max_samples, device, live=False):
+        self.hop_length = self.hop = int(model.hop_length)       # (the C session is created from the handle's hop: _ensure_handle set it)
         super().__init__(model, slots, max_samples, device, live)
-        self.max_samples, self.hop = int(max_samples), model.num_freqs - 1
+        self.max_samples = int(max_samples)
         self.delay, self.live = int(self._lib.fsnp_wave_stream_delay(self._st)), bool(live)
 
     def push(self, wav, counts=None):
@@ -303,7 +321,7 @@ class WaveStream(_Session):
     def finish(self, slots=None):
         """End the clips of `slots` (None: all) -> [slots, delay]: each clip's last `delay` samples (exactly 0 where the clip is shorter);
         rows of slots not listed, and of slots that hold no samples, are exactly 0.  The finished slots are reset: their next push starts
-        a fresh clip.  A slot that holds 1 .. hop samples is refused, as enhance_wave refuses such a clip."""
+        a fresh clip.  A slot that holds 1 .. n_fft / 2 samples is refused, as enhance_wave refuses such a clip."""
         st = self._session()
         arr, num = _slot_array(slots)
         out = torch.empty((self.slots, self.delay), dtype=torch.float32, device=self.device)
