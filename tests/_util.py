@@ -112,6 +112,15 @@ def plane_errs(got, want):
     return errs, where
 
 
+def mask_errs(got, want):
+    """got, want [B, output_size, Fo, T] -> plane_errs of each utterance's own [output_size, Fo, T] block (reshaped to one plane of
+    Fo * output_size rows): (errs, where) with where[b] = (bin, output, frame)."""
+    got, want = np.asarray(got), np.asarray(want)
+    B, O, Fo, T = want.shape
+    errs, where = plane_errs(got.transpose(0, 2, 1, 3).reshape(B, Fo * O, T), want.transpose(0, 2, 1, 3).reshape(B, Fo * O, T))
+    return errs, [(r // O, r % O, t) for r, t in where]
+
+
 @torch.no_grad()
 def oracle_stages(sd, ins, args, dtype=torch.float64):
     """The attention and full-band stages of fsnp_torch.forward alone (no sub-band model), evaluated in `dtype` with the state dict and
@@ -129,6 +138,41 @@ def oracle_stages(sd, ins, args, dtype=torch.float64):
         out["att_" + tag] = att
         out["fb_" + tag] = fsnp_torch.fb_sequence_model(att, p, "fb_model" + sfx, args["fb_output_activate_function"])
     return out
+
+
+@torch.no_grad()
+def oracle_subband(sd, stages, args, dtype, drop_band=False, record=None):
+    """The sub-band half of fsnp_torch.forward / forward_fullsubnet alone (oracle/fsnp_torch.py: unfold with reflect padding,
+    concatenate, normalise over the concatenated tensor, drop bands, lstm2_fc or the TCN sub-band model, reshape, look-ahead trim),
+    evaluated in `dtype` with the sub-band weights cast to it.  stages = {att_mag, fb_mag[, fb_real, fb_imag]}, each
+    [B, F, T + look_ahead] (the original FullSubNet has one fb branch and the padded magnitude as att_mag)
+    -> mask [B', output_size, Fo, T].  The oracle's functions are looked up when called, so a test may replace one; record: a dict that
+    receives "sb_input", the sub-band model's input [B' * Fo, features, T + look_ahead]."""
+    from oracle import fsnp_torch
+    p = {k: v.to(dtype) for k, v in sd.items() if k.startswith("sb_model")}
+    att = stages["att_mag"].to(dtype)
+    fbs = [stages[tag].to(dtype) for tag in ("fb_mag", "fb_real", "fb_imag") if tag in stages]
+    B, F, T = att.shape
+    la, nsbn, nfbn, out_size = args["look_ahead"], args["sb_num_neighbors"], args["fb_num_neighbors"], args.get("output_size", 2)
+    nsb, nfb = 2 * nsbn + 1, 2 * nfbn + 1
+    parts = [fsnp_torch.unfold(att.reshape(B, 1, F, T), nsbn).reshape(B, F, nsb, T)]
+    parts += [fsnp_torch.unfold(o.reshape(B, 1, F, T), nfbn).reshape(B, F, nfb, T) for o in fbs]
+    sb_input = fsnp_torch.NORMS[args["norm_type"]](torch.cat(parts, dim=2))
+    Fo = F
+    if drop_band:
+        sb_input = fsnp_torch.drop_band(sb_input.permute(0, 2, 1, 3), args["num_groups_in_drop_band"])
+        Fo = sb_input.shape[2]
+        sb_input = sb_input.permute(0, 2, 1, 3)
+    sb_input = sb_input.reshape(sb_input.shape[0] * Fo, nsb + len(fbs) * nfb, T)
+    if record is not None:
+        record["sb_input"] = sb_input
+    act = args.get("sb_output_activate_function", False)
+    if "sb_model.sequence_model.0.conv1x1.weight" in p:
+        sb_mask = fsnp_torch.fb_sequence_model(sb_input, p, "sb_model", act).contiguous()
+    else:
+        sb_mask = fsnp_torch.lstm2_fc(sb_input, p, "sb_model", act)
+    sb_mask = sb_mask.reshape(-1, Fo, out_size, T).permute(0, 2, 1, 3).contiguous()
+    return sb_mask[:, :, :, la:]
 
 
 # ------------------------------------------------------------------------------------------------ clips of different lengths
