@@ -102,6 +102,7 @@ SYMBOLS = {
     "fsnp_debug_weight_blob_ptr": (c_vp, [c_vp]),
     "fsnp_debug_commit_stats": (c_i32, [c_vp, ctypes.POINTER(c_i64 * 4)]),
     "fsnp_debug_pack_emulate": (c_i32, [c_i32, ctypes.POINTER(c_i32), c_i32, ctypes.POINTER(c_vp), ctypes.POINTER(c_i64), c_i32, c_vp, c_i64]),
+    "fsnp_debug_pcm_convert": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, ctypes.POINTER(c_i32), c_i32, c_vp, c_vp]),
     "fsnp_last_error": (ctypes.c_char_p, []),
     "fsnp_version": (ctypes.c_char_p, []),
 }
@@ -174,6 +175,17 @@ STFT_GEOMETRY_SYMBOLS = {
     "fsnp_hop_length": (c_i32, [c_vp]),
 }
 
+# every symbol include/fsnp_pcm.h declares (16-bit PCM and strided samples on the waveform path and in wave sessions; same ABI version)
+PCM_SYMBOLS = {
+    "fsnp_enhance_wave_pcm": (c_i32, [c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_i32, c_i64, c_i64, ctypes.POINTER(c_i32), c_i32, c_i32, c_vp,
+                                      c_vp]),
+    "fsnp_stft_pcm": (c_i32, [c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_i32, c_i32, c_vp]),
+    "fsnp_wave_stream_push_pcm": (c_i32, [c_vp, c_vp, c_i32, c_i64, c_i64, ctypes.POINTER(c_i32), c_vp, c_i32, c_i64, c_i64, c_i32, c_vp]),
+    "fsnp_wave_stream_finish_pcm": (c_i32, [c_vp, ctypes.POINTER(c_i32), c_i32, c_vp, c_i32, c_i64, c_i64, c_vp]),
+}
+SAMPLE_F32, SAMPLE_S16, SAMPLE_S16_PEAK = 0, 1, 2      # FSNP_SAMPLE_*
+SAMPLE_FORMATS = {"f32": SAMPLE_F32, "s16": SAMPLE_S16, "s16_peak": SAMPLE_S16_PEAK}
+
 ABI_VERSION = 13         # FSNP_ABI_VERSION of the include/fsnp.h these signatures were written against
 
 _lib = None
@@ -197,7 +209,7 @@ def load(build_if_missing=True):
     lib = ctypes.CDLL(path)
     for name, (res, args) in (list(SYMBOLS.items()) + list(LENGTHS_SYMBOLS.items()) + list(STREAM_SYMBOLS.items()) + list(WAVE_STREAM_SYMBOLS.items())
                               + list(LIVE_STREAM_SYMBOLS.items()) + list(SPEC_STREAM_SYMBOLS.items()) + list(DEVICE_WEIGHTS_SYMBOLS.items())
-                              + list(STFT_GEOMETRY_SYMBOLS.items())):
+                              + list(STFT_GEOMETRY_SYMBOLS.items()) + list(PCM_SYMBOLS.items())):
         fn = getattr(lib, name)          # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

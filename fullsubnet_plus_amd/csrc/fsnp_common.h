@@ -189,13 +189,15 @@ void launch_linear_act(const float* A, int lda, const float* W, int ldw, const f
                        int N, int B, int Tp, int act, int num_cus, hipStream_t s, long a_utt_stride = 0, int a_cols = 0);
 // stft.hip : SURVEY.md 8(f-3) second half - torch.stft / torch.istft of audio_zen/acoustics/feature.py:10-56 as
 // reflect-pad + DFT GEMM and inverse-DFT GEMM + windowed overlap-add (n_fft = win_length, n_fft / 8 <= hop <= n_fft / 2, hann)
-void launch_stft_pad(const float* wav, long wav_stride, float* xp, long xp_stride, int B, int L, int n_fft, hipStream_t s);
-void launch_istft_ola(const float* frames, const float* window, float* wav, long wav_stride, int B, int T, int L, int n_fft, int hop,
-                      hipStream_t s);
+// (samples in and out as the views of pcm.h: fp32 or int16 at any sample step, include/fsnp_pcm.h)
+struct PcmIn;
+struct PcmOut;
+void launch_stft_pad(const PcmIn& wav, float* xp, long xp_stride, int B, int L, int n_fft, hipStream_t s);
+void launch_istft_ola(const float* frames, const float* window, const PcmOut& wav, int B, int T, int L, int n_fft, int hop, hipStream_t s);
 // the same per row of a batch of clips of different lengths: samples[b] host values (kernel arguments, up to 256 rows per launch)
-void launch_stft_pad_lengths(const float* wav, long wav_stride, float* xp, long xp_stride, int B, const int* samples, int n_fft, hipStream_t s);
-void launch_istft_ola_lengths(const float* frames, const float* window, float* wav, long wav_stride, int B, int T, int L, const int* samples,
-                              int n_fft, int hop, hipStream_t s);
+void launch_stft_pad_lengths(const PcmIn& wav, float* xp, long xp_stride, int B, const int* samples, int n_fft, hipStream_t s);
+void launch_istft_ola_lengths(const float* frames, const float* window, const PcmOut& wav, int B, int T, int L, const int* samples, int n_fft,
+                              int hop, hipStream_t s);
 // spec_stream.hip : the look-ahead ring and the two short launches around one mag push that a spectrum session (include/fsnp_spec_stream.h)
 // and a wave session (include/fsnp_wave_stream.h) share.  Per slot a ring complex64 [look_ahead][F]: the noisy spectra of the newest
 // look_ahead frames, frame g in row g % look_ahead (they wait for their masks: the mask of frame t is the model's output of step
@@ -255,11 +257,11 @@ __host__ __device__ inline WaveStep wave_step(long long P, int c, int fin, int h
 inline int wave_finish_rows(int hop, int half, int LA) { return (half + hop - 1) / hop + LA; }
 // c.v[slot]: samples of a push, or (fin) 1 = finish this slot.  Frame rows xfr [S][nrow][xl] of the newly complete frames (zeros
 // behind them; the pad columns past n_fft are never written), the carry and the sample count advanced, meta written
-void launch_wave_gather(const WaveArgs& a, const SlotCounts& c, int fin, const float* wav, long wav_stride, float* xfr, hipStream_t s);
+void launch_wave_gather(const WaveArgs& a, const SlotCounts& c, int fin, const PcmIn& wav /*finish: p = NULL*/, float* xfr, hipStream_t s);
 // overlap-add with the window-envelope division over the frames fr [S][nrow][n_fft] (row j = the frame of step j of this call), into the
 // fifo and out [S][ncols]: column j is sample P + j - D (finish: L - D + j), exactly 0 where that is negative and past the slot's count
 // (finish: in rows not finished)
-void launch_wave_ola(const WaveArgs& a, const float* fr, const float* window, float* out, long out_stride, int ncols, hipStream_t s);
+void launch_wave_ola(const WaveArgs& a, const float* fr, const float* window, const PcmOut& out, int ncols, hipStream_t s);
 void stft_build_matrices(int n_fft, float* fwd /*[N2 pad 384][n_fft pad 16]*/, float* inv /*[n_fft pad 384][K pad 16]*/,
                          float* window /*[n_fft]*/);
 

@@ -9,6 +9,7 @@
 #include "planner.h"
 #include "fsnp_handle.h"
 #include "weight_layouts.h"
+#include "pcm.h"
 
 static double lstm_flops_per_step(const fsnp_handle* h) {
     if (h->sb_tcn) return 8 * (2.0 * h->NIN * h->CH + 2.0 * h->CH * 3 + 2.0 * h->CH * h->NIN) + 2.0 * h->NIN * h->cfg.output_size;
@@ -502,6 +503,38 @@ int fsnp_debug_pack_emulate(int32_t kind, const int32_t* sizes, int32_t num_size
     }
     pack_image_host(J, arena.data(), out, J.n);
     return 0;
+}
+
+int fsnp_debug_pcm_convert(fsnp_handle* h, const float* dev_in, int16_t* dev_out, int32_t rows, int32_t n, const int32_t* samples,
+                           int32_t out_format, int32_t* dev_clipped, void* stream) {
+    if (!h || !dev_in || !dev_out) { set_error("fsnp_debug_pcm_convert: null argument"); return 1; }
+    if (rows < 1 || n < 1) { set_error("fsnp_debug_pcm_convert: empty input"); return 2; }
+    if (out_format != FSNP_SAMPLE_S16 && out_format != FSNP_SAMPLE_S16_PEAK) {
+        set_error("fsnp_debug_pcm_convert: out_format %d is neither FSNP_SAMPLE_S16 nor FSNP_SAMPLE_S16_PEAK", (int)out_format);
+        return 2;
+    }
+    for (int b = 0; samples && b < rows; ++b)
+        if (samples[b] < 0 || samples[b] > n) { set_error("fsnp_debug_pcm_convert: row %d: %d samples outside [0, n = %d]", b, (int)samples[b], n); return 2; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    FSNP_ON_DEVICE(h);
+    PcmOut out{dev_out, n, 1, kPcmS16, nullptr, nullptr};
+    if (dev_clipped) FSNP_HIP_CHECK(hipMemsetAsync(dev_clipped, 0, (size_t)rows * 4, s));
+    if (out_format == FSNP_SAMPLE_S16) {
+        out.clipped = dev_clipped;
+        launch_pcm_convert(dev_in, n, out, rows, n, samples, s);
+    } else {
+        // the two passes of the whole-clip call: fp32 staging rows and per-row maxima in the I/O area, then scale and truncate
+        const size_t stage_b = align_up((size_t)rows * n * 4, 256);
+        if (order_after_last_forward(h, s)) return 4;
+        if (ensure_io(h, stage_b + (size_t)rows * 4, s)) return 4;
+        float* stage = reinterpret_cast<float*>(h->io);
+        unsigned* peak = reinterpret_cast<unsigned*>(h->io + stage_b);
+        FSNP_HIP_CHECK(hipMemsetAsync(peak, 0, (size_t)rows * 4, s));
+        launch_pcm_convert(dev_in, n, PcmOut{stage, n, 1, kPcmPeak, nullptr, peak}, rows, n, samples, s);
+        launch_pcm_peak_scale(stage, n, peak, out, rows, n, s);
+    }
+    FSNP_HIP_CHECK(hipGetLastError());
+    return mark_forward_done(h, s);
 }
 
 }  // extern "C"

@@ -255,6 +255,9 @@ StftPlan stft_plan(const fsnp_handle* h);
 int check_hop_length(int F, int hop, const char* where);
 int ensure_stft(fsnp_handle* h);
 int ensure_io(fsnp_handle* h, size_t bytes, hipStream_t s);
+// 0, or 2 with the error set: the format and step rules of include/fsnp_pcm.h for one sample buffer (`what`: "input" / "output";
+// peak_ok: FSNP_SAMPLE_S16_PEAK is a format this buffer may have)
+int check_sample_format(const char* where, const char* what, int32_t format, int64_t step, bool peak_ok);
 // ---- stream, wave and spectrum sessions (fsnp_stream_abi.hip, fsnp_wave_stream_abi.hip, fsnp_spec_stream_abi.hip) ----
 // argument checks of their entry points: `where` names the entry point in every message; 0, or 2 with the error set
 inline int check_slot(const char* where, int slot, int S) {

@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "fsnp_handle.h"
+#include "pcm.h"
 
 // ---------------------------------------------------------------------------------------------- STFT / iSTFT (f-3)
 namespace fsnp {
@@ -64,10 +65,10 @@ __global__ void spec_repack_kernel(const float2* __restrict__ in, long sb, long 
     out[i] = f < F ? in[b * sb + f * sf + t * st] : make_float2(0.f, 0.f);
 }
 // wav [B][L] -> spectrum rows [B][T][ldc] (interleaved complex), T = 1 + L / hop
-static void stft_into(fsnp_handle* h, const StftPlan& p, const float* wav, long wav_stride, float* xp, long xs, float* spec,
-                      int ldc, int B, int L, hipStream_t s) {
+static void stft_into(fsnp_handle* h, const StftPlan& p, const PcmIn& wav, float* xp, long xs, float* spec, int ldc, int B, int L,
+                      hipStream_t s) {
     const int T = 1 + L / p.hop;
-    launch_stft_pad(wav, wav_stride, xp, xs, B, L, p.n_fft, s);
+    launch_stft_pad(wav, xp, xs, B, L, p.n_fft, s);
     launch_linear_act(xp, p.hop, h->d_stft + p.o_fwd, p.fwd_ld, h->d_stft + p.o_zero, spec, ldc, p.n_fft, p.N2, B, T,
                       FSNP_ACT_NONE, h->num_cus, s, xs, p.n_fft);
 }
@@ -76,26 +77,130 @@ static void istft_from(fsnp_handle* h, const StftPlan& p, const float* spec, flo
                        int T, int L, hipStream_t s) {
     launch_linear_act(spec, p.sp, h->d_stft + p.o_inv, p.inv_ld, h->d_stft + p.o_zero, frames, p.n_fft, p.N2, p.n_fft, B, T,
                       FSNP_ACT_NONE, h->num_cus, s, (long)T * p.sp, p.N2);
-    launch_istft_ola(frames, h->d_stft + p.o_win, wav, wav_stride, B, T, L, p.n_fft, p.hop, s);
+    launch_istft_ola(frames, h->d_stft + p.o_win, pcm_out_f32(wav, wav_stride), B, T, L, p.n_fft, p.hop, s);
 }
+// the format and step rules of include/fsnp_pcm.h for one buffer (peak_ok: FSNP_SAMPLE_S16_PEAK is a format of this buffer)
+int check_sample_format(const char* where, const char* what, int32_t format, int64_t step, bool peak_ok) {
+    if (format != FSNP_SAMPLE_F32 && format != FSNP_SAMPLE_S16 && format != FSNP_SAMPLE_S16_PEAK) {
+        set_error("%s: unknown %s format %d (FSNP_SAMPLE_F32 = 0, FSNP_SAMPLE_S16 = 1, FSNP_SAMPLE_S16_PEAK = 2)", where, what, (int)format);
+        return 2;
+    }
+    if (format == FSNP_SAMPLE_S16_PEAK && !peak_ok) {
+        set_error("%s: FSNP_SAMPLE_S16_PEAK is an output format of whole-clip calls only (%s): a stream has no peak, an input no scale", where, what);
+        return 2;
+    }
+    if (step < 1) { set_error("%s: %s step %lld < 1 (elements between consecutive samples of a row)", where, what, (long long)step); return 2; }
+    return 0;
+}
+
+namespace {
+int stft_any(fsnp_handle* h, const char* where, const PcmIn& wav, float* spec, int32_t batch, int32_t samples, void* hip_stream) {
+    if (batch <= 0) { set_error("%s: empty input", where); return 2; }
+    if (ensure_stft(h)) return 2;
+    const StftPlan p = stft_plan(h);
+    if (samples <= p.half) { set_error("%s: need more than n_fft/2 = %d samples (reflect padding)", where, p.half); return 2; }
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    FSNP_ON_DEVICE(h);
+    const long xs = (long)align_up((size_t)samples + p.n_fft, 4);
+    if (order_after_last_forward(h, s)) return 4;
+    if (ensure_io(h, (size_t)batch * xs * 4, s)) return 4;
+    stft_into(h, p, wav, reinterpret_cast<float*>(h->io), xs, spec, p.N2, batch, samples, s);
+    FSNP_HIP_CHECK(hipGetLastError());
+    return mark_forward_done(h, s);
+}
+
+// fsnp_enhance_wave (samples = NULL: every row holds max_samples samples) and fsnp_enhance_wave_lengths behind every entry point;
+// out.fmt may be kPcmPeak, out.clipped the caller's (NULL or device int32 [batch], overwritten)
+int enhance_wave_any(fsnp_handle* h, const char* where, const PcmIn& wav, const PcmOut& out, const int32_t* samples, int32_t batch,
+                     int32_t max_samples, void* hip_stream) {
+    if (batch <= 0) { set_error("%s: empty input", where); return 2; }
+    if (!h->committed) { set_error("%s: weights not committed (call fsnp_commit_weights)", where); return 2; }
+    // the cIRM epilogue multiplies by exactly two mask planes (decompress_cIRM, audio_zen/acoustics/mask.py:60-63) and the io area is
+    // sized for them: a model built with another output_size has no waveform path (ADVICE r04)
+    if (h->cfg.output_size != 2) { set_error("%s: the cIRM epilogue needs output_size = 2 (this handle: %d)", where, h->cfg.output_size); return 2; }
+    if (ensure_stft(h)) return 2;
+    const StftPlan p = stft_plan(h);
+    if (max_samples <= p.half) { set_error("%s: need more than n_fft/2 = %d samples (reflect padding)", where, p.half); return 2; }
+    // every check of the forward too, before anything is enqueued: each clip's frame count is its own STFT's, T_b = 1 + samples[b] / hop
+    const int T = 1 + max_samples / p.hop;
+    std::vector<int32_t> frames;
+    if (samples) {
+        frames.resize(batch);
+        for (int b = 0; b < batch; ++b) {
+            if (samples[b] <= p.half || samples[b] > max_samples) {
+                set_error("%s: utterance %d: %d samples outside (n_fft/2 = %d, %d]", where, b, (int)samples[b], p.half, max_samples);
+                return 2;
+            }
+            frames[b] = 1 + samples[b] / p.hop;
+        }
+        if (const int rc = check_lengths(h, frames.data(), batch, T, where)) return rc;
+    }
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    FSNP_ON_DEVICE(h);
+    const long xs = (long)align_up((size_t)max_samples + p.n_fft, 4);
+    const size_t xp_b = align_up((size_t)batch * xs * 4, 256), spec_b = align_up((size_t)batch * T * p.sp * 4 + 256, 256);
+    const size_t mask_b = align_up((size_t)batch * 2 * p.F * T * 4, 256), fr_b = (size_t)batch * T * p.n_fft * 4;
+    if (order_after_last_forward(h, s)) return 4;
+    if (ensure_io(h, xp_b + 2 * spec_b + mask_b + fr_b, s)) return 4;
+    float* xp = reinterpret_cast<float*>(h->io);
+    float* noisy = reinterpret_cast<float*>(h->io + xp_b);
+    float* enh = reinterpret_cast<float*>(h->io + xp_b + spec_b);
+    float* mask = reinterpret_cast<float*>(h->io + xp_b + 2 * spec_b);
+    float* fr = reinterpret_cast<float*>(h->io + xp_b + 2 * spec_b + mask_b);
+    // inferencer.py:142-158: stft -> (mag, real, imag) -> model -> decompress_cIRM, complex multiply -> istft(length); with lengths
+    // the reflect padding at each clip's end (frames past T_b see zeros: the forward never reads them)
+    if (samples) {
+        launch_stft_pad_lengths(wav, xp, xs, batch, samples, p.n_fft, s);
+        launch_linear_act(xp, p.hop, h->d_stft + p.o_fwd, p.fwd_ld, h->d_stft + p.o_zero, noisy, p.sp, p.n_fft, p.N2, batch, T,
+                          FSNP_ACT_NONE, h->num_cus, s, xs, p.n_fft);
+    } else {
+        stft_into(h, p, wav, xp, xs, noisy, p.sp, batch, max_samples, s);
+    }
+    const int64_t cst[3] = {(int64_t)T * (p.sp / 2), 1, p.sp / 2};       // complex-element strides of [B][T][sp/2] as (b, f, t)
+    const int rc = samples ? fsnp_forward_complex_lengths(h, noisy, cst, frames.data(), mask, batch, T, hip_stream)
+                           : fsnp_forward_complex(h, noisy, cst, mask, batch, T, FSNP_MODE_FULL, 0, batch, hip_stream);
+    if (rc) return rc;
+    // pipelined mode: the forward left chunks of the sub-band plan on the side stream (at B = 1 the whole plan); `mask` is read
+    // right here and lives in the single-buffered io area, so `s` waits for them now (fsnp_flush) - nothing of this call is deferred
+    if (h->pipeline && fsnp_flush(h, hip_stream)) return 4;
+    // the pad column of every row of `enh` is never written by apply_cirm and multiplies zero weights: clear it once
+    FSNP_HIP_CHECK(hipMemsetAsync(enh, 0, spec_b, s));
+    if (samples) launch_apply_cirm_lengths(mask, noisy, cst, enh, cst, batch, p.F, T, frames.data(), s);      // frames >= T_b: 0
+    else launch_apply_cirm(mask, noisy, cst, enh, cst, batch, p.F, T, s);
+    launch_linear_act(enh, p.sp, h->d_stft + p.o_inv, p.inv_ld, h->d_stft + p.o_zero, fr, p.n_fft, p.N2, p.n_fft, batch, T,
+                      FSNP_ACT_NONE, h->num_cus, s, (long)T * p.sp, p.N2);
+    // the samples out, in the caller's format.  FSNP_SAMPLE_S16_PEAK needs the clip's peak before any sample can be written: the
+    // overlap-add stages fp32 rows where the padded input was and folds |v| into per-row maxima where the noisy spectra were (both are
+    // dead by now, so the area fsnp_reserve sized is enough), and a second kernel scales and truncates
+    PcmOut o = out;
+    if (out.clipped) FSNP_HIP_CHECK(hipMemsetAsync(out.clipped, 0, (size_t)batch * 4, s));
+    if (out.fmt != kPcmS16) o.clipped = nullptr;                          // nothing clips in the other formats
+    if (out.fmt == kPcmPeak) {
+        FSNP_HIP_CHECK(hipMemsetAsync(noisy, 0, (size_t)batch * 4, s));
+        o = PcmOut{xp, xs, 1, kPcmPeak, nullptr, reinterpret_cast<unsigned*>(noisy)};
+    }
+    if (samples) launch_istft_ola_lengths(fr, h->d_stft + p.o_win, o, batch, T, max_samples, samples, p.n_fft, p.hop, s);
+    else launch_istft_ola(fr, h->d_stft + p.o_win, o, batch, T, max_samples, p.n_fft, p.hop, s);
+    if (out.fmt == kPcmPeak)
+        launch_pcm_peak_scale(xp, xs, o.peak, PcmOut{out.p, out.stride, out.step, kPcmS16, nullptr, nullptr}, batch, max_samples, s);
+    FSNP_HIP_CHECK(hipGetLastError());
+    return mark_forward_done(h, s);
+}
+}  // namespace
 }  // namespace fsnp
 
 extern "C" {
 
 int fsnp_stft(fsnp_handle* h, const float* wav, int64_t wav_stride, float* spec, int32_t batch, int32_t samples, void* hip_stream) {
     if (!h || !wav || !spec) { set_error("fsnp_stft: null argument"); return 1; }
-    if (batch <= 0) { set_error("fsnp_stft: empty input"); return 2; }
-    if (ensure_stft(h)) return 2;
-    const StftPlan p = stft_plan(h);
-    if (samples <= p.half) { set_error("fsnp_stft: need more than n_fft/2 = %d samples (reflect padding)", p.half); return 2; }
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    FSNP_ON_DEVICE(h);
-    const long xs = (long)align_up((size_t)samples + p.n_fft, 4);
-    if (order_after_last_forward(h, s)) return 4;
-    if (ensure_io(h, (size_t)batch * xs * 4, s)) return 4;
-    stft_into(h, p, wav, wav_stride, reinterpret_cast<float*>(h->io), xs, spec, p.N2, batch, samples, s);
-    FSNP_HIP_CHECK(hipGetLastError());
-    return mark_forward_done(h, s);
+    return stft_any(h, "fsnp_stft", pcm_in_f32(wav, (long)wav_stride), spec, batch, samples, hip_stream);
+}
+
+int fsnp_stft_pcm(fsnp_handle* h, const void* wav, int32_t in_format, int64_t wav_stride, int64_t wav_step, float* spec, int32_t batch,
+                  int32_t samples, void* hip_stream) {
+    if (!h || !wav || !spec) { set_error("fsnp_stft_pcm: null argument"); return 1; }
+    if (const int rc = check_sample_format("fsnp_stft_pcm", "input", in_format, wav_step, false)) return rc;
+    return stft_any(h, "fsnp_stft_pcm", PcmIn{wav, (long)wav_stride, (long)wav_step, in_format}, spec, batch, samples, hip_stream);
 }
 
 int fsnp_istft(fsnp_handle* h, const float* spec, const int64_t strides[3], float* wav, int64_t wav_stride, int32_t batch,
@@ -123,90 +228,25 @@ int fsnp_istft(fsnp_handle* h, const float* spec, const int64_t strides[3], floa
 int fsnp_enhance_wave(fsnp_handle* h, const float* wav, int64_t wav_stride, float* out, int64_t out_stride, int32_t batch,
                       int32_t samples, void* hip_stream) {
     if (!h || !wav || !out) { set_error("fsnp_enhance_wave: null argument"); return 1; }
-    if (batch <= 0) { set_error("fsnp_enhance_wave: empty input"); return 2; }
-    if (!h->committed) { set_error("fsnp_enhance_wave: weights not committed (call fsnp_commit_weights)"); return 2; }
-    // the cIRM epilogue multiplies by exactly two mask planes (decompress_cIRM, audio_zen/acoustics/mask.py:60-63) and the io area is
-    // sized for them: a model built with another output_size has no waveform path (ADVICE r04)
-    if (h->cfg.output_size != 2) { set_error("fsnp_enhance_wave: the cIRM epilogue needs output_size = 2 (this handle: %d)", h->cfg.output_size); return 2; }
-    if (ensure_stft(h)) return 2;
-    const StftPlan p = stft_plan(h);
-    if (samples <= p.half) { set_error("fsnp_enhance_wave: need more than n_fft/2 = %d samples (reflect padding)", p.half); return 2; }
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    FSNP_ON_DEVICE(h);
-    const int T = 1 + samples / p.hop;
-    const long xs = (long)align_up((size_t)samples + p.n_fft, 4);
-    const size_t xp_b = align_up((size_t)batch * xs * 4, 256), spec_b = align_up((size_t)batch * T * p.sp * 4 + 256, 256);
-    const size_t mask_b = align_up((size_t)batch * 2 * p.F * T * 4, 256), fr_b = (size_t)batch * T * p.n_fft * 4;
-    if (order_after_last_forward(h, s)) return 4;
-    if (ensure_io(h, xp_b + 2 * spec_b + mask_b + fr_b, s)) return 4;
-    float* xp = reinterpret_cast<float*>(h->io);
-    float* noisy = reinterpret_cast<float*>(h->io + xp_b);
-    float* enh = reinterpret_cast<float*>(h->io + xp_b + spec_b);
-    float* mask = reinterpret_cast<float*>(h->io + xp_b + 2 * spec_b);
-    float* fr = reinterpret_cast<float*>(h->io + xp_b + 2 * spec_b + mask_b);
-    // inferencer.py:142-158: stft -> (mag, real, imag) -> model -> decompress_cIRM, complex multiply -> istft(length)
-    stft_into(h, p, wav, wav_stride, xp, xs, noisy, p.sp, batch, samples, s);
-    const int64_t cst[3] = {(int64_t)T * (p.sp / 2), 1, p.sp / 2};       // complex-element strides of [B][T][sp/2] as (b, f, t)
-    const int rc = fsnp_forward_complex(h, noisy, cst, mask, batch, T, FSNP_MODE_FULL, 0, batch, hip_stream);
-    if (rc) return rc;
-    // pipelined mode: the forward left chunks of the sub-band plan on the side stream (at B = 1 the whole plan); `mask` is read
-    // right here and lives in the single-buffered io area, so `s` waits for them now (fsnp_flush) - nothing of this call is deferred
-    if (h->pipeline && fsnp_flush(h, hip_stream)) return 4;
-    // the pad column of every row of `enh` is never written by apply_cirm and multiplies zero weights: clear it once
-    FSNP_HIP_CHECK(hipMemsetAsync(enh, 0, spec_b, s));
-    launch_apply_cirm(mask, noisy, cst, enh, cst, batch, p.F, T, s);
-    istft_from(h, p, enh, fr, out, out_stride, batch, T, samples, s);
-    FSNP_HIP_CHECK(hipGetLastError());
-    return mark_forward_done(h, s);
+    return enhance_wave_any(h, "fsnp_enhance_wave", pcm_in_f32(wav, (long)wav_stride), pcm_out_f32(out, (long)out_stride), nullptr, batch,
+                            samples, hip_stream);
 }
 
 int fsnp_enhance_wave_lengths(fsnp_handle* h, const float* wav, int64_t wav_stride, float* out, int64_t out_stride, const int32_t* samples,
                               int32_t batch, int32_t max_samples, void* hip_stream) {
     if (!h || !wav || !out || !samples) { set_error("fsnp_enhance_wave_lengths: null argument"); return 1; }
-    if (batch <= 0) { set_error("fsnp_enhance_wave_lengths: empty input"); return 2; }
-    if (!h->committed) { set_error("fsnp_enhance_wave_lengths: weights not committed (call fsnp_commit_weights)"); return 2; }
-    if (h->cfg.output_size != 2) { set_error("fsnp_enhance_wave_lengths: the cIRM epilogue needs output_size = 2 (this handle: %d)", h->cfg.output_size); return 2; }
-    if (ensure_stft(h)) return 2;
-    const StftPlan p = stft_plan(h);
-    if (max_samples <= p.half) { set_error("fsnp_enhance_wave_lengths: need more than n_fft/2 = %d samples (reflect padding)", p.half); return 2; }
-    // every check of the forward too, before anything is enqueued: each clip's frame count is its own STFT's, T_b = 1 + samples[b] / hop
-    const int T = 1 + max_samples / p.hop;
-    std::vector<int32_t> frames(batch);
-    for (int b = 0; b < batch; ++b) {
-        if (samples[b] <= p.half || samples[b] > max_samples) {
-            set_error("fsnp_enhance_wave_lengths: utterance %d: %d samples outside (n_fft/2 = %d, %d]", b, (int)samples[b], p.half, max_samples);
-            return 2;
-        }
-        frames[b] = 1 + samples[b] / p.hop;
-    }
-    if (const int rc = check_lengths(h, frames.data(), batch, T, "fsnp_enhance_wave_lengths")) return rc;
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    FSNP_ON_DEVICE(h);
-    const long xs = (long)align_up((size_t)max_samples + p.n_fft, 4);
-    const size_t xp_b = align_up((size_t)batch * xs * 4, 256), spec_b = align_up((size_t)batch * T * p.sp * 4 + 256, 256);
-    const size_t mask_b = align_up((size_t)batch * 2 * p.F * T * 4, 256), fr_b = (size_t)batch * T * p.n_fft * 4;
-    if (order_after_last_forward(h, s)) return 4;
-    if (ensure_io(h, xp_b + 2 * spec_b + mask_b + fr_b, s)) return 4;
-    float* xp = reinterpret_cast<float*>(h->io);
-    float* noisy = reinterpret_cast<float*>(h->io + xp_b);
-    float* enh = reinterpret_cast<float*>(h->io + xp_b + spec_b);
-    float* mask = reinterpret_cast<float*>(h->io + xp_b + 2 * spec_b);
-    float* fr = reinterpret_cast<float*>(h->io + xp_b + 2 * spec_b + mask_b);
-    // as fsnp_enhance_wave, with the reflect padding at each clip's end (frames past T_b see zeros: the forward never reads them)
-    launch_stft_pad_lengths(wav, wav_stride, xp, xs, batch, samples, p.n_fft, s);
-    launch_linear_act(xp, p.hop, h->d_stft + p.o_fwd, p.fwd_ld, h->d_stft + p.o_zero, noisy, p.sp, p.n_fft, p.N2, batch, T,
-                      FSNP_ACT_NONE, h->num_cus, s, xs, p.n_fft);
-    const int64_t cst[3] = {(int64_t)T * (p.sp / 2), 1, p.sp / 2};
-    const int rc = fsnp_forward_complex_lengths(h, noisy, cst, frames.data(), mask, batch, T, hip_stream);
-    if (rc) return rc;
-    if (h->pipeline && fsnp_flush(h, hip_stream)) return 4;
-    FSNP_HIP_CHECK(hipMemsetAsync(enh, 0, spec_b, s));
-    launch_apply_cirm_lengths(mask, noisy, cst, enh, cst, batch, p.F, T, frames.data(), s);      // frames >= T_b: 0
-    launch_linear_act(enh, p.sp, h->d_stft + p.o_inv, p.inv_ld, h->d_stft + p.o_zero, fr, p.n_fft, p.N2, p.n_fft, batch, T,
-                      FSNP_ACT_NONE, h->num_cus, s, (long)T * p.sp, p.N2);
-    launch_istft_ola_lengths(fr, h->d_stft + p.o_win, out, out_stride, batch, T, max_samples, samples, p.n_fft, p.hop, s);
-    FSNP_HIP_CHECK(hipGetLastError());
-    return mark_forward_done(h, s);
+    return enhance_wave_any(h, "fsnp_enhance_wave_lengths", pcm_in_f32(wav, (long)wav_stride), pcm_out_f32(out, (long)out_stride), samples,
+                            batch, max_samples, hip_stream);
+}
+
+int fsnp_enhance_wave_pcm(fsnp_handle* h, const void* wav, int32_t in_format, int64_t wav_stride, int64_t wav_step, void* out,
+                          int32_t out_format, int64_t out_stride, int64_t out_step, const int32_t* samples, int32_t batch,
+                          int32_t max_samples, int32_t* clipped, void* hip_stream) {
+    if (!h || !wav || !out) { set_error("fsnp_enhance_wave_pcm: null argument"); return 1; }
+    if (const int rc = check_sample_format("fsnp_enhance_wave_pcm", "input", in_format, wav_step, false)) return rc;
+    if (const int rc = check_sample_format("fsnp_enhance_wave_pcm", "output", out_format, out_step, true)) return rc;
+    return enhance_wave_any(h, "fsnp_enhance_wave_pcm", PcmIn{wav, (long)wav_stride, (long)wav_step, in_format},
+                            PcmOut{out, (long)out_stride, (long)out_step, out_format, clipped, nullptr}, samples, batch, max_samples, hip_stream);
 }
 
 // ---------------------------------------------------------------------------------------------- include/fsnp_stft_geometry.h

@@ -14,11 +14,13 @@
 // fsnp_wave_stream_finish runs the same chain with the clip's last frames (1 + L / hop - nf(L) <= ceil(n_fft / (2 hop)) of them, each
 // reflected at the end) and look_ahead zero frames into the model, emits the remaining D samples and resets the slots.  The session keeps
 // the hop its handle had at creation (include/fsnp_stft_geometry.h).  The host mirrors every slot's sample count,
-// so frames per slot are known without asking the device.
+// so frames per slot are known without asking the device.  The fp32 entry points and the ones of include/fsnp_pcm.h are one push and
+// one finish behind two sets of checks: the sample format is a property of the two kernels' loads and stores (pcm.h), not of the session.
 #include <algorithm>
 #include <vector>
 
 #include "fsnp_handle.h"
+#include "pcm.h"
 
 struct fsnp_wave_stream {
     fsnp_handle* h = nullptr;
@@ -37,8 +39,7 @@ struct fsnp_wave_stream {
 namespace {
 
 // the chain of one push (fin = 0, c.v = samples per slot) or one finish (fin = 1, c.v = 1 for the slots that end): checks are done
-int wave_run(fsnp_wave_stream* w, const SlotCounts& c, int fin, const float* wav, long wav_stride, float* out, long out_stride, int ncols,
-             hipStream_t s) {
+int wave_run(fsnp_wave_stream* w, const SlotCounts& c, int fin, const PcmIn& wav, const PcmOut& out, int ncols, hipStream_t s) {
     fsnp_handle* h = w->h;
     const StftPlan& p = w->p;
     SlotCounts spectra{}, steps{};
@@ -56,7 +57,7 @@ int wave_run(fsnp_wave_stream* w, const SlotCounts& c, int fin, const float* wav
     a.meta = reinterpret_cast<WaveMeta*>(w->ws + w->w_meta);
     a.S = w->S; a.hop = w->hop; a.half = w->half; a.LA = w->LA; a.nrow = nrow; a.xl = p.xl;
     const int rows = w->S * nrow;
-    launch_wave_gather(a, c, fin, wav, wav_stride, fptr(w->w_xfr), s);
+    launch_wave_gather(a, c, fin, wav, fptr(w->w_xfr), s);
     if (frames > 0)
         launch_linear_act(fptr(w->w_xfr), p.xl, h->d_stft + p.o_fwd, p.fwd_ld, h->d_stft + p.o_zero, fptr(w->w_spec), p.sp, p.n_fft, p.N2, 1,
                           rows, FSNP_ACT_NONE, h->num_cus, s);
@@ -69,7 +70,7 @@ int wave_run(fsnp_wave_stream* w, const SlotCounts& c, int fin, const float* wav
     if (frames > 0)
         launch_linear_act(fptr(w->w_enh), p.sp, h->d_stft + p.o_inv, p.inv_ld, h->d_stft + p.o_zero, fptr(w->w_fr), p.n_fft, p.N2, p.n_fft, 1,
                           rows, FSNP_ACT_NONE, h->num_cus, s, 0, p.N2);
-    launch_wave_ola(a, fptr(w->w_fr), h->d_stft + p.o_win, out, out_stride, ncols, s);
+    launch_wave_ola(a, fptr(w->w_fr), h->d_stft + p.o_win, out, ncols, s);
     FSNP_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -145,6 +146,36 @@ int wave_create(fsnp_handle* h, int32_t slots, int32_t max_samples, int live, co
     return 0;
 }
 
+// fsnp_wave_stream_push / _push_pcm and fsnp_wave_stream_finish / _finish_pcm behind their own checks
+int wave_push(fsnp_wave_stream* w, const char* where, const PcmIn& wav, const int32_t* counts, const PcmOut& out, int32_t n, void* hip_stream) {
+    if (n < 1 || n > w->max_samples) { set_error("%s: n = %d outside [1, max_samples = %d]", where, n, w->max_samples); return 2; }
+    SlotCounts c{};
+    if (const int rc = read_counts(where, counts, w->S, n, c)) return rc;
+    if (const int rc = push_preamble(w->h, where)) return rc;
+    if (const int rc = wave_run(w, c, 0, wav, out, n, static_cast<hipStream_t>(hip_stream))) return rc;
+    for (int b = 0; b < w->S; ++b) w->samples[b] += c.v[b];
+    return 0;
+}
+
+int wave_finish(fsnp_wave_stream* w, const char* where, const int32_t* slots, int32_t num, const PcmOut& out, void* hip_stream) {
+    if (const int rc = check_slots(where, slots, num, w->S)) return rc;
+    SlotCounts c{};
+    if (slots) for (int i = 0; i < num; ++i) c.v[slots[i]] = 1;
+    else for (int b = 0; b < w->S; ++b) c.v[b] = 1;
+    for (int b = 0; b < w->S; ++b) {
+        if (!c.v[b]) continue;
+        if (w->samples[b] == 0) { c.v[b] = 0; continue; }      // nothing to finish: a row of zeros
+        if (w->samples[b] <= w->half) {
+            set_error("%s: slot %d holds %lld samples: a clip needs more than n_fft/2 = %d (reflect padding)", where, b,
+                      (long long)w->samples[b], w->half);
+            return 2;
+        }
+    }
+    if (const int rc = push_preamble(w->h, where)) return rc;
+    if (const int rc = wave_run(w, c, 1, PcmIn{nullptr, 0, 1, kPcmF32}, out, w->D, static_cast<hipStream_t>(hip_stream))) return rc;
+    return wave_reset(w, slots, num, hip_stream);
+}
+
 }  // namespace
 
 extern "C" {
@@ -171,33 +202,30 @@ void fsnp_wave_stream_destroy(fsnp_wave_stream* w) {
 int fsnp_wave_stream_push(fsnp_wave_stream* w, const float* wav, int64_t wav_stride, const int32_t* counts, float* out, int64_t out_stride,
                           int32_t n, void* hip_stream) {
     if (!w || !wav || !out) { set_error("fsnp_wave_stream_push: null argument"); return 1; }
-    if (n < 1 || n > w->max_samples) { set_error("fsnp_wave_stream_push: n = %d outside [1, max_samples = %d]", n, w->max_samples); return 2; }
-    SlotCounts c{};
-    if (const int rc = read_counts("fsnp_wave_stream_push", counts, w->S, n, c)) return rc;
-    if (const int rc = push_preamble(w->h, "fsnp_wave_stream_push")) return rc;
-    if (const int rc = wave_run(w, c, 0, wav, (long)wav_stride, out, (long)out_stride, n, static_cast<hipStream_t>(hip_stream))) return rc;
-    for (int b = 0; b < w->S; ++b) w->samples[b] += c.v[b];
-    return 0;
+    return wave_push(w, "fsnp_wave_stream_push", pcm_in_f32(wav, (long)wav_stride), counts, pcm_out_f32(out, (long)out_stride), n, hip_stream);
+}
+
+int fsnp_wave_stream_push_pcm(fsnp_wave_stream* w, const void* wav, int32_t in_format, int64_t wav_stride, int64_t wav_step,
+                              const int32_t* counts, void* out, int32_t out_format, int64_t out_stride, int64_t out_step, int32_t n,
+                              void* hip_stream) {
+    if (!w || !wav || !out) { set_error("fsnp_wave_stream_push_pcm: null argument"); return 1; }
+    if (const int rc = check_sample_format("fsnp_wave_stream_push_pcm", "input", in_format, wav_step, false)) return rc;
+    if (const int rc = check_sample_format("fsnp_wave_stream_push_pcm", "output", out_format, out_step, false)) return rc;
+    return wave_push(w, "fsnp_wave_stream_push_pcm", PcmIn{wav, (long)wav_stride, (long)wav_step, in_format}, counts,
+                     PcmOut{out, (long)out_stride, (long)out_step, out_format, nullptr, nullptr}, n, hip_stream);
 }
 
 int fsnp_wave_stream_finish(fsnp_wave_stream* w, const int32_t* slots, int32_t num, float* out, int64_t out_stride, void* hip_stream) {
     if (!w || !out) { set_error("fsnp_wave_stream_finish: null argument"); return 1; }
-    if (const int rc = check_slots("fsnp_wave_stream_finish", slots, num, w->S)) return rc;
-    SlotCounts c{};
-    if (slots) for (int i = 0; i < num; ++i) c.v[slots[i]] = 1;
-    else for (int b = 0; b < w->S; ++b) c.v[b] = 1;
-    for (int b = 0; b < w->S; ++b) {
-        if (!c.v[b]) continue;
-        if (w->samples[b] == 0) { c.v[b] = 0; continue; }      // nothing to finish: a row of zeros
-        if (w->samples[b] <= w->half) {
-            set_error("fsnp_wave_stream_finish: slot %d holds %lld samples: a clip needs more than n_fft/2 = %d (reflect padding)", b,
-                      (long long)w->samples[b], w->half);
-            return 2;
-        }
-    }
-    if (const int rc = push_preamble(w->h, "fsnp_wave_stream_finish")) return rc;
-    if (const int rc = wave_run(w, c, 1, nullptr, 0, out, (long)out_stride, w->D, static_cast<hipStream_t>(hip_stream))) return rc;
-    return wave_reset(w, slots, num, hip_stream);
+    return wave_finish(w, "fsnp_wave_stream_finish", slots, num, pcm_out_f32(out, (long)out_stride), hip_stream);
+}
+
+int fsnp_wave_stream_finish_pcm(fsnp_wave_stream* w, const int32_t* slots, int32_t num, void* out, int32_t out_format, int64_t out_stride,
+                                int64_t out_step, void* hip_stream) {
+    if (!w || !out) { set_error("fsnp_wave_stream_finish_pcm: null argument"); return 1; }
+    if (const int rc = check_sample_format("fsnp_wave_stream_finish_pcm", "output", out_format, out_step, false)) return rc;
+    return wave_finish(w, "fsnp_wave_stream_finish_pcm", slots, num, PcmOut{out, (long)out_stride, (long)out_step, out_format, nullptr, nullptr},
+                       hip_stream);
 }
 
 int fsnp_wave_stream_reset(fsnp_wave_stream* w, const int32_t* slots, int32_t num, void* hip_stream) {

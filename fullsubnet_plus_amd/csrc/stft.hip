@@ -13,32 +13,39 @@
 //          wav[i] = (sum_t fr[t][i + N/2 - t*hop]) / (sum_t w^2[i + N/2 - t*hop])   (torch.istft's envelope division).
 // Geometry (include/fsnp_stft_geometry.h): n_fft = 2 (F - 1), window = periodic hann(n_fft), N/8 <= hop <= N/2 with hop % 4 == 0 (the A
 // rows above are read as float4); T = 1 + L / hop frames, the reflect padding is N/2 whatever the hop.
+// Samples come in and go out in the formats of include/fsnp_pcm.h (pcm.h): fp32 or int16, at any sample step, converted in the
+// pad kernels' loads and the overlap-add kernels' stores.  One workgroup works on one row (blockIdx.y), so that a wave's clipped
+// count and peak belong to one row.
 #include <cmath>
 
 #include "fsnp_common.h"
+#include "pcm.h"
 
 namespace fsnp {
 
-__global__ __launch_bounds__(256) void stft_pad_kernel(const float* __restrict__ wav, long wav_stride, float* __restrict__ xp,
-                                                       long xp_stride, int L, int half, long total) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;      // index into [B][L + 2 half (+ tail)]
-    if (i >= total) return;
-    const int b = (int)(i / xp_stride);
-    const int p = (int)(i - (long)b * xp_stride);
+template <int FMT>
+__global__ __launch_bounds__(256) void stft_pad_kernel(PcmIn wav, float* __restrict__ xp, long xp_stride, int L, int half) {
+    const int b = blockIdx.y;
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;      // index into row b of [B][L + 2 half (+ tail)]
+    if (p >= xp_stride) return;
     float v = 0.0f;
     if (p < L + 2 * half) {
-        int j = p - half;                                      // torch "reflect": no edge repeat
+        int j = (int)p - half;                                 // torch "reflect": no edge repeat
         if (j < 0) j = -j;
         if (j >= L) j = 2 * (L - 1) - j;
-        v = wav[(long)b * wav_stride + j];
+        v = pcm_load<FMT>(wav, b, j);
     }
-    xp[i] = v;
+    xp[(long)b * xp_stride + p] = v;
 }
 
-void launch_stft_pad(const float* wav, long wav_stride, float* xp, long xp_stride, int B, int L, int n_fft, hipStream_t s) {
-    const long total = (long)B * xp_stride;
-    hipLaunchKernelGGL(stft_pad_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, wav, wav_stride, xp, xp_stride,
-                       L, n_fft / 2, total);
+void launch_stft_pad(const PcmIn& wav, float* xp, long xp_stride, int B, int L, int n_fft, hipStream_t s) {
+    for (int b0 = 0; b0 < B; b0 += kLenRows) {                 // (rows per launch: the grid's y extent)
+        const int rows = B - b0 < kLenRows ? B - b0 : kLenRows;
+        const dim3 grid((unsigned)((xp_stride + 255) / 256), rows);
+#define FSNP_CALL(F) hipLaunchKernelGGL(stft_pad_kernel<F>, grid, dim3(256), 0, s, pcm_rows(wav, b0), xp + (long)b0 * xp_stride, xp_stride, L, n_fft / 2)
+        FSNP_PCM_SWITCH2(wav.fmt, FSNP_CALL);
+#undef FSNP_CALL
+    }
 }
 
 // One output sample: overlap-add and envelope division over the frames t < T that cover it, t * hop - n_fft / 2 <= n < t * hop + n_fft / 2
@@ -73,87 +80,86 @@ __device__ __forceinline__ float istft_ola_sample(const float* __restrict__ fram
     return den > 1e-11f ? num / den : 0.0f;
 }
 
-template <bool HALF>
-__global__ __launch_bounds__(256) void istft_ola_kernel(const float* __restrict__ frames, const float* __restrict__ window,
-                                                        float* __restrict__ wav, long wav_stride, int T, int L, int n_fft, int hop,
-                                                        long total) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;      // (b, sample)
-    if (i >= total) return;
-    const int b = (int)(i / L), n = (int)(i % L);
-    wav[(long)b * wav_stride + n] = istft_ola_sample<HALF>(frames + (long)b * T * n_fft, window, n, T, n_fft, hop);
+template <bool HALF, int FMT>
+__global__ __launch_bounds__(256) void istft_ola_kernel(const float* __restrict__ frames, const float* __restrict__ window, PcmOut wav,
+                                                        int T, int L, int n_fft, int hop) {
+    const int b = blockIdx.y, n = blockIdx.x * 256 + threadIdx.x;      // (row, sample)
+    const bool live = n < L;
+    float v = 0.0f;
+    if (live) v = istft_ola_sample<HALF>(frames + (long)b * T * n_fft, window, n, T, n_fft, hop);
+    pcm_store<FMT>(wav, b, n, v, live);
 }
 
-void launch_istft_ola(const float* frames, const float* window, float* wav, long wav_stride, int B, int T, int L, int n_fft, int hop,
-                      hipStream_t s) {
-    const long total = (long)B * L;
-    const dim3 grid((unsigned)((total + 255) / 256));
-    if (2 * hop == n_fft)
-        hipLaunchKernelGGL(istft_ola_kernel<true>, grid, dim3(256), 0, s, frames, window, wav, wav_stride, T, L, n_fft, hop, total);
-    else
-        hipLaunchKernelGGL(istft_ola_kernel<false>, grid, dim3(256), 0, s, frames, window, wav, wav_stride, T, L, n_fft, hop, total);
+void launch_istft_ola(const float* frames, const float* window, const PcmOut& wav, int B, int T, int L, int n_fft, int hop, hipStream_t s) {
+    for (int b0 = 0; b0 < B; b0 += kLenRows) {
+        const int rows = B - b0 < kLenRows ? B - b0 : kLenRows;
+        const dim3 grid((unsigned)((L + 255) / 256), rows);
+        const float* fr = frames + (long)b0 * T * n_fft;
+#define FSNP_CALL(F)                                                                                                                     \
+    if (2 * hop == n_fft) hipLaunchKernelGGL((istft_ola_kernel<true, F>), grid, dim3(256), 0, s, fr, window, pcm_rows(wav, b0), T, L, n_fft, hop); \
+    else hipLaunchKernelGGL((istft_ola_kernel<false, F>), grid, dim3(256), 0, s, fr, window, pcm_rows(wav, b0), T, L, n_fft, hop)
+        FSNP_PCM_SWITCH3(wav.fmt, FSNP_CALL);
+#undef FSNP_CALL
+    }
 }
 
 // ---- clips of different lengths in one batch (fsnp_enhance_wave_lengths): row b is its own samples[b] long.  The sample counts travel
 // as kernel arguments (RowLengths: no copy to the device, nothing to synchronise), kLenRows rows per launch.
 
 // reflect padding at each row's own end (torch.stft of the clip alone), zeros behind it
-__global__ __launch_bounds__(256) void stft_pad_lengths_kernel(const float* __restrict__ wav, long wav_stride, float* __restrict__ xp,
-                                                               long xp_stride, int half, long total, RowLengths len) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= total) return;
-    const int b = (int)(i / xp_stride);
-    const int p = (int)(i - (long)b * xp_stride);
+template <int FMT>
+__global__ __launch_bounds__(256) void stft_pad_lengths_kernel(PcmIn wav, float* __restrict__ xp, long xp_stride, int half, RowLengths len) {
+    const int b = blockIdx.y;
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= xp_stride) return;
     const int L = len.v[b];
     float v = 0.0f;
     if (p < L + 2 * half) {
-        int j = p - half;
+        int j = (int)p - half;
         if (j < 0) j = -j;
         if (j >= L) j = 2 * (L - 1) - j;
-        v = wav[(long)b * wav_stride + j];
+        v = pcm_load<FMT>(wav, b, j);
     }
-    xp[i] = v;
+    xp[(long)b * xp_stride + p] = v;
 }
 
-void launch_stft_pad_lengths(const float* wav, long wav_stride, float* xp, long xp_stride, int B, const int* samples, int n_fft, hipStream_t s) {
+void launch_stft_pad_lengths(const PcmIn& wav, float* xp, long xp_stride, int B, const int* samples, int n_fft, hipStream_t s) {
     for (int b0 = 0; b0 < B; b0 += kLenRows) {
         const int rows = B - b0 < kLenRows ? B - b0 : kLenRows;
         RowLengths len{};
         for (int r = 0; r < rows; ++r) len.v[r] = samples[b0 + r];
-        const long total = (long)rows * xp_stride;
-        hipLaunchKernelGGL(stft_pad_lengths_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, wav + (long)b0 * wav_stride,
-                           wav_stride, xp + (long)b0 * xp_stride, xp_stride, n_fft / 2, total, len);
+        const dim3 grid((unsigned)((xp_stride + 255) / 256), rows);
+#define FSNP_CALL(F) hipLaunchKernelGGL(stft_pad_lengths_kernel<F>, grid, dim3(256), 0, s, pcm_rows(wav, b0), xp + (long)b0 * xp_stride, xp_stride, n_fft / 2, len)
+        FSNP_PCM_SWITCH2(wav.fmt, FSNP_CALL);
+#undef FSNP_CALL
     }
 }
 
 // overlap-add and window-envelope division over row b's own 1 + samples[b] / hop frames (torch.istft(..., length=samples[b]) of the
 // clip alone: frame T_b, which still overlaps the clip's last samples, is not part of it); samples past samples[b] are written as 0
-template <bool HALF>
+template <bool HALF, int FMT>
 __global__ __launch_bounds__(256) void istft_ola_lengths_kernel(const float* __restrict__ frames, const float* __restrict__ window,
-                                                                float* __restrict__ wav, long wav_stride, int T, int L, int n_fft,
-                                                                int hop, long total, RowLengths len) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;      // (b, sample)
-    if (i >= total) return;
-    const int b = (int)(i / L), n = (int)(i % L);
+                                                                PcmOut wav, int T, int L, int n_fft, int hop, RowLengths len) {
+    const int b = blockIdx.y, n = blockIdx.x * 256 + threadIdx.x;      // (row, sample)
     const int Lb = len.v[b], Tb = 1 + Lb / hop;
     float out = 0.0f;
     if (n < Lb) out = istft_ola_sample<HALF>(frames + (long)b * T * n_fft, window, n, Tb, n_fft, hop);
-    wav[(long)b * wav_stride + n] = out;
+    pcm_store<FMT>(wav, b, n, out, n < L);
 }
 
-void launch_istft_ola_lengths(const float* frames, const float* window, float* wav, long wav_stride, int B, int T, int L, const int* samples,
-                              int n_fft, int hop, hipStream_t s) {
+void launch_istft_ola_lengths(const float* frames, const float* window, const PcmOut& wav, int B, int T, int L, const int* samples, int n_fft,
+                              int hop, hipStream_t s) {
     for (int b0 = 0; b0 < B; b0 += kLenRows) {
         const int rows = B - b0 < kLenRows ? B - b0 : kLenRows;
         RowLengths len{};
         for (int r = 0; r < rows; ++r) len.v[r] = samples[b0 + r];
-        const long total = (long)rows * L;
-        const dim3 grid((unsigned)((total + 255) / 256));
-        if (2 * hop == n_fft)
-            hipLaunchKernelGGL(istft_ola_lengths_kernel<true>, grid, dim3(256), 0, s, frames + (long)b0 * T * n_fft, window,
-                               wav + (long)b0 * wav_stride, wav_stride, T, L, n_fft, hop, total, len);
-        else
-            hipLaunchKernelGGL(istft_ola_lengths_kernel<false>, grid, dim3(256), 0, s, frames + (long)b0 * T * n_fft, window,
-                               wav + (long)b0 * wav_stride, wav_stride, T, L, n_fft, hop, total, len);
+        const dim3 grid((unsigned)((L + 255) / 256), rows);
+        const float* fr = frames + (long)b0 * T * n_fft;
+#define FSNP_CALL(F)                                                                                                                       \
+    if (2 * hop == n_fft) hipLaunchKernelGGL((istft_ola_lengths_kernel<true, F>), grid, dim3(256), 0, s, fr, window, pcm_rows(wav, b0), T, L, n_fft, hop, len); \
+    else hipLaunchKernelGGL((istft_ola_lengths_kernel<false, F>), grid, dim3(256), 0, s, fr, window, pcm_rows(wav, b0), T, L, n_fft, hop, len)
+        FSNP_PCM_SWITCH3(wav.fmt, FSNP_CALL);
+#undef FSNP_CALL
     }
 }
 

@@ -10,16 +10,18 @@
 // whole-clip path (launch_linear_act with the handle's matrices) and what lies between them is a spectrum session's push
 // (spec_push_body: |X|, the mag push, cIRM times the waiting spectrum); the two kernels here gather the frame rows in front of it and
 // overlap-add behind it, and carry what a later push needs (layout: fsnp_common.h, WaveArgs).  {P, c} of every slot: c as a kernel
-// argument, P from the slot's record (WaveMeta).
+// argument, P from the slot's record (WaveMeta).  The caller's samples are read and written in the formats of include/fsnp_pcm.h
+// (pcm.h), converted in the gather's loads and the overlap-add's stores; the records (carry, partial sums, fifo) are fp32 whatever the format.
 #include "fsnp_common.h"
+#include "pcm.h"
 
 namespace fsnp {
 
 __device__ __forceinline__ unsigned char* wave_rec(const WaveArgs& a, int b) { return a.state + (size_t)b * a.stride; }
 
 // one workgroup per slot; dynamic LDS: the old carry, n_fft + 1 floats (the carry is rewritten in place)
-__global__ __launch_bounds__(256) void wave_gather_kernel(WaveArgs a, SlotCounts cnt, int fin_call, const float* __restrict__ wav,
-                                                          long wav_stride, float* __restrict__ xfr) {
+template <int FMT>
+__global__ __launch_bounds__(256) void wave_gather_kernel(WaveArgs a, SlotCounts cnt, int fin_call, PcmIn wav, float* __restrict__ xfr) {
     extern __shared__ float old[];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int hop = a.hop, half = a.half, N = 2 * half;
@@ -35,9 +37,8 @@ __global__ __launch_bounds__(256) void wave_gather_kernel(WaveArgs a, SlotCounts
     }
     const WaveStep w = wave_step(P, c, fin, hop, half, a.LA);
     const long long total = P + c;
-    const float* in = wav ? wav + (long)b * wav_stride : nullptr;
-    // sample i of the clip, P - (n_fft + 1) <= i < P + c
-    auto sample = [&](long long i) { return i < P ? old[(int)(i - P) + N + 1] : in[i - P]; };
+    // sample i of the clip, P - (n_fft + 1) <= i < P + c (a finish has no input and c = 0)
+    auto sample = [&](long long i) { return i < P ? old[(int)(i - P) + N + 1] : pcm_load<FMT>(wav, b, (long)(i - P)); };
     for (int idx = tid; idx < a.nrow * N; idx += 256) {
         const int j = idx / N, k = idx - j * N;
         float v = 0.0f;
@@ -56,15 +57,18 @@ __global__ __launch_bounds__(256) void wave_gather_kernel(WaveArgs a, SlotCounts
         }
 }
 
-void launch_wave_gather(const WaveArgs& a, const SlotCounts& c, int fin, const float* wav, long wav_stride, float* xfr, hipStream_t s) {
-    hipLaunchKernelGGL(wave_gather_kernel, dim3(a.S), dim3(256), (size_t)(2 * a.half + 1) * sizeof(float), s, a, c, fin, wav, wav_stride, xfr);
+void launch_wave_gather(const WaveArgs& a, const SlotCounts& c, int fin, const PcmIn& wav, float* xfr, hipStream_t s) {
+#define FSNP_CALL(F) hipLaunchKernelGGL(wave_gather_kernel<F>, dim3(a.S), dim3(256), (size_t)(2 * a.half + 1) * sizeof(float), s, a, c, fin, wav, xfr)
+    FSNP_PCM_SWITCH2(wav.fmt, FSNP_CALL);
+#undef FSNP_CALL
 }
 
 // one workgroup per slot; dynamic LDS: the old tail (n_fft - hop floats) and the old fifo (hop floats), both rewritten in place.  The
 // arithmetic of istft_ola_sample: the covering frames from the newest to the oldest, the ones of earlier calls through the tail's partial
 // sum, over the same frames' w^2, den > 1e-11.  At hop = half that is the two-frame sum the default geometry has always had, term by term.
+template <int FMT>
 __global__ __launch_bounds__(256) void wave_ola_kernel(WaveArgs a, const float* __restrict__ fr, const float* __restrict__ window,
-                                                       float* __restrict__ out, long out_stride, int ncols) {
+                                                       PcmOut out /*no clipped count: every thread stores on its own*/, int ncols) {
     extern __shared__ float lds[];
     const int b = blockIdx.x, tid = threadIdx.x;
     const int hop = a.hop, half = a.half, N = 2 * half, NT = N - hop;
@@ -103,7 +107,7 @@ __global__ __launch_bounds__(256) void wave_ola_kernel(WaveArgs a, const float* 
     for (int j = tid; j < ncols; j += 256) {
         float v = 0.0f;
         if (j < valid && first + j >= 0) v = sample(first + j);
-        out[(long)b * out_stride + j] = v;
+        pcm_store<FMT>(out, b, j, v, true);
     }
     if (m.c > 0) {
         const long long sent_new = m.p + m.c > D ? m.p + m.c - D : 0;
@@ -121,8 +125,10 @@ __global__ __launch_bounds__(256) void wave_ola_kernel(WaveArgs a, const float* 
     }
 }
 
-void launch_wave_ola(const WaveArgs& a, const float* fr, const float* window, float* out, long out_stride, int ncols, hipStream_t s) {
-    hipLaunchKernelGGL(wave_ola_kernel, dim3(a.S), dim3(256), (size_t)2 * a.half * sizeof(float), s, a, fr, window, out, out_stride, ncols);
+void launch_wave_ola(const WaveArgs& a, const float* fr, const float* window, const PcmOut& out, int ncols, hipStream_t s) {
+#define FSNP_CALL(F) hipLaunchKernelGGL(wave_ola_kernel<F>, dim3(a.S), dim3(256), (size_t)2 * a.half * sizeof(float), s, a, fr, window, out, ncols)
+    FSNP_PCM_SWITCH2(out.fmt, FSNP_CALL);
+#undef FSNP_CALL
 }
 
 }  // namespace fsnp

@@ -691,16 +691,40 @@ class _HipModel(nn.Module):
             wav = wav.contiguous()
         return wav, self._ensure_handle(wav.device), torch.cuda.current_stream(wav.device).cuda_stream
 
+    @staticmethod
+    def _pcm_view(wav):
+        """-> the tensor the PCM entry points read in place (include/fsnp_pcm.h: int16 or fp32 at any strides), or None where the
+        fp32 entry point takes it as it always has (contiguous rows, after .float())."""
+        if wav.dtype == torch.int16:
+            return wav
+        if wav.dtype == torch.float32 and wav.shape[1] > 1 and wav.stride(1) != 1:
+            return wav if wav.stride(1) >= 1 else wav.contiguous()
+        return None
+
     def stft(self, wav):
         """audio_zen/acoustics/feature.py:10-31 (torch.stft, n_fft = win_length = 2 (F - 1), hop_length = self.hop_length, hann, center)
-        in HIP: wav [B, samples] -> complex64 [B, F, T = 1 + samples // hop_length] with torch.stft's strides."""
-        wav, lib, stream = self._wave_args(wav)
+        in HIP: wav [B, samples] -> complex64 [B, F, T = 1 + samples // hop_length] with torch.stft's strides.  wav: fp32, or
+        torch.int16 full-scale PCM (the spectrum of wav.float() / 32768, bit for bit), rows and samples at any strides - one channel
+        of an interleaved buffer is read in place (fsnp_stft_pcm)."""
+        assert wav.dim() == 2, "expected [B, samples]"
+        if not wav.is_cuda:
+            raise RuntimeError("fullsubnet_plus_amd runs on MI355X (HIP) only; there is deliberately no CPU fallback.")
+        pcm = self._pcm_view(wav)
+        if pcm is None:
+            wav, lib, stream = self._wave_args(wav)
+        else:
+            wav, lib, stream = pcm, self._ensure_handle(pcm.device), torch.cuda.current_stream(pcm.device).cuda_stream
         B, L = wav.shape
         T = 1 + L // self.hop_length
         spec = torch.empty((B, T, self.num_freqs), dtype=torch.complex64, device=wav.device)
         with torch.cuda.device(wav.device):
-            _lib.check(lib.fsnp_stft(self._handle, wav.data_ptr(), wav.stride(0), torch.view_as_real(spec).data_ptr(), B, L,
-                                     ctypes.c_void_p(stream)), "fsnp_stft")
+            if pcm is None:
+                _lib.check(lib.fsnp_stft(self._handle, wav.data_ptr(), wav.stride(0), torch.view_as_real(spec).data_ptr(), B, L,
+                                         ctypes.c_void_p(stream)), "fsnp_stft")
+            else:
+                fmt = _lib.SAMPLE_S16 if wav.dtype == torch.int16 else _lib.SAMPLE_F32
+                _lib.check(lib.fsnp_stft_pcm(self._handle, wav.data_ptr(), fmt, wav.stride(0), max(wav.stride(1), 1),
+                                             torch.view_as_real(spec).data_ptr(), B, L, ctypes.c_void_p(stream)), "fsnp_stft_pcm")
         return spec.permute(0, 2, 1)
 
     def istft(self, spec, length):
@@ -718,7 +742,7 @@ class _HipModel(nn.Module):
                                       out.stride(0), B, T, int(length), ctypes.c_void_p(stream)), "fsnp_istft")
         return out
 
-    def enhance_wave(self, noisy, lengths=None):
+    def enhance_wave(self, noisy, lengths=None, out_format=None, clipped=None):
         """The reference inferencer's inner loop in ONE call (fullsubnet_plus/inferencer/inferencer.py:142-158,
         `mag_complex_full_band_crm_mask`; `full_band_crm_mask` of fullsubnet/inferencer/inferencer.py for the original
         FullSubNet): noisy waveform [B, samples] -> enhanced waveform [B, samples]; STFT, model (all bins), cIRM
@@ -726,9 +750,25 @@ class _HipModel(nn.Module):
         (1 + samples // hop_length model steps).  lengths: None, or SAMPLES per
         utterance (a Python sequence or a CPU integer tensor): row b is then enhance_wave(noisy[b:b+1, :lengths[b]]) of that
         clip alone, and 0 past lengths[b].  Follows error_check like forward: under "deferred", too, a `.data` edit that the weight
-        watch flagged on an earlier call is answered by a RuntimeWarning, a re-pack and the edited weights' result."""
+        watch flagged on an earlier call is answered by a RuntimeWarning, a re-pack and the edited weights' result.
+
+        PCM (include/fsnp_pcm.h): noisy may be torch.int16 (full scale: what noisy.float() / 32768 gives, bit for bit) and may have
+        any strides - a channel of an interleaved buffer is read in place, nothing is converted or copied in front.  out_format: None
+        (follow the input: float -> fp32 as ever, int16 -> "s16"), "f32", "s16" (int16, round half to even, saturating) or "s16_peak"
+        (int16, the reference CLI's peak normalisation np.int16(0.8 * 32767 * y / max|y|) over each clip's own samples).  clipped:
+        optional int32 CUDA tensor [B], overwritten with the number of samples of each row that saturated or were NaN ("s16" only:
+        0 for the other formats)."""
         assert self.output_size == 2, "the cIRM epilogue needs the two mask channels (decompress_cIRM, acoustics/mask.py:60-63)"
+        assert noisy.dim() == 2, "expected [B, samples]"
+        if out_format is not None and out_format not in _lib.SAMPLE_FORMATS:
+            raise ValueError(f"enhance_wave: out_format {out_format!r} is none of None, 'f32', 's16', 's16_peak'")
+        if not noisy.is_cuda:
+            raise RuntimeError("fullsubnet_plus_amd runs on MI355X (HIP) only; there is deliberately no CPU fallback.")
         samples = None if lengths is None else _host_lengths(lengths, noisy.shape[0], f"{self.__class__.__name__}.enhance_wave")
+        pcm = self._pcm_view(noisy)
+        ofmt = _lib.SAMPLE_FORMATS[out_format or ("s16" if noisy.dtype == torch.int16 else "f32")]
+        if pcm is not None or ofmt != _lib.SAMPLE_F32 or clipped is not None:
+            return self._enhance_wave_pcm(noisy if pcm is None else pcm, samples, ofmt, clipped)
         wav, lib, stream = self._wave_args(noisy)
         B, L = wav.shape
         out = torch.empty((B, L), dtype=torch.float32, device=wav.device)
@@ -744,6 +784,33 @@ class _HipModel(nn.Module):
 
         def run():
             _policy.enqueue_retrying_stale(enqueue, self._stale_weights_noticed, what)
+            return out
+        return self._checked(run)
+
+    def _enhance_wave_pcm(self, wav, samples, ofmt, clipped):
+        """enhance_wave through fsnp_enhance_wave_pcm: wav int16 or floating point at any strides, samples the ctypes int32[B] of
+        _host_lengths or None, ofmt a _lib.SAMPLE_* value."""
+        if wav.dtype not in (torch.int16, torch.float32):
+            wav = wav.float()
+        if wav.shape[1] > 1 and wav.stride(1) < 1:
+            wav = wav.contiguous()
+        B, L = wav.shape
+        if clipped is not None:
+            if not (clipped.is_cuda and clipped.device == wav.device and clipped.dtype == torch.int32 and clipped.shape == (B,)
+                    and clipped.is_contiguous()):
+                raise ValueError(f"enhance_wave: clipped must be a contiguous torch.int32 tensor [{B}] on {wav.device}")
+        lib, stream = self._ensure_handle(wav.device), torch.cuda.current_stream(wav.device).cuda_stream
+        ifmt = _lib.SAMPLE_S16 if wav.dtype == torch.int16 else _lib.SAMPLE_F32
+        out = torch.empty((B, L), dtype=torch.float32 if ofmt == _lib.SAMPLE_F32 else torch.int16, device=wav.device)
+
+        def enqueue():
+            with torch.cuda.device(wav.device):
+                return lib.fsnp_enhance_wave_pcm(self._handle, wav.data_ptr(), ifmt, wav.stride(0), max(wav.stride(1), 1), out.data_ptr(), ofmt,
+                                                 out.stride(0), 1, samples, B, L, None if clipped is None else clipped.data_ptr(),
+                                                 ctypes.c_void_p(stream))
+
+        def run():
+            _policy.enqueue_retrying_stale(enqueue, self._stale_weights_noticed, "fsnp_enhance_wave_pcm")
             return out
         return self._checked(run)
 

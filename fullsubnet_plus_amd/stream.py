@@ -294,11 +294,27 @@ class WaveStream(_Session):
         self.max_samples = int(max_samples)
         self.delay, self.live = int(self._lib.fsnp_wave_stream_delay(self._st)), bool(live)
 
-    def push(self, wav, counts=None):
-        """wav [slots, n] fp32 CUDA tensor (rows of any stride), n <= max_samples; counts: None (n samples for every slot) or samples per
+    @staticmethod
+    def _out_format(out_format, default, where):
+        """-> the _lib.SAMPLE_* value of a session call's out_format (None: `default`); a stream has no peak."""
+        if out_format is None:
+            out_format = default
+        if out_format not in ("f32", "s16"):
+            raise ValueError(f"WaveStream.{where}: out_format {out_format!r} is none of None, 'f32', 's16'"
+                             + (" (a stream has no peak: 's16_peak' is a format of enhance_wave only)" if out_format == "s16_peak" else ""))
+        return _lib.SAMPLE_FORMATS[out_format]
+
+    def push(self, wav, counts=None, out_format=None):
+        """wav [slots, n] CUDA tensor, n <= max_samples; counts: None (n samples for every slot) or samples per
         slot (a Python sequence or a CPU integer tensor, 0 <= counts[b] <= n; input past counts[b] is never read) -> [slots, n]: column
         j < counts[b] of slot b is enhanced sample P + j - delay of its clip (exactly 0 while P + j < delay), columns >= counts[b] are
-        exactly 0."""
+        exactly 0.
+
+        PCM (include/fsnp_pcm.h): wav is fp32 or torch.int16 (full scale: what wav.float() / 32768 gives, bit for bit) at any strides -
+        the [slots, n] view of a channel-interleaved socket buffer is read in place.  out_format: None (follow the input: float -> fp32,
+        int16 -> "s16"), "f32" or "s16" (int16, round half to even, saturating).  The session's state is fp32 whatever the formats, so
+        PCM and fp32 pushes mix freely."""
+        ofmt = self._out_format(out_format, "s16" if wav.dtype == torch.int16 else "f32", "push")
         st = self._session()
         assert wav.dim() == 2, "WaveStream.push takes [slots, n] samples"
         S, n = wav.shape
@@ -307,29 +323,47 @@ class WaveStream(_Session):
             raise RuntimeError("fullsubnet_plus_amd runs on MI355X (HIP) only; move the model and inputs to 'cuda'. "
                                "There is deliberately no CPU fallback.")
         assert wav.device == self.device
-        x = wav if wav.dtype == torch.float32 else wav.float()
-        if n > 1 and x.stride(1) != 1:
+        x = wav if wav.dtype in (torch.float32, torch.int16) else wav.float()
+        if n > 1 and x.stride(1) < 1:
             x = x.contiguous()
         cnt = None if counts is None else _host_lengths(counts, S, "WaveStream.push")
-        out = torch.empty((S, n), dtype=torch.float32, device=self.device)
+        if x.dtype == torch.float32 and ofmt == _lib.SAMPLE_F32 and (n == 1 or x.stride(1) == 1):
+            out = torch.empty((S, n), dtype=torch.float32, device=self.device)
 
-        def enqueue():
+            def enqueue():
+                with torch.cuda.device(self.device):
+                    return self._lib.fsnp_wave_stream_push(st, x.data_ptr(), x.stride(0), cnt, out.data_ptr(), n, n, self._cuda_stream())
+            return self._guarded(enqueue, out, "fsnp_wave_stream_push")
+        ifmt = _lib.SAMPLE_S16 if x.dtype == torch.int16 else _lib.SAMPLE_F32
+        out = torch.empty((S, n), dtype=torch.float32 if ofmt == _lib.SAMPLE_F32 else torch.int16, device=self.device)
+
+        def enqueue_pcm():
             with torch.cuda.device(self.device):
-                return self._lib.fsnp_wave_stream_push(st, x.data_ptr(), x.stride(0), cnt, out.data_ptr(), n, n, self._cuda_stream())
-        return self._guarded(enqueue, out, "fsnp_wave_stream_push")
+                return self._lib.fsnp_wave_stream_push_pcm(st, x.data_ptr(), ifmt, x.stride(0), max(x.stride(1), 1), cnt, out.data_ptr(), ofmt,
+                                                           n, 1, n, self._cuda_stream())
+        return self._guarded(enqueue_pcm, out, "fsnp_wave_stream_push_pcm")
 
-    def finish(self, slots=None):
+    def finish(self, slots=None, out_format=None):
         """End the clips of `slots` (None: all) -> [slots, delay]: each clip's last `delay` samples (exactly 0 where the clip is shorter);
         rows of slots not listed, and of slots that hold no samples, are exactly 0.  The finished slots are reset: their next push starts
-        a fresh clip.  A slot that holds 1 .. n_fft / 2 samples is refused, as enhance_wave refuses such a clip."""
+        a fresh clip.  A slot that holds 1 .. n_fft / 2 samples is refused, as enhance_wave refuses such a clip.  out_format: None or
+        "f32" (fp32), or "s16" (int16, as push)."""
+        ofmt = self._out_format(out_format, "f32", "finish")
         st = self._session()
         arr, num = _slot_array(slots)
-        out = torch.empty((self.slots, self.delay), dtype=torch.float32, device=self.device)
+        if ofmt == _lib.SAMPLE_F32:
+            out = torch.empty((self.slots, self.delay), dtype=torch.float32, device=self.device)
 
-        def enqueue():
+            def enqueue():
+                with torch.cuda.device(self.device):
+                    return self._lib.fsnp_wave_stream_finish(st, arr, num, out.data_ptr(), self.delay, self._cuda_stream())
+            return self._guarded(enqueue, out, "fsnp_wave_stream_finish")
+        out = torch.empty((self.slots, self.delay), dtype=torch.int16, device=self.device)
+
+        def enqueue_pcm():
             with torch.cuda.device(self.device):
-                return self._lib.fsnp_wave_stream_finish(st, arr, num, out.data_ptr(), self.delay, self._cuda_stream())
-        return self._guarded(enqueue, out, "fsnp_wave_stream_finish")
+                return self._lib.fsnp_wave_stream_finish_pcm(st, arr, num, out.data_ptr(), ofmt, self.delay, 1, self._cuda_stream())
+        return self._guarded(enqueue_pcm, out, "fsnp_wave_stream_finish_pcm")
 
     def samples(self, slot):
         """Samples pushed into `slot` since its last reset or finish (host-side count)."""

@@ -313,4 +313,5 @@ int32_t fsnp_config_size(void);
 #include "fsnp_spec_stream.h" /* spectrum sessions: STFT frames in, enhanced STFT frames out (the caller owns the STFT) */
 #include "fsnp_device_weights.h" /* weights handed over in device memory and packed on the GPU */
 #include "fsnp_stft_geometry.h" /* the hop length of the waveform path (n_fft = 2 (num_freqs - 1), periodic Hann of n_fft) */
+#include "fsnp_pcm.h" /* 16-bit PCM and strided samples at the boundary of the waveform path and of wave sessions */
 #endif /* FSNP_H */

@@ -242,6 +242,15 @@ int fsnp_debug_commit_stats(const fsnp_handle* h, int64_t out[4]);
 int fsnp_debug_pack_emulate(int32_t kind, const int32_t* sizes, int32_t num_sizes, const float* const* sources, const int64_t* numels,
                             int32_t num_sources, float* out, int64_t out_floats);
 
+/* PCM output (fsnp_pcm.h): exactly the output conversion of the waveform path's overlap-add kernels - the same device function, the
+ * reduction and second pass of FSNP_SAMPLE_S16_PEAK included - on an arbitrary DEVICE float buffer dev_in [rows][n] (contiguous) ->
+ * dev_out int16 [rows][n], because a test cannot make the model produce a tie, an overflow or a NaN on demand.  samples: HOST int32
+ * [rows], 0 <= samples[b] <= n (NULL: n for every row): columns >= samples[b] are written as exactly 0 and take no part in the peak;
+ * out_format: FSNP_SAMPLE_S16 or FSNP_SAMPLE_S16_PEAK; dev_clipped: NULL or DEVICE int32 [rows], overwritten.  Stream-ordered, uses the
+ * handle's I/O area for the peak pass; no synchronisation. */
+int fsnp_debug_pcm_convert(fsnp_handle* h, const float* dev_in, int16_t* dev_out, int32_t rows, int32_t n, const int32_t* samples,
+                           int32_t out_format, int32_t* dev_clipped, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
