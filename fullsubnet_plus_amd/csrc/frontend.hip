@@ -410,34 +410,13 @@ __global__ __launch_bounds__(256) void fe_apply_kernel(const float* __restrict__
 
 // ------------------------------------------------------------------------------------------------
 // decompress_cIRM (mask.py:60-63) + complex multiply (inferencer.py:152-157)
+// Rows b0 ... b0 + rows - 1 of the batch, thread per (row, t, f) with f fastest: matches torch.stft's memory order for the complex
+// operands.  Row b's frames >= row_len(len, b - b0) are written as 0 without reading the mask or the input there (clips of different
+// lengths, LEN = RowLengths: the contract lets the input past a length hold anything, NaN included); equal clips: LEN = int, the T of all
+template <typename LEN>
 __global__ __launch_bounds__(256) void apply_cirm_kernel(const float* __restrict__ mask, const float2* __restrict__ noisy,
                                                          long sb, long sf, long st, float2* __restrict__ out, long ob,
-                                                         long of, long ot, int B, int F, int T) {
-    // thread per (b, t, f) with f fastest: matches torch.stft's memory order for the complex operands
-    const long total = (long)B * T * F;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-        const int f = (int)(i % F);
-        const int t = (int)((i / F) % T);
-        const int b = (int)(i / ((long)F * T));
-        const float2 x = noisy[b * sb + f * sf + t * st];
-        out[b * ob + f * of + t * ot] = cirm_times(mask, ((long)b * 2 * F + f) * T + t, (long)F * T, x);
-    }
-}
-
-void launch_apply_cirm(const float* mask, const float* noisy, const int64_t strides[3], float* out,
-                       const int64_t out_strides[3], int B, int F, int T, hipStream_t s) {
-    const long total = (long)B * T * F;
-    const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    hipLaunchKernelGGL(apply_cirm_kernel, dim3(blocks), dim3(256), 0, s, mask, reinterpret_cast<const float2*>(noisy),
-                       strides[0], strides[1], strides[2], reinterpret_cast<float2*>(out), out_strides[0], out_strides[1],
-                       out_strides[2], B, F, T);
-}
-
-// the same for clips of different lengths: rows b0 ... b0 + rows - 1 of the batch, row b's frames >= len.v[b - b0] written as 0
-// without reading the mask or the input there (the contract lets the input past a length hold anything, NaN included)
-__global__ __launch_bounds__(256) void apply_cirm_lengths_kernel(const float* __restrict__ mask, const float2* __restrict__ noisy,
-                                                                 long sb, long sf, long st, float2* __restrict__ out, long ob,
-                                                                 long of, long ot, int b0, int rows, int F, int T, RowLengths len) {
+                                                         long of, long ot, int b0, int rows, int F, int T, LEN len) {
     const long total = (long)rows * T * F;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         const int f = (int)(i % F);
@@ -445,23 +424,20 @@ __global__ __launch_bounds__(256) void apply_cirm_lengths_kernel(const float* __
         const int r = (int)(i / ((long)F * T));
         const long b = (long)b0 + r;
         float2 y = make_float2(0.0f, 0.0f);
-        if (t < len.v[r]) y = cirm_times(mask, (b * 2 * F + f) * T + t, (long)F * T, noisy[b * sb + f * sf + t * st]);
+        if (t < row_len(len, r)) y = cirm_times(mask, (b * 2 * F + f) * T + t, (long)F * T, noisy[b * sb + f * sf + t * st]);
         out[b * ob + f * of + t * ot] = y;
     }
 }
 
-void launch_apply_cirm_lengths(const float* mask, const float* noisy, const int64_t strides[3], float* out,
-                               const int64_t out_strides[3], int B, int F, int T, const int* lengths, hipStream_t s) {
-    for (int b0 = 0; b0 < B; b0 += kLenRows) {
-        const int rows = B - b0 < kLenRows ? B - b0 : kLenRows;
-        RowLengths len{};
-        for (int r = 0; r < rows; ++r) len.v[r] = lengths[b0 + r];
+void launch_apply_cirm(const float* mask, const float* noisy, const int64_t strides[3], float* out,
+                       const int64_t out_strides[3], int B, int F, int T, const int* lengths, hipStream_t s) {
+    for_row_chunks(B, lengths, T, [&](int b0, int rows, auto len) {
         const long total = (long)rows * T * F;
         const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-        hipLaunchKernelGGL(apply_cirm_lengths_kernel, dim3(blocks), dim3(256), 0, s, mask, reinterpret_cast<const float2*>(noisy),
+        hipLaunchKernelGGL(apply_cirm_kernel<decltype(len)>, dim3(blocks), dim3(256), 0, s, mask, reinterpret_cast<const float2*>(noisy),
                            strides[0], strides[1], strides[2], reinterpret_cast<float2*>(out), out_strides[0], out_strides[1],
                            out_strides[2], b0, rows, F, T, len);
-    }
+    });
 }
 
 void launch_frontend(const Dims& d, int norm_type, const float* const in[3], const int64_t strides[3][3], bool is_complex,

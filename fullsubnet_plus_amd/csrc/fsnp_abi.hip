@@ -1070,12 +1070,7 @@ int fsnp_reserve(fsnp_handle* h, int32_t max_batch, int32_t max_frames, int32_t 
     if (max_samples > 0) {
         if (h->cfg.output_size != 2) { set_error("fsnp_reserve: max_samples > 0 sizes the waveform path, which needs output_size = 2 (this handle: %d)", h->cfg.output_size); return 2; }
         if (ensure_stft(h)) return 2;
-        const StftPlan p = stft_plan(h);
-        const int T = 1 + max_samples / p.hop;
-        const long xs = (long)align_up((size_t)max_samples + p.n_fft, 4);
-        const size_t xp_b = align_up((size_t)max_batch * xs * 4, 256), spec_b = align_up((size_t)max_batch * T * p.sp * 4 + 256, 256);
-        const size_t mask_b = align_up((size_t)max_batch * 2 * p.F * T * 4, 256), fr_b = (size_t)max_batch * T * p.n_fft * 4;
-        if (ensure_io(h, xp_b + 2 * spec_b + mask_b + fr_b, s)) return 4;
+        if (ensure_io(h, wave_io(stft_plan(h), max_batch, max_samples).total, s)) return 4;
     }
     return mark_forward_done(h, s);
 }
@@ -1084,7 +1079,7 @@ int fsnp_apply_cirm(const float* mask, const float* noisy, const int64_t strides
                     const int64_t out_strides[3], int32_t batch, int32_t freqs, int32_t frames, void* hip_stream) {
     if (!mask || !noisy || !out || !strides || !out_strides) { set_error("fsnp_apply_cirm: null argument"); return 1; }
     if (batch <= 0 || freqs <= 0 || frames <= 0) { set_error("fsnp_apply_cirm: empty input"); return 2; }
-    launch_apply_cirm(mask, noisy, strides, out, out_strides, batch, freqs, frames, static_cast<hipStream_t>(hip_stream));
+    launch_apply_cirm(mask, noisy, strides, out, out_strides, batch, freqs, frames, nullptr, static_cast<hipStream_t>(hip_stream));
     FSNP_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -1098,7 +1093,7 @@ int fsnp_apply_cirm_lengths(const float* mask, const float* noisy, const int64_t
             set_error("fsnp_apply_cirm_lengths: utterance %d: length %d outside [1, %d]", b, (int)lengths[b], (int)frames);
             return 2;
         }
-    launch_apply_cirm_lengths(mask, noisy, strides, out, out_strides, batch, freqs, frames, lengths, static_cast<hipStream_t>(hip_stream));
+    launch_apply_cirm(mask, noisy, strides, out, out_strides, batch, freqs, frames, lengths, static_cast<hipStream_t>(hip_stream));
     FSNP_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -95,15 +95,29 @@ void launch_attention_stage(const Dims& d, const FrontendWeights& w_slot0, const
                             const FrontendBuffers& buf, hipStream_t s);
 void launch_repack_plane(const Dims& d, const float* in, const int64_t strides[3], float* raw, hipStream_t s);
 void launch_tm_to_bft(const float* tm, float* out, int B, int T, int Tp, int F, int FP, hipStream_t s);       // stages.hip
+// lengths: HOST frames of row b, frames >= lengths[b] of `out` written as 0; NULL = every row is T frames long
 void launch_apply_cirm(const float* mask, const float* noisy, const int64_t strides[3], float* out,
-                       const int64_t out_strides[3], int B, int F, int T, hipStream_t s);
+                       const int64_t out_strides[3], int B, int F, int T, const int* lengths, hipStream_t s);
 // per-row host values as a kernel argument (clips of different lengths: no copy to the device, nothing to synchronise), kLenRows
-// rows per launch; what the launchers of such kernels (apply_cirm, stft pad, istft overlap-add) loop over
+// rows per launch.  A batch of equal clips is the same call with equal values: the whole-clip launchers (apply_cirm, stft pad, istft
+// overlap-add, pcm) have one kernel each, a template on its LEN argument - a RowLengths, or one int for every row, so that equal clips
+// do not carry the 1 KB argument (0.4 us per launch) - and walk their rows with for_row_chunks
 constexpr int kLenRows = 256;
 struct RowLengths { int v[kLenRows]; };
-// launch_apply_cirm for clips of different lengths: lengths[b] HOST frames of row b, frames >= lengths[b] of `out` written as 0
-void launch_apply_cirm_lengths(const float* mask, const float* noisy, const int64_t strides[3], float* out,
-                               const int64_t out_strides[3], int B, int F, int T, const int* lengths, hipStream_t s);
+__host__ __device__ inline int row_len(const RowLengths& len, int r) { return len.v[r]; }
+__host__ __device__ inline int row_len(int len, int) { return len; }
+// body(b0, rows, len) for rows b0 ... b0 + rows - 1 of B, chunk by chunk: len a RowLengths of values[b0 + r], or the int `uniform` where
+// values is NULL (body: a generic lambda that launches kernel<..., decltype(len)>)
+template <typename Body>
+inline void for_row_chunks(int B, const int* values, int uniform, Body body) {
+    for (int b0 = 0; b0 < B; b0 += kLenRows) {
+        const int rows = B - b0 < kLenRows ? B - b0 : kLenRows;
+        RowLengths len{};
+        for (int r = 0; values && r < rows; ++r) len.v[r] = values[b0 + r];
+        if (values) body(b0, rows, len);
+        else body(b0, rows, uniform);
+    }
+}
 // one bin of it: the compressed mask planes at mask[re_at], mask[re_at + plane] times the complex x (shared by the whole-clip kernels of
 // frontend.hip and the ring push of spec_stream.hip)
 #ifdef __HIPCC__
@@ -192,12 +206,11 @@ void launch_linear_act(const float* A, int lda, const float* W, int ldw, const f
 // (samples in and out as the views of pcm.h: fp32 or int16 at any sample step, include/fsnp_pcm.h)
 struct PcmIn;
 struct PcmOut;
-void launch_stft_pad(const PcmIn& wav, float* xp, long xp_stride, int B, int L, int n_fft, hipStream_t s);
-void launch_istft_ola(const float* frames, const float* window, const PcmOut& wav, int B, int T, int L, int n_fft, int hop, hipStream_t s);
-// the same per row of a batch of clips of different lengths: samples[b] host values (kernel arguments, up to 256 rows per launch)
-void launch_stft_pad_lengths(const PcmIn& wav, float* xp, long xp_stride, int B, const int* samples, int n_fft, hipStream_t s);
-void launch_istft_ola_lengths(const float* frames, const float* window, const PcmOut& wav, int B, int T, int L, const int* samples, int n_fft,
-                              int hop, hipStream_t s);
+// samples: HOST sample count of each row (clips of different lengths), NULL = every row holds L samples.  Row b is reflect-padded at its
+// own end and overlap-added over its own 1 + samples[b] / hop frames, zeros behind; with NULL the overlap-add sums all T frames it is given
+void launch_stft_pad(const PcmIn& wav, float* xp, long xp_stride, int B, int L, const int* samples, int n_fft, hipStream_t s);
+void launch_istft_ola(const float* frames, const float* window, const PcmOut& wav, int B, int T, int L, const int* samples, int n_fft,
+                      int hop, hipStream_t s);
 // spec_stream.hip : the look-ahead ring and the two short launches around one mag push that a spectrum session (include/fsnp_spec_stream.h)
 // and a wave session (include/fsnp_wave_stream.h) share.  Per slot a ring complex64 [look_ahead][F]: the noisy spectra of the newest
 // look_ahead frames, frame g in row g % look_ahead (they wait for their masks: the mask of frame t is the model's output of step

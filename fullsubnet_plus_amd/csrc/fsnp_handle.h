@@ -255,6 +255,15 @@ StftPlan stft_plan(const fsnp_handle* h);
 int check_hop_length(int F, int hop, const char* where);
 int ensure_stft(fsnp_handle* h);
 int ensure_io(fsnp_handle* h, size_t bytes, hipStream_t s);
+// The io area of fsnp_enhance_wave for `batch` clips of up to max_samples samples: what the call lays out and what fsnp_reserve sizes.
+// Byte offsets of the padded signal [batch][xs], the noisy and the enhanced spectra [batch][T][sp] (+ 256 bytes each), the mask
+// [batch][2][F][T] and the inverse DFT's frames [batch][T][n_fft]; T = 1 + max_samples / hop
+struct WaveIo {
+    int T;
+    long xs;
+    size_t xp, noisy, enh, mask, fr, total;
+};
+WaveIo wave_io(const StftPlan& p, int batch, int max_samples);
 // 0, or 2 with the error set: the format and step rules of include/fsnp_pcm.h for one sample buffer (`what`: "input" / "output";
 // peak_ok: FSNP_SAMPLE_S16_PEAK is a format this buffer may have)
 int check_sample_format(const char* where, const char* what, int32_t format, int64_t step, bool peak_ok);

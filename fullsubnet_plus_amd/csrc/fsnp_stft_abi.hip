@@ -64,11 +64,27 @@ __global__ void spec_repack_kernel(const float2* __restrict__ in, long sb, long 
     const int f = (int)(i % spc), t = (int)((i / spc) % T), b = (int)(i / ((long)spc * T));
     out[i] = f < F ? in[b * sb + f * sf + t * st] : make_float2(0.f, 0.f);
 }
-// wav [B][L] -> spectrum rows [B][T][ldc] (interleaved complex), T = 1 + L / hop
+WaveIo wave_io(const StftPlan& p, int batch, int max_samples) {
+    WaveIo io{};
+    io.T = 1 + max_samples / p.hop;
+    io.xs = (long)align_up((size_t)max_samples + p.n_fft, 4);
+    size_t o = 0;
+    auto take = [&](size_t bytes) { size_t r = o; o = align_up(o + bytes, 256); return r; };
+    const size_t spec = (size_t)batch * io.T * p.sp * 4 + 256;
+    io.xp = take((size_t)batch * io.xs * 4);
+    io.noisy = take(spec);
+    io.enh = take(spec);
+    io.mask = take((size_t)batch * 2 * p.F * io.T * 4);
+    io.fr = o;
+    io.total = io.fr + (size_t)batch * io.T * p.n_fft * 4;
+    return io;
+}
+// wav [B][L] -> spectrum rows [B][T][ldc] (interleaved complex), T = 1 + L / hop; samples: NULL, or each row's own HOST sample count
+// (reflect padding at each clip's own end; frames past 1 + samples[b] / hop see zeros behind it)
 static void stft_into(fsnp_handle* h, const StftPlan& p, const PcmIn& wav, float* xp, long xs, float* spec, int ldc, int B, int L,
-                      hipStream_t s) {
+                      const int* samples, hipStream_t s) {
     const int T = 1 + L / p.hop;
-    launch_stft_pad(wav, xp, xs, B, L, p.n_fft, s);
+    launch_stft_pad(wav, xp, xs, B, L, samples, p.n_fft, s);
     launch_linear_act(xp, p.hop, h->d_stft + p.o_fwd, p.fwd_ld, h->d_stft + p.o_zero, spec, ldc, p.n_fft, p.N2, B, T,
                       FSNP_ACT_NONE, h->num_cus, s, xs, p.n_fft);
 }
@@ -77,7 +93,7 @@ static void istft_from(fsnp_handle* h, const StftPlan& p, const float* spec, flo
                        int T, int L, hipStream_t s) {
     launch_linear_act(spec, p.sp, h->d_stft + p.o_inv, p.inv_ld, h->d_stft + p.o_zero, frames, p.n_fft, p.N2, p.n_fft, B, T,
                       FSNP_ACT_NONE, h->num_cus, s, (long)T * p.sp, p.N2);
-    launch_istft_ola(frames, h->d_stft + p.o_win, pcm_out_f32(wav, wav_stride), B, T, L, p.n_fft, p.hop, s);
+    launch_istft_ola(frames, h->d_stft + p.o_win, pcm_out_f32(wav, wav_stride), B, T, L, nullptr, p.n_fft, p.hop, s);   // all T frames
 }
 // the format and step rules of include/fsnp_pcm.h for one buffer (peak_ok: FSNP_SAMPLE_S16_PEAK is a format of this buffer)
 int check_sample_format(const char* where, const char* what, int32_t format, int64_t step, bool peak_ok) {
@@ -104,7 +120,7 @@ int stft_any(fsnp_handle* h, const char* where, const PcmIn& wav, float* spec, i
     const long xs = (long)align_up((size_t)samples + p.n_fft, 4);
     if (order_after_last_forward(h, s)) return 4;
     if (ensure_io(h, (size_t)batch * xs * 4, s)) return 4;
-    stft_into(h, p, wav, reinterpret_cast<float*>(h->io), xs, spec, p.N2, batch, samples, s);
+    stft_into(h, p, wav, reinterpret_cast<float*>(h->io), xs, spec, p.N2, batch, samples, nullptr, s);
     FSNP_HIP_CHECK(hipGetLastError());
     return mark_forward_done(h, s);
 }
@@ -137,25 +153,18 @@ int enhance_wave_any(fsnp_handle* h, const char* where, const PcmIn& wav, const 
     }
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     FSNP_ON_DEVICE(h);
-    const long xs = (long)align_up((size_t)max_samples + p.n_fft, 4);
-    const size_t xp_b = align_up((size_t)batch * xs * 4, 256), spec_b = align_up((size_t)batch * T * p.sp * 4 + 256, 256);
-    const size_t mask_b = align_up((size_t)batch * 2 * p.F * T * 4, 256), fr_b = (size_t)batch * T * p.n_fft * 4;
+    const WaveIo io = wave_io(p, batch, max_samples);
+    const long xs = io.xs;
     if (order_after_last_forward(h, s)) return 4;
-    if (ensure_io(h, xp_b + 2 * spec_b + mask_b + fr_b, s)) return 4;
-    float* xp = reinterpret_cast<float*>(h->io);
-    float* noisy = reinterpret_cast<float*>(h->io + xp_b);
-    float* enh = reinterpret_cast<float*>(h->io + xp_b + spec_b);
-    float* mask = reinterpret_cast<float*>(h->io + xp_b + 2 * spec_b);
-    float* fr = reinterpret_cast<float*>(h->io + xp_b + 2 * spec_b + mask_b);
+    if (ensure_io(h, io.total, s)) return 4;
+    float* xp = reinterpret_cast<float*>(h->io + io.xp);
+    float* noisy = reinterpret_cast<float*>(h->io + io.noisy);
+    float* enh = reinterpret_cast<float*>(h->io + io.enh);
+    float* mask = reinterpret_cast<float*>(h->io + io.mask);
+    float* fr = reinterpret_cast<float*>(h->io + io.fr);
     // inferencer.py:142-158: stft -> (mag, real, imag) -> model -> decompress_cIRM, complex multiply -> istft(length); with lengths
     // the reflect padding at each clip's end (frames past T_b see zeros: the forward never reads them)
-    if (samples) {
-        launch_stft_pad_lengths(wav, xp, xs, batch, samples, p.n_fft, s);
-        launch_linear_act(xp, p.hop, h->d_stft + p.o_fwd, p.fwd_ld, h->d_stft + p.o_zero, noisy, p.sp, p.n_fft, p.N2, batch, T,
-                          FSNP_ACT_NONE, h->num_cus, s, xs, p.n_fft);
-    } else {
-        stft_into(h, p, wav, xp, xs, noisy, p.sp, batch, max_samples, s);
-    }
+    stft_into(h, p, wav, xp, xs, noisy, p.sp, batch, max_samples, samples, s);
     const int64_t cst[3] = {(int64_t)T * (p.sp / 2), 1, p.sp / 2};       // complex-element strides of [B][T][sp/2] as (b, f, t)
     const int rc = samples ? fsnp_forward_complex_lengths(h, noisy, cst, frames.data(), mask, batch, T, hip_stream)
                            : fsnp_forward_complex(h, noisy, cst, mask, batch, T, FSNP_MODE_FULL, 0, batch, hip_stream);
@@ -164,9 +173,8 @@ int enhance_wave_any(fsnp_handle* h, const char* where, const PcmIn& wav, const 
     // right here and lives in the single-buffered io area, so `s` waits for them now (fsnp_flush) - nothing of this call is deferred
     if (h->pipeline && fsnp_flush(h, hip_stream)) return 4;
     // the pad column of every row of `enh` is never written by apply_cirm and multiplies zero weights: clear it once
-    FSNP_HIP_CHECK(hipMemsetAsync(enh, 0, spec_b, s));
-    if (samples) launch_apply_cirm_lengths(mask, noisy, cst, enh, cst, batch, p.F, T, frames.data(), s);      // frames >= T_b: 0
-    else launch_apply_cirm(mask, noisy, cst, enh, cst, batch, p.F, T, s);
+    FSNP_HIP_CHECK(hipMemsetAsync(enh, 0, io.mask - io.enh, s));
+    launch_apply_cirm(mask, noisy, cst, enh, cst, batch, p.F, T, samples ? frames.data() : nullptr, s);      // frames >= T_b: 0
     launch_linear_act(enh, p.sp, h->d_stft + p.o_inv, p.inv_ld, h->d_stft + p.o_zero, fr, p.n_fft, p.N2, p.n_fft, batch, T,
                       FSNP_ACT_NONE, h->num_cus, s, (long)T * p.sp, p.N2);
     // the samples out, in the caller's format.  FSNP_SAMPLE_S16_PEAK needs the clip's peak before any sample can be written: the
@@ -179,8 +187,7 @@ int enhance_wave_any(fsnp_handle* h, const char* where, const PcmIn& wav, const 
         FSNP_HIP_CHECK(hipMemsetAsync(noisy, 0, (size_t)batch * 4, s));
         o = PcmOut{xp, xs, 1, kPcmPeak, nullptr, reinterpret_cast<unsigned*>(noisy)};
     }
-    if (samples) launch_istft_ola_lengths(fr, h->d_stft + p.o_win, o, batch, T, max_samples, samples, p.n_fft, p.hop, s);
-    else launch_istft_ola(fr, h->d_stft + p.o_win, o, batch, T, max_samples, p.n_fft, p.hop, s);
+    launch_istft_ola(fr, h->d_stft + p.o_win, o, batch, T, max_samples, samples, p.n_fft, p.hop, s);
     if (out.fmt == kPcmPeak)
         launch_pcm_peak_scale(xp, xs, o.peak, PcmOut{out.p, out.stride, out.step, kPcmS16, nullptr, nullptr}, batch, max_samples, s);
     FSNP_HIP_CHECK(hipGetLastError());

@@ -19,32 +19,28 @@ __global__ __launch_bounds__(256) void pcm_peak_scale_kernel(const float* __rest
 }
 
 void launch_pcm_peak_scale(const float* stage, long stage_stride, const unsigned* peak, const PcmOut& out, int rows, int n, hipStream_t s) {
-    for (int b0 = 0; b0 < rows; b0 += kLenRows) {
-        const int r = rows - b0 < kLenRows ? rows - b0 : kLenRows;
+    for_row_chunks(rows, nullptr, n, [&](int b0, int r, auto) {      // (the chunks only: the grid's y extent)
         hipLaunchKernelGGL(pcm_peak_scale_kernel, dim3((unsigned)((n + 255) / 256), r), dim3(256), 0, s, stage + (long)b0 * stage_stride,
                            stage_stride, peak + b0, pcm_rows(out, b0), n);
-    }
+    });
 }
 
-template <int FMT>
-__global__ __launch_bounds__(256) void pcm_convert_kernel(const float* __restrict__ in, long in_stride, PcmOut out, int n, RowLengths len) {
+template <int FMT, typename LEN>
+__global__ __launch_bounds__(256) void pcm_convert_kernel(const float* __restrict__ in, long in_stride, PcmOut out, int n, LEN len) {
     const int b = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
     float v = 0.0f;
-    if (j < len.v[b]) v = in[(long)b * in_stride + j];         // (len.v[b] <= n)
+    if (j < row_len(len, b)) v = in[(long)b * in_stride + j];   // (row_len <= n)
     pcm_store<FMT>(out, b, j, v, j < n);
 }
 
 void launch_pcm_convert(const float* in, long in_stride, const PcmOut& out, int rows, int n, const int* samples, hipStream_t s) {
-    for (int b0 = 0; b0 < rows; b0 += kLenRows) {
-        const int r = rows - b0 < kLenRows ? rows - b0 : kLenRows;
-        RowLengths len{};
-        for (int i = 0; i < r; ++i) len.v[i] = samples ? samples[b0 + i] : n;
+    for_row_chunks(rows, samples, n, [&](int b0, int r, auto len) {
         const dim3 grid((unsigned)((n + 255) / 256), r);
         if (out.fmt == kPcmPeak)
-            hipLaunchKernelGGL(pcm_convert_kernel<kPcmPeak>, grid, dim3(256), 0, s, in + (long)b0 * in_stride, in_stride, pcm_rows(out, b0), n, len);
+            hipLaunchKernelGGL((pcm_convert_kernel<kPcmPeak, decltype(len)>), grid, dim3(256), 0, s, in + (long)b0 * in_stride, in_stride, pcm_rows(out, b0), n, len);
         else
-            hipLaunchKernelGGL(pcm_convert_kernel<kPcmS16>, grid, dim3(256), 0, s, in + (long)b0 * in_stride, in_stride, pcm_rows(out, b0), n, len);
-    }
+            hipLaunchKernelGGL((pcm_convert_kernel<kPcmS16, decltype(len)>), grid, dim3(256), 0, s, in + (long)b0 * in_stride, in_stride, pcm_rows(out, b0), n, len);
+    });
 }
 
 }  // namespace fsnp

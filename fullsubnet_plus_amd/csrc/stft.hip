@@ -14,20 +14,27 @@
 // Geometry (include/fsnp_stft_geometry.h): n_fft = 2 (F - 1), window = periodic hann(n_fft), N/8 <= hop <= N/2 with hop % 4 == 0 (the A
 // rows above are read as float4); T = 1 + L / hop frames, the reflect padding is N/2 whatever the hop.
 // Samples come in and go out in the formats of include/fsnp_pcm.h (pcm.h): fp32 or int16, at any sample step, converted in the
-// pad kernels' loads and the overlap-add kernels' stores.  One workgroup works on one row (blockIdx.y), so that a wave's clipped
+// pad kernel's loads and the overlap-add kernel's stores.  One workgroup works on one row (blockIdx.y), so that a wave's clipped
 // count and peak belong to one row.
 #include <cmath>
+#include <type_traits>
 
 #include "fsnp_common.h"
 #include "pcm.h"
 
 namespace fsnp {
 
-template <int FMT>
-__global__ __launch_bounds__(256) void stft_pad_kernel(PcmIn wav, float* __restrict__ xp, long xp_stride, int L, int half) {
+// Clips of different lengths in one batch: row b is its own row_len(len, b) samples long.  The counts travel as a kernel argument (LEN =
+// RowLengths: no copy to the device, nothing to synchronise), kLenRows rows per launch; a batch of equal clips is the same kernel with
+// the one count every row has (LEN = int).
+
+// reflect padding at each row's own end (torch.stft of the clip alone), zeros behind it
+template <int FMT, typename LEN>
+__global__ __launch_bounds__(256) void stft_pad_kernel(PcmIn wav, float* __restrict__ xp, long xp_stride, int half, LEN len) {
     const int b = blockIdx.y;
     const long p = (long)blockIdx.x * 256 + threadIdx.x;      // index into row b of [B][L + 2 half (+ tail)]
     if (p >= xp_stride) return;
+    const int L = row_len(len, b);
     float v = 0.0f;
     if (p < L + 2 * half) {
         int j = (int)p - half;                                 // torch "reflect": no edge repeat
@@ -38,14 +45,13 @@ __global__ __launch_bounds__(256) void stft_pad_kernel(PcmIn wav, float* __restr
     xp[(long)b * xp_stride + p] = v;
 }
 
-void launch_stft_pad(const PcmIn& wav, float* xp, long xp_stride, int B, int L, int n_fft, hipStream_t s) {
-    for (int b0 = 0; b0 < B; b0 += kLenRows) {                 // (rows per launch: the grid's y extent)
-        const int rows = B - b0 < kLenRows ? B - b0 : kLenRows;
+void launch_stft_pad(const PcmIn& wav, float* xp, long xp_stride, int B, int L, const int* samples, int n_fft, hipStream_t s) {
+    for_row_chunks(B, samples, L, [&](int b0, int rows, auto len) {
         const dim3 grid((unsigned)((xp_stride + 255) / 256), rows);
-#define FSNP_CALL(F) hipLaunchKernelGGL(stft_pad_kernel<F>, grid, dim3(256), 0, s, pcm_rows(wav, b0), xp + (long)b0 * xp_stride, xp_stride, L, n_fft / 2)
+#define FSNP_CALL(F) hipLaunchKernelGGL((stft_pad_kernel<F, decltype(len)>), grid, dim3(256), 0, s, pcm_rows(wav, b0), xp + (long)b0 * xp_stride, xp_stride, n_fft / 2, len)
         FSNP_PCM_SWITCH2(wav.fmt, FSNP_CALL);
 #undef FSNP_CALL
-    }
+    });
 }
 
 // One output sample: overlap-add and envelope division over the frames t < T that cover it, t * hop - n_fft / 2 <= n < t * hop + n_fft / 2
@@ -80,87 +86,32 @@ __device__ __forceinline__ float istft_ola_sample(const float* __restrict__ fram
     return den > 1e-11f ? num / den : 0.0f;
 }
 
-template <bool HALF, int FMT>
+// Row b's samples n < L_b = row_len(len, b), samples past them written as 0 (up to the L columns of the batch).  The frames a row sums
+// are a fact of their own, not a function of its sample count.  Clips of different lengths (LEN = RowLengths): row b sums its own
+// 1 + L_b / hop frames (torch.istft(..., length=) of the clip alone: frame T_b, which still overlaps the clip's last samples, is not
+// part of it).  Equal clips (LEN = int): every row sums all T frames the caller gave, which may be more than 1 + L / hop (fsnp_istft)
+// and then reach into the clip's last samples.
+template <bool HALF, int FMT, typename LEN>
 __global__ __launch_bounds__(256) void istft_ola_kernel(const float* __restrict__ frames, const float* __restrict__ window, PcmOut wav,
-                                                        int T, int L, int n_fft, int hop) {
+                                                        int T, int L, int n_fft, int hop, LEN len) {
     const int b = blockIdx.y, n = blockIdx.x * 256 + threadIdx.x;      // (row, sample)
-    const bool live = n < L;
+    const int Lb = row_len(len, b), Tb = std::is_same<LEN, RowLengths>::value ? 1 + Lb / hop : T;
     float v = 0.0f;
-    if (live) v = istft_ola_sample<HALF>(frames + (long)b * T * n_fft, window, n, T, n_fft, hop);
-    pcm_store<FMT>(wav, b, n, v, live);
+    if (n < Lb) v = istft_ola_sample<HALF>(frames + (long)b * T * n_fft, window, n, Tb, n_fft, hop);
+    pcm_store<FMT>(wav, b, n, v, n < L);
 }
 
-void launch_istft_ola(const float* frames, const float* window, const PcmOut& wav, int B, int T, int L, int n_fft, int hop, hipStream_t s) {
-    for (int b0 = 0; b0 < B; b0 += kLenRows) {
-        const int rows = B - b0 < kLenRows ? B - b0 : kLenRows;
+void launch_istft_ola(const float* frames, const float* window, const PcmOut& wav, int B, int T, int L, const int* samples, int n_fft,
+                      int hop, hipStream_t s) {
+    for_row_chunks(B, samples, L, [&](int b0, int rows, auto len) {
         const dim3 grid((unsigned)((L + 255) / 256), rows);
         const float* fr = frames + (long)b0 * T * n_fft;
 #define FSNP_CALL(F)                                                                                                                     \
-    if (2 * hop == n_fft) hipLaunchKernelGGL((istft_ola_kernel<true, F>), grid, dim3(256), 0, s, fr, window, pcm_rows(wav, b0), T, L, n_fft, hop); \
-    else hipLaunchKernelGGL((istft_ola_kernel<false, F>), grid, dim3(256), 0, s, fr, window, pcm_rows(wav, b0), T, L, n_fft, hop)
+    if (2 * hop == n_fft) hipLaunchKernelGGL((istft_ola_kernel<true, F, decltype(len)>), grid, dim3(256), 0, s, fr, window, pcm_rows(wav, b0), T, L, n_fft, hop, len); \
+    else hipLaunchKernelGGL((istft_ola_kernel<false, F, decltype(len)>), grid, dim3(256), 0, s, fr, window, pcm_rows(wav, b0), T, L, n_fft, hop, len)
         FSNP_PCM_SWITCH3(wav.fmt, FSNP_CALL);
 #undef FSNP_CALL
-    }
-}
-
-// ---- clips of different lengths in one batch (fsnp_enhance_wave_lengths): row b is its own samples[b] long.  The sample counts travel
-// as kernel arguments (RowLengths: no copy to the device, nothing to synchronise), kLenRows rows per launch.
-
-// reflect padding at each row's own end (torch.stft of the clip alone), zeros behind it
-template <int FMT>
-__global__ __launch_bounds__(256) void stft_pad_lengths_kernel(PcmIn wav, float* __restrict__ xp, long xp_stride, int half, RowLengths len) {
-    const int b = blockIdx.y;
-    const long p = (long)blockIdx.x * 256 + threadIdx.x;
-    if (p >= xp_stride) return;
-    const int L = len.v[b];
-    float v = 0.0f;
-    if (p < L + 2 * half) {
-        int j = (int)p - half;
-        if (j < 0) j = -j;
-        if (j >= L) j = 2 * (L - 1) - j;
-        v = pcm_load<FMT>(wav, b, j);
-    }
-    xp[(long)b * xp_stride + p] = v;
-}
-
-void launch_stft_pad_lengths(const PcmIn& wav, float* xp, long xp_stride, int B, const int* samples, int n_fft, hipStream_t s) {
-    for (int b0 = 0; b0 < B; b0 += kLenRows) {
-        const int rows = B - b0 < kLenRows ? B - b0 : kLenRows;
-        RowLengths len{};
-        for (int r = 0; r < rows; ++r) len.v[r] = samples[b0 + r];
-        const dim3 grid((unsigned)((xp_stride + 255) / 256), rows);
-#define FSNP_CALL(F) hipLaunchKernelGGL(stft_pad_lengths_kernel<F>, grid, dim3(256), 0, s, pcm_rows(wav, b0), xp + (long)b0 * xp_stride, xp_stride, n_fft / 2, len)
-        FSNP_PCM_SWITCH2(wav.fmt, FSNP_CALL);
-#undef FSNP_CALL
-    }
-}
-
-// overlap-add and window-envelope division over row b's own 1 + samples[b] / hop frames (torch.istft(..., length=samples[b]) of the
-// clip alone: frame T_b, which still overlaps the clip's last samples, is not part of it); samples past samples[b] are written as 0
-template <bool HALF, int FMT>
-__global__ __launch_bounds__(256) void istft_ola_lengths_kernel(const float* __restrict__ frames, const float* __restrict__ window,
-                                                                PcmOut wav, int T, int L, int n_fft, int hop, RowLengths len) {
-    const int b = blockIdx.y, n = blockIdx.x * 256 + threadIdx.x;      // (row, sample)
-    const int Lb = len.v[b], Tb = 1 + Lb / hop;
-    float out = 0.0f;
-    if (n < Lb) out = istft_ola_sample<HALF>(frames + (long)b * T * n_fft, window, n, Tb, n_fft, hop);
-    pcm_store<FMT>(wav, b, n, out, n < L);
-}
-
-void launch_istft_ola_lengths(const float* frames, const float* window, const PcmOut& wav, int B, int T, int L, const int* samples, int n_fft,
-                              int hop, hipStream_t s) {
-    for (int b0 = 0; b0 < B; b0 += kLenRows) {
-        const int rows = B - b0 < kLenRows ? B - b0 : kLenRows;
-        RowLengths len{};
-        for (int r = 0; r < rows; ++r) len.v[r] = samples[b0 + r];
-        const dim3 grid((unsigned)((L + 255) / 256), rows);
-        const float* fr = frames + (long)b0 * T * n_fft;
-#define FSNP_CALL(F)                                                                                                                       \
-    if (2 * hop == n_fft) hipLaunchKernelGGL((istft_ola_lengths_kernel<true, F>), grid, dim3(256), 0, s, fr, window, pcm_rows(wav, b0), T, L, n_fft, hop, len); \
-    else hipLaunchKernelGGL((istft_ola_lengths_kernel<false, F>), grid, dim3(256), 0, s, fr, window, pcm_rows(wav, b0), T, L, n_fft, hop, len)
-        FSNP_PCM_SWITCH3(wav.fmt, FSNP_CALL);
-#undef FSNP_CALL
-    }
+    });
 }
 
 // Host: GEMM operands (zero padded as tcn_gemm_kernel expects: rows to a multiple of 384, K to a multiple of 16).  They depend on n_fft

@@ -286,7 +286,7 @@ def _nan_past(wav, samples):
 
 
 def test_enhance_wave_300_utterances():
-    """launch_stft_pad_lengths / launch_istft_ola_lengths / the cIRM epilogue: 256 rows per launch, rows 256 ... 299 in the second."""
+    """launch_stft_pad / launch_istft_ola / the cIRM epilogue with lengths: 256 rows per launch, rows 256 ... 299 in the second."""
     sd = make_state_dict(41, "harsh", attention="SE")
     L = 4 * HOP + 1
     base = [HOP + 1, 2 * HOP - 1, 2 * HOP, 2 * HOP + 1, 3 * HOP, L]

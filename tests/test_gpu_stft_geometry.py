@@ -281,3 +281,91 @@ def test_a_live_session_whose_finish_needs_more_than_16_rows_is_refused_at_creat
     m.hop_length = 80                                        # 2 + 13 frames: a live session again
     with m.open_wave_stream(1, max_samples=80, live=True) as ws:
         assert ws.delay == 320 + 13 * 80 and ws.hop_length == 80
+
+
+# ------------------------------------------------------------------------------------------------ 8. one set of whole-clip kernels
+# A batch of equal clips is the batch of clips of different lengths whose lengths are all equal: the whole-clip waveform path has one
+# kernel body per step, and a call without lengths= runs it with the one length every row has.  The one thing that is NOT a function of
+# the sample count is the number of frames the overlap-add sums: fsnp_istft sums every frame it is given.
+@pytest.mark.parametrize("hop,T", [(80, 8), (160, 5)])
+def test_istft_sums_every_frame_it_is_given(hop, T):
+    """fsnp_istft takes any frames with (frames - 1) hop + n_fft >= length + n_fft / 2, so more than the 1 + length / hop of the clip's
+    own STFT: the spare frames still reach into the clip's last samples, as in torch.istft(..., length=).  [2, 161, T] random spectra,
+    length 200 (3 frames at hop 80, 2 at hop 160 - the two-frame branch of the default geometry - would do) against torch on the CPU
+    under the 1e-5 of test_stft_istft_vs_torch_at_any_hop.  An overlap-add over the clip's own frames alone is 8e-2 off."""
+    L, n_fft = 200, 320
+    assert T > 1 + L // hop
+    rng = torch.Generator().manual_seed(hop)
+    spec = torch.complex(torch.randn((2, 161, T), generator=rng), torch.randn((2, 161, T), generator=rng))
+    want = fsnp_torch.istft(spec, L, n_fft, hop, n_fft)
+    m = _plus(161)
+    m.hop_length = hop
+    try:
+        got = m.istft(spec.cuda(), L).cpu()
+    finally:
+        m.hop_length = 160
+    err = _rel(got, want)
+    print(f"istft of {T} frames at hop {hop} into {L} samples: rel err {err:.2e}")
+    assert got.shape == want.shape == (2, L) and err < 1e-5, err
+
+
+@pytest.mark.parametrize("hop", [160, 80])
+def test_a_batch_of_equal_clips_is_the_ragged_batch_with_equal_lengths_bit_for_bit(hop):
+    """B = 3 x 4000 samples at F = 161: enhance_wave(w) against enhance_wave(w, lengths=[4000] * 3) as fp32, as int16 with the clipped
+    counts and peak-normalised, and enhance(X) against enhance(X, lengths=[T] * 3)."""
+    m = _model(FullSubNet_Plus, dict(WAVE_ARGS, num_freqs=161), make_state_dict(41, "harsh", num_freqs=161, attention="SE"))
+    m.hop_length = hop
+    wav = torch.from_numpy(make_wave(3, 0.25, 611)).cuda()
+    L = wav.shape[1]
+    assert L == 4000
+    for fmt in ("f32", "s16", "s16_peak"):
+        ca, cb = (torch.full((3,), -1, dtype=torch.int32, device="cuda") for _ in range(2))
+        counts = fmt == "s16"
+        a = m.enhance_wave(wav, out_format=fmt, clipped=ca if counts else None)
+        b = m.enhance_wave(wav, lengths=[L] * 3, out_format=fmt, clipped=cb if counts else None)
+        m.check_errors()
+        assert a.dtype == b.dtype == (torch.float32 if fmt == "f32" else torch.int16) and a.shape == b.shape == (3, L)
+        assert torch.count_nonzero(a) > 0 and torch.equal(a, b), fmt
+        if counts:
+            print(f"hop {hop}: clipped samples per row {ca.tolist()}")
+            assert (ca >= 0).all() and torch.equal(ca, cb)
+    X = m.stft(wav)
+    T = X.shape[-1]
+    assert T == 1 + L // hop
+    assert torch.equal(m.enhance(X), m.enhance(X, lengths=[T] * 3))
+    m.check_errors()
+
+
+def _row_errs(got, want, rows=(0, 255, 256)):
+    """worst relative error of the whole batch and of each row of `rows` against that row's own maximum"""
+    return [_rel(got, want)] + [_rel(got[r], want[r]) for r in rows]
+
+
+def test_equal_clips_past_the_256_rows_of_one_launch():
+    """The launchers walk a batch 256 rows per launch, with or without lengths: B = 257 puts row 256 into a launch of its own.  The
+    cIRM epilogue at [257, 3, 4] against oracle.fsnp_torch.apply_cirm, stft and istft of 257 x 400 samples against torch on the CPU; the
+    whole batch and rows 0, 255 and 256 each.  Bounds: 1e-5 for the transforms, as test_stft_istft_vs_torch_at_any_hop; 1e-5 for the
+    epilogue: a mask value near 0 goes through log((K - v) / (K + v)) of an argument near 1, where three fp32 roundings (2^-24 each)
+    times K = 10 leave up to 2e-6 absolute in the decompressed mask of either side, on values of the order of 1."""
+    B = 257
+    m = _plus(161)
+    rng = torch.Generator().manual_seed(257)
+    mask = torch.randn((B, 2, 3, 4), generator=rng)
+    X = torch.complex(torch.randn((B, 3, 4), generator=rng), torch.randn((B, 3, 4), generator=rng))
+    got = m._apply_cirm(mask.cuda(), X.cuda()).cpu()
+    errs = _row_errs(torch.view_as_real(got), torch.view_as_real(fsnp_torch.apply_cirm(mask, X)))
+    print("apply_cirm B257: rel err of all rows, row 0, row 255, row 256:", " ".join(f"{e:.2e}" for e in errs))
+    assert max(errs) < 1e-5, errs
+    L, n_fft, hop = 400, 320, 160
+    wav = torch.from_numpy(make_wave(B, L / 16000.0, 257))
+    assert wav.shape == (B, L) and not torch.equal(wav[255], wav[256])
+    want = fsnp_torch.stft(wav, n_fft, hop, n_fft)
+    got = m.stft(wav.cuda()).cpu()
+    assert got.shape == want.shape == (B, 161, 1 + L // hop)
+    errs = _row_errs(torch.view_as_real(got), torch.view_as_real(want))
+    print("stft B257: rel err of all rows, row 0, row 255, row 256:", " ".join(f"{e:.2e}" for e in errs))
+    assert max(errs) < 1e-5, errs
+    spec = torch.complex(torch.randn(want.shape, generator=rng), torch.randn(want.shape, generator=rng))
+    errs = _row_errs(m.istft(spec.cuda(), L).cpu(), fsnp_torch.istft(spec, L, n_fft, hop, n_fft))
+    print("istft B257: rel err of all rows, row 0, row 255, row 256:", " ".join(f"{e:.2e}" for e in errs))
+    assert max(errs) < 1e-5, errs
