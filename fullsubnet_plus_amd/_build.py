@@ -2,6 +2,7 @@
 
 Every csrc/*.hip is compiled to its own object (in parallel, cached by content hash under csrc/build/) and the objects are
 linked into one shared library, so touching one kernel file costs one compile instead of eight."""
+import glob
 import hashlib
 import os
 import shutil
@@ -14,12 +15,7 @@ OBJDIR = os.path.join(CSRC, "build")
 LIB_PATH = os.path.join(HERE, "libfsnp_hip.so")
 SOURCES = ["fsnp_abi.hip", "forward_kernels.hip", "fsnp_verify.hip", "fsnp_debug_abi.hip", "fsnp_weights.hip", "weight_pack.hip", "fsnp_stft_abi.hip", "fsnp_stream_abi.hip", "fsnp_wave_stream_abi.hip", "fsnp_spec_stream_abi.hip", "planner.cpp", "frontend.hip", "tcn.hip", "subband.hip", "lstm.hip", "lstm16.hip", "lstm_gru.hip", "lstm_coop.hip",
            "lstm_hp.hip", "lstm_hpw.hip", "lstm_generic.hip", "lstm_step.hip", "lstm_coopn.hip", "lstm_coopw.hip", "lstm_fbv.hip", "stft.hip", "stft_stream.hip", "pcm.hip", "spec_stream.hip", "box_probe.hip", "stages.hip"]
-HEADERS = [os.path.join(CSRC, "fsnp_common.h"), os.path.join(CSRC, "lstm_common.h"), os.path.join(CSRC, "planner.h"), os.path.join(CSRC, "fsnp_handle.h"), os.path.join(CSRC, "weight_watch.h"), os.path.join(CSRC, "weight_layouts.h"), os.path.join(CSRC, "pcm.h"),
-           os.path.join(os.path.dirname(HERE), "include", "fsnp.h"), os.path.join(os.path.dirname(HERE), "include", "fsnp_debug.h"),
-           os.path.join(os.path.dirname(HERE), "include", "fsnp_lengths.h"), os.path.join(os.path.dirname(HERE), "include", "fsnp_stream.h"),
-           os.path.join(os.path.dirname(HERE), "include", "fsnp_wave_stream.h"), os.path.join(os.path.dirname(HERE), "include", "fsnp_stream_live.h"),
-           os.path.join(os.path.dirname(HERE), "include", "fsnp_spec_stream.h"), os.path.join(os.path.dirname(HERE), "include", "fsnp_device_weights.h"),
-           os.path.join(os.path.dirname(HERE), "include", "fsnp_stft_geometry.h"), os.path.join(os.path.dirname(HERE), "include", "fsnp_pcm.h")]
+INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 # -fno-slp-vectorize: the SLP pass pairs the LSTM kernel's per-tile VALU FMAs across tiles, which breaks the
 # refill-in-place weight pipeline and makes hipcc drain vmcnt(0) + copy 48 registers every k-group
 # (no fast-math: the peak-normalised PCM output of include/fsnp_pcm.h needs the IEEE fp32 division and an uncontracted product)
@@ -38,7 +34,8 @@ def _sources():
 
 
 def _headers():
-    return [h for h in HEADERS if os.path.exists(h)]
+    """Every header a source may include: a header missing from the hash would leave a stale library in use after an edit."""
+    return sorted(glob.glob(os.path.join(CSRC, "*.h"))) + sorted(glob.glob(os.path.join(INCLUDE, "*.h")))
 
 
 def _digest(paths):

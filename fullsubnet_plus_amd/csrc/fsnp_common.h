@@ -409,7 +409,6 @@ size_t lstm_coop_exchange_bytes(int H, int row_tiles);
 // lstm_hp.hip: 16 units per workgroup (S = H / 16 workgroups per row tile, one XCD), waves split the gates, weights resident,
 // every row tile worked on as two half tiles of 16 sequences in turn (the hand-off of one half hidden behind the other)
 void launch_lstm_hp(const LstmWeights& w, const LstmArgs& a, hipStream_t s);
-bool lstm_hp_available(const LstmWeights& w);
 // lstm_hpw.hip: the same launch shape, exchange region and counters; a WAVE owns 4 units x 4 gates over the whole K (transposed MFMA:
 // lane-local cells), operands streamed L2 -> registers, no workgroup barrier in the time loop
 void launch_lstm_hpw(const LstmWeights& w, const LstmArgs& a, hipStream_t s);
@@ -417,8 +416,6 @@ bool lstm_hpw_available(const LstmWeights& w);
 // lstm_coopw.hip: a wave owns 8 NT hidden units over the full K, S = H / (32 NT) workgroups per row tile (a.coop_units = 32 NT in
 // {32, 64}), layer-skewed schedule without workgroup barriers: 11 ... 42 row tiles per launch (B = 2 ... 8)
 void launch_lstm_coopw(const LstmWeights& w, const LstmArgs& a, hipStream_t s);
-bool lstm_coopw_available(const LstmWeights& w, int units);
-int lstm_coopw_occupancy(const LstmWeights& w, int units);
 // lstm_fbv.hip: the full-band LSTM(num_freqs -> 512 x 2) of the original FullSubNet for 1 ... 4 utterances as matrix-VECTOR products
 // on the VALU (weights resident, H / 8 workgroups, serial schedule with one hand-off per step); h1 sequence out
 void launch_lstm_fbv(const LstmWeights& w, const LstmArgs& a, hipStream_t s);

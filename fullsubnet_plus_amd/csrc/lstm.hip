@@ -48,23 +48,11 @@ __host__ __device__ __forceinline__ int e_frag_index(int e, int k) {
 // Consume `ngroups` k-groups: A from LDS (A already offset by lane), B from the rotating register
 // buffer `b` (always holding the group about to be used); refills b from the weight stream.
 // AE (offset by (lane>>5)*EX) is the E-image of the extra rows; accx their per-lane partial sums.
-// One 1 KiB weight fragment (tile n of k-group g) of this wave's stream: SRD in SGPRs, constant per-lane
-// voffset (lane * 16), everything else in the scalar offset - no VALU address math in the hot loop, and the
-// cheapest load form measured next to MFMAs (tools/ubench/mfma_issue.hip: 18 vs 23.5 pipe cycles).
-struct WStream {
-    __amdgpu_buffer_rsrc_t rsrc;
-    int voff;
-};
-template <int NT>
-__device__ __forceinline__ float4 wload(const WStream& ws, int g, int n) {
-    const auto v = __builtin_amdgcn_raw_buffer_load_b128(ws.rsrc, ws.voff, (g * NT + n) * 1024, 0);
-    return __builtin_bit_cast(float4, v);
-}
-
+// The weight stream (BufStream / wload, lstm_common.h) is this wave's private slice.
 template <int NT, int EX>
 __device__ __forceinline__ void mfma_groups(f32x16 (&acc)[NT], float (&accx)[EX > 0 ? EX : 1][NT], float4 (&b)[NT],
                                             const float4* __restrict__ A, const float4* __restrict__ AE, int ngroups,
-                                            const WStream& ws, int& gnext, int groups_total) {
+                                            const BufStream& ws, int& gnext, int groups_total) {
     float4 a = A[0];
     float4 ae[EX > 0 ? EX : 1];
 #pragma unroll
@@ -126,11 +114,6 @@ __device__ __forceinline__ void mfma_groups(f32x16 (&acc)[NT], float (&accx)[EX 
     }
 }
 
-// bf16 (round-to-nearest-even) bits of an fp32 value
-__device__ __forceinline__ unsigned short bf16_bits(float v) {
-    const unsigned u = __float_as_uint(v);
-    return (unsigned short)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
 // index (in 2-byte elements) of element (row, k) inside the bf16 A image of v_mfma_f32_32x32x16_bf16:
 // [k-step of 16][k half of 8][row][8]  - lane l of a step reads the 16 bytes of (half l>>5, row l&31)
 __host__ __device__ __forceinline__ int a_frag_index_bf16(int row, int k) {
@@ -180,7 +163,7 @@ using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 template <int NT, int EX, int ALO>
 __device__ __forceinline__ void mfma_groups_bf16(f32x16 (&acc)[NT], float (&accx)[EX > 0 ? EX : 1][NT], float4 (&b)[NT],
                                                  const float4* __restrict__ A, const float4* __restrict__ AE, int nsteps,
-                                                 const WStream& ws, int& gnext, int groups_total, int lane) {
+                                                 const BufStream& ws, int& gnext, int groups_total, int lane) {
     float4 a = A[0], al = A[ALO];                 // (ALO == 0 - VALU-row tiles - : hi only)
     for (int g = 0; g < nsteps; ++g) {
         const float4 an = A[(g + 1 < nsteps ? g + 1 : g) * 64], aln = A[ALO + (g + 1 < nsteps ? g + 1 : g) * 64];
@@ -385,7 +368,7 @@ void lstm2_fc_kernel(LstmWeights w, LstmArgs a) {
         for (int e = 0; e < EXA; ++e) { cx0[e][s] = 0.0f; cx1[e][s] = 0.0f; }
     }
 
-    WStream ws;
+    BufStream ws;
     ws.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(w.wpack) + (size_t)wave * KGT * NT * 256, 0,
                                                 KGT * NT * 1024, 0x00020000);
     ws.voff = lane * 16;
@@ -714,7 +697,7 @@ void lstm2_fc_stream_kernel(LstmWeights w, LstmArgs a) {
     stream_state_io<ST, UW, HID, true>(c0, c1, reinterpret_cast<float*>(H0s), reinterpret_cast<float*>(H1s), rows_s, a.st_sb, a.st_stride, 0,
                                        wave, lane);
 
-    WStream ws;
+    BufStream ws;
     ws.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(w.wpack) + (size_t)wave * KGT * NT * 256, 0, KGT * NT * 1024, 0x00020000);
     ws.voff = lane * 16;
     float4 breg[NT];

@@ -28,18 +28,9 @@ __host__ __device__ __forceinline__ int a16_index(int row, int k) {
     return ((((k >> 4) * 4) + (k & 3)) * 16 + row) * 4 + ((k >> 2) & 3);
 }
 
-struct S16 {
-    __amdgpu_buffer_rsrc_t rsrc;
-    int voff;
-};
-template <int NT>
-__device__ __forceinline__ float4 w16load(const S16& ws, int g, int n) {
-    return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(ws.rsrc, ws.voff, (g * NT + n) * 1024, 0));
-}
-
 // `ngroups` k-groups of 16 (A already offset by lane); b holds the group about to be used and is refilled in place
 template <int NT>
-__device__ __forceinline__ void groups16(f32x4 (&acc)[NT], float4 (&b)[NT], const float4* __restrict__ A, int ngroups, const S16& ws,
+__device__ __forceinline__ void groups16(f32x4 (&acc)[NT], float4 (&b)[NT], const float4* __restrict__ A, int ngroups, const BufStream& ws,
                                          int& gnext, int groups_total) {
     float4 a = A[0];
     for (int g = 0; g < ngroups; ++g) {
@@ -55,8 +46,8 @@ __device__ __forceinline__ void groups16(f32x4 (&acc)[NT], float4 (&b)[NT], cons
             acc[n + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b[n + 1].z, acc[n + 1], 0, 0, 0);
             acc[n] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b[n].w, acc[n], 0, 0, 0);
             acc[n + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b[n + 1].w, acc[n + 1], 0, 0, 0);
-            b[n] = w16load<NT>(ws, gnext, n);
-            b[n + 1] = w16load<NT>(ws, gnext, n + 1);
+            b[n] = wload<NT>(ws, gnext, n);
+            b[n + 1] = wload<NT>(ws, gnext, n + 1);
             __builtin_amdgcn_sched_barrier(0);
         }
         gnext = (gnext + 1 == groups_total) ? 0 : gnext + 1;
@@ -70,17 +61,13 @@ __device__ __forceinline__ void groups16(f32x4 (&acc)[NT], float4 (&b)[NT], cons
 // fragments that travel through the same 16-byte-per-lane register pipeline as the fp32 groups (a k-step of 32 is NT KiB per wave,
 // exactly one fp32 k-group's worth).  A / B operand: lane l holds the 8 elements k = 32 ks + 8 (l >> 4) + j of row / column l & 15.
 using bf16x8_16 = __attribute__((ext_vector_type(8))) __bf16;
-__device__ __forceinline__ unsigned short bf16_bits16(float v) {
-    const unsigned u = __float_as_uint(v);
-    return (unsigned short)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);           // round to nearest even
-}
 // index (in 2-byte elements) of element (row < 16, k) inside the bf16 half-tile A image: [k-step of 32][k quarter of 8][row][8]
 __host__ __device__ __forceinline__ int a16_index_bf16(int row, int k) {
     return (((k >> 5) * 64) + (((k >> 3) & 3) * 16) + row) * 8 + (k & 7);
 }
 // (round 6: the bf16 A image of h0_t is a hi + lo PAIR, ALO float4 apart - every weight fragment multiplies both: lstm.hip mfma_groups_bf16)
 template <int NT, int ALO>
-__device__ __forceinline__ void groups16_bf16(f32x4 (&acc)[NT], float4 (&b)[NT], const float4* __restrict__ A, int nsteps, const S16& ws,
+__device__ __forceinline__ void groups16_bf16(f32x4 (&acc)[NT], float4 (&b)[NT], const float4* __restrict__ A, int nsteps, const BufStream& ws,
                                               int& gnext, int groups_total) {
     float4 a = A[0], al = A[ALO];
     for (int g = 0; g < nsteps; ++g) {
@@ -91,8 +78,8 @@ __device__ __forceinline__ void groups16_bf16(f32x4 (&acc)[NT], float4 (&b)[NT],
             acc[n + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_16, a), __builtin_bit_cast(bf16x8_16, b[n + 1]), acc[n + 1], 0, 0, 0);
             acc[n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_16, al), __builtin_bit_cast(bf16x8_16, b[n]), acc[n], 0, 0, 0);
             acc[n + 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_16, al), __builtin_bit_cast(bf16x8_16, b[n + 1]), acc[n + 1], 0, 0, 0);
-            b[n] = w16load<NT>(ws, gnext, n);
-            b[n + 1] = w16load<NT>(ws, gnext, n + 1);
+            b[n] = wload<NT>(ws, gnext, n);
+            b[n + 1] = wload<NT>(ws, gnext, n + 1);
             __builtin_amdgcn_sched_barrier(0);
         }
         gnext = (gnext + 1 == groups_total) ? 0 : gnext + 1;
@@ -119,11 +106,11 @@ __device__ __forceinline__ void cell16(f32x4 (&acc)[4 * SB], f32x4 (&c)[SB], flo
             Hs[a16_index(4 * (lane >> 4) + r, k)] = h.x;
             Hs[a16_index(4 * (lane >> 4) + r + 1, k)] = h.y;
             if (Hb) {           // hi + lo: h = hi + lo to ~16 mantissa bits (HBLO 2-byte elements apart)
-                const unsigned short hx = bf16_bits16(h.x), hy = bf16_bits16(h.y);
+                const unsigned short hx = bf16_bits(h.x), hy = bf16_bits(h.y);
                 const int ix = a16_index_bf16(4 * (lane >> 4) + r, k), iy = a16_index_bf16(4 * (lane >> 4) + r + 1, k);
                 Hb[ix] = hx; Hb[iy] = hy;
-                Hb[HBLO + ix] = bf16_bits16(h.x - __uint_as_float((unsigned)hx << 16));
-                Hb[HBLO + iy] = bf16_bits16(h.y - __uint_as_float((unsigned)hy << 16));
+                Hb[HBLO + ix] = bf16_bits(h.x - __uint_as_float((unsigned)hx << 16));
+                Hb[HBLO + iy] = bf16_bits(h.y - __uint_as_float((unsigned)hy << 16));
             }
         }
     }
@@ -214,12 +201,12 @@ void lstm2_fc16_kernel(LstmWeights w, LstmArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) { c0[s][r] = 0.0f; c1[s][r] = 0.0f; }
 
-    S16 ws;
+    BufStream ws;
     ws.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(w.wpack) + (size_t)wave * KGT * NT * 256, 0, KGT * NT * 1024, 0x00020000);
     ws.voff = lane * 16;
     float4 breg[NT];
 #pragma unroll
-    for (int n = 0; n < NT; ++n) breg[n] = w16load<NT>(ws, 0, n);
+    for (int n = 0; n < NT; ++n) breg[n] = wload<NT>(ws, 0, n);
     int gnext = 1;
 
     // Linear: wave w sums rows 4 w .. 4 w + 3 x 2 outputs over 8 k-parts of HID / 8 (all in-wave)

@@ -1,5 +1,9 @@
-// lstm_common.h - device helpers shared by lstm.hip (row-tile kernel) and lstm_coop.hip (column-split kernel)
+// lstm_common.h - device helpers shared by every recurrent kernel file (lstm*.hip): buffer streams, cell math, static unrolling,
+// DPP row sums, the column-split kernels' exchange protocol.  Host launch glue: lstm_launch.h.
 #pragma once
+#include <type_traits>
+#include <utility>
+
 #include "fsnp_common.h"
 
 namespace fsnp {
@@ -8,6 +12,41 @@ using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 __device__ __forceinline__ float fast_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 __device__ __forceinline__ float fast_tanh(float x) { return 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(-2.0f * x)) - 1.0f; }
+// the exact kind (IEEE division) of the generic and per-step kernels: NOT interchangeable with fast_*
+__device__ __forceinline__ float exact_sigmoid(float x) { return 1.0f / (1.0f + __expf(-x)); }
+__device__ __forceinline__ float exact_tanh(float x) { return 2.0f / (1.0f + __expf(-2.0f * x)) - 1.0f; }
+
+// bf16 (round-to-nearest-even) bits of an fp32 value
+__device__ __forceinline__ unsigned short bf16_bits(float v) {
+    const unsigned u = __float_as_uint(v);
+    return (unsigned short)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+}
+
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a loop whose index is a constant expression in the body
+template <typename F, int... I>
+__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
+template <int N, typename F>
+__device__ __forceinline__ void static_for(F&& f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
+
+// sum over the 16 lanes of a DPP row, in every lane (row_ror 8, 4, 2, 1: no LDS round trips)
+template <int N>
+__device__ __forceinline__ float row_ror(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x120 + N, 0xf, 0xf, false)); }
+__device__ __forceinline__ float row_sum16(float v) { v += row_ror<8>(v); v += row_ror<4>(v); v += row_ror<2>(v); v += row_ror<1>(v); return v; }
+
+// ---- a stream of 128-bit buffer loads: SRD in SGPRs, constant per-lane voffset (lane * 16), everything else in the scalar
+// offset - no VALU address math in a hot loop, and the cheapest load form measured next to MFMAs (tools/ubench/mfma_issue.hip:
+// 18 vs 23.5 pipe cycles).  AUX is the instruction's cache-policy immediate: 0, or kSc1 for exchange images (bypass L1, below).
+struct BufStream {
+    __amdgpu_buffer_rsrc_t rsrc;
+    int voff;
+};
+template <int AUX = 0>
+__device__ __forceinline__ float4 stream_load(const BufStream& s, int soff) {
+    return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(s.rsrc, s.voff, soff, AUX));
+}
+// one 1 KiB weight fragment (tile n of k-group g) of a stream packed [k-group][NT tiles]
+template <int NT>
+__device__ __forceinline__ float4 wload(const BufStream& ws, int g, int n) { return stream_load(ws, (g * NT + n) * 1024); }
 
 // ---- LSTM cell update on TWO cells at a time (packed fp32 VALU: v_pk_mul / v_pk_add / v_pk_fma) with 8 transcendentals
 // per cell instead of 10:   sigmoid(i) tanh(g) = (1 - eg) / ((1 + ei)(1 + eg)),   sigmoid(o) tanh(c') likewise - one v_rcp per

@@ -27,22 +27,12 @@
 
 #include "fsnp_common.h"
 #include "lstm_common.h"
+#include "lstm_launch.h"
 #include "weight_layouts.h"
 
 namespace fsnp {
 
 namespace {
-
-struct CoopStream {
-    __amdgpu_buffer_rsrc_t rsrc;
-    int voff;
-};
-
-template <int NT>
-__device__ __forceinline__ float4 coop_wload(const CoopStream& ws, int group, int n) {
-    const auto v = __builtin_amdgcn_raw_buffer_load_b128(ws.rsrc, ws.voff, (group * NT + n) * 1024, 0);
-    return __builtin_bit_cast(float4, v);
-}
 
 // One layer's share of this wave: G local k-groups (global k-group 4 i + wave - the waves interleave so that every
 // trip count is a compile-time constant and the loop unrolls into straight-line code with immediate offsets), weights
@@ -61,24 +51,24 @@ using CoopB = float4[CoopDepth<NT, G>::value][NT];        // their weight fragme
 // a whole phase earlier, so their round trip overlaps the hand-off instead of following it)
 template <int NT, int G, int XG, int WBASE, typename SrcX, typename SrcH>
 __device__ __forceinline__ void coop_layer_prefill(CoopA<NT, G>& a, CoopB<NT, G>& b,
-                                                   const CoopStream& ws, SrcX srcx, SrcH srch) {
+                                                   const BufStream& ws, SrcX srcx, SrcH srch) {
     constexpr int D = CoopDepth<NT, G>::value;
 #pragma unroll
     for (int k = 0; k < D; ++k) {
         a[k] = k < XG ? srcx(k) : srch(k - XG);
 #pragma unroll
-        for (int n = 0; n < NT; ++n) b[k][n] = coop_wload<NT>(ws, WBASE + k, n);
+        for (int n = 0; n < NT; ++n) b[k][n] = wload<NT>(ws, WBASE + k, n);
     }
 }
 
 template <int NT, int G, int XG, int WBASE, typename SrcX, typename SrcH>
 __device__ __forceinline__ void coop_layer_run(f32x16 (&acc)[NT], CoopA<NT, G>& a, CoopB<NT, G>& b,
-                                               const CoopStream& ws, SrcX srcx, SrcH srch) {
+                                               const BufStream& ws, SrcX srcx, SrcH srch) {
     constexpr int D = CoopDepth<NT, G>::value;
     auto fill = [&](int slot, int i) {
         a[slot] = i < XG ? srcx(i) : srch(i - XG);
 #pragma unroll
-        for (int n = 0; n < NT; ++n) b[slot][n] = coop_wload<NT>(ws, WBASE + i, n);
+        for (int n = 0; n < NT; ++n) b[slot][n] = wload<NT>(ws, WBASE + i, n);
     };
 #pragma unroll
     for (int i = 0; i < G; ++i) {
@@ -96,7 +86,7 @@ __device__ __forceinline__ void coop_layer_run(f32x16 (&acc)[NT], CoopA<NT, G>& 
 }
 
 template <int NT, int G, int XG, int WBASE, typename SrcX, typename SrcH>
-__device__ __forceinline__ void coop_layer(f32x16 (&acc)[NT], const CoopStream& ws, SrcX srcx, SrcH srch) {
+__device__ __forceinline__ void coop_layer(f32x16 (&acc)[NT], const BufStream& ws, SrcX srcx, SrcH srch) {
     constexpr int D = CoopDepth<NT, G>::value;
     float4 a[D];
     float4 b[D][NT];
@@ -231,7 +221,7 @@ __global__ __launch_bounds__(256) void lstm2_coop_kernel(LstmWeights w, LstmArgs
     }
 
     // ---- this wave's private weight stream: [cs][wave][local k-group][tile][lane][4]
-    CoopStream ws;
+    BufStream ws;
     ws.rsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float*>(w.wpack) + (size_t)(cs * 4 + wave) * (G0W + G1W) * NT * 256, 0, (G0W + G1W) * NT * 1024, 0x00020000);
     ws.voff = lane * 16;
@@ -240,19 +230,19 @@ __global__ __launch_bounds__(256) void lstm2_coop_kernel(LstmWeights w, LstmArgs
 #pragma unroll
         for (int i = 0; i < G0W; ++i)
 #pragma unroll
-            for (int n = 0; n < NT; ++n) bw0[i][n] = coop_wload<NT>(ws, i, n);
+            for (int n = 0; n < NT; ++n) bw0[i][n] = wload<NT>(ws, i, n);
 #pragma unroll
         for (int i = 0; i < G1W; ++i)
 #pragma unroll
-            for (int n = 0; n < NT; ++n) bw1[i][n] = coop_wload<NT>(ws, G0W + i, n);
+            for (int n = 0; n < NT; ++n) bw1[i][n] = wload<NT>(ws, G0W + i, n);
     }
     const float4* Xw = Xs + wave * 64 + lane;           // local group i of this wave = global k-group 4 i + wave
     // A operands from the exchange images: buffer loads too (a flat load would make hipcc drain vmcnt AND lgkmcnt)
-    CoopStream hs;
+    BufStream hs;
     hs.rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(hx), 0, 4 * HIMG * 16, 0x00020000);
     hs.voff = (wave * 64 + lane) * 16;
     auto hload = [&](int image, int i) -> float4 {      // image: 0/1 = h0 parity 0/1, 2/3 = h1 parity 0/1
-        return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(hs.rsrc, hs.voff, image * (HIMG * 16) + i * 4096, kSc1));
+        return stream_load<kSc1>(hs, image * (HIMG * 16) + i * 4096);
     };
 
     // ---- cell update ownership: pair p = tid + 256 i  ->  unit u = p % UNITS (fastest: conflict-free LDS reads),
@@ -541,7 +531,7 @@ __global__ __launch_bounds__(256) void lstm2_coop_skew_kernel(LstmWeights w, Lst
         for (int i = 0; i < NG; ++i) Xf[xdst0 + i * 256] = goff[i] >= 0 ? (x_load(i, 0) - m0.m) / m0.d : 0.0f;
     }
 
-    CoopStream ws;
+    BufStream ws;
     ws.rsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float*>(w.wpack) + (size_t)(cs * 4 + wave) * (G0W + G1W) * NT * 256, 0, (G0W + G1W) * NT * 1024, 0x00020000);
     ws.voff = lane * 16;
@@ -550,18 +540,18 @@ __global__ __launch_bounds__(256) void lstm2_coop_skew_kernel(LstmWeights w, Lst
 #pragma unroll
         for (int i = 0; i < G0W; ++i)
 #pragma unroll
-            for (int n = 0; n < NT; ++n) bw0[i][n] = coop_wload<NT>(ws, i, n);
+            for (int n = 0; n < NT; ++n) bw0[i][n] = wload<NT>(ws, i, n);
 #pragma unroll
         for (int i = 0; i < G1W; ++i)
 #pragma unroll
-            for (int n = 0; n < NT; ++n) bw1[i][n] = coop_wload<NT>(ws, G0W + i, n);
+            for (int n = 0; n < NT; ++n) bw1[i][n] = wload<NT>(ws, G0W + i, n);
     }
     const float4* Xw = Xs + wave * 64 + lane;
-    CoopStream hs;
+    BufStream hs;
     hs.rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(hx), 0, coop_tile_f4(HID) * 16, 0x00020000);
     hs.voff = (wave * 64 + lane) * 16;
     auto hload = [&](int off_f4, int i) -> float4 {      // local k-group i (global 4 i + wave) of the image at float4 offset off_f4
-        return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(hs.rsrc, hs.voff, off_f4 * 16 + i * 4096, kSc1));
+        return stream_load<kSc1>(hs, off_f4 * 16 + i * 4096);
     };
 
     int prow[NP], pk[NP], pred[NP][4];
@@ -777,40 +767,23 @@ size_t lstm_coop_exchange_bytes(int H, int row_tiles) {
     return (size_t)row_tiles * (size_t)coop_tile_f4(H) * 16;
 }
 
-// dynamic LDS a launch may claim to keep a CU to itself (LstmArgs::coop_own_cu): 160 KiB per CU minus the static __shared__ words
-constexpr size_t kOwnCuLds = 160 * 1024 - 256;
-
 // occ != nullptr: do not launch; report how many workgroups of this instantiation fit one CU at once
 template <int HID, int KX, int UNITS, bool SEQ, bool GRU>
 static void launch_coop_inst(const LstmWeights& w, const LstmArgs& a, hipStream_t s, int* occ) {
     constexpr int S = HID / UNITS, NT = UNITS / 8;
     const size_t smem_need = (size_t)coop_kgxp(KX) * 64 * 16 + (size_t)4 * NT * 16 * 64 * 4 + 32 * sizeof(RowDesc);
-    auto kern = lstm2_coop_kernel<HID, KX, UNITS, SEQ, GRU>;
-    static PerDeviceOnce attr_once;            // the attribute is per device: one process may drive several GPUs
-    attr_once.run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kOwnCuLds); });
-    if (occ) {
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, reinterpret_cast<const void*>(kern), 256, smem_need) != hipSuccess) *occ = 0;
-        return;
-    }
-    const size_t smem = a.coop_own_cu > 0 && (size_t)a.coop_own_cu > smem_need ? (size_t)a.coop_own_cu : smem_need;
     LstmWeights wv = w;
     wv.wpack = w.wpack_coop[coop_units_index(UNITS)];
-    const int grid = a.coop_xcd ? 8 * xcd_local_blocks_per_xcd(S, a.num_tiles, a.coop_xcd) : a.num_tiles * S;
-    if constexpr (!SEQ) {
-        // layer-skewed schedule (lstm2_coop_skew_kernel), same launch shape.  Measured (profiles/r02_column_split.md): 16 units per
-        // workgroup and up: 9 tiles 19.8 -> 18.0 us per step, 17 tiles 28.1 -> 25.8, 41 tiles 53.0 -> 48.4.  At 8 units it did not
-        // pay in round 2 (1 tile 11.0 -> 10.8, 5 tiles 16 -> 28) - its two arrival counters per tile sat in the one cache line all
-        // counters shared; with a line per counter (round 3, profiles/r03_column_split.md section 8) it does: 1 tile 9.7 -> 8.8,
-        // 5 tiles 10.4 -> 9.1.
-        if (a.coop_skew) {
-            auto skew = lstm2_coop_skew_kernel<HID, KX, UNITS, GRU>;
-            static PerDeviceOnce skew_once;
-            skew_once.run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(skew), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kOwnCuLds); });
-            hipLaunchKernelGGL(skew, dim3(grid), dim3(256), smem, s, wv, a);
-            return;
-        }
+    if (SEQ || occ || !a.coop_skew) {
+        launch_column_split<lstm2_coop_kernel<HID, KX, UNITS, SEQ, GRU>>(wv, a, s, S, a.num_tiles, smem_need, occ);
+        return;
     }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, s, wv, a);
+    // layer-skewed schedule (lstm2_coop_skew_kernel), same launch shape.  Measured (profiles/r02_column_split.md): 16 units per
+    // workgroup and up: 9 tiles 19.8 -> 18.0 us per step, 17 tiles 28.1 -> 25.8, 41 tiles 53.0 -> 48.4.  At 8 units it did not
+    // pay in round 2 (1 tile 11.0 -> 10.8, 5 tiles 16 -> 28) - its two arrival counters per tile sat in the one cache line all
+    // counters shared; with a line per counter (round 3, profiles/r03_column_split.md section 8) it does: 1 tile 9.7 -> 8.8,
+    // 5 tiles 10.4 -> 9.1.
+    if constexpr (!SEQ) launch_column_split<lstm2_coop_skew_kernel<HID, KX, UNITS, GRU>>(wv, a, s, S, a.num_tiles, smem_need, nullptr);
 }
 
 // Finest column split (fewest units per workgroup, >= min_units) whose row_tiles * H / units workgroups are all
@@ -822,39 +795,19 @@ int lstm_coop_pick_units(int H, int row_tiles, int num_cus, int min_units) {
 }
 
 template <int HID, int KX, bool SEQ, bool GRU>
-static void launch_coop_units(const LstmWeights& w, const LstmArgs& a, hipStream_t s, int* occ = nullptr) {
-    switch (a.coop_units) {
-        case 8: launch_coop_inst<HID, KX, 8, SEQ, GRU>(w, a, s, occ); break;
-        case 16: launch_coop_inst<HID, KX, 16, SEQ, GRU>(w, a, s, occ); break;
-        case 32: launch_coop_inst<HID, KX, 32, SEQ, GRU>(w, a, s, occ); break;
-        default:
-            if constexpr (!SEQ) launch_coop_inst<HID, KX, 64, SEQ, GRU>(w, a, s, occ);
-            else launch_coop_inst<HID, KX, 32, SEQ, GRU>(w, a, s, occ);
-            break;
-    }
+static void launch_coop_units(const LstmWeights& w, const LstmArgs& a, hipStream_t s, int* occ) {
+    // (the full-band model has no 64-unit instantiation)
+    dispatch_int<8, 16, 32, (SEQ ? 32 : 64)>(a.coop_units, [&](auto U) { launch_coop_inst<HID, KX, decltype(U)::value, SEQ, GRU>(w, a, s, occ); });
 }
 
-// sub-band model: H = 384, x gathered (or dense [seq][t][NIN]), fused Linear(384, 2); w.gru selects nn.GRU
-template <int HID>
-static void dispatch_lstm_coop_h(const LstmWeights& w, const LstmArgs& a, hipStream_t s, int* occ) {   // other hidden sizes: K = 40 / 64
-    if (w.KX == 64) {
-        if (w.gru) launch_coop_units<HID, 64, false, true>(w, a, s, occ);
-        else launch_coop_units<HID, 64, false, false>(w, a, s, occ);
-        return;
-    }
-    if (w.gru) launch_coop_units<HID, 40, false, true>(w, a, s, occ);
-    else launch_coop_units<HID, 40, false, false>(w, a, s, occ);
-}
+// sub-band model: x gathered (or dense [seq][t][NIN]), fused Linear(H, 2); w.gru selects nn.GRU.  H = 256 / 512 (sb_model_hidden_size)
+// or the default 384, K = 64 (sub-band inputs of 41..64 features) or the default 40
 static void dispatch_lstm_coop(const LstmWeights& w, const LstmArgs& a, hipStream_t s, int* occ) {
-    if (w.H == 256) { dispatch_lstm_coop_h<256>(w, a, s, occ); return; }      // sb_model_hidden_size 256 / 512
-    if (w.H == 512) { dispatch_lstm_coop_h<512>(w, a, s, occ); return; }
-    if (w.KX == 64) {                  // sub-band inputs of 41..64 features
-        if (w.gru) launch_coop_units<384, 64, false, true>(w, a, s, occ);
-        else launch_coop_units<384, 64, false, false>(w, a, s, occ);
-        return;
-    }
-    if (w.gru) launch_coop_units<384, 40, false, true>(w, a, s, occ);
-    else launch_coop_units<384, 40, false, false>(w, a, s, occ);
+    dispatch_int<256, 512, 384>(w.H, [&](auto H) {
+        dispatch_int<64, 40>(w.KX, [&](auto KX) {
+            dispatch_bool(w.gru, [&](auto GRU) { launch_coop_units<decltype(H)::value, decltype(KX)::value, false, decltype(GRU)::value>(w, a, s, occ); });
+        });
+    });
 }
 void launch_lstm_coop(const LstmWeights& w, const LstmArgs& a, hipStream_t s) { dispatch_lstm_coop(w, a, s, nullptr); }
 // workgroups of the sub-band K-split kernel at `units` hidden units per workgroup that fit one CU at once (0 = unknown)
@@ -867,17 +820,16 @@ int lstm_coop_occupancy(const LstmWeights& w, int units) {
 }
 
 // full-band model of the original FullSubNet: H = 512, dense input rows of <= 264 features, h1 sequence out
-void launch_lstm_coop_seq(const LstmWeights& w, const LstmArgs& a, hipStream_t s) {
-    if (w.gru) launch_coop_units<512, 264, true, true>(w, a, s);
-    else launch_coop_units<512, 264, true, false>(w, a, s);
+static void dispatch_lstm_coop_seq(const LstmWeights& w, const LstmArgs& a, hipStream_t s, int* occ) {
+    dispatch_bool(w.gru, [&](auto GRU) { launch_coop_units<512, 264, true, decltype(GRU)::value>(w, a, s, occ); });
 }
+void launch_lstm_coop_seq(const LstmWeights& w, const LstmArgs& a, hipStream_t s) { dispatch_lstm_coop_seq(w, a, s, nullptr); }
 // workgroups of that kernel at `units` hidden units per workgroup that fit one CU at once (0 = unknown)
 int lstm_coop_seq_occupancy(const LstmWeights& w, int units) {
     LstmArgs a{};
     a.coop_units = units;
     int occ = 0;
-    if (w.gru) launch_coop_units<512, 264, true, true>(w, a, nullptr, &occ);
-    else launch_coop_units<512, 264, true, false>(w, a, nullptr, &occ);
+    dispatch_lstm_coop_seq(w, a, nullptr, &occ);
     return occ;
 }
 

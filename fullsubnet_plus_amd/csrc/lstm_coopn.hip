@@ -16,22 +16,11 @@
 // The Linear(H, 2) epilogue is a per-wave partial dot, summed in a fixed order by workgroup cs == 0 one step later.
 #include "fsnp_common.h"
 #include "lstm_common.h"
+#include "lstm_launch.h"
 
 namespace fsnp {
 
 namespace {
-
-struct NStream {
-    __amdgpu_buffer_rsrc_t rsrc;
-    int voff;
-};
-
-__device__ __forceinline__ float4 nload(const NStream& s, int soff) {
-    return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(s.rsrc, s.voff, soff, 0));
-}
-__device__ __forceinline__ float4 nload_sc1(const NStream& s, int soff) {    // exchange images: bypass L1 (lstm_common.h)
-    return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(s.rsrc, s.voff, soff, kSc1));
-}
 
 __device__ __forceinline__ void mfma16(f32x16 (&acc)[4], const float4& a, const float4 (&b)[4]) {
 #pragma unroll
@@ -46,14 +35,14 @@ __device__ __forceinline__ void mfma16(f32x16 (&acc)[4], const float4& a, const 
 // G (<= 8) k-groups, fully unrolled, every load issued up front.  aload(g) -> A fragment of group g,
 // weights at stream groups [wbase, wbase + G).
 template <int G, typename ALoad>
-__device__ __forceinline__ void coopn_unrolled(f32x16 (&acc)[4], const NStream& ws, int wbase, ALoad aload) {
+__device__ __forceinline__ void coopn_unrolled(f32x16 (&acc)[4], const BufStream& ws, int wbase, ALoad aload) {
     float4 a[G];
     float4 b[G][4];
 #pragma unroll
     for (int k = 0; k < G; ++k) {
         a[k] = aload(k);
 #pragma unroll
-        for (int n = 0; n < 4; ++n) b[k][n] = nload(ws, (wbase + k) * 4096 + n * 1024);
+        for (int n = 0; n < 4; ++n) b[k][n] = stream_load(ws, (wbase + k) * 4096 + n * 1024);
     }
 #pragma unroll
     for (int k = 0; k < G; ++k) {
@@ -64,7 +53,7 @@ __device__ __forceinline__ void coopn_unrolled(f32x16 (&acc)[4], const NStream& 
 
 // G (multiple of 4, >= 8) k-groups: register pipeline 4 groups (= 4096 MFMA cycles) deep, refill in place.
 template <int G, typename ALoad>
-__device__ __forceinline__ void coopn_loop(f32x16 (&acc)[4], const NStream& ws, int wbase, ALoad aload) {
+__device__ __forceinline__ void coopn_loop(f32x16 (&acc)[4], const BufStream& ws, int wbase, ALoad aload) {
     static_assert(G % 4 == 0 && G >= 8, "pipeline shape");
     float4 a[4];
     float4 b[4][4];
@@ -72,7 +61,7 @@ __device__ __forceinline__ void coopn_loop(f32x16 (&acc)[4], const NStream& ws, 
     for (int k = 0; k < 4; ++k) {
         a[k] = aload(k);
 #pragma unroll
-        for (int n = 0; n < 4; ++n) b[k][n] = nload(ws, (wbase + k) * 4096 + n * 1024);
+        for (int n = 0; n < 4; ++n) b[k][n] = stream_load(ws, (wbase + k) * 4096 + n * 1024);
     }
     for (int g0 = 0; g0 < G - 4; g0 += 4) {
 #pragma unroll
@@ -80,7 +69,7 @@ __device__ __forceinline__ void coopn_loop(f32x16 (&acc)[4], const NStream& ws, 
             mfma16(acc, a[k], b[k]);
             a[k] = aload(g0 + k + 4);
 #pragma unroll
-            for (int n = 0; n < 4; ++n) b[k][n] = nload(ws, (wbase + g0 + k + 4) * 4096 + n * 1024);
+            for (int n = 0; n < 4; ++n) b[k][n] = stream_load(ws, (wbase + g0 + k + 4) * 4096 + n * 1024);
             __builtin_amdgcn_sched_barrier(0);
         }
     }
@@ -181,12 +170,12 @@ __global__ __launch_bounds__(256) void lstm2_coopn_kernel(LstmWeights w, LstmArg
     }
 
     // ---- this wave's weight stream [unit block][k-group: x | h0, then h1 | h0][gate][lane][4]
-    NStream ws;
+    BufStream ws;
     ws.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(w.wpack) + (size_t)ub * (KG0 + KG1) * 1024, 0,
                                                 (KG0 + KG1) * 4096, 0x00020000);
     ws.voff = lane * 16;
     // A operands from the exchange images of each row tile
-    NStream hs[R];
+    BufStream hs[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         hs[r].rsrc = __builtin_amdgcn_make_buffer_rsrc(a.coop_hx + (size_t)rt[r] * HXT * 4, 0, 4 * HIMG * 16, 0x00020000);
@@ -267,7 +256,7 @@ __global__ __launch_bounds__(256) void lstm2_coopn_kernel(LstmWeights w, LstmArg
                 for (int q = 0; q < 16; ++q) acc[n][q] = 0.0f;
             const float4* xw = Xs[cur][r] + lane;
             coopn_unrolled<KGX>(acc, ws, 0, [&](int k) -> float4 { return xw[k * 64]; });
-            coopn_loop<KGH>(acc, ws, KGX, [&](int k) -> float4 { return nload_sc1(hs[r], prv * (HIMG * 16) + k * 1024); });
+            coopn_loop<KGH>(acc, ws, KGX, [&](int k) -> float4 { return stream_load<kSc1>(hs[r], prv * (HIMG * 16) + k * 1024); });
             float* img = reinterpret_cast<float*>(a.coop_hx + ((size_t)rt[r] * HXT + (size_t)cur * HIMG) * 4);
 #pragma unroll
             for (int q = 0; q < 16; q += 2) {                  // two cells per pass: packed fp32 math (lstm_common.h)
@@ -297,8 +286,8 @@ __global__ __launch_bounds__(256) void lstm2_coopn_kernel(LstmWeights w, LstmArg
             for (int n = 0; n < 4; ++n)
 #pragma unroll
                 for (int q = 0; q < 16; ++q) acc[n][q] = 0.0f;
-            coopn_loop<KGH>(acc, ws, KG0, [&](int k) -> float4 { return nload_sc1(hs[r], (2 + prv) * (HIMG * 16) + k * 1024); });
-            coopn_loop<KGH>(acc, ws, KG0 + KGH, [&](int k) -> float4 { return nload_sc1(hs[r], cur * (HIMG * 16) + k * 1024); });
+            coopn_loop<KGH>(acc, ws, KG0, [&](int k) -> float4 { return stream_load<kSc1>(hs[r], (2 + prv) * (HIMG * 16) + k * 1024); });
+            coopn_loop<KGH>(acc, ws, KG0 + KGH, [&](int k) -> float4 { return stream_load<kSc1>(hs[r], cur * (HIMG * 16) + k * 1024); });
             float* img = reinterpret_cast<float*>(a.coop_hx + ((size_t)rt[r] * HXT + (size_t)(2 + cur) * HIMG) * 4);
             float* part = a.coop_hx + ((size_t)rt[r] * HXT + 4 * HIMG) * 4 + ((size_t)cur * (4 * S) + ub) * 64;
 #pragma unroll
@@ -340,59 +329,30 @@ int lstm_coopn_plan(int H, int row_tiles, int num_cus, int* groups) {
     return R;
 }
 
-template <int R, bool GRU, int KX, int HID = 384>
-static void launch_coopn_inst(const LstmWeights& w, const LstmArgs& a, hipStream_t s, int* occ) {
+// a.coop_groups groups of R = a.coop_rows_per_group (1, 2) row tiles x H / 128 workgroups.  H = 256 / 512 (sb_model_hidden_size) or the
+// default 384, K = 64 (sub-band inputs of 41..64 features) or the default 40.  occ: launch_column_split (lstm_launch.h)
+static void dispatch_lstm_coopn(const LstmWeights& w, const LstmArgs& a, hipStream_t s, int* occ) {
     LstmWeights wv = w;
     wv.wpack = w.wpack_coopn;
-    if (occ) {        // do not launch: how many workgroups of this instantiation fit one CU at once
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, reinterpret_cast<const void*>(lstm2_coopn_kernel<HID, KX, R, GRU>), 256, 0) != hipSuccess) *occ = 0;
-        return;
-    }
-    const int grid = a.coop_xcd ? 8 * xcd_local_blocks_per_xcd(HID / 128, a.coop_groups, a.coop_xcd) : a.coop_groups * (HID / 128);
-    // LstmArgs::coop_own_cu: claim the rest of the CU's LDS as (unused) dynamic LDS so that no LDS-using workgroup of a
-    // concurrent kernel shares the CU (pipelined loop: the next forward's full-band GEMMs)
-    auto kern = lstm2_coopn_kernel<HID, KX, R, GRU>;
-    static PerDeviceOnce attr_once;
-    static int static_lds = 0;
-    attr_once.run([&] {
-        hipFuncAttributes fa{};
-        if (hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kern)) == hipSuccess) static_lds = (int)fa.sharedSizeBytes;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - static_lds);
+    dispatch_int<256, 512, 384>(w.H, [&](auto H) {
+        dispatch_int<64, 40>(w.KX, [&](auto KX) {
+            dispatch_bool(w.gru, [&](auto GRU) {
+                dispatch_int<1, 2>(a.coop_rows_per_group, [&](auto R) {
+                    constexpr int HID = decltype(H)::value;
+                    launch_column_split<lstm2_coopn_kernel<HID, decltype(KX)::value, decltype(R)::value, decltype(GRU)::value>, true>(
+                        wv, a, s, HID / 128, a.coop_groups, 0, occ);
+                });
+            });
+        });
     });
-    const int pad = a.coop_own_cu > 0 ? a.coop_own_cu - static_lds : 0;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), pad > 0 ? pad : 0, s, wv, a);
 }
 
-template <int KX, int HID = 384>
-static void launch_coopn_kx(const LstmWeights& w, const LstmArgs& a, hipStream_t s, int* occ) {
-    if (w.gru) {
-        if (a.coop_rows_per_group == 1) launch_coopn_inst<1, true, KX, HID>(w, a, s, occ);
-        else launch_coopn_inst<2, true, KX, HID>(w, a, s, occ);
-    } else {
-        if (a.coop_rows_per_group == 1) launch_coopn_inst<1, false, KX, HID>(w, a, s, occ);
-        else launch_coopn_inst<2, false, KX, HID>(w, a, s, occ);
-    }
-}
-template <int HID>
-static void launch_coopn_h(const LstmWeights& w, const LstmArgs& a, hipStream_t s, int* occ) {
-    if (w.KX == 64) launch_coopn_kx<64, HID>(w, a, s, occ);
-    else launch_coopn_kx<40, HID>(w, a, s, occ);
-}
-
-void launch_lstm_coopn(const LstmWeights& w, const LstmArgs& a, hipStream_t s) {
-    if (w.H == 256) { launch_coopn_h<256>(w, a, s, nullptr); return; }      // sb_model_hidden_size 256 / 512
-    if (w.H == 512) { launch_coopn_h<512>(w, a, s, nullptr); return; }
-    if (w.KX == 64) launch_coopn_kx<64>(w, a, s, nullptr);       // sub-band inputs of 41..64 features
-    else launch_coopn_kx<40>(w, a, s, nullptr);
-}
+void launch_lstm_coopn(const LstmWeights& w, const LstmArgs& a, hipStream_t s) { dispatch_lstm_coopn(w, a, s, nullptr); }
 int lstm_coopn_occupancy(const LstmWeights& w, int rows_per_group) {
     LstmArgs a{};
     a.coop_rows_per_group = rows_per_group;
     int occ = 0;
-    if (w.H == 256) launch_coopn_h<256>(w, a, nullptr, &occ);
-    else if (w.H == 512) launch_coopn_h<512>(w, a, nullptr, &occ);
-    else if (w.KX == 64) launch_coopn_kx<64>(w, a, nullptr, &occ);
-    else launch_coopn_kx<40>(w, a, nullptr, &occ);
+    dispatch_lstm_coopn(w, a, nullptr, &occ);
     return occ;
 }
 

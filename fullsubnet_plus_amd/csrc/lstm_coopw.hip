@@ -39,21 +39,11 @@
 // (tests/test_gpu_parity.py::test_wave_owned_column_split_kernel_vs_oracle), bitwise repeatable.
 #include "fsnp_common.h"
 #include "lstm_common.h"
+#include "lstm_launch.h"
 
 namespace fsnp {
 
 namespace {
-
-struct WStream {
-    __amdgpu_buffer_rsrc_t rsrc;
-    int voff;
-};
-__device__ __forceinline__ float4 wld(const WStream& s, int soff) {
-    return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(s.rsrc, s.voff, soff, 0));
-}
-__device__ __forceinline__ float4 wld_sc1(const WStream& s, int soff) {      // exchange images: bypass L1 (lstm_common.h)
-    return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(s.rsrc, s.voff, soff, kSc1));
-}
 
 template <int NT>
 __device__ __forceinline__ void w_mfma(f32x16 (&acc)[NT], const float4& a, const float4 (&b)[NT]) {
@@ -81,16 +71,16 @@ constexpr int kUb(int HID) { return HID / 8; }
 // under load - measured: the k-loops of the 32-unit kernel ran at 0.77-0.85 of their MFMA time).
 template <int NT> constexpr int coopw_depth() { return NT == 1 ? 8 : 4; }
 template <int NT, int HID, int D, typename ALoad>
-__device__ __forceinline__ void w_prefill(float4 (&a)[D], float4 (&b)[D][NT], const WStream& ws, int part, int wbase, ALoad aload) {
+__device__ __forceinline__ void w_prefill(float4 (&a)[D], float4 (&b)[D][NT], const BufStream& ws, int part, int wbase, ALoad aload) {
 #pragma unroll
     for (int k = 0; k < D; ++k) {
         a[k] = aload(k);
 #pragma unroll
-        for (int n = 0; n < NT; ++n) b[k][n] = wld(ws, ((wbase + k) * kUb(HID) + part * NT + n) * 1024);
+        for (int n = 0; n < NT; ++n) b[k][n] = stream_load(ws, ((wbase + k) * kUb(HID) + part * NT + n) * 1024);
     }
 }
 template <int NT, int HID, int D, int G, int NN, typename ALoad, typename NLoad, typename Hook>
-__device__ __forceinline__ void w_segment(f32x16 (&acc)[NT], float4 (&a)[D], float4 (&b)[D][NT], const WStream& ws, int part,
+__device__ __forceinline__ void w_segment(f32x16 (&acc)[NT], float4 (&a)[D], float4 (&b)[D][NT], const BufStream& ws, int part,
                                           int wbase, ALoad aload, int nwbase, NLoad nload, Hook pre_tail) {
     static_assert(G % D == 0 && G >= 2 * D && NN <= D, "pipeline shape");
     for (int g0 = 0; g0 < G - D; g0 += D) {
@@ -99,7 +89,7 @@ __device__ __forceinline__ void w_segment(f32x16 (&acc)[NT], float4 (&a)[D], flo
             w_mfma<NT>(acc, a[k], b[k]);
             a[k] = aload(g0 + k + D);
 #pragma unroll
-            for (int n = 0; n < NT; ++n) b[k][n] = wld(ws, ((wbase + g0 + k + D) * kUb(HID) + part * NT + n) * 1024);
+            for (int n = 0; n < NT; ++n) b[k][n] = stream_load(ws, ((wbase + g0 + k + D) * kUb(HID) + part * NT + n) * 1024);
             __builtin_amdgcn_sched_barrier(0);
         }
     }
@@ -111,7 +101,7 @@ __device__ __forceinline__ void w_segment(f32x16 (&acc)[NT], float4 (&a)[D], flo
             if (k < NN) {
                 a[k] = nload(k);
 #pragma unroll
-                for (int n = 0; n < NT; ++n) b[k][n] = wld(ws, ((nwbase + k) * kUb(HID) + part * NT + n) * 1024);
+                for (int n = 0; n < NT; ++n) b[k][n] = stream_load(ws, ((nwbase + k) * kUb(HID) + part * NT + n) * 1024);
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -166,10 +156,10 @@ __global__ __launch_bounds__(256) void lstm2_coopw_kernel(LstmWeights w, LstmArg
     float* fcp = reinterpret_cast<float*>(hx + 4 * HIMG);                                   // [2][P][2 outputs][32 rows]
     unsigned* bar0 = FSNP_COOP_BAR(a, rt, 0);
     unsigned* bar1 = FSNP_COOP_BAR(a, rt, 1);
-    WStream hs;
+    BufStream hs;
     hs.rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(hx), 0, coop_tile_f4(HID) * 16, 0x00020000);
     hs.voff = lane * 16;
-    WStream ws;
+    BufStream ws;
     ws.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(w.wpack_coopw), 0, (KG0 + 2 * KGH) * kUb(HID) * 1024, 0x00020000);
     ws.voff = lane * 16;
 
@@ -337,7 +327,7 @@ __global__ __launch_bounds__(256) void lstm2_coopw_kernel(LstmWeights w, LstmArg
         acc_init(acc, 0);
         const int hprev = h0off(pm3) * 16;
         // (the last D h0 groups refill the pipeline's WEIGHT slots with the first x k-groups; their A fragments are registers)
-        w_segment<NT, HID, D, KGH, NXN>(acc, pa, pb, ws, part, KGX, [&](int g) -> float4 { return wld_sc1(hs, hprev + g * 1024); },
+        w_segment<NT, HID, D, KGH, NXN>(acc, pa, pb, ws, part, KGX, [&](int g) -> float4 { return stream_load<kSc1>(hs, hprev + g * 1024); },
                                         0, [&](int g) -> float4 { return xfrag(g); }, [] {});
         FSNP_W_STAMP(t, 1);
         if (t > 0) x_commit(xm, xd);                     // x_t: fetched a whole phase pair ago (behind A_{t-1}'s x k-groups)
@@ -348,7 +338,7 @@ __global__ __launch_bounds__(256) void lstm2_coopw_kernel(LstmWeights w, LstmArg
             w_mfma<NT>(acc, xfrag(g), pb[g % D]);
             if (g + D < KGX) {
 #pragma unroll
-                for (int n = 0; n < NT; ++n) pb[g % D][n] = wld(ws, ((g + D) * kUb(HID) + part * NT + n) * 1024);
+                for (int n = 0; n < NT; ++n) pb[g % D][n] = stream_load(ws, ((g + D) * kUb(HID) + part * NT + n) * 1024);
             }
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -360,7 +350,7 @@ __global__ __launch_bounds__(256) void lstm2_coopw_kernel(LstmWeights w, LstmArg
         const int h1p = h1off(t & 1) * 16;                                                   // C_{t-1} starts on h1_{t-2} (parity t & 1)
         if (with_c) {
             if (!wait_for(bar1, (unsigned)P * (unsigned)(t - 1), early1)) return false;      // h1_{t-2}, Linear partials of step t - 2
-            w_prefill<NT, HID, D>(pa, pb, ws, part, KG0, [&](int g) -> float4 { return wld_sc1(hs, h1p + g * 1024); });
+            w_prefill<NT, HID, D>(pa, pb, ws, part, KG0, [&](int g) -> float4 { return stream_load<kSc1>(hs, h1p + g * 1024); });
             if (t >= 2) fc_issue(t - 2);
         }
         FSNP_W_STAMP(t, 3);
@@ -389,17 +379,17 @@ __global__ __launch_bounds__(256) void lstm2_coopw_kernel(LstmWeights w, LstmArg
         f32x16 acc[NT];
         acc_init(acc, 1);
         const int h1p = h1off(prv) * 16, h0c = h0off(m3) * 16;
-        w_segment<NT, HID, D, KGH, D>(acc, pa, pb, ws, part, KG0, [&](int g) -> float4 { return wld_sc1(hs, h1p + g * 1024); },
-                                      KG0 + KGH, [&](int g) -> float4 { return wld_sc1(hs, h0c + g * 1024); }, [] {});
+        w_segment<NT, HID, D, KGH, D>(acc, pa, pb, ws, part, KG0, [&](int g) -> float4 { return stream_load<kSc1>(hs, h1p + g * 1024); },
+                                      KG0 + KGH, [&](int g) -> float4 { return stream_load<kSc1>(hs, h0c + g * 1024); }, [] {});
         FSNP_W_STAMP(t + 1, 9);
         // (the b0 poll for the A phase behind this one is issued in front of the last D k-groups and looked at behind them)
-        w_segment<NT, HID, D, KGH, 0>(acc, pa, pb, ws, part, KG0 + KGH, [&](int g) -> float4 { return wld_sc1(hs, h0c + g * 1024); },
+        w_segment<NT, HID, D, KGH, 0>(acc, pa, pb, ws, part, KG0 + KGH, [&](int g) -> float4 { return stream_load<kSc1>(hs, h0c + g * 1024); },
                                       0, [&](int) -> float4 { return make_float4(0.f, 0.f, 0.f, 0.f); }, [&] { if (next_a) early0 = poll(bar0); });
         FSNP_W_STAMP(t + 1, 10);
         const int hn = h0off(nm3) * 16;
         if (next_a) {
             if (!wait_for(bar0, (unsigned)P * (unsigned)(t + 2), early0)) return false;       // h0_{t+1} published by every participant
-            w_prefill<NT, HID, D>(pa, pb, ws, part, KGX, [&](int g) -> float4 { return wld_sc1(hs, hn + g * 1024); });
+            w_prefill<NT, HID, D>(pa, pb, ws, part, KGX, [&](int g) -> float4 { return stream_load<kSc1>(hs, hn + g * 1024); });
         }
         FSNP_W_STAMP(t + 1, 11);
         const int himg = h1off(cur);
@@ -424,13 +414,13 @@ __global__ __launch_bounds__(256) void lstm2_coopw_kernel(LstmWeights w, LstmArg
     // ---- A_0 (h0_{-1} = the zeroed third image), then [A_t, C_{t-1}] for t = 1 .. Tp - 1, then C_{Tp-1}
     {
         const int hz = h0off(2) * 16;
-        w_prefill<NT, HID, D>(pa, pb, ws, part, KGX, [&](int g) -> float4 { return wld_sc1(hs, hz + g * 1024); });
+        w_prefill<NT, HID, D>(pa, pb, ws, part, KGX, [&](int g) -> float4 { return stream_load<kSc1>(hs, hz + g * 1024); });
     }
     if (Tp == 1) {
         // (one step only: A_0 -> C_0 with blocking waits)
         if (!phase_a(0, 0, 2, false)) return;
         if (!wait_for(bar0, (unsigned)P, 0u)) return;
-        w_prefill<NT, HID, D>(pa, pb, ws, part, KG0, [&](int g) -> float4 { return wld_sc1(hs, h1off(1) * 16 + g * 1024); });
+        w_prefill<NT, HID, D>(pa, pb, ws, part, KG0, [&](int g) -> float4 { return stream_load<kSc1>(hs, h1off(1) * 16 + g * 1024); });
         if (!phase_c(0, 0, false, 0)) return;
         if (!wait_for(bar1, (unsigned)P, 0u)) return;
         fc_issue(0); fc_finish(0);
@@ -439,7 +429,7 @@ __global__ __launch_bounds__(256) void lstm2_coopw_kernel(LstmWeights w, LstmArg
     if (!phase_a(0, 0, 2, false)) return;
     // A_1 needs h0_0 of every participant; its pipeline is filled here (no C phase in between yet)
     if (!wait_for(bar0, (unsigned)P, 0u)) return;
-    w_prefill<NT, HID, D>(pa, pb, ws, part, KGX, [&](int g) -> float4 { return wld_sc1(hs, h0off(0) * 16 + g * 1024); });
+    w_prefill<NT, HID, D>(pa, pb, ws, part, KGX, [&](int g) -> float4 { return stream_load<kSc1>(hs, h0off(0) * 16 + g * 1024); });
     int m3 = 1, pm3 = 0;                                // t % 3, (t - 1) % 3 for t = 1
     for (int t = 1; t < Tp; ++t) {
         if (!phase_a(t, m3, pm3, true)) return;         // (waits for b1 >= P (t - 1) inside, prefills C_{t-1}, Linear of step t - 2)
@@ -452,7 +442,7 @@ __global__ __launch_bounds__(256) void lstm2_coopw_kernel(LstmWeights w, LstmArg
     if (!wait_for(bar0, (unsigned)P * (unsigned)Tp, 0u)) return;
     if (!wait_for(bar1, (unsigned)P * (unsigned)(Tp - 1), 0u)) return;
     fc_issue(Tp - 2); fc_finish(Tp - 2);
-    w_prefill<NT, HID, D>(pa, pb, ws, part, KG0, [&](int g) -> float4 { return wld_sc1(hs, h1off(Tp & 1) * 16 + g * 1024); });
+    w_prefill<NT, HID, D>(pa, pb, ws, part, KG0, [&](int g) -> float4 { return stream_load<kSc1>(hs, h1off(Tp & 1) * 16 + g * 1024); });
     if (!phase_c(Tp - 1, pm3, false, 0)) return;
     if (!wait_for(bar1, (unsigned)P * (unsigned)Tp, 0u)) return;
     fc_issue(Tp - 1); fc_finish(Tp - 1);
@@ -465,43 +455,15 @@ __global__ __launch_bounds__(256) void lstm2_coopw_kernel(LstmWeights w, LstmArg
 // [k-group g (layer 0: x | h0, then layer 1: h1 | h0)][8-unit block ub][lane][k-pair p]: the B operand of MFMA p of k-group g for
 // column c = lane & 31 of block ub is W[gate (c & 3)][unit 8 ub + (c >> 2)][k = 8 g' + 2 p + (lane >> 5)]
 
-bool lstm_coopw_available(const LstmWeights& w, int units) {
-    return !w.gru && w.H == 384 && (w.KX == 40 || w.KX == 64) && (units == 32 || units == 64 || units == 96) && w.wpack_coopw != nullptr;
-}
-
-template <int HID, int KX, int NT>
-static void launch_coopw_inst(const LstmWeights& w, const LstmArgs& a, hipStream_t s, int* occ) {
-    constexpr int S = HID / (32 * NT);
-    const size_t smem_need = coopw_smem_bytes(NT, KX);
-    auto kern = lstm2_coopw_kernel<HID, KX, NT>;
-    static PerDeviceOnce attr_once;
-    attr_once.run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256); });
-    if (occ) {
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, reinterpret_cast<const void*>(kern), 256, smem_need) != hipSuccess) *occ = 0;
-        return;
-    }
-    const size_t smem = a.coop_own_cu > 0 && (size_t)a.coop_own_cu > smem_need ? (size_t)a.coop_own_cu : smem_need;
-    const int grid = a.coop_xcd ? 8 * xcd_local_blocks_per_xcd(S, a.num_tiles, a.coop_xcd) : a.num_tiles * S;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, s, w, a);
-}
-
-template <int KX>
-static void launch_coopw_kx(const LstmWeights& w, const LstmArgs& a, hipStream_t s, int* occ) {
-    if (a.coop_units == 32) launch_coopw_inst<384, KX, 1>(w, a, s, occ);
-    else if (a.coop_units == 96) launch_coopw_inst<384, KX, 3>(w, a, s, occ);
-    else launch_coopw_inst<384, KX, 2>(w, a, s, occ);
-}
-
-// a.num_tiles row tiles x H / a.coop_units workgroups (a.coop_units = 32 or 64 hidden units per workgroup), all co-resident
+// a.num_tiles row tiles x H / a.coop_units workgroups (a.coop_units = 32 NT: 32, 96 or the default 64 hidden units per workgroup), all
+// co-resident; H = 384, K = 64 or the default 40
 void launch_lstm_coopw(const LstmWeights& w, const LstmArgs& a, hipStream_t s) {
-    if (w.KX == 64) launch_coopw_kx<64>(w, a, s, nullptr); else launch_coopw_kx<40>(w, a, s, nullptr);
-}
-int lstm_coopw_occupancy(const LstmWeights& w, int units) {
-    LstmArgs a{};
-    a.coop_units = units;
-    int occ = 0;
-    if (w.KX == 64) launch_coopw_kx<64>(w, a, nullptr, &occ); else launch_coopw_kx<40>(w, a, nullptr, &occ);
-    return occ;
+    dispatch_int<64, 40>(w.KX, [&](auto KX) {
+        dispatch_int<32, 96, 64>(a.coop_units, [&](auto U) {
+            constexpr int NT = decltype(U)::value / 32;
+            launch_column_split<lstm2_coopw_kernel<384, decltype(KX)::value, NT>>(w, a, s, 384 / (32 * NT), a.num_tiles, coopw_smem_bytes(NT, decltype(KX)::value), nullptr);
+        });
+    });
 }
 
 }  // namespace fsnp

@@ -16,13 +16,11 @@
 // results meet the same oracle tolerance (tests/test_gpu_parity.py::test_generic_recurrent_kernel_*).
 #include "fsnp_common.h"
 #include "lstm_common.h"
+#include "lstm_launch.h"
 
 namespace fsnp {
 
 namespace {
-
-__device__ __forceinline__ float gen_sigmoid(float x) { return 1.0f / (1.0f + __expf(-x)); }
-__device__ __forceinline__ float gen_tanh(float x) { return 2.0f / (1.0f + __expf(-2.0f * x)) - 1.0f; }
 
 constexpr int gen_pad4(int v) { return (v + 3) / 4 * 4; }
 // dynamic LDS in floats: x [RG][NINP], h0, h1, c0, c1 [RG][HP], pre [RG][4 HP]
@@ -134,14 +132,14 @@ __device__ __forceinline__ void lstm2_generic_body(const LstmWeights& w, const L
             const float* p = pre + r * 4 * HP;
             float hv;
             if (gru) {           // r = s(a_r), z = s(a_z), n = tanh(a_nx + r a_nh), h' = (1 - z) n + z h      (torch.nn.GRU)
-                const float rg = gen_sigmoid(p[u]), zg = gen_sigmoid(p[H + u]);
-                const float ng = gen_tanh(p[2 * H + u] + rg * p[3 * H + u]);
+                const float rg = exact_sigmoid(p[u]), zg = exact_sigmoid(p[H + u]);
+                const float ng = exact_tanh(p[2 * H + u] + rg * p[3 * H + u]);
                 hv = ng + zg * (h[r * HP + u] - ng);
             } else {
-                const float ig = gen_sigmoid(p[u]), fg = gen_sigmoid(p[H + u]), gg = gen_tanh(p[2 * H + u]), og = gen_sigmoid(p[3 * H + u]);
+                const float ig = exact_sigmoid(p[u]), fg = exact_sigmoid(p[H + u]), gg = exact_tanh(p[2 * H + u]), og = exact_sigmoid(p[3 * H + u]);
                 const float cn = fg * c[r * HP + u] + ig * gg;
                 c[r * HP + u] = cn;
-                hv = og * gen_tanh(cn);
+                hv = og * exact_tanh(cn);
             }
             h[r * HP + u] = hv;      // (its readers - this layer's accumulate - finished before the barrier above)
         }
@@ -225,53 +223,22 @@ int lstm_generic_rows_per_group(int H, int NIN, int num_seq, int num_cus) {
     return gen_smem_floats(rg, H, NIN) * 4 <= (size_t)150 * 1024 ? rg : 0;
 }
 
-// LDS opt-in of one instantiation (per device) + a residency check: 1024 threads with `smem` bytes of dynamic LDS must fit a CU.
-// Returns hipSuccess, or the error of the attribute call / hipErrorLaunchOutOfResources when no workgroup fits.
+// LDS opt-in of one instantiation + residency check with `smem` bytes of dynamic LDS (0: opt-in only): lds_opt_in, lstm_launch.h
+constexpr int kGenMaxDyn = 152 * 1024;
 template <int RG, bool SEQ>
-static hipError_t generic_prepare(size_t smem) {
-    auto k = lstm2_generic_kernel<RG, SEQ>;
-    static PerDeviceOnce once;
-    static hipError_t attr_err[64] = {};                       // per device: a failure on one GPU is that GPU's alone
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const int di = dev >= 0 && dev < 64 ? dev : 0;
-    once.run([&] { attr_err[di] = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024); });
-    if (attr_err[di] != hipSuccess) return attr_err[di];
-    if (smem == 0) return hipSuccess;
-    int blocks = 0;
-    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, reinterpret_cast<const void*>(k), kGenThreads, smem);
-    if (e != hipSuccess) return e;
-    return blocks >= 1 ? hipSuccess : hipErrorLaunchOutOfResources;
-}
-
+static hipError_t generic_prepare(size_t smem) { return lds_opt_in<lstm2_generic_kernel<RG, SEQ>>(kGenMaxDyn, kGenThreads, smem); }
 template <int RG>
-static void launch_generic_rg(const LstmWeights& w, const LstmArgs& a, bool seq, hipStream_t s) {
-    const size_t smem = gen_smem_floats(RG, w.H, w.NIN) * 4;
-    // (a failed LDS opt-in makes the launch itself fail: forward_impl's hipGetLastError reports it - never a silent no-op)
-    if (seq) {
-        if (generic_prepare<RG, true>(0) != hipSuccess) set_error("lstm_generic: LDS opt-in of the runtime-sized kernel failed on this device");
-        hipLaunchKernelGGL((lstm2_generic_kernel<RG, true>), dim3(a.num_tiles), dim3(kGenThreads), smem, s, w, a);
-    } else {
-        if (generic_prepare<RG, false>(0) != hipSuccess) set_error("lstm_generic: LDS opt-in of the runtime-sized kernel failed on this device");
-        hipLaunchKernelGGL((lstm2_generic_kernel<RG, false>), dim3(a.num_tiles), dim3(kGenThreads), smem, s, w, a);
-    }
-}
+static hipError_t generic_stream_prepare(size_t smem) { return lds_opt_in<lstm2_generic_stream_kernel<RG>>(kGenMaxDyn, kGenThreads, smem); }
 
 // Commit-time check (fsnp_commit_weights): every instantiation a plan may launch for these sizes gets its LDS opt-in and must be
 // resident with its real LDS size; a failure is reported THERE with a clear message instead of surfacing as an asynchronous launch error.
 int lstm_generic_check(int H, int NIN, bool seq) {
     hipError_t e = hipSuccess;
-    auto one = [&](int rg) -> hipError_t {
+    for (int rg = 1; rg <= 8 && e == hipSuccess; rg *= 2) {
         const size_t smem = gen_smem_floats(rg, H, NIN) * 4;
-        if (smem > (size_t)150 * 1024) return hipSuccess;           // never planned (lstm_generic_rows_per_group)
-        switch (rg) {
-            case 8: return seq ? generic_prepare<8, true>(smem) : generic_prepare<8, false>(smem);
-            case 4: return seq ? generic_prepare<4, true>(smem) : generic_prepare<4, false>(smem);
-            case 2: return seq ? generic_prepare<2, true>(smem) : generic_prepare<2, false>(smem);
-            default: return seq ? generic_prepare<1, true>(smem) : generic_prepare<1, false>(smem);
-        }
-    };
-    for (int rg = 1; rg <= 8 && e == hipSuccess; rg *= 2) e = one(rg);
+        if (smem > (size_t)150 * 1024) continue;           // never planned (lstm_generic_rows_per_group)
+        dispatch_int<8, 4, 2, 1>(rg, [&](auto RG) { dispatch_bool(seq, [&](auto SEQ) { e = generic_prepare<decltype(RG)::value, decltype(SEQ)::value>(smem); }); });
+    }
     if (e != hipSuccess) {
         set_error("runtime-sized recurrent kernel (hidden %d, %d inputs): a 1024-thread workgroup with its LDS does not fit a CU of this device: %s",
                   H, NIN, hipGetErrorString(e));
@@ -280,31 +247,13 @@ int lstm_generic_check(int H, int NIN, bool seq) {
     return 0;
 }
 
-template <int RG>
-static hipError_t generic_stream_prepare(size_t smem) {
-    auto k = lstm2_generic_stream_kernel<RG>;
-    static PerDeviceOnce once;
-    static hipError_t attr_err[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const int di = dev >= 0 && dev < 64 ? dev : 0;
-    once.run([&] { attr_err[di] = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024); });
-    if (attr_err[di] != hipSuccess) return attr_err[di];
-    if (smem == 0) return hipSuccess;
-    int blocks = 0;
-    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, reinterpret_cast<const void*>(k), kGenThreads, smem);
-    if (e != hipSuccess) return e;
-    return blocks >= 1 ? hipSuccess : hipErrorLaunchOutOfResources;
-}
-
 // session-creation check of the streaming instantiations (as lstm_generic_check at commit)
 int lstm_generic_stream_check(int H, int NIN) {
     hipError_t e = hipSuccess;
     for (int rg = 1; rg <= 8 && e == hipSuccess; rg *= 2) {
         const size_t smem = gen_smem_floats(rg, H, NIN) * 4;
         if (smem > (size_t)150 * 1024) continue;
-        e = rg == 8 ? generic_stream_prepare<8>(smem) : rg == 4 ? generic_stream_prepare<4>(smem) : rg == 2 ? generic_stream_prepare<2>(smem)
-                                                                                                          : generic_stream_prepare<1>(smem);
+        dispatch_int<8, 4, 2, 1>(rg, [&](auto RG) { e = generic_stream_prepare<decltype(RG)::value>(smem); });
     }
     if (e != hipSuccess) {
         set_error("streaming full-band kernel (hidden %d, %d inputs): a 1024-thread workgroup with its LDS does not fit a CU of this device: %s",
@@ -314,30 +263,25 @@ int lstm_generic_stream_check(int H, int NIN) {
     return 0;
 }
 
-template <int RG>
-static void launch_generic_stream_rg(const LstmWeights& w, const LstmArgs& a, hipStream_t s) {
-    if (generic_stream_prepare<RG>(0) != hipSuccess) set_error("lstm_generic: LDS opt-in of the streaming kernel failed on this device");
-    hipLaunchKernelGGL((lstm2_generic_stream_kernel<RG>), dim3(a.num_tiles), dim3(kGenThreads), gen_smem_floats(RG, w.H, w.NIN) * 4, s, w, a);
-}
-
 void launch_lstm_generic_stream(const LstmWeights& w, const LstmArgs& a, hipStream_t s) {
     if (a.num_tiles <= 0) return;
-    switch (a.coop_rows_per_group) {
-        case 8: launch_generic_stream_rg<8>(w, a, s); break;
-        case 4: launch_generic_stream_rg<4>(w, a, s); break;
-        case 2: launch_generic_stream_rg<2>(w, a, s); break;
-        default: launch_generic_stream_rg<1>(w, a, s); break;
-    }
+    dispatch_int<8, 4, 2, 1>(a.coop_rows_per_group, [&](auto R) {
+        constexpr int RG = decltype(R)::value;
+        if (generic_stream_prepare<RG>(0) != hipSuccess) set_error("lstm_generic: LDS opt-in of the streaming kernel failed on this device");
+        hipLaunchKernelGGL((lstm2_generic_stream_kernel<RG>), dim3(a.num_tiles), dim3(kGenThreads), gen_smem_floats(RG, w.H, w.NIN) * 4, s, w, a);
+    });
 }
 
 // a.num_tiles workgroups of a.coop_rows_per_group (1, 2, 4 or 8) sequences each; a.rows holds num_tiles * rows-per-group slots
 void launch_lstm_generic(const LstmWeights& w, const LstmArgs& a, bool seq, hipStream_t s) {
-    switch (a.coop_rows_per_group) {
-        case 8: launch_generic_rg<8>(w, a, seq, s); break;
-        case 4: launch_generic_rg<4>(w, a, seq, s); break;
-        case 2: launch_generic_rg<2>(w, a, seq, s); break;
-        default: launch_generic_rg<1>(w, a, seq, s); break;
-    }
+    dispatch_int<8, 4, 2, 1>(a.coop_rows_per_group, [&](auto R) {
+        dispatch_bool(seq, [&](auto SEQ) {
+            constexpr int RG = decltype(R)::value;
+            // (a failed LDS opt-in makes the launch itself fail: forward_impl's hipGetLastError reports it - never a silent no-op)
+            if (generic_prepare<RG, decltype(SEQ)::value>(0) != hipSuccess) set_error("lstm_generic: LDS opt-in of the runtime-sized kernel failed on this device");
+            hipLaunchKernelGGL((lstm2_generic_kernel<RG, decltype(SEQ)::value>), dim3(a.num_tiles), dim3(kGenThreads), gen_smem_floats(RG, w.H, w.NIN) * 4, s, w, a);
+        });
+    });
 }
 
 }  // namespace fsnp

@@ -21,22 +21,12 @@ namespace fsnp {
 
 namespace {
 
-struct GStream {
-    __amdgpu_buffer_rsrc_t rsrc;
-    int voff;
-};
-// one 1 KiB weight fragment (tile n of k-group g, NL live tiles per group) of this wave's stream
-template <int NL>
-__device__ __forceinline__ float4 gload(const GStream& ws, int g, int n) {
-    return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(ws.rsrc, ws.voff, (g * NL + n) * 1024, 0));
-}
-
 // `ngroups` k-groups of one K segment.  HID_PART = false: the segment is the layer's INPUT (live tiles r, z, n_x =
 // accumulators [0, 3 ST)); true: its own previous h (r, z, n_h = accumulators [0, 2 ST) and [3 ST, 4 ST)).  b always holds
 // the group about to be used and is refilled in place from the stream (same pipeline as lstm.hip: mfma_groups).
 template <int ST, bool HID_PART>
 __device__ __forceinline__ void gru_groups(f32x16 (&acc)[4 * ST], float4 (&b)[3 * ST], const float4* __restrict__ A, int ngroups,
-                                           const GStream& ws, int& gnext, int groups_total) {
+                                           const BufStream& ws, int& gnext, int groups_total) {
     constexpr int NL = 3 * ST;
     float4 a = A[0];
     for (int g = 0; g < ngroups; ++g) {
@@ -48,7 +38,7 @@ __device__ __forceinline__ void gru_groups(f32x16 (&acc)[4 * ST], float4 (&b)[3 
             acc[ai] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b[n].y, acc[ai], 0, 0, 0);
             acc[ai] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b[n].z, acc[ai], 0, 0, 0);
             acc[ai] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b[n].w, acc[ai], 0, 0, 0);
-            b[n] = gload<NL>(ws, gnext, n);
+            b[n] = wload<NL>(ws, gnext, n);
             __builtin_amdgcn_sched_barrier(0);
         }
         gnext = (gnext + 1 == groups_total) ? 0 : gnext + 1;
@@ -162,12 +152,12 @@ void gru2_fc_kernel(LstmWeights w, LstmArgs a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) { h0r[s][r] = 0.0f; h1r[s][r] = 0.0f; }
 
-    GStream ws;
+    BufStream ws;
     ws.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(w.wpack) + (size_t)wave * KGT * NL * 256, 0, KGT * NL * 1024, 0x00020000);
     ws.voff = lane * 16;
     float4 breg[NL];
 #pragma unroll
-    for (int n = 0; n < NL; ++n) breg[n] = gload<NL>(ws, 0, n);
+    for (int n = 0; n < NL; ++n) breg[n] = wload<NL>(ws, 0, n);
     int gnext = 1;
 
     // Linear: 8 rows x 2 outputs x 4 k-parts per wave (waves 0..3)

@@ -44,6 +44,7 @@
 
 #include "fsnp_common.h"
 #include "lstm_common.h"
+#include "lstm_launch.h"
 
 namespace fsnp {
 
@@ -51,11 +52,6 @@ namespace {
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 using lds_ptr = __attribute__((address_space(3))) void*;
-
-template <typename F, int... I>
-__device__ __forceinline__ void hp_static_for_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, typename F>
-__device__ __forceinline__ void hp_static_for(F&& f) { hp_static_for_impl(f, std::make_integer_sequence<int, N>{}); }
 
 // float index of A element (row < 16, k) inside a half-tile image: [k-group of 16][k & 3][row][(k >> 2) & 3] - lane l of a
 // k-group reads the float4 at (l >> 4 = k & 3, l & 15 = row); component j feeds the group's MFMA j (k = 16 g + 4 j + (l >> 4))
@@ -65,11 +61,6 @@ constexpr int hp_gx(int KX) { return (KX + 15) / 16; }
 constexpr size_t hp_smem_bytes(int HID, int KX) {
     return (size_t)(2 * hp_gx(KX) * 64 + 4 * (HID / 16) * 64 + 8 * 64 + 2 * 64 + 8) * 16 + 2 * (HID / 16) * 4 + 32 * sizeof(RowDesc) + 64;
 }
-
-// sum over the 16 lanes of a DPP row, in every lane (row_ror 8, 4, 2, 1: no LDS round trips)
-template <int N>
-__device__ __forceinline__ float hp_ror(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x120 + N, 0xf, 0xf, false)); }
-__device__ __forceinline__ float row_sum16(float v) { v += hp_ror<8>(v); v += hp_ror<4>(v); v += hp_ror<2>(v); v += hp_ror<1>(v); return v; }
 
 #define HP_MF(acc, av, bv) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc, 0, 0, 0)
 
@@ -302,7 +293,7 @@ void lstm2_coop_hp_kernel(LstmWeights w, LstmArgs a) {
     if (wave != 0 || fc_wg) { if (wave_wait(bars[0], (unsigned)S)) fetch(std::integral_constant<int, 0>{}, 0); }
 
     for (int t = 0; t < Tp && !dead; ++t) {
-        hp_static_for<2>([&](auto HC) {
+        static_for<2>([&](auto HC) {
             constexpr int hf = decltype(HC)::value;
             constexpr int ho = hf ^ 1;
             if (hf >= nh || dead) return;
@@ -468,28 +459,14 @@ void lstm2_coop_hp_kernel(LstmWeights w, LstmArgs a) {
 // [column slice cs][gate][fragment: x k-groups | W_hh0 | W_hh1 | W_ih1][lane][4]: the B operand of MFMA j of a k-group is
 // W[gate * H + cs * 16 + (lane & 15)][k = 16 g + 4 j + (lane >> 4)]
 
-template <int HID, int KX>
-static void launch_hp_inst(const LstmWeights& w, const LstmArgs& a, hipStream_t s, int* occ) {
-    constexpr int S = HID / 16;
-    const size_t smem_need = hp_smem_bytes(HID, KX);
-    auto kern = lstm2_coop_hp_kernel<HID, KX>;
-    static PerDeviceOnce attr_once;
-    attr_once.run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256); });
-    if (occ) {
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, reinterpret_cast<const void*>(kern), 256, smem_need) != hipSuccess) *occ = 0;
-        return;
-    }
-    const size_t smem = a.coop_own_cu > 0 && (size_t)a.coop_own_cu > smem_need ? (size_t)a.coop_own_cu : smem_need;
-    const int grid = a.coop_xcd ? 8 * xcd_local_blocks_per_xcd(S, a.num_tiles, a.coop_xcd) : a.num_tiles * S;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, s, w, a);
-}
-
-bool lstm_hp_available(const LstmWeights& w) { return !w.gru && (w.H == 384 || w.H == 256) && (w.KX == 40 || w.KX == 64); }
-
-// a.num_tiles row tiles x H / 16 workgroups, all co-resident
+// a.num_tiles row tiles x H / 16 workgroups, all co-resident; H = 256 or the default 384, K = 64 or the default 40
 void launch_lstm_hp(const LstmWeights& w, const LstmArgs& a, hipStream_t s) {
-    if (w.H == 256) { if (w.KX == 64) launch_hp_inst<256, 64>(w, a, s, nullptr); else launch_hp_inst<256, 40>(w, a, s, nullptr); return; }
-    if (w.KX == 64) launch_hp_inst<384, 64>(w, a, s, nullptr); else launch_hp_inst<384, 40>(w, a, s, nullptr);
+    dispatch_int<256, 384>(w.H, [&](auto H) {
+        dispatch_int<64, 40>(w.KX, [&](auto KX) {
+            constexpr int HID = decltype(H)::value, K = decltype(KX)::value;
+            launch_column_split<lstm2_coop_hp_kernel<HID, K>>(w, a, s, HID / 16, a.num_tiles, hp_smem_bytes(HID, K), nullptr);
+        });
+    });
 }
 
 }  // namespace fsnp

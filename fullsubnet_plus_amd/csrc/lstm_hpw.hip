@@ -36,6 +36,7 @@
 
 #include "fsnp_common.h"
 #include "lstm_common.h"
+#include "lstm_launch.h"
 
 namespace fsnp {
 
@@ -43,20 +44,13 @@ namespace {
 
 using f32x4w = __attribute__((ext_vector_type(4))) float;
 
-template <typename F, int... I>
-__device__ __forceinline__ void hpw_static_for_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, typename F>
-__device__ __forceinline__ void hpw_static_for(F&& f) { hpw_static_for_impl(f, std::make_integer_sequence<int, N>{}); }
-
 constexpr int hpw_gx(int KX) { return (KX + 15) / 16; }
 // per wave: gather offsets [2 halves][KX / 4][64] + the lanes' bias quadruples [2 layers][64] float4; + the row descriptors
 constexpr size_t hpw_smem_bytes(int KX) { return (size_t)4 * (2 * (KX / 4) * 64 * 4 + 2 * 64 * 16) + 32 * sizeof(RowDesc); }
 
-template <int N>
-__device__ __forceinline__ float hpw_ror(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x120 + N, 0xf, 0xf, false)); }
 // sum over the 64 lanes of a wave in a fixed order, in every lane
 __device__ __forceinline__ float hpw_wave_sum(float v) {
-    v += hpw_ror<8>(v); v += hpw_ror<4>(v); v += hpw_ror<2>(v); v += hpw_ror<1>(v);
+    v = row_sum16(v);
     v += __shfl_xor(v, 16); v += __shfl_xor(v, 32);
     return v;
 }
@@ -178,7 +172,7 @@ void lstm2_coop_hpw_kernel(LstmWeights w, LstmArgs a) {
         __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(a.coop_hx) + (size_t)rt * (TILE_BYTES / 4), 0, TILE_BYTES, 0x00020000);
     unsigned* const bars[2] = {FSNP_COOP_BAR(a, rt, 0), FSNP_COOP_BAR(a, rt, 1)};     // one 128-byte line each
     const int hst = part * 256 + seq * 16 + kq * 4;  // byte offset of the lane's cell inside a half image (hp_a16(seq, unit))
-    auto hload = [&](int soff) -> float4 { return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(hr, lane * 16, soff, kSc1)); };
+    auto hload = [&](int soff) -> float4 { return stream_load<kSc1>(BufStream{hr, lane * 16}, soff); };
     auto hstore = [&](float v, int soff) { __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), hr, hst, soff, kSc1); };
 
     auto x_fetch = [&](auto HF, int t) {
@@ -244,7 +238,7 @@ void lstm2_coop_hpw_kernel(LstmWeights w, LstmArgs a) {
     auto chaos = [&](int t, int phase) { chaos_delay(a.coop_chaos ? a.coop_chaos + 7919 * wave : 0, t, phase); };
 
     // ================= phase -1 of every half: h0_0 = cell(W_ih0 x_0) -> h0img[0] =================
-    hpw_static_for<2>([&](auto HC) {
+    static_for<2>([&](auto HC) {
         constexpr int hf = decltype(HC)::value;
         if (hf >= nh) return;
         x_fetch(HC, 0);
@@ -346,20 +340,20 @@ void lstm2_coop_hpw_kernel(LstmWeights w, LstmArgs a) {
             if constexpr (two && g == GH - D - POLL_AHEAD) seen = __hip_atomic_load(nbar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __builtin_amdgcn_sched_barrier(0);
         };
-        hpw_static_for<GH - D>([&](auto G) { group(G, std::false_type{}); });
+        static_for<GH - D>([&](auto G) { group(G, std::false_type{}); });
         bool early = true;
         if constexpr (two) {
             early = !has_next || (unsigned)__builtin_amdgcn_readfirstlane((int)seen) >= ntarget;
             if (early) {
-                hpw_static_for<D>([&](auto K) { group(std::integral_constant<int, GH - D + decltype(K)::value>{}, std::true_type{}); });
+                static_for<D>([&](auto K) { group(std::integral_constant<int, GH - D + decltype(K)::value>{}, std::true_type{}); });
             } else {                       // not complete yet (drift): finish the pass, wait for real, fetch behind it
-                hpw_static_for<D>([&](auto K) { group(std::integral_constant<int, GH - D + decltype(K)::value>{}, std::false_type{}); });
+                static_for<D>([&](auto K) { group(std::integral_constant<int, GH - D + decltype(K)::value>{}, std::false_type{}); });
                 wave_wait(nbar, ntarget);
                 prefill(ho, ntc);
             }
             if (has_next && nt >= 1) fc_issue(ho, nt - 1);      // (the arrivals that completed the counter also published the partials of step nt - 1)
         } else {
-            hpw_static_for<D>([&](auto K) { group(std::integral_constant<int, GH - D + decltype(K)::value>{}, std::false_type{}); });
+            static_for<D>([&](auto K) { group(std::integral_constant<int, GH - D + decltype(K)::value>{}, std::false_type{}); });
         }
         FSNP_HPW_STAMP(4);
         FSNP_HPW_STAMP(5);
@@ -433,22 +427,13 @@ void lstm2_coop_hpw_kernel(LstmWeights w, LstmArgs a) {
 
 template <int HID, int KX>
 static void launch_hpw_inst(const LstmWeights& w, const LstmArgs& a, hipStream_t s) {
-    constexpr int S = HID / 16;
-    const size_t smem_need = hpw_smem_bytes(KX);
-    const size_t smem = a.coop_own_cu > 0 && (size_t)a.coop_own_cu > smem_need ? (size_t)a.coop_own_cu : smem_need;
-    const int grid = a.coop_xcd ? 8 * xcd_local_blocks_per_xcd(S, a.num_tiles, a.coop_xcd) : a.num_tiles * S;
     if constexpr (HID == 384 && KX == 40) {          // the phase-profile variant exists for the default sizes only
         if (a.prof != nullptr) {
-            auto kp = lstm2_coop_hpw_kernel<HID, KX, true>;
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kp), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
-            hipLaunchKernelGGL(kp, dim3(grid), dim3(256), smem, s, w, a);
+            launch_column_split<lstm2_coop_hpw_kernel<HID, KX, true>, false, true>(w, a, s, HID / 16, a.num_tiles, hpw_smem_bytes(KX), nullptr);
             return;
         }
     }
-    auto kern = lstm2_coop_hpw_kernel<HID, KX, false>;
-    static PerDeviceOnce attr_once;
-    attr_once.run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256); });
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, s, w, a);
+    launch_column_split<lstm2_coop_hpw_kernel<HID, KX, false>>(w, a, s, HID / 16, a.num_tiles, hpw_smem_bytes(KX), nullptr);
 }
 
 // (H = 384 with 41 ... 64 input features - fb_num_neighbors >= 2 - stays on lstm_hp.hip: 16 x fragments per lane next to the 300 weight

@@ -23,6 +23,7 @@
 // rows[].valid is the row's step count of this push: at step t a row with valid <= t keeps its state and writes nothing.
 #include "fsnp_common.h"
 #include "lstm_common.h"
+#include "lstm_launch.h"
 
 namespace fsnp {
 
@@ -30,9 +31,6 @@ namespace {
 
 constexpr int kStepKgxp = 8;           // x k-groups of the 16-unit K-split image: KX = 40 and 64 both pad to 8 groups (64 columns)
 constexpr int kPartLd = 17;            // floats per lane of a partial tile in LDS (16 + 1: lane-strided stores without bank conflicts)
-
-__device__ __forceinline__ float step_sigmoid(float x) { return 1.0f / (1.0f + __expf(-x)); }
-__device__ __forceinline__ float step_tanh(float x) { return 2.0f / (1.0f + __expf(-2.0f * x)) - 1.0f; }
 
 }  // namespace
 
@@ -286,8 +284,8 @@ __global__ __launch_bounds__(kFbThreads) void live_fb_step_kernel(LstmWeights w,
         g4[g] = s + w.bias[LAYER * G4 + g * H + cu];
     }
     float* __restrict__ rec = a.st + (size_t)rd.b * a.st_stride + LAYER * 2 * H + cu;
-    const float cn = step_sigmoid(g4[1]) * rec[H] + step_sigmoid(g4[0]) * step_tanh(g4[2]);
-    const float hv = step_sigmoid(g4[3]) * step_tanh(cn);
+    const float cn = exact_sigmoid(g4[1]) * rec[H] + exact_sigmoid(g4[0]) * exact_tanh(g4[2]);
+    const float hv = exact_sigmoid(g4[3]) * exact_tanh(cn);
     rec[H] = cn;
     rec[0] = hv;
     (LAYER ? a.h1[par ^ 1] : a.h0[par ^ 1])[(size_t)rd.b * H + cu] = hv;
@@ -302,22 +300,9 @@ bool live_sb_available(const LstmWeights& w) {
 // floats of the session's h buffers: 2 layers x 2 parities of per-tile A images / of [slot][CH] vectors
 size_t live_sb_h_floats(int H, int tiles) { return (size_t)tiles * (H / 8) * 256; }
 
+// LDS opt-in + residency check of one instantiation (smem == 0: opt-in only): lds_opt_in, lstm_launch.h
 template <int LAYER, int RB>
-static hipError_t live_fb_prepare(size_t smem) {
-    auto k = live_fb_step_kernel<LAYER, RB>;
-    static PerDeviceOnce once;
-    static hipError_t attr_err[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const int di = dev >= 0 && dev < 64 ? dev : 0;
-    once.run([&] { attr_err[di] = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024); });
-    if (attr_err[di] != hipSuccess) return attr_err[di];
-    if (smem == 0) return hipSuccess;
-    int blocks = 0;
-    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, reinterpret_cast<const void*>(k), kFbThreads, smem);
-    if (e != hipSuccess) return e;
-    return blocks >= 1 ? hipSuccess : hipErrorLaunchOutOfResources;
-}
+static hipError_t live_fb_prepare(size_t smem) { return lds_opt_in<live_fb_step_kernel<LAYER, RB>>(152 * 1024, kFbThreads, smem); }
 
 // rows per workgroup of the full-band step kernel: 8, or 1 where 8 operand rows do not fit a CU's LDS; 0 = not even one
 int live_fb_rows_per_group(int H, int NIN) {

@@ -1337,6 +1337,21 @@ def test_header_is_plain_c_and_library_links_from_c(tmp_path):
     assert "gfx950" in run.stdout and "bad config rc=2" in run.stdout and "plan chunks=2" in run.stdout
 
 
+def test_every_included_file_is_in_the_build_hash():
+    """Every #include "..." of csrc/*.hip, *.cpp, *.h resolves to a file source_digest() hashes: a header outside the hash could be
+    edited and a stale libfsnp_hip.so would stay in use."""
+    from fullsubnet_plus_amd import _build
+    hashed = {os.path.realpath(os.path.join(_build.CSRC, s)) for s in _build._sources()} | {os.path.realpath(h) for h in _build._headers()}
+    includes = []
+    for name in sorted(os.listdir(_build.CSRC)):
+        if name.endswith((".hip", ".cpp", ".h")):
+            with open(os.path.join(_build.CSRC, name)) as f:
+                includes += [(name, inc) for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', f.read(), flags=re.M)]
+    assert len(includes) > 50 and ("lstm_coop.hip", "lstm_launch.h") in includes      # the scan sees the sources
+    missing = [(name, inc) for name, inc in includes if os.path.realpath(os.path.join(_build.CSRC, inc)) not in hashed]
+    assert not missing, missing
+
+
 def test_synthetic_generators_are_frozen():
     """The seeded weight / waveform generators (fullsubnet_plus_amd/synthetic.py, numpy PCG64) are what the golden fixtures
     were generated with: known-answer checksums, so a change of generator or numpy stream shows up here and not as a
