@@ -186,6 +186,19 @@ PCM_SYMBOLS = {
 SAMPLE_F32, SAMPLE_S16, SAMPLE_S16_PEAK = 0, 1, 2      # FSNP_SAMPLE_*
 SAMPLE_FORMATS = {"f32": SAMPLE_F32, "s16": SAMPLE_S16, "s16_peak": SAMPLE_S16_PEAK}
 
+# every symbol include/fsnp_resample.h declares (the whole-clip waveform path at any input sample rate; same ABI version)
+RESAMPLE_SYMBOLS = {
+    "fsnp_resample_plan": (c_i32, [c_i32, c_i32, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), ctypes.POINTER(c_i32)]),
+    "fsnp_resample_length": (c_i32, [c_i32, c_i32, c_i64, ctypes.POINTER(c_i64)]),
+    "fsnp_resample_taps": (c_i32, [c_i32, c_i32, c_vp, c_i32]),
+    "fsnp_resample_pcm": (c_i32, [c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_i32, c_i64, c_i64, ctypes.POINTER(c_i32), c_i32, c_i32, c_i32, c_i32,
+                                  c_vp, c_vp]),
+    "fsnp_enhance_wave_rate": (c_i32, [c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_i32, c_i64, c_i64, ctypes.POINTER(c_i32), c_i32, c_i32, c_vp,
+                                       c_i32, c_i32, c_vp]),
+    "fsnp_reserve_rate": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
+}
+RESAMPLE_MAX_RATIO = 640     # max(up, down) of a pair (include/fsnp_resample.h)
+
 ABI_VERSION = 13         # FSNP_ABI_VERSION of the include/fsnp.h these signatures were written against
 
 _lib = None
@@ -209,7 +222,7 @@ def load(build_if_missing=True):
     lib = ctypes.CDLL(path)
     for name, (res, args) in (list(SYMBOLS.items()) + list(LENGTHS_SYMBOLS.items()) + list(STREAM_SYMBOLS.items()) + list(WAVE_STREAM_SYMBOLS.items())
                               + list(LIVE_STREAM_SYMBOLS.items()) + list(SPEC_STREAM_SYMBOLS.items()) + list(DEVICE_WEIGHTS_SYMBOLS.items())
-                              + list(STFT_GEOMETRY_SYMBOLS.items()) + list(PCM_SYMBOLS.items())):
+                              + list(STFT_GEOMETRY_SYMBOLS.items()) + list(PCM_SYMBOLS.items()) + list(RESAMPLE_SYMBOLS.items())):
         fn = getattr(lib, name)          # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

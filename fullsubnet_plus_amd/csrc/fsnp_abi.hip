@@ -726,6 +726,7 @@ void fsnp_destroy(fsnp_handle* h) {
     (void)hipDeviceSynchronize();
     if (h->ws) (void)hipFreeAsync(h->ws, nullptr);        // (allocated from the stream-ordered pool; the device is idle here)
     if (h->io) (void)hipFreeAsync(h->io, nullptr);
+    for (auto& r : h->resample) if (r.dev) (void)hipFreeAsync(r.dev, nullptr);      // (include/fsnp_resample.h: the pairs' tap tables)
     (void)hipDeviceSynchronize();
     if (h->ev_done) (void)hipEventDestroy(h->ev_done);
     if (h->d_stft) (void)hipFree(h->d_stft);
@@ -1271,6 +1272,7 @@ int64_t fsnp_dump_config(const fsnp_handle* h, char* buf, int64_t cap) {
         h->model == FSNP_MODEL_FULLSUBNET ? "FullSubNet" : "FullSubNet+", h->F, h->cfg.look_ahead, h->H, h->CH, h->NIN, h->KX,
         h->sb_tcn ? "TCN" : h->gru ? "GRU" : "LSTM", h->cfg.norm_type, h->cfg.attention, h->cfg.subband_num > 0 ? h->cfg.subband_num : 1);
     add("waveform path: n_fft=%d hop_length=%d (win_length = n_fft, periodic Hann; fsnp_set_hop_length)\n", 2 * (h->F - 1), (int)fsnp_hop_length(h));
+    add("waveform io area: %zu bytes at %p; resample tables: %d of %d (include/fsnp_resample.h)\n", h->io_bytes, (void*)h->io, (int)h->resample.size(), kResampleMaxPairs);
     add("weights committed=%d precision=%d (0 fp32, 1 bf16 ih-GEMM) pipeline=%d timing=%d workspace=%zu bytes x %d\n",
         (int)h->committed, h->ih_bf16, h->pipeline, (int)h->timing, h->ws_bytes, h->ws_slots);
     add("effective settings (environment variable as read at fsnp_create = value in force):\n");

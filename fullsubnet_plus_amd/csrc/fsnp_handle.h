@@ -10,6 +10,7 @@
 
 #include "fsnp_common.h"
 #include "planner.h"
+#include "resample.h"
 
 namespace fsnp {
 
@@ -147,6 +148,8 @@ struct fsnp_handle {
     int hop_length = 0;          // fsnp_set_hop_length (include/fsnp_stft_geometry.h); 0 = never set: n_fft / 2
     unsigned char* io = nullptr;
     size_t io_bytes = 0;
+    // include/fsnp_resample.h: the tap tables of the (up, down) pairs this handle has run, at most kResampleMaxPairs, never evicted
+    std::vector<fsnp::ResampleCached> resample;
 
     bool timing = false;
     std::vector<TimingRec> timing_recs;   // recorded, not yet read back (drained by fsnp_get_timing, or when 256 pile up)
@@ -257,13 +260,20 @@ int ensure_stft(fsnp_handle* h);
 int ensure_io(fsnp_handle* h, size_t bytes, hipStream_t s);
 // The io area of fsnp_enhance_wave for `batch` clips of up to max_samples samples: what the call lays out and what fsnp_reserve sizes.
 // Byte offsets of the padded signal [batch][xs], the noisy and the enhanced spectra [batch][T][sp] (+ 256 bytes each), the mask
-// [batch][2][F][T] and the inverse DFT's frames [batch][T][n_fft]; T = 1 + max_samples / hop
+// [batch][2][F][T] and the inverse DFT's frames [batch][T][n_fft]; T = 1 + max_samples / hop.  stage_samples > 0 (fsnp_enhance_wave_rate:
+// max_samples counts at the model's rate, stage_samples at the caller's): behind them fp32 rows [batch][stage_samples], the staging of
+// FSNP_SAMPLE_S16_PEAK at the caller's rate
 struct WaveIo {
     int T;
     long xs;
-    size_t xp, noisy, enh, mask, fr, total;
+    size_t xp, noisy, enh, mask, fr, stage, total;
 };
-WaveIo wave_io(const StftPlan& p, int batch, int max_samples);
+WaveIo wave_io(const StftPlan& p, int batch, int max_samples, int stage_samples = 0);
+// fsnp_resample_abi.hip (include/fsnp_resample.h): 0, or 2 with the error set when the `count` pairs would take the handle past
+// kResampleMaxPairs tables (nothing is enqueued); the device table of a pair on s, built and uploaded on first use (taps = nullptr for
+// equal rates) - between order_after_last_forward and mark_forward_done, which order other streams behind the upload
+int resample_room(const fsnp_handle* h, const char* where, const ResamplePlan* plans, int count);
+int resample_table(fsnp_handle* h, const ResamplePlan& p, hipStream_t s, ResampleTable& t);
 // 0, or 2 with the error set: the format and step rules of include/fsnp_pcm.h for one sample buffer (`what`: "input" / "output";
 // peak_ok: FSNP_SAMPLE_S16_PEAK is a format this buffer may have)
 int check_sample_format(const char* where, const char* what, int32_t format, int64_t step, bool peak_ok);

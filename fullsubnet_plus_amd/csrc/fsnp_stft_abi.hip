@@ -5,6 +5,7 @@
 
 #include "fsnp_handle.h"
 #include "pcm.h"
+#include "resample.h"
 
 // ---------------------------------------------------------------------------------------------- STFT / iSTFT (f-3)
 namespace fsnp {
@@ -64,7 +65,7 @@ __global__ void spec_repack_kernel(const float2* __restrict__ in, long sb, long 
     const int f = (int)(i % spc), t = (int)((i / spc) % T), b = (int)(i / ((long)spc * T));
     out[i] = f < F ? in[b * sb + f * sf + t * st] : make_float2(0.f, 0.f);
 }
-WaveIo wave_io(const StftPlan& p, int batch, int max_samples) {
+WaveIo wave_io(const StftPlan& p, int batch, int max_samples, int stage_samples) {
     WaveIo io{};
     io.T = 1 + max_samples / p.hop;
     io.xs = (long)align_up((size_t)max_samples + p.n_fft, 4);
@@ -77,14 +78,25 @@ WaveIo wave_io(const StftPlan& p, int batch, int max_samples) {
     io.mask = take((size_t)batch * 2 * p.F * io.T * 4);
     io.fr = o;
     io.total = io.fr + (size_t)batch * io.T * p.n_fft * 4;
+    io.stage = align_up(io.total, 256);
+    if (stage_samples > 0) io.total = io.stage + (size_t)batch * stage_samples * 4;
     return io;
 }
+// fsnp_enhance_wave_rate: the clips arrive and leave at another rate.  Every row holds n samples at the caller's rate (the call's
+// max_samples is then the model-rate count ceil(n up / down) of the `in` direction, its `samples` NULL); the caller's output rows
+// have cols >= n columns, written as 0 from n on
+struct WaveRate {
+    ResamplePlan in, out;      // caller's rate -> model's rate, and back
+    int32_t n, cols;
+};
 // wav [B][L] -> spectrum rows [B][T][ldc] (interleaved complex), T = 1 + L / hop; samples: NULL, or each row's own HOST sample count
 // (reflect padding at each clip's own end; frames past 1 + samples[b] / hop see zeros behind it)
+// (rate: the padded signal is the clip converted by `tin` in the pad kernel's loads, L and samples its model-rate counts)
 static void stft_into(fsnp_handle* h, const StftPlan& p, const PcmIn& wav, float* xp, long xs, float* spec, int ldc, int B, int L,
-                      const int* samples, hipStream_t s) {
+                      const int* samples, hipStream_t s, const WaveRate* rate = nullptr, const ResampleTable* tin = nullptr) {
     const int T = 1 + L / p.hop;
-    launch_stft_pad(wav, xp, xs, B, L, samples, p.n_fft, s);
+    if (rate) launch_stft_pad_resample(wav, xp, xs, B, nullptr, rate->n, p.n_fft, *tin, s);
+    else launch_stft_pad(wav, xp, xs, B, L, samples, p.n_fft, s);
     launch_linear_act(xp, p.hop, h->d_stft + p.o_fwd, p.fwd_ld, h->d_stft + p.o_zero, spec, ldc, p.n_fft, p.N2, B, T,
                       FSNP_ACT_NONE, h->num_cus, s, xs, p.n_fft);
 }
@@ -128,7 +140,7 @@ int stft_any(fsnp_handle* h, const char* where, const PcmIn& wav, float* spec, i
 // fsnp_enhance_wave (samples = NULL: every row holds max_samples samples) and fsnp_enhance_wave_lengths behind every entry point;
 // out.fmt may be kPcmPeak, out.clipped the caller's (NULL or device int32 [batch], overwritten)
 int enhance_wave_any(fsnp_handle* h, const char* where, const PcmIn& wav, const PcmOut& out, const int32_t* samples, int32_t batch,
-                     int32_t max_samples, void* hip_stream) {
+                     int32_t max_samples, void* hip_stream, const WaveRate* rate = nullptr) {
     if (batch <= 0) { set_error("%s: empty input", where); return 2; }
     if (!h->committed) { set_error("%s: weights not committed (call fsnp_commit_weights)", where); return 2; }
     // the cIRM epilogue multiplies by exactly two mask planes (decompress_cIRM, audio_zen/acoustics/mask.py:60-63) and the io area is
@@ -136,7 +148,10 @@ int enhance_wave_any(fsnp_handle* h, const char* where, const PcmIn& wav, const 
     if (h->cfg.output_size != 2) { set_error("%s: the cIRM epilogue needs output_size = 2 (this handle: %d)", where, h->cfg.output_size); return 2; }
     if (ensure_stft(h)) return 2;
     const StftPlan p = stft_plan(h);
-    if (max_samples <= p.half) { set_error("%s: need more than n_fft/2 = %d samples (reflect padding)", where, p.half); return 2; }
+    if (max_samples <= p.half) {
+        set_error("%s: need more than n_fft/2 = %d samples%s (reflect padding)", where, p.half, rate ? " at the model's rate" : "");
+        return 2;
+    }
     // every check of the forward too, before anything is enqueued: each clip's frame count is its own STFT's, T_b = 1 + samples[b] / hop
     const int T = 1 + max_samples / p.hop;
     std::vector<int32_t> frames;
@@ -151,12 +166,21 @@ int enhance_wave_any(fsnp_handle* h, const char* where, const PcmIn& wav, const 
         }
         if (const int rc = check_lengths(h, frames.data(), batch, T, where)) return rc;
     }
+    if (rate) {
+        const ResamplePlan both[2] = {rate->in, rate->out};
+        if (const int rc = resample_room(h, where, both, 2)) return rc;
+    }
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     FSNP_ON_DEVICE(h);
-    const WaveIo io = wave_io(p, batch, max_samples);
+    const WaveIo io = wave_io(p, batch, max_samples, rate ? rate->cols : 0);
     const long xs = io.xs;
     if (order_after_last_forward(h, s)) return 4;
     if (ensure_io(h, io.total, s)) return 4;
+    ResampleTable tin{}, tout{};
+    if (rate) {
+        if (const int rc = resample_table(h, rate->in, s, tin)) return rc;
+        if (const int rc = resample_table(h, rate->out, s, tout)) return rc;
+    }
     float* xp = reinterpret_cast<float*>(h->io + io.xp);
     float* noisy = reinterpret_cast<float*>(h->io + io.noisy);
     float* enh = reinterpret_cast<float*>(h->io + io.enh);
@@ -164,7 +188,7 @@ int enhance_wave_any(fsnp_handle* h, const char* where, const PcmIn& wav, const 
     float* fr = reinterpret_cast<float*>(h->io + io.fr);
     // inferencer.py:142-158: stft -> (mag, real, imag) -> model -> decompress_cIRM, complex multiply -> istft(length); with lengths
     // the reflect padding at each clip's end (frames past T_b see zeros: the forward never reads them)
-    stft_into(h, p, wav, xp, xs, noisy, p.sp, batch, max_samples, samples, s);
+    stft_into(h, p, wav, xp, xs, noisy, p.sp, batch, max_samples, samples, s, rate, &tin);
     const int64_t cst[3] = {(int64_t)T * (p.sp / 2), 1, p.sp / 2};       // complex-element strides of [B][T][sp/2] as (b, f, t)
     const int rc = samples ? fsnp_forward_complex_lengths(h, noisy, cst, frames.data(), mask, batch, T, hip_stream)
                            : fsnp_forward_complex(h, noisy, cst, mask, batch, T, FSNP_MODE_FULL, 0, batch, hip_stream);
@@ -183,6 +207,22 @@ int enhance_wave_any(fsnp_handle* h, const char* where, const PcmIn& wav, const 
     PcmOut o = out;
     if (out.clipped) FSNP_HIP_CHECK(hipMemsetAsync(out.clipped, 0, (size_t)batch * 4, s));
     if (out.fmt != kPcmS16) o.clipped = nullptr;                          // nothing clips in the other formats
+    if (rate) {
+        // another rate out: the overlap-add stages its fp32 model-rate rows where the padded input was, as the peak format does, and
+        // the resample kernel converts them into the caller's first n samples in the caller's format (n <= what n16 samples convert to).
+        // FSNP_SAMPLE_S16_PEAK: its first pass, into the staging rows at the caller's rate behind everything else
+        launch_istft_ola(fr, h->d_stft + p.o_win, pcm_out_f32(xp, xs), batch, T, max_samples, samples, p.n_fft, p.hop, s);
+        float* stage = reinterpret_cast<float*>(h->io + io.stage);
+        if (out.fmt == kPcmPeak) {
+            FSNP_HIP_CHECK(hipMemsetAsync(noisy, 0, (size_t)batch * 4, s));
+            o = PcmOut{stage, (long)rate->cols, 1, kPcmPeak, nullptr, reinterpret_cast<unsigned*>(noisy)};
+        }
+        launch_resample(pcm_in_f32(xp, xs), o, tout, batch, nullptr, rate->n, rate->cols, true, s);
+        if (out.fmt == kPcmPeak)
+            launch_pcm_peak_scale(stage, rate->cols, o.peak, PcmOut{out.p, out.stride, out.step, kPcmS16, nullptr, nullptr}, batch, rate->cols, s);
+        FSNP_HIP_CHECK(hipGetLastError());
+        return mark_forward_done(h, s);
+    }
     if (out.fmt == kPcmPeak) {
         FSNP_HIP_CHECK(hipMemsetAsync(noisy, 0, (size_t)batch * 4, s));
         o = PcmOut{xp, xs, 1, kPcmPeak, nullptr, reinterpret_cast<unsigned*>(noisy)};
@@ -254,6 +294,57 @@ int fsnp_enhance_wave_pcm(fsnp_handle* h, const void* wav, int32_t in_format, in
     if (const int rc = check_sample_format("fsnp_enhance_wave_pcm", "output", out_format, out_step, true)) return rc;
     return enhance_wave_any(h, "fsnp_enhance_wave_pcm", PcmIn{wav, (long)wav_stride, (long)wav_step, in_format},
                             PcmOut{out, (long)out_stride, (long)out_step, out_format, clipped, nullptr}, samples, batch, max_samples, hip_stream);
+}
+
+// include/fsnp_resample.h: the same call at another sample rate (the other entry points of that header: fsnp_resample_abi.hip)
+int fsnp_enhance_wave_rate(fsnp_handle* h, const void* wav, int32_t in_format, int64_t wav_stride, int64_t wav_step, void* out,
+                           int32_t out_format, int64_t out_stride, int64_t out_step, const int32_t* samples, int32_t batch,
+                           int32_t max_samples, int32_t* clipped, int32_t sample_rate, int32_t model_rate, void* hip_stream) {
+    const char* where = "fsnp_enhance_wave_rate";
+    if (!h || !wav || !out) { set_error("%s: null argument", where); return 1; }
+    WaveRate rate{};
+    if (const int rc = resample_plan(where, sample_rate, model_rate, rate.in)) return rc;
+    if (const int rc = resample_plan(where, model_rate, sample_rate, rate.out)) return rc;
+    if (rate.in.up == rate.in.down)
+        return fsnp_enhance_wave_pcm(h, wav, in_format, wav_stride, wav_step, out, out_format, out_stride, out_step, samples, batch,
+                                     max_samples, clipped, hip_stream);
+    if (const int rc = check_sample_format(where, "input", in_format, wav_step, false)) return rc;
+    if (const int rc = check_sample_format(where, "output", out_format, out_step, true)) return rc;
+    if (batch <= 0 || max_samples <= 0) { set_error("%s: empty input", where); return 2; }
+    const long long max16 = resample_length(rate.in, max_samples);
+    if (max16 > INT32_MAX / 2) { set_error("%s: %lld model-rate samples per clip do not fit", where, max16); return 2; }
+    rate.n = rate.cols = max_samples;
+    const PcmIn in{wav, (long)wav_stride, (long)wav_step, in_format};
+    const PcmOut o{out, (long)out_stride, (long)out_step, out_format, clipped, nullptr};
+    if (!samples) return enhance_wave_any(h, where, in, o, nullptr, batch, (int32_t)max16, hip_stream, &rate);
+    // With `samples`, row b IS that clip run alone: one call of batch 1 per row, so that a row has the bits of the clip converted,
+    // enhanced and converted back on its own.  (One batch over all rows would not: the model's kernels are chosen by the batch size,
+    // and their fp32 sums then run in another order - 1e-6 relative.)  A caller who prefers one batch's throughput to that pads the
+    // clips to one length.  Every row is checked before anything is enqueued.
+    if (ensure_stft(h)) return 2;
+    const int half = stft_plan(h).half;
+    for (int b = 0; b < batch; ++b) {
+        if (samples[b] < 1 || samples[b] > max_samples) {
+            set_error("%s: utterance %d: %d samples outside [1, %d]", where, b, (int)samples[b], (int)max_samples);
+            return 2;
+        }
+        if (resample_length(rate.in, samples[b]) <= half) {
+            set_error("%s: utterance %d: %d samples are %lld at the model's rate; need more than n_fft/2 = %d (reflect padding)", where, b,
+                      (int)samples[b], resample_length(rate.in, samples[b]), half);
+            return 2;
+        }
+    }
+    for (int b = 0; b < batch; ++b) {
+        PcmIn ib = in;
+        PcmOut ob = o;
+        ib.p = static_cast<const char*>(in.p) + (long)b * in.stride * (in.fmt == kPcmF32 ? 4 : 2);
+        ob.p = static_cast<char*>(o.p) + (long)b * o.stride * (o.fmt == kPcmF32 ? 4 : 2);      // (the CALLER's buffer: int16 for both int16 formats)
+        if (clipped) ob.clipped = clipped + b;
+        rate.n = samples[b];
+        if (const int rc = enhance_wave_any(h, where, ib, ob, nullptr, 1, (int32_t)resample_length(rate.in, samples[b]), hip_stream, &rate))
+            return rc;
+    }
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------- include/fsnp_stft_geometry.h

@@ -21,6 +21,7 @@
 
 #include "fsnp_common.h"
 #include "pcm.h"
+#include "resample.h"
 
 namespace fsnp {
 
@@ -49,6 +50,37 @@ void launch_stft_pad(const PcmIn& wav, float* xp, long xp_stride, int B, int L, 
     for_row_chunks(B, samples, L, [&](int b0, int rows, auto len) {
         const dim3 grid((unsigned)((xp_stride + 255) / 256), rows);
 #define FSNP_CALL(F) hipLaunchKernelGGL((stft_pad_kernel<F, decltype(len)>), grid, dim3(256), 0, s, pcm_rows(wav, b0), xp + (long)b0 * xp_stride, xp_stride, n_fft / 2, len)
+        FSNP_PCM_SWITCH2(wav.fmt, FSNP_CALL);
+#undef FSNP_CALL
+    });
+}
+
+// The resampling variant (include/fsnp_resample.h): the clip arrives at another rate, and the padded sample at model-rate index j - after
+// the reflect rule - is the FIR sum resample_sample taken straight from the caller's buffer.  No model-rate copy of the clip is written.
+// `len` counts samples at the caller's rate; row b is ceil(n_b up / down) model-rate samples long.
+template <int FMT, typename LEN>
+__global__ __launch_bounds__(256) void stft_pad_resample_kernel(PcmIn wav, float* __restrict__ xp, long xp_stride, int half, LEN len,
+                                                                ResampleTable t) {
+    const int b = blockIdx.y;
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= xp_stride) return;
+    const long n = row_len(len, b);
+    const long L = (n * t.up + t.down - 1) / t.down;
+    float v = 0.0f;
+    if (p < L + 2 * half) {
+        long j = p - half;
+        if (j < 0) j = -j;
+        if (j >= L) j = 2 * (L - 1) - j;
+        v = resample_sample<FMT>(wav, b, j, n, t);
+    }
+    xp[(long)b * xp_stride + p] = v;
+}
+
+void launch_stft_pad_resample(const PcmIn& wav, float* xp, long xp_stride, int B, const int* samples, int uniform, int n_fft,
+                              const ResampleTable& t, hipStream_t s) {
+    for_row_chunks(B, samples, uniform, [&](int b0, int rows, auto len) {
+        const dim3 grid((unsigned)((xp_stride + 255) / 256), rows);
+#define FSNP_CALL(F) hipLaunchKernelGGL((stft_pad_resample_kernel<F, decltype(len)>), grid, dim3(256), 0, s, pcm_rows(wav, b0), xp + (long)b0 * xp_stride, xp_stride, n_fft / 2, len, t)
         FSNP_PCM_SWITCH2(wav.fmt, FSNP_CALL);
 #undef FSNP_CALL
     });

@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib, _policy
-from ._args import _host_lengths
+from ._args import _host_lengths, _rate, resample_plan
 
 _TCN_DILATIONS = (1, 2, 5, 9, 1, 2, 5, 9)
 
@@ -611,6 +611,18 @@ class _HipModel(nn.Module):
         if self._hip.handle is not None:
             _lib.check(_lib.load().fsnp_set_hop_length(self._handle, int(hop)), "fsnp_set_hop_length")
 
+    @property
+    def sample_rate(self):
+        """The rate in Hz the model's weights were trained at and its STFT runs at: `sr` of [acoustics] in the reference's TOML, 16000
+        unless assigned.  enhance_wave(..., sample_rate=R), resample and reserve(..., sample_rate=R) convert between R and this rate
+        (include/fsnp_resample.h).  Held in Python and passed with every call; assigning validates (ValueError unless a positive
+        integer) and touches no GPU.  Sessions take no rate: they run at this one."""
+        return self.__dict__.get("_sample_rate", 16000)
+
+    @sample_rate.setter
+    def sample_rate(self, rate):
+        self.__dict__["_sample_rate"] = _rate(rate, f"{self.__class__.__name__}.sample_rate")
+
     def verify_count(self):
         """-> verification passes run so far (fsnp_verify_count)."""
         return int(_lib.load().fsnp_verify_count(self._handle))
@@ -636,17 +648,28 @@ class _HipModel(nn.Module):
         _lib.check(lib.fsnp_set_pipeline(self._handle, int(bool(enable))), "fsnp_set_pipeline")
         self._pipeline = bool(enable)
 
-    def reserve(self, max_batch, max_frames, max_samples=0, device="cuda"):
+    def reserve(self, max_batch, max_frames, max_samples=0, device="cuda", sample_rate=None):
         """Grow the handle's workspace once to what any forward of <= max_batch utterances x max_frames frames needs (and the
         STFT / iSTFT area of enhance_wave for max_samples samples per utterance): a serving loop with varying clip lengths then
-        never re-allocates (fsnp_reserve; stream-ordered on the current stream, no device synchronisation)."""
+        never re-allocates (fsnp_reserve; stream-ordered on the current stream, no device synchronisation).  sample_rate: the rate
+        enhance_wave will be called with; max_samples then counts at that rate, max_frames stays in model steps, and the tap tables
+        of both directions are uploaded too (fsnp_reserve_rate)."""
+        rate = None
+        if sample_rate is not None:
+            what = f"{self.__class__.__name__}.reserve"
+            resample_plan(sample_rate, self.sample_rate, what)
+            resample_plan(self.sample_rate, sample_rate, what)
+            rate = None if _rate(sample_rate, what) == self.sample_rate else int(sample_rate)
         dev = _resolve_device(device)
         lib = self._ensure_handle(dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
         mode = _lib.MODE_PARITY if (self.batch_mode == "parity" and max_batch > 1 and self.num_groups_in_drop_band > 1) else _lib.MODE_FULL
         with torch.cuda.device(dev):
-            _lib.check(lib.fsnp_reserve(self._handle, int(max_batch), int(max_frames), mode, int(max_samples), ctypes.c_void_p(stream)),
-                       "fsnp_reserve")
+            _lib.check(lib.fsnp_reserve(self._handle, int(max_batch), int(max_frames), mode, 0 if rate else int(max_samples),
+                                        ctypes.c_void_p(stream)), "fsnp_reserve")
+            if rate and int(max_samples) > 0:
+                _lib.check(lib.fsnp_reserve_rate(self._handle, int(max_batch), int(max_samples), rate, self.sample_rate,
+                                                 ctypes.c_void_p(stream)), "fsnp_reserve_rate")
 
     def flush(self):
         """Order the current stream after every deferred launch of earlier forwards (fsnp_flush)."""
@@ -742,7 +765,7 @@ class _HipModel(nn.Module):
                                       out.stride(0), B, T, int(length), ctypes.c_void_p(stream)), "fsnp_istft")
         return out
 
-    def enhance_wave(self, noisy, lengths=None, out_format=None, clipped=None):
+    def enhance_wave(self, noisy, lengths=None, out_format=None, clipped=None, sample_rate=None):
         """The reference inferencer's inner loop in ONE call (fullsubnet_plus/inferencer/inferencer.py:142-158,
         `mag_complex_full_band_crm_mask`; `full_band_crm_mask` of fullsubnet/inferencer/inferencer.py for the original
         FullSubNet): noisy waveform [B, samples] -> enhanced waveform [B, samples]; STFT, model (all bins), cIRM
@@ -757,9 +780,23 @@ class _HipModel(nn.Module):
         (follow the input: float -> fp32 as ever, int16 -> "s16"), "f32", "s16" (int16, round half to even, saturating) or "s16_peak"
         (int16, the reference CLI's peak normalisation np.int16(0.8 * 32767 * y / max|y|) over each clip's own samples).  clipped:
         optional int32 CUDA tensor [B], overwritten with the number of samples of each row that saturated or were NaN ("s16" only:
-        0 for the other formats)."""
+        0 for the other formats).
+
+        sample_rate (include/fsnp_resample.h): None or self.sample_rate is the call as it has always been.  Any other rate in Hz: noisy
+        [B, L] holds samples at that rate and so does the result [B, L]; lengths count samples at that rate.  The clip is converted
+        to the model's rate inside the kernel that pads it for the STFT and the result is converted back on the way out, by one
+        fixed polyphase FIR: the call gives, bit for bit, resample(enhance_wave(resample(noisy, R, M)), M, R)[:, :L] - with lengths,
+        row b is that composition of noisy[b:b+1, :lengths[b]] alone, bit for bit: the rows then run one clip at a time (the model is
+        not bit-identical between batch sizes), which costs the batch's throughput; pad to one length for one batch.  ValueError
+        for a rate that is no positive integer or a ratio with max(up, down) > 640, before any GPU is touched."""
         assert self.output_size == 2, "the cIRM epilogue needs the two mask channels (decompress_cIRM, acoustics/mask.py:60-63)"
         assert noisy.dim() == 2, "expected [B, samples]"
+        rate = None
+        if sample_rate is not None:
+            what = f"{self.__class__.__name__}.enhance_wave"
+            resample_plan(sample_rate, self.sample_rate, what)
+            resample_plan(self.sample_rate, sample_rate, what)
+            rate = None if _rate(sample_rate, what) == self.sample_rate else int(sample_rate)
         if out_format is not None and out_format not in _lib.SAMPLE_FORMATS:
             raise ValueError(f"enhance_wave: out_format {out_format!r} is none of None, 'f32', 's16', 's16_peak'")
         if not noisy.is_cuda:
@@ -767,8 +804,8 @@ class _HipModel(nn.Module):
         samples = None if lengths is None else _host_lengths(lengths, noisy.shape[0], f"{self.__class__.__name__}.enhance_wave")
         pcm = self._pcm_view(noisy)
         ofmt = _lib.SAMPLE_FORMATS[out_format or ("s16" if noisy.dtype == torch.int16 else "f32")]
-        if pcm is not None or ofmt != _lib.SAMPLE_F32 or clipped is not None:
-            return self._enhance_wave_pcm(noisy if pcm is None else pcm, samples, ofmt, clipped)
+        if pcm is not None or ofmt != _lib.SAMPLE_F32 or clipped is not None or rate is not None:
+            return self._enhance_wave_pcm(noisy if pcm is None else pcm, samples, ofmt, clipped, rate)
         wav, lib, stream = self._wave_args(noisy)
         B, L = wav.shape
         out = torch.empty((B, L), dtype=torch.float32, device=wav.device)
@@ -787,9 +824,10 @@ class _HipModel(nn.Module):
             return out
         return self._checked(run)
 
-    def _enhance_wave_pcm(self, wav, samples, ofmt, clipped):
+    def _enhance_wave_pcm(self, wav, samples, ofmt, clipped, rate=None):
         """enhance_wave through fsnp_enhance_wave_pcm: wav int16 or floating point at any strides, samples the ctypes int32[B] of
-        _host_lengths or None, ofmt a _lib.SAMPLE_* value."""
+        _host_lengths or None, ofmt a _lib.SAMPLE_* value.  rate: None, or the samples' rate in Hz where it is not the model's
+        (fsnp_enhance_wave_rate)."""
         if wav.dtype not in (torch.int16, torch.float32):
             wav = wav.float()
         if wav.shape[1] > 1 and wav.stride(1) < 1:
@@ -803,16 +841,58 @@ class _HipModel(nn.Module):
         ifmt = _lib.SAMPLE_S16 if wav.dtype == torch.int16 else _lib.SAMPLE_F32
         out = torch.empty((B, L), dtype=torch.float32 if ofmt == _lib.SAMPLE_F32 else torch.int16, device=wav.device)
 
+        model_rate = self.sample_rate
+
         def enqueue():
             with torch.cuda.device(wav.device):
+                if rate is not None:
+                    return lib.fsnp_enhance_wave_rate(self._handle, wav.data_ptr(), ifmt, wav.stride(0), max(wav.stride(1), 1), out.data_ptr(),
+                                                      ofmt, out.stride(0), 1, samples, B, L, None if clipped is None else clipped.data_ptr(),
+                                                      rate, model_rate, ctypes.c_void_p(stream))
                 return lib.fsnp_enhance_wave_pcm(self._handle, wav.data_ptr(), ifmt, wav.stride(0), max(wav.stride(1), 1), out.data_ptr(), ofmt,
                                                  out.stride(0), 1, samples, B, L, None if clipped is None else clipped.data_ptr(),
                                                  ctypes.c_void_p(stream))
 
         def run():
-            _policy.enqueue_retrying_stale(enqueue, self._stale_weights_noticed, "fsnp_enhance_wave_pcm")
+            _policy.enqueue_retrying_stale(enqueue, self._stale_weights_noticed,
+                                           "fsnp_enhance_wave_pcm" if rate is None else "fsnp_enhance_wave_rate")
             return out
         return self._checked(run)
+
+    def resample(self, wav, from_rate, to_rate, lengths=None, out_format=None, clipped=None):
+        """Sample-rate conversion on the device by the filter enhance_wave(..., sample_rate=) uses (include/fsnp_resample.h; one fixed
+        zero-phase polyphase FIR, one thread per output sample): wav [B, L] at from_rate -> [B, ceil(L * up / down)] at to_rate.
+        wav, out_format and clipped follow enhance_wave's rules: fp32 or torch.int16 at any strides, read in place; out_format None
+        follows the input, or "f32" / "s16" / "s16_peak" (peak over each row's own output samples); clipped an int32 CUDA tensor [B].
+        lengths: samples per row at from_rate; row b is then that clip converted alone, 0 from its ceil(lengths[b] * up / down) on.
+        from_rate == to_rate is a format-converting copy.  ValueError for a bad rate or ratio before any GPU is touched; a handle
+        keeps the tables of 8 (up, down) pairs and refuses a ninth."""
+        what = f"{self.__class__.__name__}.resample"
+        assert wav.dim() == 2, "expected [B, samples]"
+        up, down, _ = resample_plan(from_rate, to_rate, what)
+        if out_format is not None and out_format not in _lib.SAMPLE_FORMATS:
+            raise ValueError(f"resample: out_format {out_format!r} is none of None, 'f32', 's16', 's16_peak'")
+        if not wav.is_cuda:
+            raise RuntimeError("fullsubnet_plus_amd runs on MI355X (HIP) only; there is deliberately no CPU fallback.")
+        samples = None if lengths is None else _host_lengths(lengths, wav.shape[0], what)
+        if wav.dtype not in (torch.int16, torch.float32):
+            wav = wav.float()
+        if wav.shape[1] > 1 and wav.stride(1) < 1:
+            wav = wav.contiguous()
+        B, L = wav.shape
+        if clipped is not None:
+            if not (clipped.is_cuda and clipped.device == wav.device and clipped.dtype == torch.int32 and clipped.shape == (B,)
+                    and clipped.is_contiguous()):
+                raise ValueError(f"resample: clipped must be a contiguous torch.int32 tensor [{B}] on {wav.device}")
+        ofmt = _lib.SAMPLE_FORMATS[out_format or ("s16" if wav.dtype == torch.int16 else "f32")]
+        ifmt = _lib.SAMPLE_S16 if wav.dtype == torch.int16 else _lib.SAMPLE_F32
+        lib, stream = self._ensure_handle(wav.device), torch.cuda.current_stream(wav.device).cuda_stream
+        out = torch.empty((B, -(-L * up // down)), dtype=torch.float32 if ofmt == _lib.SAMPLE_F32 else torch.int16, device=wav.device)
+        with torch.cuda.device(wav.device):
+            _lib.check(lib.fsnp_resample_pcm(self._handle, wav.data_ptr(), ifmt, wav.stride(0), max(wav.stride(1), 1), out.data_ptr(), ofmt,
+                                             out.stride(0), 1, samples, B, L, int(from_rate), int(to_rate),
+                                             None if clipped is None else clipped.data_ptr(), ctypes.c_void_p(stream)), "fsnp_resample_pcm")
+        return out
 
     def _apply_cirm(self, mask, noisy_complex, lengths=None):
         """lengths: None, or the ctypes int32[B] of _host_lengths (frames >= lengths[b] of row b are written as 0)."""

@@ -314,4 +314,5 @@ int32_t fsnp_config_size(void);
 #include "fsnp_device_weights.h" /* weights handed over in device memory and packed on the GPU */
 #include "fsnp_stft_geometry.h" /* the hop length of the waveform path (n_fft = 2 (num_freqs - 1), periodic Hann of n_fft) */
 #include "fsnp_pcm.h" /* 16-bit PCM and strided samples at the boundary of the waveform path and of wave sessions */
+#include "fsnp_resample.h" /* the whole-clip waveform path at any input sample rate, converted on the device */
 #endif /* FSNP_H */
