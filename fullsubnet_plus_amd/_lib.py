@@ -197,6 +197,23 @@ RESAMPLE_SYMBOLS = {
                                        c_i32, c_i32, c_vp]),
     "fsnp_reserve_rate": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
 }
+# every symbol include/fsnp_wave_rate_stream.h declares (wave sessions at any input sample rate; same ABI version)
+WAVE_RATE_STREAM_SYMBOLS = {
+    "fsnp_resample_ready": (c_i32, [c_i32, c_i32, c_i64, ctypes.POINTER(c_i64)]),
+    "fsnp_wave_rate_stream_create": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_vp)]),
+    "fsnp_wave_rate_stream_create_live": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, ctypes.POINTER(c_vp)]),
+    "fsnp_wave_rate_stream_destroy": (None, [c_vp]),
+    "fsnp_wave_rate_stream_push_pcm": (c_i32, [c_vp, c_vp, c_i32, c_i64, c_i64, ctypes.POINTER(c_i32), c_vp, c_i32, c_i64, c_i64, c_i32, c_vp]),
+    "fsnp_wave_rate_stream_finish_pcm": (c_i32, [c_vp, ctypes.POINTER(c_i32), c_i32, c_vp, c_i32, c_i64, c_i64, c_vp]),
+    "fsnp_wave_rate_stream_reset": (c_i32, [c_vp, ctypes.POINTER(c_i32), c_i32, c_vp]),
+    "fsnp_wave_rate_stream_delay": (c_i32, [c_vp]),
+    "fsnp_wave_rate_stream_model_delay": (c_i32, [c_vp]),
+    "fsnp_wave_rate_stream_model_max_samples": (c_i32, [c_vp]),
+    "fsnp_wave_rate_stream_state_bytes": (c_i64, [c_vp]),
+    "fsnp_wave_rate_stream_get_state": (c_i32, [c_vp, c_i32, c_vp, c_vp]),
+    "fsnp_wave_rate_stream_set_state": (c_i32, [c_vp, c_i32, c_vp, c_vp]),
+    "fsnp_wave_rate_stream_samples": (c_i32, [c_vp, c_i32, ctypes.POINTER(c_i64)]),
+}
 RESAMPLE_MAX_RATIO = 640     # max(up, down) of a pair (include/fsnp_resample.h)
 
 ABI_VERSION = 13         # FSNP_ABI_VERSION of the include/fsnp.h these signatures were written against
@@ -222,7 +239,8 @@ def load(build_if_missing=True):
     lib = ctypes.CDLL(path)
     for name, (res, args) in (list(SYMBOLS.items()) + list(LENGTHS_SYMBOLS.items()) + list(STREAM_SYMBOLS.items()) + list(WAVE_STREAM_SYMBOLS.items())
                               + list(LIVE_STREAM_SYMBOLS.items()) + list(SPEC_STREAM_SYMBOLS.items()) + list(DEVICE_WEIGHTS_SYMBOLS.items())
-                              + list(STFT_GEOMETRY_SYMBOLS.items()) + list(PCM_SYMBOLS.items()) + list(RESAMPLE_SYMBOLS.items())):
+                              + list(STFT_GEOMETRY_SYMBOLS.items()) + list(PCM_SYMBOLS.items()) + list(RESAMPLE_SYMBOLS.items())
+                              + list(WAVE_RATE_STREAM_SYMBOLS.items())):
         fn = getattr(lib, name)          # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

@@ -2,7 +2,8 @@
 // fsnp_abi.hip (create / forward orchestration / workspace / calibration), forward_kernels.hip (the forward's small kernels),
 // fsnp_verify.hip (exchange verification), fsnp_debug_abi.hip (include/fsnp_debug.h: test and tuning hooks), fsnp_weights.hip
 // (strict weight loading + packing), fsnp_stft_abi.hip (STFT / iSTFT / waveform entry points), fsnp_stream_abi.hip,
-// fsnp_wave_stream_abi.hip and fsnp_spec_stream_abi.hip (stream, wave and spectrum sessions, and the slot helpers they share).  Host only.
+// fsnp_wave_stream_abi.hip, fsnp_spec_stream_abi.hip and fsnp_wave_rate_stream_abi.hip (stream, wave, spectrum and rate sessions, and the
+// slot helpers they share).  Host only.
 #pragma once
 #include <map>
 #include <string>
@@ -351,5 +352,11 @@ struct SpecRing { unsigned char* ring; size_t ring_stride; int look_ahead; };
 int spec_push_body(fsnp_stream* mag_session, const SpecRing& ring, float* mag, float* mask, const float* spec, const int64_t strides[3],
                    const SlotCounts& spectra, const SlotCounts& steps, float* out, const int64_t out_strides[3], bool write_idle, int n,
                    hipStream_t s);
+// fsnp_wave_stream_abi.hip: what the public push, finish and set_state of a wave session run behind their NULL and format checks
+// (`where` names the entry point in every message) - and what a rate session (fsnp_wave_rate_stream_abi.hip) drives its inner session
+// through, on workspace rows.  wave_set_state: known = NULL reads the loaded sample count back (one wait); a caller that knows it passes it.
+int wave_push(fsnp_wave_stream* w, const char* where, const PcmIn& wav, const int32_t* counts, const PcmOut& out, int32_t n, void* hip_stream);
+int wave_finish(fsnp_wave_stream* w, const char* where, const int32_t* slots, int32_t num, const PcmOut& out, void* hip_stream);
+int wave_set_state(fsnp_wave_stream* w, int32_t slot, const void* dev_src, const long long* known, void* hip_stream);
 
 }  // namespace fsnp

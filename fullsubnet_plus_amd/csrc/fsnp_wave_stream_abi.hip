@@ -146,7 +146,12 @@ int wave_create(fsnp_handle* h, int32_t slots, int32_t max_samples, int live, co
     return 0;
 }
 
-// fsnp_wave_stream_push / _push_pcm and fsnp_wave_stream_finish / _finish_pcm behind their own checks
+}  // namespace
+
+namespace fsnp {
+
+// fsnp_wave_stream_push / _push_pcm and fsnp_wave_stream_finish / _finish_pcm behind their own checks (fsnp_handle.h: a rate session,
+// fsnp_wave_rate_stream_abi.hip, drives its inner session through these same bodies)
 int wave_push(fsnp_wave_stream* w, const char* where, const PcmIn& wav, const int32_t* counts, const PcmOut& out, int32_t n, void* hip_stream) {
     if (n < 1 || n > w->max_samples) { set_error("%s: n = %d outside [1, max_samples = %d]", where, n, w->max_samples); return 2; }
     SlotCounts c{};
@@ -176,7 +181,25 @@ int wave_finish(fsnp_wave_stream* w, const char* where, const int32_t* slots, in
     return wave_reset(w, slots, num, hip_stream);
 }
 
-}  // namespace
+// fsnp_wave_stream_set_state behind its checks.  known = NULL: a migration call - the frames a later push completes follow from the
+// slot's sample count, which the host must know - one wait.  A caller that knows the count (a rate session: it follows from its own) waits itself.
+int wave_set_state(fsnp_wave_stream* w, int32_t slot, const void* dev_src, const long long* known, void* hip_stream) {
+    if (const int rc = fsnp_stream_set_state(w->mag, slot, dev_src, hip_stream)) return rc;
+    FSNP_ON_DEVICE(w->h);
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    if (const int rc = w->rec.set(slot, dev_src, w->mag_bytes, s)) return rc;
+    long long v = 0;
+    if (known) v = *known;
+    else {
+        FSNP_HIP_CHECK(hipMemcpyAsync(&v, static_cast<const unsigned char*>(dev_src) + w->mag_bytes + w->o_count, 8, hipMemcpyDeviceToHost, s));
+        FSNP_HIP_CHECK(hipStreamSynchronize(s));
+    }
+    if (v < 0) { set_error("fsnp_wave_stream_set_state: slot %d: the loaded record holds a negative sample count", slot); return 2; }
+    w->samples[slot] = v;
+    return 0;
+}
+
+}  // namespace fsnp
 
 extern "C" {
 
@@ -249,17 +272,7 @@ int fsnp_wave_stream_get_state(fsnp_wave_stream* w, int32_t slot, void* dev_dst,
 int fsnp_wave_stream_set_state(fsnp_wave_stream* w, int32_t slot, const void* dev_src, void* hip_stream) {
     if (!w || !dev_src) { set_error("fsnp_wave_stream_set_state: null argument"); return 1; }
     if (const int rc = check_slot("fsnp_wave_stream_set_state", slot, w->S)) return rc;
-    if (const int rc = fsnp_stream_set_state(w->mag, slot, dev_src, hip_stream)) return rc;
-    FSNP_ON_DEVICE(w->h);
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    if (const int rc = w->rec.set(slot, dev_src, w->mag_bytes, s)) return rc;
-    // a migration call: the frames a later push completes follow from the slot's sample count, which the host must know - one wait
-    long long v = 0;
-    FSNP_HIP_CHECK(hipMemcpyAsync(&v, static_cast<const unsigned char*>(dev_src) + w->mag_bytes + w->o_count, 8, hipMemcpyDeviceToHost, s));
-    FSNP_HIP_CHECK(hipStreamSynchronize(s));
-    if (v < 0) { set_error("fsnp_wave_stream_set_state: slot %d: the loaded record holds a negative sample count", slot); return 2; }
-    w->samples[slot] = v;
-    return 0;
+    return wave_set_state(w, slot, dev_src, nullptr, hip_stream);
 }
 
 int fsnp_wave_stream_samples(fsnp_wave_stream* w, int32_t slot, int64_t* pushed) {

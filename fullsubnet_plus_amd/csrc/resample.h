@@ -48,10 +48,11 @@ void resample_build_taps(const ResamplePlan& p, float* taps);
 void resample_build_table(const ResamplePlan& p, float* table /*[up][tpp]*/);
 
 #ifdef __HIPCC__
-// Output sample m of a row of n input samples.  Starts from 0.0f, ascending k, every step an explicit fmaf(t, x, acc); samples outside
-// [0, n) are zeros and never read.
-template <int FMT>
-__device__ __forceinline__ float resample_sample(const PcmIn& in, long b, long m, long n, const ResampleTable& r) {
+// Output sample m of a row of n input samples, sample k of the row being load(k).  Starts from 0.0f, ascending k, every step an explicit
+// fmaf(t, x, acc); samples outside [0, n) are zeros and never loaded.  Where the samples lie is the caller's: one buffer (resample_sample),
+// or a slot's carried history in front of a push's new samples (resample_stream.hip).
+template <typename LOAD>
+__device__ __forceinline__ float resample_sum(LOAD&& load, long m, long n, const ResampleTable& r) {
     const long c = m * r.down;                                 // the output's position on the grid of rate from * up
     const long q = c / r.up;
     const long at = (c - q * r.up) * r.tpp + r.J - q;          // table index of sample k: at + k
@@ -59,10 +60,50 @@ __device__ __forceinline__ float resample_sample(const PcmIn& in, long b, long m
     long k1 = (c + r.half) / r.up;                             // last k with c - k up >= -half
     if (k1 > n - 1) k1 = n - 1;
     float acc = 0.0f;
-    for (; k <= k1; ++k) acc = fmaf(r.taps[at + k], pcm_load<FMT>(in, b, k), acc);
+    for (; k <= k1; ++k) acc = fmaf(r.taps[at + k], load(k), acc);
     return acc;
 }
+template <int FMT>
+__device__ __forceinline__ float resample_sample(const PcmIn& in, long b, long m, long n, const ResampleTable& r) {
+    return resample_sum([&](long k) { return pcm_load<FMT>(in, b, k); }, m, n, r);
+}
 #endif
+
+// ---- streaming conversion (include/fsnp_wave_rate_stream.h; kernels: resample_stream.hip).  `p` is the plan of the caller's rate R ->
+// the model's rate M; the way back is (down, up, half).  All of it 64-bit host-and-device arithmetic on the slot's sample count.
+// model-rate samples whose whole window lies inside the first P input samples: sample j needs input up to floor((j down + half) / up)
+__host__ __device__ inline long long resample_ready(int up, int down, int half, long long P) {
+    return P * up <= half ? 0 : (P * up - half - 1) / down + 1;
+}
+__host__ __device__ inline long long resample_total(int up, int down, long long L) { return (L * up + down - 1) / down; }
+// the smallest delay at rate R at which every push can return as many samples as it took, the inner session being DM samples late
+inline long long resample_stream_delay(const ResamplePlan& p, long long DM) { return (DM * p.down + 2LL * p.half + 1 + p.up - 1) / p.up - 1; }
+// carried samples: the input ones below P that sample ready(P) still reads, the enhanced ones a push's first output still reads
+inline int resample_hist_in(const ResamplePlan& p) { return 2 * p.half / p.up; }
+inline int resample_hist_out(const ResamplePlan& p) { return (2 * p.half + p.down - 1) / p.down; }
+// most model-rate samples one push of c input samples completes, and a finish adds (total(L) - ready(L))
+inline long long resample_push_max(const ResamplePlan& p, long long c) { return c * p.up / p.down + 1; }
+inline int resample_finish_max(const ResamplePlan& p) { return (p.half + p.down - 1) / p.down; }
+
+struct RateMeta { long long p; int c, fin; };      // samples (rate R) the slot had before this call, samples it gets now, 1 = it is finished now
+struct RateArgs {
+    unsigned char* state;                          // rate record of slot 0: [ input history fp32 [HI] | enhanced history fp32 [HE] | count int64 | up, down int32 ]
+    size_t stride, o_he, o_count;                  // bytes between slots, byte offsets inside a record (the input history is at 0)
+    RateMeta* meta;                                // [S], written by the in kernel for the out kernel behind it
+    int S, HI, HE;
+    int up, down, half;                            // the plan R -> M
+    long long DM, DR;                              // the inner session's delay (rate M), the rate session's (rate R)
+};
+struct SlotCounts;
+// c.v[slot]: samples of a push, or (fin) 1 = finish this slot.  xin [S][xs] fp32: the model-rate samples ready(P) .. ready(P + c) - 1
+// (finish: .. total(L) - 1, the input clamped at L - 1) of every slot from its history and wav; history, count and pair advanced; meta written
+void launch_rate_in(const RateArgs& a, const SlotCounts& c, int fin, const PcmIn& wav /*finish: p = NULL*/, const ResampleTable& t, float* xin,
+                    long xs, hipStream_t s);
+// out [S][ncols]: column j < c (finish: < DR) is sample P + j - DR (finish: L - DR + j) at rate R summed from the enhanced history, xout
+// (the inner push's output, its column i = inner sample ready(P) + i - DM) and, at finish, xfin (the inner finish's DM columns); exactly 0
+// where that index is negative and in every other column; the enhanced history advanced (push)
+void launch_rate_out(const RateArgs& a, const ResampleTable& t /*M -> R*/, const float* xout, long xs, const float* xfin, long fs,
+                     const PcmOut& out, int ncols, hipStream_t s);
 
 // resample.hip
 // out[b][m] = y_b[m] for m < the row's output count, exactly 0 from there to `cols`; one launch per kLenRows rows.

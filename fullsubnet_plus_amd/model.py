@@ -616,7 +616,8 @@ class _HipModel(nn.Module):
         """The rate in Hz the model's weights were trained at and its STFT runs at: `sr` of [acoustics] in the reference's TOML, 16000
         unless assigned.  enhance_wave(..., sample_rate=R), resample and reserve(..., sample_rate=R) convert between R and this rate
         (include/fsnp_resample.h).  Held in Python and passed with every call; assigning validates (ValueError unless a positive
-        integer) and touches no GPU.  Sessions take no rate: they run at this one."""
+        integer) and touches no GPU.  open_wave_stream(..., sample_rate=R) opens a wave session that converts inside every push
+        (include/fsnp_wave_rate_stream.h); spectrum and stream sessions see no samples and take no rate."""
         return self.__dict__.get("_sample_rate", 16000)
 
     @sample_rate.setter
@@ -1216,7 +1217,7 @@ class FullSubNet_Plus(_HipModel):
         from .stream import PLUS_REASON
         raise NotImplementedError(f"{self.__class__.__name__}.open_stream: {PLUS_REASON}")
 
-    def open_wave_stream(self, slots, max_samples=4096, device="cuda", live=False):
+    def open_wave_stream(self, slots, max_samples=4096, device="cuda", live=False, sample_rate=None):
         """FullSubNet+ is not streamable (see fullsubnet_plus_amd.stream): always raises NotImplementedError with the reason."""
         from .stream import PLUS_REASON
         raise NotImplementedError(f"{self.__class__.__name__}.open_wave_stream: {PLUS_REASON}")
@@ -1330,18 +1331,32 @@ class FullSubNet(_HipModel):
             raise NotImplementedError(f"{self.__class__.__name__}.open_stream: {why}")
         return Stream(self, slots, max_chunk, _resolve_device(device), live=live)
 
-    def open_wave_stream(self, slots, max_samples=4096, device="cuda", live=False):
+    def open_wave_stream(self, slots, max_samples=4096, device="cuda", live=False, sample_rate=None):
         """-> fullsubnet_plus_amd.stream.WaveStream: `slots` independent live audio streams, blocks of up to max_samples samples in, as
         many enhanced samples out at the fixed delay n_fft + look_ahead * hop_length (include/fsnp_wave_stream.h; (2 + look_ahead) * hop
         in the default geometry).  The session runs at the model's hop_length of this moment and keeps it.  All push outputs of a clip
         followed by finish(), without the first `delay` samples, are enhance_wave() of that clip alone.  The refusals of open_stream
         apply (NotImplementedError with the reason, before any GPU is touched).  live=True: the model inside runs as a live session
         (see open_stream); max_samples / hop + 1 frames per push must then be <= 16, e.g. max_samples = hop for one hop per push, and so
-        must the ceil(n_fft / (2 hop)) + look_ahead frames of a finish."""
-        from .stream import WaveStream, wave_refusal
+        must the ceil(n_fft / (2 hop)) + look_ahead frames of a finish.
+
+        sample_rate (include/fsnp_wave_rate_stream.h): None or self.sample_rate is the session as it has always been.  Any other rate
+        in Hz -> fullsubnet_plus_amd.stream.WaveRateStream: blocks at that rate in, as many samples at that rate out, converted to and
+        from self.sample_rate on the device inside every push by the filter of enhance_wave(..., sample_rate=); max_samples then counts
+        at that rate, and so does the session's `delay` (68 ms at 48 kHz where the model's own is 64 ms).  A live session's 16 frames
+        per call apply to the model-rate samples a push turns into (`model_max_samples`): at 48 kHz, hop 256 and one 10 ms block per
+        push, max_samples = 480.  ValueError, before any GPU is touched, for a rate that is no positive integer or a ratio with
+        max(up, down) > 640."""
+        from .stream import WaveRateStream, WaveStream, wave_refusal
+        what = f"{self.__class__.__name__}.open_wave_stream"
         why = wave_refusal(self)
         if why is not None:
-            raise NotImplementedError(f"{self.__class__.__name__}.open_wave_stream: {why}")
+            raise NotImplementedError(f"{what}: {why}")
+        if sample_rate is not None:
+            resample_plan(sample_rate, self.sample_rate, what)
+            resample_plan(self.sample_rate, sample_rate, what)
+            if _rate(sample_rate, what) != self.sample_rate:
+                return WaveRateStream(self, slots, max_samples, _resolve_device(device), live=live, sample_rate=int(sample_rate))
         return WaveStream(self, slots, max_samples, _resolve_device(device), live=live)
 
     def open_spec_stream(self, slots, max_chunk=16, device="cuda", live=False):

@@ -12,6 +12,11 @@ and the same for waveforms (include/fsnp_wave_stream.h): samples in, samples out
     ...
     out = wave.finish()                      # [8, wave.delay]: the clips' last samples; the slots are reset
 
+and for samples at another rate than the model's (include/fsnp_wave_rate_stream.h): the same session between two streaming converters.
+
+    wave = model.open_wave_stream(slots=1, max_samples=480, live=True, sample_rate=48000)
+    out = wave.push(block)                   # [1, 480] at 48 kHz -> [1, 480] at 48 kHz, wave.delay = 3264 samples (68 ms) late
+
 and for a caller who owns the STFT (include/fsnp_spec_stream.h): noisy complex frames in, enhanced complex frames out, look_ahead late.
 
     spec = model.open_spec_stream(slots=8, max_chunk=16)
@@ -113,11 +118,15 @@ class _Session:
         create = f"{self._prefix}_create_live" if live else f"{self._prefix}_create"
         sp = ctypes.c_void_p()
         with torch.cuda.device(device):
-            _lib.check(getattr(lib, create)(model._hip.handle, self.slots, int(limit), ctypes.byref(sp)), create)
+            _lib.check(getattr(lib, create)(model._hip.handle, self.slots, int(limit), *self._create_extra(), ctypes.byref(sp)), create)
         self._st, self._backup = sp, None
         self.state_bytes = int(self._state_bytes(sp))
 
     # ------------------------------------------------------------------ plumbing
+    def _create_extra(self):
+        """what the session's create call takes between its limit and its out pointer"""
+        return ()
+
     def _session(self):
         if self._st is None:
             raise RuntimeError("this stream is closed")
@@ -287,12 +296,13 @@ class WaveStream(_Session):
     waits and polls, as forward does).  load_state takes what state() of a slot of any wave session of a model of the same sizes
     returned and is a migration call here: it waits once for the copy, to learn the slot's sample count."""
     _prefix, _opener = "fsnp_wave_stream", "open_wave_stream"
+    _f32_calls = True                # the session has fp32 entry points next to the _pcm ones
 
     def __init__(self, model, slots, max_samples, device, live=False):
         self.hop_length = self.hop = int(model.hop_length)       # (the C session is created from the handle's hop: _ensure_handle set it)
         super().__init__(model, slots, max_samples, device, live)
         self.max_samples = int(max_samples)
-        self.delay, self.live = int(self._lib.fsnp_wave_stream_delay(self._st)), bool(live)
+        self.delay, self.live = int(getattr(self._lib, f"{self._prefix}_delay")(self._st)), bool(live)
 
     @staticmethod
     def _out_format(out_format, default, where):
@@ -327,7 +337,7 @@ class WaveStream(_Session):
         if n > 1 and x.stride(1) < 1:
             x = x.contiguous()
         cnt = None if counts is None else _host_lengths(counts, S, "WaveStream.push")
-        if x.dtype == torch.float32 and ofmt == _lib.SAMPLE_F32 and (n == 1 or x.stride(1) == 1):
+        if self._f32_calls and x.dtype == torch.float32 and ofmt == _lib.SAMPLE_F32 and (n == 1 or x.stride(1) == 1):
             out = torch.empty((S, n), dtype=torch.float32, device=self.device)
 
             def enqueue():
@@ -336,12 +346,13 @@ class WaveStream(_Session):
             return self._guarded(enqueue, out, "fsnp_wave_stream_push")
         ifmt = _lib.SAMPLE_S16 if x.dtype == torch.int16 else _lib.SAMPLE_F32
         out = torch.empty((S, n), dtype=torch.float32 if ofmt == _lib.SAMPLE_F32 else torch.int16, device=self.device)
+        push_pcm = getattr(self._lib, f"{self._prefix}_push_pcm")
 
         def enqueue_pcm():
             with torch.cuda.device(self.device):
-                return self._lib.fsnp_wave_stream_push_pcm(st, x.data_ptr(), ifmt, x.stride(0), max(x.stride(1), 1), cnt, out.data_ptr(), ofmt,
-                                                           n, 1, n, self._cuda_stream())
-        return self._guarded(enqueue_pcm, out, "fsnp_wave_stream_push_pcm")
+                return push_pcm(st, x.data_ptr(), ifmt, x.stride(0), max(x.stride(1), 1), cnt, out.data_ptr(), ofmt, n, 1, n,
+                                self._cuda_stream())
+        return self._guarded(enqueue_pcm, out, f"{self._prefix}_push_pcm")
 
     def finish(self, slots=None, out_format=None):
         """End the clips of `slots` (None: all) -> [slots, delay]: each clip's last `delay` samples (exactly 0 where the clip is shorter);
@@ -351,23 +362,47 @@ class WaveStream(_Session):
         ofmt = self._out_format(out_format, "f32", "finish")
         st = self._session()
         arr, num = _slot_array(slots)
-        if ofmt == _lib.SAMPLE_F32:
+        if self._f32_calls and ofmt == _lib.SAMPLE_F32:
             out = torch.empty((self.slots, self.delay), dtype=torch.float32, device=self.device)
 
             def enqueue():
                 with torch.cuda.device(self.device):
                     return self._lib.fsnp_wave_stream_finish(st, arr, num, out.data_ptr(), self.delay, self._cuda_stream())
             return self._guarded(enqueue, out, "fsnp_wave_stream_finish")
-        out = torch.empty((self.slots, self.delay), dtype=torch.int16, device=self.device)
+        out = torch.empty((self.slots, self.delay), dtype=torch.float32 if ofmt == _lib.SAMPLE_F32 else torch.int16, device=self.device)
+        finish_pcm = getattr(self._lib, f"{self._prefix}_finish_pcm")
 
         def enqueue_pcm():
             with torch.cuda.device(self.device):
-                return self._lib.fsnp_wave_stream_finish_pcm(st, arr, num, out.data_ptr(), ofmt, self.delay, 1, self._cuda_stream())
-        return self._guarded(enqueue_pcm, out, "fsnp_wave_stream_finish_pcm")
+                return finish_pcm(st, arr, num, out.data_ptr(), ofmt, self.delay, 1, self._cuda_stream())
+        return self._guarded(enqueue_pcm, out, f"{self._prefix}_finish_pcm")
 
     def samples(self, slot):
         """Samples pushed into `slot` since its last reset or finish (host-side count)."""
         return self._counter("samples", slot)
+
+
+class WaveRateStream(WaveStream):
+    """A WaveStream whose samples arrive, and leave, at `sample_rate` instead of the model's (include/fsnp_wave_rate_stream.h; open one
+    through FullSubNet.open_wave_stream(..., sample_rate=R)): a wave session at model.sample_rate between two streaming converters, the
+    filter of enhance_wave(..., sample_rate=R) run push by push on the device.  Same interface as WaveStream - int16 and strided input,
+    out_format, counts, finish, state / load_state, samples, the model's error policy; `max_samples`, `delay` and samples() count at
+    `sample_rate`.  `delay` = ceil((model_delay * down + 2 half + 1) / up) - 1, the smallest at which every push returns as many
+    samples as it took (3264 samples = 68 ms at 48 kHz against the model's 64 ms, at n_fft 512, hop 256, look_ahead 2).
+    `model_max_samples` and `model_delay` are the inner session's.  All push outputs of a clip followed by finish(), without the first
+    `delay` samples, are enhance_wave(clip, sample_rate=sample_rate) of that clip alone, whatever the block sizes.  A state loads into
+    a session of the same rate pair only."""
+    _prefix, _opener = "fsnp_wave_rate_stream", "open_wave_stream"
+    _f32_calls = False               # one push and one finish: fp32 is FSNP_SAMPLE_F32 of the _pcm calls
+
+    def __init__(self, model, slots, max_samples, device, live=False, sample_rate=None):
+        self.sample_rate, self.model_rate = int(sample_rate), int(model.sample_rate)
+        super().__init__(model, slots, max_samples, device, live)
+        self.model_delay = int(self._lib.fsnp_wave_rate_stream_model_delay(self._st))
+        self.model_max_samples = int(self._lib.fsnp_wave_rate_stream_model_max_samples(self._st))
+
+    def _create_extra(self):
+        return (self.sample_rate, self.model_rate)
 
 
 class SpecStream(_FrameSession):

@@ -315,4 +315,5 @@ int32_t fsnp_config_size(void);
 #include "fsnp_stft_geometry.h" /* the hop length of the waveform path (n_fft = 2 (num_freqs - 1), periodic Hann of n_fft) */
 #include "fsnp_pcm.h" /* 16-bit PCM and strided samples at the boundary of the waveform path and of wave sessions */
 #include "fsnp_resample.h" /* the whole-clip waveform path at any input sample rate, converted on the device */
+#include "fsnp_wave_rate_stream.h" /* wave sessions at any input sample rate: a wave session between two streaming converters */
 #endif /* FSNP_H */

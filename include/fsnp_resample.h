@@ -2,7 +2,8 @@
  * fsnp_resample.h - the whole-clip waveform path at any input sample rate: samples in at the caller's rate, samples out at the
  * caller's rate, converted to and from the model's rate on the device.  Part of the public surface of libfsnp_hip.so next to fsnp.h
  * (which includes this header), same FSNP_ABI_VERSION.  The kernels' side is in DESIGN.md ("Sample rates"), a 48 kHz serving call in
- * INTEGRATION.md.  Whole-clip calls only: wave, spectrum and stream sessions run at the model's rate and take no rate.
+ * INTEGRATION.md.  Whole-clip calls here; wave sessions at another rate are fsnp_wave_rate_stream.h (this filter, push by push);
+ * spectrum and stream sessions see no samples and take no rate.
  *
  * The converter is ONE filter, a rational polyphase FIR with zero phase.  For from_rate -> to_rate:
  *

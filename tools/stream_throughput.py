@@ -26,6 +26,13 @@ push that does the same on the device.  One JSON line per cell and session mode 
 min and max of the --runs timed runs, per push.
 
     python tools/stream_throughput.py --spec --live [--slots 1 8 64] [--chunks 1 4]
+
+--rate times rate sessions (FullSubNet.open_wave_stream(..., live=True, sample_rate=R): 10 ms of audio at R per push, converted to and
+from the model's rate inside the push) next to the model-rate live wave session fed the same 10 ms as 160-sample pushes.  All sessions
+of one S are open at once and take turns run by run, so drift of the machine falls on all of them alike; one JSON line per S and
+session: median with min and max of the --runs timed runs, per push.  --rates without a value times the model-rate session alone.
+
+    python tools/stream_throughput.py --rate [--slots 1 8] [--rates 48000 44100 8000] [--runs 7] [--pushes 50]
 """
 import argparse
 import json
@@ -96,6 +103,38 @@ def wave_mode(model, a):
         print(json.dumps(rec))
 
 
+def rate_mode(model, a):
+    """10 ms pushes: the model-rate live wave session and a live rate session per rate in a.rates, alternating run by run"""
+    for S in a.slots:
+        wav = torch.from_numpy(make_wave(S, 2.0, 3)).cuda()
+        sessions = {}
+        try:
+            for rate in [model.sample_rate] + list(a.rates):
+                c = rate // 100
+                assert a.pushes * c <= wav.shape[1], "--pushes: 2 s of audio per slot"
+                kw = {} if rate == model.sample_rate else {"sample_rate": rate}
+                ws = model.open_wave_stream(S, max_samples=c, live=True, **kw)
+                sessions[rate] = (ws, [wav[:, k * c:(k + 1) * c].contiguous() for k in range(a.pushes)], [])
+            for rnd in range(a.runs + 1):                              # round 0 warms every session up
+                for rate, (ws, blocks, runs) in sessions.items():
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for blk in blocks:
+                        ws.push(blk)
+                    torch.cuda.synchronize()
+                    if rnd:
+                        runs.append((time.perf_counter() - t0) / a.pushes)
+            base = statistics.median(sessions[model.sample_rate][2])
+            for rate, (ws, blocks, runs) in sessions.items():
+                med = statistics.median(runs)
+                print(json.dumps({"slots": S, "sample_rate": rate, "samples_per_push": rate // 100, "delay_ms": round(1e3 * ws.delay / rate, 2),
+                                  "ms_per_push": round(med * 1e3, 4), "ms_per_push_min_max": [round(min(runs) * 1e3, 4), round(max(runs) * 1e3, 4)],
+                                  "minus_model_rate_ms": round((med - base) * 1e3, 4), "real_time_streams": round(10e-3 / med * S, 1)}))
+        finally:
+            for ws, _, _ in sessions.values():
+                ws.close()
+
+
 def recipe_push(model, st, X, counts, lengths, delay):
     """One push of a mag session with the other half of a spectrum session written out in torch: -> enhanced [S, F, n] complex64.
     delay[b]: the noisy frames of slot b that have no mask yet, complex [F, <= look_ahead] (frames P - w .. P - 1)."""
@@ -161,6 +200,8 @@ def main():
     ap.add_argument("--wave", action="store_true", help="time wave sessions (hop-sized pushes) next to the mag push of one frame")
     ap.add_argument("--spec", action="store_true", help="time spectrum sessions next to the mag push and the host-side loop they replace")
     ap.add_argument("--live", action="store_true", help="time a live session beside the default one in every cell of n <= 16 frames")
+    ap.add_argument("--rate", action="store_true", help="time live rate sessions (10 ms per push) next to the model-rate live wave session")
+    ap.add_argument("--rates", type=int, nargs="*", default=[48000, 44100, 8000], help="--rate: the sample rates (none: the model-rate session alone)")
     ap.add_argument("--slots", type=int, nargs="+", default=[1, 8, 32, 64])
     ap.add_argument("--chunks", type=int, nargs="+", default=[1, 4, 16, 64])
     ap.add_argument("--runs", type=int, default=5)
@@ -174,6 +215,10 @@ def main():
     model.error_check = "deferred"
 
     with torch.no_grad():
+        if a.rate:
+            rate_mode(model, a)
+            model.check_errors()
+            return
         if a.wave:
             wave_mode(model, a)
             model.check_errors()
