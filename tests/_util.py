@@ -140,6 +140,30 @@ def oracle_stages(sd, ins, args, dtype=torch.float64):
     return out
 
 
+FB_LSTM_K, FB_LSTM_CAP, FB_LSTM_FLOOR = 8, 2e-5, 2.0 ** -23
+
+
+def fullband_lstm_bound(e32, k=FB_LSTM_K):
+    """What tests/test_gpu_fullband_lstm.py allows plane_errs(hip, oracle64) of one fb_mag plane of the original FullSubNet, given e32 =
+    plane_errs(oracle32, oracle64) of that plane: k times the float32 oracle's own error (floored at one fp32 spacing of the plane's
+    maximum, below which e32 is luck), never beyond what the suite asserts of every recurrent kernel in dense mode."""
+    return min(k * max(e32, FB_LSTM_FLOOR), FB_LSTM_CAP)
+
+
+@torch.no_grad()
+def oracle_fullband_fullsubnet(sd, mag, args, dtype=torch.float64):
+    """The full-band stage of fsnp_torch.forward_fullsubnet alone (pad by look_ahead, norm, the two-layer recurrent fb_model, Linear,
+    activation), evaluated in `dtype` with the fb_model.* weights and the input cast to it: mag [B, 1, F, T] ->
+    {"fb_mag": [B, F, T + look_ahead]}."""
+    from oracle import fsnp_torch
+    p = {k: v.to(dtype) for k, v in sd.items() if k.startswith("fb_model.")}
+    x = torch.nn.functional.pad(mag.to(dtype), [0, args["look_ahead"]])
+    B, C, F, T = x.shape
+    assert C == 1
+    fb_input = fsnp_torch.NORMS[args["norm_type"]](x).reshape(B, F, T)
+    return {"fb_mag": fsnp_torch.lstm2_fc(fb_input, p, "fb_model", args["fb_output_activate_function"])}
+
+
 @torch.no_grad()
 def oracle_subband(sd, stages, args, dtype, drop_band=False, record=None):
     """The sub-band half of fsnp_torch.forward / forward_fullsubnet alone (oracle/fsnp_torch.py: unfold with reflect padding,

@@ -13,7 +13,7 @@ from fullsubnet_plus_amd import FullSubNet
 from oracle import fsnp_torch
 from oracle.ref_loader import FULLSUBNET_MODEL_ARGS
 from oracle.weights import make_inputs, make_state_dict_fullsubnet
-from tests._util import Golden, golden_names, rel_err
+from tests._util import FB_LSTM_CAP, Golden, golden_names, rel_err
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-3
@@ -63,7 +63,7 @@ def test_fullsubnet_forward_vs_reference_golden(name):
     _record(f"forward_{name}", **rec)
     assert err < TOL, rec
     if "fb_stage" in rec:
-        assert rec["fb_stage"] < 2e-4, rec
+        assert rec["fb_stage"] < FB_LSTM_CAP, rec      # (<= 8.5e-7 measured; tests/test_gpu_fullband_lstm.py checks the stage per kernel path)
     if "full" in g.arrays:
         m.batch_mode = "full"
         full = m(_cuda(mag)).cpu().numpy()
