@@ -36,6 +36,7 @@
 
 #include "fsnp_common.h"
 #include "lstm_common.h"
+#include "rowtile.h"
 
 namespace fsnp {
 
@@ -127,7 +128,7 @@ __device__ __forceinline__ void lstm_cell(f32x16 (&acc)[4 * ST], f32x2 (&c)[ST][
 #pragma unroll
     for (int s = 0; s < ST; ++s) {
         const int k = wave * UW + s * 32 + (lane & 31);
-        const int kbase = (((k >> 3) * 64) + ((k & 1) * 32)) * 4 + ((k >> 1) & 3);
+        const int kbase = a_frag_col(k);
 #pragma unroll
         for (int r = 0; r < 16; r += 2) {                  // two cells per pass: packed fp32 math (lstm_common.h)
             // element-wise AGPR reads: handed `f32x2{acc[..][r], acc[..][r + 1]}` hipcc copies whole 16-register tiles to VGPRs
@@ -246,22 +247,24 @@ void lstm2_fc_kernel(LstmWeights w, LstmArgs a) {
     constexpr int RT = 32 + EX;                 // row slots per tile
     constexpr int EXA = EX > 0 ? EX : 1;
 
+    // LDS: RowTileLds (rowtile.h).  BF (bf16-ih variant): the layer-0 bias is FOLDED into the product - input slot k = NIN (one of the
+    // zero-padded columns of the x image) holds the constant 1, the weight column k = NIN holds b_ih0 + b_hh0 (weight_layouts.h,
+    // PK_ROWTILE_BF) - so the bias table holds layer 1 only: the 6 KB that frees are what the second (lo) bf16 image of h0_t needs to
+    // fit a CU's 160 KB next to the fp32 images
+    using L = RowTileLds<32, HID, KX, EX, NW, BF>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    float4* Xs = reinterpret_cast<float4*>(smem_raw);   // [KGX][64]           A image of x_t (rows 0..31)
-    float4* H0s = Xs + KGX * 64;                         // [KGH][64]           h0
-    float4* H1s = H0s + KGH * 64;                        // [KGH][64]           h1
-    float4* XEs = H1s + KGH * 64;                        // [KGX][2][EX]        E image of x_t (extra rows)
-    float4* HE0s = XEs + KGX * 2 * EX;                   // [KGH][2][EX]
-    float4* HE1s = HE0s + KGH * 2 * EX;                  // [KGH][2][EX]
-    float4* Wfc4 = HE1s + KGH * 2 * EX;                  // [OUT][KGH][2]
-    RowDesc* rows_s = reinterpret_cast<RowDesc*>(Wfc4 + OUT * KGH * 2);  // [RT]
-    // BF (bf16-ih variant): the layer-0 bias is FOLDED into the product - input slot k = NIN (one of the zero-padded columns of the x
-    // image) holds the constant 1, the weight column k = NIN holds b_ih0 + b_hh0 (weight_layouts.h, PK_ROWTILE_BF) - so the table holds layer 1
-    // only: the 6 KB that frees are what the second (lo) bf16 image of h0_t needs to fit a CU's 160 KB next to the fp32 images
-    constexpr int BL = BF ? 1 : 2;                                       // bias layers in LDS
-    constexpr bool HILO = BF && EX == 0;                                 // h0_t as bf16 hi + lo (VALU-row tiles: hi only, the E images take the room)
-    float* Bs = reinterpret_cast<float*>(rows_s + RT);                   // [BL][NW][NT][32]
-    float4* H0b = reinterpret_cast<float4*>(Bs + BL * NW * NT * 32);     // BF: [hi | lo][KSB][64] bf16 A images of h0_t (h = hi + lo)
+    float4* Xs = reinterpret_cast<float4*>(smem_raw + L::x);
+    float4* H0s = reinterpret_cast<float4*>(smem_raw + L::h0);
+    float4* H1s = reinterpret_cast<float4*>(smem_raw + L::h1);
+    float4* XEs = reinterpret_cast<float4*>(smem_raw + L::xe);
+    float4* HE0s = reinterpret_cast<float4*>(smem_raw + L::he0);
+    float4* HE1s = reinterpret_cast<float4*>(smem_raw + L::he1);
+    float4* Wfc4 = reinterpret_cast<float4*>(smem_raw + L::fc);
+    RowDesc* rows_s = reinterpret_cast<RowDesc*>(smem_raw + L::rows);
+    float* Bs = reinterpret_cast<float*>(smem_raw + L::bias);
+    float4* H0b = reinterpret_cast<float4*>(smem_raw + L::h0b);
+    constexpr int BL = L::BL;                       // bias layers in LDS
+    constexpr bool HILO = L::HB == 2;               // h0_t as bf16 hi + lo (VALU-row tiles: hi only, the E images take the room)
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -274,19 +277,18 @@ void lstm2_fc_kernel(LstmWeights w, LstmArgs a) {
     // ... and EVERY workgroup folds its own duration into a maximum / minimum (one 64-bit atomic each at the very end): the launch lasts as
     // long as its slowest workgroup, and the chip's XCDs do not hold the same clock (profiles/r06_box_variance.md)
     __shared__ unsigned long long clk_s[2];
+    static_assert(L::fits(sizeof(clk_s)), "the tile's LDS image must fit a CU");
     if (a.clk != nullptr && tid == 0) {
         clk_s[1] = __builtin_amdgcn_s_memrealtime();
         clk_s[0] = __builtin_amdgcn_s_memtime();
         if (blockIdx.x == 0) { a.clk[0] = clk_s[0]; a.clk[1] = clk_s[1]; a.clk[4] = 0ull; a.clk[5] = 0ull; a.clk[6] = ~0ull; }
     }
 
-    for (int i = tid; i < (KGX + 2 * KGH) * (64 + 2 * EX); i += NTHR) Xs[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int i = tid; i < OUT * KGH * 2; i += NTHR) {
-        const int o = i / (KGH * 2), kg = (i >> 1) % KGH, kh = i & 1;
-        const float* wr = w.wfc + (size_t)o * HID + kg * 8 + kh;
-        Wfc4[i] = make_float4(wr[0], wr[2], wr[4], wr[6]);
-    }
+    for (int i = tid; i < L::state_f4; i += NTHR) Xs[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    rowtile_fill_fc<HID, NTHR>(Wfc4, w.wfc, tid);
     if (tid < RT) rows_s[tid] = a.rows[slot0 + tid];
+    // (this kernel keeps its own bias table fill, gather and accumulator fill: with rowtile.h's, hipcc spills other registers in the
+    // 12-wave and VALU-row instantiations - profiles/rowtile_shared.md)
     for (int i = tid; i < BL * NW * NT * 32; i += NTHR) {
         const int col = i & 31, n = (i >> 5) % NT, wv = (i / (32 * NT)) % NW, layer = BF ? 1 : i / (32 * NT * NW);
         Bs[i] = w.bias[layer * 4 * HID + (n / ST) * HID + wv * UW + (n % ST) * 32 + col];
@@ -380,33 +382,16 @@ void lstm2_fc_kernel(LstmWeights w, LstmArgs a) {
         mfma_groups<NT, EX>(acc_, accx_, breg, A_, AE_, ng, ws, gnext, KGT);
     };
 
-    // FC lane mapping (rows 0..31): 8 rows x 2 outputs x 4 k-parts per wave
-    const int fc_row = (wave & 3) * 8 + (lane & 7);
-    const int fc_o = (lane >> 3) & 1;
-    const int fc_kp = lane >> 4;
-    const RowDesc fc_rd = rows_s[fc_row];
-    // FC lane mapping (extra row e = wave): output = lane >> 5, k = (lane & 31) + 32 i
+    // Linear (rows 0..31): RowTileFc; (extra row e = wave): output = lane >> 5, k = (lane & 31) + 32 i
+    const RowTileFc<HID> fc(wave, lane);
+    const RowDesc fc_rd = rows_s[fc.row];
     const RowDesc fcx_rd = (EX > 0 && wave < EX) ? rows_s[32 + (wave < EX ? wave : 0)] : RowDesc{0, 0, 0, 0};
 
     auto fc_store = [&](int t_of_h) {
-      if (wave < 4) {
-        constexpr int KGP = KGH / 4;
-        float sum = 0.0f;
-#pragma unroll 4
-        for (int kk = 0; kk < KGP; ++kk) {
-            const int kg = fc_kp * KGP + kk;
-#pragma unroll
-            for (int kh = 0; kh < 2; ++kh) {
-                const float4 h4 = H1s[kg * 64 + kh * 32 + fc_row];
-                const float4 w4 = Wfc4[(fc_o * KGH + kg) * 2 + kh];
-                sum += h4.x * w4.x + h4.y * w4.y + h4.z * w4.z + h4.w * w4.w;
-            }
+        if (wave < 4) {
+            const float sum = fc.sum(H1s, Wfc4);
+            if (fc.kp == 0 && fc_rd.valid && t_of_h >= a.LA) fc.store(w, a, fc_rd, sum, t_of_h - a.LA);
         }
-        sum += __shfl_xor(sum, 16);
-        sum += __shfl_xor(sum, 32);
-        if (fc_kp == 0 && fc_rd.valid && t_of_h >= a.LA)
-            a.out[(size_t)fc_rd.out_off + (size_t)fc_o * a.out_stride_o + (t_of_h - a.LA)] = apply_act(sum + w.bfc[fc_o], a.act);
-      }
         if (EX > 0 && wave < EX) {
             const int o = lane >> 5;
             const float* he = reinterpret_cast<const float*>(HE1s);
@@ -527,9 +512,7 @@ void lstm2_fc_kernel(LstmWeights w, LstmArgs a) {
 template <int EX, int NW, bool BF, int KX, int HID = 384>
 static void launch_lstm_ex(const LstmWeights& w, const LstmArgs& a, hipStream_t s) {
     constexpr int OUT = 2;
-    constexpr int KGX = KX / 8, KGH = HID / 8, NT = 4 * (HID / NW / 32);
-    const size_t smem = (size_t)(KGX + 2 * KGH) * (64 + 2 * EX) * 16 + (size_t)OUT * KGH * 2 * 16 +
-                        (32 + EX) * sizeof(RowDesc) + (size_t)(BF ? 1 : 2) * NW * NT * 32 * 4 + (BF ? (size_t)(EX == 0 ? 2 : 1) * (HID / 16) * 64 * 16 : 0);
+    constexpr size_t smem = RowTileLds<32, HID, KX, EX, NW, BF>::bytes();
     LstmWeights wv = w;
     wv.wpack = BF ? (NW == 12 ? w.wpack_bf[1] : w.wpack_bf[0]) : (NW == 12 ? w.wpack12 : w.wpack);
     if constexpr (KX == 40 && HID == 384) {          // the phase-profile variant exists for the default sizes only
@@ -579,9 +562,10 @@ void launch_lstm(const LstmWeights& w, const LstmArgs& a, hipStream_t s) {
 }
 
 // -------------------------------------------------------------------------------------------------
-// Streaming (include/fsnp_stream.h): lstm2_fc_kernel<HID, KX, 2, EX = 0, PROF = false, NW = 4, BF = false> - same LDS images, same weight
-// stream (LstmWeights::wpack), same k-group loops (mfma_groups<NT, 0>), same cells - as a kernel of its own, so that the whole-clip
-// instantiations stay byte for byte what they were.  What differs:
+// Streaming (include/fsnp_stream.h): the row-tile kernel from carried state.  lstm2_fc_stream_kernel is the shared scaffolding of
+// rowtile.h (LDS image, table fills, gather, Linear sum, accumulator fill) around the k-group loops (mfma_groups<NT, 0>) and cells
+// (lstm_cell) of lstm2_fc_kernel<HID, KX, 2, EX = 0, PROF = false, NW = 4, BF = false>, on the same weight stream (LstmWeights::wpack),
+// plus its three own parts: the step counts, stream_state_io and the store condition.
 //   * rows[].valid is the row's STEP COUNT of this push (Tp = the push's n is only the stride of the per-frame tables); the tile runs
 //     the largest count of its rows;
 //   * the rows' (h0, c0, h1, c1) enter and leave through the structures the kernel already has - c in lstm_cell's lane-local register
@@ -603,7 +587,7 @@ __device__ __forceinline__ void stream_state_io(f32x2 (&c0)[ST][8], f32x2 (&c1)[
 #pragma unroll
         for (int s = 0; s < ST; ++s) {
             const int k = wave * UW + s * 32 + (lane & 31);
-            const int hi = (((k >> 3) * 64) + ((k & 1) * 32)) * 4 + ((k >> 1) & 3) + row * 4;
+            const int hi = a_frag_col(k) + row * 4;
             if constexpr (LOAD) {
                 H0[hi] = on ? p[k] : 0.0f;
                 c0[s][r >> 1][r & 1] = on ? p[HID + k] : 0.0f;
@@ -622,36 +606,30 @@ __device__ __forceinline__ void stream_state_io(f32x2 (&c0)[ST][8], f32x2 (&c1)[
 template <int HID, int KX>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void lstm2_fc_stream_kernel(LstmWeights w, LstmArgs a) {
-    constexpr int NW = 4, NTHR = 256, OUT = 2;
+    constexpr int NW = 4, NTHR = 256;
     constexpr int UW = HID / NW, ST = UW / 32, NT = 4 * ST;
     constexpr int KGX = KX / 8, KGH = HID / 8, KG0 = KGX + KGH, KGT = KG0 + 2 * KGH;
     static_assert(UW % 32 == 0 && KGH % 4 == 0, "hidden/4 must be a multiple of 32");
 
+    using L = RowTileLds<32, HID, KX, 0, NW, false>;
+    static_assert(L::fits(0), "the tile's LDS image must fit a CU");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    float4* Xs = reinterpret_cast<float4*>(smem_raw);   // [KGX][64]   A image of x_t
-    float4* H0s = Xs + KGX * 64;                         // [KGH][64]   h0
-    float4* H1s = H0s + KGH * 64;                        // [KGH][64]   h1
-    float4* Wfc4 = H1s + KGH * 64;                       // [OUT][KGH][2]
-    RowDesc* rows_s = reinterpret_cast<RowDesc*>(Wfc4 + OUT * KGH * 2);  // [32]
-    float* Bs = reinterpret_cast<float*>(rows_s + 32);                   // [2][NW][NT][32]
+    float4* Xs = reinterpret_cast<float4*>(smem_raw + L::x);
+    float4* H0s = reinterpret_cast<float4*>(smem_raw + L::h0);
+    float4* H1s = reinterpret_cast<float4*>(smem_raw + L::h1);
+    float4* Wfc4 = reinterpret_cast<float4*>(smem_raw + L::fc);
+    RowDesc* rows_s = reinterpret_cast<RowDesc*>(smem_raw + L::rows);
+    float* Bs = reinterpret_cast<float*>(smem_raw + L::bias);
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int slot0 = blockIdx.x * 32;
-    const int Tp = a.Tp;
 
-    for (int i = tid; i < (KGX + 2 * KGH) * 64; i += NTHR) Xs[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int i = tid; i < OUT * KGH * 2; i += NTHR) {
-        const int o = i / (KGH * 2), kg = (i >> 1) % KGH, kh = i & 1;
-        const float* wr = w.wfc + (size_t)o * HID + kg * 8 + kh;
-        Wfc4[i] = make_float4(wr[0], wr[2], wr[4], wr[6]);
-    }
+    for (int i = tid; i < L::state_f4; i += NTHR) Xs[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    rowtile_fill_fc<HID, NTHR>(Wfc4, w.wfc, tid);
     if (tid < 32) rows_s[tid] = a.rows[slot0 + tid];
-    for (int i = tid; i < 2 * NW * NT * 32; i += NTHR) {
-        const int col = i & 31, n = (i >> 5) % NT, wv = (i / (32 * NT)) % NW, layer = i / (32 * NT * NW);
-        Bs[i] = w.bias[layer * 4 * HID + (n / ST) * HID + wv * UW + (n % ST) * 32 + col];
-    }
+    rowtile_fill_bias<32, 2, HID, NW, NTHR>(Bs, w.bias, tid);
     __syncthreads();
 
     // steps of this tile, and whether some row ends before the tile does (both uniform)
@@ -665,31 +643,11 @@ void lstm2_fc_stream_kernel(LstmWeights w, LstmArgs a) {
     const bool mixed = __builtin_amdgcn_readfirstlane(cmin < nsteps ? 1 : 0) != 0;
     if (nsteps <= 0) return;                                  // (uniform; the host never launches an empty tile)
 
-    // ---- gather plan: row = tid & 31, features j = (tid >> 5) + 8 i; 32-bit float offsets from att_mag; -1 = zero
-    constexpr int JSTEP = NTHR / 32, NG = (KX + JSTEP - 1) / JSTEP;
-    const int grow = tid & 31;
-    int goff[NG], xdst[NG];
-    const float* __restrict__ gbase = a.att_mag;
-    const int gstep = a.FP;
-    const NormMD* md_row;
-    {
-        const RowDesc rd = rows_s[grow];
-#pragma unroll
-        for (int i = 0; i < NG; ++i) {
-            const int j = (tid >> 5) + JSTEP * i;
-            goff[i] = j >= KX ? -2 : (rd.valid > 0 && j < w.NIN)
-                          ? sb_feature_offset(j, rd.f, rd.b * Tp * a.FP, a.F, a.NSBN, a.NFBN, a.fb_rel, a.fb_branch_stride) : -1;
-            xdst[i] = a_frag_index(grow, j < KX ? j : 0);
-        }
-        md_row = a.md_row + (size_t)(slot0 + grow) * Tp;      // (rows without steps: never dereferenced through goff >= 0)
-    }
-    float* Xf = reinterpret_cast<float*>(Xs);
-    {   // x(0)
-        const NormMD m0 = rows_s[grow].valid > 0 ? md_row[0] : NormMD{0.0f, 1.0f};
-#pragma unroll
-        for (int i = 0; i < NG; ++i)
-            if (goff[i] != -2) Xf[xdst[i]] = goff[i] >= 0 ? (gbase[goff[i]] - m0.m) / m0.d : 0.0f;
-    }
+    // ---- gather (rowtile.h), STREAM: valid > 0 is "the row has steps", the per-row norm table is always there
+    using Gather = RowTileGather<a_frag_index, 32, NTHR, KX, true>;
+    Gather gx;
+    gx.plan(w, a, rows_s, slot0, tid, reinterpret_cast<float*>(Xs));
+    gx.store_first();
 
     const float* __restrict__ bias_l0 = Bs + ((0 * NW + wave) * NT) * 32 + (lane & 31);
     const float* __restrict__ bias_l1 = Bs + ((1 * NW + wave) * NT) * 32 + (lane & 31);
@@ -709,28 +667,11 @@ void lstm2_fc_stream_kernel(LstmWeights w, LstmArgs a) {
         mfma_groups<NT, 0>(acc_, accx, breg, A_, A_, ng, ws, gnext, KGT);
     };
 
-    // FC lane mapping: 8 rows x 2 outputs x 4 k-parts per wave
-    const int fc_row = (wave & 3) * 8 + (lane & 7);
-    const int fc_o = (lane >> 3) & 1;
-    const int fc_kp = lane >> 4;
-    const RowDesc fc_rd = rows_s[fc_row];
+    const RowTileFc<HID> fc(wave, lane);
+    const RowDesc fc_rd = rows_s[fc.row];
     auto fc_store = [&](int t_of_h) {
-        constexpr int KGP = KGH / 4;
-        float sum = 0.0f;
-#pragma unroll 4
-        for (int kk = 0; kk < KGP; ++kk) {
-            const int kg = fc_kp * KGP + kk;
-#pragma unroll
-            for (int kh = 0; kh < 2; ++kh) {
-                const float4 h4 = H1s[kg * 64 + kh * 32 + fc_row];
-                const float4 w4 = Wfc4[(fc_o * KGH + kg) * 2 + kh];
-                sum += h4.x * w4.x + h4.y * w4.y + h4.z * w4.z + h4.w * w4.w;
-            }
-        }
-        sum += __shfl_xor(sum, 16);
-        sum += __shfl_xor(sum, 32);
-        if (fc_kp == 0 && t_of_h < fc_rd.valid)
-            a.out[(size_t)fc_rd.out_off + (size_t)fc_o * a.out_stride_o + t_of_h] = apply_act(sum + w.bfc[fc_o], a.act);
+        const float sum = fc.sum(H1s, Wfc4);
+        if (fc.kp == 0 && t_of_h < fc_rd.valid) fc.store(w, a, fc_rd, sum, t_of_h);
     };
 
     __syncthreads();
@@ -738,36 +679,22 @@ void lstm2_fc_stream_kernel(LstmWeights w, LstmArgs a) {
     for (int t = 0; t < nsteps; ++t) {
         // prefetch x(t+1) (consumed after the layer-0 MFMA phase); past a row's own count it reads the zeros / identity the push's
         // repack and prefix kernels wrote there, and whatever the full-band stages left: that row's results are dropped
-        float xr[NG];
-        NormMD mdn = {0.0f, 1.0f};
+        float xr[Gather::NG];
+        NormMD mdn = gx.md;
         const bool have_next = (t + 1 < nsteps);
-        if (have_next) {
-            if (rows_s[grow].valid > 0) mdn = md_row[t + 1];
-#pragma unroll
-            for (int i = 0; i < NG; ++i) xr[i] = goff[i] >= 0 ? gbase[goff[i] + (t + 1) * gstep] : 0.0f;
-        }
+        if (have_next) gx.prefetch(t + 1, xr, mdn);
 
         f32x16 acc[NT];
         // ---------------- layer 0: [x_t | h0_{t-1}] ----------------
-#pragma unroll
-        for (int n = 0; n < NT; ++n)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[n][r] = bias_l0[n * 32];
+        acc_from_bias<32>(acc, bias_l0);
         run_groups(acc, Xs + lane, KG0);
         __syncthreads();
         lstm_cell<ST, UW>(acc, c0, reinterpret_cast<float*>(H0s), wave, lane);
-        if (have_next) {
-#pragma unroll
-            for (int i = 0; i < NG; ++i)
-                if (goff[i] != -2) Xf[xdst[i]] = goff[i] >= 0 ? (xr[i] - mdn.m) / mdn.d : 0.0f;
-        }
+        if (have_next) gx.store_next(xr, mdn);
         if (t > 0) fc_store(t - 1);
         __syncthreads();
         // ---------------- layer 1: [h1_{t-1} | h0_t] ----------------
-#pragma unroll
-        for (int n = 0; n < NT; ++n)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[n][r] = bias_l1[n * 32];
+        acc_from_bias<32>(acc, bias_l1);
         run_groups(acc, H1s + lane, KGH);
         run_groups(acc, H0s + lane, KGH);
         __syncthreads();
@@ -782,8 +709,7 @@ void lstm2_fc_stream_kernel(LstmWeights w, LstmArgs a) {
 
 template <int HID, int KX>
 static void launch_lstm_stream_one(const LstmWeights& w, const LstmArgs& a, hipStream_t s) {
-    constexpr int KGX = KX / 8, KGH = HID / 8, NT = 4 * (HID / 4 / 32);
-    const size_t smem = (size_t)(KGX + 2 * KGH) * 64 * 16 + (size_t)2 * KGH * 2 * 16 + 32 * sizeof(RowDesc) + (size_t)2 * 4 * NT * 32 * 4;
+    constexpr size_t smem = RowTileLds<32, HID, KX, 0, 4, false>::bytes();
     auto kern = lstm2_fc_stream_kernel<HID, KX>;
     static PerDeviceOnce attr_once;
     attr_once.run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); });

@@ -15,6 +15,7 @@
 
 #include "fsnp_common.h"
 #include "lstm_common.h"
+#include "rowtile.h"
 
 namespace fsnp {
 
@@ -136,14 +137,16 @@ void lstm2_fc16_kernel(LstmWeights w, LstmArgs a) {
     constexpr int XP = KGX * 16;
     static_assert(!BF || HID % 32 == 0, "bf16 k-steps");
 
+    using L = RowTileLds<16, HID, KX, 0, NW, BF>;
+    static_assert(L::fits(0), "the tile's LDS image must fit a CU");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    float4* Xs = reinterpret_cast<float4*>(smem_raw);   // [KGX][64] A image of x_t
-    float4* H0s = Xs + KGX * 64;                         // [KGH][64]
-    float4* H1s = H0s + KGH * 64;                        // [KGH][64]
-    float* Wfc = reinterpret_cast<float*>(H1s + KGH * 64);               // [OUT][HID]
-    RowDesc* rows_s = reinterpret_cast<RowDesc*>(Wfc + OUT * HID);       // [16]
-    float* Bs = reinterpret_cast<float*>(rows_s + 16);                   // [2][NW][NT][16]
-    float4* H0b = reinterpret_cast<float4*>(Bs + 2 * NW * NT * 16);      // BF: [hi | lo][KSB][64] bf16 A images of h0_t
+    float4* Xs = reinterpret_cast<float4*>(smem_raw + L::x);
+    float4* H0s = reinterpret_cast<float4*>(smem_raw + L::h0);
+    float4* H1s = reinterpret_cast<float4*>(smem_raw + L::h1);
+    float* Wfc = reinterpret_cast<float*>(smem_raw + L::fc);
+    RowDesc* rows_s = reinterpret_cast<RowDesc*>(smem_raw + L::rows);
+    float* Bs = reinterpret_cast<float*>(smem_raw + L::bias);
+    float4* H0b = reinterpret_cast<float4*>(smem_raw + L::h0b);
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -151,47 +154,16 @@ void lstm2_fc16_kernel(LstmWeights w, LstmArgs a) {
     const int slot0 = blockIdx.x * 16;
     const int Tp = a.Tp;
 
-    for (int i = tid; i < (KGX + 2 * KGH) * 64; i += 256) Xs[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int i = tid; i < L::state_f4; i += 256) Xs[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int i = tid; i < OUT * HID; i += 256) Wfc[i] = w.wfc[i];
     if (tid < 16) rows_s[tid] = a.rows[slot0 + tid];
-    for (int i = tid; i < 2 * NW * NT * 16; i += 256) {
-        const int col = i & 15, n = (i >> 4) % NT, wv = (i / (16 * NT)) % NW, layer = i / (16 * NT * NW);
-        Bs[i] = w.bias[layer * 4 * HID + (n / SB) * HID + wv * UW + (n % SB) * 16 + col];
-    }
+    rowtile_fill_bias<16, 2, HID, NW, 256>(Bs, w.bias, tid);
     __syncthreads();
 
-    // ---- gather plan: thread owns row = tid & 15, features j = (tid >> 4) + 16 i
-    const bool dense = a.dense != nullptr;
-    const float* __restrict__ gbase = dense ? a.dense : a.att_mag;
-    const int gstep = dense ? w.NIN : a.FP;
-    constexpr int NG = XP / 16;
-    const int grow = tid & 15;
-    int goff[NG], xdst[NG];
-    NormMD md = {0.0f, 1.0f};
-    const NormMD* md_row = nullptr;
-    {
-        const RowDesc rd = rows_s[grow];
-#pragma unroll
-        for (int i = 0; i < NG; ++i) {
-            const int j = (tid >> 4) + 16 * i;
-            int off = -1;
-            if (rd.valid && j < w.NIN)
-                off = dense ? rd.b * Tp * w.NIN + j
-                            : sb_feature_offset(j, rd.f, rd.b * Tp * a.FP, a.F, a.NSBN, a.NFBN, a.fb_rel, a.fb_branch_stride);
-            goff[i] = off;
-            xdst[i] = a16_index(grow, j);
-        }
-        if (!dense && rd.valid) {
-            if (a.md_row != nullptr) md_row = a.md_row + (size_t)(slot0 + grow) * Tp;
-            else md = a.md_utt[rd.b];
-        }
-    }
-    float* Xf = reinterpret_cast<float*>(Xs);
-    {
-        const NormMD m0 = md_row ? md_row[0] : md;
-#pragma unroll
-        for (int i = 0; i < NG; ++i) Xf[xdst[i]] = goff[i] >= 0 ? (gbase[goff[i]] - m0.m) / m0.d : 0.0f;
-    }
+    using Gather = RowTileGather<a16_index, 16, 256, XP, false>;
+    Gather gx;
+    gx.plan(w, a, rows_s, slot0, tid, reinterpret_cast<float*>(Xs));
+    gx.store_first();
 
     const float* __restrict__ bias_l0 = Bs + ((0 * NW + wave) * NT) * 16 + (lane & 15);
     const float* __restrict__ bias_l1 = Bs + ((1 * NW + wave) * NT) * 16 + (lane & 15);
@@ -237,20 +209,13 @@ void lstm2_fc16_kernel(LstmWeights w, LstmArgs a) {
     __syncthreads();
 
     for (int t = 0; t < Tp; ++t) {
-        float xr[NG];
-        NormMD mdn = md;
+        float xr[Gather::NG];
+        NormMD mdn = gx.md;
         const bool have_next = (t + 1 < Tp);
-        if (have_next) {                                    // prefetch x(t+1)
-            if (md_row) mdn = md_row[t + 1];
-#pragma unroll
-            for (int i = 0; i < NG; ++i) xr[i] = goff[i] >= 0 ? gbase[goff[i] + (t + 1) * gstep] : 0.0f;
-        }
+        if (have_next) gx.prefetch(t + 1, xr, mdn);     // x(t+1) (consumed after the layer-0 MFMA phase)
         f32x4 acc[NT];
         // ---------------- layer 0: [x_t | h0_{t-1}] ----------------
-#pragma unroll
-        for (int n = 0; n < NT; ++n)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[n][r] = bias_l0[n * 16];
+        acc_from_bias<16>(acc, bias_l0);
 #pragma unroll
         for (int n = 0; n < NT; ++n) asm volatile("" : "+a"(acc[n]));
         groups16<NT>(acc, breg, Xs + lane, KGX, ws, gnext, KGT);
@@ -259,17 +224,11 @@ void lstm2_fc16_kernel(LstmWeights w, LstmArgs a) {
         groups16<NT>(acc, breg, H0s + lane, KGH, ws, gnext, KGT);
         __syncthreads();
         cell16<SB, UW, KSB * 64 * 8>(acc, c0, reinterpret_cast<float*>(H0s), wave, lane, BF ? reinterpret_cast<unsigned short*>(H0b) : nullptr);
-        if (have_next) {
-#pragma unroll
-            for (int i = 0; i < NG; ++i) Xf[xdst[i]] = goff[i] >= 0 ? (xr[i] - mdn.m) / mdn.d : 0.0f;
-        }
+        if (have_next) gx.store_next(xr, mdn);
         if (t > 0) fc_store(t - 1);
         __syncthreads();
         // ---------------- layer 1: [h1_{t-1} | h0_t] ----------------
-#pragma unroll
-        for (int n = 0; n < NT; ++n)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[n][r] = bias_l1[n * 16];
+        acc_from_bias<16>(acc, bias_l1);
 #pragma unroll
         for (int n = 0; n < NT; ++n) asm volatile("" : "+a"(acc[n]));   // pin the tiles to AGPRs: left alone, hipcc moves them to VGPRs and back
                                                                         // inside one of the k-loops (124 v_accvgpr moves per k-group)
@@ -297,9 +256,7 @@ void lstm2_fc16_kernel(LstmWeights w, LstmArgs a) {
 template <bool BF>
 static void launch_lstm16_bf(const LstmWeights& w, const LstmArgs& a, hipStream_t s) {
     constexpr int HID = 384, KX = 40, OUT = 2;
-    constexpr int KGX = (KX + 15) / 16, KGH = HID / 16, NT = 4 * (HID / 4 / 16);
-    const size_t smem = (size_t)(KGX + 2 * KGH) * 64 * 16 + (size_t)OUT * HID * 4 + 16 * sizeof(RowDesc) + (size_t)2 * 4 * NT * 16 * 4 +
-                        (BF ? (size_t)2 * (HID / 32) * 64 * 16 : 0);
+    constexpr size_t smem = RowTileLds<16, HID, KX, 0, 4, BF>::bytes();
     LstmWeights wv = w;
     wv.wpack = BF ? w.wpack16_bf : w.wpack16;
     if constexpr (!BF) {

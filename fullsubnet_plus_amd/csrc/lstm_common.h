@@ -92,10 +92,13 @@ __device__ __forceinline__ float apply_act(float v, int act) {
     return v;
 }
 
-// float index of A element (row, k) inside an A-fragment-ordered LDS matrix
-__host__ __device__ __forceinline__ int a_frag_index(int row, int k) {
+// float index of A element (row, k) inside an A-fragment-ordered LDS matrix ([k-group][k parity][row][4 k-pairs])
+__host__ __device__ __forceinline__ constexpr int a_frag_index(int row, int k) {
     return (((k >> 3) * 64) + ((k & 1) * 32) + row) * 4 + ((k >> 1) & 3);
 }
+// the base of column k (its row 0), which the cells compute once per unit: a row is 4 floats further
+__host__ __device__ __forceinline__ constexpr int a_frag_col(int k) { return a_frag_index(0, k); }
+static_assert(a_frag_index(5, 77) == a_frag_col(77) + 5 * 4 && a_frag_index(31, 383) == a_frag_col(383) + 31 * 4, "rows are 4 floats apart");
 
 
 // ---- per-row-tile exchange region of the column-split kernels, in float4 units (HIMG = (HID / 8) * 64 = one 32 x HID image

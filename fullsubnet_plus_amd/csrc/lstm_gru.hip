@@ -16,6 +16,7 @@
 // k-group, so a step costs 3/4 of the LSTM's matrix-pipe time.  The per-unit register state is h itself.
 #include "fsnp_common.h"
 #include "lstm_common.h"
+#include "rowtile.h"
 
 namespace fsnp {
 
@@ -53,7 +54,7 @@ __device__ __forceinline__ void gru_cell(f32x16 (&acc)[4 * ST], f32x16 (&hreg)[S
 #pragma unroll
     for (int s = 0; s < ST; ++s) {
         const int k = wave * UW + s * 32 + (lane & 31);
-        const int kbase = (((k >> 3) * 64) + ((k & 1) * 32)) * 4 + ((k >> 1) & 3);
+        const int kbase = a_frag_col(k);
 #pragma unroll
         for (int r = 0; r < 16; r += 2) {                  // two cells per pass: packed fp32 math (lstm_common.h gru_cell_pair)
             auto rd = [](float v) { float o; asm("v_accvgpr_read_b32 %0, %1" : "=v"(o) : "a"(v)); return o; };   // (see lstm.hip lstm_cell)
@@ -80,13 +81,15 @@ void gru2_fc_kernel(LstmWeights w, LstmArgs a) {
     constexpr int KGX = KX / 8, KGH = HID / 8, KG0 = KGX + KGH, KGT = KG0 + 2 * KGH;
     static_assert(KGH % 4 == 0, "FC k-split");
 
+    using L = RowTileLds<32, HID, KX, 0, NW, false>;
+    static_assert(L::fits(0), "the tile's LDS image must fit a CU");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    float4* Xs = reinterpret_cast<float4*>(smem_raw);   // [KGX][64]  A image of x_t
-    float4* H0s = Xs + KGX * 64;                         // [KGH][64]  h0
-    float4* H1s = H0s + KGH * 64;                        // [KGH][64]  h1
-    float4* Wfc4 = H1s + KGH * 64;                       // [OUT][KGH][2]
-    RowDesc* rows_s = reinterpret_cast<RowDesc*>(Wfc4 + OUT * KGH * 2);  // [32]
-    float* Bs = reinterpret_cast<float*>(rows_s + 32);                   // [2][NW][NT][32]
+    float4* Xs = reinterpret_cast<float4*>(smem_raw + L::x);
+    float4* H0s = reinterpret_cast<float4*>(smem_raw + L::h0);
+    float4* H1s = reinterpret_cast<float4*>(smem_raw + L::h1);
+    float4* Wfc4 = reinterpret_cast<float4*>(smem_raw + L::fc);
+    RowDesc* rows_s = reinterpret_cast<RowDesc*>(smem_raw + L::rows);
+    float* Bs = reinterpret_cast<float*>(smem_raw + L::bias);
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -94,55 +97,16 @@ void gru2_fc_kernel(LstmWeights w, LstmArgs a) {
     const int slot0 = blockIdx.x * 32;
     const int Tp = a.Tp;
 
-    for (int i = tid; i < (KGX + 2 * KGH) * 64; i += NTHR) Xs[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int i = tid; i < OUT * KGH * 2; i += NTHR) {
-        const int o = i / (KGH * 2), kg = (i >> 1) % KGH, kh = i & 1;
-        const float* wr = w.wfc + (size_t)o * HID + kg * 8 + kh;
-        Wfc4[i] = make_float4(wr[0], wr[2], wr[4], wr[6]);
-    }
+    for (int i = tid; i < L::state_f4; i += NTHR) Xs[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    rowtile_fill_fc<HID, NTHR>(Wfc4, w.wfc, tid);
     if (tid < 32) rows_s[tid] = a.rows[slot0 + tid];
-    for (int i = tid; i < 2 * NW * NT * 32; i += NTHR) {     // biases: four slots r, z, n_x, n_h per unit (fsnp_abi.hip: expand)
-        const int col = i & 31, n = (i >> 5) % NT, wv = (i / (32 * NT)) % NW, layer = i / (32 * NT * NW);
-        Bs[i] = w.bias[layer * 4 * HID + (n / ST) * HID + wv * UW + (n % ST) * 32 + col];
-    }
+    rowtile_fill_bias<32, 2, HID, NW, NTHR>(Bs, w.bias, tid);      // four slots r, z, n_x, n_h per unit (fsnp_abi.hip: expand)
     __syncthreads();
 
-    // ---- gather plan (as lstm.hip): thread owns row = tid & 31, features j = (tid >> 5) + (NTHR / 32) i
-    const bool dense = a.dense != nullptr;
-    const float* __restrict__ gbase = dense ? a.dense : a.att_mag;
-    const int gstep = dense ? w.NIN : a.FP;
-    constexpr int JSTEP = NTHR / 32, NG = (KX + JSTEP - 1) / JSTEP;
-    const int grow = tid & 31;
-    int goff[NG], xdst[NG];
-    NormMD md = {0.0f, 1.0f};
-    const NormMD* md_row = nullptr;
-    {
-        const RowDesc rd = rows_s[grow];
-#pragma unroll
-        for (int i = 0; i < NG; ++i) {
-            const int j = (tid >> 5) + JSTEP * i;
-            int off = -2;                                   // -2: this thread has no element i; -1: zero
-            if (j < KX) {
-                off = -1;
-                if (rd.valid && j < w.NIN)
-                    off = dense ? rd.b * Tp * w.NIN + j
-                                : sb_feature_offset(j, rd.f, rd.b * Tp * a.FP, a.F, a.NSBN, a.NFBN, a.fb_rel, a.fb_branch_stride);
-            }
-            goff[i] = off;
-            xdst[i] = a_frag_index(grow, j < KX ? j : 0);
-        }
-        if (!dense && rd.valid) {
-            if (a.md_row != nullptr) md_row = a.md_row + (size_t)(slot0 + grow) * Tp;
-            else md = a.md_utt[rd.b];
-        }
-    }
-    float* Xf = reinterpret_cast<float*>(Xs);
-    {
-        const NormMD m0 = md_row ? md_row[0] : md;
-#pragma unroll
-        for (int i = 0; i < NG; ++i)
-            if (goff[i] != -2) Xf[xdst[i]] = goff[i] >= 0 ? (gbase[goff[i]] - m0.m) / m0.d : 0.0f;
-    }
+    using Gather = RowTileGather<a_frag_index, 32, NTHR, KX, false>;
+    Gather gx;
+    gx.plan(w, a, rows_s, slot0, tid, reinterpret_cast<float*>(Xs));
+    gx.store_first();
 
     const float* __restrict__ bias_l0 = Bs + ((0 * NW + wave) * NT) * 32 + (lane & 31);
     const float* __restrict__ bias_l1 = Bs + ((1 * NW + wave) * NT) * 32 + (lane & 31);
@@ -160,46 +124,26 @@ void gru2_fc_kernel(LstmWeights w, LstmArgs a) {
     for (int n = 0; n < NL; ++n) breg[n] = wload<NL>(ws, 0, n);
     int gnext = 1;
 
-    // Linear: 8 rows x 2 outputs x 4 k-parts per wave (waves 0..3)
-    const int fc_row = (wave & 3) * 8 + (lane & 7);
-    const int fc_o = (lane >> 3) & 1;
-    const int fc_kp = lane >> 4;
-    const RowDesc fc_rd = rows_s[fc_row];
+    const RowTileFc<HID> fc(wave, lane);
+    const RowDesc fc_rd = rows_s[fc.row];
     auto fc_store = [&](int t_of_h) {
         if (wave < 4) {
-            constexpr int KGP = KGH / 4;
-            float sum = 0.0f;
-#pragma unroll 4
-            for (int kk = 0; kk < KGP; ++kk) {
-                const int kg = fc_kp * KGP + kk;
-#pragma unroll
-                for (int kh = 0; kh < 2; ++kh) {
-                    const float4 h4 = H1s[kg * 64 + kh * 32 + fc_row];
-                    const float4 w4 = Wfc4[(fc_o * KGH + kg) * 2 + kh];
-                    sum += h4.x * w4.x + h4.y * w4.y + h4.z * w4.z + h4.w * w4.w;
-                }
-            }
-            sum += __shfl_xor(sum, 16);
-            sum += __shfl_xor(sum, 32);
-            if (fc_kp == 0 && fc_rd.valid && t_of_h >= a.LA)
-                a.out[(size_t)fc_rd.out_off + (size_t)fc_o * a.out_stride_o + (t_of_h - a.LA)] = apply_act(sum + w.bfc[fc_o], a.act);
+            const float sum = fc.sum(H1s, Wfc4);
+            if (fc.kp == 0 && fc_rd.valid && t_of_h >= a.LA) fc.store(w, a, fc_rd, sum, t_of_h - a.LA);
         }
     };
 
     __syncthreads();
 
     for (int t = 0; t < Tp; ++t) {
-        float xr[NG];
-        NormMD mdn = md;
+        float xr[Gather::NG];
+        NormMD mdn = gx.md;
         const bool have_next = (t + 1 < Tp);
-        if (have_next) {                                    // prefetch x(t+1) (consumed after the layer-0 MFMA phase)
-            if (md_row) mdn = md_row[t + 1];
-#pragma unroll
-            for (int i = 0; i < NG; ++i) xr[i] = goff[i] >= 0 ? gbase[goff[i] + (t + 1) * gstep] : 0.0f;
-        }
+        if (have_next) gx.prefetch(t + 1, xr, mdn);     // x(t+1) (consumed after the layer-0 MFMA phase)
 
         f32x16 acc[NT];
         // ---------------- layer 0: input x_t (r, z, n_x), then h0_{t-1} (r, z, n_h) ----------------
+        // (the accumulator fill stays written out: as rowtile.h's acc_from_bias it costs this kernel 8 registers at K = 64)
 #pragma unroll
         for (int n = 0; n < NT; ++n)
 #pragma unroll
@@ -208,11 +152,7 @@ void gru2_fc_kernel(LstmWeights w, LstmArgs a) {
         gru_groups<ST, true>(acc, breg, H0s + lane, KGH, ws, gnext, KGT);
         __syncthreads();
         gru_cell<ST, UW>(acc, h0r, reinterpret_cast<float*>(H0s), wave, lane);
-        if (have_next) {
-#pragma unroll
-            for (int i = 0; i < NG; ++i)
-                if (goff[i] != -2) Xf[xdst[i]] = goff[i] >= 0 ? (xr[i] - mdn.m) / mdn.d : 0.0f;
-        }
+        if (have_next) gx.store_next(xr, mdn);
         if (t > 0) fc_store(t - 1);
         __syncthreads();
         // ---------------- layer 1: h1_{t-1} (r, z, n_h), then its input h0_t (r, z, n_x) ----------------
@@ -239,8 +179,7 @@ void gru2_fc_kernel(LstmWeights w, LstmArgs a) {
 template <int KX>
 static void launch_gru_kx(const LstmWeights& w, const LstmArgs& a, hipStream_t s) {
     constexpr int HID = 384, OUT = 2, NW = 4;
-    constexpr int KGX = KX / 8, KGH = HID / 8, NT = 4 * (HID / NW / 32);
-    const size_t smem = (size_t)(KGX + 2 * KGH) * 64 * 16 + (size_t)OUT * KGH * 2 * 16 + 32 * sizeof(RowDesc) + (size_t)2 * NW * NT * 32 * 4;
+    constexpr size_t smem = RowTileLds<32, HID, KX, 0, NW, false>::bytes();
     auto kern = gru2_fc_kernel<HID, KX, OUT, NW>;
     static PerDeviceOnce attr_once;
     attr_once.run([&] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); });

@@ -153,7 +153,9 @@ case("generic_fbn6", kernels=("lstm2_generic_kernel",), B=1, T=10, over=dict(fb_
 case("hidden256_rt", [P(0, 257, 9)], B=1, coop=0, over=dict(sb_model_hidden_size=256), host=False)
 case("hidden256_column_split", kernels=("lstm2_coop",), B=1, over=dict(sb_model_hidden_size=256), costs=None)
 case("hidden512_column_split", kernels=("lstm2_coop",), B=1, over=dict(sb_model_hidden_size=512), costs=None)
+case("hidden256_fbn2_rt", [P(0, 257, 9)], B=1, coop=0, over=dict(sb_model_hidden_size=256, fb_num_neighbors=2), host=False)   # (H = 256 at K = 64)
 case("gru_rt", [P(0, 257, 9)], B=1, coop=0, over=dict(sequence_model="GRU"), host=False)
+case("gru_fbn2_rt", [P(0, 257, 9)], B=1, coop=0, over=dict(sequence_model="GRU", fb_num_neighbors=2), host=False)             # (the GRU at K = 64)
 case("gru_ks16", [P(1, 257, 9, par=16)], B=1, costs="ks16", over=dict(sequence_model="GRU"), host=False, differs_from="gru_rt")
 case("tcn_f161_b1", kernels=("sub-band TCN",), B=1, T=8, F=161, over=dict(sequence_model="TCN"), costs=None)      # (the oracle's TCN costs 25 ms per sequence)
 case("output3_generic", kernels=("lstm2_generic_kernel",), B=1, T=10, over=dict(output_size=3))          # (the tuned kernels write two outputs)

@@ -168,6 +168,22 @@ def test_tile_and_round_edges(slots):
 
 
 # ------------------------------------------------------------------------------------------------ independence, reset, migration
+@pytest.mark.parametrize("sb_hidden,fb_neighbors", [(256, 0), (384, 5), (256, 5)])
+def test_other_row_tile_sizes(sb_hidden, fb_neighbors):
+    """The other instantiations of the streaming row-tile kernel (csrc/lstm.hip lstm2_fc_stream_kernel): sb_model_hidden_size 256, and
+    fb_num_neighbors 5 (42 sub-band inputs: K = 64), at S = 2 with pushes of different counts per slot."""
+    args = _args("cumulative_laplace_norm", sb_model_hidden_size=sb_hidden, fb_num_neighbors=fb_neighbors)
+    sd = make_state_dict_fullsubnet(29, "default", sb_hidden=sb_hidden, fb_num_neighbors=fb_neighbors)
+    clips = [make_spec(1, 9, 450 + b)[0] for b in range(2)]
+    m = _model(args, sd)
+    with m.open_stream(2, max_chunk=4) as st:
+        got = _feed(st, clips, [[1, 4, 1, 3], [4, 0, 2, 3]], 2)
+        m.check_errors()
+    for b in range(2):
+        want = fsnp_torch.forward_fullsubnet_full(sd, clips[b], **stream_kwargs(args))[0]
+        _check(f"sb hidden {sb_hidden}, fb neighbours {fb_neighbors}, slot {b}", got[b], want, 2)
+
+
 def test_slots_are_independent_and_reset_starts_a_fresh_clip():
     args = _args("cumulative_laplace_norm")
     sd = make_state_dict_fullsubnet(24, "default")

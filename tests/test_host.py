@@ -311,6 +311,26 @@ def test_lstm_hot_loops_have_no_scratch_or_drain():
                 assert l["drain"] == 0, (key, l)
 
 
+def test_gru_hot_loops_have_no_scratch_or_drain():
+    """Static check of gru2_fc_kernel's gfx950 assembly (tools/check_lstm_asm.py analyse_gru), both instantiations: every k-group loop
+    is 3 live tiles x 3 blocks of 32 units x 4 MFMAs with one 16-byte refill per tile, no scratch and no vmcnt(0) drain; the kernel
+    spills nothing, has no scratch anywhere, and uses 224 AGPRs (what the parent commit's assembly shows)."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("check_lstm_asm", os.path.join(ROOT, "tools", "check_lstm_asm.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    res = mod.analyse_gru()
+    assert sorted(res) == ["KX40", "KX64"]
+    for key, k in res.items():
+        assert len(k["loops"]) >= 3, (key, k["loops"])          # the loops over h0 (layer 0), h1 and h0 (layer 1); hipcc may unroll the one over x
+        for l in k["loops"]:
+            assert l["mfma"] == 36 and l["gload"] == 9, (key, l)
+            assert l["scratch"] == 0 and l["drain"] == 0, (key, l)
+        assert k["vgpr_spill_count"] == 0 and k["sgpr_spill_count"] == 0, (key, k)
+        assert k["private_segment_fixed_size"] == 0 and k["scratch_total"] == 0, (key, k)
+        assert k["agpr_count"] == 224 and k["vgpr_count"] <= 512, (key, k)
+
+
 def test_groupnorm_fold_algebra_of_the_dma_sconv_gemm():
     """The identity csrc/tcn.hip's tcn_gemm_dma_kernel<EPI_RESIDUAL> relies on (weights and constants packed by fsnp_create in
     fsnp_abi.hip pack_tcn):  sum_k ((a_k - m) r g_k + b_k) W[n][k] + bias[n] = r * sum_k a_k (g_k W[n][k]) + c1[n] - r m c2[n]

@@ -11,37 +11,55 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "fullsubnet_plus_amd", "csrc", "lstm.hip")
+CSRC = os.path.join(ROOT, "fullsubnet_plus_amd", "csrc")
+
+
+def _asm(source, flags):
+    """gfx950 assembly of csrc/<source>, compiled as the build does"""
+    with tempfile.TemporaryDirectory() as td:
+        out = os.path.join(td, "k.s")
+        subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", *flags, "-S", "--cuda-device-only", os.path.join(CSRC, source), "-o", out],
+                       check=True, capture_output=True)
+        return open(out).read()
+
+
+def _kernel_meta(text, name):
+    """the integer fields of kernel `name` in the code object metadata at the end of the assembly (.vgpr_count, ...)"""
+    for entry in re.split(r"^  - (?=\.)", text[text.index("amdhsa.kernels:"):], flags=re.M)[1:]:
+        if re.search(r"^    \.name:\s+" + re.escape(name) + r"$", entry, re.M):
+            return {k: int(v) for k, v in re.findall(r"^    \.(\w+):\s+(\d+)$", "    " + entry, re.M)}
+    raise KeyError(name)
+
+
+def _kgroup_loops(body, **extra):
+    """The depth-2 loops of a kernel body (lines) that hold an MFMA - the k-group loops - each as counts of MFMAs, scratch accesses,
+    full vmcnt(0) drains, 16-byte weight loads and instructions, plus one count per extra name=pattern."""
+    pats = dict(mfma=r"v_mfma", scratch=r"scratch_", drain=r"vmcnt\(0\)", gload=r"global_load_dwordx4|buffer_load_dwordx4", **extra)
+    loops = []
+    for i, l in enumerate(body):
+        if "Inner Loop Header: Depth=2" not in l:
+            continue
+        lab = None
+        for k in range(i, max(i - 4, 0), -1):
+            mm = re.match(r"^(\.LBB\d+_\d+):", body[k])
+            if mm:
+                lab = mm.group(1)
+                break
+        end = next(k for k in range(i, len(body)) if re.search(r"s_cbranch_\w+ " + re.escape(lab) + r"\b", body[k]))
+        seg = body[i:end]
+        loops.append(dict({name: sum(1 for x in seg if re.search(pat, x)) for name, pat in pats.items()}, lines=len(seg)))
+    return [l for l in loops if l["mfma"] > 0]
 
 
 def analyse(flags=("-fno-slp-vectorize",)):
-    with tempfile.TemporaryDirectory() as td:
-        out = os.path.join(td, "lstm.s")
-        cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", *flags, "-S", "--cuda-device-only", SRC, "-o", out]
-        subprocess.run(cmd, check=True, capture_output=True)
-        text = open(out).read()
+    text = _asm("lstm.hip", flags)
     res = {}
     for m in re.finditer(r"^(_ZN4fsnp15lstm2_fc_kernelI\w+):[^\n]*\n(.*?)s_endpgm", text, re.S | re.M):
         name, body = m.group(1), m.group(2).split("\n")
         tag = re.search(r"Li(\d+)ELi(\d+)ELi2ELi(\d)ELb(\d)ELi(\d+)ELb(\d)E", name)
         key = (f"H{tag.group(1)}_" if tag.group(1) != "384" else "") + \
             f"KX{tag.group(2)}_EX{tag.group(3)}_PROF{tag.group(4)}_NW{tag.group(5)}_BF{tag.group(6)}"
-        loops = []
-        for i, l in enumerate(body):
-            if "Inner Loop Header: Depth=2" not in l:
-                continue
-            lab = None
-            for k in range(i, max(i - 4, 0), -1):
-                mm = re.match(r"^(\.LBB\d+_\d+):", body[k])
-                if mm:
-                    lab = mm.group(1)
-                    break
-            end = next(k for k in range(i, len(body)) if re.search(r"s_cbranch_\w+ " + re.escape(lab) + r"\b", body[k]))
-            seg = body[i:end]
-            cnt = lambda pat: sum(1 for x in seg if re.search(pat, x))
-            loops.append(dict(mfma=cnt(r"v_mfma"), scratch=cnt(r"scratch_"), drain=cnt(r"vmcnt\(0\)"),
-                              gload=cnt(r"global_load_dwordx4|buffer_load_dwordx4"), valu=cnt(r"\bv_fma|\bv_fmac"), lines=len(seg)))
-        res[key] = [l for l in loops if l["mfma"] > 0]
+        res[key] = _kgroup_loops(body, valu=r"\bv_fma|\bv_fmac")
     return res
 
 
@@ -50,32 +68,29 @@ def analyse_stream(text=None, flags=("-fno-slp-vectorize",)):
     facts as analyse() - to be compared with the whole-clip instantiation KX.._EX0_PROF0_NW4_BF0 of the same sizes - and where the
     kernel's scratch accesses are (none may sit inside a k-group loop)."""
     if text is None:
-        with tempfile.TemporaryDirectory() as td:
-            out = os.path.join(td, "lstm.s")
-            subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", *flags, "-S", "--cuda-device-only", SRC, "-o", out],
-                           check=True, capture_output=True)
-            text = open(out).read()
+        text = _asm("lstm.hip", flags)
     res = {}
     for m in re.finditer(r"^(_ZN4fsnp22lstm2_fc_stream_kernelI\w+):[^\n]*\n(.*?)s_endpgm", text, re.S | re.M):
         name, body = m.group(1), m.group(2).split("\n")
         tag = re.search(r"Li(\d+)ELi(\d+)E", name)
         key = (f"H{tag.group(1)}_" if tag.group(1) != "384" else "") + f"KX{tag.group(2)}_STREAM"
-        loops = []
-        for i, l in enumerate(body):
-            if "Inner Loop Header: Depth=2" not in l:
-                continue
-            lab = None
-            for k in range(i, max(i - 4, 0), -1):
-                mm = re.match(r"^(\.LBB\d+_\d+):", body[k])
-                if mm:
-                    lab = mm.group(1)
-                    break
-            end = next(k for k in range(i, len(body)) if re.search(r"s_cbranch_\w+ " + re.escape(lab) + r"\b", body[k]))
-            seg = body[i:end]
-            cnt = lambda pat: sum(1 for x in seg if re.search(pat, x))
-            loops.append(dict(mfma=cnt(r"v_mfma"), scratch=cnt(r"scratch_"), drain=cnt(r"vmcnt\(0\)"),
-                              gload=cnt(r"global_load_dwordx4|buffer_load_dwordx4"), valu=cnt(r"\bv_fma|\bv_fmac"), lines=len(seg)))
-        res[key] = dict(loops=[l for l in loops if l["mfma"] > 0], scratch_total=sum(1 for x in body if "scratch_" in x))
+        res[key] = dict(loops=_kgroup_loops(body, valu=r"\bv_fma|\bv_fmac"), scratch_total=sum(1 for x in body if "scratch_" in x))
+    return res
+
+
+def analyse_gru(text=None, flags=("-fno-slp-vectorize",)):
+    """gru2_fc_kernel (lstm_gru.hip), per instantiation KX..: the k-group loop facts of analyse() for every k-group loop hipcc keeps as a
+    loop (the three over h; per k-group three live tiles of 4 MFMAs per 32-unit block) and the kernel's register, spill and scratch
+    metadata."""
+    if text is None:
+        text = _asm("lstm_gru.hip", flags)
+    res = {}
+    for m in re.finditer(r"^(_ZN4fsnp14gru2_fc_kernelI\w+):[^\n]*\n(.*?)s_endpgm", text, re.S | re.M):
+        name, body = m.group(1), m.group(2).split("\n")
+        meta = _kernel_meta(text, name)
+        res["KX" + re.search(r"Li\d+ELi(\d+)E", name).group(1)] = dict(
+            loops=_kgroup_loops(body, valu=r"\bv_fma|\bv_fmac"), scratch_total=sum(1 for x in body if "scratch_" in x),
+            **{k: meta[k] for k in ("vgpr_count", "agpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size")})
     return res
 
 
@@ -85,12 +100,7 @@ def analyse_column_split(flags=("-fno-slp-vectorize",)):
     instructions (the write-through hand-off needs none), sc1 loads / stores of the exchange images, MFMAs."""
     res = {}
     for fn, sym in (("lstm_coop.hip", "_ZN4fsnp17lstm2_coop_kernelI"), ("lstm_coopn.hip", "_ZN4fsnp18lstm2_coopn_kernelI")):
-        with tempfile.TemporaryDirectory() as td:
-            out = os.path.join(td, "k.s")
-            src = os.path.join(ROOT, "fullsubnet_plus_amd", "csrc", fn)
-            subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", *flags, "-S", "--cuda-device-only", src, "-o", out],
-                           check=True, capture_output=True)
-            text = open(out).read()
+        text = _asm(fn, flags)
         for m in re.finditer(r"^(" + sym + r"\w+):[^\n]*\n(.*?)s_endpgm", text, re.S | re.M):
             name, body = m.group(1), m.group(2).split("\n")
             first_mfma = next(i for i, l in enumerate(body) if "v_mfma" in l)
@@ -106,12 +116,7 @@ def analyse_half_tile_ping_pong(flags=("-fno-slp-vectorize",)):
     """Whole-kernel invariants of lstm2_coop_hp_kernel (lstm_hp.hip), per instantiation: 16x16x4 MFMAs (and how many take their B
     operand - a resident weight - from an AGPR), scratch, cache maintenance, LDS-DMA operand loads (sc1), 16-byte sc1 stores of the
     exchange images, DPP row rotations (the Linear partial sums), ds_bpermute (must be none)."""
-    with tempfile.TemporaryDirectory() as td:
-        out = os.path.join(td, "k.s")
-        src = os.path.join(ROOT, "fullsubnet_plus_amd", "csrc", "lstm_hp.hip")
-        subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", *flags, "-S", "--cuda-device-only", src, "-o", out],
-                       check=True, capture_output=True)
-        text = open(out).read()
+    text = _asm("lstm_hp.hip", flags)
     res = {}
     for m in re.finditer(r"^(_ZN4fsnp20lstm2_coop_hp_kernelI\w+):[^\n]*\n(.*?)^\.Lfunc_end", text, re.S | re.M):
         name, body = m.group(1), m.group(2).split("\n")
@@ -127,12 +132,7 @@ def analyse_wave_owned(flags=("-fno-slp-vectorize",)):
     """lstm2_coopw_kernel (lstm_coopw.hip), per instantiation: the k-group loops (depth-2 loops with MFMAs: NT x 4 MFMAs and NT + 1
     16-byte loads per k-group, D groups per iteration, counted waits only - no drain, no scratch, no accumulator moves), and
     whole-kernel facts: no scratch anywhere, no cache maintenance, no workgroup barrier behind the first MFMA, 16-byte sc1 stores."""
-    with tempfile.TemporaryDirectory() as td:
-        out = os.path.join(td, "k.s")
-        src = os.path.join(ROOT, "fullsubnet_plus_amd", "csrc", "lstm_coopw.hip")
-        subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", *flags, "-S", "--cuda-device-only", src, "-o", out],
-                       check=True, capture_output=True)
-        text = open(out).read()
+    text = _asm("lstm_coopw.hip", flags)
     res = {}
     for m in re.finditer(r"^(_ZN4fsnp18lstm2_coopw_kernelI\w+):[^\n]*\n(.*?)^\.Lfunc_end", text, re.S | re.M):
         name, body = m.group(1), m.group(2).split("\n")
@@ -156,12 +156,7 @@ def analyse_wave_owned(flags=("-fno-slp-vectorize",)):
 def analyse_splitk_gemm(flags=("-fno-slp-vectorize",)):
     """tcn_gemm_sk_kernel (tcn.hip), per instantiation: one k-tile body per wave (16 MFMAs, 6 fragment reads, 6 DMA pieces + the 6 of the
     first tile), no scratch, and NO workgroup barrier between the first and the last MFMA (a wave waits for its own DMA only)."""
-    with tempfile.TemporaryDirectory() as td:
-        out = os.path.join(td, "k.s")
-        src = os.path.join(ROOT, "fullsubnet_plus_amd", "csrc", "tcn.hip")
-        subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", *flags, "-S", "--cuda-device-only", src, "-o", out],
-                       check=True, capture_output=True)
-        text = open(out).read()
+    text = _asm("tcn.hip", flags)
     res = {}
     for m in re.finditer(r"^(_ZN4fsnp18tcn_gemm_sk_kernel\w+):[^\n]*\n(.*?)^\.Lfunc_end", text, re.S | re.M):
         name, body = m.group(1), [l for l in m.group(2).split("\n") if l.strip() and not l.strip().startswith(";")]
@@ -174,12 +169,7 @@ def analyse_splitk_gemm(flags=("-fno-slp-vectorize",)):
 
 def analyse_generic(flags=("-fno-slp-vectorize",)):
     """lstm2_generic_kernel (lstm_generic.hip): fp32 FMAs only - no MFMA - and no scratch in any instantiation."""
-    with tempfile.TemporaryDirectory() as td:
-        out = os.path.join(td, "k.s")
-        src = os.path.join(ROOT, "fullsubnet_plus_amd", "csrc", "lstm_generic.hip")
-        subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", *flags, "-S", "--cuda-device-only", src, "-o", out],
-                       check=True, capture_output=True)
-        text = open(out).read()
+    text = _asm("lstm_generic.hip", flags)
     res = {}
     for m in re.finditer(r"^(_ZN4fsnp20lstm2_generic_kernelI\w+):[^\n]*\n(.*?)^\.Lfunc_end", text, re.S | re.M):
         name, body = m.group(1), m.group(2).split("\n")
@@ -191,43 +181,17 @@ def analyse_generic(flags=("-fno-slp-vectorize",)):
 def analyse_half_tile(flags=("-fno-slp-vectorize",)):
     """k-group loops of lstm2_fc16_kernel (lstm16.hip): MFMAs, weight loads, scratch, drains and AGPR<->VGPR moves per loop
     (hipcc once shuttled the 24 accumulator tiles through VGPRs inside one of the loops: 124 moves per k-group)."""
-    with tempfile.TemporaryDirectory() as td:
-        out = os.path.join(td, "k.s")
-        src = os.path.join(ROOT, "fullsubnet_plus_amd", "csrc", "lstm16.hip")
-        subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", *flags, "-S", "--cuda-device-only", src, "-o", out],
-                       check=True, capture_output=True)
-        text = open(out).read()
+    text = _asm("lstm16.hip", flags)
     res = {}
     for m in re.finditer(r"^(_ZN4fsnp17lstm2_fc16_kernelI\w+):[^\n]*\n(.*?)s_endpgm", text, re.S | re.M):
-        name, body = m.group(1), m.group(2).split("\n")
-        loops = []
-        for i, l in enumerate(body):
-            if "Inner Loop Header: Depth=2" not in l:
-                continue
-            lab = None
-            for k in range(i, max(i - 4, 0), -1):
-                mm = re.match(r"^(\.LBB\d+_\d+):", body[k])
-                if mm:
-                    lab = mm.group(1)
-                    break
-            end = next(k for k in range(i, len(body)) if re.search(r"s_cbranch_\w+ " + re.escape(lab) + r"\b", body[k]))
-            seg = body[i:end]
-            cnt = lambda pat: sum(1 for x in seg if re.search(pat, x))
-            loops.append(dict(mfma=cnt(r"v_mfma"), scratch=cnt(r"scratch_"), drain=cnt(r"vmcnt\(0\)"),
-                              gload=cnt(r"buffer_load_dwordx4"), acc_moves=cnt(r"v_accvgpr"), lines=len(seg)))
-        res[name] = [l for l in loops if l["mfma"] > 0]
+        res[m.group(1)] = _kgroup_loops(m.group(2).split("\n"), acc_moves=r"v_accvgpr")
     return res
 
 
 def analyse_dma_gemm(flags=("-fno-slp-vectorize",)):
     """k-loop of tcn_gemm_dma_kernel (tcn.hip), per instantiation: per k-tile 16 MFMAs, 6 ds_read_b128, 3 LDS-DMA loads and two
     offset selects - no ds_write, no scratch, no AGPR<->VGPR moves (counts over the span between the first and the last MFMA)."""
-    with tempfile.TemporaryDirectory() as td:
-        out = os.path.join(td, "k.s")
-        src = os.path.join(ROOT, "fullsubnet_plus_amd", "csrc", "tcn.hip")
-        subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", *flags, "-S", "--cuda-device-only", src, "-o", out],
-                       check=True, capture_output=True)
-        text = open(out).read()
+    text = _asm("tcn.hip", flags)
     res = {}
     for m in re.finditer(r"^(_ZN4fsnp19tcn_gemm_dma_kernel\w+):[^\n]*\n(.*?)s_endpgm", text, re.S | re.M):
         name, body = m.group(1), [l for l in m.group(2).split("\n") if l.strip() and not l.strip().startswith(";")]
@@ -250,12 +214,7 @@ def analyse_dma64_gemm(flags=("-fno-slp-vectorize",)):
     """tcn_gemm_dma64_kernel (tcn.hip, round 4): whole-kernel counts.  The k-loop body exists twice (two k-tiles per trip), each with 16
     MFMAs, 4 LDS-DMA pieces and 8 fragment reads (+ 4 reads of the VALU column's operands); no scratch, no AGPR<->VGPR moves; the epilogue
     moves 16-byte rows (4 residual loads + 4 stores per lane for the 64 x 64 tile, one float4 store per row of the VALU column)."""
-    with tempfile.TemporaryDirectory() as td:
-        out = os.path.join(td, "k.s")
-        src = os.path.join(ROOT, "fullsubnet_plus_amd", "csrc", "tcn.hip")
-        subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", *flags, "-S", "--cuda-device-only", src, "-o", out],
-                       check=True, capture_output=True)
-        text = open(out).read()
+    text = _asm("tcn.hip", flags)
     res = {}
     for m in re.finditer(r"^(_ZN4fsnp21tcn_gemm_dma64_kernel\w+):[^\n]*\n(.*?)^\.Lfunc_end", text, re.S | re.M):
         name, body = m.group(1), [l for l in m.group(2).split("\n") if l.strip() and not l.strip().startswith(";")]
@@ -281,6 +240,10 @@ if __name__ == "__main__":
         print(k, "scratch accesses in the whole kernel:", v["scratch_total"])
         for l in v["loops"]:
             print(k, l)
+    for k, v in analyse_gru().items():
+        print("gru", k, {n: x for n, x in v.items() if n != "loops"})
+        for l in v["loops"]:
+            print("gru", k, l)
     r = analyse()
     bad = 0
     for k in sorted(r):
