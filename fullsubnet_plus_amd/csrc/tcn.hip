@@ -68,11 +68,163 @@ __device__ __forceinline__ bool xcd_decode(int id, int inner, int units, int& un
 static int xcd_grid(int inner, int units) { return inner * ((units + 7) / 8 * 8); }
 
 constexpr int BM = 128, BK = 16;   // BN (32-column accumulator tiles per wave) is a template parameter
+constexpr int BMS = 32;            // rows of a split-K tile (tcn_gemm_sk_kernel)
+constexpr int BM64 = 64, BK64 = 32;   // tcn_gemm_dma64_kernel
+
+// ------------------------------------------------------------------------------------------------
+// ---- device helpers shared by the kernels of this file: each fact about a tile, the LDS image and the epilogues is stated once here
+
+// The output tile of workgroup blockIdx.x: ROWS rows [t0, t0 + ROWS) of utterance utt of one branch (a row tile never straddles
+// utterances), bn columns from n0.  ok == false: a padding id of the XCD order, the workgroup leaves.
+template <int ROWS>
+struct GemmTile {
+    int branch, utt, t0, n0, ntile, rows_valid;
+    bool ok;
+    __device__ __forceinline__ GemmTile(const GemmArgs& g, int bn) {
+        int row_tile_all;
+        ok = xcd_decode(blockIdx.x, g.ntiles_n, g.row_tiles_all, row_tile_all, ntile);
+        branch = row_tile_all / g.row_tiles;
+        const int row_tile = row_tile_all % g.row_tiles, tiles_per_utt = cdiv(g.Tp, ROWS);
+        utt = row_tile / tiles_per_utt;
+        t0 = (row_tile % tiles_per_utt) * ROWS;
+        n0 = ntile * bn;
+        rows_valid = min(ROWS, g.Tp - t0);
+    }
+};
+
+// The operand windows of a tile for the DMA kernels: buffer resources over the tile's valid rows of A and its bn rows of W.  Whatever
+// lies beyond a window (rows past the plane, the offset a_bytes itself) is out of range and reads as zeros: no bounds checks.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buffer_window(const float* p, int bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p), 0, bytes, 0x00020000);
+}
+struct DmaWindow { __amdgpu_buffer_rsrc_t ra, rw; int a_bytes; };
+template <int ROWS>
+__device__ __forceinline__ DmaWindow dma_window(const GemmArgs& g, const GemmTile<ROWS>& tl, int bn) {
+    const float* A = g.A + tl.branch * g.a_bs + ((long)tl.utt * g.Tp + tl.t0) * g.lda;
+    const float* W = g.W + tl.branch * g.w_bs + (long)tl.n0 * g.ldw;
+    const int a_bytes = tl.rows_valid * g.lda * 4;
+    return {buffer_window(A, a_bytes), buffer_window(W, bn * g.ldw * 4), a_bytes};
+}
+
+// The LDS image of a DMA k-tile: row-major [row][QUADS k-quads] float4 slots, XOR-swizzled on BOTH sides.  The DMA destination is
+// lane-linear (piece base + 16 bytes x lane), so the lane of slot s FETCHES what belongs there (`fetched`); readers apply the same
+// involution (`slot`).  swz spreads 16 consecutive rows of one k-quad over all 64 banks: ds_read_b128 is conflict-free.
+// (tests/test_host.py restates both images: test_dma_gemm_lds_image_is_a_conflict_free_permutation,
+// test_dma64_gemm_image_column_ownership_and_asm.)
+template <int QUADS>
+struct DmaImage {
+    static_assert(QUADS == 4 || QUADS == 8, "a k-tile is 16 or 32 deep");
+    static constexpr int LOG = QUADS == 4 ? 2 : 3;
+    struct Piece { int row, kq; };
+    static __device__ __forceinline__ int swz(int row) {
+        if constexpr (QUADS == 4) return (row >> 2) & 3;
+        else return (row >> 1) & 7;
+    }
+    static __device__ __forceinline__ Piece fetched(int s) { return {s >> LOG, (s & (QUADS - 1)) ^ swz(s >> LOG)}; }     // slot -> (row, k-quad)
+    static __device__ __forceinline__ int slot(int row, int kq) { return row * QUADS + (kq ^ swz(row)); }              // (row, k-quad) -> slot
+    // byte offset, in an operand of ld floats per row, of what the lane of slot s fetches (k-tile 0; the k-tile goes in the scalar offset)
+    static __device__ __forceinline__ int src_bytes(int s, int ld) { const Piece p = fetched(s); return p.row * ld * 4 + p.kq * 16; }
+};
+// A's offsets of slot s in the kernels whose last k-tile may reach beyond a row (ldw - lda < 16): rows >= rows_valid lie beyond
+// a_bytes -> zeros; in the last k-tile so do the k-quads beyond the row
+__device__ __forceinline__ void dma_a_piece(const GemmArgs& g, int ktiles, int a_bytes, int s, int& va, int& va_last) {
+    va = DmaImage<4>::src_bytes(s, g.lda);
+    va_last = ((ktiles - 1) * BK + DmaImage<4>::fetched(s).kq * 4 < g.lda) ? va : a_bytes;
+}
+
+// the four MFMAs of one (a, b) float4 pair = 4 consecutive k (lanes 0-31) and the 4 after them (lanes 32-63)
+__device__ __forceinline__ void mfma_quad(f32x16& acc, const float4& a, const float4& b) {
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc, 0, 0, 0);
+}
+// C/D layout of v_mfma_f32_32x32x2_f32: register q of a lane holds column lane & 31 of this row
+__device__ __forceinline__ int acc_row(int q, int lane) { return (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5); }
 
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
+}
+
+// GroupNorm(1, C) scalars of plane (branch, utt) from its {sum, sum of squares} slot, in fp64: mean and 1 / sqrt(var + eps)
+struct GnScalars { double m, rs; };
+__device__ __forceinline__ GnScalars gn_scalars(const double* gn, int branch, int B, int utt, double gn_count, int Tp, const int* tpb, float eps) {
+    const double* st = gn + ((long)branch * B + utt) * kGnStride;
+    const double cnt = gn_count_of(gn_count, Tp, tpb, utt);
+    const double m = st[0] / cnt;
+    const double var = st[1] / cnt - m * m;
+    return {m, 1.0 / sqrt((var > 0 ? var : 0) + (double)eps)};
+}
+// the statistics tail of a producing kernel: one fp64 atomic pair per workgroup into the plane's {sum, sum of squares} slot
+__device__ __forceinline__ void epi_stats_finish(double* gn_out, int B, double s, double q2, double* red, int branch, int utt, int tid, int lane, int wave) {
+    s = wave_sum(s);
+    q2 = wave_sum(q2);
+    if (lane == 0) { red[wave * 2] = s; red[wave * 2 + 1] = q2; }
+    __syncthreads();
+    if (tid == 0) {
+        double* out = gn_out + ((long)branch * B + utt) * kGnStride;
+        atomicAdd(out, red[0] + red[2] + red[4] + red[6]);
+        atomicAdd(out + 1, red[1] + red[3] + red[5] + red[7]);
+    }
+}
+
+__device__ __forceinline__ float apply_act(float v, int act) {
+    if (act == FSNP_ACT_RELU) v = fmaxf(v, 0.f);
+    else if (act == FSNP_ACT_RELU6) v = fminf(fmaxf(v, 0.f), 6.f);
+    else if (act == FSNP_ACT_TANH) v = tanhf(v);
+    return v;
+}
+
+// ---- epilogues: per-plane scalars, per-column constant, one output element
+struct EpiCtx { float slope, rstd, mr; int t_stats; };     // t_stats (EPI_PRELU_STATS): rows of the utterance's GroupNorm plane
+template <int EPI>
+__device__ __forceinline__ EpiCtx epi_ctx(const GemmArgs& g, int branch, int utt) {
+    EpiCtx e{0.f, 1.f, 0.f, g.Tp};
+    if constexpr (EPI == EPI_PRELU_STATS) {
+        e.slope = g.prelu[branch * g.prelu_bs];
+        e.t_stats = utt_frames(g.tpb, utt, g.Tp);      // (loaded here, under the first DMA round trips, like the other plane scalars)
+    }
+    if constexpr (EPI == EPI_RESIDUAL) {
+        const GnScalars n = gn_scalars(g.gn_in, branch, g.B, utt, g.gn_count, g.Tp, g.tpb, g.gn_eps);
+        e.rstd = (float)n.rs;
+        e.mr = (float)(n.m * n.rs);
+    }
+    return e;
+}
+// the constant of output column col: the bias; with GroupNorm folded c1[n] - m r c2[n] (see tcn_gemm_dma_kernel)
+template <int EPI>
+__device__ __forceinline__ float col_const(const GemmArgs& g, const EpiCtx& ec, int branch, int col) {
+    float cb = g.bias[branch * g.bias_bs + col];
+    if constexpr (EPI == EPI_RESIDUAL) cb -= ec.mr * g.c2[branch * g.c2_bs + col];
+    return cb;
+}
+// one accumulator element in the register layout: everything but the residual (added in the float4 phase)
+template <int EPI>
+__device__ __forceinline__ float epi_stage_value(const EpiCtx& e, float acc, float cb, int act, bool counted, double& s, double& q2) {
+    float v;
+    if constexpr (EPI == EPI_PRELU_STATS) {
+        v = acc + cb;
+        v = v >= 0.f ? v : e.slope * v;
+        if (counted) { s += (double)v; q2 += (double)v * (double)v; }
+    } else if constexpr (EPI == EPI_RESIDUAL) {
+        v = e.rstd * acc + cb;
+    } else {
+        v = apply_act(acc + cb, act);
+    }
+    return v;
+}
+// NQ accumulator registers acc(q) of one 32-column tile -> the lane's column `dst` of a row-major [rows][64] LDS slice whose row 0 is
+// frame t_first; an element counts for the statistics inside the utterance's plane and the GEMM's N columns
+template <int EPI, int NQ, class Acc>
+__device__ __forceinline__ void epi_stage(const EpiCtx& ec, Acc&& acc, float cb, int act, bool col_ok, int t_first, int lane, float* dst, double& s, double& q2) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        const int rl = acc_row(q, lane);
+        const bool counted = col_ok && t_first + rl < ec.t_stats;
+        dst[rl * 64] = epi_stage_value<EPI>(ec, acc(q), cb, act, counted, s, q2);
+    }
 }
 
 // One workgroup = 4 waves, wave w owns rows [32 w, 32 w + 32) of the 128-row tile and all BN columns
@@ -91,13 +243,9 @@ __global__ __launch_bounds__(256) void tcn_gemm_kernel(GemmArgs g) {
     double* red = reinterpret_cast<double*>(smem + 2 * STAGE);  // [8]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int row_tile_all, ntile;
-    if (!xcd_decode(blockIdx.x, g.ntiles_n, g.row_tiles_all, row_tile_all, ntile)) return;
-    const int branch = row_tile_all / g.row_tiles, row_tile = row_tile_all % g.row_tiles;
-    const int tiles_per_utt = cdiv(g.Tp, BM);
-    const int utt = row_tile / tiles_per_utt;
-    const int t0 = (row_tile % tiles_per_utt) * BM;
-    const int n0 = ntile * BN;
+    const GemmTile<BM> tl(g, BN);
+    if (!tl.ok) return;
+    const int branch = tl.branch, utt = tl.utt, t0 = tl.t0, n0 = tl.n0;
 
     const float* __restrict__ A = g.A + branch * g.a_bs + (g.a_us ? (long)utt * g.a_us : ((long)utt * g.Tp) * g.lda);
     const int a_cols = g.a_cols ? g.a_cols : g.lda;
@@ -107,12 +255,9 @@ __global__ __launch_bounds__(256) void tcn_gemm_kernel(GemmArgs g) {
     const float* gamma = nullptr;
     const float* beta = nullptr;
     if constexpr (PRO == PRO_GN) {
-        const double* st = g.gn_in + ((long)branch * g.B + utt) * kGnStride;
-        const double cnt = gn_count_of(g.gn_count, g.Tp, g.tpb, utt);
-        const double m = st[0] / cnt;
-        const double var = st[1] / cnt - m * m;
-        mean = (float)m;
-        rstd = (float)(1.0 / sqrt((var > 0 ? var : 0) + (double)g.gn_eps));
+        const GnScalars n = gn_scalars(g.gn_in, branch, g.B, utt, g.gn_count, g.Tp, g.tpb, g.gn_eps);
+        mean = (float)n.m;
+        rstd = (float)n.rs;
         gamma = g.gamma + branch * g.gb_bs;
         beta = g.beta + branch * g.gb_bs;
     }
@@ -220,10 +365,7 @@ __global__ __launch_bounds__(256) void tcn_gemm_kernel(GemmArgs g) {
 #pragma unroll
             for (int jn = 0; jn < NTILE; ++jn) {
                 const float4 b4 = Bs4[(kg * 2 + (lane >> 5)) * BN + jn * 32 + (lane & 31)];
-                acc[jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.x, b4.x, acc[jn], 0, 0, 0);
-                acc[jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.y, b4.y, acc[jn], 0, 0, 0);
-                acc[jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.z, b4.z, acc[jn], 0, 0, 0);
-                acc[jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4.w, b4.w, acc[jn], 0, 0, 0);
+                mfma_quad(acc[jn], a4, b4);
             }
         }
         if (kt + 1 < ktiles) {
@@ -239,12 +381,12 @@ __global__ __launch_bounds__(256) void tcn_gemm_kernel(GemmArgs g) {
         if constexpr (PF > 3) { if (kt0 + 3 < ktiles) k_iteration(std::integral_constant<int, 3 % PF>{}, kt0 + 3); }
     }
 
-    // ---- epilogue: C/D layout of 32x32: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5) ----
+    // ---- epilogue, straight from the accumulator layout (acc_row).  EPI_PRELU_STATS and EPI_ACT are the DMA kernels' expressions
+    // (epi_stage_value); EPI_RESIDUAL here is bias + residual, WITHOUT the GroupNorm fold (PRO_GN normalised the operand)
     float* C = g.C + branch * g.c_bs + ((long)utt * g.Tp) * g.ldc;
     double s = 0.0, q = 0.0;
-    float slope = 0.f;
-    if constexpr (EPI == EPI_PRELU_STATS) slope = g.prelu[branch * g.prelu_bs];
-    const int t_stats = utt_frames(g.tpb, utt, g.Tp);     // (EPI_PRELU_STATS) rows of the utterance's GroupNorm plane
+    EpiCtx ec{0.f, 1.f, 0.f, utt_frames(g.tpb, utt, g.Tp)};
+    if constexpr (EPI == EPI_PRELU_STATS) ec.slope = g.prelu[branch * g.prelu_bs];
 #pragma unroll
     for (int j = 0; j < NTILE; ++j) {
         const int col = n0 + j * 32 + (lane & 31);
@@ -252,76 +394,24 @@ __global__ __launch_bounds__(256) void tcn_gemm_kernel(GemmArgs g) {
         const float bias = g.bias[branch * g.bias_bs + col];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int t = t0 + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            const int t = t0 + wave * 32 + acc_row(r, lane);
             if (t < g.Tp && col_ok) {
-                float v = acc[j][r] + bias;
-                if constexpr (EPI == EPI_PRELU_STATS) {
-                    v = v >= 0.f ? v : slope * v;
-                    if (t < t_stats) {
-                        s += (double)v;
-                        q += (double)v * (double)v;
-                    }
-                }
+                float v;
                 if constexpr (EPI == EPI_RESIDUAL) {
+                    v = acc[j][r] + bias;
                     v += g.R[branch * g.r_bs + ((long)utt * g.Tp + t) * g.ldr + col];
                     if (g.relu_out) v = fmaxf(v, 0.f);
-                }
-                if constexpr (EPI == EPI_ACT) {
-                    if (g.act == FSNP_ACT_RELU) v = fmaxf(v, 0.f);
-                    else if (g.act == FSNP_ACT_RELU6) v = fminf(fmaxf(v, 0.f), 6.f);
-                    else if (g.act == FSNP_ACT_TANH) v = tanhf(v);
+                } else {
+                    v = epi_stage_value<EPI>(ec, acc[j][r], bias, g.act, t < ec.t_stats, s, q);
                 }
                 C[(long)t * g.ldc + col] = v;
             }
         }
     }
-    if constexpr (EPI == EPI_PRELU_STATS) {
-        s = wave_sum(s);
-        q = wave_sum(q);
-        if (lane == 0) { red[wave * 2] = s; red[wave * 2 + 1] = q; }
-        __syncthreads();
-        if (tid == 0) {
-            double* out = g.gn_out + ((long)branch * g.B + utt) * kGnStride;
-            atomicAdd(out, red[0] + red[2] + red[4] + red[6]);
-            atomicAdd(out + 1, red[1] + red[3] + red[5] + red[7]);
-        }
-    }
+    if constexpr (EPI == EPI_PRELU_STATS) epi_stats_finish(g.gn_out, g.B, s, q, red, branch, utt, tid, lane, wave);
 }
 
 // ------------------------------------------------------------------------------------------------
-// ---- epilogues shared by tcn_gemm_dma_kernel and tcn_gemm_sk_kernel: per-plane scalars, one output element, the statistics tail
-struct EpiCtx { float slope, rstd, mr; int t_stats; };     // t_stats (EPI_PRELU_STATS): rows of the utterance's GroupNorm plane
-template <int EPI>
-__device__ __forceinline__ EpiCtx epi_ctx(const GemmArgs& g, int branch, int utt) {
-    EpiCtx e{0.f, 1.f, 0.f, g.Tp};
-    if constexpr (EPI == EPI_PRELU_STATS) {
-        e.slope = g.prelu[branch * g.prelu_bs];
-        e.t_stats = utt_frames(g.tpb, utt, g.Tp);      // (loaded here, under the first DMA round trips, like the other plane scalars)
-    }
-    if constexpr (EPI == EPI_RESIDUAL) {
-        const double* stt = g.gn_in + ((long)branch * g.B + utt) * kGnStride;
-        const double cnt = gn_count_of(g.gn_count, g.Tp, g.tpb, utt);
-        const double m = stt[0] / cnt;
-        const double var = stt[1] / cnt - m * m;
-        const double rs = 1.0 / sqrt((var > 0 ? var : 0) + (double)g.gn_eps);
-        e.rstd = (float)rs;
-        e.mr = (float)(m * rs);
-    }
-    return e;
-}
-// one fp64 atomic pair per workgroup into the plane's {sum, sum of squares} slot
-__device__ __forceinline__ void epi_stats_finish(const GemmArgs& g, double s, double q2, double* red, int branch, int utt, int tid, int lane, int wave) {
-    s = wave_sum(s);
-    q2 = wave_sum(q2);
-    if (lane == 0) { red[wave * 2] = s; red[wave * 2 + 1] = q2; }
-    __syncthreads();
-    if (tid == 0) {
-        double* out = g.gn_out + ((long)branch * g.B + utt) * kGnStride;
-        atomicAdd(out, red[0] + red[2] + red[4] + red[6]);
-        atomicAdd(out + 1, red[1] + red[3] + red[5] + red[7]);
-    }
-}
-
 // ---- float4 epilogue of the DMA GEMM kernels (round 4).  The accumulator layout of v_mfma_f32_32x32x2_f32 gives a lane ONE column
 // and 16 scattered rows: stored from there, a tile leaves as 32 (sconv: 32 + 32 residual loads, each load -> add -> store a dependent
 // round trip because the residual aliases the output: the in-place x += ...) 4-byte instructions per lane.  Here a wave first
@@ -372,24 +462,6 @@ struct EpiF4 {
         }
     }
 };
-// one accumulator element in the register layout: everything but the residual (added in the float4 phase)
-template <int EPI>
-__device__ __forceinline__ float epi_stage_value(const EpiCtx& e, float acc, float cb, int act, bool counted, double& s, double& q2) {
-    float v;
-    if constexpr (EPI == EPI_PRELU_STATS) {
-        v = acc + cb;
-        v = v >= 0.f ? v : e.slope * v;
-        if (counted) { s += (double)v; q2 += (double)v * (double)v; }
-    } else if constexpr (EPI == EPI_RESIDUAL) {
-        v = e.rstd * acc + cb;                   // cb = c1[n] - m r c2[n]  (GroupNorm folded, see tcn_gemm_dma_kernel)
-    } else {
-        v = acc + cb;
-        if (act == FSNP_ACT_RELU) v = fmaxf(v, 0.f);
-        else if (act == FSNP_ACT_RELU6) v = fminf(fmaxf(v, 0.f), 6.f);
-        else if (act == FSNP_ACT_TANH) v = tanhf(v);
-    }
-    return v;
-}
 
 // tcn_gemm_dma_kernel: the two GEMMs of a TCNBlock with the k-loop stripped to what the matrix pipe needs.
 // tcn_gemm_kernel above issues ~200 VALU/SALU instructions per 16 MFMAs (bounds checks, the GroupNorm prologue, the
@@ -398,8 +470,7 @@ __device__ __forceinline__ float epi_stage_value(const EpiCtx& e, float acc, flo
 //  * operands go global -> LDS by DMA (`buffer_load_dwordx4 ... lds`: no staging registers, no ds_write, no VALU): three
 //    16-byte pieces per lane and k-tile with loop-invariant per-lane offsets and the k position in the scalar offset;
 //    rows beyond the plane and k beyond the row are out of the descriptor's range (-> zeros), so there are no bounds checks;
-//  * the LDS image is plain row-major [row][16 k], XOR-swizzled on BOTH sides (the DMA destination is lane-linear: lane l of a
-//    piece fetches the k-quad that belongs in slot l; readers apply the same involution): ds_read_b128 is conflict-free;
+//  * the LDS image is plain row-major [row][16 k], XOR-swizzled on BOTH sides (DmaImage<4>): ds_read_b128 is conflict-free;
 //  * a lane's float4 is 4 consecutive k, i.e. MFMA j multiplies k = k0 + 8 kg + j (lanes 0-31) and + 4 (lanes 32-63) - a
 //    permutation of the 16 k of the tile that A and B share, so no fragment shuffle is needed;
 //  * GroupNorm on the sconv operand is folded out of the loop: sum_k ((a - m) r g_k + b_k) W[n][k] =
@@ -416,61 +487,41 @@ __global__ __launch_bounds__(256) void tcn_gemm_dma_kernel(GemmArgs g) {
     __shared__ double red[8];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int row_tile_all, ntile;
-    if (!xcd_decode(blockIdx.x, g.ntiles_n, g.row_tiles_all, row_tile_all, ntile)) return;
-    const int branch = row_tile_all / g.row_tiles, row_tile = row_tile_all % g.row_tiles;
-    const int tiles_per_utt = cdiv(g.Tp, BM);
-    const int utt = row_tile / tiles_per_utt;
-    const int t0 = (row_tile % tiles_per_utt) * BM;
-    const int n0 = ntile * BN;
-    const int rows_valid = min(BM, g.Tp - t0);
+    const GemmTile<BM> tl(g, BN);
+    if (!tl.ok) return;
+    const int branch = tl.branch, utt = tl.utt, t0 = tl.t0, n0 = tl.n0;
     // the plane's scalars (EPI_RESIDUAL: two loads + an fp64 rsqrt / divide chain) and the columns' constants: fetched and computed
     // here, under the first DMA round trips, instead of at the head of the epilogue
     const EpiCtx ec = epi_ctx<EPI>(g, branch, utt);
     float cb[2];
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int col = n0 + j * 32 + (lane & 31);
-        cb[j] = g.bias[branch * g.bias_bs + col];
-        if constexpr (EPI == EPI_RESIDUAL) cb[j] -= ec.mr * g.c2[branch * g.c2_bs + col];
-    }
+    for (int j = 0; j < 2; ++j) cb[j] = col_const<EPI>(g, ec, branch, n0 + j * 32 + (lane & 31));
 
-    const float* A = g.A + branch * g.a_bs + ((long)utt * g.Tp + t0) * g.lda;
-    const float* W = g.W + branch * g.w_bs + (long)n0 * g.ldw;
-    const int a_bytes = rows_valid * g.lda * 4, w_bytes = BN * g.ldw * 4;
-    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A), 0, a_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W), 0, w_bytes, 0x00020000);
+    const DmaWindow win = dma_window(g, tl, BN);
 
-    // DMA pieces: wave w moves A slots [128 w, 128 w + 128) (two pieces) and B slots [64 w, 64 w + 64).  Slot s holds row
-    // s >> 2, k-quad (s & 3) ^ swz(row); swz(row) = (row >> 2) & 3 spreads 16 consecutive rows of one k-quad over all banks.
+    // DMA pieces: wave w moves A slots [128 w, 128 w + 128) (two pieces) and B slots [64 w, 64 w + 64)
+    using Img = DmaImage<4>;
     const int ktiles = g.ldw / BK;
-    int va[2], va_last[2], vb;
+    int va[2], va_last[2];
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int s = (wave * 2 + i) * 64 + lane, row = s >> 2, kq = (s & 3) ^ ((row >> 2) & 3);
-        va[i] = row * g.lda * 4 + kq * 16;                                    // rows >= rows_valid: beyond a_bytes -> zeros
-        va_last[i] = ((ktiles - 1) * BK + kq * 4 < g.lda) ? va[i] : a_bytes;   // last k-tile: k-quads beyond the row -> zeros
-    }
-    {
-        const int s = wave * 64 + lane, n = s >> 2, kq = (s & 3) ^ ((n >> 2) & 3);
-        vb = n * g.ldw * 4 + kq * 16;
-    }
+    for (int i = 0; i < 2; ++i) dma_a_piece(g, ktiles, win.a_bytes, (wave * 2 + i) * 64 + lane, va[i], va_last[i]);
+    const int vb = Img::src_bytes(wave * 64 + lane, g.ldw);
     using lds_ptr = __attribute__((address_space(3))) void*;
     auto issue = [&](int kt, int stage) {
         float4* st = smem + stage * STAGE;
         const bool last = kt == ktiles - 1;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_ptr)(st + (wave * 2 + 0) * 64), 16, last ? va_last[0] : va[0], kt * (BK * 4), 0, 0);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_ptr)(st + (wave * 2 + 1) * 64), 16, last ? va_last[1] : va[1], kt * (BK * 4), 0, 0);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr)(st + A_SLOTS + wave * 64), 16, vb, kt * (BK * 4), 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(win.ra, (lds_ptr)(st + (wave * 2 + 0) * 64), 16, last ? va_last[0] : va[0], kt * (BK * 4), 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(win.ra, (lds_ptr)(st + (wave * 2 + 1) * 64), 16, last ? va_last[1] : va[1], kt * (BK * 4), 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(win.rw, (lds_ptr)(st + A_SLOTS + wave * 64), 16, vb, kt * (BK * 4), 0, 0);
     };
     // readers: lane = (r = lane & 31, kh = lane >> 5) takes k-quad 2 kg + kh of row 32 wave + r (A) / column 32 jn + r (B)
-    const int r = lane & 31, kh = lane >> 5, sw = (r >> 2) & 3;
+    const int r = lane & 31, kh = lane >> 5;
     int aoff[2], boff[2][2];
 #pragma unroll
     for (int kg = 0; kg < 2; ++kg) {
-        aoff[kg] = (wave * 32 + r) * 4 + ((kg * 2 + kh) ^ sw);
+        aoff[kg] = Img::slot(wave * 32 + r, kg * 2 + kh);
 #pragma unroll
-        for (int jn = 0; jn < 2; ++jn) boff[kg][jn] = A_SLOTS + (jn * 32 + r) * 4 + ((kg * 2 + kh) ^ sw);
+        for (int jn = 0; jn < 2; ++jn) boff[kg][jn] = A_SLOTS + Img::slot(jn * 32 + r, kg * 2 + kh);
     }
 
     f32x16 acc[2];
@@ -495,12 +546,7 @@ __global__ __launch_bounds__(256) void tcn_gemm_dma_kernel(GemmArgs g) {
 #pragma unroll
         for (int kg = 0; kg < 2; ++kg)
 #pragma unroll
-            for (int jn = 0; jn < 2; ++jn) {
-                acc[jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[kg].x, b4[kg][jn].x, acc[jn], 0, 0, 0);
-                acc[jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[kg].y, b4[kg][jn].y, acc[jn], 0, 0, 0);
-                acc[jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[kg].z, b4[kg][jn].z, acc[jn], 0, 0, 0);
-                acc[jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[kg].w, b4[kg][jn].w, acc[jn], 0, 0, 0);
-            }
+            for (int jn = 0; jn < 2; ++jn) mfma_quad(acc[jn], a4[kg], b4[kg][jn]);
         __builtin_amdgcn_sched_barrier(0);          // else hipcc hoists the vmcnt(0) + s_barrier above 15 of the 16 MFMAs
         __syncthreads();
     };
@@ -522,18 +568,12 @@ __global__ __launch_bounds__(256) void tcn_gemm_dma_kernel(GemmArgs g) {
     ef.load_residual(g, branch, utt, t0 + wave * 32);
     float* slice = reinterpret_cast<float*>(smem) + wave * (32 * 64);
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const bool col_ok = n0 + j * 32 + (lane & 31) < g.N;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int rl = (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
-            const bool counted = col_ok && t0 + wave * 32 + rl < ec.t_stats;
-            slice[rl * 64 + j * 32 + (lane & 31)] = epi_stage_value<EPI>(ec, acc[j][q], cb[j], g.act, counted, s, q2);
-        }
-    }
+    for (int j = 0; j < 2; ++j)
+        epi_stage<EPI, 16>(ec, [&](int q) { return acc[j][q]; }, cb[j], g.act, n0 + j * 32 + (lane & 31) < g.N, t0 + wave * 32, lane,
+                           slice + j * 32 + (lane & 31), s, q2);
     __builtin_amdgcn_wave_barrier();            // (LDS operations of one wave execute in order; this only pins the compiler's order)
     ef.store(g, slice, C, t0 + wave * 32, lane);
-    if constexpr (EPI == EPI_PRELU_STATS) epi_stats_finish(g, s, q2, red, branch, utt, tid, lane, wave);
+    if constexpr (EPI == EPI_PRELU_STATS) epi_stats_finish(g.gn_out, g.B, s, q2, red, branch, utt, tid, lane, wave);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -544,7 +584,6 @@ __global__ __launch_bounds__(256) void tcn_gemm_dma_kernel(GemmArgs g) {
 // the loop has no workgroup barrier at all - the wave waits for its own DMA only; the four partial tiles are added in a fixed order
 // (wave 0 + 1 + 2 + 3) through the staging LDS and wave w finishes rows [8 w, 8 w + 8) with the same epilogues.  K is summed in another
 // order than by tcn_gemm_dma_kernel: same tolerance, not bit-identical to it.
-constexpr int BMS = 32;
 template <int EPI>
 __global__ __launch_bounds__(256) void tcn_gemm_sk_kernel(GemmArgs g) {
     constexpr int BN = 64;
@@ -553,52 +592,36 @@ __global__ __launch_bounds__(256) void tcn_gemm_sk_kernel(GemmArgs g) {
     __shared__ double red[8];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int row_tile_all, ntile;
-    if (!xcd_decode(blockIdx.x, g.ntiles_n, g.row_tiles_all, row_tile_all, ntile)) return;
-    const int branch = row_tile_all / g.row_tiles, row_tile = row_tile_all % g.row_tiles;
-    const int tiles_per_utt = cdiv(g.Tp, BMS);
-    const int utt = row_tile / tiles_per_utt;
-    const int t0 = (row_tile % tiles_per_utt) * BMS;
-    const int n0 = ntile * BN;
-    const int rows_valid = min(BMS, g.Tp - t0);
+    const GemmTile<BMS> tl(g, BN);
+    if (!tl.ok) return;
+    const int branch = tl.branch, utt = tl.utt, t0 = tl.t0, n0 = tl.n0;
+    const DmaWindow win = dma_window(g, tl, BN);
 
-    const float* A = g.A + branch * g.a_bs + ((long)utt * g.Tp + t0) * g.lda;
-    const float* W = g.W + branch * g.w_bs + (long)n0 * g.ldw;
-    const int a_bytes = rows_valid * g.lda * 4, w_bytes = BN * g.ldw * 4;
-    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A), 0, a_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W), 0, w_bytes, 0x00020000);
-
-    // DMA pieces of one k-tile (per wave): A slots [0, 128) = two pieces, B slots [0, 256) = four.  Slot s = row s >> 2, k-quad (s & 3) ^ swz(row)
+    // DMA pieces of one k-tile (per wave): A slots [0, 128) = two pieces, B slots [0, 256) = four
+    using Img = DmaImage<4>;
     const int ktiles = g.ldw / BK;
     int va[2], va_last[2], vb[4];
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int sl = i * 64 + lane, row = sl >> 2, kq = (sl & 3) ^ ((row >> 2) & 3);
-        va[i] = row * g.lda * 4 + kq * 16;                                    // rows >= rows_valid: beyond a_bytes -> zeros
-        va_last[i] = ((ktiles - 1) * BK + kq * 4 < g.lda) ? va[i] : a_bytes;   // last k-tile: k-quads beyond the row -> zeros
-    }
+    for (int i = 0; i < 2; ++i) dma_a_piece(g, ktiles, win.a_bytes, i * 64 + lane, va[i], va_last[i]);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int sl = i * 64 + lane, n = sl >> 2, kq = (sl & 3) ^ ((n >> 2) & 3);
-        vb[i] = n * g.ldw * 4 + kq * 16;
-    }
+    for (int i = 0; i < 4; ++i) vb[i] = Img::src_bytes(i * 64 + lane, g.ldw);
     using lds_ptr = __attribute__((address_space(3))) void*;
     float4* mine = smem + wave * 2 * STAGE;
     auto issue = [&](int kt, int stage) {
         float4* st = mine + stage * STAGE;
         const bool last = kt == ktiles - 1;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_ptr)(st + 0), 16, last ? va_last[0] : va[0], kt * (BK * 4), 0, 0);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_ptr)(st + 64), 16, last ? va_last[1] : va[1], kt * (BK * 4), 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(win.ra, (lds_ptr)(st + 0), 16, last ? va_last[0] : va[0], kt * (BK * 4), 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(win.ra, (lds_ptr)(st + 64), 16, last ? va_last[1] : va[1], kt * (BK * 4), 0, 0);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr)(st + A_SLOTS + i * 64), 16, vb[i], kt * (BK * 4), 0, 0);
+        for (int i = 0; i < 4; ++i) __builtin_amdgcn_raw_ptr_buffer_load_lds(win.rw, (lds_ptr)(st + A_SLOTS + i * 64), 16, vb[i], kt * (BK * 4), 0, 0);
     };
-    const int r = lane & 31, kh = lane >> 5, sw = (r >> 2) & 3;
+    const int r = lane & 31, kh = lane >> 5;
     int aoff[2], boff[2][2];
 #pragma unroll
     for (int kg = 0; kg < 2; ++kg) {
-        aoff[kg] = r * 4 + ((kg * 2 + kh) ^ sw);
+        aoff[kg] = Img::slot(r, kg * 2 + kh);
 #pragma unroll
-        for (int jn = 0; jn < 2; ++jn) boff[kg][jn] = A_SLOTS + (jn * 32 + r) * 4 + ((kg * 2 + kh) ^ sw);
+        for (int jn = 0; jn < 2; ++jn) boff[kg][jn] = A_SLOTS + Img::slot(jn * 32 + r, kg * 2 + kh);
     }
     f32x16 acc[2];
 #pragma unroll
@@ -623,12 +646,7 @@ __global__ __launch_bounds__(256) void tcn_gemm_sk_kernel(GemmArgs g) {
 #pragma unroll
         for (int kg = 0; kg < 2; ++kg)
 #pragma unroll
-            for (int jn = 0; jn < 2; ++jn) {
-                acc[jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[kg].x, b4[kg][jn].x, acc[jn], 0, 0, 0);
-                acc[jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[kg].y, b4[kg][jn].y, acc[jn], 0, 0, 0);
-                acc[jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[kg].z, b4[kg][jn].z, acc[jn], 0, 0, 0);
-                acc[jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[kg].w, b4[kg][jn].w, acc[jn], 0, 0, 0);
-            }
+            for (int jn = 0; jn < 2; ++jn) mfma_quad(acc[jn], a4[kg], b4[kg][jn]);
         __builtin_amdgcn_sched_barrier(0);
         stage ^= 1;
     }
@@ -637,11 +655,7 @@ __global__ __launch_bounds__(256) void tcn_gemm_sk_kernel(GemmArgs g) {
     const EpiCtx ec = epi_ctx<EPI>(g, branch, utt);
     float cb[2];
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int col = n0 + j * 32 + (lane & 31);
-        cb[j] = g.bias[branch * g.bias_bs + col];
-        if constexpr (EPI == EPI_RESIDUAL) cb[j] -= ec.mr * g.c2[branch * g.c2_bs + col];
-    }
+    for (int j = 0; j < 2; ++j) cb[j] = col_const<EPI>(g, ec, branch, n0 + j * 32 + (lane & 31));
     EpiF4<EPI, 8> ef;
     ef.init(g, n0, lane);
     ef.load_residual(g, branch, utt, t0 + wave * 8);
@@ -670,19 +684,14 @@ __global__ __launch_bounds__(256) void tcn_gemm_sk_kernel(GemmArgs g) {
     float* C = g.C + branch * g.c_bs + ((long)utt * g.Tp) * g.ldc;
     double s = 0.0, q2 = 0.0;
     float* slice = reinterpret_cast<float*>(smem) + 4 * 2 * 16 * 64 + wave * (8 * 64);
+    // (registers 4 w ... 4 w + 3 are rows 8 w + acc_row(0 ... 3): the slice's row 0 is frame t0 + 8 w)
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const bool col_ok = n0 + j * 32 + (lane & 31) < g.N;
-#pragma unroll
-        for (int qq = 0; qq < 4; ++qq) {
-            const int rl = qq + 4 * (lane >> 5);
-            const bool counted = col_ok && t0 + wave * 8 + rl < ec.t_stats;
-            slice[rl * 64 + j * 32 + (lane & 31)] = epi_stage_value<EPI>(ec, sum[j][qq], cb[j], g.act, counted, s, q2);
-        }
-    }
+    for (int j = 0; j < 2; ++j)
+        epi_stage<EPI, 4>(ec, [&](int qq) { return sum[j][qq]; }, cb[j], g.act, n0 + j * 32 + (lane & 31) < g.N, t0 + wave * 8, lane,
+                          slice + j * 32 + (lane & 31), s, q2);
     __builtin_amdgcn_wave_barrier();
     ef.store(g, slice, C, t0 + wave * 8, lane);
-    if constexpr (EPI == EPI_PRELU_STATS) epi_stats_finish(g, s, q2, red, branch, utt, tid, lane, wave);
+    if constexpr (EPI == EPI_PRELU_STATS) epi_stats_finish(g.gn_out, g.B, s, q2, red, branch, utt, tid, lane, wave);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -695,11 +704,10 @@ __global__ __launch_bounds__(256) void tcn_gemm_sk_kernel(GemmArgs g) {
 //  * tiles are 64 rows: 192 x 4 = 768 workgroups = exactly 3 per CU at B = 32 (three rounds of a 6.8 us k-loop: 20.4 us of MFMA time
 //    instead of 27.2); the four waves sit 2 x 2 on the tile (one 32 x 32 accumulator each);
 //  * a k-tile is 32 deep so that a wave still issues 16 MFMAs per barrier (as the 128-row kernel); the LDS image is [row][8 k-quads],
-//    XOR-swizzled by (row >> 1) & 7 on both sides (16 consecutive rows of one k-quad cover all 64 banks); 4 DMA pieces per wave and k-tile.
+//    XOR-swizzled on both sides (DmaImage<8>); 4 DMA pieces per wave and k-tile.
 // Same operands, GroupNorm fold and float4 epilogue as tcn_gemm_dma_kernel<EPI_RESIDUAL>; the k-sum of a column runs over the same k
 // in another association, column N - 1 is summed by fp32 FMAs: equal to the 128-row kernel within rounding, not bit for bit.
 // Requirements (launch_gemm_dma64): N % 64 == 1, K % 32 == 0, lda == ldw == K (no k tail), float4-aligned C / R rows.
-constexpr int BM64 = 64, BK64 = 32;
 template <int EPI>
 __global__ __launch_bounds__(256) void tcn_gemm_dma64_kernel(GemmArgs g) {
     constexpr int BN = 64;
@@ -709,55 +717,44 @@ __global__ __launch_bounds__(256) void tcn_gemm_dma64_kernel(GemmArgs g) {
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 1, wc = wave & 1;
-    int row_tile_all, ntile;
-    if (!xcd_decode(blockIdx.x, g.ntiles_n, g.row_tiles_all, row_tile_all, ntile)) return;
-    const int branch = row_tile_all / g.row_tiles, row_tile = row_tile_all % g.row_tiles;
-    const int tiles_per_utt = cdiv(g.Tp, BM64);
-    const int utt = row_tile / tiles_per_utt;
-    const int t0 = (row_tile % tiles_per_utt) * BM64;
-    const int n0 = ntile * BN;
-    const int rows_valid = min(BM64, g.Tp - t0);
-    const bool xcol = ntile == g.ntiles_n - 1;          // this workgroup also owns column N - 1 = ntiles_n * 64
+    const GemmTile<BM64> tl(g, BN);
+    if (!tl.ok) return;
+    const int branch = tl.branch, utt = tl.utt, t0 = tl.t0, n0 = tl.n0;
+    const bool xcol = tl.ntile == g.ntiles_n - 1;       // this workgroup also owns column N - 1 = ntiles_n * 64
 
     const EpiCtx ec = epi_ctx<EPI>(g, branch, utt);
     const int mycol = n0 + wc * 32 + (lane & 31);
-    float cb = g.bias[branch * g.bias_bs + mycol];
-    if constexpr (EPI == EPI_RESIDUAL) cb -= ec.mr * g.c2[branch * g.c2_bs + mycol];
+    const float cb = col_const<EPI>(g, ec, branch, mycol);
 
-    const float* A = g.A + branch * g.a_bs + ((long)utt * g.Tp + t0) * g.lda;
-    const float* W = g.W + branch * g.w_bs + (long)n0 * g.ldw;
-    const int a_bytes = rows_valid * g.lda * 4, w_bytes = BN * g.ldw * 4;
-    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(A), 0, a_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(W), 0, w_bytes, 0x00020000);
+    const DmaWindow win = dma_window(g, tl, BN);
 
-    // DMA pieces: wave w moves A slots [128 w, 128 w + 128) and B slots [128 w, 128 w + 128).  Slot s holds row s >> 3, k-quad (s & 7) ^ swz(row)
+    // DMA pieces: wave w moves A slots [128 w, 128 w + 128) and B slots [128 w, 128 w + 128); rows >= rows_valid: beyond a_bytes -> zeros
+    using Img = DmaImage<8>;
     const int ktiles = g.ldw / BK64;
     int va[2], vb[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-        const int sl = (wave * 2 + i) * 64 + lane, row = sl >> 3, kq = (sl & 7) ^ ((row >> 1) & 7);
-        va[i] = row * g.lda * 4 + kq * 16;               // rows >= rows_valid: beyond a_bytes -> zeros
-        vb[i] = row * g.ldw * 4 + kq * 16;
+        va[i] = Img::src_bytes((wave * 2 + i) * 64 + lane, g.lda);
+        vb[i] = Img::src_bytes((wave * 2 + i) * 64 + lane, g.ldw);
     }
     using lds_ptr = __attribute__((address_space(3))) void*;
     auto issue = [&](int kt, int stage) {
         float4* st = smem + stage * STAGE;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_ptr)(st + (wave * 2 + 0) * 64), 16, va[0], kt * (BK64 * 4), 0, 0);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(ra, (lds_ptr)(st + (wave * 2 + 1) * 64), 16, va[1], kt * (BK64 * 4), 0, 0);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr)(st + A_SLOTS + (wave * 2 + 0) * 64), 16, vb[0], kt * (BK64 * 4), 0, 0);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr)(st + A_SLOTS + (wave * 2 + 1) * 64), 16, vb[1], kt * (BK64 * 4), 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(win.ra, (lds_ptr)(st + (wave * 2 + 0) * 64), 16, va[0], kt * (BK64 * 4), 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(win.ra, (lds_ptr)(st + (wave * 2 + 1) * 64), 16, va[1], kt * (BK64 * 4), 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(win.rw, (lds_ptr)(st + A_SLOTS + (wave * 2 + 0) * 64), 16, vb[0], kt * (BK64 * 4), 0, 0);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(win.rw, (lds_ptr)(st + A_SLOTS + (wave * 2 + 1) * 64), 16, vb[1], kt * (BK64 * 4), 0, 0);
     };
     // readers: lane = (r = lane & 31, kh = lane >> 5) takes k-quad 2 kg + kh of row 32 wr + r (A) / column 32 wc + r (B)
     const int r = lane & 31, kh = lane >> 5;
     int aoff[4], boff[4];
 #pragma unroll
     for (int kg = 0; kg < 4; ++kg) {
-        const int ar = wr * 32 + r, br = wc * 32 + r;
-        aoff[kg] = ar * 8 + ((kg * 2 + kh) ^ ((ar >> 1) & 7));
-        boff[kg] = A_SLOTS + br * 8 + ((kg * 2 + kh) ^ ((br >> 1) & 7));
+        aoff[kg] = Img::slot(wr * 32 + r, kg * 2 + kh);
+        boff[kg] = A_SLOTS + Img::slot(wc * 32 + r, kg * 2 + kh);
     }
-    // column N - 1: thread -> A slots tid and tid + 256 of a stage = rows tid >> 3 and 32 + (tid >> 3), the k-quad that sits in position tid & 7
-    const int xrow = tid >> 3, xq0 = (tid & 7) ^ ((xrow >> 1) & 7), xq1 = (tid & 7) ^ (((xrow + 32) >> 1) & 7);
+    // column N - 1: thread -> A slots tid and tid + 256 of a stage = rows tid >> 3 and 32 + (tid >> 3), whichever k-quads the image put there
+    const int xrow = tid >> 3, xq0 = Img::fetched(tid).kq, xq1 = Img::fetched(tid + 256).kq;
     float xacc0 = 0.f, xacc1 = 0.f;
     if (xcol) {
         const float* wl = g.W + branch * g.w_bs + (long)(g.ntiles_n * BN) * g.ldw;
@@ -781,12 +778,7 @@ __global__ __launch_bounds__(256) void tcn_gemm_dma64_kernel(GemmArgs g) {
         }
         if (kt_next < ktiles) issue(kt_next, stage ^ 1);
 #pragma unroll
-        for (int kg = 0; kg < 4; ++kg) {
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[kg].x, b4[kg].x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[kg].y, b4[kg].y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[kg].z, b4[kg].z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[kg].w, b4[kg].w, acc, 0, 0, 0);
-        }
+        for (int kg = 0; kg < 4; ++kg) mfma_quad(acc, a4[kg], b4[kg]);
         if (xcol) {
             xacc0 = fmaf(xa0.x, xw0.x, xacc0); xacc0 = fmaf(xa0.y, xw0.y, xacc0); xacc0 = fmaf(xa0.z, xw0.z, xacc0); xacc0 = fmaf(xa0.w, xw0.w, xacc0);
             xacc1 = fmaf(xa1.x, xw1.x, xacc1); xacc1 = fmaf(xa1.y, xw1.y, xacc1); xacc1 = fmaf(xa1.z, xw1.z, xacc1); xacc1 = fmaf(xa1.w, xw1.w, xacc1);
@@ -824,20 +816,12 @@ __global__ __launch_bounds__(256) void tcn_gemm_dma64_kernel(GemmArgs g) {
         }
     }
     float* tile = reinterpret_cast<float*>(smem);
-    {
-        const bool col_ok = mycol < g.N;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int rl = (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
-            const bool counted = col_ok && t0 + wr * 32 + rl < ec.t_stats;
-            tile[(wr * 32 + rl) * 64 + wc * 32 + (lane & 31)] = epi_stage_value<EPI>(ec, acc[q], cb, g.act, counted, s, q2);
-        }
-    }
+    epi_stage<EPI, 16>(ec, [&](int q) { return acc[q]; }, cb, g.act, mycol < g.N, t0 + wr * 32, lane,
+                       tile + wr * 32 * 64 + wc * 32 + (lane & 31), s, q2);
     __syncthreads();
     ef.store(g, tile + wave * 16 * 64, C, t0 + wave * 16, lane);
     if (xcol && (tid & 7) == 0) {
-        float cx = g.bias[branch * g.bias_bs + xcolumn];
-        if constexpr (EPI == EPI_RESIDUAL) cx -= ec.mr * g.c2[branch * g.c2_bs + xcolumn];
+        const float cx = col_const<EPI>(g, ec, branch, xcolumn);
         double sd = 0.0, qd = 0.0;
         float v0 = epi_stage_value<EPI>(ec, xacc0, cx, g.act, false, sd, qd) + xr0;
         float v1 = epi_stage_value<EPI>(ec, xacc1, cx, g.act, false, sd, qd) + xr1;
@@ -848,16 +832,22 @@ __global__ __launch_bounds__(256) void tcn_gemm_dma64_kernel(GemmArgs g) {
     }
 }
 
+// What every DMA kernel asks of its operands: 16-byte aligned planes and rows of A and W (the DMA pieces) and of C and the residual
+// (the float4 epilogue), and 31-bit byte ranges of a `rows`-row A window and a 64-row W window (the buffer offsets are ints)
+static bool dma_operands_ok(const GemmArgs& g, int rows, bool residual) {
+    auto plane16 = [](const float* p, long bs, int ld) { return !((reinterpret_cast<uintptr_t>(p) & 15) || (bs * 4) % 16 || ld % 4); };
+    if (!plane16(g.A, g.a_bs, g.lda) || !plane16(g.W, g.w_bs, g.ldw) || !plane16(g.C, g.c_bs, g.ldc)) return false;
+    if (residual && !plane16(g.R, g.r_bs, g.ldr)) return false;
+    return (long)rows * g.lda * 4 < (1L << 31) && (long)64 * g.ldw * 4 < (1L << 31);
+}
+
 // launched (true) when the 64-row kernel applies AND beats the 128-row kernel's round count
 template <int EPI>
 static bool launch_gemm_dma64(const GemmArgs& g, int n, int num_cus, hipStream_t s, int branches) {
     if constexpr (EPI != EPI_RESIDUAL) return false;      // (sconv only: conv1x1 and the final Linear have K = 257 -> a 16-deep k tail)
     else {
     if (n % 64 != 1 || g.K % BK64 || g.lda != g.K || g.ldw != g.K || g.K > 1024 || g.a_us || g.a_cols) return false;
-    if (g.ldc % 4 || g.ldc < n + 3 || g.ldr % 4) return false;            // the float4 {column N - 1, three pad columns}
-    if ((reinterpret_cast<uintptr_t>(g.A) | reinterpret_cast<uintptr_t>(g.W) | reinterpret_cast<uintptr_t>(g.C) | reinterpret_cast<uintptr_t>(g.R)) & 15) return false;
-    if ((g.a_bs * 4) % 16 || (g.w_bs * 4) % 16 || (g.c_bs * 4) % 16 || (g.r_bs * 4) % 16) return false;
-    if ((long)BM64 * g.lda * 4 >= (1L << 31) || (long)64 * g.ldw * 4 >= (1L << 31)) return false;
+    if (g.ldc < n + 3 || !dma_operands_ok(g, BM64, true)) return false;    // the float4 {column N - 1, three pad columns}
     GemmArgs ga = g;
     ga.ntiles_n = n / 64;
     ga.row_tiles = cdiv(g.Tp, BM64) * g.B; ga.row_tiles_all = ga.row_tiles * branches;
@@ -873,13 +863,9 @@ static bool launch_gemm_dma64(const GemmArgs& g, int n, int num_cus, hipStream_t
 // true (and launched) when the DMA kernel's requirements hold
 template <int EPI>
 static bool launch_gemm_dma(const GemmArgs& g, int n, int row_tiles, int num_cus, hipStream_t s, int branches, bool allow_splitk, bool allow_bm64 = false) {
-    if (g.a_us || g.a_cols || g.lda % 4 || g.ldw % BK || g.ldw < g.K || g.lda < g.K) return false;
+    if (g.a_us || g.a_cols || g.ldw % BK || g.ldw < g.K || g.lda < g.K) return false;
     if (g.ldw - g.lda >= BK) return false;                 // only the LAST k-tile may reach beyond a row of A
-    if ((reinterpret_cast<uintptr_t>(g.A) | reinterpret_cast<uintptr_t>(g.W)) & 15 || (g.a_bs * 4) % 16 || (g.w_bs * 4) % 16) return false;
-    if ((long)BM * g.lda * 4 >= (1L << 31) || (long)64 * g.ldw * 4 >= (1L << 31)) return false;
-    // float4 epilogue: 16-byte rows of C (and of the residual)
-    if (g.ldc % 4 || (reinterpret_cast<uintptr_t>(g.C) & 15) || (g.c_bs * 4) % 16) return false;
-    if (EPI == EPI_RESIDUAL && (g.ldr % 4 || (reinterpret_cast<uintptr_t>(g.R) & 15) || (g.r_bs * 4) % 16)) return false;
+    if (!dma_operands_ok(g, BM, EPI == EPI_RESIDUAL)) return false;
     GemmArgs ga = g;
     ga.ntiles_n = cdiv(n, 64); ga.row_tiles = row_tiles; ga.row_tiles_all = row_tiles * branches;
     // small problems: 32-row tiles whose four waves split K (tcn_gemm_sk_kernel) while that launch has at most 6 workgroups per CU
@@ -953,15 +939,11 @@ __global__ __launch_bounds__(256) void tcn_dwconv_kernel(DwArgs g) {
     int plane, chunk;
     if (!xcd_decode(blockIdx.x, g.chunks, g.planes, plane, chunk)) return;
     const int branch = plane / g.B, utt = plane % g.B, t0 = chunk * DW_ROWS;
-    const double* st = g.gn_in + ((long)branch * g.B + utt) * kGnStride;
-    const double cnt = gn_count_of(g.gn_count, g.Tp, g.tpb, utt);
-    const double m = st[0] / cnt;
-    const double var = st[1] / cnt - m * m;
-    const float mean = (float)m;
     // the utterance's own frames: the conv's zero padding starts there (the NON-causal halo reads up to dilation frames ahead), and
     // frames past it are left out of the GroupNorm2 statistics
     const int tv = utt_frames(g.tpb, utt, g.Tp);
-    const float rstd = (float)(1.0 / sqrt((var > 0 ? var : 0) + (double)g.gn_eps));
+    const GnScalars n = gn_scalars(g.gn_in, branch, g.B, utt, g.gn_count, g.Tp, g.tpb, g.gn_eps);
+    const float mean = (float)n.m, rstd = (float)n.rs;
     const float slope = g.prelu[branch * g.prelu_bs];
     const float* __restrict__ Y1 = g.Y1 + branch * g.y_bs + (long)utt * g.Tp * g.CH;
     float* __restrict__ Y2 = g.Y2 + branch * g.y_bs + (long)utt * g.Tp * g.CH;
@@ -994,15 +976,7 @@ __global__ __launch_bounds__(256) void tcn_dwconv_kernel(DwArgs g) {
         s += (double)acc.x + (double)acc.y + (double)acc.z + (double)acc.w;
         q += (double)acc.x * acc.x + (double)acc.y * acc.y + (double)acc.z * acc.z + (double)acc.w * acc.w;
     }
-    s = wave_sum(s);
-    q = wave_sum(q);
-    if (lane == 0) { red[wave * 2] = s; red[wave * 2 + 1] = q; }
-    __syncthreads();
-    if (tid == 0) {
-        double* out = g.gn_out + ((long)branch * g.B + utt) * kGnStride;
-        atomicAdd(out, red[0] + red[2] + red[4] + red[6]);
-        atomicAdd(out + 1, red[1] + red[3] + red[5] + red[7]);
-    }
+    epi_stats_finish(g.gn_out, g.B, s, q, red, branch, utt, tid, lane, wave);
 }
 
 // ------------------------------------------------------------------------------------------------

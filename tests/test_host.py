@@ -357,7 +357,8 @@ def test_groupnorm_fold_algebra_of_the_dma_sconv_gemm():
 
 
 def test_dma_gemm_lds_image_is_a_conflict_free_permutation():
-    """csrc/tcn.hip tcn_gemm_dma_kernel, index arithmetic restated: the DMA writes lane-linear (piece base + 16 bytes x lane), so
+    """csrc/tcn.hip DmaImage<4> (the image of tcn_gemm_dma_kernel and tcn_gemm_sk_kernel: `swz`, `fetched`, `slot`), index arithmetic
+    restated: the DMA writes lane-linear (piece base + 16 bytes x lane), so
     lane l of a piece FETCHES row s >> 2, k-quad (s & 3) ^ swz(row) for slot s; readers take slot row * 4 + (kq ^ swz(row)).
     Checked here: every (row, k-quad) of the 128 x 16 A tile and the 64 x 16 B tile lands in exactly one slot, readers find
     the k-quad they ask for, the 16 lanes of each quarter of a ds_read_b128 touch 64 distinct LDS banks, and the k
@@ -406,6 +407,38 @@ def test_dma_gemm_k_loop_is_stripped_to_the_matrix_pipe():
         assert l["epi_load16"] == (8 if "ILi1E" in key else 0), (key, l)             # EPI_RESIDUAL: the eight residual rows
 
 
+def test_asm_diff_compares_a_gemm_k_loop_opcode_for_opcode(tmp_path):
+    """tools/asm_diff.py: a kernel without a depth-2 MFMA loop (the GEMMs of csrc/tcn.hip: the k-loop is the depth-1 loop) must keep
+    that loop opcode for opcode.  tcn.s against itself has no DIFFERENT kernel; with ONE ds_read_b128 of tcn_gemm_dma_kernel<1>'s
+    k-loop turned into another LDS read (every count and length of the loop unchanged) exactly that kernel is DIFFERENT."""
+    import importlib.util
+    mods = []
+    for name in ("asm_diff", "check_lstm_asm"):
+        spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tools", name + ".py"))
+        mods.append(importlib.util.module_from_spec(spec))
+        spec.loader.exec_module(mods[-1])
+    diff, chk = mods
+    text = chk._asm("tcn.hip", ("-fno-slp-vectorize",))
+    for d in ("parent", "same", "altered"):
+        os.mkdir(tmp_path / d)
+    sym = "_ZN4fsnp19tcn_gemm_dma_kernelILi1EEEvNS_8GemmArgsE"
+    start = text.index("\n" + sym + ":")
+    first_mfma = text.index("v_mfma", start)
+    at = text.index("ds_read_b128", first_mfma)            # the second k-tile's fragment reads: behind the first tile's MFMAs, in the loop
+    assert at < text.index(".Lfunc_end", start) and "v_mfma" in text[at:text.index(".Lfunc_end", start)]
+    altered = text[:at] + "ds_read_b96 " + text[at + len("ds_read_b128"):]
+    for d, t in (("parent", text), ("same", text), ("altered", altered)):
+        (tmp_path / d / "tcn.s").write_text(t)
+    parent = diff.kernels(str(tmp_path / "parent" / "tcn.s"))
+    assert len(parent) == 20 and sum(1 for k in parent.values() if k["k_loop"]) == 19        # every GEMM; the depthwise conv has no MFMA
+    rows, bad = diff.compare(parent, diff.kernels(str(tmp_path / "same" / "tcn.s")))
+    assert bad == 0 and all(r[1] == "identical" for r in rows), rows
+    rows, bad = diff.compare(parent, diff.kernels(str(tmp_path / "altered" / "tcn.s")))
+    different = [r for r in rows if r[1] == "DIFFERENT"]
+    assert bad == 1 and [r[0] for r in different] == [diff.short(sym)] and "depth-1 k-loop opcodes differ" in different[0][2], rows
+    assert all(r[1] == "identical" for r in rows if r[1] != "DIFFERENT")
+
+
 def test_float4_epilogue_covers_every_element_once():
     """csrc/tcn.hip EpiF4 / the staging loops of the three DMA GEMM kernels, restated: the accumulator layout of
     v_mfma_f32_32x32x2_f32 (lane -> column lane & 31, register q -> row (q & 3) + 8 (q >> 2) + 4 (lane >> 5)) written into a row-major
@@ -437,7 +470,8 @@ def test_float4_epilogue_covers_every_element_once():
 
 def test_dma64_gemm_image_column_ownership_and_asm():
     """csrc/tcn.hip tcn_gemm_dma64_kernel (round 4: the sconv GEMM on 64 x 64 tiles, column 256 on the VALU), restated:
-    * the LDS image [row][8 k-quads] XOR-swizzled by (row >> 1) & 7: the lane-linear DMA pieces (4 per wave and k-tile) cover every
+    * the LDS image [row][8 k-quads] XOR-swizzled by (row >> 1) & 7 (DmaImage<8>: `swz`, `fetched`, `slot`; the VALU column's k-quads
+      are `fetched(tid).kq` and `fetched(tid + 256).kq`): the lane-linear DMA pieces (4 per wave and k-tile) cover every
       (row, k-quad) of the 64 x 32 A tile and the 64 x 32 B tile exactly once, readers find the k-quad they ask for, the 16 lanes of
       each quarter of a ds_read_b128 touch 64 distinct banks, and the k permutation is shared by A and B and covers the 32 k of a tile;
     * the VALU column: thread -> slots tid and tid + 256 = rows tid >> 3 and 32 + (tid >> 3); the eight threads of a row hold its eight

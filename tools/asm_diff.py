@@ -6,7 +6,8 @@ in fullsubnet_plus_amd/_build.py).  Per kernel symbol the verdict is
   identical  the function's text and its metadata are equal (the `.file` lines and the function number in local labels aside), or
   (ii)       equal register / spill / scratch / LDS / kernarg figures, opcode-for-opcode equal depth-2 loops that hold an MFMA,
              a time loop (the depth-1 loop with the most MFMAs) that is not longer and holds the same number of MFMAs, 16-byte
-             buffer loads, LDS reads, LDS writes, barriers and waits, or
+             buffer loads, LDS reads, LDS writes, barriers and waits; a kernel WITHOUT a depth-2 MFMA loop (a GEMM: its k-loop is
+             the depth-1 loop) must keep that time loop opcode for opcode instead, or
   DIFFERENT  with the figures that differ.
 Exit status 1 if any kernel is DIFFERENT or missing on one side."""
 import os
@@ -69,8 +70,9 @@ def kernels(path):
         inner = [[x.split()[0] for x in instructions(body[a:b + 1])] for a, b in loops(body, 2) if cnt(body[a:b + 1], r"v_mfma")]
         outer = max(loops(body, 1), key=lambda ab: cnt(body[ab[0]:ab[1] + 1], r"v_mfma"), default=None)
         tl = body[outer[0]:outer[1] + 1] if outer else []
-        res[name] = dict(text=re.sub(r"\.LBB\d+_", ".LBB_", m.group(1)), meta=meta[name], inner=inner, time_loop=len(instructions(tl)),
-                         counts={p: cnt(tl, p) for p in COUNTED})
+        k_loop = [x.split()[0] for x in instructions(tl)] if not inner and cnt(tl, r"v_mfma") else None
+        res[name] = dict(text=re.sub(r"\.LBB\d+_", ".LBB_", m.group(1)), meta=meta[name], inner=inner, k_loop=k_loop,
+                         time_loop=len(instructions(tl)), counts={p: cnt(tl, p) for p in COUNTED})
     return res
 
 
@@ -101,6 +103,8 @@ def compare(old, new):
         why = [f"{k} {o['meta'][k]} -> {n['meta'][k]}" for k in META if o["meta"][k] != n["meta"][k]]
         if o["inner"] != n["inner"]:
             why.append("k-group loop opcodes differ")
+        if o["k_loop"] != n["k_loop"]:
+            why.append("depth-1 k-loop opcodes differ")
         if n["time_loop"] > o["time_loop"]:
             why.append(f"time loop {o['time_loop']} -> {n['time_loop']} instructions")
         why += [f"{p} in time loop {o['counts'][p]} -> {n['counts'][p]}" for p in COUNTED if o["counts"][p] != n["counts"][p]]

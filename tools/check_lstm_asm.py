@@ -51,6 +51,19 @@ def _kgroup_loops(body, **extra):
     return [l for l in loops if l["mfma"] > 0]
 
 
+def _gemm_spans(prefix, flags, lead=0):
+    """Every instantiation of the tcn.hip GEMM kernel whose mangled name starts with `prefix`, as
+    (name, whole body, k-loop, epilogue, count): the body without comment lines; the k-loop = the span from the first to the last MFMA
+    (plus `lead` instructions in front of the first: the fragment reads and DMA issue); the epilogue = everything behind the last MFMA;
+    count(segment, pattern) = instructions of the segment that match."""
+    text = _asm("tcn.hip", flags)
+    cnt = lambda seg, pat: sum(1 for x in seg if re.search(pat, x))
+    for m in re.finditer(r"^(" + re.escape(prefix) + r"\w+):[^\n]*\n(.*?)^\.Lfunc_end", text, re.S | re.M):
+        body = [l for l in m.group(2).split("\n") if l.strip() and not l.strip().startswith(";")]
+        idx = [i for i, l in enumerate(body) if "v_mfma" in l]
+        yield m.group(1), body, body[idx[0] - lead:idx[-1] + 1], body[idx[-1] + 1:], cnt
+
+
 def analyse(flags=("-fno-slp-vectorize",)):
     text = _asm("lstm.hip", flags)
     res = {}
@@ -156,15 +169,9 @@ def analyse_wave_owned(flags=("-fno-slp-vectorize",)):
 def analyse_splitk_gemm(flags=("-fno-slp-vectorize",)):
     """tcn_gemm_sk_kernel (tcn.hip), per instantiation: one k-tile body per wave (16 MFMAs, 6 fragment reads, 6 DMA pieces + the 6 of the
     first tile), no scratch, and NO workgroup barrier between the first and the last MFMA (a wave waits for its own DMA only)."""
-    text = _asm("tcn.hip", flags)
-    res = {}
-    for m in re.finditer(r"^(_ZN4fsnp18tcn_gemm_sk_kernel\w+):[^\n]*\n(.*?)^\.Lfunc_end", text, re.S | re.M):
-        name, body = m.group(1), [l for l in m.group(2).split("\n") if l.strip() and not l.strip().startswith(";")]
-        cnt = lambda seg, pat: sum(1 for x in seg if re.search(pat, x))
-        idx = [i for i, l in enumerate(body) if "v_mfma" in l]
-        res[name] = dict(mfma=cnt(body, r"v_mfma"), dma=cnt(body, r"buffer_load_dwordx4 .* lds"), scratch=cnt(body, r"scratch_"),
-                         barriers_between_mfmas=cnt(body[idx[0]:idx[-1] + 1], r"s_barrier"))
-    return res
+    return {name: dict(mfma=cnt(body, r"v_mfma"), dma=cnt(body, r"buffer_load_dwordx4 .* lds"), scratch=cnt(body, r"scratch_"),
+                       barriers_between_mfmas=cnt(loop, r"s_barrier"))
+            for name, body, loop, epi, cnt in _gemm_spans("_ZN4fsnp18tcn_gemm_sk_kernel", flags)}
 
 
 def analyse_generic(flags=("-fno-slp-vectorize",)):
@@ -190,42 +197,27 @@ def analyse_half_tile(flags=("-fno-slp-vectorize",)):
 
 def analyse_dma_gemm(flags=("-fno-slp-vectorize",)):
     """k-loop of tcn_gemm_dma_kernel (tcn.hip), per instantiation: per k-tile 16 MFMAs, 6 ds_read_b128, 3 LDS-DMA loads and two
-    offset selects - no ds_write, no scratch, no AGPR<->VGPR moves (counts over the span between the first and the last MFMA)."""
-    text = _asm("tcn.hip", flags)
-    res = {}
-    for m in re.finditer(r"^(_ZN4fsnp19tcn_gemm_dma_kernel\w+):[^\n]*\n(.*?)s_endpgm", text, re.S | re.M):
-        name, body = m.group(1), [l for l in m.group(2).split("\n") if l.strip() and not l.strip().startswith(";")]
-        idx = [i for i, l in enumerate(body) if "v_mfma" in l]            # the k-loop = everything between the first and the last MFMA
-        seg = body[idx[0] - 12:idx[-1] + 1]                               # (+ the fragment reads and DMA issue in front of the first)
-        cnt = lambda pat: sum(1 for x in seg if re.search(pat, x))
-        res[name] = dict(mfma=cnt(r"v_mfma"), ds_read=cnt(r"ds_read_b128"), dma=cnt(r"buffer_load_dwordx4 .* lds"), scratch=cnt(r"scratch_"),
-                         acc_moves=cnt(r"v_accvgpr"), valu=cnt(r"^\s+v_(?!mfma)"), ds_write=cnt(r"ds_write"))
-        # the epilogue = everything behind the last MFMA: 16-byte global traffic only, at most two full vmcnt drains (round 4: the
-        # accumulator tile is transposed through LDS so that a lane owns float4s along a row; before, the sconv epilogue was 32
-        # dependent 4-byte load -> add -> store round trips per lane)
-        epi = body[idx[-1] + 1:]
-        ecnt = lambda pat: sum(1 for x in epi if re.search(pat, x))
-        res[name].update(epi_drains=ecnt(r"vmcnt\(0\)"), epi_load16=ecnt(r"global_load_dwordx4"), epi_load4=ecnt(r"global_load_dword\s"),
-                         epi_store16=ecnt(r"global_store_dwordx4"), epi_store4=ecnt(r"global_store_dword\s"), epi_scratch=ecnt(r"scratch_"))
-    return res
+    offset selects - no ds_write, no scratch, no AGPR<->VGPR moves (counts over the span between the first and the last MFMA, plus
+    the fragment reads and DMA issue in front of the first).  The epilogue: 16-byte global traffic only, at most two full vmcnt
+    drains (round 4: the accumulator tile is transposed through LDS so that a lane owns float4s along a row; before, the sconv
+    epilogue was 32 dependent 4-byte load -> add -> store round trips per lane)."""
+    return {name: dict(mfma=cnt(loop, r"v_mfma"), ds_read=cnt(loop, r"ds_read_b128"), dma=cnt(loop, r"buffer_load_dwordx4 .* lds"),
+                       scratch=cnt(loop, r"scratch_"), acc_moves=cnt(loop, r"v_accvgpr"), valu=cnt(loop, r"^\s+v_(?!mfma)"),
+                       ds_write=cnt(loop, r"ds_write"), epi_drains=cnt(epi, r"vmcnt\(0\)"), epi_load16=cnt(epi, r"global_load_dwordx4"),
+                       epi_load4=cnt(epi, r"global_load_dword\s"), epi_store16=cnt(epi, r"global_store_dwordx4"),
+                       epi_store4=cnt(epi, r"global_store_dword\s"), epi_scratch=cnt(epi, r"scratch_"))
+            for name, body, loop, epi, cnt in _gemm_spans("_ZN4fsnp19tcn_gemm_dma_kernel", flags, lead=12)}
 
 
 def analyse_dma64_gemm(flags=("-fno-slp-vectorize",)):
     """tcn_gemm_dma64_kernel (tcn.hip, round 4): whole-kernel counts.  The k-loop body exists twice (two k-tiles per trip), each with 16
     MFMAs, 4 LDS-DMA pieces and 8 fragment reads (+ 4 reads of the VALU column's operands); no scratch, no AGPR<->VGPR moves; the epilogue
     moves 16-byte rows (4 residual loads + 4 stores per lane for the 64 x 64 tile, one float4 store per row of the VALU column)."""
-    text = _asm("tcn.hip", flags)
-    res = {}
-    for m in re.finditer(r"^(_ZN4fsnp21tcn_gemm_dma64_kernel\w+):[^\n]*\n(.*?)^\.Lfunc_end", text, re.S | re.M):
-        name, body = m.group(1), [l for l in m.group(2).split("\n") if l.strip() and not l.strip().startswith(";")]
-        idx = [i for i, l in enumerate(body) if "v_mfma" in l]
-        loop, epi = body[idx[0]:idx[-1] + 1], body[idx[-1] + 1:]
-        cnt = lambda seg, pat: sum(1 for x in seg if re.search(pat, x))
-        res[name] = dict(mfma=cnt(body, r"v_mfma_f32_32x32x2"), dma=cnt(body, r"buffer_load_dwordx4 .* lds"), scratch=cnt(body, r"scratch_"),
-                         acc_moves_in_loop=cnt(loop, r"v_accvgpr"), ds_write_in_loop=cnt(loop, r"ds_write"),
-                         epi_store16=cnt(epi, r"global_store_dwordx4"), epi_store4=cnt(epi, r"global_store_dword\s"),
-                         epi_load16=cnt(epi, r"global_load_dwordx4"), epi_drains=cnt(epi, r"vmcnt\(0\)"))
-    return res
+    return {name: dict(mfma=cnt(body, r"v_mfma_f32_32x32x2"), dma=cnt(body, r"buffer_load_dwordx4 .* lds"), scratch=cnt(body, r"scratch_"),
+                       acc_moves_in_loop=cnt(loop, r"v_accvgpr"), ds_write_in_loop=cnt(loop, r"ds_write"),
+                       epi_store16=cnt(epi, r"global_store_dwordx4"), epi_store4=cnt(epi, r"global_store_dword\s"),
+                       epi_load16=cnt(epi, r"global_load_dwordx4"), epi_drains=cnt(epi, r"vmcnt\(0\)"))
+            for name, body, loop, epi, cnt in _gemm_spans("_ZN4fsnp21tcn_gemm_dma64_kernel", flags)}
 
 
 if __name__ == "__main__":
