@@ -114,6 +114,40 @@ constexpr int kCoopCounterStride = 64;      // words per row tile
                                                            : ((which) ? (a).coop_bar2 : (a).coop_bar) + (tile))
 __host__ __device__ constexpr size_t coop_counter_bytes(int tiles) { return (size_t)tiles * kCoopCounterStride * 4; }
 __host__ __device__ constexpr int coop_tile_f4(int HID) { return 5 * (HID / 8) * 64 + 2 * (HID / 8) * 16; }
+// The map of that region: float4 offset of every part from the tile's base (x 16 = bytes), in the order they lie.  Every kernel
+// that addresses the region takes its offsets from here.
+template <int HID>
+struct CoopRegion {
+    static constexpr int img = (HID / 8) * 64;                 // float4 of one 32 x HID image
+    static constexpr int img_bytes = img * 16;
+    static constexpr int fc_f4 = 2 * (HID / 8) * 16;           // float4 of the Linear-partials slot
+    static constexpr int fc_floats = fc_f4 * 4;
+    static constexpr int h0_0 = 0, h0_1 = img, h1_0 = 2 * img, h1_1 = 3 * img, fc = 4 * img, h0_third = fc + fc_f4;
+    static constexpr int total = h0_third + img;
+    // The four double-buffered images lie one behind the other and have numbers: h0 of parity p is image p, h1 of parity p is
+    // image 2 + p.  h0_image / h1_image give the number; a kernel multiplies it by img or img_bytes.  h0 / h1 give the float4
+    // offset directly, in the caller's integer type (a size_t parity gives a 64-bit offset).  Both say the same; which one a
+    // kernel uses follows the parent's spelling of that kernel, because hipcc's code for the time loops follows the spelling
+    // (profiles/colsplit_shared.md).  h0_of3 is the h0 image m3 of the three the skewed schedules cycle through: the third lies
+    // behind the partials.
+    __host__ __device__ static constexpr int h0_image(int par) { return par; }
+    __host__ __device__ static constexpr int h1_image(int par) { return 2 + par; }
+    template <typename I> __host__ __device__ static constexpr I h0(I par) { return par * img; }
+    template <typename I> __host__ __device__ static constexpr I h1(I par) { return (2 + par) * img; }
+    __host__ __device__ static constexpr int h0_of3(int m3) { return m3 < 2 ? m3 * img : h0_third; }
+    static_assert(h0_1 == h0_0 + img && h1_0 == h0_1 + img && h1_1 == h1_0 + img && fc == h1_1 + img && h0_third == fc + fc_f4,
+                  "the parts lie in order and do not overlap");
+    static_assert(total == coop_tile_f4(HID), "the parts fill the region");
+};
+// (the selectors against the named offsets: checked outside the class, where its member functions are complete)
+template <int HID>
+constexpr bool coop_region_selectors_agree() {
+    using R = CoopRegion<HID>;
+    return R::h0(0) == R::h0_0 && R::h0(1) == R::h0_1 && R::h1(0) == R::h1_0 && R::h1(1) == R::h1_1 && R::h0_image(1) * R::img == R::h0(1) &&
+           R::h1_image(0) * R::img == R::h1(0) && R::h1_image(1) * R::img == R::h1(1) && R::h0_of3(0) == R::h0_0 && R::h0_of3(1) == R::h0_1 &&
+           R::h0_of3(2) == R::h0_third;
+}
+static_assert(coop_region_selectors_agree<256>() && coop_region_selectors_agree<384>() && coop_region_selectors_agree<512>(), "CoopRegion selectors");
 
 // ---- XCD-local placement of the column-split kernels' workgroups.  The S workgroups that share a row tile (a group)
 // exchange h through global memory every step; the dispatcher places workgroup id i on XCD i % 8, so with consecutive ids

@@ -25,6 +25,7 @@
 //     Linear(512, 257) + activation is one GEMM afterwards (tcn.hip).
 #include <cstdlib>
 
+#include "colsplit.h"
 #include "fsnp_common.h"
 #include "lstm_common.h"
 #include "lstm_launch.h"
@@ -120,201 +121,267 @@ __device__ __forceinline__ void coop_layer_resident(f32x16 (&acc)[NT], const flo
 
 constexpr int coop_units_index(int units) { return units == 8 ? 0 : units == 16 ? 1 : units == 32 ? 2 : 3; }
 
-}  // namespace
+// ---- what lstm2_coop_kernel and lstm2_coop_skew_kernel share: everything but their schedules.
 
-// GRU = true: nn.GRU instead of nn.LSTM (sequence_model.py:39-46).  The four column slots of a hidden unit are then
-// (r, z, n_x, n_h) - the host packs W_in only into the input part of K and W_hn only into the hidden part (zero blocks
-// elsewhere), so the MFMA loops are unchanged - and the per-unit state kept in registers is h itself:
-//   r = s(a_r), z = s(a_z), n = tanh(a_nx + r * a_nh), h' = (1 - z) n + z h          (torch.nn.GRU)
-template <int HID, int KX, int UNITS, bool SEQ, bool GRU>
-__global__ __launch_bounds__(256) void lstm2_coop_kernel(LstmWeights w, LstmArgs a) {
-    constexpr int NT = UNITS / 8;                  // 32-column accumulator tiles per workgroup
-    constexpr int NP = UNITS / 8;                  // (row, unit) pairs per thread in the cell update
-    constexpr int KGX = KX / 8, KGH = HID / 8;
-    constexpr int KGXP = (KGX + 3) / 4 * 4;        // x k-groups padded (zero weights, zero A) so that 4 waves split evenly
-    constexpr int G0W = (KGXP + KGH) / 4;          // local k-groups per wave, layer 0: [x | h0_{t-1}]
-    constexpr int G1W = KGH / 2;                   //                          layer 1: [h1_{t-1} | h0_t]
-    constexpr int S = HID / UNITS;
-    constexpr int HIMG = KGH * 64;                 // float4 per exchange image (32 rows x HID)
-    constexpr bool GATHER = KX <= 64;              // sub-band input built from att_mag / fb; else dense rows only
-    constexpr bool BIAS_REGS = UNITS <= 32;
+// shape of an instantiation
+template <int HID, int KX, int UNITS>
+struct CoopShape {
+    static constexpr int NT = UNITS / 8;                  // 32-column accumulator tiles per workgroup
+    static constexpr int NP = UNITS / 8;                  // (row, unit) pairs per thread in the cell update
+    static constexpr int KGX = KX / 8, KGH = HID / 8;
+    static constexpr int KGXP = (KGX + 3) / 4 * 4;        // x k-groups padded (zero weights, zero A) so that 4 waves split evenly
+    static constexpr int G0W = (KGXP + KGH) / 4;          // local k-groups per wave, layer 0: [x | h0_{t-1}]
+    static constexpr int G1W = KGH / 2;                   //                          layer 1: [h1_{t-1} | h0_t]
+    static constexpr int S = HID / UNITS;
+    static constexpr bool BIAS_REGS = UNITS <= 32;
     // weights resident in VGPRs (see coop_layer_resident): 152 (H = 384) / 228 (H = 512) registers at 8 units per workgroup.
     // Not at 16 units (304): half of them would live in AGPRs and be copied back before every MFMA - measured 16 % SLOWER.
-    constexpr bool WREG = NT * (G0W + G1W) * 4 <= 232;
+    static constexpr bool WREG = NT * (G0W + G1W) * 4 <= 232;
+    static_assert(2 * S * 64 <= CoopRegion<HID>::fc_floats, "Linear partials [parity][S][64] fit their slot of the exchange region");
+    // the dynamic-LDS image: byte offset of every part, in the order they lie
+    static constexpr size_t lds_x = 0;                                        // [KGXP][64] float4   A image of x_t
+    static constexpr size_t lds_red = lds_x + (size_t)KGXP * 64 * 16;         // [4 waves][NT][16][64] float
+    static constexpr size_t lds_rows = lds_red + (size_t)4 * NT * 16 * 64 * 4; // [32] RowDesc
+    static constexpr size_t lds_bytes() { return lds_rows + 32 * sizeof(RowDesc); }
+};
 
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    float4* Xs = reinterpret_cast<float4*>(smem_raw);                     // [KGXP][64] A image of x_t
-    float* red = reinterpret_cast<float*>(Xs + KGXP * 64);                // [4 waves][NT][16][64]
-    RowDesc* rows_s = reinterpret_cast<RowDesc*>(red + 4 * NT * 16 * 64); // [32]
-
+// the fills of the prologue: abort word, zeroed x image, the tile's row descriptors
+template <int KGXP>
+__device__ __forceinline__ void coop_fill(float4* Xs, RowDesc* rows_s, int& abort_s, const LstmArgs& a, int slot0) {
     const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // workgroup id -> (row tile, column slice).  Flat: consecutive ids = the S slices of one tile (spread over the 8 XCDs by
-    // the dispatcher's id % 8 placement).  XCD-local (a.coop_xcd = CUs per XCD): see lstm_common.h xcd_local_decode.
-    int rt = blockIdx.x / S, cs = blockIdx.x % S;
-    if (a.coop_xcd && !xcd_local_decode(blockIdx.x, S, a.num_tiles, a.coop_xcd, rt, cs)) return;
-    const int slot0 = rt * 32;
-    const int Tp = a.Tp;
-
-    // exchange region of this row tile: [h0 p0][h0 p1][h1 p0][h1 p1] images + FC partials [2][H/8][64]
-    float4* hx = reinterpret_cast<float4*>(a.coop_hx) + (size_t)rt * coop_tile_f4(HID);
-    float4* h0img[2] = {hx, hx + HIMG};
-    float4* h1img[2] = {hx + 2 * HIMG, hx + 3 * HIMG};
-    float* fcp = reinterpret_cast<float*>(hx + 4 * HIMG);                  // [2][S][64]
-    unsigned* bar = FSNP_COOP_BAR(a, rt, 0);
-
-    __shared__ int abort_s;                        // set by thread 0 when an inter-workgroup wait gives up
     if (tid == 0) abort_s = 0;
     for (int i = tid; i < KGXP * 64; i += 256) Xs[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     if (tid < 32) rows_s[tid] = a.rows[slot0 + tid];
     __syncthreads();
+}
 
-    // ---- input plan: thread owns row = tid & 31, features j = (tid >> 5) + 8 i
-    const bool dense = a.dense != nullptr;
-    const float* __restrict__ gbase = dense ? a.dense : a.att_mag;
-    const int gstep = dense ? a.dense_stride : a.FP;
-    constexpr int NG = KGX;
-    const int grow = tid & 31;
-    const int jrow = tid >> 5;
-    int goff[GATHER ? NG : 1];
-    int dbase = -1;                                   // dense-only variant: offset of (row, t = 0, j = 0)
-    NormMD md = {0.0f, 1.0f};
-    const NormMD* md_t = nullptr;                     // per-step table of this row (stride 1 in t)
-    {
-        const RowDesc rd = rows_s[grow];
-        if constexpr (GATHER) {
-#pragma unroll
-            for (int i = 0; i < NG; ++i) {
-                const int j = jrow + 8 * i;
-                int off = -1;
-                if (rd.valid && j < w.NIN) {
-                    if (dense) off = rd.b * Tp * gstep + j;
-                    else off = sb_feature_offset(j, rd.f, rd.b * Tp * a.FP, a.F, a.NSBN, a.NFBN, a.fb_rel, a.fb_branch_stride);
-                }
-                goff[i] = off;
-            }
-        } else {
-            goff[0] = 0;
-            if (rd.valid) dbase = rd.b * Tp * gstep;
-        }
-        if (rd.valid) {
-            if (a.md_seq != nullptr) md_t = a.md_seq + (size_t)rd.b * Tp;                            // [sequence][t]
-            else if (!dense && a.md_row != nullptr) md_t = a.md_row + (size_t)(slot0 + grow) * Tp;   // [slot][t]
-            else if (!dense) md = a.md_utt[rd.b];
-        }
-    }
-    auto x_valid = [&](int i) -> bool {
-        if constexpr (GATHER) return goff[i] >= 0;
-        else return dbase >= 0 && jrow + 8 * i < w.NIN;
-    };
-    auto x_load = [&](int i, int t) -> float {
-        if constexpr (GATHER) return goff[i] >= 0 ? gbase[goff[i] + t * gstep] : 0.0f;
-        else return x_valid(i) ? gbase[dbase + t * gstep + jrow + 8 * i] : 0.0f;
-    };
-    const int xdst0 = a_frag_index(grow, jrow);
-    float* Xf = reinterpret_cast<float*>(Xs);
-    {
-        const NormMD m0 = md_t ? md_t[0] : md;
-#pragma unroll
-        for (int i = 0; i < NG; ++i) Xf[xdst0 + i * 256] = x_valid(i) ? (x_load(i, 0) - m0.m) / m0.d : 0.0f;
-    }
-
-    // ---- this wave's private weight stream: [cs][wave][local k-group][tile][lane][4]
+// this wave's private weight stream: [cs][wave][local k-group][tile][lane][4]
+template <typename SH>
+__device__ __forceinline__ BufStream coop_weight_stream(const LstmWeights& w, int cs, int wave, int lane) {
     BufStream ws;
     ws.rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(w.wpack) + (size_t)(cs * 4 + wave) * (G0W + G1W) * NT * 256, 0, (G0W + G1W) * NT * 1024, 0x00020000);
+        const_cast<float*>(w.wpack) + (size_t)(cs * 4 + wave) * (SH::G0W + SH::G1W) * SH::NT * 256, 0, (SH::G0W + SH::G1W) * SH::NT * 1024, 0x00020000);
     ws.voff = lane * 16;
-    float4 bw0[WREG ? G0W : 1][NT], bw1[WREG ? G1W : 1][NT];
-    if constexpr (WREG) {
+    return ws;
+}
+template <typename SH>
+__device__ __forceinline__ void coop_load_resident(float4 (&bw0)[SH::WREG ? SH::G0W : 1][SH::NT], float4 (&bw1)[SH::WREG ? SH::G1W : 1][SH::NT],
+                                                   const BufStream& ws) {
+    if constexpr (SH::WREG) {
 #pragma unroll
-        for (int i = 0; i < G0W; ++i)
+        for (int i = 0; i < SH::G0W; ++i)
 #pragma unroll
-            for (int n = 0; n < NT; ++n) bw0[i][n] = wload<NT>(ws, i, n);
+            for (int n = 0; n < SH::NT; ++n) bw0[i][n] = wload<SH::NT>(ws, i, n);
 #pragma unroll
-        for (int i = 0; i < G1W; ++i)
+        for (int i = 0; i < SH::G1W; ++i)
 #pragma unroll
-            for (int n = 0; n < NT; ++n) bw1[i][n] = wload<NT>(ws, G0W + i, n);
+            for (int n = 0; n < SH::NT; ++n) bw1[i][n] = wload<SH::NT>(ws, SH::G0W + i, n);
     }
+}
+
+// partial tiles of the 4 waves -> LDS; afterwards coop_red_sum(idx) is the full pre-activation
+template <int NT>
+__device__ __forceinline__ void coop_publish_tiles(float* red, const f32x16 (&acc)[NT], int wave, int lane) {
+    __syncthreads();                       // previous readers of `red` are done
+#pragma unroll
+    for (int n = 0; n < NT; ++n)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) red[((wave * NT + n) * 16 + r) * 64 + lane] = acc[n][r];
+    __syncthreads();
+}
+template <int NT>
+__device__ __forceinline__ float coop_red_sum(const float* red, int idx) {
+    return red[idx] + red[idx + NT * 1024] + red[idx + 2 * NT * 1024] + red[idx + 3 * NT * 1024];
+}
+
+// one layer's cell update of pair i of this thread from the summed tiles: the state c (LSTM: c; GRU: h itself) and the layer's four
+// biases (gate-major at b: registers, or w.bias + layer * 4 HID + unit with STRIDE = HID).  Returns h.
+//   GRU: r = s(a_r), z = s(a_z), n = tanh(a_nx + r * a_nh), h' = (1 - z) n + z h          (torch.nn.GRU)
+template <int NT, bool GRU, int STRIDE>
+__device__ __forceinline__ float coop_cell(const float* red, const int (&pred)[4], const float* b, float& c) {
+    const float bi = b[0], bf = b[STRIDE], bg = b[2 * STRIDE], bo = b[3 * STRIDE];
+    float hval;
+    if constexpr (GRU) {
+        const float rg = fast_sigmoid(coop_red_sum<NT>(red, pred[0]) + bi);
+        const float zg = fast_sigmoid(coop_red_sum<NT>(red, pred[1]) + bf);
+        const float ng = fast_tanh(coop_red_sum<NT>(red, pred[2]) + bg + rg * (coop_red_sum<NT>(red, pred[3]) + bo));
+        hval = ng + zg * (c - ng);
+        c = hval;
+    } else {
+        const float ig = fast_sigmoid(coop_red_sum<NT>(red, pred[0]) + bi);
+        const float fg = fast_sigmoid(coop_red_sum<NT>(red, pred[1]) + bf);
+        const float gg = fast_tanh(coop_red_sum<NT>(red, pred[2]) + bg);
+        const float og = fast_sigmoid(coop_red_sum<NT>(red, pred[3]) + bo);
+        const float cn = fg * c + ig * gg;
+        c = cn;
+        hval = og * fast_tanh(cn);
+    }
+    return hval;
+}
+// all NP pairs of a layer; h goes through `emit`
+template <int HID, int NT, bool GRU, int NP, int NB, typename Emit>
+__device__ __forceinline__ void coop_cells(const float* red, const LstmWeights& w, const int (&pred)[NP][4], const int (&pk)[NP], float (&c)[NP],
+                                           const float (&bias)[NB][4], int layer, Emit emit) {
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+        float hval;
+        if constexpr (NB == NP) hval = coop_cell<NT, GRU, 1>(red, pred[i], bias[i], c[i]);          // biases in registers
+        else hval = coop_cell<NT, GRU, HID>(red, pred[i], w.bias + layer * 4 * HID + pk[i], c[i]);
+        emit(i, hval);
+    }
+}
+
+// ---- the two kernels' input plan and cell-ownership tables, written ONCE as text: moved into functions (CoopGather / CoopOwn structs,
+// colsplit.h's offset and norm functions) hipcc's code for 11 to 53 of the 102 instantiations came out with more registers or a longer
+// time loop (profiles/colsplit_shared.md), so the kernels share the tokens instead of a callee.
+// Input plan: thread owns row = tid & 31, features j = (tid >> 5) + 8 i.  GATHER: one offset per feature (sub-band input built from
+// att_mag / fb, or dense rows), -1 = zero; else dense rows only, one base offset dbase.  md / md_t: the row's norm source (one pair, or
+// a per-step table of its sequence [sequence][t] / its slot [slot][t]).  Ends with x_0 stored into the A image.
+//   requires: w, a, tid, rt, Tp, rows_s, Xs, and the constants GATHER, NG (the skew kernel sets GATHER = true: its dbase goes unused)
+//   defines : dense, gbase, gstep, grow, jrow, goff[], dbase, md, md_t, x_valid(i), x_load(i, t), xdst0, Xf
+#define COOP_INPUT_PLAN() \
+    const bool dense = a.dense != nullptr;                                                                                       \
+    const float* __restrict__ gbase = dense ? a.dense : a.att_mag;                                                               \
+    const int gstep = dense ? a.dense_stride : a.FP;                                                                             \
+    const int grow = tid & 31;                                                                                                   \
+    const int jrow = tid >> 5;                                                                                                   \
+    int goff[GATHER ? NG : 1];                                                                                                   \
+    int dbase = -1;                                                                                                              \
+    NormMD md = {0.0f, 1.0f};                                                                                                    \
+    const NormMD* md_t = nullptr;                                                                                                \
+    {                                                                                                                            \
+        const RowDesc rd = rows_s[grow];                                                                                         \
+        if constexpr (GATHER) {                                                                                                  \
+_Pragma("unroll")                                                                                                                \
+            for (int i = 0; i < NG; ++i) {                                                                                       \
+                const int j = jrow + 8 * i;                                                                                      \
+                int off = -1;                                                                                                    \
+                if (rd.valid && j < w.NIN) {                                                                                     \
+                    if (dense) off = rd.b * Tp * gstep + j;                                                                      \
+                    else off = sb_feature_offset(j, rd.f, rd.b * Tp * a.FP, a.F, a.NSBN, a.NFBN, a.fb_rel, a.fb_branch_stride);  \
+                }                                                                                                                \
+                goff[i] = off;                                                                                                   \
+            }                                                                                                                    \
+        } else {                                                                                                                 \
+            goff[0] = 0;                                                                                                         \
+            if (rd.valid) dbase = rd.b * Tp * gstep;                                                                             \
+        }                                                                                                                        \
+        if (rd.valid) {                                                                                                          \
+            if (a.md_seq != nullptr) md_t = a.md_seq + (size_t)rd.b * Tp;                                                        \
+            else if (!dense && a.md_row != nullptr) md_t = a.md_row + (size_t)(rt * 32 + grow) * Tp;                             \
+            else if (!dense) md = a.md_utt[rd.b];                                                                                \
+        }                                                                                                                        \
+    }                                                                                                                            \
+    auto x_valid = [&](int i) -> bool {                                                                                          \
+        if constexpr (GATHER) return goff[i] >= 0;                                                                               \
+        else return dbase >= 0 && jrow + 8 * i < w.NIN;                                                                          \
+    };                                                                                                                           \
+    auto x_load = [&](int i, int t) -> float {                                                                                   \
+        if constexpr (GATHER) return goff[i] >= 0 ? gbase[goff[i] + t * gstep] : 0.0f;                                           \
+        else return x_valid(i) ? gbase[dbase + t * gstep + jrow + 8 * i] : 0.0f;                                                 \
+    };                                                                                                                           \
+    const int xdst0 = a_frag_index(grow, jrow);                                                                                  \
+    float* Xf = reinterpret_cast<float*>(Xs);                                                                                    \
+    {                                                                                                                            \
+        const NormMD m0 = md_t ? md_t[0] : md;                                                                                   \
+_Pragma("unroll")                                                                                                                \
+        for (int i = 0; i < NG; ++i) Xf[xdst0 + i * 256] = x_valid(i) ? (x_load(i, 0) - m0.m) / m0.d : 0.0f;                     \
+    }
+// Cell-update ownership: pair p = tid + 256 i -> unit u = p % UNITS (fastest: conflict-free LDS reads), row = p / UNITS.  In the
+// accumulator layout (row, column j) sits in tile j / 32, register (row & 3) + 4 (row >> 3), lane (j & 31) + 32 ((row >> 2) & 1).
+//   requires: w, tid, cs, and the constants SH, NP, UNITS, HID, FCW (the kernel has a Linear epilogue)
+//   defines : BIAS_REGS, prow[], pk[], pred[][4], bias0[][4], bias1[][4], wfc0[], wfc1[]
+#define COOP_OWNERSHIP_TABLES() \
+    constexpr bool BIAS_REGS = SH::BIAS_REGS;                                                                        \
+    int prow[NP], pk[NP], pred[NP][4];                                                                               \
+    float bias0[BIAS_REGS ? NP : 1][4], bias1[BIAS_REGS ? NP : 1][4];                                                \
+    float wfc0[FCW ? NP : 1], wfc1[FCW ? NP : 1];                                                                    \
+_Pragma("unroll")                                                                                                    \
+    for (int i = 0; i < NP; ++i) {                                                                                   \
+        const int p = tid + 256 * i;                                                                                 \
+        const int u = p % UNITS, row = p / UNITS;                                                                    \
+        prow[i] = row;                                                                                               \
+        pk[i] = cs * UNITS + u;                                                                                      \
+_Pragma("unroll")                                                                                                    \
+        for (int gate = 0; gate < 4; ++gate) {                                                                       \
+            const int j = gate * UNITS + u;                                                                          \
+            pred[i][gate] = (((j >> 5) * 16) + (row & 3) + 4 * (row >> 3)) * 64 + (j & 31) + 32 * ((row >> 2) & 1);  \
+            if constexpr (BIAS_REGS) {                                                                               \
+                bias0[i][gate] = w.bias[gate * HID + pk[i]];                                                         \
+                bias1[i][gate] = w.bias[4 * HID + gate * HID + pk[i]];                                               \
+            }                                                                                                        \
+        }                                                                                                            \
+        if constexpr (FCW) {                                                                                         \
+            wfc0[i] = w.wfc[pk[i]];                                                                                  \
+            wfc1[i] = w.wfc[HID + pk[i]];                                                                            \
+        }                                                                                                            \
+    }                                                                                                                \
+    if constexpr (!BIAS_REGS) { bias0[0][0] = 0.f; bias1[0][0] = 0.f; }                                              \
+    if constexpr (!FCW) { wfc0[0] = 0.f; wfc1[0] = 0.f; }
+
+}  // namespace
+
+// GRU = true: nn.GRU instead of nn.LSTM (sequence_model.py:39-46).  The four column slots of a hidden unit are then
+// (r, z, n_x, n_h) - the host packs W_in only into the input part of K and W_hn only into the hidden part (zero blocks
+// elsewhere), so the MFMA loops are unchanged - and the per-unit state kept in registers is h itself.
+template <int HID, int KX, int UNITS, bool SEQ, bool GRU>
+__global__ __launch_bounds__(256) void lstm2_coop_kernel(LstmWeights w, LstmArgs a) {
+    using SH = CoopShape<HID, KX, UNITS>;
+    using R = CoopRegion<HID>;
+    constexpr int NT = SH::NT, NP = SH::NP, KGXP = SH::KGXP, KGH = SH::KGH, G0W = SH::G0W, G1W = SH::G1W, S = SH::S;
+    constexpr bool GATHER = KX <= 64;              // sub-band input built from att_mag / fb; else dense rows only
+    constexpr bool WREG = SH::WREG;
+    constexpr int NG = SH::KGX;
+
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    float4* Xs = reinterpret_cast<float4*>(smem_raw + SH::lds_x);
+    float* red = reinterpret_cast<float*>(smem_raw + SH::lds_red);
+    RowDesc* rows_s = reinterpret_cast<RowDesc*>(smem_raw + SH::lds_rows);
+    __shared__ int abort_s;                        // set by thread 0 when an inter-workgroup wait gives up
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    int rt = blockIdx.x / S, cs = blockIdx.x % S;
+    if (a.coop_xcd && !xcd_local_decode(blockIdx.x, S, a.num_tiles, a.coop_xcd, rt, cs)) return;
+    const int Tp = a.Tp;
+
+    float4* hx = reinterpret_cast<float4*>(a.coop_hx) + (size_t)rt * R::total;
+    float4* h0img[2] = {hx + R::h0(0), hx + R::h0(1)};
+    float4* h1img[2] = {hx + R::h1(0), hx + R::h1(1)};
+    float* fcp = reinterpret_cast<float*>(hx + R::fc);                     // [2][S][64]
+    unsigned* bar = FSNP_COOP_BAR(a, rt, 0);
+
+    coop_fill<KGXP>(Xs, rows_s, abort_s, a, rt * 32);
+    COOP_INPUT_PLAN();
+
+    const BufStream ws = coop_weight_stream<SH>(w, cs, wave, lane);
+    float4 bw0[WREG ? G0W : 1][NT], bw1[WREG ? G1W : 1][NT];
+    coop_load_resident<SH>(bw0, bw1, ws);
     const float4* Xw = Xs + wave * 64 + lane;           // local group i of this wave = global k-group 4 i + wave
     // A operands from the exchange images: buffer loads too (a flat load would make hipcc drain vmcnt AND lgkmcnt)
     BufStream hs;
-    hs.rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(hx), 0, 4 * HIMG * 16, 0x00020000);
+    hs.rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(hx), 0, R::fc * 16, 0x00020000);
     hs.voff = (wave * 64 + lane) * 16;
-    auto hload = [&](int image, int i) -> float4 {      // image: 0/1 = h0 parity 0/1, 2/3 = h1 parity 0/1
-        return stream_load<kSc1>(hs, image * (HIMG * 16) + i * 4096);
+    auto hload = [&](int off_f4, int i) -> float4 {     // local k-group i (global 4 i + wave) of the image at float4 offset off_f4
+        return stream_load<kSc1>(hs, off_f4 * 16 + i * 4096);
     };
 
-    // ---- cell update ownership: pair p = tid + 256 i  ->  unit u = p % UNITS (fastest: conflict-free LDS reads),
-    //      row = p / UNITS.  In the accumulator layout (row, column j) sits in tile j / 32, register
-    //      (row & 3) + 4 (row >> 3), lane (j & 31) + 32 ((row >> 2) & 1).
-    int prow[NP], pk[NP], pred[NP][4];
+    constexpr bool FCW = !SEQ;
+    COOP_OWNERSHIP_TABLES();
     float c0[NP], c1[NP];
-    float bias0[BIAS_REGS ? NP : 1][4], bias1[BIAS_REGS ? NP : 1][4];
-    float wfc0[SEQ ? 1 : NP], wfc1[SEQ ? 1 : NP];
 #pragma unroll
-    for (int i = 0; i < NP; ++i) {
-        const int p = tid + 256 * i;
-        const int u = p % UNITS, row = p / UNITS;
-        prow[i] = row;
-        pk[i] = cs * UNITS + u;
-        c0[i] = 0.f; c1[i] = 0.f;
-#pragma unroll
-        for (int gate = 0; gate < 4; ++gate) {
-            const int j = gate * UNITS + u;
-            pred[i][gate] = (((j >> 5) * 16) + (row & 3) + 4 * (row >> 3)) * 64 + (j & 31) + 32 * ((row >> 2) & 1);
-            if constexpr (BIAS_REGS) {
-                bias0[i][gate] = w.bias[gate * HID + pk[i]];
-                bias1[i][gate] = w.bias[4 * HID + gate * HID + pk[i]];
-            }
-        }
-        if constexpr (!SEQ) {
-            wfc0[i] = w.wfc[pk[i]];
-            wfc1[i] = w.wfc[HID + pk[i]];
-        }
-    }
-    if constexpr (!BIAS_REGS) { bias0[0][0] = 0.f; bias1[0][0] = 0.f; }
-    if constexpr (SEQ) { wfc0[0] = 0.f; wfc1[0] = 0.f; }
-
-    // partial tiles of the 4 waves -> LDS; afterwards red_sum(idx) is the full pre-activation
-    auto publish_tiles = [&](f32x16 (&acc)[NT]) {
-        __syncthreads();                       // previous readers of `red` are done
-#pragma unroll
-        for (int n = 0; n < NT; ++n)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) red[((wave * NT + n) * 16 + r) * 64 + lane] = acc[n][r];
-        __syncthreads();
-    };
-    auto red_sum = [&](int idx) -> float {
-        return red[idx] + red[idx + NT * 1024] + red[idx + 2 * NT * 1024] + red[idx + 3 * NT * 1024];
-    };
-
-    // returns false (to every thread) once the launch is aborted: a peer never arrived (lstm_common.h: xchg_wait)
-    auto inter_wg_barrier = [&](unsigned target) -> bool {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // every storing wave drains its stores
-        __syncthreads();
-        if (tid == 0) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __hip_atomic_fetch_add(bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (!xchg_wait(bar, target, a.coop_abort, a.coop_err)) abort_s = 1;
-        }
-        __syncthreads();
-        return abort_s == 0;
-    };
+    for (int i = 0; i < NP; ++i) { c0[i] = 0.f; c1[i] = 0.f; }
+    auto red_sum = [&](int idx) -> float { return coop_red_sum<NT>(red, idx); };
+    auto inter_wg_barrier = [&](unsigned target) -> bool { return wg_barrier(bar, target, a, tid, abort_s); };
     auto fc_epilogue = [&](int t_done) {     // workgroup cs == 0 sums the S partials of step t_done in a fixed order
-        if (cs == 0 && tid < 64) {
-            const int row = tid & 31, o = tid >> 5;
-            const RowDesc rd = rows_s[row];
-            const float* part = fcp + (size_t)(t_done & 1) * S * 64;
-            float sum = w.bfc[o];
-            for (int p = 0; p < S; ++p) sum += xchg_load(part + p * 64 + o * 32 + row);
-            if (rd.valid && t_done >= a.LA)
-                a.out[(size_t)rd.out_off + (size_t)o * a.out_stride_o + (t_done - a.LA)] = apply_act(sum, a.act);
-        }
+        if (cs == 0 && tid < 64) colsplit_fc_sum<S>(w, a, rows_s, fcp + (size_t)(t_done & 1) * S * 64, t_done);
     };
 
     __syncthreads();
 
+    // Serial schedule.  (The cells are written out per layer: through coop_cell one instantiation's time loop grows, through
+    //  coop_cells every instantiation needs 2 to 8 more registers - profiles/colsplit_shared.md.)
     for (int t = 0; t < Tp; ++t) {
         const int cur = t & 1, prv = cur ^ 1;
         chaos_delay(a.coop_chaos, t, 0);
@@ -336,17 +403,17 @@ __global__ __launch_bounds__(256) void lstm2_coop_kernel(LstmWeights w, LstmArgs
             for (int r = 0; r < 16; ++r) acc[n][r] = 0.0f;
         if constexpr (WREG)
             coop_layer_resident<NT, G0W, KGXP / 4>(acc, bw0, [&](int i) -> float4 { return Xw[i * 256]; },
-                                                   [&](int i) -> float4 { return hload(prv, i); });
+                                                   [&](int i) -> float4 { return hload(R::h0(prv), i); });
         else
             coop_layer<NT, G0W, KGXP / 4, 0>(acc, ws, [&](int i) -> float4 { return Xw[i * 256]; },
-                                             [&](int i) -> float4 { return hload(prv, i); });
-        publish_tiles(acc);
+                                             [&](int i) -> float4 { return hload(R::h0(prv), i); });
+        coop_publish_tiles<NT>(red, acc, wave, lane);
         {
             float* img = reinterpret_cast<float*>(h0img[cur]);
 #pragma unroll
             for (int i = 0; i < NP; ++i) {
                 float bi, bf, bg, bo;
-                if constexpr (BIAS_REGS) { bi = bias0[i][0]; bf = bias0[i][1]; bg = bias0[i][2]; bo = bias0[i][3]; }
+                if constexpr (SH::BIAS_REGS) { bi = bias0[i][0]; bf = bias0[i][1]; bg = bias0[i][2]; bo = bias0[i][3]; }
                 else { bi = w.bias[pk[i]]; bf = w.bias[HID + pk[i]]; bg = w.bias[2 * HID + pk[i]]; bo = w.bias[3 * HID + pk[i]]; }
                 float hval;
                 if constexpr (GRU) {
@@ -384,18 +451,18 @@ __global__ __launch_bounds__(256) void lstm2_coop_kernel(LstmWeights w, LstmArgs
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[n][r] = 0.0f;
         if constexpr (WREG)
-            coop_layer_resident<NT, G1W, KGH / 4>(acc, bw1, [&](int i) -> float4 { return hload(2 + prv, i); },
-                                                  [&](int i) -> float4 { return hload(cur, i); });
+            coop_layer_resident<NT, G1W, KGH / 4>(acc, bw1, [&](int i) -> float4 { return hload(R::h1(prv), i); },
+                                                  [&](int i) -> float4 { return hload(R::h0(cur), i); });
         else
-            coop_layer<NT, G1W, KGH / 4, G0W>(acc, ws, [&](int i) -> float4 { return hload(2 + prv, i); },
-                                              [&](int i) -> float4 { return hload(cur, i); });
-        publish_tiles(acc);
+            coop_layer<NT, G1W, KGH / 4, G0W>(acc, ws, [&](int i) -> float4 { return hload(R::h1(prv), i); },
+                                              [&](int i) -> float4 { return hload(R::h0(cur), i); });
+        coop_publish_tiles<NT>(red, acc, wave, lane);
         {
             float* img = reinterpret_cast<float*>(h1img[cur]);
 #pragma unroll
             for (int i = 0; i < NP; ++i) {
                 float bi, bf, bg, bo;
-                if constexpr (BIAS_REGS) { bi = bias1[i][0]; bf = bias1[i][1]; bg = bias1[i][2]; bo = bias1[i][3]; }
+                if constexpr (SH::BIAS_REGS) { bi = bias1[i][0]; bf = bias1[i][1]; bg = bias1[i][2]; bo = bias1[i][3]; }
                 else {
                     bi = w.bias[4 * HID + pk[i]]; bf = w.bias[5 * HID + pk[i]];
                     bg = w.bias[6 * HID + pk[i]]; bo = w.bias[7 * HID + pk[i]];
@@ -457,21 +524,17 @@ __global__ __launch_bounds__(256) void lstm2_coop_kernel(LstmWeights w, LstmArgs
 // b1 wait of C_{t+1}: two buffers.  Same arithmetic and summation order as lstm2_coop_kernel: results are bit-identical.
 template <int HID, int KX, int UNITS, bool GRU>
 __global__ __launch_bounds__(256) void lstm2_coop_skew_kernel(LstmWeights w, LstmArgs a) {
-    constexpr int NT = UNITS / 8, NP = UNITS / 8;
-    constexpr int KGX = KX / 8, KGH = HID / 8;
-    constexpr int KGXP = (KGX + 3) / 4 * 4;
-    constexpr int G0W = (KGXP + KGH) / 4, G1W = KGH / 2;
-    constexpr int S = HID / UNITS;
-    constexpr int HIMG = KGH * 64;
-    constexpr int FCP4 = 2 * (HID / 8) * 16;
-    constexpr bool BIAS_REGS = UNITS <= 32;
-    constexpr bool WREG = NT * (G0W + G1W) * 4 <= 232;
+    using SH = CoopShape<HID, KX, UNITS>;
+    using R = CoopRegion<HID>;
+    constexpr int NT = SH::NT, NP = SH::NP, KGXP = SH::KGXP, KGH = SH::KGH, G0W = SH::G0W, G1W = SH::G1W, S = SH::S;
+    constexpr bool WREG = SH::WREG;
+    constexpr int NG = SH::KGX;
     static_assert(KX <= 64, "gathered sub-band input");
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    float4* Xs = reinterpret_cast<float4*>(smem_raw);                     // [KGXP][64] A image of x_t
-    float* red = reinterpret_cast<float*>(Xs + KGXP * 64);                // [4 waves][NT][16][64]
-    RowDesc* rows_s = reinterpret_cast<RowDesc*>(red + 4 * NT * 16 * 64); // [32]
+    float4* Xs = reinterpret_cast<float4*>(smem_raw + SH::lds_x);
+    float* red = reinterpret_cast<float*>(smem_raw + SH::lds_red);
+    RowDesc* rows_s = reinterpret_cast<RowDesc*>(smem_raw + SH::lds_rows);
     __shared__ int abort_s;
 
     const int tid = threadIdx.x;
@@ -479,170 +542,39 @@ __global__ __launch_bounds__(256) void lstm2_coop_skew_kernel(LstmWeights w, Lst
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int rt = blockIdx.x / S, cs = blockIdx.x % S;
     if (a.coop_xcd && !xcd_local_decode(blockIdx.x, S, a.num_tiles, a.coop_xcd, rt, cs)) return;
-    const int slot0 = rt * 32;
     const int Tp = a.Tp;
 
-    float4* hx = reinterpret_cast<float4*>(a.coop_hx) + (size_t)rt * coop_tile_f4(HID);
-    // float4 offsets of the images inside the tile's region (lstm_common.h: coop_tile_f4)
-    auto h0off = [](int m3) -> int { return m3 < 2 ? m3 * HIMG : 4 * HIMG + FCP4; };
-    auto h1off = [](int par) -> int { return (2 + par) * HIMG; };
-    float* fcp = reinterpret_cast<float*>(hx + 4 * HIMG);                  // [2][S][64]
+    float4* hx = reinterpret_cast<float4*>(a.coop_hx) + (size_t)rt * R::total;
+    float* fcp = reinterpret_cast<float*>(hx + R::fc);                     // [2][S][64]
     unsigned* bar0 = FSNP_COOP_BAR(a, rt, 0);
     unsigned* bar1 = FSNP_COOP_BAR(a, rt, 1);
 
-    if (tid == 0) abort_s = 0;
-    for (int i = tid; i < KGXP * 64; i += 256) Xs[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (tid < 32) rows_s[tid] = a.rows[slot0 + tid];
-    __syncthreads();
+    coop_fill<KGXP>(Xs, rows_s, abort_s, a, rt * 32);
+    constexpr bool GATHER = true;
+    COOP_INPUT_PLAN();
 
-    // ---- input plan: thread owns row = tid & 31, features j = (tid >> 5) + 8 i
-    const bool dense = a.dense != nullptr;
-    const float* __restrict__ gbase = dense ? a.dense : a.att_mag;
-    const int gstep = dense ? a.dense_stride : a.FP;
-    constexpr int NG = KGX;
-    const int grow = tid & 31, jrow = tid >> 5;
-    int goff[NG];
-    NormMD md = {0.0f, 1.0f};
-    const NormMD* md_t = nullptr;
-    {
-        const RowDesc rd = rows_s[grow];
-#pragma unroll
-        for (int i = 0; i < NG; ++i) {
-            const int j = jrow + 8 * i;
-            int off = -1;
-            if (rd.valid && j < w.NIN) {
-                if (dense) off = rd.b * Tp * gstep + j;
-                else off = sb_feature_offset(j, rd.f, rd.b * Tp * a.FP, a.F, a.NSBN, a.NFBN, a.fb_rel, a.fb_branch_stride);
-            }
-            goff[i] = off;
-        }
-        if (rd.valid) {
-            if (a.md_seq != nullptr) md_t = a.md_seq + (size_t)rd.b * Tp;
-            else if (!dense && a.md_row != nullptr) md_t = a.md_row + (size_t)(slot0 + grow) * Tp;
-            else if (!dense) md = a.md_utt[rd.b];
-        }
-    }
-    auto x_load = [&](int i, int t) -> float { return goff[i] >= 0 ? gbase[goff[i] + t * gstep] : 0.0f; };
-    const int xdst0 = a_frag_index(grow, jrow);
-    float* Xf = reinterpret_cast<float*>(Xs);
-    {
-        const NormMD m0 = md_t ? md_t[0] : md;
-#pragma unroll
-        for (int i = 0; i < NG; ++i) Xf[xdst0 + i * 256] = goff[i] >= 0 ? (x_load(i, 0) - m0.m) / m0.d : 0.0f;
-    }
-
-    BufStream ws;
-    ws.rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(w.wpack) + (size_t)(cs * 4 + wave) * (G0W + G1W) * NT * 256, 0, (G0W + G1W) * NT * 1024, 0x00020000);
-    ws.voff = lane * 16;
+    const BufStream ws = coop_weight_stream<SH>(w, cs, wave, lane);
     float4 bw0[WREG ? G0W : 1][NT], bw1[WREG ? G1W : 1][NT];
-    if constexpr (WREG) {
-#pragma unroll
-        for (int i = 0; i < G0W; ++i)
-#pragma unroll
-            for (int n = 0; n < NT; ++n) bw0[i][n] = wload<NT>(ws, i, n);
-#pragma unroll
-        for (int i = 0; i < G1W; ++i)
-#pragma unroll
-            for (int n = 0; n < NT; ++n) bw1[i][n] = wload<NT>(ws, G0W + i, n);
-    }
+    coop_load_resident<SH>(bw0, bw1, ws);
     const float4* Xw = Xs + wave * 64 + lane;
     BufStream hs;
-    hs.rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(hx), 0, coop_tile_f4(HID) * 16, 0x00020000);
+    hs.rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(hx), 0, R::total * 16, 0x00020000);
     hs.voff = (wave * 64 + lane) * 16;
     auto hload = [&](int off_f4, int i) -> float4 {      // local k-group i (global 4 i + wave) of the image at float4 offset off_f4
         return stream_load<kSc1>(hs, off_f4 * 16 + i * 4096);
     };
 
-    int prow[NP], pk[NP], pred[NP][4];
+    constexpr bool FCW = true;
+    COOP_OWNERSHIP_TABLES();
     float c0[NP], c1[NP];
-    float bias0[BIAS_REGS ? NP : 1][4], bias1[BIAS_REGS ? NP : 1][4];
-    float wfc0[NP], wfc1[NP];
 #pragma unroll
-    for (int i = 0; i < NP; ++i) {
-        const int p = tid + 256 * i;
-        const int u = p % UNITS, row = p / UNITS;
-        prow[i] = row;
-        pk[i] = cs * UNITS + u;
-        c0[i] = 0.f; c1[i] = 0.f;
-#pragma unroll
-        for (int gate = 0; gate < 4; ++gate) {
-            const int j = gate * UNITS + u;
-            pred[i][gate] = (((j >> 5) * 16) + (row & 3) + 4 * (row >> 3)) * 64 + (j & 31) + 32 * ((row >> 2) & 1);
-            if constexpr (BIAS_REGS) {
-                bias0[i][gate] = w.bias[gate * HID + pk[i]];
-                bias1[i][gate] = w.bias[4 * HID + gate * HID + pk[i]];
-            }
-        }
-        wfc0[i] = w.wfc[pk[i]];
-        wfc1[i] = w.wfc[HID + pk[i]];
-    }
-    if constexpr (!BIAS_REGS) { bias0[0][0] = 0.f; bias1[0][0] = 0.f; }
-
-    auto publish_tiles = [&](f32x16 (&acc)[NT]) {
-        __syncthreads();
-#pragma unroll
-        for (int n = 0; n < NT; ++n)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) red[((wave * NT + n) * 16 + r) * 64 + lane] = acc[n][r];
-        __syncthreads();
-    };
-    auto red_sum = [&](int idx) -> float { return red[idx] + red[idx + NT * 1024] + red[idx + 2 * NT * 1024] + red[idx + 3 * NT * 1024]; };
+    for (int i = 0; i < NP; ++i) { c0[i] = 0.f; c1[i] = 0.f; }
     // one layer's cell update of this thread's NP (row, unit) pairs from the summed tiles; returns h through `emit`
-    auto cell = [&](float (&c)[NP], const float (&bias)[BIAS_REGS ? NP : 1][4], int layer, auto emit) {
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            float bi, bf, bg, bo;
-            if constexpr (BIAS_REGS) { bi = bias[i][0]; bf = bias[i][1]; bg = bias[i][2]; bo = bias[i][3]; }
-            else {
-                const float* b = w.bias + layer * 4 * HID + pk[i];
-                bi = b[0]; bf = b[HID]; bg = b[2 * HID]; bo = b[3 * HID];
-            }
-            float hval;
-            if constexpr (GRU) {
-                const float rg = fast_sigmoid(red_sum(pred[i][0]) + bi);
-                const float zg = fast_sigmoid(red_sum(pred[i][1]) + bf);
-                const float ng = fast_tanh(red_sum(pred[i][2]) + bg + rg * (red_sum(pred[i][3]) + bo));
-                hval = ng + zg * (c[i] - ng);
-                c[i] = hval;
-            } else {
-                const float ig = fast_sigmoid(red_sum(pred[i][0]) + bi);
-                const float fg = fast_sigmoid(red_sum(pred[i][1]) + bf);
-                const float gg = fast_tanh(red_sum(pred[i][2]) + bg);
-                const float og = fast_sigmoid(red_sum(pred[i][3]) + bo);
-                const float cn = fg * c[i] + ig * gg;
-                c[i] = cn;
-                hval = og * fast_tanh(cn);
-            }
-            emit(i, hval);
-        }
-    };
-    // split-phase barrier: arrive now, wait a phase later
-    auto arrive = [&](unsigned* bar) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // every storing wave drains its write-through stores
-        __syncthreads();
-        if (tid == 0) __hip_atomic_fetch_add(bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    };
-    // `early` = the counter as thread 0 read it at the end of the previous MFMA phase (poll_early): in lockstep it is already
-    // complete, and the wait costs one __syncthreads instead of a fabric round trip
-    auto poll_early = [&](unsigned* bar) -> unsigned {
-        return tid == 0 ? __hip_atomic_load(bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-    };
-    auto wait_for = [&](unsigned* bar, unsigned target, unsigned early) -> bool {
-        if (tid == 0 && early < target && !xchg_wait(bar, target, a.coop_abort, a.coop_err)) abort_s = 1;
-        __syncthreads();
-        return abort_s == 0;
+    auto cell = [&](float (&c)[NP], const float (&bias)[SH::BIAS_REGS ? NP : 1][4], int layer, auto emit) {
+        coop_cells<HID, NT, GRU>(red, w, pred, pk, c, bias, layer, emit);
     };
     auto fc_epilogue = [&](int t_done) {     // slice 0 sums the S partials of step t_done in a fixed order
-        if (cs == 0 && tid < 64) {
-            const int row = tid & 31, o = tid >> 5;
-            const RowDesc rd = rows_s[row];
-            const float* part = fcp + (size_t)(t_done & 1) * S * 64;
-            float sum = w.bfc[o];
-            for (int p = 0; p < S; ++p) sum += xchg_load(part + p * 64 + o * 32 + row);
-            if (rd.valid && t_done >= a.LA)
-                a.out[(size_t)rd.out_off + (size_t)o * a.out_stride_o + (t_done - a.LA)] = apply_act(sum, a.act);
-        }
+        if (cs == 0 && tid < 64) colsplit_fc_sum<S>(w, a, rows_s, fcp + (size_t)(t_done & 1) * S * 64, t_done);
     };
 
     // A_t: layer 0 of step t.  m3 = t % 3, pm3 = (t - 1) % 3
@@ -667,34 +599,34 @@ __global__ __launch_bounds__(256) void lstm2_coop_skew_kernel(LstmWeights w, Lst
         for (int n = 0; n < NT; ++n)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[n][r] = 0.0f;
-        const int hprev = h0off(pm3);
+        const int hprev = R::h0_of3(pm3);
         if constexpr (WREG)
             coop_layer_resident<NT, G0W, KGXP / 4>(acc, bw0, [&](int i) -> float4 { return Xw[i * 256]; },
                                                    [&](int i) -> float4 { return hload(hprev, i); });
         else
             coop_layer<NT, G0W, KGXP / 4, 0>(acc, ws, [&](int i) -> float4 { return Xw[i * 256]; },
                                              [&](int i) -> float4 { return hload(hprev, i); });
-        if (with_c) early1 = poll_early(bar1);           // for the wait in front of the C phase that follows
-        publish_tiles(acc);
-        float* img = reinterpret_cast<float*>(hx + h0off(m3));
+        if (with_c) early1 = wg_poll_early(bar1, tid);   // for the wait in front of the C phase that follows
+        coop_publish_tiles<NT>(red, acc, wave, lane);
+        float* img = reinterpret_cast<float*>(hx + R::h0_of3(m3));
         cell(c0, bias0, 0, [&](int i, float hval) {
             if (a.coop_corrupt != 0 && rt == 0 && pk[i] == 0 && prow[i] == 0 && t + 1 == a.coop_corrupt) hval += 1.0f;     // test hook: published value only
             xchg_store(img + a_frag_index(prow[i], pk[i]), hval);
         });
         if (have_next) {
 #pragma unroll
-            for (int i = 0; i < NG; ++i) Xf[xdst0 + i * 256] = goff[i] >= 0 ? (xr[i] - mdn.m) / mdn.d : 0.0f;
+            for (int i = 0; i < NG; ++i) Xf[xdst0 + i * 256] = x_valid(i) ? (xr[i] - mdn.m) / mdn.d : 0.0f;
         }
         if (with_c) {
-            if (!wait_for(bar1, (unsigned)S * (unsigned)(t - 1), early1)) return false;   // h1_{t-2}, Linear partials of step t-2
+            if (!wg_wait(bar1, (unsigned)S * (unsigned)(t - 1), early1, a, tid, abort_s)) return false;   // h1_{t-2}, Linear partials of step t-2
             if constexpr (!WREG) {
-                const int h1p = h1off(t & 1), h0c = h0off(pm3);      // C_{t-1} reads h1_{t-2} (parity t & 1) and h0_{t-1}
+                const int h1p = R::h1(t & 1), h0c = R::h0_of3(pm3);      // C_{t-1} reads h1_{t-2} (parity t & 1) and h0_{t-1}
                 coop_layer_prefill<NT, G1W, KGH / 4, G0W>(ca, cb, ws, [&](int i) -> float4 { return hload(h1p, i); },
                                                           [&](int i) -> float4 { return hload(h0c, i); });
             }
         }
         chaos_delay(a.coop_chaos, t, 1);
-        arrive(bar0);
+        wg_arrive(bar0, tid);
         return true;
     };
     // C_t: layer 1 of step t over [h1_{t-1} | h0_t]
@@ -706,7 +638,7 @@ __global__ __launch_bounds__(256) void lstm2_coop_skew_kernel(LstmWeights w, Lst
         for (int n = 0; n < NT; ++n)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[n][r] = 0.0f;
-        const int h1p = h1off(prv), h0c = h0off(m3);
+        const int h1p = R::h1(prv), h0c = R::h0_of3(m3);
         if constexpr (WREG)
             coop_layer_resident<NT, G1W, KGH / 4>(acc, bw1, [&](int i) -> float4 { return hload(h1p, i); },
                                                   [&](int i) -> float4 { return hload(h0c, i); });
@@ -717,9 +649,9 @@ __global__ __launch_bounds__(256) void lstm2_coop_skew_kernel(LstmWeights w, Lst
             coop_layer_run<NT, G1W, KGH / 4, G0W>(acc, ca, cb, ws, [&](int i) -> float4 { return hload(h1p, i); },
                                                   [&](int i) -> float4 { return hload(h0c, i); });
         }
-        early0 = poll_early(bar0);                       // for the wait in front of the next A phase
-        publish_tiles(acc);
-        float* img = reinterpret_cast<float*>(hx + h1off(cur));
+        early0 = wg_poll_early(bar0, tid);               // for the wait in front of the next A phase
+        coop_publish_tiles<NT>(red, acc, wave, lane);
+        float* img = reinterpret_cast<float*>(hx + R::h1(cur));
         cell(c1, bias1, 1, [&](int i, float h) {
             xchg_store(img + a_frag_index(prow[i], pk[i]), h);
             float p0 = h * wfc0[i], p1 = h * wfc1[i];                 // partial Linear over this workgroup's units
@@ -732,25 +664,25 @@ __global__ __launch_bounds__(256) void lstm2_coop_skew_kernel(LstmWeights w, Lst
             }
         });
         chaos_delay(a.coop_chaos, t, 3);
-        arrive(bar1);
+        wg_arrive(bar1, tid);
     };
 
     __syncthreads();
     (void)phase_a(0, 0, 2, false);                      // h0_{-1} = the (zeroed) third image
     int m3 = 1, pm3 = 0;                                // t % 3, (t - 1) % 3 for t = 1
     for (int t = 1; t < Tp; ++t) {
-        if (!wait_for(bar0, (unsigned)S * (unsigned)t, early0)) return;            // h0_{t-1} published by every slice
+        if (!wg_wait(bar0, (unsigned)S * (unsigned)t, early0, a, tid, abort_s)) return;            // h0_{t-1} published by every slice
         if (!phase_a(t, m3, pm3, true)) return;                                    // (waits for b1 >= S (t-1) inside)
         if (t >= 2) fc_epilogue(t - 2);
         phase_c(t - 1, pm3, !WREG);
         pm3 = m3;
         m3 = m3 == 2 ? 0 : m3 + 1;
     }
-    if (!wait_for(bar0, (unsigned)S * (unsigned)Tp, early0)) return;
-    if (!wait_for(bar1, (unsigned)S * (unsigned)(Tp - 1), Tp >= 2 ? poll_early(bar1) : 0u)) return;
+    if (!wg_wait(bar0, (unsigned)S * (unsigned)Tp, early0, a, tid, abort_s)) return;
+    if (!wg_wait(bar1, (unsigned)S * (unsigned)(Tp - 1), Tp >= 2 ? wg_poll_early(bar1, tid) : 0u, a, tid, abort_s)) return;
     if (Tp >= 2) fc_epilogue(Tp - 2);
     phase_c(Tp - 1, pm3, false);
-    if (!wait_for(bar1, (unsigned)S * (unsigned)Tp, 0u)) return;
+    if (!wg_wait(bar1, (unsigned)S * (unsigned)Tp, 0u, a, tid, abort_s)) return;
     fc_epilogue(Tp - 1);
 }
 
@@ -770,8 +702,9 @@ size_t lstm_coop_exchange_bytes(int H, int row_tiles) {
 // occ != nullptr: do not launch; report how many workgroups of this instantiation fit one CU at once
 template <int HID, int KX, int UNITS, bool SEQ, bool GRU>
 static void launch_coop_inst(const LstmWeights& w, const LstmArgs& a, hipStream_t s, int* occ) {
-    constexpr int S = HID / UNITS, NT = UNITS / 8;
-    const size_t smem_need = (size_t)coop_kgxp(KX) * 64 * 16 + (size_t)4 * NT * 16 * 64 * 4 + 32 * sizeof(RowDesc);
+    using SH = CoopShape<HID, KX, UNITS>;
+    constexpr int S = SH::S;
+    const size_t smem_need = SH::lds_bytes();
     LstmWeights wv = w;
     wv.wpack = w.wpack_coop[coop_units_index(UNITS)];
     if (SEQ || occ || !a.coop_skew) {

@@ -14,6 +14,7 @@
 // with ONE inter-workgroup barrier per step per group (write-through hand-off of lstm_common.h: sc1 stores, drained
 // arrive, sc1 loads, no fences; bounded spins).
 // The Linear(H, 2) epilogue is a per-wave partial dot, summed in a fixed order by workgroup cs == 0 one step later.
+#include "colsplit.h"
 #include "fsnp_common.h"
 #include "lstm_common.h"
 #include "lstm_launch.h"
@@ -89,9 +90,9 @@ __global__ __launch_bounds__(256) void lstm2_coopn_kernel(LstmWeights w, LstmArg
     constexpr int UNITS = 128;                     // hidden units per workgroup, 32 per wave
     constexpr int S = HID / UNITS;
     constexpr int KGX = KX / 8, KGH = HID / 8, KG0 = KGX + KGH, KG1 = 2 * KGH;
-    constexpr int HIMG = KGH * 64;                 // float4 per exchange image (32 rows x HID)
-    constexpr int HXT = coop_tile_f4(HID);         // float4 per row tile of the exchange region (lstm_common.h)
+    using RG = CoopRegion<HID>;                    // the row tile's exchange region (lstm_common.h); the third h0 image is not used
     constexpr int NG = KGX;
+    static_assert(2 * 4 * S * 64 <= RG::fc_floats, "Linear partials [parity][4 S waves][64] fit their slot of the exchange region");
 
     __shared__ __attribute__((aligned(16))) float4 Xs[2][R][KGX * 64];  // A images of x_t, double buffered by step parity
     __shared__ RowDesc rows_s[R][32];
@@ -178,7 +179,7 @@ __global__ __launch_bounds__(256) void lstm2_coopn_kernel(LstmWeights w, LstmArg
     BufStream hs[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        hs[r].rsrc = __builtin_amdgcn_make_buffer_rsrc(a.coop_hx + (size_t)rt[r] * HXT * 4, 0, 4 * HIMG * 16, 0x00020000);
+        hs[r].rsrc = __builtin_amdgcn_make_buffer_rsrc(a.coop_hx + (size_t)rt[r] * RG::total * 4, 0, RG::fc * 16, 0x00020000);
         hs[r].voff = lane * 16;
     }
 
@@ -208,28 +209,9 @@ __global__ __launch_bounds__(256) void lstm2_coopn_kernel(LstmWeights w, LstmArg
         return h;
     };
 
-    // returns false (to every thread) once the launch is aborted: a peer never arrived (lstm_common.h: xchg_wait)
-    auto inter_wg_barrier = [&](unsigned target) -> bool {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // every storing wave drains its stores
-        __syncthreads();
-        if (tid == 0) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __hip_atomic_fetch_add(bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (!xchg_wait(bar, target, a.coop_abort, a.coop_err)) abort_s = 1;
-        }
-        __syncthreads();
-        return abort_s == 0;
-    };
     auto fc_epilogue = [&](int r, int t_done) {   // workgroup cs == 0 sums the 4 S per-wave partials in a fixed order
-        if (cs == 0 && tid < 64 && live[r]) {
-            const int row = tid & 31, o = tid >> 5;
-            const RowDesc rd = rows_s[r][row];
-            const float* part = a.coop_hx + ((size_t)rt[r] * HXT + 4 * HIMG) * 4 + (size_t)(t_done & 1) * (4 * S) * 64;
-            float sum = w.bfc[o];
-            for (int p = 0; p < 4 * S; ++p) sum += xchg_load(part + p * 64 + o * 32 + row);
-            if (rd.valid && t_done >= a.LA)
-                a.out[(size_t)rd.out_off + (size_t)o * a.out_stride_o + (t_done - a.LA)] = apply_act(sum, a.act);
-        }
+        if (cs == 0 && tid < 64 && live[r])
+            colsplit_fc_sum<4 * S>(w, a, rows_s[r], a.coop_hx + ((size_t)rt[r] * RG::total + RG::fc) * 4 + (size_t)(t_done & 1) * (4 * S) * 64, t_done);
     };
 
     __syncthreads();
@@ -256,8 +238,8 @@ __global__ __launch_bounds__(256) void lstm2_coopn_kernel(LstmWeights w, LstmArg
                 for (int q = 0; q < 16; ++q) acc[n][q] = 0.0f;
             const float4* xw = Xs[cur][r] + lane;
             coopn_unrolled<KGX>(acc, ws, 0, [&](int k) -> float4 { return xw[k * 64]; });
-            coopn_loop<KGH>(acc, ws, KGX, [&](int k) -> float4 { return stream_load<kSc1>(hs[r], prv * (HIMG * 16) + k * 1024); });
-            float* img = reinterpret_cast<float*>(a.coop_hx + ((size_t)rt[r] * HXT + (size_t)cur * HIMG) * 4);
+            coopn_loop<KGH>(acc, ws, KGX, [&](int k) -> float4 { return stream_load<kSc1>(hs[r], RG::h0_image(prv) * RG::img_bytes + k * 1024); });
+            float* img = reinterpret_cast<float*>(a.coop_hx + ((size_t)rt[r] * RG::total + (size_t)RG::h0_image(cur) * RG::img) * 4);
 #pragma unroll
             for (int q = 0; q < 16; q += 2) {                  // two cells per pass: packed fp32 math (lstm_common.h)
                 const f32x2 h2 = cell_pair(acc, q, b0, c0[r]);
@@ -273,7 +255,7 @@ __global__ __launch_bounds__(256) void lstm2_coopn_kernel(LstmWeights w, LstmArg
             }
         }
         chaos_delay(a.coop_chaos, t, 1);
-        if (!inter_wg_barrier((unsigned)S * (unsigned)(t + 1))) return;   // h0_t, h1_{t-1} and the FC partials of step t-1 are now visible
+        if (!wg_barrier(bar, (unsigned)S * (unsigned)(t + 1), a, tid, abort_s)) return;   // h0_t, h1_{t-1} and the FC partials of step t-1 are now visible
         chaos_delay(a.coop_chaos, t, 2);
 
         // ---------------- layer 1 of every row tile: [h1_{t-1} | h0_t] ----------------
@@ -286,10 +268,10 @@ __global__ __launch_bounds__(256) void lstm2_coopn_kernel(LstmWeights w, LstmArg
             for (int n = 0; n < 4; ++n)
 #pragma unroll
                 for (int q = 0; q < 16; ++q) acc[n][q] = 0.0f;
-            coopn_loop<KGH>(acc, ws, KG0, [&](int k) -> float4 { return stream_load<kSc1>(hs[r], (2 + prv) * (HIMG * 16) + k * 1024); });
-            coopn_loop<KGH>(acc, ws, KG0 + KGH, [&](int k) -> float4 { return stream_load<kSc1>(hs[r], cur * (HIMG * 16) + k * 1024); });
-            float* img = reinterpret_cast<float*>(a.coop_hx + ((size_t)rt[r] * HXT + (size_t)(2 + cur) * HIMG) * 4);
-            float* part = a.coop_hx + ((size_t)rt[r] * HXT + 4 * HIMG) * 4 + ((size_t)cur * (4 * S) + ub) * 64;
+            coopn_loop<KGH>(acc, ws, KG0, [&](int k) -> float4 { return stream_load<kSc1>(hs[r], RG::h1_image(prv) * RG::img_bytes + k * 1024); });
+            coopn_loop<KGH>(acc, ws, KG0 + KGH, [&](int k) -> float4 { return stream_load<kSc1>(hs[r], RG::h0_image(cur) * RG::img_bytes + k * 1024); });
+            float* img = reinterpret_cast<float*>(a.coop_hx + ((size_t)rt[r] * RG::total + (size_t)RG::h1_image(cur) * RG::img) * 4);
+            float* part = a.coop_hx + ((size_t)rt[r] * RG::total + RG::fc) * 4 + ((size_t)cur * (4 * S) + ub) * 64;
 #pragma unroll
             for (int q = 0; q < 16; q += 2) {
                 const f32x2 h2 = cell_pair(acc, q, b1, c1[r]);
@@ -307,7 +289,7 @@ __global__ __launch_bounds__(256) void lstm2_coopn_kernel(LstmWeights w, LstmArg
         }
     }
     // last step's Linear: one more barrier so that every partial of step Tp-1 is visible
-    if (!inter_wg_barrier((unsigned)S * (unsigned)(Tp + 1))) return;
+    if (!wg_barrier(bar, (unsigned)S * (unsigned)(Tp + 1), a, tid, abort_s)) return;
 #pragma unroll
     for (int r = 0; r < R; ++r) fc_epilogue(r, Tp - 1);
 }

@@ -39,6 +39,7 @@
 // (tests/test_gpu_parity.py::test_wave_owned_column_split_kernel_vs_oracle), bitwise repeatable.
 #include "fsnp_common.h"
 #include "lstm_common.h"
+#include "colsplit.h"
 #include "lstm_launch.h"
 
 namespace fsnp {
@@ -123,13 +124,12 @@ __global__ __launch_bounds__(256) void lstm2_coopw_kernel(LstmWeights w, LstmArg
     constexpr int P = 4 * S;                       // participants (waves) per row tile
     constexpr int KGX = KX / 8, KGH = HID / 8, KG0 = KGX + KGH;
     constexpr int NXL = KX / 2;                    // input features per lane
-    constexpr int HIMG = KGH * 64;                 // float4 per exchange image (32 rows x HID)
-    constexpr int FCP4 = 2 * (HID / 8) * 16;       // float4 of the Linear-partial slot of the exchange region (lstm_common.h)
+    using R = CoopRegion<HID>;                     // the row tile's exchange region (lstm_common.h)
     constexpr int STRIDE = coopw_stride(NT);
     constexpr int D = coopw_depth<NT>();            // depth of the k-loops' register pipeline, in k-groups
     constexpr int NXN = KGX < D ? KGX : D;         // x k-groups whose weights the h0 segment's tail fetches
     static_assert(HID % (32 * NT) == 0 && KX % 8 == 0 && KX <= 64, "shape");
-    static_assert(2 * P * 64 <= FCP4 * 4, "Linear partials of every participant fit their slot of the exchange region");
+    static_assert(2 * P * 64 <= R::fc_floats, "Linear partials of every participant fit their slot of the exchange region");
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     constexpr int SLICE = coopw_slice_words(NT, KX);
@@ -149,15 +149,13 @@ __global__ __launch_bounds__(256) void lstm2_coopw_kernel(LstmWeights w, LstmArg
     int* gofft = reinterpret_cast<int*>(stg + 32 * STRIDE) + lane;              // [NXL][64]: this lane's gather offsets (-1 = no source)
     float4* wfct = reinterpret_cast<float4*>(stg + 32 * STRIDE + NXL * 64) + lane;   // [NT][2 outputs][64]: Linear weights of this lane's cells
 
-    // ---- exchange region of this row tile (lstm_common.h: coop_tile_f4)
-    float4* hx = reinterpret_cast<float4*>(a.coop_hx) + (size_t)rt * coop_tile_f4(HID);
-    auto h0off = [](int m3) -> int { return m3 < 2 ? m3 * HIMG : 4 * HIMG + FCP4; };       // float4 offsets inside the region
-    auto h1off = [](int par) -> int { return (2 + par) * HIMG; };
-    float* fcp = reinterpret_cast<float*>(hx + 4 * HIMG);                                   // [2][P][2 outputs][32 rows]
+    // ---- exchange region of this row tile (lstm_common.h: CoopRegion)
+    float4* hx = reinterpret_cast<float4*>(a.coop_hx) + (size_t)rt * R::total;
+    float* fcp = reinterpret_cast<float*>(hx + R::fc);                                      // [2][P][2 outputs][32 rows]
     unsigned* bar0 = FSNP_COOP_BAR(a, rt, 0);
     unsigned* bar1 = FSNP_COOP_BAR(a, rt, 1);
     BufStream hs;
-    hs.rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(hx), 0, coop_tile_f4(HID) * 16, 0x00020000);
+    hs.rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(hx), 0, R::total * 16, 0x00020000);
     hs.voff = lane * 16;
     BufStream ws;
     ws.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(w.wpack_coopw), 0, (KG0 + 2 * KGH) * kUb(HID) * 1024, 0x00020000);
@@ -169,23 +167,11 @@ __global__ __launch_bounds__(256) void lstm2_coopw_kernel(LstmWeights w, LstmArg
     const bool dense = a.dense != nullptr;
     const float* __restrict__ gbase = dense ? a.dense : a.att_mag;
     const int gstep = dense ? a.dense_stride : a.FP;
-    NormMD md = {0.0f, 1.0f};
-    const NormMD* md_t = nullptr;
+    NormMD md;
+    const NormMD* md_t;
 #pragma unroll
-    for (int i = 0; i < NXL; ++i) {
-        const int j = hi + 2 * i;
-        int off = -1;
-        if (rd.valid && j < w.NIN) {
-            if (dense) off = rd.b * Tp * gstep + j;
-            else off = sb_feature_offset(j, rd.f, rd.b * Tp * a.FP, a.F, a.NSBN, a.NFBN, a.fb_rel, a.fb_branch_stride);
-        }
-        gofft[i * 64] = off;
-    }
-    if (rd.valid) {
-        if (a.md_seq != nullptr) md_t = a.md_seq + (size_t)rd.b * Tp;
-        else if (!dense && a.md_row != nullptr) md_t = a.md_row + (size_t)(rt * 32 + row) * Tp;
-        else if (!dense) md = a.md_utt[rd.b];
-    }
+    for (int i = 0; i < NXL; ++i) gofft[i * 64] = colsplit_input_offset(w, a, rd, hi + 2 * i);
+    colsplit_norms(a, rd, rt * 32 + row, md, md_t);
     float xv[NXL];                                 // the lane's A fragments of x_t: k-group g = xv[4 g .. 4 g + 3]
     // raw values of step t (issued as soon as x_{t-1}'s MFMAs are done; lanes without a source read element 0 and discard it: no
     // per-element branches) ...
@@ -269,17 +255,9 @@ __global__ __launch_bounds__(256) void lstm2_coopw_kernel(LstmWeights w, LstmArg
     };
 
     // ---- hand-off, per wave (lstm_common.h): drained write-through stores, one relaxed arrival; waits polled ahead
-    auto arrive = [&](unsigned* bar) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (lane == 0) __hip_atomic_fetch_add(bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    };
+    auto arrive = [&](unsigned* bar) { wave_drain_arrive(bar, lane); };
     auto poll = [&](unsigned* bar) -> unsigned { return __hip_atomic_load(bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
-    auto wait_for = [&](unsigned* bar, unsigned target, unsigned early) -> bool {
-        if ((unsigned)__builtin_amdgcn_readfirstlane((int)early) >= target) return true;
-        int ok = 1;
-        if (lane == 0) ok = xchg_wait(bar, target, a.coop_abort, a.coop_err) ? 1 : 0;
-        return __builtin_amdgcn_readfirstlane(ok) != 0;
-    };
+    auto wait_for = [&](unsigned* bar, unsigned target, unsigned early) -> bool { return wave_wait(bar, target, early, a, lane); };
     // ONE participant sums the P partials of a finished step in a fixed order: the loads are issued where the step's partials are known
     // to be complete (fc_issue) and summed a cell phase later (fc_finish), so that their round trip is not on that wave's path.  Round 6:
     // the owner ROTATES (step t_done belongs to participant t_done mod P).  With participant 0 as the fixed owner its P extra loads and adds
@@ -325,7 +303,7 @@ __global__ __launch_bounds__(256) void lstm2_coopw_kernel(LstmWeights w, LstmArg
         const bool have_next = t + 1 < Tp;
         f32x16 acc[NT];
         acc_init(acc, 0);
-        const int hprev = h0off(pm3) * 16;
+        const int hprev = R::h0_of3(pm3) * 16;
         // (the last D h0 groups refill the pipeline's WEIGHT slots with the first x k-groups; their A fragments are registers)
         w_segment<NT, HID, D, KGH, NXN>(acc, pa, pb, ws, part, KGX, [&](int g) -> float4 { return stream_load<kSc1>(hs, hprev + g * 1024); },
                                         0, [&](int g) -> float4 { return xfrag(g); }, [] {});
@@ -347,14 +325,14 @@ __global__ __launch_bounds__(256) void lstm2_coopw_kernel(LstmWeights w, LstmArg
             md_at(t + 1, xm, xd);
             x_fetch(t + 1);
         }
-        const int h1p = h1off(t & 1) * 16;                                                   // C_{t-1} starts on h1_{t-2} (parity t & 1)
+        const int h1p = R::h1(t & 1) * 16;                                                   // C_{t-1} starts on h1_{t-2} (parity t & 1)
         if (with_c) {
             if (!wait_for(bar1, (unsigned)P * (unsigned)(t - 1), early1)) return false;      // h1_{t-2}, Linear partials of step t - 2
             w_prefill<NT, HID, D>(pa, pb, ws, part, KG0, [&](int g) -> float4 { return stream_load<kSc1>(hs, h1p + g * 1024); });
             if (t >= 2) fc_issue(t - 2);
         }
         FSNP_W_STAMP(t, 3);
-        const int himg = h0off(m3);
+        const int himg = R::h0_of3(m3);
         const bool corrupt = a.coop_corrupt != 0 && rt == 0 && part == 0 && lane == 0 && t + 1 == a.coop_corrupt;     // test hook (LstmArgs)
         cells(acc, c0, [&](int n, const float4& h) {
             float4 hp = h;
@@ -378,7 +356,7 @@ __global__ __launch_bounds__(256) void lstm2_coopw_kernel(LstmWeights w, LstmArg
         unsigned early0 = 0u;
         f32x16 acc[NT];
         acc_init(acc, 1);
-        const int h1p = h1off(prv) * 16, h0c = h0off(m3) * 16;
+        const int h1p = R::h1(prv) * 16, h0c = R::h0_of3(m3) * 16;
         w_segment<NT, HID, D, KGH, D>(acc, pa, pb, ws, part, KG0, [&](int g) -> float4 { return stream_load<kSc1>(hs, h1p + g * 1024); },
                                       KG0 + KGH, [&](int g) -> float4 { return stream_load<kSc1>(hs, h0c + g * 1024); }, [] {});
         FSNP_W_STAMP(t + 1, 9);
@@ -386,13 +364,13 @@ __global__ __launch_bounds__(256) void lstm2_coopw_kernel(LstmWeights w, LstmArg
         w_segment<NT, HID, D, KGH, 0>(acc, pa, pb, ws, part, KG0 + KGH, [&](int g) -> float4 { return stream_load<kSc1>(hs, h0c + g * 1024); },
                                       0, [&](int) -> float4 { return make_float4(0.f, 0.f, 0.f, 0.f); }, [&] { if (next_a) early0 = poll(bar0); });
         FSNP_W_STAMP(t + 1, 10);
-        const int hn = h0off(nm3) * 16;
+        const int hn = R::h0_of3(nm3) * 16;
         if (next_a) {
             if (!wait_for(bar0, (unsigned)P * (unsigned)(t + 2), early0)) return false;       // h0_{t+1} published by every participant
             w_prefill<NT, HID, D>(pa, pb, ws, part, KGX, [&](int g) -> float4 { return stream_load<kSc1>(hs, hn + g * 1024); });
         }
         FSNP_W_STAMP(t + 1, 11);
-        const int himg = h1off(cur);
+        const int himg = R::h1(cur);
         float p0 = 0.0f, p1 = 0.0f;
         cells(acc, c1, [&](int n, const float4& h) {
             hstore(himg, n, h);
@@ -413,14 +391,14 @@ __global__ __launch_bounds__(256) void lstm2_coopw_kernel(LstmWeights w, LstmArg
 
     // ---- A_0 (h0_{-1} = the zeroed third image), then [A_t, C_{t-1}] for t = 1 .. Tp - 1, then C_{Tp-1}
     {
-        const int hz = h0off(2) * 16;
+        const int hz = R::h0_of3(2) * 16;
         w_prefill<NT, HID, D>(pa, pb, ws, part, KGX, [&](int g) -> float4 { return stream_load<kSc1>(hs, hz + g * 1024); });
     }
     if (Tp == 1) {
         // (one step only: A_0 -> C_0 with blocking waits)
         if (!phase_a(0, 0, 2, false)) return;
         if (!wait_for(bar0, (unsigned)P, 0u)) return;
-        w_prefill<NT, HID, D>(pa, pb, ws, part, KG0, [&](int g) -> float4 { return stream_load<kSc1>(hs, h1off(1) * 16 + g * 1024); });
+        w_prefill<NT, HID, D>(pa, pb, ws, part, KG0, [&](int g) -> float4 { return stream_load<kSc1>(hs, R::h1(1) * 16 + g * 1024); });
         if (!phase_c(0, 0, false, 0)) return;
         if (!wait_for(bar1, (unsigned)P, 0u)) return;
         fc_issue(0); fc_finish(0);
@@ -429,7 +407,7 @@ __global__ __launch_bounds__(256) void lstm2_coopw_kernel(LstmWeights w, LstmArg
     if (!phase_a(0, 0, 2, false)) return;
     // A_1 needs h0_0 of every participant; its pipeline is filled here (no C phase in between yet)
     if (!wait_for(bar0, (unsigned)P, 0u)) return;
-    w_prefill<NT, HID, D>(pa, pb, ws, part, KGX, [&](int g) -> float4 { return stream_load<kSc1>(hs, h0off(0) * 16 + g * 1024); });
+    w_prefill<NT, HID, D>(pa, pb, ws, part, KGX, [&](int g) -> float4 { return stream_load<kSc1>(hs, R::h0_of3(0) * 16 + g * 1024); });
     int m3 = 1, pm3 = 0;                                // t % 3, (t - 1) % 3 for t = 1
     for (int t = 1; t < Tp; ++t) {
         if (!phase_a(t, m3, pm3, true)) return;         // (waits for b1 >= P (t - 1) inside, prefills C_{t-1}, Linear of step t - 2)
@@ -442,7 +420,7 @@ __global__ __launch_bounds__(256) void lstm2_coopw_kernel(LstmWeights w, LstmArg
     if (!wait_for(bar0, (unsigned)P * (unsigned)Tp, 0u)) return;
     if (!wait_for(bar1, (unsigned)P * (unsigned)(Tp - 1), 0u)) return;
     fc_issue(Tp - 2); fc_finish(Tp - 2);
-    w_prefill<NT, HID, D>(pa, pb, ws, part, KG0, [&](int g) -> float4 { return stream_load<kSc1>(hs, h1off(Tp & 1) * 16 + g * 1024); });
+    w_prefill<NT, HID, D>(pa, pb, ws, part, KG0, [&](int g) -> float4 { return stream_load<kSc1>(hs, R::h1(Tp & 1) * 16 + g * 1024); });
     if (!phase_c(Tp - 1, pm3, false, 0)) return;
     if (!wait_for(bar1, (unsigned)P * (unsigned)Tp, 0u)) return;
     fc_issue(Tp - 1); fc_finish(Tp - 1);

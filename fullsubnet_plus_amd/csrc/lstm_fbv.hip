@@ -18,6 +18,7 @@
 // h1_t also goes row-major to seq_out[seq][t][H] for the Linear(512, 257) GEMM (tcn.hip), as from the SEQ K-split kernel.  Same cell
 // arithmetic (fast_sigmoid / fast_tanh) as that kernel; K is summed in another order: same oracle tolerance
 // (tests/test_gpu_fullsubnet.py), bitwise repeatable.  LSTM only (a GRU full-band model keeps the K-split kernel).
+#include "colsplit.h"
 #include "fsnp_common.h"
 #include "lstm_common.h"
 #include "weight_layouts.h"
@@ -114,17 +115,6 @@ __global__ __launch_bounds__(256) void lstm2_fbv_kernel(LstmWeights w, LstmArgs 
             }
         }
     };
-    auto inter_wg_barrier = [&](unsigned target) -> bool {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid == 0) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __hip_atomic_fetch_add(bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (!xchg_wait(bar, target, a.coop_abort, a.coop_err)) abort_s = 1;
-        }
-        __syncthreads();
-        return abort_s == 0;
-    };
     // sum of the 4 waves' partials of column 4 cu + g, row crow (+ bias) -> gate pre-activation
     auto pre = [&](int par, int g, const float (&b)[4]) -> float {
         const int col = 4 * cu + g;
@@ -148,7 +138,7 @@ __global__ __launch_bounds__(256) void lstm2_fbv_kernel(LstmWeights w, LstmArgs 
         }
         if (t + 1 < Tp) stage_x(t + 1);                      // (x_t was last read by the layer-0 products above, in front of the barrier)
         chaos_delay(a.coop_chaos, t, 1);
-        if (!inter_wg_barrier((unsigned)S * (unsigned)(t + 1))) return;      // h0_t and h1_{t-1} of every slice are now visible
+        if (!wg_barrier(bar, (unsigned)S * (unsigned)(t + 1), a, tid, abort_s)) return;      // h0_t and h1_{t-1} of every slice are now visible
         chaos_delay(a.coop_chaos, t, 2);
         // h0_t -> V[.][x | H0 | .], h1_{t-1} -> V[.][. | . | H1]: 2 NB HID floats as 16-byte write-through-coherent loads
         for (int i = tid; i < 2 * NB * (HID / 4); i += 256) {

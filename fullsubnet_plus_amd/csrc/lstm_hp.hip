@@ -42,6 +42,7 @@
 #include <type_traits>
 #include <utility>
 
+#include "colsplit.h"
 #include "fsnp_common.h"
 #include "lstm_common.h"
 #include "lstm_launch.h"
@@ -73,16 +74,15 @@ void lstm2_coop_hp_kernel(LstmWeights w, LstmArgs a) {
     constexpr int GX = hp_gx(KX), GH = HID / 16;     // k-groups of 16: x (zero padded), one h image
     constexpr int NW0 = GX + GH, NW1 = 2 * GH;       // the wave's weight fragments (float4): layer 0 [x | h0], layer 1 [h1 | h0]
     constexpr int HALF_B = GH * 1024;                // bytes of one half image (16 rows x HID)
-    constexpr int IMG_B = (HID / 8) * 1024;          // bytes of one 32-row image slot of the exchange region (lstm_common.h)
-    constexpr int TILE_BYTES = coop_tile_f4(HID) * 16;
-    constexpr int H0OFF = 0, H1OFF = 2 * IMG_B, FCOFF = 4 * IMG_B;
+    using R = CoopRegion<HID>;                       // the row tile's exchange region (lstm_common.h), float4 offsets: x 16 = bytes;
+                                                     // a 32-row image slot holds the two half images one behind the other
     // events inside the MFMA pass, in k-groups of the h part (a group = 12 MFMAs = 384 matrix-pipe cycles)
     // (measured: arrival after 3 ... 6 of 24 groups, poll at 8 ... 12, check at 14 ... 16 make no difference - profiles/r03_column_split.md)
     constexpr int ARRIVE_G = GH / 4, POLL1_G = GH / 2, CHECK1_G = (GH * 2) / 3, PEER_G = CHECK1_G + GH / 8, POLL2_G = PEER_G + 1;
     static_assert(KX <= 64 && GX <= 4, "gathered sub-band input");
     static_assert(S >= 16 && 2 * S <= 64, "one workgroup per output row of a half tile; the Linear partials are fetched by wave 0");
     static_assert((NW0 + NW1) * 4 <= 320 && NW1 * 4 <= 192, "the wave's weights must fit the register file (layer 1: AGPRs)");
-    static_assert(4 * S * 128 <= 2 * (HID / 8) * 256, "Linear partials fit their slot of the exchange region");
+    static_assert(4 * S * 128 <= R::fc_f4 * 16, "Linear partials [parity][half][S][2][16] fit their slot of the exchange region");
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     float4* Xs = reinterpret_cast<float4*>(smem_raw);                  // [2 halves][GX][64]  A images of x
@@ -119,23 +119,11 @@ void lstm2_coop_hp_kernel(LstmWeights w, LstmArgs a) {
 #pragma unroll
     for (int hf = 0; hf < 2; ++hf) {
         const RowDesc rd = rows_s[hf * 16 + xrow];
-        md[hf] = NormMD{0.0f, 1.0f};
-        md_t[hf] = nullptr;
 #pragma unroll
         for (int i = 0; i < GX; ++i) {
-            const int j = j0 + 16 * i;
-            int off = -1;
-            if (rd.valid && j < w.NIN) {
-                if (dense) off = rd.b * Tp * gstep + j;
-                else off = sb_feature_offset(j, rd.f, rd.b * Tp * a.FP, a.F, a.NSBN, a.NFBN, a.fb_rel, a.fb_branch_stride);
-            }
-            goff[hf][i] = off;
+            goff[hf][i] = colsplit_input_offset(w, a, rd, j0 + 16 * i);
         }
-        if (rd.valid) {
-            if (a.md_seq != nullptr) md_t[hf] = a.md_seq + (size_t)rd.b * Tp;
-            else if (!dense && a.md_row != nullptr) md_t[hf] = a.md_row + (size_t)(rt * 32 + hf * 16 + xrow) * Tp;
-            else if (!dense) md[hf] = a.md_utt[rd.b];
-        }
+        colsplit_norms(a, rd, rt * 32 + hf * 16 + xrow, md[hf], md_t[hf]);
     }
     const int xdst0 = hp_a16(xrow, j0);               // (+ 256 floats per further k-group)
     // (one buffer load per element and step: the per-lane byte offset is loop invariant, the step goes into the scalar offset;
@@ -166,7 +154,7 @@ void lstm2_coop_hp_kernel(LstmWeights w, LstmArgs a) {
 
     // ---- exchange region of this row tile
     const __amdgpu_buffer_rsrc_t hr =
-        __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(a.coop_hx) + (size_t)rt * (TILE_BYTES / 4), 0, TILE_BYTES, 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(a.coop_hx) + (size_t)rt * (R::total * 4), 0, R::total * 16, 0x00020000);
     unsigned* const bars[2] = {FSNP_COOP_BAR(a, rt, 0), FSNP_COOP_BAR(a, rt, 1)};     // one 128-byte line each
     auto store16 = [&](const float4& v, int voff, int soff) {
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, v), hr, voff, soff, kSc1);
@@ -242,9 +230,8 @@ void lstm2_coop_hp_kernel(LstmWeights w, LstmArgs a) {
         }
         __syncthreads();
         if (wave == 0) {
-            store16(stage[lane], (cs * 64 + lane) * 16, H0OFF + hf * HALF_B);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (lane == 0) __hip_atomic_fetch_add(bars[hf], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            store16(stage[lane], (cs * 64 + lane) * 16, R::h0_0 * 16 + hf * HALF_B);
+            wave_drain_arrive(bars[hf], lane);
         }
     }
 
@@ -257,22 +244,20 @@ void lstm2_coop_hp_kernel(LstmWeights w, LstmArgs a) {
     auto fetch = [&](auto HN, int tn) {
         constexpr int hn = decltype(HN)::value;
         if (wave != 0) {
-            const int h1src = H1OFF + ((tn & 1) ^ 1) * IMG_B + hn * HALF_B, h0src = H0OFF + (tn & 1) * IMG_B + hn * HALF_B;
+            const int h1src = R::h1((tn & 1) ^ 1) * 16 + hn * HALF_B, h0src = R::h0(tn & 1) * 16 + hn * HALF_B;
             for (int c = wave - 1; c < 2 * GH; c += 3) {
                 if (c < GH) __builtin_amdgcn_raw_ptr_buffer_load_lds(hr, (lds_ptr)(size_t)(lds_h1 + (hn * GH + c) * 1024), 16, lane * 16, h1src + c * 1024, 0, kSc1);
                 else __builtin_amdgcn_raw_ptr_buffer_load_lds(hr, (lds_ptr)(size_t)(lds_h0 + (hn * GH + c - GH) * 1024), 16, lane * 16, h0src + (c - GH) * 1024, 0, kSc1);
             }
         } else if (fc_wg && tn >= 1 && tid < 2 * S) {
-            fcv = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(hr, fc_voff, FCOFF + ((((tn & 1) ^ 1) * 2 + hn) * S) * 128, kSc1));
+            fcv = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(hr, fc_voff, R::fc * 16 + ((((tn & 1) ^ 1) * 2 + hn) * S) * 128, kSc1));
         }
     };
     // a wave's blocking wait for a counter (lane 0 polls; the whole wave learns the outcome)
     auto wave_wait = [&](unsigned* bar, unsigned target) -> bool {
-        int ok = 1;
-        if (lane == 0) ok = xchg_wait(bar, target, a.coop_abort, a.coop_err) ? 1 : 0;
-        ok = __builtin_amdgcn_readfirstlane(ok);
+        const bool ok = fsnp::wave_wait(bar, target, a, lane);
         if (!ok && lane == 0) flags[0] = 1;
-        return ok != 0;
+        return ok;
     };
     // optional phase profile (fsnp_debug_pp_profile): thread 0 of workgroup 0 stamps the 100 MHz wall clock: prof[(t * 2 + hf) * 16 + k]
     unsigned long long* prof = (a.prof != nullptr && blockIdx.x == 0 && tid == 0) ? a.prof : nullptr;
@@ -282,9 +267,9 @@ void lstm2_coop_hp_kernel(LstmWeights w, LstmArgs a) {
     unsigned* pending_bar = nullptr;
     // wave 0 publishes the staged h0 / h1 / Linear partials of half-phase (hp, tp): three 16-byte write-through stores per lane
     auto publish = [&](int hp, int tp) {
-        store16(stage[lane], (cs * 64 + lane) * 16, H0OFF + ((tp + 1) & 1) * IMG_B + hp * HALF_B);
-        store16(stage[64 + lane], (cs * 64 + lane) * 16, H1OFF + (tp & 1) * IMG_B + hp * HALF_B);
-        if (lane < 8) store16(stage[128 + lane], lane * 16, FCOFF + (((tp & 1) * 2 + hp) * S + cs) * 128);
+        store16(stage[lane], (cs * 64 + lane) * 16, R::h0((tp + 1) & 1) * 16 + hp * HALF_B);
+        store16(stage[64 + lane], (cs * 64 + lane) * 16, R::h1(tp & 1) * 16 + hp * HALF_B);
+        if (lane < 8) store16(stage[128 + lane], lane * 16, R::fc * 16 + (((tp & 1) * 2 + hp) * S + cs) * 128);
     };
     bool pub_pending = false;             // (two halves) the previous half-phase's cells are staged but not published yet: that happens behind
     int pub_t = 0;                        // the NEXT half-phase's first barrier, which saves a workgroup barrier per half-phase
@@ -352,8 +337,7 @@ void lstm2_coop_hp_kernel(LstmWeights w, LstmArgs a) {
                 if (g == ARRIVE_G) {
                     FSNP_HP_STAMP(2);
                     if (wave == 0 && pending) {      // the previous half-phase's stores are a quarter pass old; nothing else is in wave 0's queue
-                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                        if (lane == 0) __hip_atomic_fetch_add(pending_bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        wave_drain_arrive(pending_bar, lane);
                         pending = false;
                     }
                     FSNP_HP_STAMP(3);
@@ -409,8 +393,7 @@ void lstm2_coop_hp_kernel(LstmWeights w, LstmArgs a) {
                 __syncthreads();
                 if (wave == 0) {
                     publish(hf, t);
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    if (lane == 0) __hip_atomic_fetch_add(bars[hf], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    wave_drain_arrive(bars[hf], lane);
                 }
             } else {
                 pub_pending = true; pub_t = t;    // (published behind the next half-phase's first barrier)
@@ -426,13 +409,11 @@ void lstm2_coop_hp_kernel(LstmWeights w, LstmArgs a) {
     __syncthreads();                      // the last half-phase's cells are staged
     if (wave == 0 && !dead) {
         if (pending) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (lane == 0) __hip_atomic_fetch_add(pending_bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            wave_drain_arrive(pending_bar, lane);
         }
         if (pub_pending) {
             publish(nh - 1, pub_t);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (lane == 0) __hip_atomic_fetch_add(bars[nh - 1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            wave_drain_arrive(bars[nh - 1], lane);
         }
     }
     if (flags[0] || dead) return;
@@ -446,7 +427,7 @@ void lstm2_coop_hp_kernel(LstmWeights w, LstmArgs a) {
         __syncthreads();
         if (flags[0]) return;
         if (tid < 2 * S)
-            fc_red[tid] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(hr, fc_voff, FCOFF + ((((Tp - 1) & 1) * 2 + hf) * S) * 128, kSc1));
+            fc_red[tid] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(hr, fc_voff, R::fc * 16 + ((((Tp - 1) & 1) * 2 + hf) * S) * 128, kSc1));
         __syncthreads();
         fc_finish(hf, Tp - 1);
     }

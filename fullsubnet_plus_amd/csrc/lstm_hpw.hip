@@ -36,6 +36,7 @@
 
 #include "fsnp_common.h"
 #include "lstm_common.h"
+#include "colsplit.h"
 #include "lstm_launch.h"
 
 namespace fsnp {
@@ -72,9 +73,8 @@ void lstm2_coop_hpw_kernel(LstmWeights w, LstmArgs a) {
     constexpr int NX = KX / 4;                       // input features per lane (k = kq + 4 i < KX; the zero-padded tail of the last k-group is skipped)
     constexpr int NW0 = GX + GH, NW1 = 2 * GH;       // the wave's weight fragments (float4): layer 0 [x | h0], layer 1 [h1 | h0]
     constexpr int HALF_B = GH * 1024;                // bytes of one half image (16 sequences x HID)
-    constexpr int IMG_B = (HID / 8) * 1024;          // bytes of one 32-row image slot of the exchange region (lstm_common.h)
-    constexpr int TILE_BYTES = coop_tile_f4(HID) * 16;
-    constexpr int H0OFF = 0, H1OFF = 2 * IMG_B, FCOFF = 4 * IMG_B;     // (the Linear partials also use the third h0 image behind their slot)
+    using R = CoopRegion<HID>;                       // the row tile's exchange region (lstm_common.h), float4 offsets: x 16 = bytes;
+                                                     // a 32-row image slot holds the two half images one behind the other
     constexpr int D = GH % 6 == 0 ? 6 : 8;           // depth of the operand pipeline, in k-groups of 384 matrix-pipe cycles (H = 384: 6, the registers allow no more; H = 256: 8)
     constexpr int NPL = (P + 63) / 64;               // Linear partials per lane of the summing wave
     constexpr int XLOAD_G = 2;                       // k-group of the pass behind which the raw x of step t + 2 is requested
@@ -83,7 +83,8 @@ void lstm2_coop_hpw_kernel(LstmWeights w, LstmArgs a) {
     static_assert(GH % D == 0 && GH >= 2 * D, "pipeline shape");
     static_assert(P % 32 == 0 && P >= 32, "the 32 Linear sums of a half-phase rotate over the participants");
     static_assert((NW0 + NW1) * 4 <= 320 && NW1 * 4 <= 192, "the wave's weights must fit the register file (layer 1: AGPRs)");
-    static_assert(FCOFF + 4 * P * 128 <= TILE_BYTES, "Linear partials [parity][half][participant][16 sequences][2] fit the exchange region");
+    static_assert(4 * P * 128 <= (R::total - R::fc) * 16,
+                  "Linear partials [parity][half][participant][16 sequences][2] fit their slot and the third h0 image behind it, which this kernel does not use");
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     int* goff_all = reinterpret_cast<int*>(smem_raw);                                   // [4 waves][2 halves][NX][64]: lane-private gather offsets
@@ -125,12 +126,8 @@ void lstm2_coop_hpw_kernel(LstmWeights w, LstmArgs a) {
             // features beyond NIN meet zero weights and rows without a sequence are never written out: both read element 0 of the
             // input (a finite value) - no per-element select anywhere
             const int k = 4 * i + kq;               // = 16 g + 4 j + kq with i = 4 g + j
-            int off = 0;
-            if (rd.valid && k < w.NIN) {
-                if (dense) off = rd.b * Tp * gstep + k;
-                else off = sb_feature_offset(k, rd.f, rd.b * Tp * a.FP, a.F, a.NSBN, a.NFBN, a.fb_rel, a.fb_branch_stride);
-            }
-            gofft[(hf * NX + i) * 64] = off * 4;
+            const int off = colsplit_input_offset(w, a, rd, k);
+            gofft[(hf * NX + i) * 64] = (off < 0 ? 0 : off) * 4;
         }
         if (rd.valid) {
             if (a.md_seq != nullptr) { md_p[hf] = (gmd_ptr)(a.md_seq + (size_t)rd.b * Tp); md_s[hf] = 1; }
@@ -169,7 +166,7 @@ void lstm2_coop_hpw_kernel(LstmWeights w, LstmArgs a) {
 
     // ---- exchange region of this row tile
     const __amdgpu_buffer_rsrc_t hr =
-        __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(a.coop_hx) + (size_t)rt * (TILE_BYTES / 4), 0, TILE_BYTES, 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(a.coop_hx) + (size_t)rt * (R::total * 4), 0, R::total * 16, 0x00020000);
     unsigned* const bars[2] = {FSNP_COOP_BAR(a, rt, 0), FSNP_COOP_BAR(a, rt, 1)};     // one 128-byte line each
     const int hst = part * 256 + seq * 16 + kq * 4;  // byte offset of the lane's cell inside a half image (hp_a16(seq, unit))
     auto hload = [&](int soff) -> float4 { return stream_load<kSc1>(BufStream{hr, lane * 16}, soff); };
@@ -206,7 +203,7 @@ void lstm2_coop_hpw_kernel(LstmWeights w, LstmArgs a) {
 #pragma unroll
         for (int q = 0; q < NPL; ++q) {
             const int p = q * 64 + lane;
-            fcv[q] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(hr, ((p < P ? p : 0) * 32 + j) * 4, FCOFF + (((t_done & 1) * 2 + hn) * P) * 128, kSc1));
+            fcv[q] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(hr, ((p < P ? p : 0) * 32 + j) * 4, R::fc * 16 + (((t_done & 1) * 2 + hn) * P) * 128, kSc1));
         }
         fc_job = j; fc_hf = hn; fc_t = t_done;
     };
@@ -225,15 +222,11 @@ void lstm2_coop_hpw_kernel(LstmWeights w, LstmArgs a) {
         fc_job = -1;
     };
 
-    auto arrive = [&](unsigned* bar) {
-        if (lane == 0) __hip_atomic_fetch_add(bar, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    };
+    auto arrive = [&](unsigned* bar) { wave_arrive(bar, lane); };
     // blocking wait of a wave for a counter; a wait that gives up (time-out / launch-wide abort: lstm_common.h) ENDS the wave - nothing
     // in this kernel waits for a wave of its own workgroup, and a plain exit keeps the hot loop's control flow free of merge points
     auto wave_wait = [&](unsigned* bar, unsigned target) {
-        int ok = 1;
-        if (lane == 0) ok = xchg_wait(bar, target, a.coop_abort, a.coop_err) ? 1 : 0;
-        if (__builtin_amdgcn_readfirstlane(ok) == 0) __builtin_amdgcn_endpgm();
+        if (!fsnp::wave_wait(bar, target, a, lane)) __builtin_amdgcn_endpgm();
     };
     auto chaos = [&](int t, int phase) { chaos_delay(a.coop_chaos ? a.coop_chaos + 7919 * wave : 0, t, phase); };
 
@@ -253,7 +246,7 @@ void lstm2_coop_hpw_kernel(LstmWeights w, LstmArgs a) {
         f32x2 c = {0.f, cst[hf].y};
         const f32x2 hh = lstm_cell_pair(f32x2{0.f, a0a[0]}, f32x2{0.f, a0a[1]}, f32x2{0.f, a0a[2]}, f32x2{0.f, a0a[3]}, c);
         cst[hf].y = c.y;
-        hstore(hh.y, H0OFF + hf * HALF_B);
+        hstore(hh.y, R::h0_0 * 16 + hf * HALF_B);
         const int t1 = Tp > 1 ? 1 : 0;
         x_fetch(HC, t1);
         x_commit(HC, md_at(hf, t1));
@@ -264,7 +257,7 @@ void lstm2_coop_hpw_kernel(LstmWeights w, LstmArgs a) {
     // ================= phases 0 .. Tp - 1, the two halves in turn =================
     float4 pp[D], pq[D];                   // operand pipeline: k-groups of h1_{t-1} and h0_t of the half-phase at hand
     auto prefill = [&](int hn, int tn) {
-        const int s1 = H1OFF + ((tn & 1) ^ 1) * IMG_B + hn * HALF_B, s0 = H0OFF + (tn & 1) * IMG_B + hn * HALF_B;
+        const int s1 = R::h1((tn & 1) ^ 1) * 16 + hn * HALF_B, s0 = R::h0(tn & 1) * 16 + hn * HALF_B;
 #pragma unroll
         for (int k = 0; k < D; ++k) { pp[k] = hload(s1 + k * 1024); pq[k] = hload(s0 + k * 1024); }
     };
@@ -307,10 +300,10 @@ void lstm2_coop_hpw_kernel(LstmWeights w, LstmArgs a) {
         const int tx = t + 2 < Tp ? t + 2 : Tp - 1;
         NormMD mdn = {0.f, 1.f};
         unsigned seen = 0;
-        const int s1 = H1OFF + ((t & 1) ^ 1) * IMG_B + hf * HALF_B, s0 = H0OFF + (t & 1) * IMG_B + hf * HALF_B;
+        const int s1 = R::h1((t & 1) ^ 1) * 16 + hf * HALF_B, s0 = R::h0(t & 1) * 16 + hf * HALF_B;
         // operands of the NEXT half-phase (two halves: the other half's; its step nt)
         const int ntc = has_next ? nt : Tp - 1;                    // (behind the last half-phase of all: a harmless re-read)
-        const int n1 = H1OFF + ((ntc & 1) ^ 1) * IMG_B + (two ? ho : 0) * HALF_B, n0 = H0OFF + (ntc & 1) * IMG_B + (two ? ho : 0) * HALF_B;
+        const int n1 = R::h1((ntc & 1) ^ 1) * 16 + (two ? ho : 0) * HALF_B, n0 = R::h0(ntc & 1) * 16 + (two ? ho : 0) * HALF_B;
         auto group = [&](auto G, auto REFILL_NEXT) {
             constexpr int g = decltype(G)::value;
             constexpr bool refill_next = decltype(REFILL_NEXT)::value;
@@ -362,8 +355,8 @@ void lstm2_coop_hpw_kernel(LstmWeights w, LstmArgs a) {
         const f32x2 hh = lstm_cell_pair(f32x2{a1a[0], a0a[0]}, f32x2{a1a[1], a0a[1]}, f32x2{a1a[2], a0a[2]}, f32x2{a1a[3], a0a[3]}, cst[hf]);
         // (test hook, LstmArgs::coop_corrupt: h0 of step t + 1, sequence 0, unit 0 of row tile 0 is published with 1.0 added)
         const bool corrupt = a.coop_corrupt != 0 && rt == 0 && part == 0 && hf == 0 && lane == 0 && t + 2 == a.coop_corrupt;
-        hstore(corrupt ? hh.y + 1.0f : hh.y, H0OFF + ((t + 1) & 1) * IMG_B + hf * HALF_B);
-        hstore(hh.x, H1OFF + (t & 1) * IMG_B + hf * HALF_B);
+        hstore(corrupt ? hh.y + 1.0f : hh.y, R::h0((t + 1) & 1) * 16 + hf * HALF_B);
+        hstore(hh.x, R::h1(t & 1) * 16 + hf * HALF_B);
         {
             float p0 = hh.x * wfc0, p1 = hh.x * wfc1;              // Linear partial over the wave's 4 units
             p0 += __shfl_xor(p0, 16); p1 += __shfl_xor(p1, 16);
@@ -371,7 +364,7 @@ void lstm2_coop_hpw_kernel(LstmWeights w, LstmArgs a) {
             if (lane < 16) {
                 const float2 pv = make_float2(p0, p1);
                 __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(__attribute__((ext_vector_type(2))) unsigned, pv), hr, (part * 32 + seq * 2) * 4,
-                                                      FCOFF + (((t & 1) * 2 + hf) * P) * 128, kSc1);
+                                                      R::fc * 16 + (((t & 1) * 2 + hf) * P) * 128, kSc1);
             }
         }
         FSNP_HPW_STAMP(6);

@@ -439,6 +439,80 @@ def test_asm_diff_compares_a_gemm_k_loop_opcode_for_opcode(tmp_path):
     assert all(r[1] == "identical" for r in rows if r[1] != "DIFFERENT")
 
 
+def _synthetic_asm(time_loop, k_group_loop=None, vgpr=96, lds=1024, kernarg=64):
+    """gfx950 assembly text of one kernel `kern`, as far as tools/asm_diff.py reads it: a depth-1 time loop of the given instructions
+    (with a depth-2 k-group loop in front of them if one is given), and the kernel's metadata entry."""
+    lines = ["kern:", "; %bb.0:", "\ts_load_dword s0, s[4:5], 0x0"]
+    lines += [".LBB0_1:                                ; =>This Loop Header: Depth=1"]
+    if k_group_loop is not None:
+        lines += ["                                        ;     Child Loop BB0_2 Depth 2",
+                  ".LBB0_2:                                ;   Parent Loop BB0_1 Depth=1",
+                  "                                        ; =>  This Inner Loop Header: Depth=2"]
+        lines += ["\t" + x for x in k_group_loop] + ["\ts_cbranch_scc1 .LBB0_2", "; %bb.3:                                ;   in Loop: Header=BB0_1 Depth=1"]
+    lines += ["\t" + x for x in time_loop] + ["\ts_cbranch_scc1 .LBB0_1", "; %bb.4:", "\ts_endpgm", ".Lfunc_end0:"]
+    meta = {".agpr_count": 0, ".group_segment_fixed_size": lds, ".kernarg_segment_size": kernarg, ".name": "kern", ".private_segment_fixed_size": 0,
+            ".sgpr_count": 40, ".sgpr_spill_count": 0, ".vgpr_count": vgpr, ".vgpr_spill_count": 0}
+    entry = ["amdhsa.kernels:"] + [("  - " if i == 0 else "    ") + f"{k}: {v}" for i, (k, v) in enumerate(meta.items())]
+    return "\n".join(lines + entry) + "\n"
+
+
+def test_asm_diff_not_worse_verdict_is_for_straight_line_time_loops_only(tmp_path):
+    """tools/asm_diff.py --not-worse, on synthetic assembly: a kernel without a depth-2 MFMA loop whose time loop came out shorter and
+    reordered (one register fewer) is DIFFERENT without the flag and (iii) with it; a longer time loop, or an equally long one with one
+    more wait, stays DIFFERENT with the flag; and the flag never applies to a kernel that has a depth-2 MFMA loop."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("asm_diff", os.path.join(ROOT, "tools", "asm_diff.py"))
+    diff = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(diff)
+    mf = "v_mfma_f32_32x32x2_f32 a[0:15], v0, v1, a[0:15]"
+    base = ["ds_read_b128 v[0:3], v9", "buffer_load_dwordx4 v[4:7], v8, s[0:3], 0 offen", "s_waitcnt vmcnt(0) lgkmcnt(0)", mf, mf,
+            "v_add_f32_e32 v10, v0, v1", "v_mul_f32_e32 v11, v2, v3", "v_mov_b32_e32 v12, v11", "ds_write_b32 v9, v12", "s_barrier"]
+    shorter = [base[1], base[0], base[2], mf, base[6], mf, base[5], "ds_write_b32 v9, v11", base[9]]        # reordered, one move fewer
+    longer = base[:7] + ["v_mov_b32_e32 v13, v10"] + base[7:]
+    more_waits = base[:5] + ["s_waitcnt lgkmcnt(0)"] + base[6:]                                           # same length, one more wait
+    inner = ["ds_read_b128 v[0:3], v9", mf, mf]
+
+    def verdicts(parent, new, **kw):
+        for name, text in (("p", parent), ("n", new)):
+            os.makedirs(tmp_path / name, exist_ok=True)
+            (tmp_path / name / "k.s").write_text(text)
+        rows, bad = diff.compare(diff.kernels(str(tmp_path / "p" / "k.s")), diff.kernels(str(tmp_path / "n" / "k.s")), **kw)
+        assert len(rows) == 1
+        return rows[0][1], bad, rows[0][2]
+
+    assert verdicts(_synthetic_asm(base), _synthetic_asm(base))[:2] == ("identical", 0)
+    v, bad, why = verdicts(_synthetic_asm(base), _synthetic_asm(shorter, vgpr=95))
+    assert (v, bad) == ("DIFFERENT", 1) and "depth-1 k-loop opcodes differ" in why and ".vgpr_count 96 -> 95" in why
+    assert verdicts(_synthetic_asm(base), _synthetic_asm(shorter, vgpr=95), allow_not_worse=True)[:2] == ("(iii)", 0)
+    assert verdicts(_synthetic_asm(base), _synthetic_asm(shorter, vgpr=97), allow_not_worse=True)[:2] == ("DIFFERENT", 1)     # a register more
+    v, bad, why = verdicts(_synthetic_asm(base), _synthetic_asm(longer), allow_not_worse=True)
+    assert (v, bad) == ("DIFFERENT", 1) and "time loop 11 -> 12 instructions" in why
+    v, bad, why = verdicts(_synthetic_asm(base), _synthetic_asm(more_waits), allow_not_worse=True)
+    assert (v, bad) == ("DIFFERENT", 1) and "s_waitcnt in time loop 1 -> 2" in why
+    # (iii) needs EQUAL counts of MFMAs and 16-byte buffer loads and equal LDS and kernarg sizes: less is not "not worse" there
+    fewer_mfma = [x for i, x in enumerate(shorter) if i != 3]                       # one MFMA dropped
+    fewer_loads = ["v_mov_b32_e32 v4, 0" if x.startswith("buffer_load_dwordx4") else x for x in shorter]
+    for new, why_part in ((_synthetic_asm(fewer_mfma, vgpr=95), "v_mfma in time loop 2 -> 1"),
+                          (_synthetic_asm(fewer_loads, vgpr=95), "buffer_load_dwordx4 in time loop 1 -> 0"),
+                          (_synthetic_asm(shorter, vgpr=95, lds=512), ".group_segment_fixed_size 1024 -> 512"),
+                          (_synthetic_asm(shorter, vgpr=95, kernarg=56), ".kernarg_segment_size 64 -> 56")):
+        v, bad, why = verdicts(_synthetic_asm(base), new, allow_not_worse=True)
+        assert (v, bad) == ("DIFFERENT", 1) and why_part in why, (v, why)
+    # a depth-2 MFMA loop: its opcodes must stay, however the rest of the time loop came out
+    with_inner = _synthetic_asm(base, k_group_loop=inner)
+    altered = _synthetic_asm(shorter, k_group_loop=[inner[1], inner[0], inner[2]], vgpr=95)
+    for kw in ({}, {"allow_not_worse": True}):
+        v, bad, why = verdicts(with_inner, altered, **kw)
+        assert (v, bad) == ("DIFFERENT", 1) and "k-group loop opcodes differ" in why
+    assert verdicts(with_inner, _synthetic_asm(shorter, k_group_loop=inner), allow_not_worse=True)[:2] == ("(ii)", 0)
+    assert verdicts(with_inner, _synthetic_asm(shorter, k_group_loop=inner, vgpr=95), allow_not_worse=True)[:2] == ("DIFFERENT", 1)
+    # the command line: exit status 1 without the flag, 0 with it
+    for name, text in (("p", _synthetic_asm(base)), ("n", _synthetic_asm(shorter, vgpr=95))):
+        (tmp_path / name / "k.s").write_text(text)
+    assert diff.main([str(tmp_path / "p"), str(tmp_path / "n")]) == 1
+    assert diff.main([str(tmp_path / "p"), str(tmp_path / "n"), "--not-worse"]) == 0
+
+
 def test_float4_epilogue_covers_every_element_once():
     """csrc/tcn.hip EpiF4 / the staging loops of the three DMA GEMM kernels, restated: the accumulator layout of
     v_mfma_f32_32x32x2_f32 (lane -> column lane & 31, register q -> row (q & 3) + 8 (q >> 2) + 4 (lane >> 5)) written into a row-major

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Compare two compiler outputs kernel by kernel:  tools/asm_diff.py PARENT_DIR NEW_DIR [--md]
+"""Compare two compiler outputs kernel by kernel:  tools/asm_diff.py PARENT_DIR NEW_DIR [--md] [--not-worse]
 
 Both directories hold the gfx950 assembly of the same sources (hipcc FLAGS --cuda-device-only -S X.hip -o DIR/X.s, FLAGS as
 in fullsubnet_plus_amd/_build.py).  Per kernel symbol the verdict is
@@ -9,6 +9,10 @@ in fullsubnet_plus_amd/_build.py).  Per kernel symbol the verdict is
              buffer loads, LDS reads, LDS writes, barriers and waits; a kernel WITHOUT a depth-2 MFMA loop (a GEMM: its k-loop is
              the depth-1 loop) must keep that time loop opcode for opcode instead, or
   DIFFERENT  with the figures that differ.
+With --not-worse a kernel WITHOUT a depth-2 MFMA loop on either side (the column-split recurrent kernels: their k-loops are unrolled
+into a time loop of thousands of instructions, which a freed register reorders) that would be DIFFERENT is instead
+  (iii)      "not worse": no register / spill / scratch figure higher, LDS and kernarg equal, a time loop that is not longer and holds
+             the same number of MFMAs and 16-byte buffer loads and no more LDS reads, LDS writes, barriers or waits.
 Exit status 1 if any kernel is DIFFERENT or missing on one side."""
 import os
 import re
@@ -85,7 +89,22 @@ def short(name):
     return m.group(1) + "<" + ", ".join(("true" if v == "1" else "false") if t == "b" else v for t, v in args) + ">"
 
 
-def compare(old, new):
+EQUAL_META = (".group_segment_fixed_size", ".kernarg_segment_size")
+EQUAL_COUNTS = (r"v_mfma", r"buffer_load_dwordx4")
+
+
+def not_worse(o, n):
+    """verdict (iii): see the module's docstring"""
+    if o["inner"] or n["inner"]:
+        return False
+    if any(int(n["meta"][k]) != int(o["meta"][k]) if k in EQUAL_META else int(n["meta"][k]) > int(o["meta"][k]) for k in META):
+        return False
+    if n["time_loop"] > o["time_loop"]:
+        return False
+    return all(n["counts"][p] == o["counts"][p] if p in EQUAL_COUNTS else n["counts"][p] <= o["counts"][p] for p in COUNTED)
+
+
+def compare(old, new, allow_not_worse=False):
     rows, bad = [], 0
     for name in sorted(set(old) | set(new)):
         if name not in old or name not in new:
@@ -110,17 +129,18 @@ def compare(old, new):
         why += [f"{p} in time loop {o['counts'][p]} -> {n['counts'][p]}" for p in COUNTED if o["counts"][p] != n["counts"][p]]
         changed = sum(1 for a, b in zip(o["text"].split("\n"), n["text"].split("\n")) if a != b) + \
             abs(len(o["text"].split("\n")) - len(n["text"].split("\n")))
-        rows.append((short(name), "DIFFERENT" if why else "(ii)", ("; ".join(why) + "; " if why else "") + figures + f"; ~{changed} lines changed"))
-        bad += bool(why)
+        verdict = "(ii)" if not why else "(iii)" if allow_not_worse and not_worse(o, n) else "DIFFERENT"
+        rows.append((short(name), verdict, ("; ".join(why) + "; " if why else "") + figures + f"; ~{changed} lines changed"))
+        bad += verdict == "DIFFERENT"
     return rows, bad
 
 
 def main(argv):
-    md = "--md" in argv
+    md, allow_not_worse = "--md" in argv, "--not-worse" in argv
     pdir, ndir = [a for a in argv if not a.startswith("--")]
     total_bad = 0
     for fn in sorted(f for f in os.listdir(pdir) if f.endswith(".s")):
-        rows, bad = compare(kernels(os.path.join(pdir, fn)), kernels(os.path.join(ndir, fn)))
+        rows, bad = compare(kernels(os.path.join(pdir, fn)), kernels(os.path.join(ndir, fn)), allow_not_worse)
         total_bad += bad
         if md:
             print(f"\n### {fn}\n\n| kernel | verdict | figures (new build) |\n|---|---|---|")
