@@ -4,6 +4,8 @@ import operator
 
 import torch
 
+from . import _lib
+
 
 RESAMPLE_Z = 32             # kResampleZ (csrc/resample.h): half = RESAMPLE_Z * max(up, down)
 RESAMPLE_MAX_RATIO = 640    # kResampleMaxRatio
@@ -61,3 +63,65 @@ def _host_lengths(lengths, batch, what):
         if not -2 ** 31 <= v < 2 ** 31:
             raise ValueError(f"{what}: utterance {b}: length {v} is not an int32")
     return (ctypes.c_int32 * batch)(*vals)
+
+
+def require_cuda(tensor):
+    """The one refusal of a tensor that is not on a GPU: nothing here computes on the CPU."""
+    if not tensor.is_cuda:
+        raise RuntimeError("fullsubnet_plus_amd runs on MI355X (HIP) only; move the model and inputs to 'cuda'. "
+                           "There is deliberately no CPU fallback.")
+
+
+def other_rate(sample_rate, model_rate, what):
+    """A call's sample_rate argument -> None (None, or the model's own rate) or the int rate, after resample_plan has accepted both
+    directions (ValueError otherwise)."""
+    if sample_rate is None:
+        return None
+    resample_plan(sample_rate, model_rate, what)
+    resample_plan(model_rate, sample_rate, what)
+    return None if _rate(sample_rate, what) == model_rate else int(sample_rate)
+
+
+def reads_in_place(wav):
+    """Whether [B, samples] goes to the PCM entry points, which read int16 and strided fp32 where they lie (include/fsnp_pcm.h); every
+    other tensor goes to the fp32 entry points as it always has, as contiguous rows after .float()."""
+    return wav.dtype == torch.int16 or (wav.dtype == torch.float32 and wav.shape[1] > 1 and wav.stride(1) != 1)
+
+
+def f32_rows(wav):
+    """[B, samples] -> fp32 with contiguous rows, what the fp32 entry points read"""
+    wav = wav.float()
+    return wav if wav.stride(1) == 1 else wav.contiguous()
+
+
+def pcm_input(wav):
+    """[B, samples] -> (tensor, FSNP_SAMPLE_* code, row stride, step) as the PCM entry points take them: int16 or fp32, copied only where
+    the step between samples is below 1 (an expanded tensor)."""
+    if wav.dtype not in (torch.int16, torch.float32):
+        wav = wav.float()
+    if wav.shape[1] > 1 and wav.stride(1) < 1:
+        wav = wav.contiguous()
+    return wav, _lib.SAMPLE_S16 if wav.dtype == torch.int16 else _lib.SAMPLE_F32, wav.stride(0), max(wav.stride(1), 1)
+
+
+def output_format(out_format, like, what, peak=True):
+    """An out_format argument -> (FSNP_SAMPLE_* code, torch dtype of the result).  None follows the dtype `like`: int16 -> "s16", anything
+    else -> "f32".  peak=False: a stream session, which has no "s16_peak".  ValueError under the caller's name `what` otherwise."""
+    allowed = ("f32", "s16", "s16_peak") if peak else ("f32", "s16")
+    if out_format is None:
+        out_format = "s16" if like == torch.int16 else "f32"
+    elif out_format not in allowed:
+        raise ValueError(f"{what}: out_format {out_format!r} is none of None, " + ", ".join(repr(f) for f in allowed)
+                         + (" (a stream has no peak: 's16_peak' is a format of enhance_wave only)" if out_format == "s16_peak" else ""))
+    code = _lib.SAMPLE_FORMATS[out_format]
+    return code, torch.float32 if code == _lib.SAMPLE_F32 else torch.int16
+
+
+def clipped_pointer(clipped, batch, device, what):
+    """A call's `clipped` argument -> None or the device pointer of its int32 [batch]; ValueError under the caller's name `what`."""
+    if clipped is None:
+        return None
+    if not (clipped.is_cuda and clipped.device == device and clipped.dtype == torch.int32 and clipped.shape == (batch,)
+            and clipped.is_contiguous()):
+        raise ValueError(f"{what}: clipped must be a contiguous torch.int32 tensor [{batch}] on {device}")
+    return clipped.data_ptr()

@@ -216,9 +216,33 @@ WAVE_RATE_STREAM_SYMBOLS = {
 }
 RESAMPLE_MAX_RATIO = 640     # max(up, down) of a pair (include/fsnp_resample.h)
 
+# The one registry: include/<header> -> the table that mirrors it, in the order the headers were added.  load() binds exactly these;
+# tests/test_host_abi_signatures.py compares every table with its header's prototypes, type by type.
+HEADER_TABLES = {
+    "fsnp.h": SYMBOLS, "fsnp_debug.h": SYMBOLS, "fsnp_lengths.h": LENGTHS_SYMBOLS, "fsnp_stream.h": STREAM_SYMBOLS,
+    "fsnp_wave_stream.h": WAVE_STREAM_SYMBOLS, "fsnp_stream_live.h": LIVE_STREAM_SYMBOLS, "fsnp_spec_stream.h": SPEC_STREAM_SYMBOLS,
+    "fsnp_device_weights.h": DEVICE_WEIGHTS_SYMBOLS, "fsnp_stft_geometry.h": STFT_GEOMETRY_SYMBOLS, "fsnp_pcm.h": PCM_SYMBOLS,
+    "fsnp_resample.h": RESAMPLE_SYMBOLS, "fsnp_wave_rate_stream.h": WAVE_RATE_STREAM_SYMBOLS,
+}
+
 ABI_VERSION = 13         # FSNP_ABI_VERSION of the include/fsnp.h these signatures were written against
 
 _lib = None
+
+
+def all_symbols(registry=None):
+    """name -> (restype, argtypes) over every table of the registry (a table two headers share counts once); RuntimeError if a name
+    is in two tables."""
+    merged, seen = {}, []
+    for header, table in (HEADER_TABLES if registry is None else registry).items():
+        if any(table is t for t in seen):
+            continue
+        seen.append(table)
+        both = sorted(set(merged) & set(table))
+        if both:
+            raise RuntimeError(f"_lib: {both} of include/{header} are in another header's table too")
+        merged.update(table)
+    return merged
 
 
 def load(build_if_missing=True):
@@ -237,10 +261,7 @@ def load(build_if_missing=True):
     if not os.path.exists(path):
         raise RuntimeError(f"{path} is missing: run `python -m fullsubnet_plus_amd._build`")
     lib = ctypes.CDLL(path)
-    for name, (res, args) in (list(SYMBOLS.items()) + list(LENGTHS_SYMBOLS.items()) + list(STREAM_SYMBOLS.items()) + list(WAVE_STREAM_SYMBOLS.items())
-                              + list(LIVE_STREAM_SYMBOLS.items()) + list(SPEC_STREAM_SYMBOLS.items()) + list(DEVICE_WEIGHTS_SYMBOLS.items())
-                              + list(STFT_GEOMETRY_SYMBOLS.items()) + list(PCM_SYMBOLS.items()) + list(RESAMPLE_SYMBOLS.items())
-                              + list(WAVE_RATE_STREAM_SYMBOLS.items())):
+    for name, (res, args) in all_symbols().items():
         fn = getattr(lib, name)          # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

@@ -21,8 +21,10 @@ import weakref
 import torch
 import torch.nn as nn
 
-from . import _lib, _policy
-from ._args import _host_lengths, _rate, resample_plan
+from . import _call, _lib, _policy
+from ._args import _host_lengths, _rate, clipped_pointer, f32_rows, other_rate, output_format, pcm_input, reads_in_place, require_cuda, resample_plan
+from ._call import resolve_device as _resolve_device
+from ._debug import _DebugHooks
 
 _TCN_DILATIONS = (1, 2, 5, 9, 1, 2, 5, 9)
 
@@ -45,18 +47,23 @@ class _StageHolder(nn.Module):
     """A parameter holder that is CALLABLE like the reference's submodule: the call runs the owning model's HIP stage kernels on the branch
     this holder belongs to (_HipModel._attach_holders sets owner, branch and the C entry point).  No torch fallback."""
 
-    def __getstate__(self):              # (the back-reference is re-made by the owner; a weakref does not pickle)
+    def __getstate__(self):              # (the back-reference is re-made by the owner: _HipModel._attach_holders; a weakref does not pickle)
         state = self.__dict__.copy()
         for k in ("_fsnp_owner", "_fsnp_branch", "_fsnp_entry"):
             state.pop(k, None)
         return state
 
-    def forward(self, x):
+    def _owner(self, otherwise):
+        """-> the model whose kernels a call on this holder runs; RuntimeError(otherwise) for a holder that no model attached"""
         owner = self.__dict__.get("_fsnp_owner")
         owner = owner() if owner is not None else None
         if owner is None:
-            raise RuntimeError(f"{self.__class__.__name__}: this parameter holder is not a callable stage of a fullsubnet_plus_amd model "
-                               "(only the full-band attention layers and TCN stacks of FullSubNet_Plus, and the sub-band recurrent model, are)")
+            raise RuntimeError(otherwise)
+        return owner
+
+    def forward(self, x):
+        owner = self._owner(f"{self.__class__.__name__}: this parameter holder is not a callable stage of a fullsubnet_plus_amd model "
+                            "(only the full-band attention layers and TCN stacks of FullSubNet_Plus, and the sub-band recurrent model, are)")
         return owner._stage_call(self.__dict__["_fsnp_entry"], self.__dict__["_fsnp_branch"], x)
 
 
@@ -113,7 +120,7 @@ class _FullBandParams(_StageHolder):
         self.fc_output_layer = nn.Linear(num_freqs, num_freqs if output_size is None else output_size)
 
 
-class _SubBandParams(nn.Module):
+class _SubBandParams(_StageHolder):
     """Parameter holder named like SequenceModel(sequence_model="LSTM") (sequence_model.py:31-38,78-79)."""
 
     def __init__(self, input_size, hidden, output_size, kind="LSTM"):
@@ -122,23 +129,13 @@ class _SubBandParams(nn.Module):
         self.sequence_model = rnn(input_size, hidden, num_layers=2, batch_first=True)
         self.fc_output_layer = nn.Linear(hidden, output_size)
 
-    def __getstate__(self):              # (the back-reference is re-made by the owner: _HipModel._attach_holders; a weakref does not pickle)
-        state = self.__dict__.copy()
-        state.pop("_fsnp_owner", None)
-        return state
-
     def forward(self, x):
         """SequenceModel.forward (sequence_model.py:97-123) of the sub-band model as a call on the submodule, like the reference's
         `self.sb_model(sb_input)` (fullsubnet_plus.py:203): x [N, input, T] -> [N, output, T] on the fused HIP kernels of the model that
         owns this holder (fsnp_lstm2_fc).  No torch fallback: CPU tensors are refused like forward() refuses them."""
         assert x.dim() == 3, f"The shape of input is {x.shape}."          # sequence_model.py:103
-        owner = self.__dict__.get("_fsnp_owner")
-        owner = owner() if owner is not None else None
-        if owner is None:
-            raise RuntimeError("this sub-band model holder is not attached to a fullsubnet_plus_amd model")
-        if not x.is_cuda:
-            raise RuntimeError("fullsubnet_plus_amd runs on MI355X (HIP) only; move the model and inputs to 'cuda'. "
-                               "There is deliberately no CPU fallback.")
+        owner = self._owner("this sub-band model holder is not attached to a fullsubnet_plus_amd model")
+        require_cuda(x)
         return owner.lstm2_fc(x)
 
 
@@ -189,18 +186,20 @@ def _reference_style_init(m):
             (nn.init.orthogonal_ if p.dim() >= 2 else nn.init.normal_)(p.data)
 
 
-def _resolve_device(device):
-    """"cuda" -> the current device with its index (a handle is bound to one device)."""
-    dev = torch.device(device)
-    if dev.type == "cuda" and dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
-    return dev
+def _check_norm_and_activations(norm_type, *activations):
+    """What both constructors refuse like the reference (base_model.py:328, sequence_model.py:96)."""
+    if norm_type not in _lib.NORM_TYPES:
+        raise NotImplementedError("You must set up a type of Norm. "
+                                  "e.g. offline_laplace_norm, cumulative_laplace_norm, forgetting_norm, etc.")
+    for act in activations:
+        if act and act not in _lib.ACTIVATIONS:
+            raise NotImplementedError(f"Not implemented activation function {act}")
 
 
-class _HipModel(nn.Module):
+class _HipModel(_DebugHooks, nn.Module):
     """Everything the two reference models share on the HIP side: the fsnp_handle, lazy strict weight packing,
-    the fsnp_forward call and the test / bench hooks.  Subclasses hold the reference's parameter tree and
-    provide ``_config()``."""
+    the fsnp_forward call and - from _DebugHooks, the counterpart of include/fsnp_debug.h - the test / bench hooks.
+    Subclasses hold the reference's parameter tree and provide ``_config()``."""
 
     def _attach_holders(self):
         """The sub-band holder is callable like the reference's submodule (`model.sb_model(x)`): it needs to know whose kernels to run."""
@@ -221,18 +220,13 @@ class _HipModel(nn.Module):
     def _stage_call(self, entry, branch, x):
         """One of the forward's submodules on a caller's [B, F, T] tensor (fsnp_channel_attention / fsnp_fullband_model)."""
         assert x.dim() == 3, f"The shape of input is {x.shape}."
-        if not x.is_cuda:
-            raise RuntimeError("fullsubnet_plus_amd runs on MI355X (HIP) only; move the model and inputs to 'cuda'. "
-                               "There is deliberately no CPU fallback.")
+        require_cuda(x)
         assert x.shape[1] == self.num_freqs, f"expected {self.num_freqs} channels, got {x.shape[1]}"
         lib = self._ensure_handle(x.device)
         x = x if x.dtype == torch.float32 else x.float()
         out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
         st = (ctypes.c_int64 * 3)(*x.stride())
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        with torch.cuda.device(x.device):
-            _lib.check(getattr(lib, entry)(self._handle, int(branch), x.data_ptr(), ctypes.byref(st), out.data_ptr(), x.shape[0], x.shape[2],
-                                           ctypes.c_void_p(stream)), entry)
+        _call.call(getattr(lib, entry), x.device, self._handle, int(branch), x.data_ptr(), ctypes.byref(st), out.data_ptr(), x.shape[0], x.shape[2])
         return out
 
     def _init_hip(self):
@@ -266,39 +260,33 @@ class _HipModel(nn.Module):
     @staticmethod
     def _stage_input(input):
         assert input.dim() == 4, f"The dim of input is {input.dim()}. It should be four dim."
-        if not input.is_cuda:
-            raise RuntimeError("fullsubnet_plus_amd runs on MI355X (HIP) only; move the tensor to 'cuda'. There is deliberately no CPU fallback.")
+        require_cuda(input)
         x = input if input.dtype == torch.float32 else input.float()
-        return x, (ctypes.c_int64 * 4)(*x.stride()), torch.cuda.current_stream(x.device).cuda_stream
+        return x, (ctypes.c_int64 * 4)(*x.stride())
 
     @staticmethod
     def unfold(input, num_neighbor):
         """BaseModel.unfold (audio_zen/model/base_model.py:15-47): [B, C, F, T] -> [B, F, C, 2 num_neighbor + 1, T], the overlapped sub-band
         units along the frequency axis (reflect padded); num_neighbor < 1: [B, F, C, 1, T].  HIP kernel (fsnp_unfold) on CUDA tensors of
         any strides.  (The forward never calls it: the recurrent kernels gather the sub-band input on the fly.)"""
-        x, st, stream = _HipModel._stage_input(input)
+        x, st = _HipModel._stage_input(input)
         B, C, F, T = x.shape
         ns = 2 * int(num_neighbor) + 1 if num_neighbor >= 1 else 1
         out = torch.empty((B, F, C, ns, T), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.load().fsnp_unfold(x.data_ptr(), ctypes.byref(st), out.data_ptr(), B, C, F, T, int(num_neighbor), ctypes.c_void_p(stream)),
-                       "fsnp_unfold")
+        _call.call(_lib.load().fsnp_unfold, x.device, x.data_ptr(), ctypes.byref(st), out.data_ptr(), B, C, F, T, int(num_neighbor))
         return out
 
     def norm_wrapper(self, norm_type: str):
         """BaseModel.norm_wrapper (base_model.py:318-330): -> a callable [B, C, F, T] -> [B, C, F, T] running the named normalisation as HIP
         kernels (fsnp_norm); unknown names raise NotImplementedError like the reference."""
-        if norm_type not in _lib.NORM_TYPES:
-            raise NotImplementedError("You must set up a type of Norm. "
-                                      "e.g. offline_laplace_norm, cumulative_laplace_norm, forgetting_norm, etc.")
+        _check_norm_and_activations(norm_type)
         code = _lib.NORM_TYPES[norm_type]
 
         def norm(input):
-            x, st, stream = _HipModel._stage_input(input)
+            x, st = _HipModel._stage_input(input)
             B, C, F, T = x.shape
             out = torch.empty((B, C, F, T), dtype=torch.float32, device=x.device)
-            with torch.cuda.device(x.device):
-                _lib.check(_lib.load().fsnp_norm(code, x.data_ptr(), ctypes.byref(st), out.data_ptr(), B, C, F, T, ctypes.c_void_p(stream)), "fsnp_norm")
+            _call.call(_lib.load().fsnp_norm, x.device, code, x.data_ptr(), ctypes.byref(st), out.data_ptr(), B, C, F, T)
             return out
         norm.__name__ = norm_type
         return norm
@@ -380,24 +368,30 @@ class _HipModel(nn.Module):
             st.handle, st.device, st.packed_key = hp, device, None
             self.__dict__.pop("_vs_applied", None)
             if self.__dict__.get("_verify_every"):
-                _lib.check(lib.fsnp_set_verify(hp, int(self.__dict__["_verify_every"])), "fsnp_set_verify")
+                _call.check(lib.fsnp_set_verify, hp, int(self.__dict__["_verify_every"]))
             if "_hop_length" in self.__dict__:
-                _lib.check(lib.fsnp_set_hop_length(hp, self.__dict__["_hop_length"]), "fsnp_set_hop_length")
-        key = self._weights_key()
-        if key != st.packed_key and self.weight_upload != "host":
+                _call.check(lib.fsnp_set_hop_length, hp, self.__dict__["_hop_length"])
+        if self._weights_key() != st.packed_key:
             self._upload_weights(lib, device)
             self._watch_parameters(lib, device)
             st.packed_key = self._weights_key()
-        elif key != st.packed_key:
-            for name, tensor in self.state_dict().items():
-                t = tensor.detach().to("cpu", torch.float32).contiguous()
-                _lib.check(lib.fsnp_set_weight(st.handle, name.encode(), t.data_ptr(), t.numel()),
-                           f"fsnp_set_weight({name})")
-            with torch.cuda.device(device):
-                _lib.check(lib.fsnp_commit_weights(st.handle), "fsnp_commit_weights")
-            self._watch_parameters(lib, device)
-            st.packed_key = self._weights_key()
         return lib
+
+    def _common_config(self):
+        """-> an FsnpConfig with the fields both models fill from attributes of the same names; _config() adds the model's own."""
+        cfg = _lib.FsnpConfig()
+        cfg.num_freqs = self.num_freqs
+        cfg.look_ahead = self.look_ahead
+        cfg.sb_num_neighbors = self.sb_num_neighbors
+        cfg.fb_num_neighbors = self.fb_num_neighbors
+        cfg.sb_hidden = self.sb_model_hidden_size
+        cfg.output_size = self.output_size
+        cfg.norm_type = _lib.NORM_TYPES[self.norm_type]
+        cfg.fb_act = _lib.ACTIVATIONS[self.fb_output_activate_function or None]
+        cfg.sb_act = _lib.ACTIVATIONS[self.sb_output_activate_function or None]
+        cfg.num_groups_in_drop_band = self.num_groups_in_drop_band
+        cfg.sequence_model = _lib.SEQUENCE_MODELS[self.sequence_model]
+        return cfg
 
     def _upload_plan(self, device):
         """[(name, tensor, "host" | "device")] over state_dict(): which setter each tensor goes through under self.weight_upload."""
@@ -413,24 +407,24 @@ class _HipModel(nn.Module):
         return plan
 
     def _upload_weights(self, lib, device):
-        """The re-pack of weight_upload "auto" / "device": tensors on the handle's device go to fsnp_set_weight_device on the current
+        """The re-pack under every weight_upload: tensors that _upload_plan marks "device" go to fsnp_set_weight_device on the current
         stream (converted there first if they are not contiguous fp32; the library copies them into its own arena in stream order, so
-        a temporary may be released right away), the others to fsnp_set_weight; fsnp_commit_weights_on then packs on the device
-        when every tensor came that way, else on the host."""
-        st = self._hip
-        stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        with torch.cuda.device(device):
+        a temporary may be released right away), the others ("host": every tensor) to fsnp_set_weight; fsnp_commit_weights_on then
+        packs on the device when every tensor came that way, else on the host exactly as fsnp_commit_weights does."""
+        h = self._hip.handle
+
+        def upload(stream):                 # (one device context and one stream for the few hundred setter calls of a re-pack)
             for name, tensor, where in self._upload_plan(device):
                 if where == "device":
                     t = tensor.detach()
                     if t.dtype != torch.float32 or not t.is_contiguous():
                         t = t.to(torch.float32).contiguous()
-                    _lib.check(lib.fsnp_set_weight_device(st.handle, name.encode(), t.data_ptr(), t.numel(), stream),
-                               f"fsnp_set_weight_device({name})")
+                    _lib.check(lib.fsnp_set_weight_device(h, name.encode(), t.data_ptr(), t.numel(), stream), f"fsnp_set_weight_device({name})")
                 else:
                     t = tensor.detach().to("cpu", torch.float32).contiguous()
-                    _lib.check(lib.fsnp_set_weight(st.handle, name.encode(), t.data_ptr(), t.numel()), f"fsnp_set_weight({name})")
-            _lib.check(lib.fsnp_commit_weights_on(st.handle, stream), "fsnp_commit_weights_on")
+                    _lib.check(lib.fsnp_set_weight(h, name.encode(), t.data_ptr(), t.numel()), f"fsnp_set_weight({name})")
+            return lib.fsnp_commit_weights_on(h, stream)
+        _call.call(upload, device, what="fsnp_commit_weights_on")
 
     def _watch_parameters(self, lib, device):
         """fsnp_watch_weights over the parameters' own storage - possible when every parameter is contiguous fp32 on the handle's
@@ -440,10 +434,7 @@ class _HipModel(nn.Module):
         n = len(plist) if ok else 0
         ptrs = (ctypes.c_void_p * max(n, 1))(*([p.data_ptr() for p in plist] if ok else [None]))
         nums = (ctypes.c_int64 * max(n, 1))(*([p.numel() for p in plist] if ok else [0]))
-        stream = torch.cuda.current_stream(device).cuda_stream
-        with torch.cuda.device(device):
-            _lib.check(lib.fsnp_watch_weights(self._hip.handle, ptrs, nums, n, max(1, int(self.weight_watch_every)), ctypes.c_void_p(stream)),
-                       "fsnp_watch_weights")
+        _call.call(lib.fsnp_watch_weights, device, self._hip.handle, ptrs, nums, n, max(1, int(self.weight_watch_every)))
         was = self.__dict__.get("_fsnp_watched", False)
         self.__dict__["_fsnp_watched"] = ok
         if ok != was:                       # the key's fingerprint slot follows (None while the device watches)
@@ -471,9 +462,7 @@ class _HipModel(nn.Module):
         for t in ins[1:]:
             assert t.shape == noisy_mag.shape
         assert num_freqs == self.num_freqs, f"expected {self.num_freqs} frequency bins, got {num_freqs}"
-        if not noisy_mag.is_cuda:
-            raise RuntimeError("fullsubnet_plus_amd runs on MI355X (HIP) only; move the model and inputs to 'cuda'. "
-                               "There is deliberately no CPU fallback.")
+        require_cuda(noisy_mag)
         device = noisy_mag.device
         if lengths is not None:
             if int(batch_offset) != 0 or global_batch is not None:
@@ -504,36 +493,23 @@ class _HipModel(nn.Module):
         out = torch.empty((gb if parity else batch_size, self.output_size, out_f, num_frames), dtype=torch.float32, device=device)
         if parity and not standalone:
             out.zero_()     # a shard writes only its own rows of the global tensor
-        stream = torch.cuda.current_stream(device).cuda_stream
-        mode = _lib.MODE_PARITY if parity else _lib.MODE_FULL
+        # the entry point without lengths takes the sharding arguments where the one with lengths (never sharded, never parity) has none
+        shard = (_lib.MODE_PARITY if parity else _lib.MODE_FULL, int(batch_offset), gb) if lengths is None else ()
         if complex_in:
-            cst = (ctypes.c_int64 * 3)(*noisy_mag.stride())
-
-            def enqueue():
-                with torch.cuda.device(device):
-                    if lengths is not None:
-                        return lib.fsnp_forward_complex_lengths(self._handle, torch.view_as_real(noisy_mag).data_ptr(), ctypes.byref(cst),
-                                                                lengths, out.data_ptr(), batch_size, num_frames, ctypes.c_void_p(stream))
-                    return lib.fsnp_forward_complex(self._handle, torch.view_as_real(noisy_mag).data_ptr(), ctypes.byref(cst),
-                                                    out.data_ptr(), batch_size, num_frames, mode, int(batch_offset), gb,
-                                                    ctypes.c_void_p(stream))
-            _policy.enqueue_retrying_stale(enqueue, self._stale_weights_noticed, "fsnp_forward_complex")
-            return out
-        strides = (ctypes.c_int64 * 3 * 3)()
-        for i, t in enumerate(ins):
-            sb, _, sf, st = t.stride()
-            strides[i][0], strides[i][1], strides[i][2] = sb, sf, st
-        ptrs = [t.data_ptr() for t in ins] + [None] * (3 - len(ins))
-
-        def enqueue():
-            with torch.cuda.device(device):
-                if lengths is not None:
-                    return lib.fsnp_forward_lengths(self._handle, ptrs[0], ptrs[1], ptrs[2], ctypes.byref(strides), lengths,
-                                                    out.data_ptr(), batch_size, num_frames, ctypes.c_void_p(stream))
-                return lib.fsnp_forward(self._handle, ptrs[0], ptrs[1], ptrs[2],
-                                        ctypes.byref(strides), out.data_ptr(), batch_size, num_frames,
-                                        mode, int(batch_offset), gb, ctypes.c_void_p(stream))
-        _policy.enqueue_retrying_stale(enqueue, self._stale_weights_noticed, "fsnp_forward")
+            fn = lib.fsnp_forward_complex if lengths is None else lib.fsnp_forward_complex_lengths
+            strides = (ctypes.c_int64 * 3)(*noisy_mag.stride())
+            ptrs = [torch.view_as_real(noisy_mag).data_ptr()]
+        else:
+            fn = lib.fsnp_forward if lengths is None else lib.fsnp_forward_lengths
+            strides = (ctypes.c_int64 * 3 * 3)()
+            for i, t in enumerate(ins):
+                sb, _, sf, st = t.stride()
+                strides[i][0], strides[i][1], strides[i][2] = sb, sf, st
+            ptrs = [t.data_ptr() for t in ins] + [None] * (3 - len(ins))
+        lens = () if lengths is None else (lengths,)
+        args = (self._handle, *ptrs, ctypes.byref(strides), *lens, out.data_ptr(), batch_size, num_frames, *shard)
+        _policy.enqueue_retrying_stale(lambda: _call.enqueue(fn, device, *args), self._stale_weights_noticed,
+                                       "fsnp_forward_complex" if complex_in else "fsnp_forward")
         return out
 
     def _stale_weights_noticed(self):
@@ -565,7 +541,7 @@ class _HipModel(nn.Module):
         lib = _lib.load()
         warnings.warn(f"fullsubnet_plus_amd: {_lib.last_error()}; re-running this batch on the one-tile-per-CU kernel", RuntimeWarning)
         prev = self.__dict__.get("_lstm_coop_mode", 1)
-        _lib.check(lib.fsnp_debug_set_lstm_coop(self._handle, 0), "fsnp_debug_set_lstm_coop")
+        _call.check(lib.fsnp_debug_set_lstm_coop, self._handle, 0)
         try:
             out = run()
             _lib.check(self._wait_and_poll(), "fsnp_forward (retry)")
@@ -580,8 +556,7 @@ class _HipModel(nn.Module):
         "deferred" reports through poll_errors() / check_errors() / the next call).  0 = off.  Also `model.verify_every = N`
         before the first forward, or FSNP_VERIFY_EVERY=N in the environment."""
         self.__dict__["_verify_every"] = int(every)
-        lib = self._ensure_handle(_resolve_device(device))
-        _lib.check(lib.fsnp_set_verify(self._handle, int(every)), "fsnp_set_verify")
+        self._setting("fsnp_set_verify", int(every), device=device)
 
     @property
     def verify_every(self):
@@ -591,7 +566,7 @@ class _HipModel(nn.Module):
     def verify_every(self, every):
         self.__dict__["_verify_every"] = int(every)
         if self._hip.handle is not None:
-            _lib.check(_lib.load().fsnp_set_verify(self._handle, int(every)), "fsnp_set_verify")
+            _call.check(_lib.load().fsnp_set_verify, self._handle, int(every))
 
     @property
     def hop_length(self):
@@ -609,7 +584,7 @@ class _HipModel(nn.Module):
             raise ValueError(f"{self.__class__.__name__}.hop_length: {why}")
         self.__dict__["_hop_length"] = int(hop)
         if self._hip.handle is not None:
-            _lib.check(_lib.load().fsnp_set_hop_length(self._handle, int(hop)), "fsnp_set_hop_length")
+            _call.check(_lib.load().fsnp_set_hop_length, self._handle, int(hop))
 
     @property
     def sample_rate(self):
@@ -628,26 +603,29 @@ class _HipModel(nn.Module):
         """-> verification passes run so far (fsnp_verify_count)."""
         return int(_lib.load().fsnp_verify_count(self._handle))
 
-    def verify_sample_stats(self):
-        """-> {"samples", "skipped", "eligible_forwards"} of the sampled exchange verification (fsnp_set_verify_sample)."""
-        out = (ctypes.c_int64 * 3)()
-        _lib.check(_lib.load().fsnp_debug_verify_sample_stats(self._handle, ctypes.byref(out)), "fsnp_debug_verify_sample_stats")
-        return {"samples": int(out[0]), "skipped": int(out[1]), "eligible_forwards": int(out[2])}
-
-    def debug_corrupt_exchange(self, step):
-        """Test hook (fsnp_debug_corrupt_exchange): the next forward's column-split launches publish one wrong h0 value at `step` - 1."""
-        _lib.check(_lib.load().fsnp_debug_corrupt_exchange(self._handle, int(step)), "fsnp_debug_corrupt_exchange")
-
     def poll_errors(self):
         """Raise if a finished launch flagged the handle; no synchronisation (fsnp_poll_errors)."""
-        _lib.check(_lib.load().fsnp_poll_errors(self._handle), "fsnp_poll_errors")
+        _call.check(_lib.load().fsnp_poll_errors, self._handle)
+
+    def check_errors(self):
+        """Synchronise and raise if an earlier call failed on the device (see fsnp_check_errors)."""
+        _call.check(_lib.load().fsnp_check_errors, self._handle)
+
+    def set_precision(self, mode, device="cuda"):
+        """"fp32" (default) or "bf16_ih" (BASELINE.json configs[4]: layer-1 ih-GEMM of the sub-band LSTM in bf16; fsnp.h)."""
+        assert mode in ("fp32", "bf16_ih")
+        self._setting("fsnp_set_precision", {"fp32": 0, "bf16_ih": 1}[mode], device=device)
 
     def set_pipeline(self, enable=True, device="cuda"):
         """Pipelined serving mode (include/fsnp.h: fsnp_set_pipeline): the remainder chunks of the sub-band plan overlap
         the NEXT forward's full-band stages.  Outputs are complete only after flush()."""
-        lib = self._ensure_handle(_resolve_device(device))
-        _lib.check(lib.fsnp_set_pipeline(self._handle, int(bool(enable))), "fsnp_set_pipeline")
+        self._setting("fsnp_set_pipeline", int(bool(enable)), device=device)
         self._pipeline = bool(enable)
+
+    def _setting(self, entry, *values, device="cuda"):
+        """One of the handle's setters, fsnp_set_* / fsnp_debug_set_*(handle, values...), on the handle of `device` (created if need be)."""
+        lib = self._ensure_handle(_resolve_device(device))
+        _call.check(getattr(lib, entry), self._handle, *values)
 
     def reserve(self, max_batch, max_frames, max_samples=0, device="cuda", sample_rate=None):
         """Grow the handle's workspace once to what any forward of <= max_batch utterances x max_frames frames needs (and the
@@ -655,30 +633,19 @@ class _HipModel(nn.Module):
         never re-allocates (fsnp_reserve; stream-ordered on the current stream, no device synchronisation).  sample_rate: the rate
         enhance_wave will be called with; max_samples then counts at that rate, max_frames stays in model steps, and the tap tables
         of both directions are uploaded too (fsnp_reserve_rate)."""
-        rate = None
-        if sample_rate is not None:
-            what = f"{self.__class__.__name__}.reserve"
-            resample_plan(sample_rate, self.sample_rate, what)
-            resample_plan(self.sample_rate, sample_rate, what)
-            rate = None if _rate(sample_rate, what) == self.sample_rate else int(sample_rate)
+        rate = other_rate(sample_rate, self.sample_rate, f"{self.__class__.__name__}.reserve")
         dev = _resolve_device(device)
         lib = self._ensure_handle(dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
         mode = _lib.MODE_PARITY if (self.batch_mode == "parity" and max_batch > 1 and self.num_groups_in_drop_band > 1) else _lib.MODE_FULL
-        with torch.cuda.device(dev):
-            _lib.check(lib.fsnp_reserve(self._handle, int(max_batch), int(max_frames), mode, 0 if rate else int(max_samples),
-                                        ctypes.c_void_p(stream)), "fsnp_reserve")
-            if rate and int(max_samples) > 0:
-                _lib.check(lib.fsnp_reserve_rate(self._handle, int(max_batch), int(max_samples), rate, self.sample_rate,
-                                                 ctypes.c_void_p(stream)), "fsnp_reserve_rate")
+        _call.call(lib.fsnp_reserve, dev, self._handle, int(max_batch), int(max_frames), mode, 0 if rate else int(max_samples))
+        if rate and int(max_samples) > 0:
+            _call.call(lib.fsnp_reserve_rate, dev, self._handle, int(max_batch), int(max_samples), rate, self.sample_rate)
 
     def flush(self):
         """Order the current stream after every deferred launch of earlier forwards (fsnp_flush)."""
         if self._hip.handle is None:
             return
-        stream = torch.cuda.current_stream(self._hip.device).cuda_stream
-        with torch.cuda.device(self._hip.device):
-            _lib.check(_lib.load().fsnp_flush(self._handle, ctypes.c_void_p(stream)), "fsnp_flush")
+        _call.call(_lib.load().fsnp_flush, self._hip.device, self._handle)
 
     def forward_complex(self, noisy_complex, batch_offset=0, global_batch=None, lengths=None):
         """the forward fed with the complex64 STFT itself ([B, F, T], any strides - torch.stft's
@@ -706,64 +673,35 @@ class _HipModel(nn.Module):
         return self._apply_cirm(mask, noisy_complex, lengths)
 
     # ------------------------------------------------------------------ STFT / iSTFT in HIP
-    def _wave_args(self, wav):
-        assert wav.dim() == 2, "expected [B, samples]"
-        if not wav.is_cuda:
-            raise RuntimeError("fullsubnet_plus_amd runs on MI355X (HIP) only; there is deliberately no CPU fallback.")
-        wav = wav.float()
-        if wav.stride(1) != 1:
-            wav = wav.contiguous()
-        return wav, self._ensure_handle(wav.device), torch.cuda.current_stream(wav.device).cuda_stream
-
-    @staticmethod
-    def _pcm_view(wav):
-        """-> the tensor the PCM entry points read in place (include/fsnp_pcm.h: int16 or fp32 at any strides), or None where the
-        fp32 entry point takes it as it always has (contiguous rows, after .float())."""
-        if wav.dtype == torch.int16:
-            return wav
-        if wav.dtype == torch.float32 and wav.shape[1] > 1 and wav.stride(1) != 1:
-            return wav if wav.stride(1) >= 1 else wav.contiguous()
-        return None
-
     def stft(self, wav):
         """audio_zen/acoustics/feature.py:10-31 (torch.stft, n_fft = win_length = 2 (F - 1), hop_length = self.hop_length, hann, center)
         in HIP: wav [B, samples] -> complex64 [B, F, T = 1 + samples // hop_length] with torch.stft's strides.  wav: fp32, or
         torch.int16 full-scale PCM (the spectrum of wav.float() / 32768, bit for bit), rows and samples at any strides - one channel
         of an interleaved buffer is read in place (fsnp_stft_pcm)."""
         assert wav.dim() == 2, "expected [B, samples]"
-        if not wav.is_cuda:
-            raise RuntimeError("fullsubnet_plus_amd runs on MI355X (HIP) only; there is deliberately no CPU fallback.")
-        pcm = self._pcm_view(wav)
-        if pcm is None:
-            wav, lib, stream = self._wave_args(wav)
-        else:
-            wav, lib, stream = pcm, self._ensure_handle(pcm.device), torch.cuda.current_stream(pcm.device).cuda_stream
+        require_cuda(wav)
+        lib = self._ensure_handle(wav.device)
         B, L = wav.shape
         T = 1 + L // self.hop_length
         spec = torch.empty((B, T, self.num_freqs), dtype=torch.complex64, device=wav.device)
-        with torch.cuda.device(wav.device):
-            if pcm is None:
-                _lib.check(lib.fsnp_stft(self._handle, wav.data_ptr(), wav.stride(0), torch.view_as_real(spec).data_ptr(), B, L,
-                                         ctypes.c_void_p(stream)), "fsnp_stft")
-            else:
-                fmt = _lib.SAMPLE_S16 if wav.dtype == torch.int16 else _lib.SAMPLE_F32
-                _lib.check(lib.fsnp_stft_pcm(self._handle, wav.data_ptr(), fmt, wav.stride(0), max(wav.stride(1), 1),
-                                             torch.view_as_real(spec).data_ptr(), B, L, ctypes.c_void_p(stream)), "fsnp_stft_pcm")
+        if reads_in_place(wav):
+            wav, fmt, row, step = pcm_input(wav)
+            _call.call(lib.fsnp_stft_pcm, wav.device, self._handle, wav.data_ptr(), fmt, row, step, torch.view_as_real(spec).data_ptr(), B, L)
+        else:
+            wav = f32_rows(wav)
+            _call.call(lib.fsnp_stft, wav.device, self._handle, wav.data_ptr(), wav.stride(0), torch.view_as_real(spec).data_ptr(), B, L)
         return spec.permute(0, 2, 1)
 
     def istft(self, spec, length):
         """feature.py:34-56 (torch.istft(..., length=length), at self.hop_length) in HIP: complex64 [B, F, T] (any strides) -> [B, length]."""
         assert spec.dim() == 3 and spec.dtype == torch.complex64 and spec.shape[1] == self.num_freqs
-        if not spec.is_cuda:
-            raise RuntimeError("fullsubnet_plus_amd runs on MI355X (HIP) only; there is deliberately no CPU fallback.")
+        require_cuda(spec)
         lib = self._ensure_handle(spec.device)
         B, _, T = spec.shape
         out = torch.empty((B, int(length)), dtype=torch.float32, device=spec.device)
         st = (ctypes.c_int64 * 3)(*spec.stride())
-        stream = torch.cuda.current_stream(spec.device).cuda_stream
-        with torch.cuda.device(spec.device):
-            _lib.check(lib.fsnp_istft(self._handle, torch.view_as_real(spec).data_ptr(), ctypes.byref(st), out.data_ptr(),
-                                      out.stride(0), B, T, int(length), ctypes.c_void_p(stream)), "fsnp_istft")
+        _call.call(lib.fsnp_istft, spec.device, self._handle, torch.view_as_real(spec).data_ptr(), ctypes.byref(st), out.data_ptr(), out.stride(0),
+                   B, T, int(length))
         return out
 
     def enhance_wave(self, noisy, lengths=None, out_format=None, clipped=None, sample_rate=None):
@@ -792,71 +730,28 @@ class _HipModel(nn.Module):
         for a rate that is no positive integer or a ratio with max(up, down) > 640, before any GPU is touched."""
         assert self.output_size == 2, "the cIRM epilogue needs the two mask channels (decompress_cIRM, acoustics/mask.py:60-63)"
         assert noisy.dim() == 2, "expected [B, samples]"
-        rate = None
-        if sample_rate is not None:
-            what = f"{self.__class__.__name__}.enhance_wave"
-            resample_plan(sample_rate, self.sample_rate, what)
-            resample_plan(self.sample_rate, sample_rate, what)
-            rate = None if _rate(sample_rate, what) == self.sample_rate else int(sample_rate)
-        if out_format is not None and out_format not in _lib.SAMPLE_FORMATS:
-            raise ValueError(f"enhance_wave: out_format {out_format!r} is none of None, 'f32', 's16', 's16_peak'")
-        if not noisy.is_cuda:
-            raise RuntimeError("fullsubnet_plus_amd runs on MI355X (HIP) only; there is deliberately no CPU fallback.")
+        rate = other_rate(sample_rate, self.sample_rate, f"{self.__class__.__name__}.enhance_wave")
+        ofmt, out_dtype = output_format(out_format, noisy.dtype, "enhance_wave")
+        require_cuda(noisy)
         samples = None if lengths is None else _host_lengths(lengths, noisy.shape[0], f"{self.__class__.__name__}.enhance_wave")
-        pcm = self._pcm_view(noisy)
-        ofmt = _lib.SAMPLE_FORMATS[out_format or ("s16" if noisy.dtype == torch.int16 else "f32")]
-        if pcm is not None or ofmt != _lib.SAMPLE_F32 or clipped is not None or rate is not None:
-            return self._enhance_wave_pcm(noisy if pcm is None else pcm, samples, ofmt, clipped, rate)
-        wav, lib, stream = self._wave_args(noisy)
-        B, L = wav.shape
-        out = torch.empty((B, L), dtype=torch.float32, device=wav.device)
-        what = "fsnp_enhance_wave" if samples is None else "fsnp_enhance_wave_lengths"
-
-        def enqueue():
-            with torch.cuda.device(wav.device):
-                if samples is not None:
-                    return lib.fsnp_enhance_wave_lengths(self._handle, wav.data_ptr(), wav.stride(0), out.data_ptr(), out.stride(0),
-                                                         samples, B, L, ctypes.c_void_p(stream))
-                return lib.fsnp_enhance_wave(self._handle, wav.data_ptr(), wav.stride(0), out.data_ptr(), out.stride(0), B, L,
-                                             ctypes.c_void_p(stream))
-
-        def run():
-            _policy.enqueue_retrying_stale(enqueue, self._stale_weights_noticed, what)
-            return out
-        return self._checked(run)
-
-    def _enhance_wave_pcm(self, wav, samples, ofmt, clipped, rate=None):
-        """enhance_wave through fsnp_enhance_wave_pcm: wav int16 or floating point at any strides, samples the ctypes int32[B] of
-        _host_lengths or None, ofmt a _lib.SAMPLE_* value.  rate: None, or the samples' rate in Hz where it is not the model's
-        (fsnp_enhance_wave_rate)."""
-        if wav.dtype not in (torch.int16, torch.float32):
-            wav = wav.float()
-        if wav.shape[1] > 1 and wav.stride(1) < 1:
-            wav = wav.contiguous()
-        B, L = wav.shape
-        if clipped is not None:
-            if not (clipped.is_cuda and clipped.device == wav.device and clipped.dtype == torch.int32 and clipped.shape == (B,)
-                    and clipped.is_contiguous()):
-                raise ValueError(f"enhance_wave: clipped must be a contiguous torch.int32 tensor [{B}] on {wav.device}")
-        lib, stream = self._ensure_handle(wav.device), torch.cuda.current_stream(wav.device).cuda_stream
-        ifmt = _lib.SAMPLE_S16 if wav.dtype == torch.int16 else _lib.SAMPLE_F32
-        out = torch.empty((B, L), dtype=torch.float32 if ofmt == _lib.SAMPLE_F32 else torch.int16, device=wav.device)
-
-        model_rate = self.sample_rate
-
-        def enqueue():
-            with torch.cuda.device(wav.device):
-                if rate is not None:
-                    return lib.fsnp_enhance_wave_rate(self._handle, wav.data_ptr(), ifmt, wav.stride(0), max(wav.stride(1), 1), out.data_ptr(),
-                                                      ofmt, out.stride(0), 1, samples, B, L, None if clipped is None else clipped.data_ptr(),
-                                                      rate, model_rate, ctypes.c_void_p(stream))
-                return lib.fsnp_enhance_wave_pcm(self._handle, wav.data_ptr(), ifmt, wav.stride(0), max(wav.stride(1), 1), out.data_ptr(), ofmt,
-                                                 out.stride(0), 1, samples, B, L, None if clipped is None else clipped.data_ptr(),
-                                                 ctypes.c_void_p(stream))
+        B, L = noisy.shape
+        if reads_in_place(noisy) or ofmt != _lib.SAMPLE_F32 or clipped is not None or rate is not None:
+            # include/fsnp_pcm.h: int16 or floating point at any strides, any output format; fsnp_enhance_wave_rate where the samples'
+            # rate is not the model's
+            wav, ifmt, row, step = pcm_input(noisy)
+            clip = clipped_pointer(clipped, B, wav.device, "enhance_wave")
+            fn, rates = ("fsnp_enhance_wave_pcm", ()) if rate is None else ("fsnp_enhance_wave_rate", (rate, self.sample_rate))
+            out = torch.empty((B, L), dtype=out_dtype, device=wav.device)
+            args = (wav.data_ptr(), ifmt, row, step, out.data_ptr(), ofmt, out.stride(0), 1, samples, B, L, clip, *rates)
+        else:
+            wav = f32_rows(noisy)
+            fn, lens = ("fsnp_enhance_wave", ()) if samples is None else ("fsnp_enhance_wave_lengths", (samples,))
+            out = torch.empty((B, L), dtype=torch.float32, device=wav.device)
+            args = (wav.data_ptr(), wav.stride(0), out.data_ptr(), out.stride(0), *lens, B, L)
+        entry = getattr(self._ensure_handle(wav.device), fn)
 
         def run():
-            _policy.enqueue_retrying_stale(enqueue, self._stale_weights_noticed,
-                                           "fsnp_enhance_wave_pcm" if rate is None else "fsnp_enhance_wave_rate")
+            _policy.enqueue_retrying_stale(lambda: _call.enqueue(entry, wav.device, self._handle, *args), self._stale_weights_noticed, fn)
             return out
         return self._checked(run)
 
@@ -871,28 +766,16 @@ class _HipModel(nn.Module):
         what = f"{self.__class__.__name__}.resample"
         assert wav.dim() == 2, "expected [B, samples]"
         up, down, _ = resample_plan(from_rate, to_rate, what)
-        if out_format is not None and out_format not in _lib.SAMPLE_FORMATS:
-            raise ValueError(f"resample: out_format {out_format!r} is none of None, 'f32', 's16', 's16_peak'")
-        if not wav.is_cuda:
-            raise RuntimeError("fullsubnet_plus_amd runs on MI355X (HIP) only; there is deliberately no CPU fallback.")
+        ofmt, out_dtype = output_format(out_format, wav.dtype, "resample")
+        require_cuda(wav)
         samples = None if lengths is None else _host_lengths(lengths, wav.shape[0], what)
-        if wav.dtype not in (torch.int16, torch.float32):
-            wav = wav.float()
-        if wav.shape[1] > 1 and wav.stride(1) < 1:
-            wav = wav.contiguous()
+        wav, ifmt, row, step = pcm_input(wav)
         B, L = wav.shape
-        if clipped is not None:
-            if not (clipped.is_cuda and clipped.device == wav.device and clipped.dtype == torch.int32 and clipped.shape == (B,)
-                    and clipped.is_contiguous()):
-                raise ValueError(f"resample: clipped must be a contiguous torch.int32 tensor [{B}] on {wav.device}")
-        ofmt = _lib.SAMPLE_FORMATS[out_format or ("s16" if wav.dtype == torch.int16 else "f32")]
-        ifmt = _lib.SAMPLE_S16 if wav.dtype == torch.int16 else _lib.SAMPLE_F32
-        lib, stream = self._ensure_handle(wav.device), torch.cuda.current_stream(wav.device).cuda_stream
-        out = torch.empty((B, -(-L * up // down)), dtype=torch.float32 if ofmt == _lib.SAMPLE_F32 else torch.int16, device=wav.device)
-        with torch.cuda.device(wav.device):
-            _lib.check(lib.fsnp_resample_pcm(self._handle, wav.data_ptr(), ifmt, wav.stride(0), max(wav.stride(1), 1), out.data_ptr(), ofmt,
-                                             out.stride(0), 1, samples, B, L, int(from_rate), int(to_rate),
-                                             None if clipped is None else clipped.data_ptr(), ctypes.c_void_p(stream)), "fsnp_resample_pcm")
+        clip = clipped_pointer(clipped, B, wav.device, "resample")
+        lib = self._ensure_handle(wav.device)
+        out = torch.empty((B, -(-L * up // down)), dtype=out_dtype, device=wav.device)
+        _call.call(lib.fsnp_resample_pcm, wav.device, self._handle, wav.data_ptr(), ifmt, row, step, out.data_ptr(), ofmt, out.stride(0), 1,
+                   samples, B, L, int(from_rate), int(to_rate), clip)
         return out
 
     def _apply_cirm(self, mask, noisy_complex, lengths=None):
@@ -902,18 +785,11 @@ class _HipModel(nn.Module):
         xr, orr = torch.view_as_real(noisy_complex), torch.view_as_real(out)
         st = (ctypes.c_int64 * 3)(*noisy_complex.stride())
         ost = (ctypes.c_int64 * 3)(*out.stride())
-        stream = torch.cuda.current_stream(noisy_complex.device).cuda_stream
-        with torch.cuda.device(noisy_complex.device):
-            if lengths is not None:
-                _lib.check(_lib.load().fsnp_apply_cirm_lengths(mask.data_ptr(), xr.data_ptr(), ctypes.byref(st), orr.data_ptr(),
-                                                               ctypes.byref(ost), lengths, B, F, T, ctypes.c_void_p(stream)),
-                           "fsnp_apply_cirm_lengths")
-            else:
-                _lib.check(_lib.load().fsnp_apply_cirm(mask.data_ptr(), xr.data_ptr(), ctypes.byref(st), orr.data_ptr(),
-                                                       ctypes.byref(ost), B, F, T, ctypes.c_void_p(stream)), "fsnp_apply_cirm")
+        lib, lens = _lib.load(), () if lengths is None else (lengths,)
+        _call.call(lib.fsnp_apply_cirm if lengths is None else lib.fsnp_apply_cirm_lengths, noisy_complex.device,
+                   mask.data_ptr(), xr.data_ptr(), ctypes.byref(st), orr.data_ptr(), ctypes.byref(ost), *lens, B, F, T)
         return out
 
-    # ------------------------------------------------------------------ test / bench helpers
     def lstm2_fc(self, x):
         """Fused sub-band LSTM + Linear alone (sequence_model.py:113-123): x [N, input, T] -> [N, 2, T]."""
         assert x.dim() == 3 and x.is_cuda
@@ -921,180 +797,8 @@ class _HipModel(nn.Module):
         n, _, steps = x.shape
         xt = x.permute(0, 2, 1).contiguous().float()
         out = torch.empty((n, self.output_size, steps), dtype=torch.float32, device=x.device)
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        with torch.cuda.device(x.device):
-            _lib.check(lib.fsnp_lstm2_fc(self._handle, xt.data_ptr(), out.data_ptr(), n, steps,
-                                         ctypes.c_void_p(stream)), "fsnp_lstm2_fc")
+        _call.call(lib.fsnp_lstm2_fc, x.device, self._handle, xt.data_ptr(), out.data_ptr(), n, steps)
         return out
-
-    def read_stage(self, name, batch, frames):
-        """Stage buffer of the last forward, time-major: [B, T', F] (gates: [B, F])."""
-        lib = _lib.load()
-        rows = batch if name.startswith("gate_") else batch * (frames + self.look_ahead)
-        host = torch.empty((rows, self.num_freqs), dtype=torch.float32)
-        _lib.check(lib.fsnp_read_stage(self._handle, name.encode(), host.data_ptr(), host.numel()), "fsnp_read_stage")
-        return host if name.startswith("gate_") else host.view(batch, frames + self.look_ahead, self.num_freqs)
-
-    def debug_set_num_cus(self, num_cus, device="cuda"):
-        """Test hook: plan LSTM tiles as if the chip had `num_cus` CUs (exercises multi-round / VALU-row tiles)."""
-        lib = self._ensure_handle(_resolve_device(device))
-        _lib.check(lib.fsnp_debug_set_num_cus(self._handle, int(num_cus)), "fsnp_debug_set_num_cus")
-
-    def debug_set_lstm_waves(self, waves, device="cuda"):
-        """Tuning hook: waves per workgroup of the fused LSTM kernel (12 = three per SIMD, or 4)."""
-        lib = self._ensure_handle(_resolve_device(device))
-        _lib.check(lib.fsnp_debug_set_lstm_waves(self._handle, int(waves)), "fsnp_debug_set_lstm_waves")
-
-    def debug_set_lstm_coop(self, mode, device="cuda"):
-        """Tuning hook: 1 = use the column-split LSTM kernels for small batches (default), 0 = never, 2 = as 1 with the
-        K-split kernel's serial (round-1) step schedule instead of the layer-skewed one and without the half-tile ping-pong
-        kernel, 4 = as 1 + the half-tile ping-pong kernel even where FSNP_COOP_HP=0."""
-        lib = self._ensure_handle(_resolve_device(device))
-        _lib.check(lib.fsnp_debug_set_lstm_coop(self._handle, int(mode)), "fsnp_debug_set_lstm_coop")
-        self.__dict__["_lstm_coop_mode"] = int(mode)
-
-    def debug_set_gemm_dma(self, mode, device="cuda"):
-        """Tuning hook: 1 = full-band TCN GEMMs on the LDS-DMA kernels with GroupNorm folded into the weights (default; small
-        batches: the split-K kernel tcn_gemm_sk_kernel; sconv of larger problems: the 64-row kernel tcn_gemm_dma64_kernel), 2 = as 1 but
-        never the small-batch kernel, 3 = the 128-row DMA kernel only, 0 = the general GEMM kernel."""
-        lib = self._ensure_handle(_resolve_device(device))
-        _lib.check(lib.fsnp_debug_set_gemm_dma(self._handle, int(mode)), "fsnp_debug_set_gemm_dma")
-
-    def set_precision(self, mode, device="cuda"):
-        """"fp32" (default) or "bf16_ih" (BASELINE.json configs[4]: layer-1 ih-GEMM of the sub-band LSTM in bf16; fsnp.h)."""
-        assert mode in ("fp32", "bf16_ih")
-        lib = self._ensure_handle(_resolve_device(device))
-        _lib.check(lib.fsnp_set_precision(self._handle, {"fp32": 0, "bf16_ih": 1}[mode]), "fsnp_set_precision")
-
-    def debug_set_chaos(self, seed, device="cuda"):
-        """Test hook: drift injection for the column-split recurrent kernels (fsnp_debug_set_chaos); 0 = off."""
-        lib = self._ensure_handle(_resolve_device(device))
-        _lib.check(lib.fsnp_debug_set_chaos(self._handle, int(seed)), "fsnp_debug_set_chaos")
-
-    def debug_inject_error(self):
-        """Test hook: pretend an inter-workgroup wait timed out (see fsnp_debug_inject_error)."""
-        _lib.check(_lib.load().fsnp_debug_inject_error(self._handle), "fsnp_debug_inject_error")
-
-    def check_errors(self):
-        """Synchronise and raise if an earlier call failed on the device (see fsnp_check_errors)."""
-        _lib.check(_lib.load().fsnp_check_errors(self._handle), "fsnp_check_errors")
-
-    def set_timing(self, enable=True):
-        _lib.check(_lib.load().fsnp_set_timing(self._handle, int(bool(enable))), "fsnp_set_timing")
-
-    def get_timing(self, reset=True):
-        """-> {"lstm_ms", "fullband_ms", "forward_ms", "count"}: hipEvent sums on the forward's stream."""
-        ms = (ctypes.c_double * 4)()
-        cnt = (ctypes.c_int64 * 4)()
-        _lib.check(_lib.load().fsnp_get_timing(self._handle, ctypes.byref(ms), ctypes.byref(cnt), int(reset)),
-                   "fsnp_get_timing")
-        return {"lstm_ms": ms[0], "fullband_ms": ms[1], "forward_ms": ms[2], "lstm_first_chunk_ms": ms[3], "count": int(cnt[0])}
-
-    def launch_clock(self):
-        """-> {"wall_ms", "s_memtime_ticks", "s_memtime_mhz"} of the LAST launch of the one-tile-per-CU LSTM kernel on this handle, as its
-        workgroup 0 stamped them (fsnp_debug_launch_clock; synchronise first), or None if there was no such launch."""
-        out = (ctypes.c_double * 7)()
-        with torch.cuda.device(self._hip.device):
-            if _lib.load().fsnp_debug_launch_clock(self._handle, ctypes.byref(out)) != 0:
-                return None
-        return {"wall_ms": out[2], "s_memtime_ticks": out[0], "s_memtime_mhz": out[3], "slowest_workgroup_ms": out[4],
-                "fastest_workgroup_ms": out[5], "most_cycles_of_a_workgroup": out[6]}
-
-    def describe_plan(self, batch, parity=False):
-        """-> [{"kernel", "sequences", "tiles", "valu_rows", "precision", "workgroups", "deferred_when_pipelined"}, ...]: how the
-        sub-band sequences of a `batch`-utterance forward are cut into kernel launches, the arithmetic each launch runs in under the
-        current set_precision mode, and whether the pipelined serving loop sends it to the side stream (fsnp_describe_plan_ex)."""
-        buf = (ctypes.c_int32 * 112)()
-        n = _lib.load().fsnp_describe_plan_ex(self._handle, int(batch), int(parity), buf, 16)
-        if n < 0:
-            raise RuntimeError(_lib.last_error())
-        names = {0: ("gru2_fc_kernel" if self.sequence_model == "GRU" else "lstm2_fc_kernel") + " (one 32-row tile per CU)",
-                 1: "lstm2_coop_kernel (K split)",
-                 2: "lstm2_coopn_kernel (three-way column split)", 3: "sub-band TCN",
-                 4: "lstm2_fc16_kernel (one 16-row tile per CU)",
-                 11: "lstm2_generic_kernel (runtime-sized fp32 FMA kernel: no tuned instantiation for these sizes)",
-                 12: "lstm2_coop_hp_kernel (16 units per workgroup, gate-split waves, two half tiles per row tile in turn)",
-                 13: "lstm2_coopw_kernel (a wave owns 8 / 16 units over the whole K, layer-skewed, no workgroup barrier)",
-                 14: "lstm2_coop_hpw_kernel (16 units per workgroup, a wave owns 4 of them over the whole K, two half tiles per row tile in turn, no workgroup barrier)"}
-        prec = {0: "f32", 1: "f32 + bf16 layer-1 ih-GEMM"}
-        return [{"kernel": names[buf[7 * i]], "sequences": buf[7 * i + 1], "tiles": buf[7 * i + 2], "valu_rows": buf[7 * i + 3],
-                 "precision": prec[buf[7 * i + 4]], "workgroups": buf[7 * i + 5], "deferred_when_pipelined": bool(buf[7 * i + 6])} for i in range(n)]
-
-    def pipeline_pairing(self, batch):
-        """-> [{"chunk", "kind", "tiles", "workgroups", "max_per_xcd", "fb_workgroups", "fb_max_per_xcd", "fb_per_cu", "side_by_side"}, ...]:
-        for each sub-band launch the pipelined loop defers at `batch` utterances (full mode), whether the next forward's full-band LSTM
-        runs beside it or is chained behind it, as this handle decides it (fsnp_debug_pipeline_pairing; FullSubNet+: [])."""
-        buf = (ctypes.c_int32 * (9 * 16))()
-        n = _lib.load().fsnp_debug_pipeline_pairing(self._handle, int(batch), buf, 16)
-        if n < 0:
-            raise RuntimeError(_lib.last_error())
-        keys = ("chunk", "kind", "tiles", "workgroups", "max_per_xcd", "fb_workgroups", "fb_max_per_xcd", "fb_per_cu", "side_by_side")
-        return [dict(zip(keys, buf[9 * i:9 * i + 9])) for i in range(n)]
-
-    def fullband_launch(self, batch):
-        """-> {"kernel", "tiles", "rows_per_tile", "units"}: the full-band LSTM launch of a `batch`-utterance forward of the original
-        FullSubNet (fsnp_debug_fullband_launch; kernel: "coop_seq" / "fbv" / "generic")."""
-        out = (ctypes.c_int32 * 4)()
-        _lib.check(_lib.load().fsnp_debug_fullband_launch(self._handle, int(batch), ctypes.byref(out)), "fsnp_debug_fullband_launch")
-        return {"kernel": ("coop_seq", "fbv", "generic")[out[0]], "tiles": out[1], "rows_per_tile": out[2], "units": out[3]}
-
-    def coop_chain_stats(self, reset=False):
-        """-> (beside, chained): this handle's column-split launches that ran beside / were chained behind one of its own launches on
-        another stream since the last reset (fsnp_debug_coop_chain_stats)."""
-        out = (ctypes.c_int64 * 2)()
-        _lib.check(_lib.load().fsnp_debug_coop_chain_stats(self._handle, ctypes.byref(out), int(bool(reset))), "fsnp_debug_coop_chain_stats")
-        return int(out[0]), int(out[1])
-
-    def debug_set_costs(self, costs=None, workgroups_per_cu=1, device="cuda"):
-        """Test hook: pin the planner's cost table (_lib.NUM_COSTS values, fsnp_get_costs order; None = built-in) and whether it
-        may put two column-split workgroups on a CU (fsnp_debug_set_costs).  A shorter table prices the launch shapes it does
-        not name out of every plan (19 values = no half-tile ping-pong kernel and no wave-owned column split, 21 = no wave-owned
-        column split)."""
-        lib = self._ensure_handle(_resolve_device(device))
-        n = _lib.NUM_COSTS
-        if costs is not None and len(costs) < n:
-            costs = list(costs) + [1e9] * (n - len(costs))
-        arr = (ctypes.c_double * n)(*costs) if costs is not None else None
-        _lib.check(lib.fsnp_debug_set_costs(self._handle, arr, int(workgroups_per_cu)), "fsnp_debug_set_costs")
-
-    @staticmethod
-    def _cost_dict(v):
-        return {"ksplit_us": {u: {"one_per_cu": v[2 * i], "two_per_cu": v[2 * i + 1], "one_tile": v[14 + i]} for i, u in enumerate((8, 16, 32, 64))},
-                "coopn_us": {r: {"one_per_cu": v[8 + 2 * i], "two_per_cu": v[9 + 2 * i]} for i, r in enumerate((1, 2))},
-                "rowtile_us": v[12], "valu_row_surcharge": v[13], "rowtile16_us": v[18],
-                "halftile_pingpong_us": {"one_tile": v[19], "full_launch": v[20]},
-                "coopw_us": {**{u: {"one_tile": v[23 + i], "full_launch": v[21 + i]} for i, u in enumerate((32, 64))},
-                             96: {"one_tile": v[26], "full_launch": v[25]}}}
-
-    def measure_costs(self):
-        """-> the same table MEASURED on the device (fsnp_measure_costs; ~0.3 s, synchronises; the plan is not touched)."""
-        buf = (ctypes.c_double * _lib.NUM_COSTS)()
-        with torch.cuda.device(self._hip.device):
-            _lib.check(_lib.load().fsnp_measure_costs(self._handle, ctypes.byref(buf)), "fsnp_measure_costs")
-        return self._cost_dict(list(buf))
-
-    def dump_config(self):
-        """-> text: the handle's configuration and every effective FSNP_* setting (fsnp_dump_config), for bug reports."""
-        lib = _lib.load()
-        n = lib.fsnp_dump_config(self._handle, None, 0)
-        buf = ctypes.create_string_buffer(int(n))
-        lib.fsnp_dump_config(self._handle, buf, n)
-        return buf.value.decode()
-
-    def planner_costs_raw(self):
-        """-> the _lib.NUM_COSTS values of fsnp_get_costs (the layout debug_set_costs takes)."""
-        buf = (ctypes.c_double * _lib.NUM_COSTS)()
-        _lib.check(_lib.load().fsnp_get_costs(self._handle, ctypes.byref(buf), None, None), "fsnp_get_costs")
-        return list(buf)
-
-    def planner_costs(self):
-        """-> the per-step cost table (us) the sub-band planner minimises (fsnp_get_costs)."""
-        buf, cal, occ = (ctypes.c_double * _lib.NUM_COSTS)(), ctypes.c_int32(), ctypes.c_int32()
-        _lib.check(_lib.load().fsnp_get_costs(self._handle, ctypes.byref(buf), ctypes.byref(cal), ctypes.byref(occ)), "fsnp_get_costs")
-        return {**self._cost_dict(list(buf)), "calibrated": bool(cal.value), "workgroups_per_cu": occ.value}
-
-    def forward_flops(self, batch, frames, parity=False):
-        return float(_lib.load().fsnp_forward_flops(self._handle, batch, frames, int(parity)))
 
 
 class FullSubNet_Plus(_HipModel):
@@ -1129,12 +833,7 @@ class FullSubNet_Plus(_HipModel):
             raise NotImplementedError("subband_num != 1 only works with channel_attention_model='ECA' (as in the reference)")
         if subband_num < 1:
             raise NotImplementedError("subband_num must be >= 1")
-        if norm_type not in _lib.NORM_TYPES:
-            raise NotImplementedError("You must set up a type of Norm. "
-                                      "e.g. offline_laplace_norm, cumulative_laplace_norm, forgetting_norm, etc.")
-        for act in (fb_output_activate_function, sb_output_activate_function):
-            if act and act not in _lib.ACTIVATIONS:
-                raise NotImplementedError(f"Not implemented activation function {act}")
+        _check_norm_and_activations(norm_type, fb_output_activate_function, sb_output_activate_function)
 
         self.num_channels = num_freqs
         def make_attention():
@@ -1178,23 +877,12 @@ class FullSubNet_Plus(_HipModel):
 
     # ------------------------------------------------------------------ handle / weights
     def _config(self):
-        cfg = _lib.FsnpConfig()
-        cfg.num_freqs = self.num_freqs
-        cfg.look_ahead = self.look_ahead
-        cfg.sb_num_neighbors = self.sb_num_neighbors
-        cfg.fb_num_neighbors = self.fb_num_neighbors
+        cfg = self._common_config()
         cfg.tcn_hidden = 512
         cfg.num_tcn_blocks = len(_TCN_DILATIONS)
-        cfg.sb_hidden = self.sb_model_hidden_size
-        cfg.output_size = self.output_size
-        cfg.norm_type = _lib.NORM_TYPES[self.norm_type]
-        cfg.fb_act = _lib.ACTIVATIONS[self.fb_output_activate_function or None]
-        cfg.sb_act = _lib.ACTIVATIONS[self.sb_output_activate_function or None]
         for i, k in enumerate(self.kersize):
             cfg.kersize[i] = int(k)
-        cfg.num_groups_in_drop_band = self.num_groups_in_drop_band
         cfg.attention = _lib.ATTENTION[self.channel_attention_model]
-        cfg.sequence_model = _lib.SEQUENCE_MODELS[self.sequence_model]
         cfg.subband_num = self.subband_num
         return cfg
 
@@ -1212,20 +900,21 @@ class FullSubNet_Plus(_HipModel):
         """
         return self._checked(lambda: self._forward_impl([noisy_mag, noisy_real, noisy_imag], batch_offset, global_batch, lengths=lengths))
 
+    def _not_streamable(self, opener):
+        from .stream import PLUS_REASON
+        raise NotImplementedError(f"{self.__class__.__name__}.{opener}: {PLUS_REASON}")
+
     def open_stream(self, slots, max_chunk=16, device="cuda", live=False):
         """FullSubNet+ is not streamable (see fullsubnet_plus_amd.stream): always raises NotImplementedError with the reason."""
-        from .stream import PLUS_REASON
-        raise NotImplementedError(f"{self.__class__.__name__}.open_stream: {PLUS_REASON}")
+        self._not_streamable("open_stream")
 
     def open_wave_stream(self, slots, max_samples=4096, device="cuda", live=False, sample_rate=None):
         """FullSubNet+ is not streamable (see fullsubnet_plus_amd.stream): always raises NotImplementedError with the reason."""
-        from .stream import PLUS_REASON
-        raise NotImplementedError(f"{self.__class__.__name__}.open_wave_stream: {PLUS_REASON}")
+        self._not_streamable("open_wave_stream")
 
     def open_spec_stream(self, slots, max_chunk=16, device="cuda", live=False):
         """FullSubNet+ is not streamable (see fullsubnet_plus_amd.stream): always raises NotImplementedError with the reason."""
-        from .stream import PLUS_REASON
-        raise NotImplementedError(f"{self.__class__.__name__}.open_spec_stream: {PLUS_REASON}")
+        self._not_streamable("open_spec_stream")
 
 
 class _FullBandLSTMParams(_StageHolder):
@@ -1260,12 +949,7 @@ class FullSubNet(_HipModel):
                  ):
         super().__init__()
         assert sequence_model in ("GRU", "LSTM"), f"{self.__class__.__name__} only support GRU and LSTM."
-        if norm_type not in _lib.NORM_TYPES:
-            raise NotImplementedError("You must set up a type of Norm. "
-                                      "e.g. offline_laplace_norm, cumulative_laplace_norm, forgetting_norm, etc.")
-        for act in (fb_output_activate_function, sb_output_activate_function):
-            if act and act not in _lib.ACTIVATIONS:
-                raise NotImplementedError(f"Not implemented activation function {act}")
+        _check_norm_and_activations(norm_type, fb_output_activate_function, sb_output_activate_function)
         self.fb_model = _FullBandLSTMParams(num_freqs, fb_model_hidden_size, sequence_model)
         self.sb_model = _SubBandParams((sb_num_neighbors * 2 + 1) + (fb_num_neighbors * 2 + 1), sb_model_hidden_size, 2,
                                        sequence_model)
@@ -1288,24 +972,13 @@ class FullSubNet(_HipModel):
             self.apply(self.weight_init)          # fullsubnet.py:65-66
 
     def _config(self):
-        cfg = _lib.FsnpConfig()
+        cfg = self._common_config()
         cfg.model = _lib.MODEL_FULLSUBNET
-        cfg.num_freqs = self.num_freqs
-        cfg.look_ahead = self.look_ahead
-        cfg.sb_num_neighbors = self.sb_num_neighbors
-        cfg.fb_num_neighbors = self.fb_num_neighbors
         cfg.tcn_hidden = self.fb_model_hidden_size       # fb_model_hidden_size (fsnp.h: FSNP_MODEL_FULLSUBNET)
         cfg.num_tcn_blocks = 0
-        cfg.sb_hidden = self.sb_model_hidden_size
-        cfg.output_size = 2
-        cfg.norm_type = _lib.NORM_TYPES[self.norm_type]
-        cfg.fb_act = _lib.ACTIVATIONS[self.fb_output_activate_function or None]
-        cfg.sb_act = _lib.ACTIVATIONS[self.sb_output_activate_function or None]
         for i in range(3):
             cfg.kersize[i] = 1
-        cfg.num_groups_in_drop_band = self.num_groups_in_drop_band
         cfg.attention = 0
-        cfg.sequence_model = _lib.SEQUENCE_MODELS[self.sequence_model]
         return cfg
 
     def forward(self, noisy_mag, batch_offset=0, global_batch=None, lengths=None):
@@ -1352,11 +1025,9 @@ class FullSubNet(_HipModel):
         why = wave_refusal(self)
         if why is not None:
             raise NotImplementedError(f"{what}: {why}")
-        if sample_rate is not None:
-            resample_plan(sample_rate, self.sample_rate, what)
-            resample_plan(self.sample_rate, sample_rate, what)
-            if _rate(sample_rate, what) != self.sample_rate:
-                return WaveRateStream(self, slots, max_samples, _resolve_device(device), live=live, sample_rate=int(sample_rate))
+        rate = other_rate(sample_rate, self.sample_rate, what)
+        if rate is not None:
+            return WaveRateStream(self, slots, max_samples, _resolve_device(device), live=live, sample_rate=rate)
         return WaveStream(self, slots, max_samples, _resolve_device(device), live=live)
 
     def open_spec_stream(self, slots, max_chunk=16, device="cuda", live=False):

@@ -33,8 +33,8 @@ import numbers
 
 import torch
 
-from . import _lib, _policy
-from ._args import _host_lengths
+from . import _call, _lib, _policy
+from ._args import _host_lengths, output_format, pcm_input, require_cuda
 
 PLUS_REASON = ("FullSubNet+ cannot be streamed exactly: its full-band TCN blocks are not causal and normalise with GroupNorm(1, C) over "
                "the whole clip, and TSSE pools over all of time; stream the original FullSubNet (fullsubnet_plus_amd.FullSubNet) with a "
@@ -117,8 +117,7 @@ class _Session:
             setattr(self, "_" + name, getattr(lib, f"{self._prefix}_{name}"))
         create = f"{self._prefix}_create_live" if live else f"{self._prefix}_create"
         sp = ctypes.c_void_p()
-        with torch.cuda.device(device):
-            _lib.check(getattr(lib, create)(model._hip.handle, self.slots, int(limit), *self._create_extra(), ctypes.byref(sp)), create)
+        _call.call(getattr(lib, create), device, model._hip.handle, self.slots, int(limit), *self._create_extra(), ctypes.byref(sp), stream=False)
         self._st, self._backup = sp, None
         self.state_bytes = int(self._state_bytes(sp))
 
@@ -135,15 +134,11 @@ class _Session:
             raise RuntimeError(f"the model's HIP handle was re-created (device change or copy) since {self._opener}: open a new stream")
         return self._st
 
-    def _cuda_stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def close(self):
         st, self._st = self._st, None
         h = self.model._hip.handle
         if st is not None and h is not None and h.value == self._owner:      # (a destroyed handle took nothing of the session with it)
-            with torch.cuda.device(self.device):
-                self._destroy(st)
+            _call.enqueue(self._destroy, self.device, st, stream=False)
 
     def __del__(self):
         try:
@@ -157,17 +152,16 @@ class _Session:
     def __exit__(self, *exc):
         self.close()
 
-    def _guarded(self, enqueue, out, what):
-        """enqueue() -> rc enqueues one library call that fills `out`.  Under error_check="sync" a call that the weight watch flags ran on
-        the OLD weights and has advanced the states: they are put back to what it started from before it runs again."""
-        model = self.model
-        if model.error_check != "sync":      # a live push is host time: "deferred" is this one call, with nothing built around it
-            _policy.enqueue_retrying_stale(enqueue, model._stale_weights_noticed, what)
-            return out
+    def _guarded(self, fn, out, *args):
+        """fn(*args, hip_stream) -> rc enqueues one library call that fills `out`.  Under error_check="sync" a call that the weight watch
+        flags ran on the OLD weights and has advanced the states: they are put back to what it started from before it runs again."""
+        model, device, what = self.model, self.device, fn.__name__
 
         def run():
-            _policy.enqueue_retrying_stale(enqueue, model._stale_weights_noticed, what)
+            _policy.enqueue_retrying_stale(lambda: _call.enqueue(fn, device, *args), model._stale_weights_noticed, what)
             return out
+        if model.error_check != "sync":      # a live push is host time: "deferred" is this one call, with nothing built around it
+            return run()
         # only watched parameters can be flagged (an unwatched model registers none with fsnp_watch_weights), so a session without
         # save / restore never sees the code that would run its push twice
         watched = model.__dict__.get("_fsnp_watched", False)
@@ -182,19 +176,16 @@ class _Session:
         if self._backup is None:
             self._backup = torch.empty((self.slots, self.state_bytes), dtype=torch.uint8, device=self.device)
         for b in range(self.slots):
-            with torch.cuda.device(self.device):
-                _lib.check(self._get_state(self._st, b, self._backup[b].data_ptr(), self._cuda_stream()), f"{self._prefix}_get_state")
+            _call.call(self._get_state, self.device, self._st, b, self._backup[b].data_ptr())
 
     def _restore_states(self):
         for b in range(self.slots):
-            with torch.cuda.device(self.device):
-                _lib.check(self._set_state(self._st, b, self._backup[b].data_ptr(), self._cuda_stream()), f"{self._prefix}_set_state")
+            _call.call(self._set_state, self.device, self._st, b, self._backup[b].data_ptr())
 
     def _counter(self, name, slot):
         st = self._session()
         v = ctypes.c_int64()
-        with torch.cuda.device(self.device):
-            _lib.check(getattr(self._lib, f"{self._prefix}_{name}")(st, int(slot), ctypes.byref(v)), f"{self._prefix}_{name}")
+        _call.call(getattr(self._lib, f"{self._prefix}_{name}"), self.device, st, int(slot), ctypes.byref(v), stream=False)
         return int(v.value)
 
     # ------------------------------------------------------------------ the slots' state
@@ -202,16 +193,14 @@ class _Session:
         """Stream-ordered zeroing of the state of `slots` (None: all): the next push starts a fresh clip there."""
         st = self._session()
         arr, num = _slot_array(slots)
-        with torch.cuda.device(self.device):
-            _lib.check(self._reset(st, arr, num, self._cuda_stream()), f"{self._prefix}_reset")
+        _call.call(self._reset, self.device, st, arr, num)
 
     def state(self, slot):
         """-> torch.uint8 CUDA tensor [state_bytes]: the slot's whole state (kernel-independent layout: the session's header, include/fsnp_stream.h,
         include/fsnp_wave_stream.h or include/fsnp_spec_stream.h)."""
         st = self._session()
         buf = torch.empty(self.state_bytes, dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self._get_state(st, int(slot), buf.data_ptr(), self._cuda_stream()), f"{self._prefix}_get_state")
+        _call.call(self._get_state, self.device, st, int(slot), buf.data_ptr())
         return buf
 
     def load_state(self, slot, tensor):
@@ -220,8 +209,7 @@ class _Session:
         if tensor.dtype != torch.uint8 or tensor.numel() != self.state_bytes:
             raise ValueError(f"load_state: expected a torch.uint8 tensor of {self.state_bytes} bytes, got {tensor.dtype} x {tensor.numel()}")
         t = tensor.to(self.device).contiguous()
-        with torch.cuda.device(self.device):
-            _lib.check(self._set_state(st, int(slot), t.data_ptr(), self._cuda_stream()), f"{self._prefix}_set_state")
+        _call.call(self._set_state, self.device, st, int(slot), t.data_ptr())
 
 
 class _FrameSession(_Session):
@@ -265,20 +253,14 @@ class Stream(_FrameSession):
         S, _, F, n = noisy_mag.shape
         assert S == self.slots, f"expected {self.slots} slots, got {S}"
         assert F == self.num_freqs, f"expected {self.num_freqs} frequency bins, got {F}"
-        if not noisy_mag.is_cuda:
-            raise RuntimeError("fullsubnet_plus_amd runs on MI355X (HIP) only; move the model and inputs to 'cuda'. "
-                               "There is deliberately no CPU fallback.")
+        require_cuda(noisy_mag)
         assert noisy_mag.device == self.device
         x = noisy_mag if noisy_mag.dtype == torch.float32 else noisy_mag.float()
         cnt = None if counts is None else _host_lengths(counts, S, "Stream.push")
         sb, _, sf, stt = x.stride()
         strides = (ctypes.c_int64 * 3)(sb, sf, stt)
         out = torch.empty((S, 2, F, n), dtype=torch.float32, device=self.device)
-
-        def enqueue():
-            with torch.cuda.device(self.device):
-                return self._lib.fsnp_stream_push(st, x.data_ptr(), ctypes.byref(strides), cnt, out.data_ptr(), n, self._cuda_stream())
-        return self._guarded(enqueue, out, "fsnp_stream_push")
+        return self._guarded(self._lib.fsnp_stream_push, out, st, x.data_ptr(), ctypes.byref(strides), cnt, out.data_ptr(), n)
 
     def tail(self, slots=None):
         """Push look_ahead all-zero frames (the reference's own pad) into `slots` (None: all): the masks of the last look_ahead frames.
@@ -304,16 +286,6 @@ class WaveStream(_Session):
         self.max_samples = int(max_samples)
         self.delay, self.live = int(getattr(self._lib, f"{self._prefix}_delay")(self._st)), bool(live)
 
-    @staticmethod
-    def _out_format(out_format, default, where):
-        """-> the _lib.SAMPLE_* value of a session call's out_format (None: `default`); a stream has no peak."""
-        if out_format is None:
-            out_format = default
-        if out_format not in ("f32", "s16"):
-            raise ValueError(f"WaveStream.{where}: out_format {out_format!r} is none of None, 'f32', 's16'"
-                             + (" (a stream has no peak: 's16_peak' is a format of enhance_wave only)" if out_format == "s16_peak" else ""))
-        return _lib.SAMPLE_FORMATS[out_format]
-
     def push(self, wav, counts=None, out_format=None):
         """wav [slots, n] CUDA tensor, n <= max_samples; counts: None (n samples for every slot) or samples per
         slot (a Python sequence or a CPU integer tensor, 0 <= counts[b] <= n; input past counts[b] is never read) -> [slots, n]: column
@@ -324,58 +296,33 @@ class WaveStream(_Session):
         the [slots, n] view of a channel-interleaved socket buffer is read in place.  out_format: None (follow the input: float -> fp32,
         int16 -> "s16"), "f32" or "s16" (int16, round half to even, saturating).  The session's state is fp32 whatever the formats, so
         PCM and fp32 pushes mix freely."""
-        ofmt = self._out_format(out_format, "s16" if wav.dtype == torch.int16 else "f32", "push")
+        ofmt, out_dtype = output_format(out_format, wav.dtype, "WaveStream.push", peak=False)
         st = self._session()
         assert wav.dim() == 2, "WaveStream.push takes [slots, n] samples"
         S, n = wav.shape
         assert S == self.slots, f"expected {self.slots} slots, got {S}"
-        if not wav.is_cuda:
-            raise RuntimeError("fullsubnet_plus_amd runs on MI355X (HIP) only; move the model and inputs to 'cuda'. "
-                               "There is deliberately no CPU fallback.")
+        require_cuda(wav)
         assert wav.device == self.device
-        x = wav if wav.dtype in (torch.float32, torch.int16) else wav.float()
-        if n > 1 and x.stride(1) < 1:
-            x = x.contiguous()
+        x, ifmt, row, step = pcm_input(wav)
         cnt = None if counts is None else _host_lengths(counts, S, "WaveStream.push")
-        if self._f32_calls and x.dtype == torch.float32 and ofmt == _lib.SAMPLE_F32 and (n == 1 or x.stride(1) == 1):
-            out = torch.empty((S, n), dtype=torch.float32, device=self.device)
-
-            def enqueue():
-                with torch.cuda.device(self.device):
-                    return self._lib.fsnp_wave_stream_push(st, x.data_ptr(), x.stride(0), cnt, out.data_ptr(), n, n, self._cuda_stream())
-            return self._guarded(enqueue, out, "fsnp_wave_stream_push")
-        ifmt = _lib.SAMPLE_S16 if x.dtype == torch.int16 else _lib.SAMPLE_F32
-        out = torch.empty((S, n), dtype=torch.float32 if ofmt == _lib.SAMPLE_F32 else torch.int16, device=self.device)
-        push_pcm = getattr(self._lib, f"{self._prefix}_push_pcm")
-
-        def enqueue_pcm():
-            with torch.cuda.device(self.device):
-                return push_pcm(st, x.data_ptr(), ifmt, x.stride(0), max(x.stride(1), 1), cnt, out.data_ptr(), ofmt, n, 1, n,
-                                self._cuda_stream())
-        return self._guarded(enqueue_pcm, out, f"{self._prefix}_push_pcm")
+        out = torch.empty((S, n), dtype=out_dtype, device=self.device)
+        if self._f32_calls and ifmt == ofmt == _lib.SAMPLE_F32 and (n == 1 or step == 1):
+            return self._guarded(self._lib.fsnp_wave_stream_push, out, st, x.data_ptr(), row, cnt, out.data_ptr(), n, n)
+        return self._guarded(getattr(self._lib, f"{self._prefix}_push_pcm"), out, st, x.data_ptr(), ifmt, row, step, cnt, out.data_ptr(), ofmt,
+                             n, 1, n)
 
     def finish(self, slots=None, out_format=None):
         """End the clips of `slots` (None: all) -> [slots, delay]: each clip's last `delay` samples (exactly 0 where the clip is shorter);
         rows of slots not listed, and of slots that hold no samples, are exactly 0.  The finished slots are reset: their next push starts
         a fresh clip.  A slot that holds 1 .. n_fft / 2 samples is refused, as enhance_wave refuses such a clip.  out_format: None or
         "f32" (fp32), or "s16" (int16, as push)."""
-        ofmt = self._out_format(out_format, "f32", "finish")
+        ofmt, out_dtype = output_format(out_format, torch.float32, "WaveStream.finish", peak=False)
         st = self._session()
         arr, num = _slot_array(slots)
+        out = torch.empty((self.slots, self.delay), dtype=out_dtype, device=self.device)
         if self._f32_calls and ofmt == _lib.SAMPLE_F32:
-            out = torch.empty((self.slots, self.delay), dtype=torch.float32, device=self.device)
-
-            def enqueue():
-                with torch.cuda.device(self.device):
-                    return self._lib.fsnp_wave_stream_finish(st, arr, num, out.data_ptr(), self.delay, self._cuda_stream())
-            return self._guarded(enqueue, out, "fsnp_wave_stream_finish")
-        out = torch.empty((self.slots, self.delay), dtype=torch.float32 if ofmt == _lib.SAMPLE_F32 else torch.int16, device=self.device)
-        finish_pcm = getattr(self._lib, f"{self._prefix}_finish_pcm")
-
-        def enqueue_pcm():
-            with torch.cuda.device(self.device):
-                return finish_pcm(st, arr, num, out.data_ptr(), ofmt, self.delay, 1, self._cuda_stream())
-        return self._guarded(enqueue_pcm, out, f"{self._prefix}_finish_pcm")
+            return self._guarded(self._lib.fsnp_wave_stream_finish, out, st, arr, num, out.data_ptr(), self.delay)
+        return self._guarded(getattr(self._lib, f"{self._prefix}_finish_pcm"), out, st, arr, num, out.data_ptr(), ofmt, self.delay, 1)
 
     def samples(self, slot):
         """Samples pushed into `slot` since its last reset or finish (host-side count)."""
@@ -429,9 +376,7 @@ class SpecStream(_FrameSession):
         S, F, n = noisy_complex.shape
         assert S == self.slots, f"expected {self.slots} slots, got {S}"
         assert F == self.num_freqs, f"expected {self.num_freqs} frequency bins, got {F}"
-        if not noisy_complex.is_cuda:
-            raise RuntimeError("fullsubnet_plus_amd runs on MI355X (HIP) only; move the model and inputs to 'cuda'. "
-                               "There is deliberately no CPU fallback.")
+        require_cuda(noisy_complex)
         assert noisy_complex.device == self.device
         x = noisy_complex if noisy_complex.dtype == torch.complex64 else noisy_complex.to(torch.complex64)
         x = x.resolve_conj()
@@ -443,12 +388,8 @@ class SpecStream(_FrameSession):
                 f"out must be a [{S}, {F}, {n}] complex64 tensor on {self.device}"
         strides = (ctypes.c_int64 * 3)(*x.stride())
         out_strides = (ctypes.c_int64 * 3)(*out.stride())
-
-        def enqueue():
-            with torch.cuda.device(self.device):
-                return self._lib.fsnp_spec_stream_push(st, x.data_ptr(), ctypes.byref(strides), cnt, out.data_ptr(),
-                                                       ctypes.byref(out_strides), n, self._cuda_stream())
-        return self._guarded(enqueue, out, "fsnp_spec_stream_push")
+        return self._guarded(self._lib.fsnp_spec_stream_push, out, st, x.data_ptr(), ctypes.byref(strides), cnt, out.data_ptr(),
+                             ctypes.byref(out_strides), n)
 
     def tail(self, slots=None):
         """Push look_ahead all-zero frames (the reference's own pad) into `slots` (None: all): the last look_ahead enhanced frames.
