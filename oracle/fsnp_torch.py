@@ -62,8 +62,8 @@ NORMS = {
 }
 
 
-def tsse(x, p, prefix):
-    """attention_model.py:78-98"""
+def tsse_gate(x, p, prefix):
+    """attention_model.py:78-97: the gate [B, C] of the TSSE layer."""
     C = x.shape[1]
     feats = []
     for nm in ("smallConv1d", "middleConv1d", "largeConv1d"):
@@ -73,30 +73,37 @@ def tsse(x, p, prefix):
     squeeze = Fn.linear(feature, p[f"{prefix}.feature_concate_fc.weight"],
                         p[f"{prefix}.feature_concate_fc.bias"])[..., 0]
     h = torch.relu(Fn.linear(squeeze, p[f"{prefix}.fc1.weight"], p[f"{prefix}.fc1.bias"]))
-    gate = torch.sigmoid(Fn.linear(h, p[f"{prefix}.fc2.weight"], p[f"{prefix}.fc2.bias"]))
-    return x * gate.unsqueeze(2)
+    return torch.sigmoid(Fn.linear(h, p[f"{prefix}.fc2.weight"], p[f"{prefix}.fc2.bias"]))
 
 
-def attention(x, p, prefix, kind="TSSE"):
-    """channel attention selected by `channel_attention_model` (fullsubnet_plus.py:51-70):
-    SE attention_model.py:6-40, ECA :335-359, CBAM :296-332, TSSE :43-98."""
+def tsse(x, p, prefix):
+    """attention_model.py:78-98"""
+    return x * tsse_gate(x, p, prefix).unsqueeze(2)
+
+
+def attention_gate(x, p, prefix, kind="TSSE"):
+    """The per-channel gate [B, C] of the channel attention selected by `channel_attention_model` (fullsubnet_plus.py:51-70):
+    SE attention_model.py:6-40, ECA :335-359, CBAM :296-332, TSSE :43-98.  x [B, C, T]."""
     if kind == "TSSE":
-        return tsse(x, p, prefix)
+        return tsse_gate(x, p, prefix)
     if kind == "SE":
         sq = x.mean(dim=2)
         h = torch.relu(Fn.linear(sq, p[f"{prefix}.fc1.weight"], p[f"{prefix}.fc1.bias"]))
-        gate = torch.sigmoid(Fn.linear(h, p[f"{prefix}.fc2.weight"], p[f"{prefix}.fc2.bias"]))
-        return x * gate.unsqueeze(2)
+        return torch.sigmoid(Fn.linear(h, p[f"{prefix}.fc2.weight"], p[f"{prefix}.fc2.bias"]))
     if kind == "CBAM":
         h = torch.relu(Fn.linear(x.mean(dim=2), p[f"{prefix}.fc1.weight"], p[f"{prefix}.fc1.bias"])) + \
             torch.relu(Fn.linear(x.max(dim=2)[0], p[f"{prefix}.fc1.weight"], p[f"{prefix}.fc1.bias"]))
-        gate = torch.sigmoid(Fn.linear(h, p[f"{prefix}.fc2.weight"], p[f"{prefix}.fc2.bias"]))
-        return x * gate.unsqueeze(2)
+        return torch.sigmoid(Fn.linear(h, p[f"{prefix}.fc2.weight"], p[f"{prefix}.fc2.bias"]))
     if kind == "ECA":
         y = x.mean(dim=2, keepdim=True)                                   # AdaptiveAvgPool1d(1): [B,C,1]
         y = Fn.conv1d(y.transpose(-1, -2), p[f"{prefix}.conv.weight"], padding=1).transpose(-1, -2)
-        return x * torch.sigmoid(y)
+        return torch.sigmoid(y)[..., 0]
     raise NotImplementedError(kind)
+
+
+def attention(x, p, prefix, kind="TSSE"):
+    """x times its gate (attention_gate), broadcast over time."""
+    return x * attention_gate(x, p, prefix, kind).unsqueeze(2)
 
 
 def decompress_cirm(mask, K=10.0, limit=9.9):
