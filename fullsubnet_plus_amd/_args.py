@@ -45,6 +45,37 @@ def resample_length(n, from_rate, to_rate):
     return -(-n * up // down)
 
 
+def window_plan_args(window, overlap, max_batch, num_freqs, what):
+    """The host-checkable arguments of a windowed call (include/ext/fsnp_windowed.h) -> (window, overlap, max_batch) as ints; ValueError
+    for a window or overlap that is no integer, an overlap outside [n_fft / 2, window / 2] (n_fft = 2 (num_freqs - 1)) and
+    max_batch < 1.  Touches neither the library nor a GPU."""
+    vals = []
+    for name, v in (("window", window), ("overlap", overlap), ("max_batch", max_batch)):
+        try:
+            if isinstance(v, bool):
+                raise TypeError
+            vals.append(operator.index(v))
+        except TypeError:
+            raise ValueError(f"{what}: {name} must be an integer, got {v!r}") from None
+    w, v, mb = vals
+    half = num_freqs - 1
+    if not (half <= v and 2 * v <= w and w < 2 ** 30):
+        raise ValueError(f"{what}: overlap {v} outside [n_fft / 2, window / 2] = [{half}, {w // 2}] (window {w}, n_fft = {2 * half})")
+    if not 1 <= mb < 2 ** 31:
+        raise ValueError(f"{what}: max_batch {mb} < 1")
+    return w, v, mb
+
+
+def window_count(samples, window, overlap):
+    """Windows that a clip of `samples` samples is cut into at `window` and `overlap` (include/ext/fsnp_windowed.h): 1 if
+    samples <= window, else ceil((samples - overlap) / (window - overlap)).  Python integers, no library, no GPU; ValueError unless
+    window >= 2, 1 <= overlap <= window / 2 and samples >= 1."""
+    n, w, v = operator.index(samples), operator.index(window), operator.index(overlap)
+    if w < 2 or v < 1 or 2 * v > w or n < 1:
+        raise ValueError(f"window_count: samples = {n}, window = {w}, overlap = {v}: need window >= 2, 1 <= overlap <= window / 2, samples >= 1")
+    return 1 if n <= w else -(-(n - v) // (w - v))
+
+
 def _host_lengths(lengths, batch, what):
     """Per-utterance lengths (a Python sequence or a CPU integer tensor) -> ctypes int32[batch].  They are read on the host and
     reach the device as kernel arguments: a CUDA tensor is refused, because reading it would synchronise."""

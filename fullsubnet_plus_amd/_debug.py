@@ -50,6 +50,14 @@ class _DebugHooks:
         """Test hook: drift injection for the column-split recurrent kernels (fsnp_debug_set_chaos); 0 = off."""
         self._setting("fsnp_debug_set_chaos", int(seed), device=device)
 
+    def debug_window_roundtrip(self, wav, window, overlap, lengths=None, out_format=None, clipped=None, max_batch=32):
+        """Test hook (fsnp_debug_window_roundtrip, include/ext/fsnp_windowed.h): enhance_wave_windowed with the model replaced by a copy
+        of every window, so that only the plan and its two kernels run: the result equals wav bit for bit, 0 past the lengths."""
+        enqueue, out = self._windowed_call("fsnp_debug_window_roundtrip", "debug_window_roundtrip", wav, window, overlap, lengths, out_format,
+                                           clipped, max_batch)
+        _lib.check(enqueue(), "fsnp_debug_window_roundtrip")
+        return out
+
     def debug_inject_error(self):
         """Test hook: pretend an inter-workgroup wait timed out (see fsnp_debug_inject_error)."""
         _call.check(_lib.load().fsnp_debug_inject_error, self._handle)

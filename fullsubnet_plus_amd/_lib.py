@@ -268,6 +268,8 @@ def load(build_if_missing=True):
     if lib.fsnp_abi_version() != ABI_VERSION or lib.fsnp_config_size() != ctypes.sizeof(FsnpConfig):
         raise RuntimeError(f"{path}: ABI mismatch (library: version {lib.fsnp_abi_version()}, fsnp_config {lib.fsnp_config_size()} "
                            f"bytes; binding: version {ABI_VERSION}, {ctypes.sizeof(FsnpConfig)} bytes) - rebuild the library")
+    from . import _lib_ext                    # the extension headers' registry (include/ext/*.h), typed on the same CDLL
+    _lib_ext.bind(lib)
     _lib = lib
     return lib
 

@@ -727,6 +727,8 @@ void fsnp_destroy(fsnp_handle* h) {
     if (h->ws) (void)hipFreeAsync(h->ws, nullptr);        // (allocated from the stream-ordered pool; the device is idle here)
     if (h->io) (void)hipFreeAsync(h->io, nullptr);
     for (auto& r : h->resample) if (r.dev) (void)hipFreeAsync(r.dev, nullptr);      // (include/fsnp_resample.h: the pairs' tap tables)
+    if (h->win_stage) (void)hipFreeAsync(h->win_stage, nullptr);                    // (include/ext/fsnp_windowed.h)
+    for (auto& f : h->win_fades) if (f.dev) (void)hipFreeAsync(f.dev, nullptr);
     (void)hipDeviceSynchronize();
     if (h->ev_done) (void)hipEventDestroy(h->ev_done);
     if (h->d_stft) (void)hipFree(h->d_stft);

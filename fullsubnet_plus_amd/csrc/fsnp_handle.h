@@ -1,7 +1,7 @@
 // fsnp_handle.h - the handle behind the C ABI (include/fsnp.h) and the helpers its translation units share:
 // fsnp_abi.hip (create / forward orchestration / workspace / calibration), forward_kernels.hip (the forward's small kernels),
 // fsnp_verify.hip (exchange verification), fsnp_debug_abi.hip (include/fsnp_debug.h: test and tuning hooks), fsnp_weights.hip
-// (strict weight loading + packing), fsnp_stft_abi.hip (STFT / iSTFT / waveform entry points), fsnp_stream_abi.hip,
+// (strict weight loading + packing), fsnp_stft_abi.hip (STFT / iSTFT / waveform entry points), fsnp_windowed_abi.hip, fsnp_stream_abi.hip,
 // fsnp_wave_stream_abi.hip, fsnp_spec_stream_abi.hip and fsnp_wave_rate_stream_abi.hip (stream, wave, spectrum and rate sessions, and the
 // slot helpers they share).  Host only.
 #pragma once
@@ -12,6 +12,7 @@
 #include "fsnp_common.h"
 #include "planner.h"
 #include "resample.h"
+#include "windowed.h"
 
 namespace fsnp {
 
@@ -151,6 +152,12 @@ struct fsnp_handle {
     size_t io_bytes = 0;
     // include/fsnp_resample.h: the tap tables of the (up, down) pairs this handle has run, at most kResampleMaxPairs, never evicted
     std::vector<fsnp::ResampleCached> resample;
+    // include/ext/fsnp_windowed.h: the windows' enhanced fp32 rows [windows][window] (behind them the first pass of FSNP_SAMPLE_S16_PEAK),
+    // grown stream-ordered like io, and the cross-fade tables of the overlaps this handle has run, at most kWindowMaxFades, never
+    // evicted (like `resample`)
+    unsigned char* win_stage = nullptr;
+    size_t win_stage_bytes = 0;
+    std::vector<fsnp::WindowFade> win_fades;
 
     bool timing = false;
     std::vector<TimingRec> timing_recs;   // recorded, not yet read back (drained by fsnp_get_timing, or when 256 pile up)
@@ -270,6 +277,10 @@ struct WaveIo {
     size_t xp, noisy, enh, mask, fr, stage, total;
 };
 WaveIo wave_io(const StftPlan& p, int batch, int max_samples, int stage_samples = 0);
+// The model between the two sample kernels of a waveform call, on the io area laid out by `io` (grown by the caller): the padded rows
+// at io.xp, already written on the stream -> forward DFT, forward (frames: NULL, or each row's HOST frame count as check_lengths
+// accepted it), flush in pipelined mode, cIRM, inverse DFT -> the frames [batch][io.T][n_fft] at io.fr, ready for launch_istft_ola
+int enhance_padded(fsnp_handle* h, const StftPlan& p, const WaveIo& io, int batch, const int32_t* frames, void* hip_stream);
 // fsnp_resample_abi.hip (include/fsnp_resample.h): 0, or 2 with the error set when the `count` pairs would take the handle past
 // kResampleMaxPairs tables (nothing is enqueued); the device table of a pair on s, built and uploaded on first use (taps = nullptr for
 // equal rates) - between order_after_last_forward and mark_forward_done, which order other streams behind the upload

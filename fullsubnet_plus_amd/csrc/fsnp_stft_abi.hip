@@ -91,12 +91,10 @@ struct WaveRate {
 };
 // wav [B][L] -> spectrum rows [B][T][ldc] (interleaved complex), T = 1 + L / hop; samples: NULL, or each row's own HOST sample count
 // (reflect padding at each clip's own end; frames past 1 + samples[b] / hop see zeros behind it)
-// (rate: the padded signal is the clip converted by `tin` in the pad kernel's loads, L and samples its model-rate counts)
 static void stft_into(fsnp_handle* h, const StftPlan& p, const PcmIn& wav, float* xp, long xs, float* spec, int ldc, int B, int L,
-                      const int* samples, hipStream_t s, const WaveRate* rate = nullptr, const ResampleTable* tin = nullptr) {
+                      const int* samples, hipStream_t s) {
     const int T = 1 + L / p.hop;
-    if (rate) launch_stft_pad_resample(wav, xp, xs, B, nullptr, rate->n, p.n_fft, *tin, s);
-    else launch_stft_pad(wav, xp, xs, B, L, samples, p.n_fft, s);
+    launch_stft_pad(wav, xp, xs, B, L, samples, p.n_fft, s);
     launch_linear_act(xp, p.hop, h->d_stft + p.o_fwd, p.fwd_ld, h->d_stft + p.o_zero, spec, ldc, p.n_fft, p.N2, B, T,
                       FSNP_ACT_NONE, h->num_cus, s, xs, p.n_fft);
 }
@@ -118,6 +116,34 @@ int check_sample_format(const char* where, const char* what, int32_t format, int
         return 2;
     }
     if (step < 1) { set_error("%s: %s step %lld < 1 (elements between consecutive samples of a row)", where, what, (long long)step); return 2; }
+    return 0;
+}
+
+// The model between the two sample kernels of a waveform call: the padded rows xp [batch][io.xs] of h->io (already written on the
+// stream) -> the inverse DFT's frames [batch][io.T][n_fft] at io.fr.  frames: NULL (every row has io.T frames), or each row's own HOST
+// frame count, already accepted by check_lengths.  Shared by enhance_wave_any and the windowed call (fsnp_windowed_abi.hip).
+int enhance_padded(fsnp_handle* h, const StftPlan& p, const WaveIo& io, int batch, const int32_t* frames, void* hip_stream) {
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    const int T = io.T;
+    float* xp = reinterpret_cast<float*>(h->io + io.xp);
+    float* noisy = reinterpret_cast<float*>(h->io + io.noisy);
+    float* enh = reinterpret_cast<float*>(h->io + io.enh);
+    float* mask = reinterpret_cast<float*>(h->io + io.mask);
+    float* fr = reinterpret_cast<float*>(h->io + io.fr);
+    launch_linear_act(xp, p.hop, h->d_stft + p.o_fwd, p.fwd_ld, h->d_stft + p.o_zero, noisy, p.sp, p.n_fft, p.N2, batch, T,
+                      FSNP_ACT_NONE, h->num_cus, s, io.xs, p.n_fft);
+    const int64_t cst[3] = {(int64_t)T * (p.sp / 2), 1, p.sp / 2};       // complex-element strides of [B][T][sp/2] as (b, f, t)
+    const int rc = frames ? fsnp_forward_complex_lengths(h, noisy, cst, frames, mask, batch, T, hip_stream)
+                          : fsnp_forward_complex(h, noisy, cst, mask, batch, T, FSNP_MODE_FULL, 0, batch, hip_stream);
+    if (rc) return rc;
+    // pipelined mode: the forward left chunks of the sub-band plan on the side stream (at B = 1 the whole plan); `mask` is read
+    // right here and lives in the single-buffered io area, so `s` waits for them now (fsnp_flush) - nothing of this call is deferred
+    if (h->pipeline && fsnp_flush(h, hip_stream)) return 4;
+    // the pad column of every row of `enh` is never written by apply_cirm and multiplies zero weights: clear it once
+    FSNP_HIP_CHECK(hipMemsetAsync(enh, 0, io.mask - io.enh, s));
+    launch_apply_cirm(mask, noisy, cst, enh, cst, batch, p.F, T, frames, s);      // frames >= T_b: 0
+    launch_linear_act(enh, p.sp, h->d_stft + p.o_inv, p.inv_ld, h->d_stft + p.o_zero, fr, p.n_fft, p.N2, p.n_fft, batch, T,
+                      FSNP_ACT_NONE, h->num_cus, s, (long)T * p.sp, p.N2);
     return 0;
 }
 
@@ -183,24 +209,12 @@ int enhance_wave_any(fsnp_handle* h, const char* where, const PcmIn& wav, const 
     }
     float* xp = reinterpret_cast<float*>(h->io + io.xp);
     float* noisy = reinterpret_cast<float*>(h->io + io.noisy);
-    float* enh = reinterpret_cast<float*>(h->io + io.enh);
-    float* mask = reinterpret_cast<float*>(h->io + io.mask);
     float* fr = reinterpret_cast<float*>(h->io + io.fr);
     // inferencer.py:142-158: stft -> (mag, real, imag) -> model -> decompress_cIRM, complex multiply -> istft(length); with lengths
     // the reflect padding at each clip's end (frames past T_b see zeros: the forward never reads them)
-    stft_into(h, p, wav, xp, xs, noisy, p.sp, batch, max_samples, samples, s, rate, &tin);
-    const int64_t cst[3] = {(int64_t)T * (p.sp / 2), 1, p.sp / 2};       // complex-element strides of [B][T][sp/2] as (b, f, t)
-    const int rc = samples ? fsnp_forward_complex_lengths(h, noisy, cst, frames.data(), mask, batch, T, hip_stream)
-                           : fsnp_forward_complex(h, noisy, cst, mask, batch, T, FSNP_MODE_FULL, 0, batch, hip_stream);
-    if (rc) return rc;
-    // pipelined mode: the forward left chunks of the sub-band plan on the side stream (at B = 1 the whole plan); `mask` is read
-    // right here and lives in the single-buffered io area, so `s` waits for them now (fsnp_flush) - nothing of this call is deferred
-    if (h->pipeline && fsnp_flush(h, hip_stream)) return 4;
-    // the pad column of every row of `enh` is never written by apply_cirm and multiplies zero weights: clear it once
-    FSNP_HIP_CHECK(hipMemsetAsync(enh, 0, io.mask - io.enh, s));
-    launch_apply_cirm(mask, noisy, cst, enh, cst, batch, p.F, T, samples ? frames.data() : nullptr, s);      // frames >= T_b: 0
-    launch_linear_act(enh, p.sp, h->d_stft + p.o_inv, p.inv_ld, h->d_stft + p.o_zero, fr, p.n_fft, p.N2, p.n_fft, batch, T,
-                      FSNP_ACT_NONE, h->num_cus, s, (long)T * p.sp, p.N2);
+    if (rate) launch_stft_pad_resample(wav, xp, xs, batch, nullptr, rate->n, p.n_fft, tin, s);
+    else launch_stft_pad(wav, xp, xs, batch, max_samples, samples, p.n_fft, s);
+    if (const int rc = enhance_padded(h, p, io, batch, samples ? frames.data() : nullptr, hip_stream)) return rc;
     // the samples out, in the caller's format.  FSNP_SAMPLE_S16_PEAK needs the clip's peak before any sample can be written: the
     // overlap-add stages fp32 rows where the padded input was and folds |v| into per-row maxima where the noisy spectra were (both are
     // dead by now, so the area fsnp_reserve sized is enough), and a second kernel scales and truncates

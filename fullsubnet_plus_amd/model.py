@@ -22,7 +22,8 @@ import torch
 import torch.nn as nn
 
 from . import _call, _lib, _policy
-from ._args import _host_lengths, _rate, clipped_pointer, f32_rows, other_rate, output_format, pcm_input, reads_in_place, require_cuda, resample_plan
+from ._args import (_host_lengths, _rate, clipped_pointer, f32_rows, other_rate, output_format, pcm_input, reads_in_place, require_cuda,
+                    resample_plan, window_plan_args)
 from ._call import resolve_device as _resolve_device
 from ._debug import _DebugHooks
 
@@ -752,6 +753,48 @@ class _HipModel(_DebugHooks, nn.Module):
 
         def run():
             _policy.enqueue_retrying_stale(lambda: _call.enqueue(entry, wav.device, self._handle, *args), self._stale_weights_noticed, fn)
+            return out
+        return self._checked(run)
+
+    def _windowed_call(self, fn, what, noisy, window, overlap, lengths, out_format, clipped, max_batch):
+        """Arguments and output of fsnp_enhance_wave_windowed / fsnp_debug_window_roundtrip (include/ext/fsnp_windowed.h, one signature)
+        -> (run, out): run() enqueues the call once and returns its code, unchecked."""
+        assert noisy.dim() == 2, "expected [B, samples]"
+        window, overlap, max_batch = window_plan_args(window, overlap, max_batch, self.num_freqs, what)
+        ofmt, out_dtype = output_format(out_format, noisy.dtype, what)
+        require_cuda(noisy)
+        B, L = noisy.shape
+        samples = None if lengths is None else _host_lengths(lengths, B, what)
+        wav, ifmt, row, step = pcm_input(noisy)
+        clip = clipped_pointer(clipped, B, wav.device, what)
+        out = torch.empty((B, L), dtype=out_dtype, device=wav.device)
+        entry = getattr(self._ensure_handle(wav.device), fn)
+        args = (self._handle, wav.data_ptr(), ifmt, row, step, out.data_ptr(), ofmt, out.stride(0), 1, samples, B, L, window, overlap,
+                max_batch, clip)
+        return (lambda: _call.enqueue(entry, wav.device, *args)), out
+
+    def enhance_wave_windowed(self, noisy, window, overlap, lengths=None, out_format=None, clipped=None, max_batch=32):
+        """One long recording per row: enhance_wave in overlapping windows, cross-faded on the device (include/ext/fsnp_windowed.h,
+        DESIGN.md 8f).  noisy [B, samples] -> [B, samples].  window, overlap: samples at the model's rate, with
+        n_fft / 2 <= overlap <= window / 2; a clip of L samples is cut into window_count(L, window, overlap) windows that start
+        window - overlap samples apart (the last one as long as what is left, more than `overlap`).  Every window is enhanced as a clip
+        of its own - its own reflect padding, frames and norms - and where two windows overlap the result fades from the earlier to
+        the later one by 0.5 - 0.5 cos(pi j / overlap); at overlap = window / 2 that is the periodic-Hann weighting of the reference's
+        Inferencer.overlapped_chunk.  The result is NOT enhance_wave(noisy): there every statistic is taken over the whole recording.
+
+        The windows of all rows run through the model max_batch at a time, across rows.  Windows of one length run as an ordinary
+        batch (a call in which no row is longer than `window` and B <= max_batch is enhance_wave, bit for bit); a batch that mixes
+        lengths runs like enhance_wave(lengths=) and is refused where that is (subband_num > 1, the sub-band "TCN", a last window too
+        short for the TSSE kernels).  noisy, lengths, out_format and clipped follow enhance_wave's rules; there is no sample_rate=
+        (compose with resample, INTEGRATION.md "One long recording").  ValueError, before any GPU is touched, for a window or overlap
+        that is no integer, an overlap outside its range and max_batch < 1."""
+        assert self.output_size == 2, "the cIRM epilogue needs the two mask channels (decompress_cIRM, acoustics/mask.py:60-63)"
+        fn = "fsnp_enhance_wave_windowed"
+        enqueue, out = self._windowed_call(fn, f"{self.__class__.__name__}.enhance_wave_windowed", noisy, window, overlap, lengths,
+                                           out_format, clipped, max_batch)
+
+        def run():
+            _policy.enqueue_retrying_stale(enqueue, self._stale_weights_noticed, fn)
             return out
         return self._checked(run)
 
