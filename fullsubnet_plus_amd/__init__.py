@@ -9,7 +9,7 @@ Drop-in for the reference's plugin point (``[model].path`` in config/inference.t
 The arithmetic runs in hand-written HIP kernels behind the C ABI of ``libfsnp_hip.so``
 (include/fsnp.h); PyTorch is only the tensor container.  There is no CPU fallback.
 """
-from ._args import resample_length, window_count  # noqa: F401
+from ._args import resample_length, window_count, window_stream_plan  # noqa: F401
 from .model import FullSubNet, FullSubNet_Plus, Model  # noqa: F401
 
-__all__ = ["FullSubNet_Plus", "Model", "FullSubNet", "resample_length", "window_count"]
+__all__ = ["FullSubNet_Plus", "Model", "FullSubNet", "resample_length", "window_count", "window_stream_plan"]

@@ -76,6 +76,38 @@ def window_count(samples, window, overlap):
     return 1 if n <= w else -(-(n - v) // (w - v))
 
 
+def window_stream_plan(pushed, count, window, overlap):
+    """-> (first, num): a push of `count` samples on a window-session slot that held `pushed` completes windows first ... first + num - 1
+    (window k is complete at k (window - overlap) + window samples; include/session/fsnp_window_stream.h).  The library's own host
+    arithmetic (fsnp_window_stream_plan), no GPU; ValueError for what it answers with -1: window < 2, overlap outside
+    [1, window / 2], pushed < 0, count < 0."""
+    p, c, w, v = (operator.index(x) for x in (pushed, count, window, overlap))
+    first, num = ctypes.c_int64(), ctypes.c_int64()
+    fits = max(abs(p), abs(c)) < 2 ** 62 and max(abs(w), abs(v)) < 2 ** 31
+    if not fits or _lib.load().fsnp_window_stream_plan(p, c, w, v, ctypes.byref(first), ctypes.byref(num)) != 0:
+        raise ValueError(f"window_stream_plan: pushed = {p}, count = {c}, window = {w}, overlap = {v}: need window >= 2, "
+                         "1 <= overlap <= window / 2, pushed >= 0, count >= 0")
+    return int(first.value), int(num.value)
+
+
+def window_stream_args(slots, window, overlap, max_samples, max_batch, num_freqs, what):
+    """The host-checkable arguments of open_window_stream -> ints: window_plan_args' checks, and slots, max_samples >= 1."""
+    window, overlap, max_batch = window_plan_args(window, overlap, max_batch, num_freqs, what)
+    vals = []
+    for name, v in (("slots", slots), ("max_samples", max_samples)):
+        try:
+            if isinstance(v, bool):
+                raise TypeError
+            vals.append(operator.index(v))
+        except TypeError:
+            raise ValueError(f"{what}: {name} must be an integer, got {v!r}") from None
+        if vals[-1] < 1:
+            raise ValueError(f"{what}: {name} {vals[-1]} < 1")
+        if vals[-1] >= 2 ** 31:
+            raise ValueError(f"{what}: {name} {vals[-1]} is not an int32")
+    return vals[0], window, overlap, vals[1], max_batch
+
+
 def _host_lengths(lengths, batch, what):
     """Per-utterance lengths (a Python sequence or a CPU integer tensor) -> ctypes int32[batch].  They are read on the host and
     reach the device as kernel arguments: a CUDA tensor is refused, because reading it would synchronise."""

@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJDIR = os.path.join(CSRC, "build")
 LIB_PATH = os.path.join(HERE, "libfsnp_hip.so")
 SOURCES = ["fsnp_abi.hip", "forward_kernels.hip", "fsnp_verify.hip", "fsnp_debug_abi.hip", "fsnp_weights.hip", "weight_pack.hip", "fsnp_stft_abi.hip", "fsnp_stream_abi.hip", "fsnp_wave_stream_abi.hip", "fsnp_spec_stream_abi.hip", "planner.cpp", "frontend.hip", "tcn.hip", "subband.hip", "lstm.hip", "lstm16.hip", "lstm_gru.hip", "lstm_coop.hip",
-           "lstm_hp.hip", "lstm_hpw.hip", "lstm_generic.hip", "lstm_step.hip", "lstm_coopn.hip", "lstm_coopw.hip", "lstm_fbv.hip", "stft.hip", "stft_stream.hip", "pcm.hip", "resample.hip", "fsnp_resample_abi.hip", "resample_stream.hip", "fsnp_wave_rate_stream_abi.hip", "windowed.hip", "fsnp_windowed_abi.hip", "spec_stream.hip", "box_probe.hip", "stages.hip"]
+           "lstm_hp.hip", "lstm_hpw.hip", "lstm_generic.hip", "lstm_step.hip", "lstm_coopn.hip", "lstm_coopw.hip", "lstm_fbv.hip", "stft.hip", "stft_stream.hip", "pcm.hip", "resample.hip", "fsnp_resample_abi.hip", "resample_stream.hip", "fsnp_wave_rate_stream_abi.hip", "windowed.hip", "fsnp_windowed_abi.hip", "window_stream.hip", "fsnp_window_stream_abi.hip", "spec_stream.hip", "box_probe.hip", "stages.hip"]
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 # -fno-slp-vectorize: the SLP pass pairs the LSTM kernel's per-tile VALU FMAs across tiles, which breaks the
 # refill-in-place weight pipeline and makes hipcc drain vmcnt(0) + copy 48 registers every k-group

@@ -58,6 +58,18 @@ class _DebugHooks:
         _lib.check(enqueue(), "fsnp_debug_window_roundtrip")
         return out
 
+    def debug_open_window_stream_copy(self, slots, window, overlap, max_samples=4096, max_batch=32, device="cuda"):
+        """Test hook (fsnp_debug_window_stream_create_copy, include/session/fsnp_window_stream.h): open_window_stream with every
+        forward replaced by a copy of its windows, so that only the schedule and the session's kernels run: the session returns its
+        input `window` samples late, bit for bit.  Skips the model's minimum clip."""
+        from ._args import window_stream_args
+        from .stream import WindowStream
+
+        class _CopyWindowStream(WindowStream):
+            _copy = True
+        args = window_stream_args(slots, window, overlap, max_samples, max_batch, self.num_freqs, "debug_open_window_stream_copy")
+        return _CopyWindowStream(self, *args, _call.resolve_device(device))
+
     def debug_inject_error(self):
         """Test hook: pretend an inter-workgroup wait timed out (see fsnp_debug_inject_error)."""
         _call.check(_lib.load().fsnp_debug_inject_error, self._handle)

@@ -94,6 +94,16 @@ PlannerCtx pctx(const fsnp_handle* h) {
     return c;
 }
 
+// The one statement of the TSSE frame floor: a clip's frames + look_ahead must reach the attention's largest kernel (0: no such rule -
+// the original FullSubNet, or another attention).  check_lengths, the equal-length forward and min_clip_frames all ask here.
+static int tsse_largest_kernel(const fsnp_handle* h) {
+    if (h->model == FSNP_MODEL_FULLSUBNET || h->cfg.attention != FSNP_ATT_TSSE) return 0;
+    int kmax = 1;
+    for (int c = 0; c < 3; ++c) kmax = std::max(kmax, (int)h->cfg.kersize[c]);
+    return kmax;
+}
+int min_clip_frames(const fsnp_handle* h) { return std::max(1, tsse_largest_kernel(h) - (int)h->cfg.look_ahead); }
+
 int check_lengths(const fsnp_handle* h, const int32_t* lengths, int batch, int frames, const char* where) {
     if (!lengths) { set_error("%s: null lengths", where); return 1; }
     const bool fsn = h->model == FSNP_MODEL_FULLSUBNET;
@@ -101,15 +111,13 @@ int check_lengths(const fsnp_handle* h, const int32_t* lengths, int batch, int f
     // GroupNorm is per sub-band sequence, which would need a length per slot)
     if (!fsn && h->cfg.subband_num > 1) { set_error("%s: per-utterance lengths are not supported with subband_num = %d > 1", where, h->cfg.subband_num); return 2; }
     if (h->sb_tcn) { set_error("%s: per-utterance lengths are not supported with the sub-band sequence_model \"TCN\"", where); return 2; }
-    int kmax = 1;
-    for (int c = 0; c < 3; ++c) kmax = std::max(kmax, (int)h->cfg.kersize[c]);
-    const bool tsse = !fsn && h->cfg.attention == FSNP_ATT_TSSE;
+    const int kmax = tsse_largest_kernel(h);
     for (int b = 0; b < batch; ++b) {
         if (lengths[b] < 1 || lengths[b] > frames) {
             set_error("%s: utterance %d: length %d outside [1, %d]", where, b, (int)lengths[b], frames);
             return 2;
         }
-        if (tsse && lengths[b] + h->cfg.look_ahead < kmax) {
+        if (lengths[b] + h->cfg.look_ahead < kmax) {
             set_error("%s: utterance %d: too few frames: length %d + look_ahead %d = %d < largest TSSE kernel %d", where, b, (int)lengths[b],
                       (int)h->cfg.look_ahead, (int)lengths[b] + h->cfg.look_ahead, kmax);
             return 2;
@@ -779,9 +787,8 @@ static int check_forward_args(fsnp_handle* h, const float* mag, const float* rea
     if (batch_offset < 0 || global_batch < batch_offset + batch) { set_error("bad batch_offset/global_batch"); return 2; }
     d.B = batch; d.T = frames; d.LA = h->cfg.look_ahead; d.Tp = frames + d.LA; d.F = h->F; d.FP = h->FP;
     d.CH = h->CH; d.H = h->H; d.NSB = h->NSB; d.NIN = h->NIN;
-    int kmax = 1;
-    for (int c = 0; c < 3; ++c) kmax = kmax > h->cfg.kersize[c] ? kmax : h->cfg.kersize[c];
-    if (!fsn && h->cfg.attention == FSNP_ATT_TSSE && d.Tp < kmax) { set_error("too few frames: T + look_ahead = %d < largest TSSE kernel %d", d.Tp, kmax); return 2; }
+    const int kmax = tsse_largest_kernel(h);
+    if (d.Tp < kmax) { set_error("too few frames: T + look_ahead = %d < largest TSSE kernel %d", d.Tp, kmax); return 2; }
     if ((double)3 * d.B * d.Tp * d.FP * 2 > 2.0e9) { set_error("batch too large for 32-bit gather offsets; split the batch"); return 2; }
     if (lengths) {
         if (mode != FSNP_MODE_FULL) { set_error("fsnp_forward_lengths: per-utterance lengths need FULL mode"); return 2; }

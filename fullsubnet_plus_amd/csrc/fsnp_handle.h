@@ -3,7 +3,7 @@
 // fsnp_verify.hip (exchange verification), fsnp_debug_abi.hip (include/fsnp_debug.h: test and tuning hooks), fsnp_weights.hip
 // (strict weight loading + packing), fsnp_stft_abi.hip (STFT / iSTFT / waveform entry points), fsnp_windowed_abi.hip, fsnp_stream_abi.hip,
 // fsnp_wave_stream_abi.hip, fsnp_spec_stream_abi.hip and fsnp_wave_rate_stream_abi.hip (stream, wave, spectrum and rate sessions, and the
-// slot helpers they share).  Host only.
+// slot helpers they share), fsnp_window_stream_abi.hip (window sessions).  Host only.
 #pragma once
 #include <map>
 #include <string>
@@ -289,6 +289,13 @@ int resample_table(fsnp_handle* h, const ResamplePlan& p, hipStream_t s, Resampl
 // 0, or 2 with the error set: the format and step rules of include/fsnp_pcm.h for one sample buffer (`what`: "input" / "output";
 // peak_ok: FSNP_SAMPLE_S16_PEAK is a format this buffer may have)
 int check_sample_format(const char* where, const char* what, int32_t format, int64_t step, bool peak_ok);
+// fsnp_windowed_abi.hip: the handle's cross-fade table of overlap V, or NULL; and its device copy on s, built and uploaded on first use
+// (between order_after_last_forward and mark_forward_done, by a caller that has checked that the handle has room for it)
+const WindowFade* find_window_fade(const fsnp_handle* h, int V);
+int window_fade_device(fsnp_handle* h, int V, hipStream_t s, const float*& g);
+// fsnp_abi.hip: the fewest frames of a clip the model accepts (TSSE: its largest kernel - look_ahead; else 1) - what check_lengths and
+// the equal-length forward call "too few frames"
+int min_clip_frames(const fsnp_handle* h);
 // ---- stream, wave and spectrum sessions (fsnp_stream_abi.hip, fsnp_wave_stream_abi.hip, fsnp_spec_stream_abi.hip) ----
 // argument checks of their entry points: `where` names the entry point in every message; 0, or 2 with the error set
 inline int check_slot(const char* where, int slot, int S) {

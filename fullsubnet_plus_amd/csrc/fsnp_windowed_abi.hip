@@ -23,15 +23,18 @@ int ensure_window_stage(fsnp_handle* h, size_t bytes, hipStream_t s) {      // s
     return 0;
 }
 
-const WindowFade* find_fade(const fsnp_handle* h, int V) {
+}  // namespace
+
+// (shared with the window sessions, fsnp_window_stream_abi.hip: fsnp_handle.h)
+const WindowFade* find_window_fade(const fsnp_handle* h, int V) {
     for (const WindowFade& f : h->win_fades)
         if (f.overlap == V) return &f;
     return nullptr;
 }
 // the fade table of overlap V on s, built and uploaded on first use (the caller is between order_after_last_forward and
 // mark_forward_done, and has checked that the handle has room for it)
-int fade_table(fsnp_handle* h, int V, hipStream_t s, const float*& g) {
-    const WindowFade* f = find_fade(h, V);
+int window_fade_device(fsnp_handle* h, int V, hipStream_t s, const float*& g) {
+    const WindowFade* f = find_window_fade(h, V);
     if (!f) {
         h->win_fades.reserve(kWindowMaxFades);                     // (entries never move: uploads in flight read their host copies)
         h->win_fades.emplace_back();
@@ -53,6 +56,8 @@ int fade_table(fsnp_handle* h, int V, hipStream_t s, const float*& g) {
     return 0;
 }
 
+namespace {
+
 // Both entry points.  model = false (fsnp_debug_window_roundtrip): a forward copies every padded row's centre into its staging row.
 int windowed_any(fsnp_handle* h, const char* where, const PcmIn& wav, const PcmOut& out, const int32_t* samples, int32_t batch,
                  int32_t max_samples, int32_t W, int32_t V, int32_t max_batch, void* hip_stream, bool model) {
@@ -71,7 +76,7 @@ int windowed_any(fsnp_handle* h, const char* where, const PcmIn& wav, const PcmO
         return 2;
     }
     if (W > INT_MAX / 2) { set_error("%s: window %d does not fit", where, (int)W); return 2; }
-    if (!find_fade(h, V) && (int)h->win_fades.size() >= kWindowMaxFades) {
+    if (!find_window_fade(h, V) && (int)h->win_fades.size() >= kWindowMaxFades) {
         set_error("%s: this handle already keeps the cross-fade tables of %d overlaps, the most it holds (they are never evicted: launches "
                   "in flight may read them); overlap %d needs another handle", where, kWindowMaxFades, (int)V);
         return 2;
@@ -124,7 +129,7 @@ int windowed_any(fsnp_handle* h, const char* where, const PcmIn& wav, const PcmO
     if (ensure_io(h, model ? io_max.total : io_max.noisy, s)) return 4;
     if (ensure_window_stage(h, stage_rows + (out.fmt == kPcmPeak ? peak_rows + (size_t)batch * 4 : 0), s)) return 4;
     const float* g = nullptr;
-    if (const int rc = fade_table(h, V, s, g)) return rc;
+    if (const int rc = window_fade_device(h, V, s, g)) return rc;
     float* stage = reinterpret_cast<float*>(h->win_stage);
     for (const Forward& f : forwards) {
         const WaveIo io = wave_io(p, f.n, f.longest);

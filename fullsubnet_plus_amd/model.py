@@ -23,7 +23,7 @@ import torch.nn as nn
 
 from . import _call, _lib, _policy
 from ._args import (_host_lengths, _rate, clipped_pointer, f32_rows, other_rate, output_format, pcm_input, reads_in_place, require_cuda,
-                    resample_plan, window_plan_args)
+                    resample_plan, window_plan_args, window_stream_args)
 from ._call import resolve_device as _resolve_device
 from ._debug import _DebugHooks
 
@@ -797,6 +797,22 @@ class _HipModel(_DebugHooks, nn.Module):
             _policy.enqueue_retrying_stale(enqueue, self._stale_weights_noticed, fn)
             return out
         return self._checked(run)
+
+    def open_window_stream(self, slots, window, overlap, max_samples=4096, max_batch=32, device="cuda"):
+        """-> fullsubnet_plus_amd.stream.WindowStream: `slots` independent live audio streams enhanced in the windows of
+        enhance_wave_windowed (include/session/fsnp_window_stream.h) - for FullSubNet+, which has no other online form,
+        and for the original FullSubNet alike.  Blocks of up to max_samples samples in, as many out, `window` samples late; a
+        window runs through the model in the push that completes it, up to max_batch windows of all slots per forward.  All push
+        outputs of a clip followed by finish(), without the first `window` samples, are enhance_wave_windowed(clip, window, overlap)
+        of that clip alone for any block sizes, bit for bit at max_batch=1 on both sides.  There is no sample_rate= (compose with
+        resample).  ValueError, before any GPU is touched, for arguments that are no integers, an overlap outside
+        [n_fft / 2, window / 2] and slots, max_samples or max_batch < 1.  What a finish could otherwise refuse is refused here by the
+        library (FsnpError, code 2): an overlap so short that a clip's last window may fall below the model's minimum clip (TSSE: 8
+        frames, overlap >= 1791 at the default geometry), and subband_num > 1 or the sub-band "TCN" unless max_batch=1."""
+        from .stream import WindowStream
+        assert self.output_size == 2, "the cIRM epilogue needs the two mask channels (decompress_cIRM, acoustics/mask.py:60-63)"
+        args = window_stream_args(slots, window, overlap, max_samples, max_batch, self.num_freqs, f"{self.__class__.__name__}.open_window_stream")
+        return WindowStream(self, *args, _resolve_device(device))
 
     def resample(self, wav, from_rate, to_rate, lengths=None, out_format=None, clipped=None):
         """Sample-rate conversion on the device by the filter enhance_wave(..., sample_rate=) uses (include/fsnp_resample.h; one fixed

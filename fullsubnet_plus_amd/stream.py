@@ -24,7 +24,15 @@ and for a caller who owns the STFT (include/fsnp_spec_stream.h): noisy complex f
     ...
     enh = spec.tail()                        # look_ahead zero frames: the last look_ahead enhanced frames
 
-All three take live=True (include/fsnp_stream_live.h): the session mode for a few streams fed one hop at a time, on per-step kernels that
+and, for either model, live audio in the cross-faded windows of enhance_wave_windowed (include/session/fsnp_window_stream.h): the only
+online form FullSubNet+ has.
+
+    win = plus.open_window_stream(slots=8, window=32000, overlap=4000, max_samples=160)
+    out = win.push(block)                    # [8, n] -> [8, n]; column j = merged sample P + j - win.delay, win.delay = window
+    ...
+    out = win.finish()                       # [8, window]: the clips' last samples; the slots are reset
+
+The first three take live=True (include/fsnp_stream_live.h): the session mode for a few streams fed one hop at a time, on per-step kernels that
 fill the chip at one slot.  Same interface, same state records; max_chunk <= 16.
 """
 import ctypes
@@ -34,7 +42,7 @@ import numbers
 import torch
 
 from . import _call, _lib, _policy
-from ._args import _host_lengths, output_format, pcm_input, require_cuda
+from ._args import _host_lengths, clipped_pointer, output_format, pcm_input, require_cuda
 
 PLUS_REASON = ("FullSubNet+ cannot be streamed exactly: its full-band TCN blocks are not causal and normalise with GroupNorm(1, C) over "
                "the whole clip, and TSSE pools over all of time; stream the original FullSubNet (fullsubnet_plus_amd.FullSubNet) with a "
@@ -115,13 +123,15 @@ class _Session:
         self._owner = model._hip.handle.value
         for name in ("destroy", "reset", "get_state", "set_state", "state_bytes"):
             setattr(self, "_" + name, getattr(lib, f"{self._prefix}_{name}"))
-        create = f"{self._prefix}_create_live" if live else f"{self._prefix}_create"
         sp = ctypes.c_void_p()
-        _call.call(getattr(lib, create), device, model._hip.handle, self.slots, int(limit), *self._create_extra(), ctypes.byref(sp), stream=False)
+        _call.call(getattr(lib, self._create_symbol(live)), device, model._hip.handle, self.slots, int(limit), *self._create_extra(), ctypes.byref(sp), stream=False)
         self._st, self._backup = sp, None
         self.state_bytes = int(self._state_bytes(sp))
 
     # ------------------------------------------------------------------ plumbing
+    def _create_symbol(self, live):
+        return f"{self._prefix}_create_live" if live else f"{self._prefix}_create"
+
     def _create_extra(self):
         """what the session's create call takes between its limit and its out pointer"""
         return ()
@@ -395,3 +405,74 @@ class SpecStream(_FrameSession):
         """Push look_ahead all-zero frames (the reference's own pad) into `slots` (None: all): the last look_ahead enhanced frames.
         -> [slots, F, look_ahead] (an empty tensor for look_ahead = 0)."""
         return self._tail(slots, torch.complex64, (self.slots, self.num_freqs), (self.slots, self.num_freqs))
+
+
+class WindowStream(_Session):
+    """`slots` independent live audio streams on either model, enhanced in the overlapping, cross-faded windows of enhance_wave_windowed
+    (include/session/fsnp_window_stream.h; open one through model.open_window_stream): blocks of samples in, the same
+    number of samples out, `delay` = `window` samples late.  A window runs through the model in the push that completes it (window k
+    at k (window - overlap) + window samples), up to `max_batch` windows of all slots per forward; most pushes complete none and
+    only move samples.  All push outputs of a clip followed by its finish() output, without the first `delay` samples, are
+    enhance_wave_windowed(clip, window, overlap) of that clip alone, whatever the block sizes - bit for bit when both run one window
+    per forward (max_batch=1).  Everything runs on the current CUDA stream; a push allocates nothing but its output tensor and never
+    synchronises (under the model's error_check="sync" it then waits and polls, as forward does).  load_state takes what state() of a
+    slot of any window session of the same window and overlap returned; it waits once for the copy, to learn the slot's sample count."""
+    _prefix, _opener = "fsnp_window_stream", "open_window_stream"
+    _copy = False                    # _debug.debug_open_window_stream_copy: the test hook's session, whose forwards copy
+
+    def __init__(self, model, slots, window, overlap, max_samples, max_batch, device):
+        self.window, self.overlap, self.max_samples, self.max_batch = window, overlap, max_samples, max_batch
+        self.hop_length = int(model.hop_length)                  # (kept, as a WaveStream keeps it: later assignments do not touch the session)
+        super().__init__(model, slots, window, device, False)
+        self.delay = int(self._lib.fsnp_window_stream_delay(self._st))
+
+    def _create_symbol(self, live):
+        return "fsnp_debug_window_stream_create_copy" if self._copy else "fsnp_window_stream_create"
+
+    def _create_extra(self):
+        return (self.overlap, self.max_samples, self.max_batch)
+
+    def _guarded(self, fn, out, *args):
+        if self._copy:               # no model runs: nothing of the model's error policy applies
+            _lib.check(_call.enqueue(fn, self.device, *args), fn.__name__)
+            return out
+        return super()._guarded(fn, out, *args)
+
+    def push(self, wav, counts=None, out_format=None, clipped=None):
+        """wav [slots, n] CUDA tensor, fp32 or torch.int16 at any strides (read in place), n <= max_samples; counts: None (n samples
+        for every slot) or samples per slot (a Python sequence or a CPU integer tensor, 0 <= counts[b] <= n; input past counts[b] is
+        never read) -> [slots, n]: column j < counts[b] of slot b is merged sample P + j - delay of its clip (exactly 0 while
+        P + j < delay), columns >= counts[b] are exactly 0.  out_format: None (follow the input: float -> fp32, int16 -> "s16"), "f32"
+        or "s16"; clipped: optional int32 CUDA tensor [slots], overwritten with each row's saturated or NaN samples ("s16" only)."""
+        what = "WindowStream.push"
+        ofmt, out_dtype = output_format(out_format, wav.dtype, what, peak=False)
+        st = self._session()
+        assert wav.dim() == 2, "WindowStream.push takes [slots, n] samples"
+        S, n = wav.shape
+        assert S == self.slots, f"expected {self.slots} slots, got {S}"
+        require_cuda(wav)
+        assert wav.device == self.device
+        x, ifmt, row, step = pcm_input(wav)
+        cnt = None if counts is None else _host_lengths(counts, S, what)
+        clip = clipped_pointer(clipped, S, self.device, what)
+        out = torch.empty((S, n), dtype=out_dtype, device=self.device)
+        return self._guarded(self._lib.fsnp_window_stream_push_pcm, out, st, x.data_ptr(), ifmt, row, step, cnt, out.data_ptr(), ofmt, n, 1, n,
+                             clip)
+
+    def finish(self, slots=None, out_format=None, clipped=None):
+        """End the clips of `slots` (None: all) -> [slots, delay]: each clip's last `delay` merged samples (exactly 0 where the clip is
+        shorter), after running the clip's last window if the pushes have not; rows of slots not listed, and of slots that hold no
+        samples, are exactly 0.  The finished slots are reset.  Refused, with every slot untouched, for a slot whose whole clip the
+        model does not accept (1 .. n_fft / 2 samples; for the TSSE attention fewer than its 8 frames).  out_format: None or "f32",
+        or "s16"; clipped as in push."""
+        what = "WindowStream.finish"
+        ofmt, out_dtype = output_format(out_format, torch.float32, what, peak=False)
+        st = self._session()
+        arr, num = _slot_array(slots)
+        clip = clipped_pointer(clipped, self.slots, self.device, what)
+        out = torch.empty((self.slots, self.delay), dtype=out_dtype, device=self.device)
+        return self._guarded(self._lib.fsnp_window_stream_finish_pcm, out, st, arr, num, out.data_ptr(), ofmt, self.delay, 1, clip)
+
+    def samples(self, slot):
+        """Samples pushed into `slot` since its last reset or finish (host-side count)."""
+        return self._counter("samples", slot)
